@@ -7,15 +7,19 @@ BGV, logN=15, 12 Q-limbs (LogQ=[55,45x11]), 3 P-limbs (LogP=[55x3]), T=65537, ct
 ciphertext pairs already resident in HBM.  Synthetic inputs: coefficients uniform in [0, q_i), PCG64 seed
 0x1A77160 + 2.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 --workload c2: BASELINE configs[1], CKKS logN=14, 8-level chain: Evaluator.Mul (degree 2) + Rescale;
 --workload c4: BASELINE configs[3], CKKS logN=16, 20+4 limbs, Rotate (automorphism + Galois key-switch);
 --workload c5: BASELINE configs[4], the operation trace of one CKKS bootstrap at the N16QP1546H192H32 shape.
 N > 1: launched by torch.distributed.run, one rank per GPU; independent ciphertexts are sharded across ranks (weak
 scaling, no data-path collective -- SURVEY.md section 8e); ranks synchronise only for the barrier around the timed region
-and the MAX over ranks of the elapsed time.  After the timed region the output of the LAST step is checked against the CPU
-oracle on EVERY batch entry of every rank ("verified"; a mismatch makes the run fail).  Prints ONE JSON line on rank 0.
+and the MAX over ranks of the elapsed time.  Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.
+
+A plain run sets up, warms up, times the K steps, writes the last step's results if --dump-outputs is given, and prints the
+line.  --full adds everything else: the output of the LAST step is checked against the CPU oracle on EVERY batch entry of every
+rank ("verified"; a mismatch makes the run fail), then the roofline leg, the B = 1 and concurrent-caller figures, NTT/s, the
+CPU baseline and, for the default workload, the other BASELINE configurations (`other_configs`).
 
 Byte accounting (DESIGN.md sections 4 and 6): per-kernel algorithmic bytes come from the launchers themselves (he_prof_end_bytes:
 every polynomial stream a launch reads or writes, once), per-op algorithmic bytes from the per-primitive formulas of SURVEY.md
@@ -254,6 +258,28 @@ def verify_batch(kind, N, q, p, kq, kp, host_in, outs, out_limbs, t=0, gal=0, ch
     return True, f"{B}/{B} entries x {out_limbs} limbs x {len(outs)} components equal the oracle's {kind}"
 
 
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: the files of one run stay below 64 MB in all
+
+
+def dump_outputs(ctx, outputs, out_dir):
+    """--dump-outputs DIR: what the timed path handed back in its last step, one DIR/<name>.npy per result polynomial (ct0, ct1
+    [, ct2] of the ciphertext), so that two builds can be compared output for output.  A residue is a 64-bit word, which neither
+    float32 nor float64 holds exactly, so every word is written as its eight bytes, least significant first, each a float32 in
+    [0, 255]: array [rows][N][8], exact, and a change of one unit anywhere in a word is a visible relative change.  A row is one
+    (batch entry, limb) of the polynomial; when the result has more rows than the byte budget allows, a fixed sample of them is
+    written (PCG64 seed 0x1A77160 + 99, sorted: the same rows on every run with the same arguments)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ctx.sync()
+    words = DUMP_BYTES // (8 * 4) // len(outputs)  # per polynomial
+    for name, poly, n_limbs in outputs:
+        rows = poly.batch * n_limbs
+        keep = max(1, words // poly.N)
+        sel = np.arange(rows) if rows <= keep else \
+            np.sort(np.random.Generator(np.random.PCG64(0x1A77160 + 99)).choice(rows, keep, replace=False))
+        a = np.stack([poly.download_limb(int(r) // n_limbs, int(r) % n_limbs) for r in sel])
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype("<u8").view(np.uint8).reshape(len(sel), poly.N, 8).astype(np.float32))
+
+
 def setup_c3(la, ctx, rank, B, cp, args):
     N = 1 << LOGN
     q, p = gen_moduli()
@@ -281,6 +307,9 @@ def setup_c3(la, ctx, rank, B, cp, args):
 
     def verify():
         return verify_batch("bgv_mulrelin", N, q, p, kq, kp, host_in, out, L, t=T)
+
+    def outputs():
+        return [("ct0", out[0], L), ("ct1", out[1], L)]
 
     limb = N * 8
     nonown = beta * (L + alpha) - L
@@ -321,7 +350,7 @@ def setup_c3(la, ctx, rank, B, cp, args):
         del kernel_bytes["ntt_rows_fwd_f64"]
     return {
         "metric": "ciphertext-mul+relin ops/s", "unit": "ctxt-mul+relin ops/s", "step": step, "units": B, "verify": verify,
-        "kernel_bytes": kernel_bytes,
+        "outputs": outputs, "kernel_bytes": kernel_bytes,
         # (6L + 2 beta (L+alpha)) limbs = 48 MiB with the key charged to every op; one key read
         # serves the B ciphertexts of a step, so the batch-amortised figure is 6L limbs + key / B
         "alg_bytes_per_op": (6 * L + 2 * beta * (L + alpha)) * limb,
@@ -359,10 +388,13 @@ def setup_c2(la, ctx, rank, B, cp, args):
     def verify():
         return verify_batch("ckks_mul_rescale", N, q, p, None, None, host_in, r3, L - 1, chunk=128)
 
+    def outputs():
+        return [(f"ct{k}", r3[k], L - 1) for k in range(3)]
+
     limb = N * 8
     return {
         "metric": "ciphertext mul+rescale ops/s", "unit": "ctxt-mul+rescale ops/s", "step": step, "units": B, "verify": verify,
-        "kernel_bytes": None,
+        "outputs": outputs, "kernel_bytes": None,
         "alg_bytes_per_op": (7 * L + 3 * (2 * L - 1)) * limb,  # Mul 7 L + Rescale 3 (2L - 1) = 12.625 MiB
         "alg_bytes_per_op_amortised": (7 * L + 3 * (2 * L - 1)) * limb,
         "cpu": lambda: cpu_baseline("ckks_mul_rescale", N, q, p, None, None, "ctxt-mul+rescale ops/s", "CKKS Mul + Rescale (logN=14, 8 limbs)"),
@@ -397,10 +429,13 @@ def setup_c4(la, ctx, rank, B, cp, args):
     def verify():
         return verify_batch("rotate", N, q, p, kq, kp, host_in, out, L, gal=gal, chunk=32)
 
+    def outputs():
+        return [("ct0", out[0], L), ("ct1", out[1], L)]
+
     limb = N * 8
     return {
         "metric": "ciphertext rotate ops/s", "unit": "ctxt-rotate ops/s", "step": step, "units": B, "verify": verify,
-        "kernel_bytes": None,
+        "outputs": outputs, "kernel_bytes": None,
         "alg_bytes_per_op": (4 * L + 2 * beta * (L + alpha)) * limb,  # 160 MiB
         "alg_bytes_per_op_amortised": 4 * L * limb + 2 * beta * (L + alpha) * limb / B,
         "key_digest": lambda: key_digest(gk),
@@ -463,10 +498,15 @@ def setup_c5(la, ctx, rank, B, cp, args):
             return False, f"batch entries {bad[:8]} differ from the oracle-backed trace (tests/golden/c5_trace_digest.json)"
         return True, f"{len(got['entries'])}/{len(got['entries'])} entries: SHA-256 of the refreshed ciphertext equals the oracle-backed trace's"
 
+    def outputs():
+        res = last["res"]
+        return [(f"ct{k}", v, int(res.level) + 1) for k, v in enumerate(res.Value)]
+
     step._shape = run._shape
     return {
         "cpu_c5": lambda trace_bytes: c5_cpu_baseline(la, ctx, run._shape, trace_bytes),
-        "metric": "bootstraps/s", "unit": "ctxt-bootstraps/s", "step": step, "units": B, "verify": verify, "kernel_bytes": None,
+        "metric": "bootstraps/s", "unit": "ctxt-bootstraps/s", "step": step, "units": B, "verify": verify, "outputs": outputs,
+        "kernel_bytes": None,
         # no closed form: summed over the operation trace by the library (he_alg_bytes), see main()
         "alg_bytes_per_op": None, "alg_bytes_per_op_amortised": None, "cpu": None,
         "config": dict({"workload": "CKKS bootstrap operation trace at the N16QP1546H192H32 shape (logN=16, 25+5 limbs; "
@@ -737,8 +777,11 @@ _CLOCK_DIR = {}
 
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves (torch.distributed.run, one
-    rank per GPU, rendezvous on 127.0.0.1) and hand over -- so that --gpus means N however the script is invoked.  A node with
-    fewer than N GPUs is refused (exit 2) unless HERING_FORCE_DEVICE (test hook: ranks share one GPU) is set."""
+    rank per GPU, rendezvous on 127.0.0.1) as a child process and exit with its status -- so that --gpus means N however the
+    script is invoked.  (Not an exec: this process has initialised the GPU to count the devices, and replacing the program of
+    such a process is not safe.)  A node with fewer than N GPUs is refused (exit 2) unless HERING_FORCE_DEVICE (test hook:
+    ranks share one GPU) is set."""
+    import subprocess
     import socket
     import lattigo_amd as la
     have = la.device_count()
@@ -753,7 +796,8 @@ def self_launch(args):
     sys.stderr.write(f"bench.py: --gpus {args.gpus} without a launcher: starting {args.gpus} ranks ({' '.join(cmd[1:8])} ...)\n")
     sys.stderr.flush()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    sys.exit(128 - rc if rc < 0 else rc)  # a launcher killed by a signal exits as a shell would report it
 
 
 # the other BASELINE configurations in the default line (`other_configs`): (workload, steps, warmup); c5's step is a whole
@@ -770,7 +814,7 @@ def other_configs(args):
     out = {}
     for wl, steps, warmup in OTHER_CONFIGS:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", wl, "--steps", str(steps), "--warmup", str(warmup),
-               "--no-b1", "--no-concurrent", "--no-ntt", "--no-cpu-baseline", "--no-other-configs"]
+               "--full", "--no-b1", "--no-concurrent", "--no-ntt", "--no-cpu-baseline", "--no-other-configs"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.other_timeout)
@@ -873,13 +917,21 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="default workload, one GPU: do not measure BASELINE configs 2, 4 and 5 into the line's `other_configs`")
     ap.add_argument("--other-timeout", type=int, default=420, help="seconds a child run of `other_configs` may take")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the oracle check of the last step, the roofline leg, B = 1 and "
+                         "concurrent-caller figures, NTT/s, the CPU baseline and `other_configs` (each subject to the --no-* options "
+                         "above); without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result polynomials of the last timed step to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if args.gpus > 1 and env_world == 0:
-        self_launch(args)  # does not return
+        self_launch(args)  # exits with the ranks' status
     if env_world not in (0, args.gpus):
         # a line whose n_gpus differs from what was asked is never printed
         sys.stderr.write(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={env_world} ranks; no line printed\n")
@@ -955,9 +1007,15 @@ def main():
             multi_gpu_problems.append(f"selftest wants the RCCL leg, the run used {args.replicate_keys!r}")
     n_bad = cp.sum_over_ranks(1.0 if multi_gpu_problems else 0.0)
 
-    # ---- parity of what was timed: the output of the last timed step against the oracle, on every rank ------------
+    # ---- what the last timed step computed (rank 0's share), for comparing builds ---------------------------------
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, W["outputs"](), args.dump_outputs)
+
+    # ---- parity of what was timed: the output of the last timed step against the oracle, on every rank (--full) ----
     verified, vmsg = None, "skipped"
-    if W["verify"] is not None and not args.no_verify:
+    if not args.full:
+        vmsg = "not checked (--full checks the last step against the oracle)"
+    elif W["verify"] is not None and not args.no_verify:
         ok, vmsg = W["verify"]()
         bad = cp.sum_over_ranks(0.0 if ok else 1.0)
         verified = bad == 0.0
@@ -973,6 +1031,27 @@ def main():
 
     ops = world * W["units"] * args.steps
     value = ops / elapsed
+
+    cfg = dict(W["config"])
+    cfg["parallelism"] = f"{world} independent replicas, ciphertext-sharded"
+    line = {
+        "metric": W["metric"], "value": value, "unit": W["unit"], "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": cfg, "verified": verified, "verified_detail": vmsg,
+        "hip_event_ms_per_step": ev_ms / args.steps,
+        "rank_ms_per_step": {"min": elapsed_min / args.steps * 1e3, "max": elapsed / args.steps * 1e3},
+        "gpu_clock": clock,
+        "ranks_seen": ranks_seen, "replicate_keys": args.replicate_keys,
+        "multi_gpu_selftest": (None if world == 1 else ("ok" if not n_bad else f"FAILED on {int(n_bad)} rank(s): {multi_gpu_problems}")),
+    }
+    if not args.full:
+        # the plain run ends here: the headline figure of the timed steps, nothing measured or checked besides
+        print(json.dumps(line), flush=True)
+        cp.close()
+        if n_bad:
+            sys.exit(5)
+        return
 
     if args.no_kernel_timing:
         print(json.dumps({"metric": W["metric"], "value": value, "unit": W["unit"], "n_gpus": world, "steps": args.steps,
@@ -1103,20 +1182,7 @@ def main():
     if W["alg_bytes_per_op"] and abs(per_op_trace - W["alg_bytes_per_op"]) > 0.005 * W["alg_bytes_per_op"]:
         problems.append(f"per-op trace accounting {per_op_trace} != closed form {W['alg_bytes_per_op']}")
 
-    cfg = dict(W["config"])
-    cfg["parallelism"] = f"{world} independent replicas, ciphertext-sharded"
-    line = {
-        "metric": W["metric"], "value": value, "unit": W["unit"], "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "config": cfg, "verified": verified, "verified_detail": vmsg,
-        "hip_event_ms_per_step": ev_ms / args.steps,
-        "rank_ms_per_step": {"min": elapsed_min / args.steps * 1e3, "max": elapsed / args.steps * 1e3},
-        "gpu_clock": clock,
-        "ranks_seen": ranks_seen, "replicate_keys": args.replicate_keys,
-        "multi_gpu_selftest": (None if world == 1 else ("ok" if not n_bad else f"FAILED on {int(n_bad)} rank(s): {multi_gpu_problems}")),
-        "roofline": roofline,
-    }
+    line["roofline"] = roofline
     if not args.no_b1 and world == 1 and args.workload != "c5" and B != 1:
         # single-ciphertext figures ("report best and B=1"): the same operation on ONE ciphertext
         W1 = setup(la, ctx, rank, 1, cp, args)

@@ -30,7 +30,7 @@ def test_bench_two_ranks_every_workload(workload, batch):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HERING_FORCE_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29561", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload",
-           workload, "--batch", str(batch), "--no-cpu-baseline", "--no-ntt"] + (["--replicate-keys", "host"] if workload != "c5" else [])
+           workload, "--batch", str(batch), "--full", "--no-cpu-baseline", "--no-ntt"] + (["--replicate-keys", "host"] if workload != "c5" else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -46,7 +46,7 @@ def test_bench_gpus_n_without_a_launcher_starts_n_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(HERING_FORCE_DEVICE="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--no-cpu-baseline", "--no-ntt", "--replicate-keys", "host"]
+           "--full", "--no-cpu-baseline", "--no-ntt", "--replicate-keys", "host"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

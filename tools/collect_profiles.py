@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Copy the summaries of tools/round_artifacts.sh from gpurun_out/ (scratch) into profiles/ (tracked): python tools/collect_profiles.py r02"""
+"""Copy the summaries of tools/round_artifacts.sh from $OUT (scratch, default prof_out/) into profiles/ (tracked):
+python tools/collect_profiles.py r02"""
 import collections
 import csv
 import json
@@ -11,7 +12,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 tag = sys.argv[1]
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("OUT", os.path.join(ROOT, "prof_out")), os.path.join(ROOT, "profiles")
 shutil.copy(os.path.join(G, "bench_final.json"), os.path.join(P, f"{tag}_bench.json"))
 shutil.copy(os.path.join(G, "bench_configs.jsonl"), os.path.join(P, f"{tag}_bench_other_configs.jsonl"))
 stats = [f for f in os.listdir(os.path.join(G, "prof_final")) if f.endswith("kernel_stats.csv")]
