@@ -627,7 +627,8 @@ func (e *Evaluator) AutomorphismHoistedLazy(levelQ int, ctIn *rlwe.Ciphertext, c
 //		err = dev.LinTransGiantStep(levelQ, tmp1QP.Q, galEl, tmp0QP, c0OutQP, c1OutQP, cnt0 != 0)
 //	} else { ... the reference's own calls ... }
 //
-// Staleness: as AutomorphismHoistedLazy (inputs from their device twins, outputs on the device only).
+// Staleness: as AutomorphismHoistedLazy (inputs from their device twins, outputs on the device only).  out0 / out1 must alias
+// neither cx nor add nor each other (Q or P part): the call returns an error before anything runs (hering.h, Conventions).
 func (e *Evaluator) LinTransGiantStep(levelQ int, cx ring.Poly, galEl uint64, add, out0, out1 ringqp.Poly, accumulate bool) (err error) {
 	gk, err := e.CheckAndGetGaloisKey(galEl)
 	if err != nil {

@@ -25,6 +25,34 @@
  *  - outputs are caller-allocated and come last; in-place aliasing is allowed
  *    exactly where the reference allows it (coefficient-wise ops, NTT), not for
  *    automorphisms (ring/automorphism.go:37).
+ *  - operand identity (aliasing), checked on the host before anything is filed --
+ *    also in deferred mode, so a rejection is the call's own HE_EINVAL; a rejected
+ *    call changes no operand and leaves the context and its queue usable:
+ *      input / input: always allowed (squaring, Add(x, x, y));
+ *      output / input: allowed where the reference computes in place, with the
+ *        words of the out-of-place call on the pre-call contents (an output that
+ *        is also an addend or accumulator -- ...ThenAdd[Lazy], accumulate -- starts
+ *        from its own pre-call words): coefficient-wise ops (scalar, big-int and
+ *        double-RNS scalar forms included; MulByVectorMontgomery with p2 == p1, not
+ *        p2 == vector), NTT / INTT, Shift, MultByMonomial, the eight rescale
+ *        variants, ModDownQPtoQ[NTT] with p2Q == p1Q, ModDownQPtoP with p2P == p1P,
+ *        ModDown with out_k == c_kQ, GadgetProduct with an output == cx,
+ *        Relinearize, Automorphism[Hoisted] on ciphertexts and MulRelin with any
+ *        output == any input, AutomorphismHoistedLazy with c0Q / c1Q == in0,
+ *        he_centered_lift with dstQ == src; every other pair is HE_EINVAL (ring
+ *        automorphisms, the giant step and the lintrans inner sum among them);
+ *      output / output: HE_EINVAL (the Q and P parts of one output included);
+ *      a Q-side and a P-side operand that are one handle, either of them written:
+ *        HE_EINVAL;
+ *      he_rescale_polys: each pair may be in place; an output that is an operand
+ *        of another pair is HE_EINVAL;
+ *      he_poly_copy_batch: overlapping entry ranges of one handle are HE_EINVAL;
+ *        he_poly_copy(x, x) is a no-op.
+ *    tests/aliasing_table.py lists every entry point's allowed pairs.
+ *  - Galois elements (ring automorphisms, index tables, ciphertext automorphisms,
+ *    the giant step, lintrans indices): any odd g acts as g mod NthRoot (2N; 4N on
+ *    conjugate-invariant rings) -- g + k NthRoot gives the same words up to 2^64 - 1
+ *    (conjugation), and the reduced element keys batches and index caches.
  */
 #ifndef HERING_H
 #define HERING_H
@@ -111,7 +139,8 @@ int he_poly_upload_limb(he_handle poly, int b, int limb, const uint64_t *src);
 int he_poly_download_limb(he_handle poly, int b, int limb, uint64_t *dst);
 int he_poly_copy(he_handle dst, he_handle src, int level);      /* Poly.CopyLvl */
 /* limbs 0..level of the batch entries [src_b0, src_b0 + nb) of src -> entries [dst_b0, dst_b0 + nb) of dst (regrouping of
- * independent ciphertexts into one batch, e.g. the real and imaginary halves before EvalMod) */
+ * independent ciphertexts into one batch, e.g. the real and imaginary halves before EvalMod).  dst may be src with disjoint
+ * entry ranges; overlapping ranges of one handle are HE_EINVAL. */
 int he_poly_copy_batch(he_handle dst, int dst_b0, he_handle src, int src_b0, int nb, int level);
 int he_poly_zero(he_handle poly);
 /* the polynomial's device storage ([batch][n_limbs][N] words) for transports that move device memory themselves (an RCCL
@@ -190,7 +219,7 @@ int he_shift(he_handle ring, int level, he_handle p1, int k, he_handle p2);
 /* Ring.MultByMonomial (operations.go:307): p2 = p1 * X^k, coefficient domain; p2 may be p1 */
 int he_mult_by_monomial(he_handle ring, int level, he_handle p1, int k, he_handle p2);
 /* Ring.MulByVectorMontgomery / MulByVectorMontgomeryThenAddLazy (operations.go:363,370): every limb of p1 times the
- * same N-word vector (limb 0 of the batch-1 polynomial `vector`) */
+ * same N-word vector (limb 0 of the batch-1 polynomial `vector`); p2 may be p1, not `vector` */
 int he_mul_by_vector_montgomery(he_handle ring, int level, he_handle p1, he_handle vector, int then_add_lazy, he_handle p2);
 
 /* named wrappers, one per reference method that the key-switch path calls */
@@ -218,7 +247,8 @@ int he_div_floor_by_last_modulus_many(he_handle ring, int level, int nb, he_hand
 /* Evaluator.Rescale's loop over the polynomials of ONE ciphertext (schemes/ckks/evaluator.go:503-507, schemes/bgv/evaluator.go:
  * 1385-1389: DivRoundByLastModulusManyNTT(level, nb, ctIn.Value[i], opOut.Value[i]) for every component) as one call: p0[i] ->
  * p1[i], i < n <= 16.  The same words as n calls of he_div_round_by_last_modulus_many_ntt; on a context whose submission queue is on
- * the n polynomials are filed together and ride in one batch with the other callers' (one round of the queue per Rescale). */
+ * the n polynomials are filed together and ride in one batch with the other callers' (one round of the queue per Rescale).
+ * p1[i] may be p0[i]; p1[i] equal to p0[j] or p1[j], j != i, is HE_EINVAL. */
 int he_rescale_polys(he_handle ring, int level, int nb, int n, const he_handle *p0, const he_handle *p1);
 
 /* ---- automorphism: ring/automorphism.go ------------------------------------------ */
@@ -233,6 +263,7 @@ int he_automorphism(he_handle ring, int level, he_handle pin, uint64_t gal_el, h
 /* ---- basis extension: ring.BasisExtender (ring/basis_extension.go:14) -------------- */
 int he_basis_extender_create(he_handle ringQ, he_handle ringP, he_handle *be);
 int he_basis_extender_destroy(he_handle be);
+/* Q-side and P-side operands are distinct handles (HE_EINVAL otherwise); p2Q may be p1Q, p2P may be p1P */
 int he_modup_q_to_p(he_handle be, int levelQ, int levelP, he_handle polQ, he_handle polP);                          /* :177 */
 int he_modup_p_to_q(he_handle be, int levelP, int levelQ, he_handle polP, he_handle polQ);                          /* :195 */
 int he_moddown_qp_to_q(he_handle be, int levelQ, int levelP, he_handle p1Q, he_handle p1P, he_handle p2Q);          /* :215 */
@@ -362,7 +393,8 @@ int he_gadget_product_hoisted_lazy(he_handle eval, int levelQ, he_handle decomp,
  * the outputs.  Same restrictions as he_gadget_product_hoisted_lazy (:379-456). */
 int he_gadget_product_hoisted_lazy_digits(he_handle eval, int levelQ, he_handle decomp, he_handle evk, int digit_begin, int digit_end,
                                           he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P);
-/* Evaluator.ModDown (:39), NTT in / NTT out; levelP = -1 (no special primes, c0P = c1P = 0): the copy of :76-81 */
+/* Evaluator.ModDown (:39), NTT in / NTT out; levelP = -1 (no special primes, c0P = c1P = 0): the copy of :76-81.  out_k may be
+ * c_kQ (the reference runs the components one after the other); no other aliasing */
 int he_moddown(he_handle eval, int levelQ, int levelP, he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P,
                he_handle out0, he_handle out1);
 /* BasisExtender.ModDownQPtoQNTT (ring/basis_extension.go:235-256) through the evaluator's fused pipeline (three launches
@@ -370,13 +402,13 @@ int he_moddown(he_handle eval, int levelQ, int levelP, he_handle c0Q, he_handle 
  * the forward row pass); p1Q in [0, 2q) as the reference's callers provide it, p2Q may alias p1Q; same canonical result
  * as he_moddown_qp_to_q_ntt. */
 int he_eval_moddown_qp_to_q_ntt(he_handle eval, int levelQ, int levelP, he_handle p1Q, he_handle p1P, he_handle p2Q);
-/* GadgetProduct (:16) and GadgetProductHoisted (:348) */
+/* GadgetProduct (:16) and GadgetProductHoisted (:348); out0 / out1 may be cx, never each other */
 int he_gadget_product(he_handle eval, int levelQ, he_handle cx, he_handle evk, he_handle out0, he_handle out1);
 int he_gadget_product_hoisted(he_handle eval, int levelQ, he_handle decomp, he_handle evk, he_handle out0, he_handle out1);
-/* Evaluator.Relinearize (core/rlwe/evaluator_evaluationkey.go:117) */
+/* Evaluator.Relinearize (core/rlwe/evaluator_evaluationkey.go:117); any output may be any input (out0 != out1) */
 int he_relinearize(he_handle eval, int level, he_handle in0, he_handle in1, he_handle in2, he_handle rlk,
                    he_handle out0, he_handle out1);
-/* Evaluator.Automorphism (core/rlwe/evaluator_automorphism.go:13), NTT domain */
+/* Evaluator.Automorphism (core/rlwe/evaluator_automorphism.go:13), NTT domain; Rotate(ct, k, ct): any output may be any input */
 int he_automorphism_ct(he_handle eval, int level, he_handle in0, he_handle in1, uint64_t gal_el, he_handle gk,
                        he_handle out0, he_handle out1);
 /* Evaluator.AutomorphismHoisted (:60): decomp = DecomposeNTT(in1) */
@@ -384,13 +416,14 @@ int he_automorphism_hoisted(he_handle eval, int level, he_handle in0, he_handle 
                             he_handle out0, he_handle out1);
 
 /* EvaluatorProvider.AutomorphismHoistedLazy (core/rlwe/evaluator_automorphism.go:104): in0 = ctIn.Value[0],
- * decomp = DecomposeNTT(ctIn.Value[1]); output in QP, NTT domain, not divided by P */
+ * decomp = DecomposeNTT(ctIn.Value[1]); output in QP, NTT domain, not divided by P; c0Q / c1Q may be in0 */
 int he_automorphism_hoisted_lazy(he_handle eval, int levelQ, he_handle in0, he_handle decomp, uint64_t gal_el, he_handle gk,
                                  he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P);
 
 /* ---- scheme call sites ------------------------------------------------------------ */
 /* CKKS Evaluator.mulRelin (schemes/ckks/evaluator.go:764), degree 1 x degree 1.
- * rlk = 0 -> no relinearisation: (out0,out1,out2); else (out0,out1), out2 ignored.  */
+ * rlk = 0 -> no relinearisation: (out0,out1,out2); else (out0,out1), out2 ignored.
+ * Any output may be any input (MulRelin(res, res, res)); the outputs are distinct. */
 int he_ckks_mul_relin(he_handle eval, int level, he_handle a0, he_handle a1, he_handle b0, he_handle b1,
                       he_handle rlk, he_handle out0, he_handle out1, he_handle out2);
 /* BGV Evaluator.tensorStandard (schemes/bgv/evaluator.go:592), plaintext modulus t */
@@ -403,7 +436,7 @@ int he_bgv_mul_relin(he_handle eval, int level, uint64_t t, he_handle a0, he_han
 /* The centred lifts of bootstrapping.Evaluator.ModUp (circuits/ckks/bootstrapping/evaluator.go:654-667, 677-696,
  * 742-755): c = src[limb 0][j] (coefficient domain, modulus q = Q[0]); neg = strict ? c > q/2 : c >= q/2; c = neg ?
  * q - c : c; every destination limb i gets t = BRedAdd(c, m_i), neg ? m_i - t : t -- Q limbs first_q..levelQ of dstQ
- * and, when levelP >= 0, P limbs 0..levelP of dstP.  dstQ may be src itself (limbs >= 1 are written).
+ * and, when levelP >= 0, P limbs 0..levelP of dstP.  dstQ may be src itself (limbs >= 1 are written); dstP may be neither.
  * strict = 3: the small-norm form of ringqp.Ring.ExtendBasisSmallNormAndCenter (ring/ringqp/operations.go:325): sign test
  * c > q/2 and |c| written without reduction (first_q > levelQ writes no Q limb). */
 int he_centered_lift(he_handle eval, int strict, he_handle src, int first_q, int levelQ, he_handle dstQ, int levelP,
@@ -420,7 +453,8 @@ int he_decomp_fill(he_handle decomp, int levelQ, int levelP, he_handle srcQ, he_
  * chain (resp. MulCoeffsMontgomery[ThenAdd]).  Arrays have n entries (n <= 64).  ptQ/ptP: encoded diagonals (batch 1
  * broadcasts).  ctkP[i] == 0: term i has no P part (the P*ct term of the zero rotation, :349-352).  index[i] != 0: the
  * ciphertext of term i is read through that automorphism index (fuses AutomorphismNTTWithIndex, :224-225);
- * index == NULL: no automorphisms.  accumulate != 0 adds to the current (canonical) content of out. */
+ * index == NULL: no automorphisms.  accumulate != 0 adds to the current (canonical) content of out.  The four outputs are distinct
+ * and alias no input. */
 int he_lintrans_mul_sum(he_handle eval, int levelQ, int levelP, int n, const he_handle *ptQ, const he_handle *ptP,
                         const he_handle *ct0Q, const he_handle *ct0P, const he_handle *ct1Q, const he_handle *ct1P,
                         const he_handle *index, int accumulate, he_handle out0Q, he_handle out0P, he_handle out1Q,
@@ -434,7 +468,7 @@ int he_lintrans_mul_sum(he_handle eval, int levelQ, int levelP, int n, const he_
  * with cx = the (ModDown'ed) inner sum of component 1, (addQ, addP) the inner sum of component 0 on Q and P, gal the Galois element
  * of the giant step's rotation, key its Galois key, out_k = (ckQ, ckP) the outer accumulators.  Word for word what the separate
  * calls produce; the intermediate ciphertext cQP is never materialised where the key inner products can store through the
- * automorphism themselves (standard rings, RNS gadgets).  The outputs must not alias the inputs. */
+ * automorphism themselves (standard rings, RNS gadgets).  The outputs must not alias the inputs or each other (HE_EINVAL). */
 int he_lintrans_giant_step(he_handle eval, int levelQ, he_handle cx, he_handle key, uint64_t gal, he_handle addQ, he_handle addP,
                            he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, int accumulate);
 

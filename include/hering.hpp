@@ -290,7 +290,8 @@ public:
         check(he_div_floor_by_last_modulus_many(h(), level_, nbRescales, p0.h(), p1.h()));
     }
 
-    // ring/automorphism.go: AutomorphismNTT (:36, not in place), Automorphism (:113, coefficient domain)
+    // ring/automorphism.go: AutomorphismNTT (:36, not in place), Automorphism (:113, coefficient domain); galEl acts mod NthRoot.
+    // Aliasing follows hering.h (Conventions): a pattern the C ABI rejects throws here before anything is launched.
     void AutomorphismNTT(const Poly &pIn, uint64_t galEl, Poly &pOut) const {
         he_handle ix = 0;
         check(he_automorphism_index_create(h(), galEl, &ix));

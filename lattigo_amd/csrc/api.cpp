@@ -126,7 +126,9 @@ struct CoReq {
                blob == o.blob;
     }
     // par[7]: which operands are the same polynomial (bit i * n + j for i < j): the launches decide in-place forms on entry 0's
-    // pointers, so every entry of a batch must alias the same way
+    // pointers, so every entry of a batch must alias the same way.  The first 11 operands give 55 bits; a request with more
+    // (CO_LINTRANS: 4 + 6 n) adds the rest of its pattern to the blob -- per operand, the first operand with the same storage --
+    // so that requests of different patterns never share a batch, whatever the operation does with them.
     void set_alias_pattern() {
         uint64_t m = 0;
         int bit = 0;
@@ -135,6 +137,11 @@ struct CoReq {
             for (size_t j = i + 1; j < n; j++, bit++)
                 if (ops[i].p && ops[i].p == ops[j].p) m |= 1ull << bit;
         par[7] = (int64_t)m;
+        if (ops.size() > 11) {
+            std::unordered_map<const uint64_t *, uint64_t> first;
+            for (size_t i = 0; i < ops.size(); i++)
+                blob.push_back(ops[i].p ? first.emplace(ops[i].p, (uint64_t)i).first->second : UINT64_MAX);
+        }
     }
 };
 struct Coalescer {
@@ -1376,6 +1383,37 @@ int check_poly(const Poly &p, const Ring &r, int level, const char *who) {
     return HE_OK;
 }
 
+// Operand identity (hering.h, Conventions, "aliasing"): one operand of a call, its role and its side.  `p` may be null (an absent
+// operand).  P-side operands are the special-prime parts (limbs of ringP); everything else is Q-side.
+struct AliasOp {
+    const Poly *p;
+    bool out;  // written by the call (outputs and accumulating outputs)
+    bool P;    // a P-side operand
+};
+// Checked on the host before anything is filed (also in deferred mode, so the call itself returns the rejection): two operands
+// that are the same polynomial are allowed when both are only read, or when they are an (output, input) pair listed in `allowed`
+// (indices into `ops`: the in-place forms the reference computes).  Two outputs, a Q-side and a P-side operand of which one is
+// written, and every other (output, input) pair fail with HE_EINVAL.
+int reject_aliasing(const char *who, const std::vector<AliasOp> &ops, const std::vector<std::pair<int, int>> &allowed = {}) {
+    for (size_t i = 0; i < ops.size(); i++) {
+        if (!ops[i].p) continue;
+        for (size_t j = i + 1; j < ops.size(); j++) {
+            if (!ops[j].p || ops[i].p->d != ops[j].p->d) continue;
+            const AliasOp &a = ops[i], &b = ops[j];
+            if (!a.out && !b.out) continue;
+            if (a.P != b.P) return fail(HE_EINVAL, "%s: operands %zu and %zu are the same polynomial on the Q and the P side", who, i, j);
+            if (a.out && b.out) return fail(HE_EINVAL, "%s: outputs %zu and %zu are the same polynomial", who, i, j);
+            bool ok = false;
+            for (const auto &pr : allowed) ok = ok || (pr.first == (int)i && pr.second == (int)j) || (pr.first == (int)j && pr.second == (int)i);
+            if (!ok) return fail(HE_EINVAL, "%s: output %zu aliases input %zu (not an in-place form of this operation)", who, a.out ? i : j, a.out ? j : i);
+        }
+    }
+    return HE_OK;
+}
+// Galois elements act through g mod NthRoot (2N, 4N on conjugate-invariant rings): the reduced element is what keys batches and
+// index caches, so that g and g + k NthRoot share them
+inline uint64_t reduce_gal(uint64_t gal, int logN, int type) { return gal & ((2ull << (logN + type)) - 1); }
+
 uint8_t modulus_class(uint64_t q) { return (q >> 47) == 0 ? 2 : ((q >> 58) == 0 ? 1 : 0); }
 // plain (non-Montgomery) twiddles as doubles for the moduli the double-precision row kernel handles
 int upload_f64_tables(const std::vector<const SubRingHost *> &subs, int N, double **d_f, double **d_i) {
@@ -1729,6 +1767,7 @@ int he_poly_copy(he_handle hdst, he_handle hsrc, int level) {
     GET(s, Poly, hsrc, T_POLY);
     if (d->N != s->N || d->batch != s->batch || level < 0 || d->nlimbs < level + 1 || s->nlimbs < level + 1 || d->ctx != s->ctx)
         return fail(HE_EINVAL, "he_poly_copy: shape or context mismatch");
+    if (d->d == s->d) return HE_OK;  // Poly.CopyLvl onto itself: nothing to copy (and no overlapping memcpy to file)
     // (the copies of concurrent single-ciphertext callers ride in the queue like every other operation: one EW_COPY launch over an
     // entry table; a lone copy is a device-to-device memcpy as before)
     const std::shared_ptr<Ctx> ctx = d->ctx;
@@ -1757,6 +1796,10 @@ int he_poly_copy_batch(he_handle hdst, int dst_b0, he_handle hsrc, int src_b0, i
     if (d->N != s->N || level < 0 || d->nlimbs < level + 1 || s->nlimbs < level + 1 || nb <= 0 || dst_b0 < 0 || src_b0 < 0 ||
         dst_b0 + nb > d->batch || src_b0 + nb > s->batch || d->ctx != s->ctx)
         return fail(HE_EINVAL, "he_poly_copy_batch: shape mismatch");
+    // overlapping entry ranges of one handle are rejected (hering.h): the copy launches give no order between entries
+    if (d->d == s->d && dst_b0 < src_b0 + nb && src_b0 < dst_b0 + nb)
+        return fail(HE_EINVAL, "he_poly_copy_batch: the entry ranges [%d,%d) and [%d,%d) of one polynomial overlap", src_b0, src_b0 + nb, dst_b0,
+                    dst_b0 + nb);
     // (a copy between entry ranges of two handles: the request of he_poly_copy over shifted views)
     const std::shared_ptr<Ctx> ctx = d->ctx;
     const int N = d->N;
@@ -2055,6 +2098,8 @@ int he_mul_by_vector_montgomery(he_handle hring, int level, he_handle h1, he_han
     TRY(check_poly(*p1, *r, level, who));
     TRY(check_poly(*p2, *r, level, who));
     if (v->N != r->N || v->batch != 1 || p1->batch != p2->batch) return fail(HE_EINVAL, "%s: the vector is one batch-1 limb of degree N", who);
+    // p2 may be p1; p2 == vector is not in place: limb 0 of the output is the vector every other limb still reads
+    TRY(reject_aliasing(who, {{p1.get(), false, false}, {v.get(), false, false}, {p2.get(), true, false}}, {{0, 2}}));
     View vv = v->view();
     vv.bstride = 0;  // the same vector for every batch entry and (through the limb override) every limb
     CoReq q;
@@ -2273,6 +2318,14 @@ int he_rescale_polys(he_handle hring, int level, int nb, int n, const he_handle 
         qs[i].nb = B;
         ptrs.push_back(&qs[i]);
     }
+    // each pair may be in place; an output that is an operand of ANOTHER pair is not (the queue files the n pairs as one batch, the
+    // direct path runs them one after the other: the two would differ).  Same polynomial = same device storage, as reject_aliasing.
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            const uint64_t *o = qs[i].ops[1].p;
+            if (i != j && (o == qs[j].ops[0].p || (i < j && o == qs[j].ops[1].p)))
+                return fail(HE_EINVAL, "he_rescale_polys: output %d is also %s %d", i, o == qs[j].ops[0].p ? "input" : "output", j);
+        }
     if (n == 0) return HE_OK;
     if (queue) {
         for (CoReq &q : qs) q.set_alias_pattern();
@@ -2294,6 +2347,7 @@ int he_rescale_polys(he_handle hring, int level, int nb, int n, const he_handle 
 int he_automorphism_index_create(he_handle hring, uint64_t gal, he_handle *out) {
     GET(r, Ring, hring, T_RING);
     if (!out || !(gal & 1)) return fail(HE_EINVAL, "he_automorphism_index_create: Galois element must be odd");
+    gal = reduce_gal(gal, r->logN, r->type);
     auto ix = std::make_shared<AutoIndex>();
     ix->ctx = r->ctx;
     ix->N = r->N;
@@ -2366,6 +2420,7 @@ int he_automorphism(he_handle hring, int level, he_handle hin, uint64_t gal, he_
     TRY(check_poly(*pout, *r, level, "he_automorphism"));
     if (pin->batch != pout->batch) return fail(HE_EINVAL, "he_automorphism: batch mismatch");
     if (pin->d == pout->d) return fail(HE_EINVAL, "he_automorphism: the automorphism cannot be evaluated in place");
+    gal = reduce_gal(gal, r->logN, r->type);
     CoReq q;
     q.op = CO_AUTO_COEFF; q.obj = r.get(); q.par[0] = level; q.par[1] = (int64_t)gal;
     q.ops = {pin->view(), pout->view()};
@@ -2508,6 +2563,7 @@ int he_modup_q_to_p(he_handle hbe, int levelQ, int levelP, he_handle hq, he_hand
     TRY(check_be_poly(*pq, *be, levelQ + 1, "he_modup_q_to_p"));
     TRY(check_be_poly(*pp, *be, levelP + 1, "he_modup_q_to_p"));
     if (pq->batch != pp->batch) return fail(HE_EINVAL, "he_modup_q_to_p: batch mismatch");
+    TRY(reject_aliasing("he_modup_q_to_p", {{pq.get(), false, false}, {pp.get(), true, true}}));
     CoReq q;
     q.op = CO_MODUP; q.obj = be.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = 1;
     q.ops = {pq->view(), pp->view()};
@@ -2527,6 +2583,7 @@ int he_modup_p_to_q(he_handle hbe, int levelP, int levelQ, he_handle hp, he_hand
     TRY(check_be_poly(*pq, *be, levelQ + 1, "he_modup_p_to_q"));
     TRY(check_be_poly(*pp, *be, levelP + 1, "he_modup_p_to_q"));
     if (pq->batch != pp->batch) return fail(HE_EINVAL, "he_modup_p_to_q: batch mismatch");
+    TRY(reject_aliasing("he_modup_p_to_q", {{pp.get(), false, true}, {pq.get(), true, false}}));
     CoReq q;
     q.op = CO_MODUP; q.obj = be.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = 0;
     q.ops = {pp->view(), pq->view()};
@@ -2548,6 +2605,8 @@ static int moddown_api(he_handle hbe, int levelQ, int levelP, he_handle h1q, he_
     TRY(check_be_poly(*p1p, *be, levelP + 1, who));
     TRY(check_be_poly(*p2, *be, (kind == 2 ? levelP : levelQ) + 1, who));
     if (p1q->batch != p1p->batch || p1q->batch != p2->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
+    // in place: p2Q == p1Q (ModDownQPtoQ[NTT]) or p2P == p1P (ModDownQPtoP), element-wise in the last launch
+    TRY(reject_aliasing(who, {{p1q.get(), false, false}, {p1p.get(), false, true}, {p2.get(), true, kind == 2}}, {{kind == 2 ? 1 : 0, 2}}));
     CoReq q;
     q.op = CO_MODDOWN_BE; q.obj = be.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = kind;
     q.ops = {p1q->view(), p1p->view(), p2->view()};
@@ -3143,6 +3202,7 @@ int he_decompose_and_split(he_handle hev, int levelQ, int levelP, int nbPi, int 
     TRY(check_be_poly(*p1q, be, levelQ + 1, "he_decompose_and_split"));
     TRY(check_be_poly(*p1p, be, levelP + 1, "he_decompose_and_split"));
     if (p0->batch != p1q->batch || p0->batch != p1p->batch) return fail(HE_EINVAL, "he_decompose_and_split: batch mismatch");
+    TRY(reject_aliasing("he_decompose_and_split", {{p0.get(), false, false}, {p1q.get(), true, false}, {p1p.get(), true, true}}));
     CoReq q;
     q.op = CO_DECOMPOSE_SPLIT; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = nbPi; q.par[3] = digit;
     q.ops = {p0->view(), p1q->view(), p1p->view()};
@@ -3256,6 +3316,7 @@ struct QPOut {
     std::shared_ptr<Poly> q0, p0, q1, p1;
     View vp0() const { return p0 ? p0->view() : View{nullptr, 0}; }
     View vp1() const { return p1 ? p1->view() : View{nullptr, 0}; }
+    std::vector<AliasOp> outs() const { return {{q0.get(), true, false}, {p0.get(), true, true}, {q1.get(), true, false}, {p1.get(), true, true}}; }
 };
 int get_qp_out(he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, const BasisExtender &be, int levelQ, int levelP, int batch,
                QPOut &o, const char *who) {
@@ -3683,6 +3744,8 @@ int he_gadget_product_lazy(he_handle hev, int levelQ, he_handle hcx, he_handle h
     TRY(check_be_poly(*cx, be, levelQ + 1, "he_gadget_product_lazy"));
     QPOut o;
     TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, k->nPk - 1, cx->batch, o, "he_gadget_product_lazy"));
+    TRY(reject_aliasing("he_gadget_product_lazy", {{cx.get(), false, false}, {o.q0.get(), true, false}, {o.p0.get(), true, true},
+                                                   {o.q1.get(), true, false}, {o.p1.get(), true, true}}));
     CoReq q;
     q.op = CO_GP_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
     q.ops = {cx->view(), o.q0->view(), o.vp0(), o.q1->view(), o.vp1()};
@@ -3715,6 +3778,7 @@ int he_gadget_product_hoisted_lazy(he_handle hev, int levelQ, he_handle hdec, he
     TRY(check_decomp(*ev, *dec, levelQ, k->nPk - 1, "he_gadget_product_hoisted_lazy"));
     QPOut o;
     TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, k->nPk - 1, dec->batch, o, "he_gadget_product_hoisted_lazy"));
+    TRY(reject_aliasing("he_gadget_product_hoisted_lazy", o.outs()));
     const size_t dec_ds = dec->dstride();
     CoReq q;
     q.op = CO_GP_HOISTED_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
@@ -3742,6 +3806,7 @@ int he_gadget_product_hoisted_lazy_digits(he_handle hev, int levelQ, he_handle h
     if (digit_begin < 0 || digit_end > beta || digit_begin > digit_end) return fail(HE_EINVAL, "%s: digits [%d,%d) outside [0,%d)", who, digit_begin, digit_end, beta);
     QPOut o;
     TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, k->nPk - 1, dec->batch, o, who));
+    TRY(reject_aliasing(who, o.outs()));
     Scope sc(be.ctx.get());
     be.ctx->acct((double)(digit_end - digit_begin) * (levelQ + k->nPk + 1) + 2.0 * (levelQ + k->nPk + 1),
                  2.0 * (digit_end - digit_begin) * (levelQ + k->nPk + 1), dec->batch, be.Q->N);
@@ -3770,6 +3835,9 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
             TRY(check_be_poly(*pp, be, levelQ + 1, "he_moddown"));
             if (pp->batch != out0->batch) return fail(HE_EINVAL, "he_moddown: batch mismatch");
         }
+        // out_k may be c_kQ (the reference's ModDown runs component by component); out_k == c_{1-k}Q is not in place
+        TRY(reject_aliasing("he_moddown", {{q0.get(), false, false}, {q1.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}},
+                            {{2, 0}, {3, 1}}));
         CoReq q;
         q.op = CO_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = -1;
         q.ops = {q0->view(), q1->view(), out0->view(), out1->view()};
@@ -3789,6 +3857,8 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
     TRY(check_be_poly(*out0, be, levelQ + 1, "he_moddown"));
     TRY(check_be_poly(*out1, be, levelQ + 1, "he_moddown"));
     if (out1->batch != out0->batch) return fail(HE_EINVAL, "he_moddown: batch mismatch");
+    TRY(reject_aliasing("he_moddown", {{o.q0.get(), false, false}, {o.p0.get(), false, true}, {o.q1.get(), false, false}, {o.p1.get(), false, true},
+                                       {out0.get(), true, false}, {out1.get(), true, false}}, {{4, 0}, {5, 2}}));
     CoReq q;
     q.op = CO_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP;
     q.ops = {o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view(), out0->view(), out1->view()};
@@ -3815,6 +3885,7 @@ int he_eval_moddown_qp_to_q_ntt(he_handle hev, int levelQ, int levelP, he_handle
     TRY(check_be_poly(*p1p, be, levelP + 1, who));
     TRY(check_be_poly(*p2, be, levelQ + 1, who));
     if (p1q->batch != p1p->batch || p1q->batch != p2->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
+    TRY(reject_aliasing(who, {{p1q.get(), false, false}, {p1p.get(), false, true}, {p2.get(), true, false}}, {{0, 2}}));
     CoReq q;
     q.op = CO_EVAL_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP;
     q.ops = {p1q->view(), p1p->view(), p2->view()};
@@ -3863,6 +3934,7 @@ int he_gadget_product(he_handle hev, int levelQ, he_handle hcx, he_handle hk, he
     TRY(check_be_poly(*out0, be, levelQ + 1, "he_gadget_product"));
     TRY(check_be_poly(*out1, be, levelQ + 1, "he_gadget_product"));
     if (out0->batch != cx->batch || out1->batch != cx->batch) return fail(HE_EINVAL, "he_gadget_product: batch mismatch");
+    TRY(reject_aliasing("he_gadget_product", {{cx.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}}, {{1, 0}, {2, 0}}));
     // an output that is the key switch's NTT-domain operand: its own-digit limbs are still being read while the fused epilogue
     // writes the outputs of OTHER entries' workgroups -- such requests (their own key: the aliasing pattern) are served one by one
     const bool alias = cx->d == out0->d || cx->d == out1->d;
@@ -3896,6 +3968,7 @@ int he_gadget_product_hoisted(he_handle hev, int levelQ, he_handle hdec, he_hand
     TRY(check_be_poly(*out0, be, levelQ + 1, "he_gadget_product_hoisted"));
     TRY(check_be_poly(*out1, be, levelQ + 1, "he_gadget_product_hoisted"));
     if (out0->batch != dec->batch || out1->batch != dec->batch) return fail(HE_EINVAL, "he_gadget_product_hoisted: batch mismatch");
+    TRY(reject_aliasing("he_gadget_product_hoisted", {{out0.get(), true, false}, {out1.get(), true, false}}));
     CoReq q;
     q.op = CO_GP_HOISTED; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
     q.ops = {dec->view(), out0->view(), out1->view()};
@@ -3926,19 +3999,31 @@ int he_relinearize(he_handle hev, int level, he_handle hin0, he_handle hin1, he_
         TRY(check_be_poly(*p, be, level + 1, "he_relinearize"));
         if (p->batch != in0->batch) return fail(HE_EINVAL, "he_relinearize: batch mismatch");
     }
+    TRY(reject_aliasing("he_relinearize", {{in0.get(), false, false}, {in1.get(), false, false}, {in2.get(), false, false}, {out0.get(), true, false},
+                                           {out1.get(), true, false}}, {{3, 0}, {3, 1}, {3, 2}, {4, 0}, {4, 1}, {4, 2}}));
     // Aliasing that the batched pipeline cannot take for a whole batch: an output that is the key switch's NTT-domain operand
     // (in2) or the OTHER component's addend.  An output equal to its own component's addend -- Relinearize in place -- is read and
     // written by the same thread and batches normally.
     const bool alias = in2->d == out0->d || in2->d == out1->d || in0->d == out1->d || in1->d == out0->d;
+    // crossed: an output is the OTHER component's addend -- the separate launches would write it before that component reads it,
+    // so the addends are staged first
+    const bool cross = in0->d == out1->d || in1->d == out0->d;
     CoReq q;
     q.op = CO_RELINEARIZE; q.obj = ev.get(); q.key = k.get(); q.par[0] = level;
     q.ops = {in0->view(), in1->view(), in2->view(), out0->view(), out1->view()};
     q.keep = {ev, k, in0, in1, in2, out0, out1};
-    q.run = [ev, k, level](const View *v, int B) -> int {
+    q.run = [ev, k, level, cross](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(5.0 * (std::min(level, k->nQk - 1) + 1), key_limbs(*k, std::min(level, k->nQk - 1)), B, be.Q->N);  // Relinearize: 3 L in, 2 L out, key
         { Valu V(be.Q->logN); const int lv = std::min(level, k->nQk - 1); valu_gadget_product(V, be, lv, k->nPk - 1, k->pw2 ? k->prefix[lv + 1] : base_rns_size(lv, k->nPk - 1), true); V.into(*be.ctx, B); }
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, k->nPk - 1, B, true, k.get())));
+        const size_t wQ = (size_t)B * (level + 1) * be.Q->N;
+        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, k->nPk - 1, B, true, k.get()) + (cross ? 2 * wQ + 4 : 0)));
+        if (cross) {  // (served one by one: plain views)
+            View a0{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N}, a1{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N};
+            HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, be.ctx->stream));
+            HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[1], v[1], a1, B, nullptr, nullptr, be.ctx->stream));
+            return gadget_product_core(*ev, level, &v[2], nullptr, *k, v[3], v[4], B, &a0, &a1);
+        }
         return gadget_product_core(*ev, level, &v[2], nullptr, *k, v[3], v[4], B, &v[0], &v[1]);
     };
     q.tables_ok = [ev, k, level, alias](bool *ok) -> int {
@@ -4036,6 +4121,9 @@ static int automorphism_common(he_handle hev, int level, he_handle hin0, he_hand
     if (!(gal & 1)) return fail(HE_EINVAL, "%s: Galois element must be odd", who);
     if (dec && k->pw2) return fail(HE_EINVAL, "%s: method is unsupported for BaseTwoDecomposition != 0", who);
     if (dec) TRY(check_decomp(*ev, *dec, level, k->nPk - 1, who));
+    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}},
+                        {{2, 0}, {2, 1}, {3, 0}, {3, 1}}));
+    gal = reduce_gal(gal, be.Q->logN, be.type);
     // (an automorphism that writes onto its own inputs takes the gather form, which reads them all first: no entry tables then)
     const bool alias = in0->d == out0->d || in0->d == out1->d || (in1 && (in1->d == out0->d || in1->d == out1->d));
     const bool hoisted = dec != nullptr;
@@ -4078,6 +4166,11 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
     if (in0->batch != B) return fail(HE_EINVAL, "he_automorphism_hoisted_lazy: batch mismatch");
     QPOut o;
     TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, levelP, B, o, "he_automorphism_hoisted_lazy"));
+    // a Q output may be in0 (read before it is written: the gather form below)
+    std::vector<AliasOp> ops = o.outs();
+    ops.push_back({in0.get(), false, false});
+    TRY(reject_aliasing("he_automorphism_hoisted_lazy", ops, {{0, 4}, {2, 4}}));
+    gal = reduce_gal(gal, be.Q->logN, be.type);
     const bool alias = o.q0->d == in0->d || o.q1->d == in0->d;
     const size_t dec_ds = dec->dstride();
     CoReq q;
@@ -4111,18 +4204,19 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
             return ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, v[2], v[3], v[4], v[5], B, nullptr, 0, 0, 0, -1, &ks);
         }
         const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
-        TRY(be.ctx->arena_reserve(2 * B * (sQw + sPw) + N + 64));
-        View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw};
+        TRY(be.ctx->arena_reserve(3 * B * sQw + 2 * B * sPw + N + 64));
+        View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw}, t2Q{be.ctx->arena_take(B * sQw), sQw};
         View t0P{be.ctx->arena_take(B * sPw), sPw}, t1P{be.ctx->arena_take(B * sPw), sPw};
         const uint32_t *index = nullptr;
         TRY(cached_auto_index(*ev, gal, &index));
         hipStream_t st = be.ctx->stream;
         TRY(ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, t0Q, t0P, t1Q, t1P, B));
         const LimbTab tq = ident_tab(levelQ + 1), tp = ident_tab(levelP + 1, 0, 0, be.LQ);
+        // in0 is read before any output is written (c0Q or c1Q may be in0)
+        HIP_TRY(launch_ew(be.qp, tq, EW_MUL_SCALAR_MONT, v[0], v[0], t2Q, B, &s, nullptr, st));
+        HIP_TRY(launch_ew(be.qp, tq, EW_ADD, t0Q, t2Q, t0Q, B, nullptr, nullptr, st));
         HIP_TRY(launch_gather(be.qp, tq, t1Q, index, v[4], B, false, st));
         HIP_TRY(launch_gather(be.qp, tp, t1P, index, v[5], B, false, st));
-        HIP_TRY(launch_ew(be.qp, tq, EW_MUL_SCALAR_MONT, v[0], v[0], t1Q, B, &s, nullptr, st));
-        HIP_TRY(launch_ew(be.qp, tq, EW_ADD, t0Q, t1Q, t0Q, B, nullptr, nullptr, st));
         HIP_TRY(launch_gather(be.qp, tq, t0Q, index, v[2], B, false, st));
         HIP_TRY(launch_gather(be.qp, tp, t0P, index, v[3], B, false, st));
         return HE_OK;
@@ -4154,8 +4248,10 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
     if (addQ->batch != B || addP->batch != B) return fail(HE_EINVAL, "%s: batch mismatch", who);
     QPOut o;
     TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, levelP, B, o, who));
-    for (const Poly *out : {o.q0.get(), o.p0.get(), o.q1.get(), o.p1.get()})
-        if (out->d == cx->d || out->d == addQ->d || out->d == addP->d) return fail(HE_EINVAL, "%s: an output aliases an input", who);
+    std::vector<AliasOp> ops = o.outs();
+    ops.insert(ops.end(), {{cx.get(), false, false}, {addQ.get(), false, false}, {addP.get(), false, true}});
+    TRY(reject_aliasing(who, ops));  // no output may alias an input or another output
+    gal = reduce_gal(gal, be.Q->logN, be.type);
     CoReq q;
     q.op = CO_GIANT_STEP; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ; q.par[1] = (int64_t)gal; q.par[2] = accumulate ? 1 : 0;
     q.ops = {cx->view(), addQ->view(), addP->view(), o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view()};
@@ -4229,6 +4325,7 @@ int he_centered_lift(he_handle hev, int strict, he_handle hsrc, int first_q, int
         TRY(check_be_poly(*dp, be, levelP + 1, who));
         if (dp->batch != src->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
     }
+    TRY(reject_aliasing(who, {{src.get(), false, false}, {dq.get(), true, false}, {dp.get(), true, true}}, {{1, 0}}));
     ModUpArgs a{};
     a.nsrc = 1;
     a.src_limb[0] = 0;
@@ -4308,6 +4405,7 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
     q.keep = {ev, o.q0, o.p0, o.q1, o.p1};
     std::vector<const uint32_t *> idx(n, nullptr);
     std::vector<uint64_t> idx_gal(n, 0);
+    std::vector<AliasOp> aops = o.outs();  // every operand, for reject_aliasing below (kept alive by q.keep)
     for (int i = 0; i < n; i++) {
         GET(tq, Poly, ptQ[i], T_POLY);
         GET(c0q, Poly, ct0Q[i], T_POLY);
@@ -4316,7 +4414,6 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
         TRY(check_be_poly(*c0q, be, levelQ + 1, who));
         TRY(check_be_poly(*c1q, be, levelQ + 1, who));
         if ((tq->batch != 1 && tq->batch != B) || c0q->batch != B || c1q->batch != B) return fail(HE_EINVAL, "%s: batch mismatch (term %d)", who, i);
-        if (c0q->d == q0->d || c0q->d == q1->d || c1q->d == q0->d || c1q->d == q1->d) return fail(HE_EINVAL, "%s: an input aliases the output", who);
         if (index && index[i]) {
             GET(ixo, AutoIndex, index[i], T_INDEX);
             if (ixo->N != be.Q->N) return fail(HE_EINVAL, "%s: automorphism index of another degree", who);
@@ -4330,6 +4427,7 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
         if (tq->batch == 1) vt.bstride = 0;  // one plaintext diagonal for the whole batch
         q.ops.push_back(vt); q.ops.push_back(c0q->view()); q.ops.push_back(c1q->view());
         q.keep.push_back(tq); q.keep.push_back(c0q); q.keep.push_back(c1q);
+        aops.insert(aops.end(), {{tq.get(), false, false}, {c0q.get(), false, false}, {c1q.get(), false, false}});
         if ((ct0P[i] == 0) != (ct1P[i] == 0)) return fail(HE_EINVAL, "%s: term %d has only one P part", who, i);
         if (ct0P[i] == 0) {
             q.ops.push_back(View{nullptr, 0}); q.ops.push_back(View{nullptr, 0}); q.ops.push_back(View{nullptr, 0});
@@ -4342,12 +4440,13 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
         TRY(check_be_poly(*c0p, be, levelP + 1, who));
         TRY(check_be_poly(*c1p, be, levelP + 1, who));
         if ((tp->batch != 1 && tp->batch != B) || c0p->batch != B || c1p->batch != B) return fail(HE_EINVAL, "%s: batch mismatch (term %d)", who, i);
-        if (c0p->d == p0->d || c0p->d == p1->d || c1p->d == p0->d || c1p->d == p1->d) return fail(HE_EINVAL, "%s: an input aliases the output", who);
         View vp = tp->view();
         if (tp->batch == 1) vp.bstride = 0;
         q.ops.push_back(vp); q.ops.push_back(c0p->view()); q.ops.push_back(c1p->view());
         q.keep.push_back(tp); q.keep.push_back(c0p); q.keep.push_back(c1p);
+        aops.insert(aops.end(), {{tp.get(), false, true}, {c0p.get(), false, true}, {c1p.get(), false, true}});
     }
+    TRY(reject_aliasing(who, aops));  // the outputs alias nothing: the terms' inputs are read by every workgroup of both launches
     q.run = [ev, levelQ, levelP, n, accumulate, idx](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         DiagMacArgs aq{}, ap{};
@@ -4489,6 +4588,10 @@ static int mul_relin_common(he_handle hev, int level, bool bgv, uint64_t t, he_h
         TRY(check_be_poly(*p, be, level + 1, who));
         if (p->batch != B) return fail(HE_EINVAL, "%s: batch mismatch", who);
     }
+    // any output may be any input (MulRelin(res, res, res)); out2 is an output only without a key
+    TRY(reject_aliasing(who, {{a0.get(), false, false}, {a1.get(), false, false}, {b0.get(), false, false}, {b1.get(), false, false},
+                              {out0.get(), true, false}, {out1.get(), true, false}, {out2.get(), true, false}},
+                        {{4, 0}, {4, 1}, {4, 2}, {4, 3}, {5, 0}, {5, 1}, {5, 2}, {5, 3}, {6, 0}, {6, 1}, {6, 2}, {6, 3}}));
     bool alias = false;
     for (Poly *o : {out0.get(), out1.get()})
         for (Poly *in : {a0.get(), a1.get(), b0.get(), b1.get()}) alias = alias || o->d == in->d;
