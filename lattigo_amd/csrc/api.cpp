@@ -237,12 +237,6 @@ struct Ctx : Obj {
     int dev = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // Small batches (a lone caller, a few callers through the queue): the key switch's double-precision NTT + MAC launch runs on
-    // this side stream beside the integer chain (forward rows -> inner product -> ModDown's inverse rows -> basis extension) and
-    // is joined before the final forward rows; side_pending: a fork of the current call has not been joined yet
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool side_pending = false;
     // stream-ordered scratch arena (temporaries of one API call)
     uint64_t *arena = nullptr;
     size_t arena_words = 0, arena_used = 0;
@@ -352,9 +346,6 @@ struct Ctx : Obj {
         if (arena) hipFree(arena);
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
-        if (side) { hipStreamSynchronize(side); hipStreamDestroy(side); }
-        if (ev_fork) hipEventDestroy(ev_fork);
-        if (ev_join) hipEventDestroy(ev_join);
         if (stream) hipStreamDestroy(stream);
     }
     void arena_reset() { arena_used = 0; }
@@ -660,7 +651,8 @@ struct Evk : Obj {
     int beta = 0, nQk = 0, nPk = 0;
     int pw2 = 0;                 // BaseTwoDecomposition
     std::vector<int> nj, prefix; // bit windows per RNS digit and their prefix sums (pw2 != 0)
-    double *keyd = nullptr;      // plain key words as doubles for the limbs below 2^47 (fused NTT+MAC kernel), same layout
+    double *keyd = nullptr;      // plain key words as doubles for the limbs below 2^47 (fused NTT+MAC kernel): the blocks of d,
+                                 // each row of 4096 / 8192 coefficients permuted for that kernel (launch_key_to_f64)
     uint64_t *d = nullptr;
     Evk() : Obj(T_EVK) {}
     ~Evk() override {
@@ -1481,9 +1473,6 @@ int he_ctx_create(int device_id, he_handle *out) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&c->ev0));
     HIP_TRY(hipEventCreate(&c->ev1));
-    HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) c->kPoolCap = std::max<size_t>(c->kPoolCap, total_b / 2);
@@ -3347,8 +3336,6 @@ int decompose_fused(Evaluator &ev, const FusedPlan &plan, int levelQ, int levelP
 // class-2 limbs of the gadget product: forward row NTT + key MAC in one kernel (dec holds the post-column state)
 // May the basis extension hand unreduced doubles to the double-precision row kernels (launch_modup_fused f64_raw)?
 static bool f64_raw_ok(const BasisExtender &be, int levelQ, int levelP, int nsrc) {
-    static const bool off = env_flag("HERING_NO_F64_RAW");
-    if (off) return false;
     uint64_t mx = 0;
     for (int j = 0; j <= levelQ; j++) if (be.small[j] == 2) mx = std::max(mx, be.Q->moduli[j]);
     for (int j = 0; j <= levelP; j++) if (be.small[be.LQ + j] == 2) mx = std::max(mx, be.P->moduli[j]);
@@ -3358,9 +3345,9 @@ static bool f64_raw_ok(const BasisExtender &be, int levelQ, int levelP, int nsrc
 // the caller guarantees that no P limb is of the double-precision class
 int ks_mac_f64(Evaluator &ev, int levelQ, int levelP, const uint64_t *dec, size_t dec_bs, size_t dec_ds, const Evk &k, View cx,
                int own_alpha, View o0Q, View o0P, View o1Q, View o1P, int batch, bool q_out_f64 = false, bool own_reduce = true,
-               bool dec_f64 = false, const NttMacEpilogue *epi = nullptr, hipStream_t on = nullptr, const KsScatter *giant = nullptr) {
+               bool dec_f64 = false, const NttMacEpilogue *epi = nullptr, const KsScatter *giant = nullptr) {
     BasisExtender &be = *ev.be;
-    const hipStream_t st = on ? on : be.ctx->stream;
+    const hipStream_t st = be.ctx->stream;
     const int LQ = be.LQ, N = be.Q->N;
     NttMacArgs a{};
     a.beta = base_rns_size(levelQ, levelP);
@@ -3430,7 +3417,6 @@ struct TensorIn {
 // the P part with the ModDown epilogue inside (gadget_product_core)
 struct MacDefer {
     bool want = false, deferred = false;
-    bool side = false;  // in: run the NTT + MAC launch on the context's side stream (the caller joins: Ctx::side_pending)
     const uint64_t *dec = nullptr;
     size_t bs = 0, ds = 0;
     bool raw = false, own_reduce = true;
@@ -3506,24 +3492,9 @@ int gadget_product_lazy_core(Evaluator &ev, int levelQ, View cx, int B, const Ev
             int max_nsrc = 1;
             for (const FusedGroup &g : plan->groups) max_nsrc = std::max(max_nsrc, g.nsrc);
             const bool raw = f64_raw_ok(be, levelQ, levelP, max_nsrc);
-            if (defer && defer->side) {
-                // small batch: every launch is one workgroup chain's latency, not throughput.  The NTT + MAC launch over the
-                // double-precision limbs needs only the basis extension's output; it runs on the side stream while this one does
-                // the integer limbs' forward rows and inner product (and, in the caller, the P part's way back to Q)
-                for (const FusedGroup &g : plan->groups)
-                    HIP_TRY(launch_modup_fused(be.qp, g.dev, g.n, g.nsrc, g.dst_classes, inv, View{dec, bs}, View{dec, bs}, B, be.ctx->stream, raw, g.total_limbs));
-                HIP_TRY(hipEventRecord(be.ctx->ev_fork, be.ctx->stream));
-                HIP_TRY(hipStreamWaitEvent(be.ctx->side, be.ctx->ev_fork, 0));
-                if (acc_q_f64) *acc_q_f64 = want_f64;
-                TRY(ks_mac_f64(ev, levelQ, levelP, dec, bs, ds, k, cx, levelP + 1, o0Q, o0P, o1Q, o1P, B, want_f64, !cx_canonical, raw, nullptr, be.ctx->side));
-                HIP_TRY(hipEventRecord(be.ctx->ev_join, be.ctx->side));
-                be.ctx->side_pending = true;
-                TRY(dec_rows_ntt(ev, levelQ, levelP, levelP + 1, View{dec, bs}, B, 1));
-                return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B, &cx, levelP + 1, 1);
-            }
             TRY(decompose_fused(ev, *plan, levelQ, levelP, levelP + 1, inv, View{dec, bs}, B, 1, raw));
             TRY(ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B, &cx, levelP + 1, 1, 0, -1, giant));
-            if (giant) return ks_mac_f64(ev, levelQ, levelP, dec, bs, ds, k, cx, levelP + 1, o0Q, o0P, o1Q, o1P, B, false, !cx_canonical, raw, nullptr, nullptr, giant);
+            if (giant) return ks_mac_f64(ev, levelQ, levelP, dec, bs, ds, k, cx, levelP + 1, o0Q, o0P, o1Q, o1P, B, false, !cx_canonical, raw, nullptr, giant);
             if (defer && defer->want) {
                 defer->deferred = true; defer->dec = dec; defer->bs = bs; defer->ds = ds; defer->raw = raw; defer->own_reduce = !cx_canonical;
                 return HE_OK;
@@ -3621,17 +3592,6 @@ int gadget_product_core(Evaluator &ev, int levelQ, const View *cx, const View *h
         defer.want = out0.p != cx->p && out1.p != cx->p;
         for (int j = 0; j <= levelP; j++) defer.want = defer.want && be.small[be.LQ + j] != 2;
     }
-    // HERING_SIDE_MAX_BATCH=n (default 0: never): up to n entries take the fork instead of the fused epilogue -- two launches
-    // more, but the longest of the step (NTT + MAC over the digits) leaves the critical path.  Built and measured in round 5
-    // (VERDICT r4 item 7): SLOWER -- 0.184 ms against 0.159 ms for a lone MulRelin, 16.8 k against 18.7 k ops/s from four callers;
-    // the two cross-stream dependencies cost more than the overlap gains (NOTES.md).  Kept as an A/B switch.  Not while a graph
-    // is recorded, not under the kernel profiler, and only when the P accumulators do not depend on that launch.
-    static const int side_max = getenv("HERING_SIDE_MAX_BATCH") ? atoi(getenv("HERING_SIDE_MAX_BATCH")) : 0;
-    if (cx && plan->ok && k.keyd && !k.pw2 && B <= side_max && !be.ctx->capturing && !prof_active(be.ctx->stream)) {
-        bool p_int = true;
-        for (int j = 0; j <= levelP; j++) p_int = p_int && be.small[be.LQ + j] != 2;
-        if (p_int) { defer.want = false; defer.side = true; }
-    }
     if (cx) TRY(gadget_product_lazy_core(ev, levelQ, *cx, B, k, a0Q, a0P, a1Q, a1P, cx_canonical, &acc_f64, &defer, tin));
     else {
         acc_f64 = false;
@@ -3684,10 +3644,6 @@ int gadget_product_core(Evaluator &ev, int levelQ, const View *cx, const View *h
                 HIP_TRY(launch_ntt_rows(be.qp, ti, sQ, out0, 2 * B, false, 0, st, &epi));
             }
             return HE_OK;
-        }
-        if (be.ctx->side_pending) {  // the Q accumulators of the double-precision limbs come from the side stream
-            HIP_TRY(hipStreamWaitEvent(st, be.ctx->ev_join, 0));
-            be.ctx->side_pending = false;
         }
         NttEpilogue epi;
         epi.scatter_ginv = tin ? 0u : want_scatter;

@@ -354,7 +354,8 @@ hipError_t launch_ntt_mac_f64(const RingDev &r, const NttMacArgs &a, View dec, V
                               View out0P, View out1Q, View out1P, int batch, hipStream_t s, const NttMacEpilogue *epi = nullptr,
                               const KsScatter *giant = nullptr);
 bool ntt_mac_giant_supported(int logN);
-// keyd[i] = (double)IMForm(key[i]) for the limbs of class 2 (plain residues < 2^47), 0 elsewhere
+// keyd = (double)IMForm(key) for the limbs of class 2 (plain residues < 2^47), 0 elsewhere.  With rows of 4096 / 8192 coefficients
+// (ntt_row_bits >= 12) each row is permuted for the NTT + MAC kernel: position k T + t (T = row / 16) holds coefficient 16 t + k.
 hipError_t launch_key_to_f64(const RingDev &r, const uint64_t *key, double *keyd, int nblocks, const uint8_t *limb_mod_host,
                              int nlimbs, hipStream_t s);
 

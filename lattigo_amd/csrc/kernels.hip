@@ -162,12 +162,8 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned lin, unsigned n) {
 // ------------------------------------------------------------------------------------
 // The butterflies take their Montgomery products through mred_lazy_w32 (modarith.h: two 32-bit reduction rounds, 8 v_mad_u64_u32 +
 // 2 v_mul_lo_u32 + a few adds instead of the 11 multiplies and ~15 carry instructions of the full-width form): only the residue
-// class of a butterfly output matters, and the operands satisfy its domain (V + q < 2^64, w < q).  HE_BFLY_W32 = 0 restores the
-// full-width products for A/B builds.
-#ifndef HE_BFLY_W32
-#define HE_BFLY_W32 1
-#endif
-// Row kernels (HE_BFLY_ASM): the same product as ONE hand-written sequence of 16 instructions.  hipcc turns every form of it
+// class of a butterfly output matters, and the operands satisfy its domain (V + q < 2^64, w < q).
+// Row kernels: the same product as ONE hand-written sequence of 16 instructions.  hipcc turns every form of it
 // into 21-26: the 64-bit addend of v_mad_u64_u32 must be an (even-aligned) register pair, so each "high word, zero-extended" is a
 // v_mov_b32 into a fresh pair, and a carry costs a 64-bit compare + select.  By column instead: L = x0 w0, M = x0 w1 + x1 w0,
 // H = x1 w1 are three aligned 64-bit accumulators (for q < 2^61 and x < 4q the middle column cannot overflow: x1 w0 < 2^63,
@@ -176,22 +172,11 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned lin, unsigned n) {
 // through asm operands, so the seven scratch registers are fixed (v116..v122, declared clobbered: inside the 128-register
 // budget of the four-wave row kernels), which is why only the row kernels take this form.
 //   8 v_mad_u64_u32 + 2 v_mul_lo_u32 + 6 v_add(c)_co_u32, result (T + m q) / 2^64 in [0, 2q) as mred_lazy_w32.
-#ifndef HE_BFLY_ASM
-#define HE_BFLY_ASM 1
-#endif
 // gfx940 / gfx950: a VALU instruction that reads VCC (a carry-in) wants two wait states after the VALU instruction that wrote it
 // -- hipcc pads its own carry chains with `s_nop 1` (llvm's VALUWriteSGPRVALURead rule), and nothing pads an asm string.  The
 // sequence ran bit-exact without the pads through every suite of this round, which is no evidence for a hazard that shows on
-// "some waves of some launches": it carries them.  An s_nop costs the wave two issue cycles, not the SIMD (HE_BFLY_VCC_PAD = 0
-// for A/B builds).
-#ifndef HE_BFLY_VCC_PAD
-#define HE_BFLY_VCC_PAD 1
-#endif
-#if HE_BFLY_VCC_PAD
+// "some waves of some launches": it carries them.  An s_nop costs the wave two issue cycles, not the SIMD.
 #define HE_VCC_PAD "s_nop 1\n\t"
-#else
-#define HE_VCC_PAD
-#endif
 __device__ __forceinline__ uint64_t mred_lazy_col_asm(uint64_t x, uint64_t w, uint64_t q, uint64_t qinv) {
     const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32), w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32);
     const uint32_t q0 = (uint32_t)q, q1 = (uint32_t)(q >> 32), nq = (uint32_t)(0 - qinv);
@@ -223,9 +208,8 @@ __device__ __forceinline__ uint64_t mred_lazy_col_asm(uint64_t x, uint64_t w, ui
 }
 template <bool ROWS = false>
 __device__ __forceinline__ uint64_t bfly_mul(uint64_t v, uint64_t w, uint64_t q, uint64_t qinv) {
-    if constexpr (HE_BFLY_ASM && ROWS) return mred_lazy_col_asm(v, w, q, qinv);
-    else if constexpr (HE_BFLY_W32) return mred_lazy_w32(v, w, q, qinv);
-    else return mred_lazy(v, w, q, qinv);
+    if constexpr (ROWS) return mred_lazy_col_asm(v, w, q, qinv);
+    else return mred_lazy_w32(v, w, q, qinv);
 }
 // forward: U,V in [0,4q) -> X,Y in [0,4q)
 template <bool ROWS = false>
@@ -256,7 +240,7 @@ __device__ __forceinline__ void bfly_inv(uint64_t &a, uint64_t &b, uint64_t w, u
     b = mred_lazy(U + twoq - V, w, q, qinv);
 }
 // the same two butterflies with the hand-written product (kernels with register room for its fixed scratch: the fused basis
-// extension, HE_MODUP_ASM)
+// extension)
 __device__ __forceinline__ void bfly_inv_asm(uint64_t &a, uint64_t &b, uint64_t w, uint64_t q, uint64_t twoq, uint64_t qinv) {
     const uint64_t U = a, V = b, X = U + V;
     a = X >= twoq ? X - twoq : X;
@@ -349,10 +333,8 @@ __device__ __forceinline__ int nat_e(int k, int tau) {
 // N = 2^n is split into a strided "column" stages and b contiguous "row" stages: rows of 4096 coefficients
 // (b = 12) up to logN = 15, rows of 8192 (b = 13, two 512-thread workgroups per CU) from logN = 16 so that the
 // fused basis extension never holds more than 8 strided coefficients per thread.
-// HERING_ROWBITS16=12: logN = 16 on 4096-rows with four column stages inside the basis extension (A/B, NOTES.md round 6)
 int ntt_row_bits(int n) {
-    static const int rb16 = getenv("HERING_ROWBITS16") && atoi(getenv("HERING_ROWBITS16")) == 12 ? 12 : 13;
-    return n <= 12 ? n : (n <= 15 ? 12 : (n == 16 ? rb16 : 13));
+    return n <= 12 ? n : (n <= 15 ? 12 : 13);
 }
 
 // ------------------------------------------------------------------------------------
@@ -470,9 +452,6 @@ __device__ __forceinline__ void rows_round16_inv_asm(uint64_t (&x)[16], const ui
 // e0 = (hi << (LOGB - s0)) + lo, and because bits [sh, sh + 4) of e0 are clear, lds_phys(e) = lds_phys(e0) + c_k with
 // c_k = (k << sh) + ((k << sh) >> 4) -- a compile-time constant where the call site knows sh (LDS offset immediates), a scalar
 // otherwise: one base address per exchange instead of a shift / add / shift / add chain per element.
-#ifndef HE_XFER16
-#define HE_XFER16 1  // 0: the per-element address arithmetic of rounds 1-2 (A/B builds)
-#endif
 template <int LOGB, class Tw>
 __device__ __forceinline__ void rows_lds_xfer16(Tw (&x)[16], Tw *lds, int tau, int s0, int sh, bool store) {
     const unsigned ut = (unsigned)tau, hi = ut >> sh, lo = ut & ((1u << sh) - 1u);
@@ -487,7 +466,7 @@ __device__ __forceinline__ void rows_lds_xfer16(Tw (&x)[16], Tw *lds, int tau, i
 }
 template <int LOGB, int G4>
 __device__ __forceinline__ void rows_lds_xfer(uint64_t (&x)[16], uint64_t *lds, int tau, int s0, int sh, bool store) {
-    if constexpr (G4 == 4 && HE_XFER16) { rows_lds_xfer16<LOGB>(x, lds, tau, s0, sh, store); return; }
+    if constexpr (G4 == 4) { rows_lds_xfer16<LOGB>(x, lds, tau, s0, sh, store); return; }
     constexpr int g = G4, G = 1 << g, W = 16 / G;
 #pragma unroll
     for (int w = 0; w < W; w++) {
@@ -814,7 +793,7 @@ __device__ __forceinline__ void rows_round16_f64(double (&x)[16], const double (
 
 template <int LOGB, int G4>
 __device__ __forceinline__ void rows_lds_xfer_f64(double (&x)[16], double *lds, int tau, int s0, int sh, bool store) {
-    if constexpr (G4 == 4 && HE_XFER16) { rows_lds_xfer16<LOGB>(x, lds, tau, s0, sh, store); return; }
+    if constexpr (G4 == 4) { rows_lds_xfer16<LOGB>(x, lds, tau, s0, sh, store); return; }
     constexpr int g = G4, G = 1 << g, W = 16 / G;
 #pragma unroll
     for (int w = 0; w < W; w++) {
@@ -934,25 +913,18 @@ __global__ void __launch_bounds__((1 << LOGB) / 16 > 0 ? (1 << LOGB) / 16 : 1) n
                 // words below 2q, which convert as they are -- the Barrett reduction (a dozen integer instructions per word, up to
                 // 64 words per thread) runs only for a wave that actually met a larger word
                 const uint64_t twoq_u = mc.q << 1;
-#ifndef HE_EPI_ALWAYS_REDUCE
-#define HE_EPI_ALWAYS_REDUCE 0  // 1: the unconditional reduction of round 2 (A/B builds)
-#endif
-#ifndef HE_EPI_SHARED_FIRST
-#define HE_EPI_SHARED_FIRST 1  // 0: round 2's order (component 1 reads a0, b1 then a1, b0)
-#endif
                 auto cvtn = [&](auto &w, auto &d) {
                     constexpr int n = (int)(sizeof(w) / sizeof(w[0]));
                     bool big = false;
 #pragma unroll
                     for (int k = 0; k < n; k++) big = big || w[k] >= twoq_u;
-                    if (HE_EPI_ALWAYS_REDUCE || __any(big)) {
+                    if (__any(big)) {
 #pragma unroll
                         for (int k = 0; k < n; k++) w[k] = bred_add_lazy(w[k], mc.q, mc.brc0);
                     }
 #pragma unroll
                     for (int k = 0; k < n; k++) d[k] = u52_to_f64(w[k]);
                 };
-#if HE_EPI_SHARED_FIRST
                 // Both components of an entry read a0 and b0 -- in two workgroups that the launch order puts on one XCD, a few
                 // microseconds apart.  Component 1 used to read a0, b1 first and a1, b0 a phase later: by then the XCD's 4 MB L2
                 // (turned over every ~6 us at this kernel's rate) had dropped b0, and 73 % of those second reads went to HBM
@@ -985,32 +957,6 @@ __global__ void __launch_bounds__((1 << LOGB) / 16 > 0 ? (1 << LOGB) / 16 : 1) n
                         stnt(&op[e], canon_f64(t, q, qi));
                     }
                 }
-#else
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    double u[8], v[8], wv[8];
-                    uint64_t ur[8], vr[8];
-                    const uint64_t *pv = second ? pb1 : pb0;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) { const int e = nat_e<T>(8 * h + k, tau); ur[k] = pa0[e]; vr[k] = pv[e]; }
-                    cvtn(ur, u); cvtn(vr, v);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) wv[k] = modmul_f64(u[k], v[k], q, qi);
-                    if (second) {
-#pragma unroll
-                        for (int k = 0; k < 8; k++) { const int e = nat_e<T>(8 * h + k, tau); ur[k] = pa1[e]; vr[k] = pb0[e]; }
-                        cvtn(ur, u); cvtn(vr, v);
-#pragma unroll
-                        for (int k = 0; k < 8; k++) wv[k] += modmul_f64(u[k], v[k], q, qi);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const int e = nat_e<T>(8 * h + k, tau);
-                        const double t = modmul_f64(wv[k], tsp, q, qi) + modmul_f64(lds[lds_phys(e)] - yv[8 * h + k], sp, q, qi);
-                        stnt(&op[e], canon_f64(t, q, qi));
-                    }
-                }
-#endif
             } else if (addw) {
                 uint64_t wv[16];
 #pragma unroll
@@ -1163,6 +1109,8 @@ struct NttMacKArgs {
     // entry tables (View::tab) of the four accumulator outputs when they are the caller's (GadgetProductLazy of a coalesced batch)
     const size_t *oQ0_tab = nullptr, *oP0_tab = nullptr, *oQ1_tab = nullptr, *oP1_tab = nullptr;
 };
+// The plain kernel: rows of 2^4 ... 2^11 coefficients (4096- and 8192-rows take the persistent kernel below, whose row-permuted
+// key copy this one cannot read).
 // QF64: every limb of the launch is a Q limb whose accumulators are written as doubles (NttMacArgs::q_out_f64)
 template <int LOGB, bool QF64>
 __global__ void __launch_bounds__((1 << LOGB) / 16 > 0 ? (1 << LOGB) / 16 : 1, 2) ntt_mac_f64_kernel(NttMacKArgs A) {
@@ -1311,22 +1259,13 @@ __global__ void __launch_bounds__((1 << LOGB) / 16 > 0 ? (1 << LOGB) / 16 : 1, 2
 // Bit-identical to the plain kernel (same arithmetic on the same operands).
 // ------------------------------------------------------------------------------------
 
-// HE_MAC_R2 (round 6): the key inner product runs in the register order the LAST round of the row transform leaves (thread tau
-// holds the sixteen consecutive coefficients 16 tau .. 16 tau + 15) instead of the coalesced order k T + tau: a transformed digit
-// no longer stores its result back to the tile, waits for the workgroup and reads it again (one LDS exchange and one barrier of
-// three fewer per digit).  The double-precision key copy is laid out to match (key_to_f64_kernel: position k T + t of a row
-// holds coefficient 16 t + k, so the key rows are still read coalesced); the digit's own limb -- NTT-domain words in natural
-// order -- takes one exchange through the tile; the accumulators take the exchange back where they leave the kernel (the
-// ModDown epilogue subtracts first and transposes the difference: the same count as before).  0: round 3-5's order (A/B builds).
-#ifndef HE_MAC_R2
-#define HE_MAC_R2 1
-#endif
-#ifndef HE_MAC_K1_EARLY
-#define HE_MAC_K1_EARLY 0
-#endif
-#ifndef HE_MAC_EPI_PREFETCH
-#define HE_MAC_EPI_PREFETCH 1
-#endif
+// The key inner product runs in the register order the LAST round of the row transform leaves (thread tau holds the sixteen
+// consecutive coefficients 16 tau .. 16 tau + 15) instead of the coalesced order k T + tau: a transformed digit does not store
+// its result back to the tile, wait for the workgroup and read it again (one LDS exchange and one barrier of three fewer per
+// digit).  The double-precision key copy is row-permuted to match (key_to_f64_kernel: position k T + t of a row holds
+// coefficient 16 t + k, so the key rows are still read coalesced); the digit's own limb -- NTT-domain words in natural order --
+// takes one exchange through the tile; the accumulators take the exchange back where they leave the kernel (the ModDown
+// epilogue subtracts first and transposes the difference).
 // the tile positions of a thread's sixteen coefficients in that order (thread-private: no other thread touches them)
 template <int LOGB>
 __device__ __forceinline__ void mac_final_xfer(double (&x)[16], double *lds, int tau, bool store) {
@@ -1474,11 +1413,10 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
             tw1s[tau] = cur.tw[((unsigned)cur.rowtw << (4 + u)) + (hi << u) + j];  // its wait is the first digit's (below)
         }
         bool more = false;
-        // forward row transform of x (element k T + tau in, the same order out), with the prefetch of `nsrc` and -- digits only --
-        // the two key rows issued where they hide best
-        auto transform = [&](int nk, auto read_back, double (&x)[16], unsigned tau, unsigned lane, const uint64_t *nsrc, const double *k0p,
+        // forward row transform of x (element k T + tau in, the last round's order out), with the prefetch of `nsrc` and -- digits
+        // only -- the two key rows issued where they hide best
+        auto transform = [&](int nk, double (&x)[16], unsigned tau, unsigned lane, const uint64_t *nsrc, const double *k0p,
                              const double *k1p, double (&kk0)[16], double (&kk1)[16], int early = 0) {
-            // read_back = false: the result stays in the tile (element e at lds_phys(e)) for the caller to pick up
             // nk (block-uniform): rows of sixteen words fetched on the way -- 2 (k0p and k1p), 1 (k0p), 0
             // round-2 twiddles first, then the DMA: ordinary loads issued after it could only return after it
             double t2[15];
@@ -1514,24 +1452,20 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
 #pragma unroll
                 for (int k = 0; k < 16; k++) kk0[k] = k0p[(unsigned)(k * T)];
             }
-            // HE_MAC_K1_EARLY: nothing stands between round 2 and the products any more (HE_MAC_R2), so the second key row is
-            // requested before the round as well where the registers allow it (4096-rows: 214 -> 2xx registers)
-            constexpr bool k1_early = HE_MAC_R2 && HE_MAC_K1_EARLY && LOGB == 12;
-            // early (the epilogue's transforms, HE_MAC_EPI_PREFETCH): both rows before the round -- held across the whole transform
-            // they cost 176 spilled registers
-            if ((k1_early || early != 0) && nk >= 2) {
+            // early (the epilogue's transforms, operands prefetched): both rows before the round -- held across the whole
+            // transform they cost 176 spilled registers
+            if (early != 0 && nk >= 2) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) kk1[k] = k1p[(unsigned)(k * T)];
             }
             __builtin_amdgcn_sched_barrier(0);
             rows_round16_f64<false>(x, t2, q, qi);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(k1_early || early != 0) && nk >= 2) {
+            if (early == 0 && nk >= 2) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) kk1[k] = k1p[(unsigned)(k * T)];
             }
             __builtin_amdgcn_sched_barrier(0);
-#if HE_MAC_R2
             // the result stays in the registers, in the last round's order (coefficients 16 tau .. 16 tau + 15)
             if constexpr (GREM > 0) {
                 rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 8, LOGB - 12, true);
@@ -1539,21 +1473,6 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 rows_lds_xfer_f64<LOGB, GREM>(x, lds, tau, 12, 0, false);
                 rows_round_f64<GREM, false>(x, cur.tw, cur.rowtw, 12, 0, tau, 0, q, qi);
             }
-            (void)read_back;
-#else
-            rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 8, LOGB - 12, true);
-            if constexpr (GREM > 0) {
-                rows_sync(LOGB - 12);
-                rows_lds_xfer_f64<LOGB, GREM>(x, lds, tau, 12, 0, false);
-                rows_round_f64<GREM, false>(x, cur.tw, cur.rowtw, 12, 0, tau, 0, q, qi);
-                rows_lds_xfer_f64<LOGB, GREM>(x, lds, tau, 12, 0, true);
-            }
-            __syncthreads();
-            if constexpr (decltype(read_back)::value) {
-#pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = lds[lds_phys(k * T + tau)];
-            }
-#endif
         };
         // the prefetch buffer's next content after source `d` of the current item (block-uniform): the item's next source, or the
         // next item's first digit (then `w`, `more` describe that item)
@@ -1594,7 +1513,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
             const double *k0p = cur.kbase + (size_t)d * A.m.key_dstride + tau, *k1p = k0p + A.m.key_kstride;
             double kk0[16], kk1[16];
             if (!is_own) {
-                transform(2, std::true_type{}, x, tau, lane, nsrc, k0p, k1p, kk0, kk1);
+                transform(2, x, tau, lane, nsrc, k0p, k1p, kk0, kk1);
             } else {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (nsrc) dma_digit(nsrc, lane);
@@ -1604,13 +1523,11 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
 #pragma unroll
                 for (int k = 0; k < 16; k++) kk1[k] = k1p[(unsigned)(k * T)];
                 __builtin_amdgcn_sched_barrier(0);
-#if HE_MAC_R2
                 // natural order -> the accumulators' order, through the tile (the key rows are in flight meanwhile)
                 __syncthreads();  // every wave is done with the tile (the previous digit's / item's last cross-wave read)
                 rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 0, LOGB - 4, true);  // element k T + tau
                 __syncthreads();
                 mac_final_xfer<LOGB>(x, lds, tau, false);
-#endif
             }
             MAC_STAMP2(1 + d * 12 + 8);
 #pragma unroll
@@ -1654,13 +1571,13 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 const bool addw = !tensor && (second ? AA.e.has_w1 : AA.e.has_w0) != 0;
                 double kd0[16], kd1[16];  // the key rows' registers: free in these transforms (no key rows on the way)
                 MAC_STAMP2(48 + c * 4 + 1);
-                // HE_MAC_EPI_PREFETCH (4096-rows): the operands the epilogue needs from memory -- a0, b0 (component 0) / a0, b1
+                // 4096-rows: the operands the epilogue needs from memory -- a0, b0 (component 0) / a0, b1
                 // (component 1) of the tensor term, or the addend row -- are requested at the head of the transform into those
                 // registers, before its last round -- the place the key rows of a digit are requested (tools/mac_timeline.py,
                 // round 6: the epilogue phases were 10.6 k and 17.1 k cycles per item for ~2.6 k and ~3.5 k cycles of arithmetic:
                 // they waited for these loads)
-                constexpr bool prefetch = HE_MAC_R2 && HE_MAC_EPI_PREFETCH && LOGB == 12;  // tensor + addend modes
-                constexpr bool prefetch_w = false;  // the addend row alone at 8192-rows: measured equal to slightly slower (c4 2.35 -> 2.37-2.39 ms)
+                // (the addend row alone at 8192-rows measured equal to slightly slower: c4 2.35 -> 2.37-2.39 ms)
+                constexpr bool prefetch = LOGB == 12;  // tensor + addend modes
                 const uint64_t *pa0 = nullptr, *pa1 = nullptr, *pb0 = nullptr, *pb1 = nullptr, *wp = nullptr;
                 if (tensor) {
                     pa0 = AA.e.ta0 + meoff(AA.e, ME_TA0, AA.e.ta0_bs, cur.bz, AA.nbatch) + off; pa1 = AA.e.ta1 + meoff(AA.e, ME_TA1, AA.e.ta1_bs, cur.bz, AA.nbatch) + off;
@@ -1675,13 +1592,10 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 if constexpr (prefetch) {
                     const double *e0 = reinterpret_cast<const double *>(tensor ? pa0 : wp);
                     const double *e1 = reinterpret_cast<const double *>(second ? pb1 : pb0);
-                    transform(tensor ? 2 : (addw ? 1 : 0), std::true_type{}, x, tau, lane, nsrc, e0, e1, kd0, kd1, 1);
-                } else if constexpr (prefetch_w) {
-                    transform(addw ? 1 : 0, std::true_type{}, x, tau, lane, nsrc, reinterpret_cast<const double *>(wp), nullptr, kd0, kd1, 1);
+                    transform(tensor ? 2 : (addw ? 1 : 0), x, tau, lane, nsrc, e0, e1, kd0, kd1, 1);
                 } else {
-                    transform(0, std::true_type{}, x, tau, lane, nsrc, nullptr, nullptr, kd0, kd1);
+                    transform(0, x, tau, lane, nsrc, nullptr, nullptr, kd0, kd1);
                 }
-#if HE_MAC_R2
                 // x - acc in the accumulators' order, then the transpose to the coalesced order of the operands and the stores
                 // (the tile positions written are the thread's own: no barrier before the stores)
 #pragma unroll
@@ -1690,7 +1604,6 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 __syncthreads();
 #pragma unroll
                 for (int k = 0; k < 16; k++) x[k] = lds[lds_phys(k * T + tau)];
-#endif
                 MAC_STAMP2(48 + c * 4 + 2);
                 if (tensor) {
                     const double tsp = AA.e.tsp[cur.l];
@@ -1733,12 +1646,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
 #pragma unroll
                         for (int k = 0; k < NB; k++) {
                             const int i = NB * h + k;
-#if HE_MAC_R2
                             const double tt = modmul_f64(wv[k], tsp, q, qi) + modmul_f64(x[i], sp, q, qi);
-#else
-                            const double yi = reduce_f64(acc0[i], q, qi);  // (|y| < q: x - y stays an exact integer below 2^53, as with the separate epilogue)
-                            const double tt = modmul_f64(wv[k], tsp, q, qi) + modmul_f64(x[i] - yi, sp, q, qi);
-#endif
                             stnt(&op[(unsigned)(i * T)], canon_f64(tt, q, qi));
                         }
                         __builtin_amdgcn_sched_barrier(0);
@@ -1788,7 +1696,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
 #undef HE_H
                 } else if (addw) {
                     uint64_t wv[16];
-                    if constexpr (prefetch || prefetch_w) {
+                    if constexpr (prefetch) {
 #pragma unroll
                         for (int k = 0; k < 16; k++) wv[k] = (uint64_t)__double_as_longlong(kd0[k]);
                     } else {
@@ -1797,11 +1705,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                     }
 #pragma unroll
                     for (int k = 0; k < 16; k++) {
-#if HE_MAC_R2
                         const uint64_t v = canon_f64(modmul_f64(x[k], sp, q, qi), q, qi);
-#else
-                        const uint64_t v = canon_f64(modmul_f64(x[k] - reduce_f64(acc0[k], q, qi), sp, q, qi), q, qi);
-#endif
                         uint64_t *dp = &op[(unsigned)(k * T)];
                         if constexpr (SCAT) dp = op - (cur.rowoff + tau) + auto_dest((unsigned)(cur.rowoff + tau) + (unsigned)(k * T), AA.e.sc_ginv, AA.e.sc_logN);
                         stnt(dp, cred(wv[k] + v, qu));
@@ -1811,11 +1715,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                     for (int k = 0; k < 16; k++) {
                         uint64_t *dp = &op[(unsigned)(k * T)];
                         if constexpr (SCAT) dp = op - (cur.rowoff + tau) + auto_dest((unsigned)(cur.rowoff + tau) + (unsigned)(k * T), AA.e.sc_ginv, AA.e.sc_logN);
-#if HE_MAC_R2
                         stnt(dp, canon_f64(modmul_f64(x[k], sp, q, qi), q, qi));
-#else
-                        stnt(dp, canon_f64(modmul_f64(x[k] - reduce_f64(acc0[k], q, qi), sp, q, qi), q, qi));
-#endif
                     }
                 }
                 MAC_STAMP2(48 + c * 4 + 3);
@@ -1824,7 +1724,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
 #pragma unroll
                 for (int k = 0; k < 16; k++) acc0[k] = acc1[k];
             };
-            if constexpr (HE_MAC_R2 && HE_MAC_EPI_PREFETCH && LOGB == 12) {
+            if constexpr (LOGB == 12) {
                 // two copies of the pass: the second accumulator's registers are free in the second one (as ONE loop body the
                 // prefetched operand rows cost 180 spilled registers)
                 ext_pass(std::integral_constant<int, 0>{});
@@ -1865,7 +1765,6 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#if HE_MAC_R2
         if constexpr (!EPI) {
             // the accumulators leave in the coalesced order: one exchange each (the tile positions a thread writes are its own, and
             // the other waves' last tile accesses were to theirs: no barrier before the first store)
@@ -1900,7 +1799,6 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
             __syncthreads();  // every wave has read acc0 before acc1 lands on it
             to_natural(acc1);
         }
-#endif
         if constexpr (EPI) {
             (void)o0; (void)o1; (void)ol;  // the epilogue wrote the final outputs
         } else if constexpr (SCAT) {
@@ -1942,8 +1840,7 @@ static unsigned mac_resident_workgroups(int logb) {
             n = 256;
         return (unsigned)n;
     }();
-    static const unsigned forced = getenv("HERING_MAC_WGS") ? (unsigned)atoi(getenv("HERING_MAC_WGS")) : 0u;
-    return forced ? forced : (logb >= 13 ? cus : 2u * cus);
+    return logb >= 13 ? cus : 2u * cus;
 }
 
 bool ntt_prod_in_supported(int logN) {
@@ -1960,7 +1857,7 @@ bool ntt_mac_epilogue_supported(int logN) {
 }
 bool ntt_mac_giant_supported(int logN) {
     const int b = ntt_row_bits(logN);
-    return HE_MAC_R2 && (b == 12 || b == 13);
+    return b == 12 || b == 13;
 }
 hipError_t launch_ntt_mac_f64(const RingDev &r, const NttMacArgs &a, View dec, View own, const double *keyd, View out0Q,
                               View out0P, View out1Q, View out1P, int batch, hipStream_t s, const NttMacEpilogue *epi,
@@ -1981,8 +1878,7 @@ hipError_t launch_ntt_mac_f64(const RingDev &r, const NttMacArgs &a, View dec, V
     double mac_bytes = ((double)a.beta * batch + 2.0 * a.beta + 2.0 * batch) * a.nlimbs * (double)r.N * 8.0;
     // with the epilogue: + the two extension rows, + the addends (w0 / w1) or the four inputs of the product, per entry and limb
     if (epi) mac_bytes += (2.0 + (epi->tensor ? 4.0 : (epi->has_w0 ? 1.0 : 0.0) + (epi->has_w1 ? 1.0 : 0.0))) * batch * a.nlimbs * (double)r.N * 8.0;
-    static const bool plain_only = env_flag("HERING_MAC_PLAIN") && !HE_MAC_R2;  // (the plain kernel reads the key rows in natural order)
-    if (epi || giant || b == 13 || (b == 12 && !plain_only)) {  // (the plain kernel has no 8192-row instantiation: it would spill)
+    if (epi || giant || b >= 12) {  // the production row sizes: the persistent kernel
         NttMacDmaArgs D;
         D.k = A;
         D.e = MacEpiK{};
@@ -2067,15 +1963,6 @@ hipError_t launch_ntt_mac_f64(const RingDev &r, const NttMacArgs &a, View dec, V
         return hipGetLastError();
     }
     dim3 grid(batch, a.nlimbs, 1u << aa);
-#ifdef HE_MAC_STAMPS
-    {   // diagnosis build only: HERING_MAC_ABL makes the key (1, 8), input (2) and output (4) streams cache-resident
-        static const int abl = getenv("HERING_MAC_ABL") ? atoi(getenv("HERING_MAC_ABL")) : 0;
-        if (abl & 1) { A.m.key_dstride = 0; A.m.key_kstride = 0; }
-        if (abl & 2) { A.dec_bs = 0; A.own_bs = 0; A.m.dec_dstride = 0; }
-        if (abl & 4) { A.oQ0_bs = A.oP0_bs = A.oQ1_bs = A.oP1_bs = 0; }
-        if (abl & 8) { for (int i = 0; i < a.nlimbs; i++) A.m.key_limb[i] = 0; }
-    }
-#endif
     ProfScope ps(K_NTT_MAC_F64, s, mac_bytes);
 #define HE_MAC_CASE(B)                                                                                      \
     case B:                                                                                                 \
@@ -2084,7 +1971,7 @@ hipError_t launch_ntt_mac_f64(const RingDev &r, const NttMacArgs &a, View dec, V
         break;
     switch (b) {
         HE_MAC_CASE(4) HE_MAC_CASE(5) HE_MAC_CASE(6) HE_MAC_CASE(7) HE_MAC_CASE(8) HE_MAC_CASE(9) HE_MAC_CASE(10)
-        HE_MAC_CASE(11) HE_MAC_CASE(12)
+        HE_MAC_CASE(11)
         default: return hipErrorInvalidValue;
     }
 #undef HE_MAC_CASE
@@ -2096,7 +1983,7 @@ struct KeyF64Args {
     double *keyd;
     const ModConst *mc;
     int N, nlimbs;
-    int rowbits;  // > 0: rows of 2^rowbits coefficients are stored in the NTT + MAC kernel's accumulator order (HE_MAC_R2)
+    int rowbits;  // > 0: rows of 2^rowbits coefficients are stored in the NTT + MAC kernel's accumulator order
     uint8_t mod[kMaxLimbs];
 };
 __global__ void __launch_bounds__(256) key_to_f64_kernel(KeyF64Args A) {
@@ -2118,11 +2005,7 @@ hipError_t launch_key_to_f64(const RingDev &r, const uint64_t *key, double *keyd
                              int nlimbs, hipStream_t s) {
     KeyF64Args A{};
     A.key = key; A.keyd = keyd; A.mc = r.mc; A.N = r.N; A.nlimbs = nlimbs;
-#if HE_MAC_R2
     A.rowbits = ntt_row_bits(r.logN) >= 12 ? ntt_row_bits(r.logN) : 0;  // the persistent kernel's rows (launch_ntt_mac_f64)
-#else
-    A.rowbits = 0;
-#endif
     for (int i = 0; i < nlimbs; i++) A.mod[i] = limb_mod_host[i];
     dim3 grid((unsigned)((r.N + 255) / 256), nlimbs, nblocks), block(256);
     hipLaunchKernelGGL(key_to_f64_kernel, grid, block, 0, s, A);
@@ -2303,9 +2186,8 @@ static hipError_t launch_rows(int logb, dim3 grid, const NttArgs &A, const uint8
     hipError_t e = hipSuccess;
     if (P[2].tab.n) {
         // entries per workgroup (inverse only): 2 while the launch still has well over the ~1500 workgroups that fill the chip
-        static const int forced = getenv("HERING_ROWS_ITERS") ? atoi(getenv("HERING_ROWS_ITERS")) : 0;
         const size_t wgs = (size_t)grid.x * P[2].tab.n * grid.z;
-        int iters = (!INV || logb > 12 || P[2].tprod) ? 1 : forced > 0 ? forced : (wgs >= 6144 ? 2 : 1);
+        int iters = (!INV || logb > 12 || P[2].tprod) ? 1 : (wgs >= 6144 ? 2 : 1);
         if (iters > (int)grid.x) iters = (int)grid.x;
         P[2].nbatch = (int)grid.x; P[2].iters = iters; P[2].nbatch_prof = (int)grid.x;
         dim3 g2((grid.x + iters - 1) / iters, P[2].tab.n, grid.z);
@@ -2973,9 +2855,7 @@ struct ModUpFusedArgs {
 // DSTF64 = false: destinations in 64-bit integer arithmetic (any modulus).
 // DSTF64 = true : only destination moduli below 2^47, the mat-vec and the column stages in exact double-precision
 //                 integer arithmetic (see ntt_rows_f64_kernel); same canonical results.
-#ifndef HE_MODUP_ASM
-#define HE_MODUP_ASM 1  // integer source stages, y_i and lean-destination butterflies through mred_lazy_col_asm (0: compiler forms)
-#endif
+// The integer source stages, the y_i and the lean-destination butterflies take their products through mred_lazy_col_asm.
 #ifndef HE_MODUP_WAVES
 #define HE_MODUP_WAVES 3  // waves per SIMD the register allocation aims at (the LDS footprint allows three)
 #endif
@@ -3089,13 +2969,8 @@ __global__ void __launch_bounds__(128, HE_MODUP_WAVES) modup_fused_kernel(ModUpF
                 for (int r = 0; r < R; r++) {
                     if (r & d) continue;
                     const uint64_t wv = tw[(1 << s) + (r >> (LOGA - s))];
-#if HE_MODUP_ASM
                     if (s == 0) bfly_inv_scaled_asm(x[r], x[r + d], mred(wv, mq.ninv, q, qinv), mq.ninv, q, twoq, qinv);
                     else bfly_inv_asm(x[r], x[r + d], wv, q, twoq, qinv);
-#else
-                    if (s == 0) bfly_inv_scaled(x[r], x[r + d], mred(wv, mq.ninv, q, qinv), mq.ninv, q, twoq, qinv);
-                    else bfly_inv(x[r], x[r + d], wv, q, twoq, qinv);
-#endif
                 }
             }
         }
@@ -3127,11 +3002,7 @@ __global__ void __launch_bounds__(128, HE_MODUP_WAVES) modup_fused_kernel(ModUpF
             } else {
 #pragma unroll
                 for (int r = 0; r < R; r++) {
-#if HE_MODUP_ASM
                     yi[r] = cred(mred_lazy_col_asm(cred(x[r] + h, q), ai, q, qinv), q);
-#else
-                    yi[r] = mred(cred(x[r] + h, q), ai, q, qinv);
-#endif
                     yd[r] = __ull2double_rn(yi[r]);
                 }
             }
@@ -3334,8 +3205,7 @@ __global__ void __launch_bounds__(128, HE_MODUP_WAVES) modup_fused_kernel(ModUpF
                 o[r] = (uint64_t)(acc >> 64) - mulhi64((uint64_t)acc * pinv, p) + p;  // (0, 2p)
             }
             if constexpr (LOGA > 0) {
-                [[maybe_unused]] const uint64_t *ts = A.tws_fwd + (size_t)mi * 32;
-                [[maybe_unused]] const uint64_t *twm = A.tw_fwd + (size_t)mi * A.N;
+                const uint64_t *twm = A.tw_fwd + (size_t)mi * A.N;
 #pragma unroll
                 for (int s = 0; s < LOGA; s++) {
                     const int d = 1 << (LOGA - 1 - s);
@@ -3344,12 +3214,7 @@ __global__ void __launch_bounds__(128, HE_MODUP_WAVES) modup_fused_kernel(ModUpF
                         if (r & d) continue;
                         const size_t ix = (size_t)((1 << s) + (r >> (LOGA - s)));
                         const uint64_t V = o[r + d];
-#if HE_MODUP_ASM
                         const uint64_t rr = mred_lazy_col_asm(V, ldc(twm, ix), p, pinv);  // [0, 2p)
-#else
-                        const uint64_t w = ldc(ts, 2 * ix), ws = ldc(ts, 2 * ix + 1);
-                        const uint64_t rr = V * w - mulhi64(V, ws) * p;  // [0, 2p)
-#endif
                         uint64_t Uu = o[r];
                         Uu = Uu >= twop ? Uu - twop : Uu;
                         o[r] = Uu + rr;
@@ -3420,8 +3285,7 @@ __global__ void __launch_bounds__(128, HE_MODUP_WAVES) modup_fused_kernel(ModUpF
                 }
             }
             if constexpr (LOGA > 0) {
-                [[maybe_unused]] const uint64_t *ts = A.tws_fwd + (size_t)mi * 32;
-                [[maybe_unused]] const uint64_t *twm = A.tw_fwd + (size_t)mi * A.N;
+                const uint64_t *twm = A.tw_fwd + (size_t)mi * A.N;
 #pragma unroll
                 for (int s = 0; s < LOGA; s++) {
                     const int d = 1 << (LOGA - 1 - s);
@@ -3430,12 +3294,7 @@ __global__ void __launch_bounds__(128, HE_MODUP_WAVES) modup_fused_kernel(ModUpF
                         if (r & d) continue;
                         const size_t ix = (size_t)((1 << s) + (r >> (LOGA - s)));
                         const uint64_t V = o[r + d];
-#if HE_MODUP_ASM
                         const uint64_t rr = mred_lazy_col_asm(V, ldc(twm, ix), p, pinv);
-#else
-                        const uint64_t w = ldc(ts, 2 * ix), ws = ldc(ts, 2 * ix + 1);
-                        const uint64_t rr = V * w - mulhi64(V, ws) * p;
-#endif
                         const uint64_t Uu = o[r];
                         o[r] = Uu + rr;
                         o[r + d] = Uu + twop - rr;
@@ -3559,9 +3418,8 @@ hipError_t launch_modup_fused(const RingDev &r, const ModUpDesc *descs_dev, int 
     const bool use_f64 = ((dst_classes & 2) && r.twd_fwd != nullptr) || !modup_int_light(nsrc, a);
     const int n2 = r.N >> a;
     // fewer than four workgroups per CU: split the destinations (up to four ways) instead of leaving the chip idle
-    static const int force_chunk = getenv("HERING_MODUP_NCHUNK") ? atoi(getenv("HERING_MODUP_NCHUNK")) : 0;
     const long wgs = (long)((n2 + 127) / 128) * ndesc * batch;
-    int nchunk = force_chunk > 0 ? force_chunk : (wgs >= 1024 ? 1 : (int)std::min<long>(4, 1024 / std::max<long>(wgs, 1)));
+    int nchunk = wgs >= 1024 ? 1 : (int)std::min<long>(4, 1024 / std::max<long>(wgs, 1));
     if (nchunk < 1) nchunk = 1;
     A.nchunk = nchunk;
     dim3 grid((unsigned)((n2 + 127) / 128), ndesc * nchunk, batch), block(128);
