@@ -57,6 +57,7 @@ type Evaluator struct {
 	evks   map[*rlwe.GadgetCiphertext]*EvaluationKey // keys are immutable once generated: uploaded once
 	decs   map[*uint64]*Decomposition             // twin of a BuffDecompQP slice, keyed like polys on its first Q row
 	index  map[uint64]*AutomorphismIndex
+	small  map[int]*Ring // device rings of smaller degree (ApplyEvaluationKey across ring degrees), by logN: created on first use
 	batch  int
 	parent *Evaluator // ShallowCopy: the evaluator that owns the shared maps (evks, index) and whose lock guards them
 }
@@ -67,7 +68,7 @@ func NewEvaluator(ctx *Context, params rlwe.ParameterProvider, evk rlwe.Evaluati
 	e := &Evaluator{params: p, ctx: ctx, keys: evk, batch: 1,
 		polys: map[*uint64]*Poly{}, hosts: map[*uint64]ring.Poly{}, dirty: map[*uint64]bool{}, used: map[*uint64]uint64{},
 		evks: map[*rlwe.GadgetCiphertext]*EvaluationKey{}, decs: map[*uint64]*Decomposition{},
-		index: map[uint64]*AutomorphismIndex{}}
+		index: map[uint64]*AutomorphismIndex{}, small: map[int]*Ring{}}
 	var err error
 	if e.RingQ, err = NewRing(ctx, p.RingQ()); err != nil {
 		return nil, err
@@ -114,7 +115,7 @@ func (e *Evaluator) ShallowCopy() *Evaluator {
 	}
 	c := &Evaluator{params: e.params, ctx: e.ctx, h: e.h, RingQ: e.RingQ, RingP: e.RingP, keys: e.keys, MaxTwins: e.MaxTwins, batch: e.batch,
 		polys: map[*uint64]*Poly{}, hosts: map[*uint64]ring.Poly{}, dirty: map[*uint64]bool{}, used: map[*uint64]uint64{},
-		evks: root.evks, decs: map[*uint64]*Decomposition{}, index: root.index, parent: root}
+		evks: root.evks, decs: map[*uint64]*Decomposition{}, index: root.index, small: root.small, parent: root}
 	return c
 }
 

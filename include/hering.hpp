@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "hering.h"
+#include "hering_ringswitch.h"
 
 namespace hering {
 
@@ -568,6 +569,13 @@ public:
         check(he_relinearize(h(), ctIn.Level(), ctIn.Value[0].h(), ctIn.Value[1].h(), ctIn.Value[2].h(), rlk.h(), opOut.Value.at(0).h(),
                              opOut.Value.at(1).h()));
     }
+    // evaluator_evaluationkey.go:36-106: ctIn and opOut of the evaluator's degree, or one of them of a smaller degree (NTT domain)
+    void ApplyEvaluationKey(const Ciphertext &ctIn, const EvaluationKey &evk, Ciphertext &opOut) const {
+        if (ctIn.Degree() != 1 || opOut.Degree() != 1)
+            throw std::invalid_argument("cannot ApplyEvaluationKey: input and output Ciphertext must be of degree 1");
+        const int level = ctIn.Level() < opOut.Level() ? ctIn.Level() : opOut.Level();
+        check(he_apply_evaluation_key(h(), level, ctIn.Value[0].h(), ctIn.Value[1].h(), evk.h(), opOut.Value[0].h(), opOut.Value[1].h()));
+    }
     void Automorphism(const Ciphertext &ctIn, uint64_t galEl, const EvaluationKey &gk, Ciphertext &opOut) const {  // evaluator_automorphism.go:13
         check(he_automorphism_ct(h(), ctIn.Level(), ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), galEl, gk.h(), opOut.Value.at(0).h(),
                                  opOut.Value.at(1).h()));
@@ -607,6 +615,25 @@ private:
                                     opOut.Value.at(1).h(), o2));
     }
 };
+
+// ring.MapSmallDimensionToLargerDimensionNTT (ring/operations.go:380)
+inline void MapSmallDimensionToLargerDimensionNTT(const Poly &polSmall, Poly &polLarge) {
+    check(he_map_small_to_large_ntt(polSmall.h(), polLarge.h(), polSmall.Level() < polLarge.Level() ? polSmall.Level() : polLarge.Level()));
+}
+// rlwe.SwitchCiphertextRingDegreeNTT (core/rlwe/element.go:250): ringQLargeDim is required for large -> small (nullptr otherwise)
+inline void SwitchCiphertextRingDegreeNTT(const Ciphertext &ctIn, const Ring *ringQLargeDim, Ciphertext &opOut) {
+    for (size_t i = 0; i < opOut.Value.size(); i++) {
+        const Poly &a = ctIn.Value.at(i), &b = opOut.Value[i];
+        check(he_switch_ring_degree_ntt(ringQLargeDim ? ringQLargeDim->h() : 0, a.Level() < b.Level() ? a.Level() : b.Level(), a.h(), b.h()));
+    }
+}
+// rlwe.SwitchCiphertextRingDegree (core/rlwe/element.go:293), coefficient domain
+inline void SwitchCiphertextRingDegree(const Ciphertext &ctIn, Ciphertext &opOut) {
+    for (size_t i = 0; i < opOut.Value.size(); i++) {
+        const Poly &a = ctIn.Value.at(i), &b = opOut.Value[i];
+        check(he_switch_ring_degree(a.Level() < b.Level() ? a.Level() : b.Level(), a.h(), b.h()));
+    }
+}
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

@@ -9,7 +9,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HERING_LIB: A/B-test another build
 _INC = os.path.join(os.path.dirname(_HERE), "include")
-_HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h")]
+_HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -110,6 +110,8 @@ def _declare(L):
         "he_moddown": [H, i, i, H, H, H, H, H, H],
         "he_gadget_product": [H, i, H, H, H, H], "he_gadget_product_hoisted": [H, i, H, H, H, H],
         "he_relinearize": [H, i, H, H, H, H, H, H],
+        "he_map_small_to_large_ntt": [H, H, i], "he_switch_ring_degree_ntt": [H, i, H, H], "he_switch_ring_degree": [i, H, H],
+        "he_apply_evaluation_key": [H, i, H, H, H, H, H],
         "he_automorphism_ct": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted_lazy": [H, i, H, H, C.c_uint64, H, H, H, H, H],
@@ -177,6 +179,8 @@ _TRACE_FNS = {
     "he_automorphism_hoisted_lazy": (44, "hihhihhhhh"), "he_centered_lift": (45, "hihiihih"), "he_decomp_fill": (46, "hiihh"),
     "he_lintrans_mul_sum": (47, "hiiiHHHHHHHihhhh"), "he_ckks_mul_relin": (48, "hihhhhhhhh"), "he_bgv_mul_relin": (49, "hiihhhhhhhh"),
     "he_lintrans_giant_step": (50, "hihhihhhhhhi"),
+    "he_map_small_to_large_ntt": (51, "hhi"), "he_switch_ring_degree_ntt": (52, "hihh"), "he_switch_ring_degree": (53, "ihh"),
+    "he_apply_evaluation_key": (54, "hihhhhh"),
 }
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments)
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),

@@ -37,6 +37,7 @@
 
 #include "../../include/hering.h"
 #include "../../include/hering_debug.h"
+#include "../../include/hering_ringswitch.h"
 #include "host_math.h"
 #include "kernels.h"
 
@@ -92,7 +93,8 @@ enum CoOp {
     CO_MUL_RELIN = 0, CO_GADGET_PRODUCT, CO_RELINEARIZE, CO_AUTOMORPHISM,
     CO_NTT, CO_EW, CO_EW_DOUBLE, CO_SHIFT, CO_RESCALE, CO_GATHER, CO_AUTO_COEFF, CO_MODUP, CO_MODDOWN_BE,
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
-    CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP
+    CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
+    CO_RING_SWITCH, CO_APPLY_EVK
 };
 struct CoReq {
     // ---- key: requests are batched together only when all of this matches
@@ -4567,6 +4569,197 @@ int he_ckks_mul_relin(he_handle ev, int level, he_handle a0, he_handle a1, he_ha
 }
 int he_bgv_mul_relin(he_handle ev, int level, uint64_t t, he_handle a0, he_handle a1, he_handle b0, he_handle b1, he_handle rlk, he_handle o0, he_handle o1, he_handle o2) {
     return mul_relin_common(ev, level, true, t, a0, a1, b0, b1, rlk, o0, o1, o2, "he_bgv_mul_relin");
+}
+
+// ---------------------------------------------------------------------------------------
+// ring-degree switching and ApplyEvaluationKey (include/hering_ringswitch.h)
+// ---------------------------------------------------------------------------------------
+// kinds of CO_RING_SWITCH (par[0])
+enum { RS_FOLD_NTT = 0, RS_REPLICATE_NTT, RS_STRIDE_DOWN, RS_STRIDE_UP };
+// a pair of polynomials of one context and batch, of degrees (n, n << log_gap) in either order, n >= 16, limbs 0..level in both
+static int ring_switch_shape(const Poly &a, const Poly &b, int level, int *log_gap, const char *who) {
+    if (a.ctx != b.ctx) return fail(HE_EINVAL, "%s: the polynomials belong to different contexts", who);
+    if (a.batch != b.batch) return fail(HE_EINVAL, "%s: batch mismatch (%d, %d)", who, a.batch, b.batch);
+    const int lo = std::min(a.N, b.N), hi = std::max(a.N, b.N);
+    if (lo < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, lo);
+    int lg = 0;
+    while ((lo << lg) < hi) lg++;
+    if ((lo << lg) != hi) return fail(HE_EINVAL, "%s: degrees %d and %d are not a power-of-two ratio", who, lo, hi);
+    if (level < 0 || level >= kMaxLimbs || a.nlimbs < level + 1 || b.nlimbs < level + 1)
+        return fail(HE_EINVAL, "%s: level %d out of range for polynomials of %d and %d limbs", who, level, a.nlimbs, b.nlimbs);
+    *log_gap = lg;
+    return HE_OK;
+}
+// MForm(gap^-1 mod q_i) for limbs 0..level of a ring: the fold's per-limb constant
+static std::vector<uint64_t> fold_constants(const std::vector<uint64_t> &moduli, int level, int log_gap) {
+    std::vector<uint64_t> g((size_t)level + 1);
+    for (int i = 0; i <= level; i++) g[i] = to_mont(invmod((1ull << log_gap) % moduli[i], moduli[i]), moduli[i]);
+    return g;
+}
+// the launch of one ring-degree map over B entries (v[0] in, v[1] out); the caller holds the context
+static int ring_switch_launch(Ctx &c, const Ring *large, int kind, int level, int log_gap, int n_small, const std::vector<uint64_t> &gapinv,
+                              const View *v, int B) {
+    const double L = level + 1, NL = (double)((size_t)n_small << log_gap), gap = (double)(1 << log_gap);
+    RingSwitchIO io;
+    io.in = v[0]; io.out = v[1];
+    const LimbTab tab = ident_tab(level + 1);
+    if (kind == RS_FOLD_NTT) {
+        c.acct(L * (1.0 + 1.0 / gap), 0, B, (int)NL);
+        Valu V(large->logN - log_gap);
+        V.mul(false, L);  // (one integer Montgomery product per output word, whatever the modulus class)
+        V.into(c, B);
+        HIP_TRY(launch_ring_degree_fold_ntt(large->dev, tab, gapinv.data(), io, n_small, log_gap, B, c.stream));
+    } else if (kind == RS_REPLICATE_NTT) {
+        c.acct(L * (1.0 + 1.0 / gap), 0, B, (int)NL);
+        HIP_TRY(launch_ring_degree_replicate_ntt(tab, io, n_small, log_gap, B, c.stream));
+    } else {
+        c.acct(2.0 * L / gap, 0, B, (int)NL);
+        HIP_TRY(launch_ring_degree_stride(tab, io, n_small, log_gap, kind == RS_STRIDE_UP, B, c.stream));
+    }
+    return HE_OK;
+}
+// files one ring-degree map of in -> out (distinct handles of different degree) on the context's queue, served one by one
+static int ring_switch_file(const std::shared_ptr<Ring> &large, int kind, int level, int log_gap, const std::shared_ptr<Poly> &in,
+                            const std::shared_ptr<Poly> &out) {
+    const std::shared_ptr<Ctx> ctx = in->ctx;
+    const int n_small = std::min(in->N, out->N);
+    std::vector<uint64_t> gapinv;
+    if (kind == RS_FOLD_NTT) gapinv = fold_constants(large->moduli, level, log_gap);
+    CoReq q;
+    q.op = CO_RING_SWITCH; q.obj = large ? (const void *)large.get() : (const void *)ctx.get();
+    q.par[0] = kind; q.par[1] = level; q.par[2] = log_gap; q.par[3] = n_small;
+    q.ops = {in->view(), out->view()};
+    q.keep = {in, out};
+    if (large) q.keep.push_back(large);
+    q.run = [ctx, large, kind, level, log_gap, n_small, gapinv](const View *v, int B) -> int {
+        return ring_switch_launch(*ctx, large.get(), kind, level, log_gap, n_small, gapinv, v, B);
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (the maps take no entry tables)
+    return co_dispatch(*ctx, in->batch, q);
+}
+int he_map_small_to_large_ntt(he_handle hsmall, he_handle hlarge, int level) {
+    GET(ps, Poly, hsmall, T_POLY);
+    GET(pl, Poly, hlarge, T_POLY);
+    int lg = 0;
+    TRY(ring_switch_shape(*ps, *pl, level, &lg, "he_map_small_to_large_ntt"));
+    if (ps->N > pl->N) return fail(HE_EINVAL, "he_map_small_to_large_ntt: polSmall (degree %d) is larger than polLarge (%d)", ps->N, pl->N);
+    if (lg == 0) return he_poly_copy(hlarge, hsmall, level);
+    return ring_switch_file(nullptr, RS_REPLICATE_NTT, level, lg, ps, pl);
+}
+int he_switch_ring_degree_ntt(he_handle hring, int level, he_handle hin, he_handle hout) {
+    GET(in, Poly, hin, T_POLY);
+    GET(out, Poly, hout, T_POLY);
+    int lg = 0;
+    TRY(ring_switch_shape(*in, *out, level, &lg, "he_switch_ring_degree_ntt"));
+    std::shared_ptr<Ring> r;
+    if (hring || in->N > out->N) {
+        r = get<Ring>(hring, T_RING);
+        if (!r) return fail(HE_EHANDLE, "he_switch_ring_degree_ntt: bad ring handle %llu (required for large -> small)", (unsigned long long)hring);
+        if (r->ctx != in->ctx) return fail(HE_EINVAL, "he_switch_ring_degree_ntt: the ring belongs to another context");
+        if (r->N != std::max(in->N, out->N)) return fail(HE_EINVAL, "he_switch_ring_degree_ntt: ring degree %d != the large degree %d", r->N, std::max(in->N, out->N));
+        if (level >= r->nmod()) return fail(HE_EINVAL, "he_switch_ring_degree_ntt: level %d out of range [0,%d]", level, r->nmod() - 1);
+    }
+    if (lg == 0) return he_poly_copy(hout, hin, level);
+    if (in->N > out->N) return ring_switch_file(r, RS_FOLD_NTT, level, lg, in, out);
+    return ring_switch_file(nullptr, RS_REPLICATE_NTT, level, lg, in, out);
+}
+int he_switch_ring_degree(int level, he_handle hin, he_handle hout) {
+    GET(in, Poly, hin, T_POLY);
+    GET(out, Poly, hout, T_POLY);
+    int lg = 0;
+    TRY(ring_switch_shape(*in, *out, level, &lg, "he_switch_ring_degree"));
+    if (lg == 0) return he_poly_copy(hout, hin, level);
+    return ring_switch_file(nullptr, in->N > out->N ? RS_STRIDE_DOWN : RS_STRIDE_UP, level, lg, in, out);
+}
+
+// ApplyEvaluationKey (core/rlwe/evaluator_evaluationkey.go:36-106): out0 = in0 + GadgetProduct(in1)_0, out1 = GadgetProduct(in1)_1
+// (applyEvaluationKey, :98-106) as ONE key switch with the Add in its ModDown epilogue; the degree-changing forms add the ring map
+// of the reference after (large -> small: the fold of both components, one launch over 2B entries) or before it (small -> large:
+// the replication of both components into scratch at N, then the key switch with the replicated in0 as the addend).
+enum { AEK_SAME = 0, AEK_DOWN, AEK_UP };
+int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hk, he_handle hout0, he_handle hout1) {
+    static const char *who = "he_apply_evaluation_key";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(in0, Poly, hin0, T_POLY);
+    GET(in1, Poly, hin1, T_POLY);
+    GET(k, Evk, hk, T_EVK);
+    GET(out0, Poly, hout0, T_POLY);
+    GET(out1, Poly, hout1, T_POLY);
+    BasisExtender &be = *ev->be;
+    TRY(check_key(*ev, *k, level, who));
+    const int N = be.Q->N, Nin = in0->N, Nout = out0->N;
+    if (in1->N != Nin || out1->N != Nout) return fail(HE_EINVAL, "%s: the two components of a ciphertext differ in degree", who);
+    // the reference's errors (:51-53, :68-70): the large side must be the evaluator's degree
+    if (Nin < Nout && Nout != N) return fail(HE_EINVAL, "%s: opOut ring degree does not match evaluator params ring degree", who);
+    if (Nin > Nout && Nin != N) return fail(HE_EINVAL, "%s: ctIn ring degree does not match evaluator params ring degree", who);
+    // same degree: both sides are the evaluator's degree (the key switch runs at N over every operand)
+    if (Nin == Nout && Nin != N) return fail(HE_EINVAL, "%s: ciphertext ring degree %d does not match evaluator params ring degree %d", who, Nin, N);
+    const int form = Nin == Nout ? AEK_SAME : (Nin > Nout ? AEK_DOWN : AEK_UP);
+    const int B = in0->batch;
+    for (Poly *p : {in0.get(), in1.get(), out0.get(), out1.get()}) {
+        if (p->batch != B) return fail(HE_EINVAL, "%s: batch mismatch", who);
+        if (p->N == N) TRY(check_be_poly(*p, be, level + 1, who));
+    }
+    int lg = 0;
+    if (form != AEK_SAME) {
+        TRY(ring_switch_shape(*in0, *out0, level, &lg, who));
+        TRY(ring_switch_shape(*in1, *out1, level, &lg, who));
+    }
+    // (handles of different degree never coincide; at equal degree any output may be any input, out0 != out1)
+    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}},
+                        {{2, 0}, {2, 1}, {3, 0}, {3, 1}}));
+    // as in he_relinearize: an output that is the key switch's operand (in1) or the OTHER component's addend (in0 == out1) cannot be
+    // batched; the crossed case stages the addend first (component 1's epilogue would overwrite it before component 0 reads it)
+    const bool alias = form == AEK_SAME && (in1->d == out0->d || in1->d == out1->d || in0->d == out1->d);
+    const bool cross = form == AEK_SAME && in0->d == out1->d;
+    const int n_small = std::min(Nin, Nout);
+    const std::vector<uint64_t> gapinv = form == AEK_DOWN ? fold_constants(be.Q->moduli, level, lg) : std::vector<uint64_t>();
+    CoReq q;
+    q.op = CO_APPLY_EVK; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = form; q.par[2] = lg;
+    q.ops = {in0->view(), in1->view(), out0->view(), out1->view()};
+    q.keep = {ev, k, in0, in1, out0, out1};
+    q.run = [ev, k, level, form, lg, n_small, cross, gapinv](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        const int N = be.Q->N, levelP = k->nPk - 1;
+        const int beta = k->pw2 ? k->prefix[level + 1] : base_rns_size(level, levelP);
+        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
+        be.ctx->acct(4.0 * (level + 1), key_limbs(*k, level), B, N);  // the key switch: 2 L in, 2 L out, key
+        { Valu V(be.Q->logN); valu_gadget_product(V, be, level, levelP, beta, true); V.into(*be.ctx, B); }
+        const size_t ks = ks_scratch_words(be, level, levelP, B, true, k.get());
+        hipStream_t st = be.ctx->stream;
+        if (form == AEK_SAME) {
+            TRY(be.ctx->arena_reserve(ks + (cross ? wQ + 2 : 0)));
+            if (cross) {  // (served one by one: plain views)
+                View a0{be.ctx->arena_take(wQ), sQ};
+                HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, st));
+                return gadget_product_core(*ev, level, &v[1], nullptr, *k, v[2], v[3], B, &a0, nullptr);
+            }
+            return gadget_product_core(*ev, level, &v[1], nullptr, *k, v[2], v[3], B, &v[0], nullptr);
+        }
+        // both components at degree N in scratch, [2][B] entries: the key switch's result (down) or the replicated input (up)
+        TRY(be.ctx->arena_reserve(ks + 2 * wQ + 2));
+        uint64_t *t = be.ctx->arena_take(2 * wQ);
+        const View t0{t, sQ}, t1{t + wQ, sQ};
+        RingSwitchIO io;
+        io.zsplit = B;
+        if (form == AEK_DOWN) {
+            TRY(gadget_product_core(*ev, level, &v[1], nullptr, *k, t0, t1, B, &v[0], nullptr));
+            io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3];
+            be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, N);
+            { Valu V(be.Q->logN - lg); V.mul(false, 2.0 * (level + 1)); V.into(*be.ctx, B); }  // (integer products on every limb)
+            HIP_TRY(launch_ring_degree_fold_ntt(be.Q->dev, ident_tab(level + 1), gapinv.data(), io, n_small, lg, 2 * B, st));
+            return HE_OK;
+        }
+        io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1;
+        be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, N);
+        HIP_TRY(launch_ring_degree_replicate_ntt(ident_tab(level + 1), io, n_small, lg, 2 * B, st));
+        return gadget_product_core(*ev, level, &t1, nullptr, *k, v[2], v[3], B, &t0, nullptr);
+    };
+    q.tables_ok = [ev, k, level, form, alias](bool *ok) -> int {
+        *ok = false;
+        return (form != AEK_SAME || alias) ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
+    };
+    return co_dispatch(*be.ctx, B, q);
 }
 
 // ---------------------------------------------------------------------------------------

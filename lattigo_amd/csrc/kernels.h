@@ -359,6 +359,24 @@ bool ntt_mac_giant_supported(int logN);
 hipError_t launch_key_to_f64(const RingDev &r, const uint64_t *key, double *keyd, int nblocks, const uint8_t *limb_mod_host,
                              int nlimbs, hipStream_t s);
 
+// ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
+// One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
+// ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
+// one n_small << log_gap (log_gap >= 1).  Limb y of the launch reads limb tab.in_limb[y], writes tab.out_limb[y].  No entry tables.
+struct RingSwitchIO {
+    View in, out;
+    View in2{nullptr, 0}, out2{nullptr, 0};
+    int zsplit = -1;
+};
+// SwitchCiphertextRingDegreeNTT, large -> small: out[j] = gap^-1 sum_{s<gap} in[j gap + s] mod q[tab.mod[y]] (the large ring's
+// modulus records), canonical; gapinv_mont[y] = MForm(gap^-1) (host array, tab.n words).  Inputs below 2^62.
+hipError_t launch_ring_degree_fold_ntt(const RingDev &large, const LimbTab &tab, const uint64_t *gapinv_mont, RingSwitchIO io,
+                                       int n_small, int log_gap, int batch, hipStream_t s);
+// MapSmallDimensionToLargerDimensionNTT: out[j gap + s] = in[j]
+hipError_t launch_ring_degree_replicate_ntt(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, int batch, hipStream_t s);
+// SwitchCiphertextRingDegree: down (up = false) out[w] = in[w gap]; up out[w gap] = in[w], the other words of out untouched
+hipError_t launch_ring_degree_stride(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, bool up, int batch, hipStream_t s);
+
 // ---- ciphertext tensor product (schemes/ckks/evaluator.go:807-820, schemes/bgv/evaluator.go:634-647)
 // c0 = MRed(MRed(a0,s),b0), c2 = MRed(MRed(a1,s),b1), c1 = CRed(MRed(MRed(a0,s),b1) + MRed(MRed(a1,s),b0))
 // with the per-limb scalar s = 2^128 mod q (CKKS: MForm) or t*2^128 mod q (BGV: tMontgomery).
@@ -369,7 +387,7 @@ hipError_t launch_tensor(const RingDev &r, const LimbTab &tab, const uint64_t *s
 enum KernelId {
     K_NTT_COLS_FWD = 0, K_NTT_ROWS_FWD, K_NTT_ROWS_INV, K_NTT_COLS_INV, K_EW, K_GATHER, K_AUTO_COEFF, K_INDEX,
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
-    K_NTT_MAC_F64, K_DIAG_MAC, K_COUNT
+    K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -71,7 +71,8 @@ const char *kernel_name(int id) {
     static const char *names[K_COUNT] = {"ntt_cols_fwd", "ntt_rows_fwd", "ntt_rows_inv", "ntt_cols_inv", "ew", "gather",
                                          "automorphism_coeff", "build_index", "modup", "center_copy", "ks_inner",
                                          "tensor", "modmul_probe", "ci_fold", "mask_spread", "ntt_rows_fwd_f64",
-                                         "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac"};
+                                         "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
+                                         "ring_degree_replicate_ntt", "ring_degree_stride"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -2662,6 +2663,147 @@ hipError_t launch_gather(const RingDev &r, const LimbTab &tab, View in, const ui
     ProfScope ps(K_GATHER, s, (then_add ? 3.0 : 2.0) * tab.n * batch * (double)r.N * 8.0);
     if (then_add) hipLaunchKernelGGL((gather_kernel<true>), grid, block, 0, s, A);
     else hipLaunchKernelGGL((gather_kernel<false>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380)
+// ------------------------------------------------------------------------------------
+struct RingSwitchArgs {
+    const uint64_t *in, *in2;
+    uint64_t *out, *out2;
+    size_t in_bs, in2_bs, out_bs, out2_bs;
+    int zsplit;   // entries z >= zsplit read in2 / write out2 (entry z - zsplit)
+    int n_small;  // the small degree: outputs of the fold, inputs of the replication
+    int log_gap;
+    const ModConst *mc;
+    uint8_t in_limb[kMaxLimbs], out_limb[kMaxLimbs], mod[kMaxLimbs];
+    uint64_t s[kMaxLimbs];  // fold: MForm(gap^-1) per launch limb
+};
+__device__ __forceinline__ const uint64_t *rs_in(const RingSwitchArgs &A, size_t z) {
+    return z < (size_t)A.zsplit ? A.in + z * A.in_bs : A.in2 + (z - A.zsplit) * A.in2_bs;
+}
+__device__ __forceinline__ uint64_t *rs_out(const RingSwitchArgs &A, size_t z) {
+    return z < (size_t)A.zsplit ? A.out + z * A.out_bs : A.out2 + (z - A.zsplit) * A.out2_bs;
+}
+// SwitchCiphertextRingDegreeNTT, large -> small, in one streaming pass: INTT at N, keeping every gap-th coefficient and the NTT
+// at n = N / gap (element.go:260-279) compose to out[j] = gap^-1 sum_{s<gap} in[j gap + s] mod q -- the small ring's forward
+// tables are a prefix of the large ring's, for both ring types.  Two outputs per thread, read as 16-byte vectors.  GAP = 2, 4:
+// the plain 64-bit sum (inputs below 2^62) goes straight into one Montgomery product with MForm(gap^-1) (exact for any 64-bit
+// left operand: hi(x y) < q); GAP = 0, any larger power of two: partial sums of four words are reduced (BRedAdd) and accumulated
+// modulo q.  Canonical output.
+template <int GAP>
+__global__ void __launch_bounds__(256) ring_fold_kernel(RingSwitchArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.n_small) return;
+    const int y = blockIdx.y;
+    const size_t z = blockIdx.z;
+    const ModConst &m = A.mc[A.mod[y]];
+    const uint64_t q = m.q, qinv = m.qinv, gi = A.s[y];
+    const uint64_t *in = rs_in(A, z) + ((size_t)A.in_limb[y] * A.n_small << A.log_gap) + ((size_t)j << A.log_gap);
+    uint64_t *out = rs_out(A, z) + (size_t)A.out_limb[y] * A.n_small + j;
+    uint64_t s0, s1;
+    if constexpr (GAP == 2) {
+        const ulonglong2 a = ldnt2(in), b = ldnt2(in + 2);
+        s0 = a.x + a.y;
+        s1 = b.x + b.y;
+    } else if constexpr (GAP == 4) {
+        const ulonglong2 a = ldnt2(in), b = ldnt2(in + 2), c = ldnt2(in + 4), d = ldnt2(in + 6);
+        s0 = (a.x + a.y) + (b.x + b.y);
+        s1 = (c.x + c.y) + (d.x + d.y);
+    } else {
+        const int gap = 1 << A.log_gap;
+        uint64_t acc[2] = {0, 0};
+        for (int o = 0; o < 2; o++) {
+            const uint64_t *p = in + ((size_t)o << A.log_gap);
+            for (int k = 0; k < gap; k += 4) {
+                const ulonglong2 a = ldnt2(p + k), b = ldnt2(p + k + 2);
+                acc[o] = cred(acc[o] + bred_add((a.x + a.y) + (b.x + b.y), q, m.brc0), q);
+            }
+        }
+        s0 = acc[0];
+        s1 = acc[1];
+    }
+    ulonglong2 o;
+    o.x = mred(s0, gi, q, qinv);
+    o.y = mred(s1, gi, q, qinv);
+    *reinterpret_cast<ulonglong2 *>(out) = o;
+}
+// MapSmallDimensionToLargerDimensionNTT: out[j gap + s] = in[j].  Four output words (two 16-byte stores) per thread.
+__global__ void __launch_bounds__(256) ring_replicate_kernel(RingSwitchArgs A) {
+    const size_t NL = (size_t)A.n_small << A.log_gap;
+    const size_t w = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (w >= NL) return;
+    const int y = blockIdx.y;
+    const size_t z = blockIdx.z;
+    const uint64_t *in = rs_in(A, z) + (size_t)A.in_limb[y] * A.n_small;
+    uint64_t *out = rs_out(A, z) + (size_t)A.out_limb[y] * NL + w;
+    ulonglong2 o0, o1;
+    if (A.log_gap == 1) {
+        const ulonglong2 v = ldnt2(in + (w >> 1));
+        o0 = make_ulonglong2(v.x, v.x);
+        o1 = make_ulonglong2(v.y, v.y);
+    } else {
+        const uint64_t v = ldnt(in + (w >> A.log_gap));
+        o0 = o1 = make_ulonglong2(v, v);
+    }
+    reinterpret_cast<ulonglong2 *>(out)[0] = o0;
+    reinterpret_cast<ulonglong2 *>(out)[1] = o1;
+}
+// SwitchCiphertextRingDegree (coefficient domain, element.go:293-313): down out[w] = in[w gap]; up out[w gap] = in[w], the
+// other words of out untouched (the reference writes only those positions)
+template <bool UP>
+__global__ void __launch_bounds__(256) ring_stride_kernel(RingSwitchArgs A) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= (size_t)A.n_small) return;
+    const size_t NL = (size_t)A.n_small << A.log_gap;
+    const int y = blockIdx.y;
+    const size_t z = blockIdx.z;
+    const uint64_t *in = rs_in(A, z) + (size_t)A.in_limb[y] * (UP ? (size_t)A.n_small : NL);
+    uint64_t *out = rs_out(A, z) + (size_t)A.out_limb[y] * (UP ? NL : (size_t)A.n_small);
+    if (UP) out[w << A.log_gap] = ldnt(in + w);
+    else out[w] = ldnt(in + (w << A.log_gap));
+}
+static bool rs_args(RingSwitchArgs &A, const LimbTab &tab, const RingSwitchIO &io, int n_small, int log_gap, int batch) {
+    if (tab.n <= 0 || tab.n > kMaxLimbs || batch <= 0 || n_small < 16 || log_gap < 1 || log_gap > kMaxLogN) return false;
+    if (!no_tab({io.in, io.out, io.in2, io.out2})) return false;
+    A.in = io.in.p; A.out = io.out.p; A.in_bs = io.in.bstride; A.out_bs = io.out.bstride;
+    A.zsplit = io.zsplit >= 0 && io.zsplit < batch ? io.zsplit : batch;
+    A.in2 = io.in2.p ? io.in2.p : io.in.p; A.in2_bs = io.in2.p ? io.in2.bstride : io.in.bstride;
+    A.out2 = io.out2.p ? io.out2.p : io.out.p; A.out2_bs = io.out2.p ? io.out2.bstride : io.out.bstride;
+    A.n_small = n_small; A.log_gap = log_gap;
+    for (int i = 0; i < tab.n; i++) { A.in_limb[i] = tab.in_limb[i]; A.out_limb[i] = tab.out_limb[i]; A.mod[i] = tab.mod[i]; }
+    return true;
+}
+hipError_t launch_ring_degree_fold_ntt(const RingDev &large, const LimbTab &tab, const uint64_t *gapinv_mont, RingSwitchIO io,
+                                       int n_small, int log_gap, int batch, hipStream_t s) {
+    RingSwitchArgs A{};
+    if (!rs_args(A, tab, io, n_small, log_gap, batch) || ((size_t)n_small << log_gap) != (size_t)large.N) return hipErrorInvalidValue;
+    A.mc = large.mc;
+    for (int i = 0; i < tab.n; i++) A.s[i] = gapinv_mont[i];
+    dim3 grid((unsigned)((n_small / 2 + 255) / 256), tab.n, batch), block(256);
+    ProfScope ps(K_RING_FOLD, s, ((double)large.N + n_small) * tab.n * batch * 8.0);
+    if (log_gap == 1) hipLaunchKernelGGL((ring_fold_kernel<2>), grid, block, 0, s, A);
+    else if (log_gap == 2) hipLaunchKernelGGL((ring_fold_kernel<4>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((ring_fold_kernel<0>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_ring_degree_replicate_ntt(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, int batch, hipStream_t s) {
+    RingSwitchArgs A{};
+    if (!rs_args(A, tab, io, n_small, log_gap, batch)) return hipErrorInvalidValue;
+    const size_t NL = (size_t)n_small << log_gap;
+    dim3 grid((unsigned)((NL / 4 + 255) / 256), tab.n, batch), block(256);
+    ProfScope ps(K_RING_REPLICATE, s, ((double)NL + n_small) * tab.n * batch * 8.0);
+    hipLaunchKernelGGL(ring_replicate_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_ring_degree_stride(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, bool up, int batch, hipStream_t s) {
+    RingSwitchArgs A{};
+    if (!rs_args(A, tab, io, n_small, log_gap, batch)) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((n_small + 255) / 256), tab.n, batch), block(256);
+    ProfScope ps(K_RING_STRIDE, s, 2.0 * n_small * tab.n * batch * 8.0);
+    if (up) hipLaunchKernelGGL((ring_stride_kernel<true>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((ring_stride_kernel<false>), grid, block, 0, s, A);
     return hipGetLastError();
 }
 

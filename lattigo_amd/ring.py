@@ -286,6 +286,12 @@ class Poly:
         check(load().he_poly_zero(self.h))
 
 
+def MapSmallDimensionToLargerDimensionNTT(polSmall: Poly, polLarge: Poly):
+    """ring.MapSmallDimensionToLargerDimensionNTT (ring/operations.go:380): polLarge[j * gap + s] = polSmall[j] on the limbs
+    both polynomials have (include/hering_ringswitch.h)."""
+    check(load().he_map_small_to_large_ntt(polSmall.h, polLarge.h, min(polSmall.Level(), polLarge.Level())))
+
+
 class Ring:
     """ring.Ring (ring/ring.go:71), standard type.  ``AtLevel`` returns a view sharing tables."""
 

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import H, check, load, u64p
+from ._lib import H, HeringError, check, load, u64p
 from .ring import BasisExtender, Poly, Ring, _p
 
 
@@ -238,6 +238,32 @@ class Evaluator:
     def GadgetProductHoisted(self, levelQ, decomp: Decomposition, evk: EvaluationKey, ct):
         check(load().he_gadget_product_hoisted(self.h, levelQ, decomp.h, evk.h, ct[0].h, ct[1].h))
 
+    # Evaluator.ApplyEvaluationKey (core/rlwe/evaluator_evaluationkey.go:36-106): ctIn and opOut of the evaluator's degree, or
+    # one of them of a smaller degree n (the key then switches between the secret of degree N and the small secret mapped up);
+    # isNTT = ctIn.IsNTT.  The coefficient-domain form is composed here from the NTT-domain call, as GadgetProduct(isNTT=False).
+    def ApplyEvaluationKey(self, level, ctIn, evk: EvaluationKey, opOut, isNTT: bool = True):
+        if isNTT:
+            check(load().he_apply_evaluation_key(self.h, level, ctIn[0].h, ctIn[1].h, evk.h, opOut[0].h, opOut[1].h))
+            return
+        N, NIn, NOut = self.ringQ.N, ctIn[0].N, opOut[0].N
+        if max(NIn, NOut) != N:  # (:51-53, :68-70; the same degree must be the evaluator's as well)
+            raise HeringError(-1, "cannot ApplyEvaluationKey: the large side's ring degree does not match evaluator params ring degree")
+        level = min(level, evk.LevelQ())
+        rQ = self.ringQ.AtLevel(level)
+        B = ctIn[0].batch
+        if NIn < NOut:  # SwitchCiphertextRingDegree into opOut (:56-58), then the key switch on opOut in place
+            SwitchCiphertextRingDegree(ctIn, opOut)
+            ctIn = opOut
+        t = [Poly(self.ringQ, level + 1, B, zero=False) for _ in range(2)]
+        for c, d in zip(ctIn, t):
+            rQ.NTT(c, d)
+        u = opOut if NIn <= NOut else [Poly(self.ringQ, level + 1, B, zero=False) for _ in range(2)]
+        check(load().he_apply_evaluation_key(self.h, level, t[0].h, t[1].h, evk.h, u[0].h, u[1].h))
+        for c in u:
+            rQ.INTT(c, c)
+        if NIn > NOut:  # SwitchCiphertextRingDegree of the key-switched ciphertext (:85-87)
+            SwitchCiphertextRingDegree(u, opOut)
+
     # Evaluator.Relinearize (core/rlwe/evaluator_evaluationkey.go:117)
     def Relinearize(self, level, ctIn, rlk: EvaluationKey, opOut):
         check(load().he_relinearize(self.h, level, ctIn[0].h, ctIn[1].h, ctIn[2].h, rlk.h, opOut[0].h, opOut[1].h))
@@ -287,6 +313,20 @@ class Evaluator:
 # device-resident operators above, exactly as the reference's own code sits on rlwe.EvaluatorProvider.
 # ----------------------------------------------------------------------------------------------------
 GaloisGen = 5  # core/rlwe/params.go:33
+
+
+# rlwe.SwitchCiphertextRingDegreeNTT (core/rlwe/element.go:250): ctIn, opOut lists of Poly (rlwe.Element.Value); ringQLargeDim
+# is required for large -> small (its moduli are those of the small polynomials' limbs) and may be None otherwise
+def SwitchCiphertextRingDegreeNTT(ctIn, ringQLargeDim: Ring | None, opOut):
+    for a, b in zip(ctIn, opOut):
+        check(load().he_switch_ring_degree_ntt(ringQLargeDim.h if ringQLargeDim is not None else 0, min(a.Level(), b.Level()), a.h, b.h))
+
+
+# rlwe.SwitchCiphertextRingDegree (core/rlwe/element.go:293), coefficient domain: up leaves the words of opOut between the
+# multiples of gap untouched, as the reference
+def SwitchCiphertextRingDegree(ctIn, opOut):
+    for a, b in zip(ctIn, opOut):
+        check(load().he_switch_ring_degree(min(a.Level(), b.Level()), a.h, b.h))
 
 
 def GaloisElement(nth_root: int, k: int) -> int:
