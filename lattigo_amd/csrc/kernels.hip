@@ -1328,7 +1328,10 @@ struct NttMacDmaArgs {
 // out_c = [w_c +] (NTT(ext_c) - acc_c) s is formed against the accumulator still in registers -- the Q accumulators are never
 // written, and the separate forward-row + epilogue launch (HBM-bound, next to this latency-bound kernel) is gone.
 // TEN (with EPI): the epilogue forms the tensor term (NttMacEpilogue::tensor) -- its own instantiation since round 6: with both
-// epilogue forms in one kernel the 4096-row variant was 75 KiB of code for a 64 KiB instruction cache shared by two CUs
+// epilogue forms in one kernel the 4096-row variant was 75 KiB of code for a 64 KiB instruction cache shared by two CUs.  At
+// 4096-rows this form transforms the two extension rows as one pair per wave (a second, independent transform to work on while
+// the first one waits) and runs the two finishes back to back, each of a0, b0, a1, b1 read once; every other form takes the
+// extension rows one after the other.
 template <int LOGB, bool QF64, bool EPI = false, bool SCAT = false, bool TEN = false>
 __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(NttMacDmaArgs AA) {
     static_assert(LOGB == 12 || LOGB == 13, "production row sizes only");
@@ -1416,27 +1419,19 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
         bool more = false;
         // forward row transform of x (element k T + tau in, the last round's order out), with the prefetch of `nsrc` and -- digits
         // only -- the two key rows issued where they hide best
-        auto transform = [&](int nk, double (&x)[16], unsigned tau, unsigned lane, const uint64_t *nsrc, const double *k0p,
-                             const double *k1p, double (&kk0)[16], double (&kk1)[16], int early = 0) {
-            // nk (block-uniform): rows of sixteen words fetched on the way -- 2 (k0p and k1p), 1 (k0p), 0
-            // round-2 twiddles first, then the DMA: ordinary loads issued after it could only return after it
-            double t2[15];
-            rows_tw16_f64(t2, cur.tw, cur.rowtw, 8, tau >> (LOGB - 12));
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the buffer have returned
-            if (nsrc) dma_digit(nsrc, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            {   // round 0: the fifteen twiddles are the same for every thread of the workgroup -> scalar cache, scalar registers
-                double t0[15];
+        // The rounds of a forward row transform, apart, so that one wave can advance two rows of an item in turn (the 4096-row
+        // epilogue below).  round 0: the fifteen twiddles are the same for every thread of the workgroup -> scalar cache, scalar
+        // registers.  round 1: from the tile in round 1's order, through the tile again (an exchange inside 2^(LOGB - 8) threads:
+        // wave-local at 4096-rows, inside the thread group's own 256 words of the tile) into the last round's order.
+        auto round0 = [&](double (&x)[16]) {
+            double t0[15];
 #pragma unroll
-                for (int u = 0; u < 4; u++)
+            for (int u = 0; u < 4; u++)
 #pragma unroll
-                    for (int j = 0; j < (1 << u); j++) t0[(1 << u) - 1 + j] = ldcd(cur.tw, (size_t)(((unsigned)cur.rowtw << u) + j));
-                rows_round16_f64<false>(x, t0, q, qi);
-            }
-            __syncthreads();  // every wave is done with the tile (previous digit's last read) -- and tw1s is in place
-            rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 0, LOGB - 4, true);
-            __syncthreads();
+                for (int j = 0; j < (1 << u); j++) t0[(1 << u) - 1 + j] = ldcd(cur.tw, (size_t)(((unsigned)cur.rowtw << u) + j));
+            rows_round16_f64<false>(x, t0, q, qi);
+        };
+        auto round1 = [&](double (&x)[16], unsigned tau) {
             rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 4, LOGB - 8, false);
             {
                 double t1[15];
@@ -1448,21 +1443,31 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
             rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 4, LOGB - 8, true);
             rows_sync(LOGB - 8);
             rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 8, LOGB - 12, false);
+        };
+        auto transform = [&](int nk, double (&x)[16], unsigned tau, unsigned lane, const uint64_t *nsrc, const double *k0p,
+                             const double *k1p, double (&kk0)[16], double (&kk1)[16]) {
+            // nk (block-uniform): rows of sixteen words fetched on the way -- 2 (k0p and k1p), 1 (k0p), 0
+            // round-2 twiddles first, then the DMA: ordinary loads issued after it could only return after it
+            double t2[15];
+            rows_tw16_f64(t2, cur.tw, cur.rowtw, 8, tau >> (LOGB - 12));
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the buffer have returned
+            if (nsrc) dma_digit(nsrc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            round0(x);
+            __syncthreads();  // every wave is done with the tile (previous digit's last read) -- and tw1s is in place
+            rows_lds_xfer_f64<LOGB, 4>(x, lds, tau, 0, LOGB - 4, true);
+            __syncthreads();
+            round1(x, tau);
             __builtin_amdgcn_sched_barrier(0);
             if (nk >= 1) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) kk0[k] = k0p[(unsigned)(k * T)];
             }
-            // early (the epilogue's transforms, operands prefetched): both rows before the round -- held across the whole
-            // transform they cost 176 spilled registers
-            if (early != 0 && nk >= 2) {
-#pragma unroll
-                for (int k = 0; k < 16; k++) kk1[k] = k1p[(unsigned)(k * T)];
-            }
             __builtin_amdgcn_sched_barrier(0);
             rows_round16_f64<false>(x, t2, q, qi);
             __builtin_amdgcn_sched_barrier(0);
-            if (early == 0 && nk >= 2) {
+            if (nk >= 2) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) kk1[k] = k1p[(unsigned)(k * T)];
             }
@@ -1538,8 +1543,143 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
             for (int k = 0; k < 16; k++) acc1[k] += modmul_f64(x[k], kk1[k], q, qi);
             MAC_STAMP2(1 + d * 12 + 10);
         }
-        if constexpr (EPI) {
-            // the two extension rows, through the same prefetch chain as two more digits
+        if constexpr (EPI && TEN && LOGB == 12) {
+            // 4096-rows, tensor term: the two extension rows A, B are ONE pair, advanced in turn by every wave through the one tile,
+            // so that a row's arithmetic runs while the other row's tile stores, barrier and operand requests are under way
+            // (B1 .. B7: workgroup barriers; the two single passes had six):
+            //   A: round 0 | B1 | store |         | B2 | round 1 | B3 |       | round 2, - acc0 | B4 |         | own-order store |
+            //   B:                      | round 0 |                   | store |                      | round 1 |                 | round 2
+            //   , - acc1 | B5 | A natural | B6 | B's own-order store, finish 0 | B7 | B natural, finish 1
+            // Row A arrives through the prefetch chain like a digit (the chain then fetches the NEXT item's first digit, a whole
+            // pair ahead); row B is requested with ordinary loads when the pair starts and is first needed after A's round 0.
+            // After B2 and after B4 a group of sixteen threads works inside its own 256 words of the tile (round1), so row A's
+            // own-order store follows the group's last read of row B without a barrier.  With both finishes adjacent each of
+            // the tensor term's four inputs is read ONCE per item (a0, b0 requested before A's last round, where a digit requests
+            // its key rows; a1, b1 once both accumulators are dead) -- 252 VGPRs.  The epilogues without the tensor term keep the
+            // single passes below: paired, they need 196 bytes of scratch per lane.
+            unsigned tau_d = threadIdx.x;
+            asm volatile("" : "+v"(tau_d));
+            const unsigned tau = tau_d, lane = tau & 63u;
+            const double *pw = pbuf + wv * 1024u + lane;
+            MAC_STAMP2(48);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // row A has landed
+            double xA[16], xB[16];
+            uint64_t wB[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) xA[k] = pw[k * 64];
+            const uint64_t *srcB = digit_src(cur, A.m.beta + 1) + tau;
+            const uint64_t *nsrc = next_src(A.m.beta + 1);
+#pragma unroll
+            for (int k = 0; k < 16; k++) wB[k] = ldnt(&srcB[(unsigned)(k * T)]);
+            double t2[15];  // the last round's twiddles: one set for both rows
+            rows_tw16_f64(t2, cur.tw, cur.rowtw, 8, tau);
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the buffer have returned
+            if (nsrc) dma_digit(nsrc, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            if (!AA.e.ext_f64) {  // words; otherwise doubles left by the basis extension (launch_modup_fused, f64_raw)
+#pragma unroll
+                for (int k = 0; k < 16; k++) xA[k] = u52_to_f64((uint64_t)__double_as_longlong(xA[k]));
+            }
+            MAC_STAMP2(49);
+            // the tensor term against (NTT(ext_c) - acc_c) s: the last op of ModDownQPtoQNTT against the accumulators
+            // in registers (arithmetic of ntt_rows_f64_kernel's epilogue, word for word)
+            const size_t off = (size_t)cur.out_limb * A.N + cur.rowoff + tau;
+            uint64_t *op0 = AA.e.out0 + meoff(AA.e, ME_OUT0, AA.e.out0_bs, cur.bz, AA.nbatch) + off;
+            uint64_t *op1 = AA.e.out1 + meoff(AA.e, ME_OUT1, AA.e.out1_bs, cur.bz, AA.nbatch) + off;
+            const double sp = AA.e.sp[cur.l];
+            const uint64_t *mcw = reinterpret_cast<const uint64_t *>(A.mc + cur.mi);
+            const uint64_t qu = ldc(mcw, 0);
+            uint64_t r0[16], r1[16], r2[16], r3[16];  // the operand rows a0, b0, a1, b1
+            round0(xA);
+            __syncthreads();  // B1: every wave is done with the tile (the last digit's last read)
+            rows_lds_xfer_f64<LOGB, 4>(xA, lds, tau, 0, LOGB - 4, true);
+            if (AA.e.ext_f64) {
+#pragma unroll
+                for (int k = 0; k < 16; k++) xB[k] = __longlong_as_double((long long)wB[k]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; k++) xB[k] = u52_to_f64(wB[k]);
+            }
+            round0(xB);
+            __syncthreads();  // B2: row A is in the tile
+            MAC_STAMP2(50);
+            round1(xA, tau);
+            __syncthreads();  // B3: every wave has taken row A out of the tile
+            rows_lds_xfer_f64<LOGB, 4>(xB, lds, tau, 0, LOGB - 4, true);
+            MAC_STAMP2(51);
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                const uint64_t *pa0 = AA.e.ta0 + meoff(AA.e, ME_TA0, AA.e.ta0_bs, cur.bz, AA.nbatch) + off;
+                const uint64_t *pb0 = AA.e.tb0 + meoff(AA.e, ME_TB0, AA.e.tb0_bs, cur.bz, AA.nbatch) + off;
+#pragma unroll
+                for (int k = 0; k < 16; k++) { r0[k] = pa0[(unsigned)(k * T)]; r1[k] = pb0[(unsigned)(k * T)]; }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            rows_round16_f64<false>(xA, t2, q, qi);
+#pragma unroll
+            for (int k = 0; k < 16; k++) xA[k] -= reduce_f64(acc0[k], q, qi);  // (|y| < q: x - y stays an exact integer below 2^53)
+            __syncthreads();  // B4: row B is in the tile
+            MAC_STAMP2(52);
+            round1(xB, tau);
+            mac_final_xfer<LOGB>(xA, lds, tau, true);  // the thread's own tile positions, inside its group's 256 words
+            MAC_STAMP2(53);
+            rows_round16_f64<false>(xB, t2, q, qi);
+#pragma unroll
+            for (int k = 0; k < 16; k++) xB[k] -= reduce_f64(acc1[k], q, qi);
+            __builtin_amdgcn_sched_barrier(0);
+            {   // both accumulators are dead and row A is in the tile: the registers for a1, b1 are free
+                const uint64_t *pa1 = AA.e.ta1 + meoff(AA.e, ME_TA1, AA.e.ta1_bs, cur.bz, AA.nbatch) + off;
+                const uint64_t *pb1 = AA.e.tb1 + meoff(AA.e, ME_TB1, AA.e.tb1_bs, cur.bz, AA.nbatch) + off;
+#pragma unroll
+                for (int k = 0; k < 16; k++) { r2[k] = pa1[(unsigned)(k * T)]; r3[k] = pb1[(unsigned)(k * T)]; }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();  // B5: row A is in the tile, in the threads' own order
+            MAC_STAMP2(54);
+#pragma unroll
+            for (int k = 0; k < 16; k++) xA[k] = lds[lds_phys(k * T + tau)];
+            __syncthreads();  // B6: every wave has taken row A out of the tile
+            mac_final_xfer<LOGB>(xB, lds, tau, true);
+            MAC_STAMP2(55);
+            // caller words may be any 64-bit representative (as MRed accepts them); every pipeline of this library hands over
+            // words below 2q, which convert as they are -- the Barrett reduction runs only for a wave that met a larger one
+            auto cvtb = [&](uint64_t (&w)[16], double (&dd)[16]) {
+                const uint64_t twoq_u = qu << 1, brc0 = ldc(mcw, 2);
+                bool big = false;
+#pragma unroll
+                for (int k = 0; k < 16; k++) big = big || w[k] >= twoq_u;
+                if (__any(big)) {
+#pragma unroll
+                    for (int k = 0; k < 16; k++) w[k] = bred_add_lazy(w[k], qu, brc0);
+                }
+#pragma unroll
+                for (int k = 0; k < 16; k++) dd[k] = u52_to_f64(w[k]);
+            };
+            const double tsp = AA.e.tsp[cur.l];
+            double u[16], v[16];  // a0, b0: both finishes
+            cvtb(r0, u); cvtb(r1, v);
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const double tt = modmul_f64(modmul_f64(u[k], v[k], q, qi), tsp, q, qi) + modmul_f64(xA[k], sp, q, qi);
+                stnt(&op0[(unsigned)(k * T)], canon_f64(tt, q, qi));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();  // B7: row B is in the tile, in the threads' own order
+            MAC_STAMP2(56);
+#pragma unroll
+            for (int k = 0; k < 16; k++) xB[k] = lds[lds_phys(k * T + tau)];
+            double u2[16], v2[16];  // a1, b1
+            cvtb(r2, u2); cvtb(r3, v2);
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const double wv = modmul_f64(u[k], v2[k], q, qi) + modmul_f64(u2[k], v[k], q, qi);
+                const double tt = modmul_f64(wv, tsp, q, qi) + modmul_f64(xB[k], sp, q, qi);
+                stnt(&op1[(unsigned)(k * T)], canon_f64(tt, q, qi));
+            }
+            MAC_STAMP2(57);
+        } else if constexpr (EPI) {
+            // the other forms: the two extension rows, one after the other through the same prefetch chain as two more digits
             auto ext_pass = [&](auto cc) __attribute__((always_inline)) {
                 const int c = cc;
                 unsigned tau_d = threadIdx.x;
@@ -1558,27 +1698,24 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 }
                 const uint64_t *nsrc = next_src(A.m.beta + c);
                 // x = NTT(ext_c) comes back in the accumulators' order (element k T + tau): the last op of ModDownQPtoQNTT against
-                // the accumulator in registers (arithmetic of ntt_rows_f64_kernel's epilogue, word for word).  The operands it
-                // needs from memory are requested before / while the transform runs, in the registers the key rows use in a digit.
+                // the accumulator in registers (arithmetic of ntt_rows_f64_kernel's epilogue, word for word)
                 const bool second = c != 0;
                 const size_t off = (size_t)cur.out_limb * A.N + cur.rowoff + tau;
                 uint64_t *op = (second ? AA.e.out1 + meoff(AA.e, ME_OUT1, AA.e.out1_bs, cur.bz, AA.nbatch) : AA.e.out0 + meoff(AA.e, ME_OUT0, AA.e.out0_bs, cur.bz, AA.nbatch)) + off;
                 const double sp = AA.e.sp[cur.l];
                 const uint64_t *mcw = reinterpret_cast<const uint64_t *>(A.mc + cur.mi);
                 const uint64_t qu = ldc(mcw, 0);
-                // (4096-rows: compile-time; the 8192-row kernel keeps both forms behind a run-time flag -- split the same way its
-                // Rotate variant measured 2 % slower, 4.35 -> 4.46 ms per c4 step of 128, with 40 KiB of code instead of 57)
-                const bool tensor = LOGB == 12 ? TEN : AA.e.tensor != 0;
+                // (4096-rows: the tensor term has the instantiation above; the 8192-row kernel keeps both forms behind a run-time
+                // flag -- split the same way its Rotate variant measured 2 % slower, 4.35 -> 4.46 ms per c4 step of 128, with
+                // 40 KiB of code instead of 57)
+                const bool tensor = LOGB == 13 && AA.e.tensor != 0;
                 const bool addw = !tensor && (second ? AA.e.has_w1 : AA.e.has_w0) != 0;
                 double kd0[16], kd1[16];  // the key rows' registers: free in these transforms (no key rows on the way)
                 MAC_STAMP2(48 + c * 4 + 1);
-                // 4096-rows: the operands the epilogue needs from memory -- a0, b0 (component 0) / a0, b1
-                // (component 1) of the tensor term, or the addend row -- are requested at the head of the transform into those
-                // registers, before its last round -- the place the key rows of a digit are requested (tools/mac_timeline.py,
-                // round 6: the epilogue phases were 10.6 k and 17.1 k cycles per item for ~2.6 k and ~3.5 k cycles of arithmetic:
-                // they waited for these loads)
-                // (the addend row alone at 8192-rows measured equal to slightly slower: c4 2.35 -> 2.37-2.39 ms)
-                constexpr bool prefetch = LOGB == 12;  // tensor + addend modes
+                // 4096-rows: the addend row is requested inside the transform into those registers, before its last round -- the
+                // place the key rows of a digit are requested
+                // (at 8192-rows it measured equal to slightly slower: c4 2.35 -> 2.37-2.39 ms)
+                constexpr bool prefetch = LOGB == 12;
                 const uint64_t *pa0 = nullptr, *pa1 = nullptr, *pb0 = nullptr, *pb1 = nullptr, *wp = nullptr;
                 if (tensor) {
                     pa0 = AA.e.ta0 + meoff(AA.e, ME_TA0, AA.e.ta0_bs, cur.bz, AA.nbatch) + off; pa1 = AA.e.ta1 + meoff(AA.e, ME_TA1, AA.e.ta1_bs, cur.bz, AA.nbatch) + off;
@@ -1586,17 +1723,12 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 } else if (addw) {
                     wp = (second ? AA.e.w1 + meoff(AA.e, ME_W1, AA.e.w1_bs, cur.bz, AA.nbatch) : AA.e.w0 + meoff(AA.e, ME_W0, AA.e.w0_bs, cur.bz, AA.nbatch)) + off;
                 }
-                constexpr int NB = LOGB == 12 ? 8 : 4;  // coefficients per batch (eight spill six registers in the 8192-row kernel).  Each batch waits ~2 000 cycles for its operands (tools/mac_timeline.py);
+                constexpr int NB = 4;  // coefficients per batch (eight spill six registers).  Each batch waits ~2 000 cycles for its operands (tools/mac_timeline.py);
                                        // the next batch in flight as well measured equal (a batch's arithmetic covers a quarter of
                                        // that), and the registers that could hold a whole row early are what the transform runs on
                 uint64_t A0[NB], A1[NB], A2[NB], A3[NB];
-                if constexpr (prefetch) {
-                    const double *e0 = reinterpret_cast<const double *>(tensor ? pa0 : wp);
-                    const double *e1 = reinterpret_cast<const double *>(second ? pb1 : pb0);
-                    transform(tensor ? 2 : (addw ? 1 : 0), x, tau, lane, nsrc, e0, e1, kd0, kd1, 1);
-                } else {
-                    transform(0, x, tau, lane, nsrc, nullptr, nullptr, kd0, kd1);
-                }
+                if constexpr (prefetch) transform(addw ? 1 : 0, x, tau, lane, nsrc, reinterpret_cast<const double *>(wp), nullptr, kd0, kd1);
+                else transform(0, x, tau, lane, nsrc, nullptr, nullptr, kd0, kd1);
                 // x - acc in the accumulators' order, then the transpose to the coalesced order of the operands and the stores
                 // (the tile positions written are the thread's own: no barrier before the stores)
 #pragma unroll
@@ -1653,47 +1785,10 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                         __builtin_amdgcn_sched_barrier(0);
                     };
 #define HE_H(n) std::integral_constant<int, n>{}
-                    if constexpr (prefetch) {
-                        // kd0 = a0, kd1 = b0 (component 0) / b1 (component 1), all sixteen coefficients, requested a transform ago
-                        if (second) {  // the other two rows (b0, a1), all sixteen coefficients in one request: the accumulators are dead by now.
-                                       // (Requested right after the transform instead, a transpose earlier: 2.37 -> 2.41 ms.)
-#pragma unroll
-                            for (int k = 0; k < NB; k++) {
-                                const unsigned e = (unsigned)(k * T), e2 = (unsigned)((NB + k) * T);
-                                A1[k] = pb0[e]; A2[k] = pa1[e]; A0[k] = pb0[e2]; A3[k] = pa1[e2];
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        auto half = [&](auto hc, uint64_t (&vb0)[NB], uint64_t (&va1)[NB]) {
-                            constexpr int h = decltype(hc)::value;
-                            uint64_t w0[NB], w1[NB];
-#pragma unroll
-                            for (int k = 0; k < NB; k++) { w0[k] = (uint64_t)__double_as_longlong(kd0[NB * h + k]); w1[k] = (uint64_t)__double_as_longlong(kd1[NB * h + k]); }
-                            // finish() forms u v (component 0) or u v2 + u2 v (component 1) from (r0, r1, r2, r3) = (u, v, u2, v2)
-                            if (!second) finish(hc, w0, w1, w0, w1);
-                            else finish(hc, w0, vb0, va1, w1);
-                        };
-                        half(HE_H(0), A1, A2);
-                        half(HE_H(1), A0, A3);
-                    } else if (NB == 8 && !second) {
-                        // component 0 has two operand rows, not four: all sixteen coefficients' words in ONE request (the second
-                        // eight in the registers component 1 uses for a1, b1)
-#pragma unroll
-                        for (int k = 0; k < NB; k++) {
-                            const unsigned e = (unsigned)(k * T), e2 = (unsigned)((NB + k) * T);
-                            A0[k] = pa0[e]; A1[k] = pb0[e]; A2[k] = pa0[e2]; A3[k] = pb0[e2];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        finish(HE_H(0), A0, A1, A0, A1);
-                        finish(HE_H(1), A2, A3, A2, A3);
-                    } else {
-                        issue(HE_H(0), A0, A1, A2, A3); finish(HE_H(0), A0, A1, A2, A3);
-                        issue(HE_H(1), A0, A1, A2, A3); finish(HE_H(1), A0, A1, A2, A3);
-                    }
-                    if constexpr (NB < 8) {
-                        issue(HE_H(2), A0, A1, A2, A3); finish(HE_H(2), A0, A1, A2, A3);
-                        issue(HE_H(3), A0, A1, A2, A3); finish(HE_H(3), A0, A1, A2, A3);
-                    }
+                    issue(HE_H(0), A0, A1, A2, A3); finish(HE_H(0), A0, A1, A2, A3);
+                    issue(HE_H(1), A0, A1, A2, A3); finish(HE_H(1), A0, A1, A2, A3);
+                    issue(HE_H(2), A0, A1, A2, A3); finish(HE_H(2), A0, A1, A2, A3);
+                    issue(HE_H(3), A0, A1, A2, A3); finish(HE_H(3), A0, A1, A2, A3);
 #undef HE_H
                 } else if (addw) {
                     uint64_t wv[16];
@@ -1726,8 +1821,7 @@ __global__ void __launch_bounds__((1 << LOGB) / 16, 2) ntt_mac_f64_dma_kernel(Nt
                 for (int k = 0; k < 16; k++) acc0[k] = acc1[k];
             };
             if constexpr (LOGB == 12) {
-                // two copies of the pass: the second accumulator's registers are free in the second one (as ONE loop body the
-                // prefetched operand rows cost 180 spilled registers)
+                // two copies of the pass: the second accumulator's registers are free in the second one
                 ext_pass(std::integral_constant<int, 0>{});
                 ext_pass(std::integral_constant<int, 1>{});
             } else {

@@ -44,7 +44,16 @@ for dg in range(4 if "--dma" not in sys.argv else 0):
               "mac0": int(np.median(own[:, 9] - own[:, 8])), "mac1": int(np.median(own[:, 10] - own[:, 9]))})
     elif len(own):
         print("digit", dg, "own waves", len(own), "start->mac", int(np.median(own[:, 10] - own[:, 0])), "mac->endbar", int(np.median(own[:, 11] - own[:, 10])))
-if "--dma" in sys.argv and (a[:, 48] > 0).any():  # fused ModDown epilogue: the two extension phases
+if "--dma" in sys.argv and (a[:, 57] > 0).any():  # fused ModDown epilogue, 4096-rows: the two extension rows as one pair
+    e = a[(a[:, 48:58] > 0).all(axis=1)]
+    pn = ["dma-wait + row A read, row B / next row / tw2 requested", "round 0 A | B1 | store A, round 0 B | B2", "round 1 A | B3 | store B",
+          "a0 b0 request, round 2 A, - acc0 | B4", "round 1 B, own-order store A", "round 2 B, - acc1, a1 b1 request | B5",
+          "A natural | B6 | own-order store B", "finish 0 | B7", "B natural, finish 1"]
+    seg = np.diff(e[:, 48:58], axis=1)
+    print("ext pair waves", len(e), {pn[i]: int(np.median(seg[:, i])) for i in range(9)})
+    print("ext pair: transforms (start -> B5)", int(np.median(e[:, 54] - e[:, 48])), " finishes (B5 -> end)", int(np.median(e[:, 57] - e[:, 54])),
+          " last digit's end -> pair:", int(np.median(e[:, 48] - e[:, 47])))
+elif "--dma" in sys.argv and (a[:, 48] > 0).any():  # fused ModDown epilogue, one extension row after the other
     e = a[(a[:, 48:56] > 0).all(axis=1)]
     for c in range(2):
         b = 48 + 4 * c
