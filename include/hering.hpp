@@ -25,6 +25,7 @@
 
 #include "hering.h"
 #include "hering_ringswitch.h"
+#include "hering_ringpack.h"
 
 namespace hering {
 
@@ -634,6 +635,79 @@ inline void SwitchCiphertextRingDegree(const Ciphertext &ctIn, Ciphertext &opOut
         check(he_switch_ring_degree(a.Level() < b.Level() ? a.Level() : b.Level(), a.h(), b.h()));
     }
 }
+
+// ---- ring packing (core/rlwe/ring_packing.go; hering_ringpack.h), standard rings, NTT domain -----------------------------------
+namespace detail {
+inline std::vector<he_handle> handles(const std::vector<const Poly *> &v) {
+    std::vector<he_handle> h(v.size());
+    for (size_t i = 0; i < v.size(); i++) h[i] = v[i] ? v[i]->h() : 0;
+    return h;
+}
+}  // namespace detail
+// GenXPow2NTT(ring.AtLevel(level), logN, div)[i] (:772-810), read off the resident twiddle tables
+inline void XPow2NTT(const Ring &ring, int level, int i, bool div, Poly &out) { check(he_ring_xpow2_ntt(ring.h(), level, i, div ? 1 : 0, out.h())); }
+// the ring maps of Split (:205-225) / Merge (:410-417) on one polynomial; the odd operand may be nullptr
+inline void SplitNTT(const Ring &ringLarge, int level, const Poly &in, Poly &outEven, Poly *outOdd) {
+    check(he_ring_split_ntt(ringLarge.h(), level, in.h(), outEven.h(), outOdd ? outOdd->h() : 0));
+}
+inline void MergeNTT(const Ring &ringLarge, int level, const Poly &inEven, const Poly *inOdd, Poly &out) {
+    check(he_ring_merge_ntt(ringLarge.h(), level, inEven.h(), inOdd ? inOdd->h() : 0, out.h()));
+}
+// Expand's inner step at n = 2^k (:528-559) over batched ciphertexts: out of 2 m entries, or m (and possibly in itself) when sumOnly
+inline void ExpandStep(const Ring &ring, int level, int k, bool sumOnly, const Ciphertext &in, const Ciphertext &tmp, Ciphertext &out) {
+    check(he_ringpack_expand_step(ring.h(), level, k, sumOnly ? 1 : 0, in.Value.at(0).h(), in.Value.at(1).h(), tmp.Value.at(0).h(),
+                                  tmp.Value.at(1).h(), out.Value.at(0).h(), out.Value.at(1).h()));
+}
+// Pack's inner step (:697-765) before / after the automorphism of T, over pairs of single ciphertexts (nullptr: absent)
+inline void PackPre(const Ring &ring, int level, int k, const std::vector<const Poly *> &a0, const std::vector<const Poly *> &a1,
+                    const std::vector<const Poly *> &b0, const std::vector<const Poly *> &b1, Ciphertext &T) {
+    const std::vector<he_handle> ha0 = detail::handles(a0), ha1 = detail::handles(a1), hb0 = detail::handles(b0), hb1 = detail::handles(b1);
+    if (ha0.empty() || ha1.size() != ha0.size() || hb0.size() != ha0.size() || hb1.size() != ha0.size()) throw std::invalid_argument("PackPre: pair lists of different length");
+    check(he_ringpack_pack_pre(ring.h(), level, k, (int)ha0.size(), ha0.data(), ha1.data(), hb0.data(), hb1.data(), T.Value.at(0).h(), T.Value.at(1).h()));
+}
+inline void PackPost(const Ring &ring, int level, const std::vector<const Poly *> &a0, const std::vector<const Poly *> &a1,
+                     const std::vector<const Poly *> &b0, const std::vector<const Poly *> &b1, Ciphertext &T) {
+    const std::vector<he_handle> ha0 = detail::handles(a0), ha1 = detail::handles(a1), hb0 = detail::handles(b0), hb1 = detail::handles(b1);
+    if (ha0.empty() || ha1.size() != ha0.size() || hb0.size() != ha0.size() || hb1.size() != ha0.size()) throw std::invalid_argument("PackPost: pair lists of different length");
+    check(he_ringpack_pack_post(ring.h(), level, (int)ha0.size(), ha0.data(), ha1.data(), hb0.data(), hb1.data(), T.Value.at(0).h(), T.Value.at(1).h()));
+}
+// rlwe.RingPackingEvaluator (:13): Split and Merge between the degree N of `evalN` and N/2; ringQNHalf allocates the halves
+class RingPackingEvaluator {
+    Evaluator evalN_;  // (a copy shares the device evaluator, as every mirror class shares its handle)
+    Ring ringQNHalf_;
+    EvaluationKey evkNToNHalf_, evkNHalfToN_;
+
+public:
+    RingPackingEvaluator(const Evaluator &evalN, const Ring &ringQNHalf, const EvaluationKey &evkNToNHalf, const EvaluationKey &evkNHalfToN)
+        : evalN_(evalN), ringQNHalf_(ringQNHalf), evkNToNHalf_(evkNToNHalf), evkNHalfToN_(evkNHalfToN) {
+        if (ringQNHalf.N() * 2 != evalN.RingQ().N()) throw std::invalid_argument("RingPackingEvaluator: ringQNHalf is not of degree N/2");
+    }
+    // :173-228; ctOddNHalf may be nullptr
+    void Split(const Ciphertext &ctN, Ciphertext &ctEvenNHalf, Ciphertext *ctOddNHalf) const {
+        check(he_ringpack_split(evalN_.h(), ctN.Level(), ctN.Value.at(0).h(), ctN.Value.at(1).h(), evkNToNHalf_.h(), ctEvenNHalf.Value.at(0).h(),
+                                ctEvenNHalf.Value.at(1).h(), ctOddNHalf ? ctOddNHalf->Value.at(0).h() : 0, ctOddNHalf ? ctOddNHalf->Value.at(1).h() : 0));
+    }
+    std::pair<Ciphertext, Ciphertext> SplitNew(const Ciphertext &ctN) const {
+        const Ring r = ringQNHalf_.AtLevel(ctN.Level());
+        const int B = ctN.Value.at(0).Batch();
+        Ciphertext even{{r.NewPoly(B), r.NewPoly(B)}}, odd{{r.NewPoly(B), r.NewPoly(B)}};
+        Split(ctN, even, &odd);
+        return {even, odd};
+    }
+    // :376-426; ctOddNHalf may be nullptr
+    void Merge(const Ciphertext &ctEvenNHalf, const Ciphertext *ctOddNHalf, Ciphertext &ctN) const {
+        check(he_ringpack_merge(evalN_.h(), ctN.Level(), ctEvenNHalf.Value.at(0).h(), ctEvenNHalf.Value.at(1).h(),
+                                ctOddNHalf ? ctOddNHalf->Value.at(0).h() : 0, ctOddNHalf ? ctOddNHalf->Value.at(1).h() : 0, evkNHalfToN_.h(),
+                                ctN.Value.at(0).h(), ctN.Value.at(1).h()));
+    }
+    Ciphertext MergeNew(const Ciphertext &ctEvenNHalf, const Ciphertext *ctOddNHalf) const {
+        const Ring r = evalN_.RingQ().AtLevel(ctEvenNHalf.Level());
+        const int B = ctEvenNHalf.Value.at(0).Batch();
+        Ciphertext ctN{{r.NewPoly(B), r.NewPoly(B)}};
+        Merge(ctEvenNHalf, ctOddNHalf, ctN);
+        return ctN;
+    }
+};
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

@@ -79,7 +79,10 @@ int he_debug_concurrent_mul_relin(int n_threads, int iters, int sync_each, int o
  * thread's own; the n_subst handles subst_from[] (the run's inputs) are replaced per thread by subst_to[thread * n_subst + i];
  * every other handle (rings, evaluator, keys, plaintexts) is shared.  watch[]: recorded handles whose per-thread counterparts of
  * the LAST round are returned in watch_out[thread * n_watch + i] and left alive (the caller downloads and frees them).  *wall_s:
- * common start to the last thread's final he_ctx_sync.  Returns the first non-zero status; err (optional) receives its message. */
+ * common start to the last thread's final he_ctx_sync.  Returns the first non-zero status; err (optional) receives its message.
+ * The recorder refuses a window that creates a ring, an evaluator or a key (they are shared, not replayed); it leaves out the
+ * he_ring_destroy of a ring made before the window, which the host's garbage collector may issue at any time for a ring nothing
+ * refers to any more: no call of the window can name that ring. */
 int he_debug_replay(he_handle ctx, const uint64_t *program, size_t n_words, int n_threads, int rounds, const uint64_t *subst_from,
                     int n_subst, const uint64_t *subst_to, const uint64_t *watch, int n_watch, uint64_t *watch_out, double *wall_s,
                     char *err, size_t err_len);

@@ -9,7 +9,8 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HERING_LIB: A/B-test another build
 _INC = os.path.join(os.path.dirname(_HERE), "include")
-_HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h")]
+_HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
+         os.path.join(_INC, "hering_ringpack.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -112,6 +113,10 @@ def _declare(L):
         "he_relinearize": [H, i, H, H, H, H, H, H],
         "he_map_small_to_large_ntt": [H, H, i], "he_switch_ring_degree_ntt": [H, i, H, H], "he_switch_ring_degree": [i, H, H],
         "he_apply_evaluation_key": [H, i, H, H, H, H, H],
+        "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
+        "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
+        "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
+        "he_ringpack_pack_pre": [H, i, i, i, HP, HP, HP, HP, H, H], "he_ringpack_pack_post": [H, i, i, HP, HP, HP, HP, H, H],
         "he_automorphism_ct": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted_lazy": [H, i, H, H, C.c_uint64, H, H, H, H, H],
@@ -181,16 +186,24 @@ _TRACE_FNS = {
     "he_lintrans_giant_step": (50, "hihhihhhhhhi"),
     "he_map_small_to_large_ntt": (51, "hhi"), "he_switch_ring_degree_ntt": (52, "hihh"), "he_switch_ring_degree": (53, "ihh"),
     "he_apply_evaluation_key": (54, "hihhhhh"),
+    "he_ring_xpow2_ntt": (55, "hiiih"), "he_ring_split_ntt": (56, "hihhh"), "he_ring_merge_ntt": (57, "hihhh"),
+    "he_ringpack_split": (58, "hihhhhhhh"), "he_ringpack_merge": (59, "hihhhhhhh"), "he_ringpack_expand_step": (60, "hiiihhhhhh"),
+    "he_ringpack_pack_pre": (61, "hiiiHHHHhh"), "he_ringpack_pack_post": (62, "hiiHHHHhh"),
 }
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments)
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
               ("he_mul_scalar_bigint", 3): (4, 0), ("he_mul_scalar_bigint_then_add", 3): (4, 0), ("he_double_rns_scalarop", 4): (1, 1),
               ("he_double_rns_scalarop", 5): (1, 1), ("he_rescale_polys", 4): (3, 0), ("he_rescale_polys", 5): (3, 0)}
 _TRACE_LEN.update({("he_lintrans_mul_sum", k): (3, 0) for k in range(4, 11)})
+_TRACE_LEN.update({("he_ringpack_pack_pre", k): (3, 0) for k in range(4, 8)})
+_TRACE_LEN.update({("he_ringpack_pack_post", k): (2, 0) for k in range(3, 7)})
 # calls a replay has no use for: they read, wait or account, and do not change what the replayed calls see
 _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start", "he_timer_stop", "he_poly_download", "he_poly_shape",
                  "he_poly_download_limb", "he_prof_begin", "he_prof_end", "he_prof_end_bytes", "he_ctx_coalescing_stats",
-                 "he_evaluator_coalescing_stats", "he_version", "he_device_info", "he_ring_constant", "he_ring_roots", "he_decomp_download_limb"}
+                 "he_evaluator_coalescing_stats", "he_version", "he_device_info", "he_ring_constant", "he_ring_roots", "he_decomp_download_limb",
+                 # a Ring owns itself (Ring._owner), so an unreachable one is released by the cycle collector, whenever that runs:
+                 # no later call of the recording can name it
+                 "he_ring_destroy"}
 _trace = None
 
 

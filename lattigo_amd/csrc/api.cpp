@@ -25,6 +25,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <cstdlib>
 #include <vector>
 #include <dlfcn.h>
@@ -38,6 +39,7 @@
 #include "../../include/hering.h"
 #include "../../include/hering_debug.h"
 #include "../../include/hering_ringswitch.h"
+#include "../../include/hering_ringpack.h"
 #include "host_math.h"
 #include "kernels.h"
 
@@ -94,8 +96,10 @@ enum CoOp {
     CO_NTT, CO_EW, CO_EW_DOUBLE, CO_SHIFT, CO_RESCALE, CO_GATHER, CO_AUTO_COEFF, CO_MODUP, CO_MODDOWN_BE,
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
-    CO_RING_SWITCH, CO_APPLY_EVK
+    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT
 };
+// kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
+enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
 struct CoReq {
     // ---- key: requests are batched together only when all of this matches
     int op = 0;
@@ -4760,6 +4764,364 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
         return (form != AEK_SAME || alias) ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
     };
     return co_dispatch(*be.ctx, B, q);
+}
+
+// ---------------------------------------------------------------------------------------
+// the ring-packing evaluator (include/hering_ringpack.h; core/rlwe/ring_packing.go)
+// ---------------------------------------------------------------------------------------
+// Every entry is filed on the queue and served one by one (none of the kernels takes entry tables, as the ring maps).
+static int rp_ring(const Ring &r, int level, const char *who) {
+    if (r.type != 0) return fail(HE_EINVAL, "%s: method is only supported for ring.Type = ring.Standard", who);
+    if (level < 0 || level >= r.nmod() || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, r.nmod() - 1);
+    return HE_OK;
+}
+// one launch covers every entry of both components in its grid's z dimension
+constexpr int kRpMaxEntries = 65535;
+static int rp_entries(long entries, const char *who) {
+    if (entries > kRpMaxEntries)
+        return fail(HE_EINVAL, "%s: %ld entries in one call, at most %d (split the batch)", who, entries, kRpMaxEntries);
+    return HE_OK;
+}
+// a polynomial of `ctx`, of degree N and batch B, with limbs 0..level
+static int rp_poly(const Poly &p, const std::shared_ptr<Ctx> &ctx, int N, int B, int level, const char *who, const char *what) {
+    if (p.ctx != ctx) return fail(HE_EINVAL, "%s: %s belongs to another context", who, what);
+    if (p.N != N) return fail(HE_EINVAL, "%s: %s has degree %d, %d expected", who, what, p.N, N);
+    if (p.batch != B) return fail(HE_EINVAL, "%s: batch mismatch (%s has %d entries, %d expected)", who, what, p.batch, B);
+    if (p.nlimbs < level + 1) return fail(HE_EINVAL, "%s: %s has %d limbs, level %d needs %d", who, what, p.nlimbs, level, level + 1);
+    return HE_OK;
+}
+int he_ring_xpow2_ntt(he_handle hring, int level, int i, int div, he_handle hout) {
+    static const char *who = "he_ring_xpow2_ntt";
+    GET(r, Ring, hring, T_RING);
+    GET(out, Poly, hout, T_POLY);
+    TRY(rp_ring(*r, level, who));
+    if (r->N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r->N);
+    if (i < 0 || i >= r->logN) return fail(HE_EINVAL, "%s: i = %d out of range [0,%d]", who, i, r->logN - 1);
+    TRY(rp_poly(*out, r->ctx, r->N, out->batch, level, who, "out"));
+    TRY(rp_entries(out->batch, who));
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    CoReq q;
+    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_XPOW2; q.par[1] = level; q.par[2] = i; q.par[3] = div != 0;
+    q.ops = {out->view()};
+    q.keep = {r, out};
+    q.run = [ctx, r, level, i, div](const View *v, int B) -> int {
+        ctx->acct(level + 1, 0, B, r->N);
+        HIP_TRY(launch_xpow2_fill(r->dev, v[0], i, div != 0, level + 1, B, ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*ctx, out->batch, q);
+}
+// the launch of Split's / Merge's ring map over B entries per component (ncomp components); the caller holds the context
+static int rp_split_launch(Ctx &c, const Ring &large, const RingPackIO &io, bool odd, int level, int B, int ncomp) {
+    c.acct(ncomp * (level + 1) * (odd ? 2.0 : 1.5), odd ? 0.5 * (level + 1) : 0.0, B, large.N);
+    if (odd) { Valu V(large.logN - 1); V.mul(false, (double)ncomp * (level + 1)); V.into(c, B); }
+    HIP_TRY(launch_ring_split(large.dev, io, level + 1, ncomp * B, c.stream));
+    return HE_OK;
+}
+static int rp_merge_launch(Ctx &c, const Ring &large, const RingPackIO &io, bool odd, int level, int B, int ncomp) {
+    c.acct(ncomp * (level + 1) * (odd ? 2.0 : 1.5), odd ? 0.5 * (level + 1) : 0.0, B, large.N);
+    if (odd) { Valu V(large.logN - 1); V.mul(false, (double)ncomp * (level + 1)); V.into(c, B); }
+    HIP_TRY(launch_ring_merge(large.dev, io, level + 1, ncomp * B, c.stream));
+    return HE_OK;
+}
+int he_ring_split_ntt(he_handle hring, int level, he_handle hin, he_handle heven, he_handle hodd) {
+    static const char *who = "he_ring_split_ntt";
+    GET(r, Ring, hring, T_RING);
+    GET(in, Poly, hin, T_POLY);
+    GET(even, Poly, heven, T_POLY);
+    std::shared_ptr<Poly> odd;
+    if (hodd) {
+        odd = get<Poly>(hodd, T_POLY);
+        if (!odd) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", who, (unsigned long long)hodd);
+    }
+    TRY(rp_ring(*r, level, who));
+    if (in->N != r->N) return fail(HE_EINVAL, "%s: in has degree %d, the ring's degree %d expected", who, in->N, r->N);
+    if (r->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, r->N / 2);
+    const int B = in->batch;
+    TRY(rp_entries(B, who));
+    TRY(rp_poly(*in, r->ctx, r->N, B, level, who, "in"));
+    TRY(rp_poly(*even, r->ctx, r->N / 2, B, level, who, "outEven"));
+    if (odd) TRY(rp_poly(*odd, r->ctx, r->N / 2, B, level, who, "outOdd"));
+    TRY(reject_aliasing(who, {{in.get(), false, false}, {even.get(), true, false}, {odd.get(), true, false}}));
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    const bool has_odd = (bool)odd;
+    CoReq q;
+    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_SPLIT; q.par[1] = level; q.par[2] = has_odd;
+    q.ops = {in->view(), even->view(), odd ? odd->view() : View{nullptr, 0}};
+    q.keep = {r, in, even};
+    if (odd) q.keep.push_back(odd);
+    q.run = [ctx, r, level, has_odd](const View *v, int B) -> int {
+        RingPackIO io;
+        io.x[0] = v[0]; io.o[0] = v[1]; io.p[0] = v[2];
+        return rp_split_launch(*ctx, *r, io, has_odd, level, B, 1);
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*ctx, B, q);
+}
+int he_ring_merge_ntt(he_handle hring, int level, he_handle heven, he_handle hodd, he_handle hout) {
+    static const char *who = "he_ring_merge_ntt";
+    GET(r, Ring, hring, T_RING);
+    GET(even, Poly, heven, T_POLY);
+    GET(out, Poly, hout, T_POLY);
+    std::shared_ptr<Poly> odd;
+    if (hodd) {
+        odd = get<Poly>(hodd, T_POLY);
+        if (!odd) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", who, (unsigned long long)hodd);
+    }
+    TRY(rp_ring(*r, level, who));
+    if (out->N != r->N) return fail(HE_EINVAL, "%s: out has degree %d, the ring's degree %d expected", who, out->N, r->N);
+    if (r->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, r->N / 2);
+    const int B = out->batch;
+    TRY(rp_entries(B, who));
+    TRY(rp_poly(*out, r->ctx, r->N, B, level, who, "out"));
+    TRY(rp_poly(*even, r->ctx, r->N / 2, B, level, who, "inEven"));
+    if (odd) TRY(rp_poly(*odd, r->ctx, r->N / 2, B, level, who, "inOdd"));
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    const bool has_odd = (bool)odd;
+    CoReq q;
+    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_MERGE; q.par[1] = level; q.par[2] = has_odd;
+    q.ops = {even->view(), odd ? odd->view() : View{nullptr, 0}, out->view()};
+    q.keep = {r, even, out};
+    if (odd) q.keep.push_back(odd);
+    q.run = [ctx, r, level, has_odd](const View *v, int B) -> int {
+        RingPackIO io;
+        io.x[0] = v[0]; io.y[0] = v[1]; io.o[0] = v[2];
+        return rp_merge_launch(*ctx, *r, io, has_odd, level, B, 1);
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*ctx, B, q);
+}
+// the shared checks of he_ringpack_split / he_ringpack_merge: L = the two components at the evaluator's degree N, e / o the halves
+static int rp_ct_checks(const Evaluator &ev, const Evk &k, int &level, Poly *const L[2], Poly *const e[2], Poly *const o[2], const char *who,
+                        const char *large_name) {
+    const BasisExtender &be = *ev.be;
+    if (be.type != 0) return fail(HE_EINVAL, "%s: method is only supported for ring.Type = ring.Standard", who);
+    const int asked = level;
+    TRY(check_key(ev, k, level, who));
+    if (level != asked) return fail(HE_EINVAL, "%s: the key has %d Q limbs, level %d needs %d", who, k.nQk, asked, asked + 1);
+    if (level >= be.LQ || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, be.LQ - 1);
+    const int N = be.Q->N, B = L[0]->batch;
+    TRY(rp_entries(2L * B, who));
+    if (L[0]->N != N || L[1]->N != N) return fail(HE_EINVAL, "%s: %s ring degree does not match evaluator params ring degree %d", who, large_name, N);
+    if (N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, N / 2);
+    if ((o[0] == nullptr) != (o[1] == nullptr)) return fail(HE_EINVAL, "%s: odd0 and odd1 are both given or both 0", who);
+    for (int c = 0; c < 2; c++) {
+        TRY(rp_poly(*L[c], be.ctx, N, B, level, who, large_name));
+        TRY(check_be_poly(*L[c], be, level + 1, who));
+        TRY(rp_poly(*e[c], be.ctx, N / 2, B, level, who, "even"));
+        if (o[c]) TRY(rp_poly(*o[c], be.ctx, N / 2, B, level, who, "odd"));
+    }
+    return HE_OK;
+}
+#define RP_GET_OPT(var, h)                                                                                 \
+    std::shared_ptr<Poly> var;                                                                             \
+    if (h) {                                                                                               \
+        var = get<Poly>(h, T_POLY);                                                                        \
+        if (!var) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", __func__, (unsigned long long)(h));  \
+    }
+int he_ringpack_split(he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hk, he_handle he0, he_handle he1, he_handle ho0,
+                      he_handle ho1) {
+    static const char *who = "he_ringpack_split";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(in0, Poly, hin0, T_POLY);
+    GET(in1, Poly, hin1, T_POLY);
+    GET(k, Evk, hk, T_EVK);
+    GET(e0, Poly, he0, T_POLY);
+    GET(e1, Poly, he1, T_POLY);
+    RP_GET_OPT(o0, ho0);
+    RP_GET_OPT(o1, ho1);
+    Poly *const L[2] = {in0.get(), in1.get()}, *const E[2] = {e0.get(), e1.get()}, *const O[2] = {o0.get(), o1.get()};
+    TRY(rp_ct_checks(*ev, *k, level, L, E, O, who, "ctN"));
+    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {e0.get(), true, false}, {e1.get(), true, false},
+                              {o0.get(), true, false}, {o1.get(), true, false}}));
+    const bool has_odd = (bool)o0;
+    BasisExtender &be = *ev->be;
+    CoReq q;
+    q.op = CO_RINGPACK_CT; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = 0; q.par[2] = has_odd;
+    q.ops = {in0->view(), in1->view(), e0->view(), e1->view(), o0 ? o0->view() : View{nullptr, 0}, o1 ? o1->view() : View{nullptr, 0}};
+    q.keep = {ev, k, in0, in1, e0, e1};
+    if (o0) { q.keep.push_back(o0); q.keep.push_back(o1); }
+    q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        const int N = be.Q->N, levelP = k->nPk - 1;
+        const int beta = k->pw2 ? k->prefix[level + 1] : base_rns_size(level, levelP);
+        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
+        be.ctx->acct(4.0 * (level + 1), key_limbs(*k, level), B, N);  // the key switch: 2 L in, 2 L out, key
+        { Valu V(be.Q->logN); valu_gadget_product(V, be, level, levelP, beta, true); V.into(*be.ctx, B); }
+        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, levelP, B, true, k.get()) + 2 * wQ + 2));
+        uint64_t *t = be.ctx->arena_take(2 * wQ);
+        const View t0{t, sQ}, t1{t + wQ, sQ};
+        TRY(gadget_product_core(*ev, level, &v[1], nullptr, *k, t0, t1, B, &v[0], nullptr));
+        RingPackIO io;
+        io.zsplit = B;
+        io.x[0] = t0; io.x[1] = t1; io.o[0] = v[2]; io.o[1] = v[3]; io.p[0] = v[4]; io.p[1] = v[5];
+        return rp_split_launch(*be.ctx, *be.Q, io, has_odd, level, B, 2);
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*be.ctx, in0->batch, q);
+}
+int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he_handle ho0, he_handle ho1, he_handle hk, he_handle hout0,
+                      he_handle hout1) {
+    static const char *who = "he_ringpack_merge";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(e0, Poly, he0, T_POLY);
+    GET(e1, Poly, he1, T_POLY);
+    RP_GET_OPT(o0, ho0);
+    RP_GET_OPT(o1, ho1);
+    GET(k, Evk, hk, T_EVK);
+    GET(out0, Poly, hout0, T_POLY);
+    GET(out1, Poly, hout1, T_POLY);
+    Poly *const L[2] = {out0.get(), out1.get()}, *const E[2] = {e0.get(), e1.get()}, *const O[2] = {o0.get(), o1.get()};
+    TRY(rp_ct_checks(*ev, *k, level, L, E, O, who, "ctN"));
+    TRY(reject_aliasing(who, {{e0.get(), false, false}, {e1.get(), false, false}, {o0.get(), false, false}, {o1.get(), false, false},
+                              {out0.get(), true, false}, {out1.get(), true, false}}));
+    const bool has_odd = (bool)o0;
+    BasisExtender &be = *ev->be;
+    CoReq q;
+    q.op = CO_RINGPACK_CT; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = 1; q.par[2] = has_odd;
+    q.ops = {e0->view(), e1->view(), o0 ? o0->view() : View{nullptr, 0}, o1 ? o1->view() : View{nullptr, 0}, out0->view(), out1->view()};
+    q.keep = {ev, k, e0, e1, out0, out1};
+    if (o0) { q.keep.push_back(o0); q.keep.push_back(o1); }
+    q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        const int N = be.Q->N, levelP = k->nPk - 1;
+        const int beta = k->pw2 ? k->prefix[level + 1] : base_rns_size(level, levelP);
+        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
+        be.ctx->acct(4.0 * (level + 1), key_limbs(*k, level), B, N);  // the key switch: 2 L in, 2 L out, key
+        { Valu V(be.Q->logN); valu_gadget_product(V, be, level, levelP, beta, true); V.into(*be.ctx, B); }
+        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, levelP, B, true, k.get()) + 2 * wQ + 2));
+        uint64_t *t = be.ctx->arena_take(2 * wQ);
+        const View t0{t, sQ}, t1{t + wQ, sQ};
+        RingPackIO io;
+        io.zsplit = B;
+        io.x[0] = v[0]; io.x[1] = v[1]; io.y[0] = v[2]; io.y[1] = v[3]; io.o[0] = t0; io.o[1] = t1;
+        TRY(rp_merge_launch(*be.ctx, *be.Q, io, has_odd, level, B, 2));
+        return gadget_product_core(*ev, level, &t1, nullptr, *k, v[4], v[5], B, &t0, nullptr);
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*be.ctx, out0->batch, q);
+}
+int he_ringpack_expand_step(he_handle hring, int level, int k, int sum_only, he_handle hin0, he_handle hin1, he_handle htmp0, he_handle htmp1,
+                            he_handle hout0, he_handle hout1) {
+    static const char *who = "he_ringpack_expand_step";
+    GET(r, Ring, hring, T_RING);
+    GET(in0, Poly, hin0, T_POLY);
+    GET(in1, Poly, hin1, T_POLY);
+    GET(tmp0, Poly, htmp0, T_POLY);
+    GET(tmp1, Poly, htmp1, T_POLY);
+    GET(out0, Poly, hout0, T_POLY);
+    GET(out1, Poly, hout1, T_POLY);
+    TRY(rp_ring(*r, level, who));
+    if (r->N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r->N);
+    if (k < 0 || k >= r->logN) return fail(HE_EINVAL, "%s: k = %d out of range [0,%d]", who, k, r->logN - 1);
+    const int m = in0->batch;
+    TRY(rp_entries(2L * m, who));
+    TRY(rp_poly(*in0, r->ctx, r->N, m, level, who, "in0"));
+    TRY(rp_poly(*in1, r->ctx, r->N, m, level, who, "in1"));
+    TRY(rp_poly(*tmp0, r->ctx, r->N, m, level, who, "tmp0"));
+    TRY(rp_poly(*tmp1, r->ctx, r->N, m, level, who, "tmp1"));
+    TRY(rp_poly(*out0, r->ctx, r->N, sum_only ? m : 2 * m, level, who, "out0"));
+    TRY(rp_poly(*out1, r->ctx, r->N, sum_only ? m : 2 * m, level, who, "out1"));
+    std::vector<std::pair<int, int>> allowed;
+    if (sum_only) allowed = {{4, 0}, {5, 1}};
+    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {tmp0.get(), false, false}, {tmp1.get(), false, false},
+                              {out0.get(), true, false}, {out1.get(), true, false}}, allowed));
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    const bool so = sum_only != 0;
+    CoReq q;
+    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_EXPAND; q.par[1] = level; q.par[2] = k; q.par[3] = so;
+    q.ops = {in0->view(), in1->view(), tmp0->view(), tmp1->view(), out0->view(), out1->view()};
+    q.keep = {r, in0, in1, tmp0, tmp1, out0, out1};
+    q.run = [ctx, r, level, k, so](const View *v, int B) -> int {
+        RingPackIO io;
+        io.zsplit = B;
+        io.x[0] = v[0]; io.x[1] = v[1]; io.y[0] = v[2]; io.y[1] = v[3]; io.o[0] = v[4]; io.o[1] = v[5];
+        ctx->acct(2.0 * (level + 1) * (so ? 3.0 : 4.0), 0, B, r->N);
+        if (!so) { Valu V(r->logN); V.mul(false, 2.0 * (level + 1)); V.into(*ctx, B); }
+        HIP_TRY(launch_expand_step(r->dev, io, k, B, so, level + 1, 2 * B, ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    // (the second half of out lies m entries past the first: a request is its whole batch, whatever the queue's limit)
+    return co_dispatch(*ctx, m, q);
+}
+// the operands of a pack step: count pairs of single ciphertexts and T; fills the request (operands 4 z + {0, 1, 2, 3} = a0, a1, b0,
+// b1 of pair z, then t0, t1) and counts the pairs by kind
+static int rp_pack_operands(const char *who, const Ring &r, int level, int count, const he_handle *a0, const he_handle *a1, const he_handle *b0,
+                            const he_handle *b1, he_handle ht0, he_handle ht1, CoReq &q, int kinds[3]) {
+    TRY(rp_ring(r, level, who));
+    if (r.N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r.N);
+    if (count < 1) return fail(HE_EINVAL, "%s: count = %d, at least one pair is needed", who, count);
+    TRY(rp_entries(2L * count, who));
+    if (!a0 || !a1 || !b0 || !b1) return fail(HE_EINVAL, "%s: null handle array", who);
+    std::shared_ptr<Poly> t[2] = {get<Poly>(ht0, T_POLY), get<Poly>(ht1, T_POLY)};
+    if (!t[0] || !t[1]) return fail(HE_EHANDLE, "%s: bad Poly handle (t0 / t1)", who);
+    TRY(rp_poly(*t[0], r.ctx, r.N, count, level, who, "t0"));
+    TRY(rp_poly(*t[1], r.ctx, r.N, count, level, who, "t1"));
+    std::unordered_set<const uint64_t *> seen;
+    kinds[0] = kinds[1] = kinds[2] = 0;
+    const he_handle *hs[4] = {a0, a1, b0, b1};
+    for (int z = 0; z < count; z++) {
+        if ((a0[z] == 0) != (a1[z] == 0) || (b0[z] == 0) != (b1[z] == 0))
+            return fail(HE_EINVAL, "%s: pair %d: the two components of a ciphertext are both given or both 0", who, z);
+        if (!a0[z] && !b0[z]) return fail(HE_EINVAL, "%s: pair %d is empty", who, z);
+        kinds[a0[z] && b0[z] ? 0 : (a0[z] ? 1 : 2)]++;
+        for (int s = 0; s < 4; s++) {
+            if (!hs[s][z]) { q.ops.push_back(View{nullptr, 0}); continue; }
+            std::shared_ptr<Poly> p = get<Poly>(hs[s][z], T_POLY);
+            if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle %llu (pair %d)", who, (unsigned long long)hs[s][z], z);
+            TRY(rp_poly(*p, r.ctx, r.N, 1, level, who, "a / b"));
+            if (!seen.insert(p->d).second) return fail(HE_EINVAL, "%s: a handle occurs twice among the operands (pair %d)", who, z);
+            q.ops.push_back(p->view());
+            q.keep.push_back(p);
+        }
+    }
+    for (int c = 0; c < 2; c++) {
+        if (!seen.insert(t[c]->d).second) return fail(HE_EINVAL, "%s: a handle occurs twice among the operands (t%d)", who, c);
+        q.ops.push_back(t[c]->view());
+        q.keep.push_back(t[c]);
+    }
+    return HE_OK;
+}
+static int rp_pack_step(const char *who, he_handle hring, int level, int k, bool post, int count, const he_handle *a0, const he_handle *a1,
+                        const he_handle *b0, const he_handle *b1, he_handle ht0, he_handle ht1) {
+    std::shared_ptr<Ring> r = get<Ring>(hring, T_RING);
+    if (!r) return fail(HE_EHANDLE, "%s: bad Ring handle %llu", who, (unsigned long long)hring);
+    CoReq q;
+    int kinds[3];
+    TRY(rp_pack_operands(who, *r, level, count, a0, a1, b0, b1, ht0, ht1, q, kinds));
+    if (!post && (k < 0 || k >= r->logN)) return fail(HE_EINVAL, "%s: k = %d out of range [0,%d]", who, k, r->logN - 1);
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    // polynomial limbs moved per component and limb: pre -- both: a, b in, a, T out; one: 1 in, T out (+ b out); post -- 2 in, 1 out
+    const double words = post ? 3.0 * count : 4.0 * kinds[0] + 2.0 * kinds[1] + 3.0 * kinds[2];
+    const double muls = post ? 0.0 : (double)(kinds[0] + kinds[2]);
+    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = post ? RP_PACK_POST : RP_PACK_PRE; q.par[1] = level; q.par[2] = k; q.par[3] = count;
+    q.keep.push_back(r);
+    q.run = [ctx, r, level, k, post, count, words, muls](const View *v, int) -> int {
+        // the addresses of the pairs' polynomials, rows [a0 | a1 | b0 | b1]: a device table in scratch, filled from kernel arguments
+        std::vector<size_t> tab(4 * (size_t)count);
+        for (int z = 0; z < count; z++)
+            for (int s = 0; s < 4; s++) tab[(size_t)s * count + z] = (size_t)(uintptr_t)v[4 * z + s].p;
+        TRY(ctx->arena_reserve(tab.size() + 2));
+        size_t *d = reinterpret_cast<size_t *>(ctx->arena_take(tab.size()));
+        HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), ctx->stream));
+        ctx->acct(2.0 * (level + 1) * words, 0, 1, r->N);
+        if (muls > 0) { Valu V(r->logN); V.mul(false, 2.0 * (level + 1) * muls); V.into(*ctx, 1); }
+        HIP_TRY(launch_pack_step(r->dev, reinterpret_cast<const uint64_t *>(d), v[4 * count], v[4 * count + 1], k, post, count, 2.0 * words,
+                                 level + 1, ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*ctx, 1, q);
+}
+int he_ringpack_pack_pre(he_handle ring, int level, int k, int count, const he_handle *a0, const he_handle *a1, const he_handle *b0,
+                         const he_handle *b1, he_handle t0, he_handle t1) {
+    return rp_pack_step("he_ringpack_pack_pre", ring, level, k, false, count, a0, a1, b0, b1, t0, t1);
+}
+int he_ringpack_pack_post(he_handle ring, int level, int count, const he_handle *a0, const he_handle *a1, const he_handle *b0,
+                          const he_handle *b1, he_handle t0, he_handle t1) {
+    return rp_pack_step("he_ringpack_pack_post", ring, level, 0, true, count, a0, a1, b0, b1, t0, t1);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -377,6 +377,29 @@ hipError_t launch_ring_degree_replicate_ntt(const LimbTab &tab, RingSwitchIO io,
 // SwitchCiphertextRingDegree: down (up = false) out[w] = in[w gap]; up out[w gap] = in[w], the other words of out untouched
 hipError_t launch_ring_degree_stride(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, bool up, int batch, hipStream_t s);
 
+// ---- ring packing (core/rlwe/ring_packing.go) -----------------------------------------------------
+// Operands by ciphertext component: entries z < zsplit are component 0, the others component 1 (entry z - zsplit), so that both
+// components go in one launch (zsplit < 0 or >= batch: component 0 only).  x / y are read, o / p written; y and p are optional
+// where the launcher says so.  Limbs 0..nlimbs-1 of the ring's moduli, standard rings only.  No entry tables.
+struct RingPackIO {
+    View x[2] = {{nullptr, 0}, {nullptr, 0}}, y[2] = {{nullptr, 0}, {nullptr, 0}};
+    View o[2] = {{nullptr, 0}, {nullptr, 0}}, p[2] = {{nullptr, 0}, {nullptr, 0}};
+    int zsplit = -1;
+};
+// Split's ring map (:205-225), N -> N/2: o[j] = (x[2j] + x[2j+1]) / 2, p[j] = (x[2j] - x[2j+1]) RootsBackward[N/2 + j] / 2 (p optional)
+hipError_t launch_ring_split(const RingDev &large, RingPackIO io, int nlimbs, int batch, hipStream_t s);
+// Merge's ring map (:410-417), N/2 -> N: o[2j] = x[j] + w y[j], o[2j+1] = x[j] - w y[j], w = RootsForward[N/2 + j] (y optional:
+// the replication of x)
+hipError_t launch_ring_merge(const RingDev &large, RingPackIO io, int nlimbs, int batch, hipStream_t s);
+// Expand's inner step (:528-559): o[e] = x[e] + y[e], o[e + m] = (x[e] - y[e]) XInvPow2NTT[k]; batch = entries of both components
+hipError_t launch_expand_step(const RingDev &r, RingPackIO io, int k, int m, bool sum_only, int nlimbs, int batch, hipStream_t s);
+// out = XPow2NTT[k] (div: XInvPow2NTT[k]) of GenXPow2NTT (:772-810), read off the resident twiddles
+hipError_t launch_xpow2_fill(const RingDev &r, View out, int k, bool div, int nlimbs, int batch, hipStream_t s);
+// Pack's inner step (:697-765) before (post = false, x = XPow2NTT[k]) and after the automorphism of T over `count` pairs; tab: a
+// device array [4][count] of the addresses of (a0 | a1 | b0 | b1), 0 = absent; words: polynomial limbs moved, for the profile
+hipError_t launch_pack_step(const RingDev &r, const uint64_t *tab, View t0, View t1, int k, bool post, int count, double words,
+                            int nlimbs, hipStream_t s);
+
 // ---- ciphertext tensor product (schemes/ckks/evaluator.go:807-820, schemes/bgv/evaluator.go:634-647)
 // c0 = MRed(MRed(a0,s),b0), c2 = MRed(MRed(a1,s),b1), c1 = CRed(MRed(MRed(a0,s),b1) + MRed(MRed(a1,s),b0))
 // with the per-limb scalar s = 2^128 mod q (CKKS: MForm) or t*2^128 mod q (BGV: tMontgomery).
@@ -387,7 +410,8 @@ hipError_t launch_tensor(const RingDev &r, const LimbTab &tab, const uint64_t *s
 enum KernelId {
     K_NTT_COLS_FWD = 0, K_NTT_ROWS_FWD, K_NTT_ROWS_INV, K_NTT_COLS_INV, K_EW, K_GATHER, K_AUTO_COEFF, K_INDEX,
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
-    K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_COUNT
+    K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
+    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

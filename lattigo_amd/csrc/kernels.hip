@@ -72,7 +72,8 @@ const char *kernel_name(int id) {
                                          "automorphism_coeff", "build_index", "modup", "center_copy", "ks_inner",
                                          "tensor", "modmul_probe", "ci_fold", "mask_spread", "ntt_rows_fwd_f64",
                                          "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
-                                         "ring_degree_replicate_ntt", "ring_degree_stride"};
+                                         "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
+                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -2898,6 +2899,236 @@ hipError_t launch_ring_degree_stride(const LimbTab &tab, RingSwitchIO io, int n_
     ProfScope ps(K_RING_STRIDE, s, 2.0 * n_small * tab.n * batch * 8.0);
     if (up) hipLaunchKernelGGL((ring_stride_kernel<true>), grid, block, 0, s, A);
     else hipLaunchKernelGGL((ring_stride_kernel<false>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// ring packing (core/rlwe/ring_packing.go): Split / Merge butterflies, the inner steps of Expand and Pack
+// ------------------------------------------------------------------------------------
+// The reference multiplies by the monomial tables XPow2NTT[k] = NTT(X^(2^k)) and XInvPow2NTT[k] = NTT(X^(-2^k)) (GenXPow2NTT,
+// :772-810).  Those tables are views of the resident twiddles: word j is w = Roots[(N >> (k+1)) + (j >> (k+1))] where bit k of j is
+// clear and q - w where it is set, with Roots = RootsForward for X^(2^k), RootsBackward for X^(-2^k), Montgomery form included.  So no
+// kernel here reads a monomial table: a thread takes its two words (j even) from one twiddle load.
+struct RingPackArgs {
+    const uint64_t *x[2], *y[2];  // inputs by component (y: the optional / second one)
+    uint64_t *o[2], *p[2];        // outputs by component (p: the optional / second one)
+    size_t x_bs[2], y_bs[2], o_bs[2], p_bs[2];
+    int zsplit;  // entries z >= zsplit are component 1 (entry z - zsplit)
+    int N;       // the ring degree (the large one in Split / Merge)
+    int k;       // which table of the family
+    int m;       // expand step: the input batch (entry e + m of the output is the second half)
+    int sum_only;
+    const ModConst *mc;
+    const uint64_t *tw;  // [n_mod][N] RootsForward or RootsBackward of the ring
+};
+__device__ __forceinline__ ulonglong2 xpow2_pair(const uint64_t *tw_row, int N, int k, int j, uint64_t q) {
+    const uint64_t w = tw_row[(N >> (k + 1)) + (j >> (k + 1))];
+    if (k == 0) return make_ulonglong2(w, q - w);
+    const uint64_t x = ((j >> k) & 1) ? q - w : w;
+    return make_ulonglong2(x, x);
+}
+// x / 2 mod q for x in [0, q), q odd: canonical, the word MRed(x, MForm(2^-1)) gives
+__device__ __forceinline__ uint64_t halve(uint64_t x, uint64_t q) { return (x & 1) ? (x + q) >> 1 : x >> 1; }
+// Split after its key switch (:205-225): SwitchCiphertextRingDegreeNTT(t) and SwitchCiphertextRingDegreeNTT(t * XInvPow2NTT[0]) as
+// ONE inverse butterfly per output word: with a = t[2j], b = t[2j+1], even[j] = (a + b) / 2, odd[j] = (a - b) w^-1 / 2,
+// w^-1 = RootsBackward[N/2 + j].  Two outputs per half per thread; canonical inputs, canonical outputs.
+__global__ void __launch_bounds__(256) ring_split_kernel(RingPackArgs A) {
+    const int n = A.N >> 1;
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= n) return;
+    const int y = blockIdx.y, c = (int)blockIdx.z >= A.zsplit;
+    const size_t z = blockIdx.z - (c ? A.zsplit : 0);
+    const uint64_t q = A.mc[y].q, qinv = A.mc[y].qinv;
+    const uint64_t *in = A.x[c] + z * A.x_bs[c] + (size_t)y * A.N + 2 * (size_t)j;
+    const ulonglong2 u = ldnt2(in), v = ldnt2(in + 2);
+    ulonglong2 e;
+    e.x = halve(cred(u.x + u.y, q), q);
+    e.y = halve(cred(v.x + v.y, q), q);
+    *reinterpret_cast<ulonglong2 *>(A.o[c] + z * A.o_bs[c] + (size_t)y * n + j) = e;
+    if (A.p[c]) {
+        const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(A.tw + (size_t)y * A.N + n + j);
+        ulonglong2 o;  // (a + q - b lies in [1, 2q): any 64-bit left operand is in mred's domain, the product's high word stays below q)
+        o.x = halve(mred(u.x + q - u.y, w.x, q, qinv), q);
+        o.y = halve(mred(v.x + q - v.y, w.y, q, qinv), q);
+        *reinterpret_cast<ulonglong2 *>(A.p[c] + z * A.p_bs[c] + (size_t)y * n + j) = o;
+    }
+}
+// Merge before its key switch (:410-417): replicate(e) + replicate(o) * XPow2NTT[0] as ONE forward butterfly per input word:
+// out[2j] = e[j] + w o[j], out[2j+1] = e[j] - w o[j], w = RootsForward[N/2 + j]; without o the replication of e
+__global__ void __launch_bounds__(256) ring_merge_kernel(RingPackArgs A) {
+    const int n = A.N >> 1;
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= n) return;
+    const int y = blockIdx.y, c = (int)blockIdx.z >= A.zsplit;
+    const size_t z = blockIdx.z - (c ? A.zsplit : 0);
+    const uint64_t q = A.mc[y].q, qinv = A.mc[y].qinv;
+    const ulonglong2 e = ldnt2(A.x[c] + z * A.x_bs[c] + (size_t)y * n + j);
+    ulonglong2 r0 = make_ulonglong2(e.x, e.x), r1 = make_ulonglong2(e.y, e.y);
+    if (A.y[c]) {
+        const ulonglong2 o = ldnt2(A.y[c] + z * A.y_bs[c] + (size_t)y * n + j);
+        const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(A.tw + (size_t)y * A.N + n + j);
+        const uint64_t t0 = mred(o.x, w.x, q, qinv), t1 = mred(o.y, w.y, q, qinv);
+        r0 = make_ulonglong2(cred(e.x + t0, q), cred(e.x + q - t0, q));
+        r1 = make_ulonglong2(cred(e.y + t1, q), cred(e.y + q - t1, q));
+    }
+    uint64_t *out = A.o[c] + z * A.o_bs[c] + (size_t)y * A.N + 2 * (size_t)j;
+    reinterpret_cast<ulonglong2 *>(out)[0] = r0;
+    reinterpret_cast<ulonglong2 *>(out)[1] = r1;
+}
+// Expand's inner step at n = 2^k (:528-559): out[e] = in[e] + tmp[e], out[e + m] = (in[e] - tmp[e]) * XInvPow2NTT[k];
+// sum_only: the first half alone (out may be in: every thread reads its words before it writes them)
+__global__ void __launch_bounds__(256) expand_step_kernel(RingPackArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, c = (int)blockIdx.z >= A.zsplit;
+    const size_t z = blockIdx.z - (c ? A.zsplit : 0);
+    const uint64_t q = A.mc[y].q, qinv = A.mc[y].qinv;
+    const size_t off = (size_t)y * A.N + j;
+    const ulonglong2 a = ldnt2(A.x[c] + z * A.x_bs[c] + off), t = ldnt2(A.y[c] + z * A.y_bs[c] + off);
+    ulonglong2 s;
+    s.x = cred(a.x + t.x, q);
+    s.y = cred(a.y + t.y, q);
+    *reinterpret_cast<ulonglong2 *>(A.o[c] + z * A.o_bs[c] + off) = s;
+    if (!A.sum_only) {
+        const ulonglong2 x = xpow2_pair(A.tw + (size_t)y * A.N, A.N, A.k, j, q);
+        ulonglong2 d;
+        d.x = mred(a.x + q - t.x, x.x, q, qinv);
+        d.y = mred(a.y + q - t.y, x.y, q, qinv);
+        *reinterpret_cast<ulonglong2 *>(A.o[c] + (z + A.m) * A.o_bs[c] + off) = d;
+    }
+}
+// one table of the family as a polynomial (the naive paths and the tests; the fused entries never materialise one)
+__global__ void __launch_bounds__(256) xpow2_fill_kernel(RingPackArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y;
+    const ulonglong2 x = xpow2_pair(A.tw + (size_t)y * A.N, A.N, A.k, j, A.mc[y].q);
+    *reinterpret_cast<ulonglong2 *>(A.o[0] + (size_t)blockIdx.z * A.o_bs[0] + (size_t)y * A.N + j) = x;
+}
+// Pack's inner step (:697-765) over a pair list.  Entry z < count is component 0 of pair z, entry count + z component 1.  a and b
+// are unrelated single polynomials: tab holds their device addresses, rows [a0 | a1 | b0 | b1] of count words, 0 = absent.
+struct PackArgs {
+    const uint64_t *tab;
+    uint64_t *t[2];
+    size_t t_bs[2];
+    int count, N, k;
+    const ModConst *mc;
+    const uint64_t *tw;
+};
+// x = XPow2NTT[k]; both: T = a - b x, a += b x; a only: T = a; b only: b = b x, T = b x (the automorphism of T follows)
+__global__ void __launch_bounds__(256) pack_pre_kernel(PackArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, c = (int)blockIdx.z >= A.count;
+    const size_t z = blockIdx.z - (c ? A.count : 0);
+    const uint64_t q = A.mc[y].q, qinv = A.mc[y].qinv;
+    const size_t off = (size_t)y * A.N + j;
+    uint64_t *a = reinterpret_cast<uint64_t *>(ldc(A.tab, (size_t)c * A.count + z));
+    uint64_t *b = reinterpret_cast<uint64_t *>(ldc(A.tab, (size_t)(2 + c) * A.count + z));
+    ulonglong2 T;
+    if (b) {
+        const ulonglong2 x = xpow2_pair(A.tw + (size_t)y * A.N, A.N, A.k, j, q), bv = ldnt2(b + off);
+        ulonglong2 bx;
+        bx.x = mred(bv.x, x.x, q, qinv);
+        bx.y = mred(bv.y, x.y, q, qinv);
+        if (a) {
+            const ulonglong2 av = ldnt2(a + off);
+            T.x = cred(av.x + q - bx.x, q);
+            T.y = cred(av.y + q - bx.y, q);
+            ulonglong2 s;
+            s.x = cred(av.x + bx.x, q);
+            s.y = cred(av.y + bx.y, q);
+            *reinterpret_cast<ulonglong2 *>(a + off) = s;
+        } else {
+            T = bx;
+            *reinterpret_cast<ulonglong2 *>(b + off) = bx;
+        }
+    } else {
+        T = ldnt2(a + off);
+    }
+    *reinterpret_cast<ulonglong2 *>(A.t[c] + z * A.t_bs[c] + off) = T;
+}
+// after the automorphism of T: a += T where a is present, b -= T otherwise
+__global__ void __launch_bounds__(256) pack_post_kernel(PackArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, c = (int)blockIdx.z >= A.count;
+    const size_t z = blockIdx.z - (c ? A.count : 0);
+    const uint64_t q = A.mc[y].q;
+    const size_t off = (size_t)y * A.N + j;
+    uint64_t *a = reinterpret_cast<uint64_t *>(ldc(A.tab, (size_t)c * A.count + z));
+    uint64_t *b = reinterpret_cast<uint64_t *>(ldc(A.tab, (size_t)(2 + c) * A.count + z));
+    const ulonglong2 T = ldnt2(A.t[c] + z * A.t_bs[c] + off);
+    uint64_t *dst = a ? a : b;
+    const ulonglong2 v = ldnt2(dst + off);
+    ulonglong2 r;
+    r.x = a ? cred(v.x + T.x, q) : cred(v.x + q - T.x, q);
+    r.y = a ? cred(v.y + T.y, q) : cred(v.y + q - T.y, q);
+    *reinterpret_cast<ulonglong2 *>(dst + off) = r;
+}
+static bool rp_args(RingPackArgs &A, const RingDev &r, bool backward, const RingPackIO &io, int nlimbs, int batch) {
+    if (nlimbs <= 0 || nlimbs > kMaxLimbs || batch <= 0 || batch > 65535 || r.N < 16) return false;  // (batch is gridDim.z)
+    for (int c = 0; c < 2; c++) {
+        if (!no_tab({io.x[c], io.y[c], io.o[c], io.p[c]})) return false;
+        A.x[c] = io.x[c].p; A.y[c] = io.y[c].p; A.o[c] = io.o[c].p; A.p[c] = io.p[c].p;
+        A.x_bs[c] = io.x[c].bstride; A.y_bs[c] = io.y[c].bstride; A.o_bs[c] = io.o[c].bstride; A.p_bs[c] = io.p[c].bstride;
+    }
+    A.zsplit = io.zsplit >= 0 && io.zsplit < batch ? io.zsplit : batch;
+    if (A.zsplit < batch && !A.o[1]) return false;
+    A.N = r.N; A.mc = r.mc; A.tw = backward ? r.tw_inv : r.tw_fwd;
+    return true;
+}
+hipError_t launch_ring_split(const RingDev &large, RingPackIO io, int nlimbs, int batch, hipStream_t s) {
+    RingPackArgs A{};
+    if (!rp_args(A, large, true, io, nlimbs, batch) || large.N < 32 || !io.x[0].p || !io.o[0].p) return hipErrorInvalidValue;
+    const int n = large.N / 2;
+    const bool odd = io.p[0].p != nullptr;
+    dim3 grid((unsigned)((n / 2 + 255) / 256), nlimbs, batch), block(256);
+    ProfScope ps(K_RING_SPLIT, s, ((double)large.N + (odd ? 2.0 : 1.0) * n) * nlimbs * batch * 8.0 + (odd ? (double)n * nlimbs * 8.0 : 0.0));
+    hipLaunchKernelGGL(ring_split_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_ring_merge(const RingDev &large, RingPackIO io, int nlimbs, int batch, hipStream_t s) {
+    RingPackArgs A{};
+    if (!rp_args(A, large, false, io, nlimbs, batch) || large.N < 32 || !io.x[0].p || !io.o[0].p) return hipErrorInvalidValue;
+    const int n = large.N / 2;
+    const bool odd = io.y[0].p != nullptr;
+    dim3 grid((unsigned)((n / 2 + 255) / 256), nlimbs, batch), block(256);
+    ProfScope ps(K_RING_MERGE, s, ((double)large.N + (odd ? 2.0 : 1.0) * n) * nlimbs * batch * 8.0 + (odd ? (double)n * nlimbs * 8.0 : 0.0));
+    hipLaunchKernelGGL(ring_merge_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_expand_step(const RingDev &r, RingPackIO io, int k, int m, bool sum_only, int nlimbs, int batch, hipStream_t s) {
+    RingPackArgs A{};
+    if (!rp_args(A, r, true, io, nlimbs, batch) || k < 0 || k >= r.logN || m < 1 || !io.x[0].p || !io.y[0].p || !io.o[0].p) return hipErrorInvalidValue;
+    A.k = k; A.m = m; A.sum_only = sum_only ? 1 : 0;
+    dim3 grid((unsigned)((r.N / 2 + 255) / 256), nlimbs, batch), block(256);
+    ProfScope ps(K_EXPAND_STEP, s, (double)r.N * nlimbs * batch * 8.0 * (sum_only ? 3.0 : 4.0));
+    hipLaunchKernelGGL(expand_step_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_xpow2_fill(const RingDev &r, View out, int k, bool div, int nlimbs, int batch, hipStream_t s) {
+    RingPackArgs A{};
+    RingPackIO io;
+    io.o[0] = out;
+    if (!rp_args(A, r, div, io, nlimbs, batch) || k < 0 || k >= r.logN || !out.p) return hipErrorInvalidValue;
+    A.k = k;
+    dim3 grid((unsigned)((r.N / 2 + 255) / 256), nlimbs, batch), block(256);
+    ProfScope ps(K_XPOW2_FILL, s, (double)r.N * nlimbs * batch * 8.0);
+    hipLaunchKernelGGL(xpow2_fill_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_pack_step(const RingDev &r, const uint64_t *tab, View t0, View t1, int k, bool post, int count, double words,
+                            int nlimbs, hipStream_t s) {
+    if (nlimbs <= 0 || nlimbs > kMaxLimbs || count <= 0 || 2 * (long)count > 65535 || r.N < 16 || !tab || !t0.p || !t1.p || !no_tab({t0, t1})) return hipErrorInvalidValue;
+    if (!post && (k < 0 || k >= r.logN)) return hipErrorInvalidValue;
+    PackArgs A{};
+    A.tab = tab; A.t[0] = t0.p; A.t[1] = t1.p; A.t_bs[0] = t0.bstride; A.t_bs[1] = t1.bstride;
+    A.count = count; A.N = r.N; A.k = k; A.mc = r.mc; A.tw = r.tw_fwd;
+    dim3 grid((unsigned)((r.N / 2 + 255) / 256), nlimbs, 2 * count), block(256);
+    ProfScope ps(post ? K_PACK_POST : K_PACK_PRE, s, words * r.N * nlimbs * 8.0);
+    if (post) hipLaunchKernelGGL(pack_post_kernel, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(pack_pre_kernel, grid, block, 0, s, A);
     return hipGetLastError();
 }
 

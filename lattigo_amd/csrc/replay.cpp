@@ -26,6 +26,7 @@
 #include "../../include/hering.h"
 #include "../../include/hering_debug.h"
 #include "../../include/hering_ringswitch.h"
+#include "../../include/hering_ringpack.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -35,7 +36,8 @@ enum Fn : uint64_t {
     F_AUTO_INDEX, F_AUTO_INDEX_ADD, F_AUTO_COEFF, F_MODUP_QP, F_MODUP_PQ, F_MODDOWN_BE, F_EVAL_MODDOWN, F_DECOMP_CREATE, F_DECOMP_DESTROY,
     F_DECOMPOSE_NTT, F_GP_LAZY, F_GP_HOISTED_LAZY, F_MODDOWN, F_GP, F_GP_HOISTED, F_RELIN, F_AUTO_CT, F_AUTO_HOISTED, F_AUTO_HOISTED_LAZY,
     F_CENTERED_LIFT, F_DECOMP_FILL, F_LINTRANS, F_CKKS_MUL, F_BGV_MUL, F_GIANT_STEP,
-    F_MAP_SMALL_TO_LARGE, F_SWITCH_RING_NTT, F_SWITCH_RING, F_APPLY_EVK, F_COUNT
+    F_MAP_SMALL_TO_LARGE, F_SWITCH_RING_NTT, F_SWITCH_RING, F_APPLY_EVK,
+    F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST, F_COUNT
 };
 struct Arg {
     uint64_t kind = 0, val = 0;
@@ -159,6 +161,14 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
         case F_SWITCH_RING_NTT: return he_switch_ring_degree_ntt(H(0), (int)I(1), H(2), H(3));
         case F_SWITCH_RING: return he_switch_ring_degree((int)I(0), H(1), H(2));
         case F_APPLY_EVK: return he_apply_evaluation_key(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6));
+        case F_RING_XPOW2: return he_ring_xpow2_ntt(H(0), (int)I(1), (int)I(2), (int)I(3), H(4));
+        case F_RING_SPLIT: return he_ring_split_ntt(H(0), (int)I(1), H(2), H(3), H(4));
+        case F_RING_MERGE: return he_ring_merge_ntt(H(0), (int)I(1), H(2), H(3), H(4));
+        case F_RP_SPLIT: return he_ringpack_split(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6), H(7), H(8));
+        case F_RP_MERGE: return he_ringpack_merge(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6), H(7), H(8));
+        case F_RP_EXPAND_STEP: return he_ringpack_expand_step(H(0), (int)I(1), (int)I(2), (int)I(3), H(4), H(5), H(6), H(7), H(8), H(9));
+        case F_RP_PACK_PRE: return he_ringpack_pack_pre(H(0), (int)I(1), (int)I(2), (int)I(3), HA(4), HA(5), HA(6), HA(7), H(8), H(9));
+        case F_RP_PACK_POST: return he_ringpack_pack_post(H(0), (int)I(1), (int)I(2), HA(3), HA(4), HA(5), HA(6), H(7), H(8));
         default: return HE_EINVAL;
     }
 }

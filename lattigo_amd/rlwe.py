@@ -346,6 +346,352 @@ class GaloisKeySet:
         return self.keys[galEl]
 
 
+# ---- the ring-packing evaluator (core/rlwe/ring_packing.go; include/hering_ringpack.h) -------------------------------------------
+def GaloisElementsForExpand(nth_root: int, logN: int):
+    """rlwe.GaloisElementsForExpand (core/rlwe/ring_packing_keys.go:143)"""
+    return [nth_root // (2 << i) + 1 for i in range(logN)]
+
+
+def GaloisElementsForPack(nth_root: int, logN_ring: int, logGap: int):
+    """rlwe.GaloisElementsForPack (core/rlwe/ring_packing_keys.go:156), standard ring"""
+    if logGap > logN_ring or logGap < 0:
+        raise ValueError("cannot GaloisElementsForPack: logGap > logN || logGap < 0")
+    galEls = [GaloisElement(nth_root, 1 << i) for i in range(logGap)]
+    if logGap == logN_ring:
+        galEls.append(nth_root - 1)  # GaloisElementOrderTwoOrthogonalSubgroup
+    return galEls
+
+
+def getMinimumGap(lst):
+    """core/rlwe/ring_packing.go:812: (the odd part of the smallest gap, log2 of its power-of-two part) of a sorted index list"""
+    gap, logGap = 0x7FFFFFFFFFFFFFFF, 0
+    for a, b in zip(lst, lst[1:]):
+        if a > b:
+            raise ValueError("invalid index list: element must be sorted from smallest to largest")
+        if a == b:
+            raise ValueError("invalid index list: contains duplicated elements")
+        gap = min(gap, b - a)
+        if gap == 1:
+            break
+    while gap & 1 == 0:
+        logGap += 1
+        gap >>= 1
+    return gap, logGap
+
+
+def XPow2NTT(ring: Ring, level: int, i: int, div: bool, out: Poly):
+    """GenXPow2NTT(ring.AtLevel(level), logN, div)[i] (core/rlwe/ring_packing.go:772), read off the resident twiddle tables"""
+    check(load().he_ring_xpow2_ntt(ring.h, level, i, int(div), out.h))
+
+
+def SplitNTT(ringLarge: Ring, level: int, pIn: Poly, outEven: Poly, outOdd: Poly | None = None):
+    """the ring maps of Split (core/rlwe/ring_packing.go:205-225) on one polynomial"""
+    check(load().he_ring_split_ntt(ringLarge.h, level, pIn.h, outEven.h, outOdd.h if outOdd is not None else 0))
+
+
+def MergeNTT(ringLarge: Ring, level: int, inEven: Poly, inOdd: Poly | None, out: Poly):
+    """the ring maps of Merge (core/rlwe/ring_packing.go:410-417) on one polynomial"""
+    check(load().he_ring_merge_ntt(ringLarge.h, level, inEven.h, inOdd.h if inOdd is not None else 0, out.h))
+
+
+def _harr(polys):
+    return (H * len(polys))(*[p.h if p is not None else 0 for p in polys])
+
+
+class RingPackingEvaluator:
+    """rlwe.RingPackingEvaluator (core/rlwe/ring_packing.go:13) on device-resident ciphertexts.
+
+    Evaluators: {logN: Evaluator} (rings of the same moduli at every degree); RingSwitchingKeys: {(logN_from, logN_to):
+    EvaluationKey of the evaluator of the larger degree}; RepackKeys / ExtractKeys: {logN: GaloisKeySet}.  Ciphertexts are
+    [Poly, Poly] in the NTT domain unless isNTT=False is passed, and every method takes the level explicitly.
+
+    No monomial table is kept: the fused entries read XPow2NTT / XInvPow2NTT off the twiddle tables, and the naive paths
+    materialise the few they need (XPow2NTT above).
+
+    Input ciphertexts are CONSUMED: Pack, Repack[Naive] and Extract[Naive] overwrite their inputs with intermediates, as the
+    reference does."""
+
+    def __init__(self, Evaluators: dict, RingSwitchingKeys: dict | None = None, RepackKeys: dict | None = None,
+                 ExtractKeys: dict | None = None):
+        self.Evaluators = dict(Evaluators)
+        self.RingSwitchingKeys = dict(RingSwitchingKeys or {})
+        self.RepackKeys, self.ExtractKeys = RepackKeys, ExtractKeys
+
+    def MinLogN(self):
+        return min(self.Evaluators)
+
+    def MaxLogN(self):
+        return max(self.Evaluators)
+
+    def NewCiphertext(self, logN, level, batch=1):
+        r = self.Evaluators[logN].ringQ
+        return [Poly(r, level + 1, batch, zero=False) for _ in range(2)]
+
+    @staticmethod
+    def _logN(ct):
+        return ct[0].N.bit_length() - 1
+
+    def _modulus(self, logN, level):
+        Q = 1
+        for m in self.Evaluators[logN].ringQ.ModuliChain()[: level + 1]:
+            Q *= int(m)
+        return Q
+
+    # ---- Split (:173): ctN = ctEvenNHalf(Y) + X ctOddNHalf(Y), Y = X^2; one key switch and one streaming launch
+    def Split(self, level, ctN, ctEvenNHalf, ctOddNHalf=None):
+        if self.MinLogN() == self.MaxLogN():
+            raise ValueError("method is not supported when eval.MinLogN() == eval.MaxLogN()")
+        LogN = self._logN(ctN)
+        if LogN <= self.MinLogN():
+            raise ValueError("ctN.Log() must be greater than eval.MinLogN()")
+        if ctEvenNHalf is None:
+            raise ValueError("ctEvenNHalf cannot be nil")
+        if self._logN(ctEvenNHalf) != LogN - 1:
+            raise ValueError("ctEvenNHalf.LogN() must be equal to ctN.LogN()-1")
+        if ctOddNHalf is not None and self._logN(ctOddNHalf) != LogN - 1:
+            raise ValueError("ctOddNHalf.LogN() must be equal to ctN.LogN()-1")
+        o = ctOddNHalf if ctOddNHalf is not None else [None, None]
+        check(load().he_ringpack_split(self.Evaluators[LogN].h, level, ctN[0].h, ctN[1].h, self.RingSwitchingKeys[(LogN, LogN - 1)].h,
+                                       ctEvenNHalf[0].h, ctEvenNHalf[1].h, o[0].h if o[0] else 0, o[1].h if o[1] else 0))
+
+    def SplitNew(self, level, ctN):
+        LogN = self._logN(ctN)
+        even, odd = self.NewCiphertext(LogN - 1, level, ctN[0].batch), self.NewCiphertext(LogN - 1, level, ctN[0].batch)
+        self.Split(level, ctN, even, odd)
+        return even, odd
+
+    # ---- Merge (:376)
+    def Merge(self, level, ctEvenNHalf, ctOddNHalf, ctN):
+        if self.MinLogN() == self.MaxLogN():
+            raise ValueError("method is not supported when eval.MinLogN() == eval.MaxLogN()")
+        if ctEvenNHalf is None:
+            raise ValueError("ctEvenNHalf cannot be nil")
+        if self._logN(ctEvenNHalf) >= self.MaxLogN():
+            raise ValueError("ctEvenNHalf.LogN() must be smaller than eval.MaxLogN()")
+        LogN = self._logN(ctN)
+        if LogN != self._logN(ctEvenNHalf) + 1:
+            raise ValueError("ctN.LogN() must be equal to ctEvenNHalf.LogN()+1")
+        if ctOddNHalf is not None and self._logN(ctOddNHalf) != LogN - 1:
+            raise ValueError("ctEvenNHalf.LogN() and ctOddNHalf.LogN() must be equal")
+        o = ctOddNHalf if ctOddNHalf is not None else [None, None]
+        check(load().he_ringpack_merge(self.Evaluators[LogN].h, level, ctEvenNHalf[0].h, ctEvenNHalf[1].h, o[0].h if o[0] else 0,
+                                       o[1].h if o[1] else 0, self.RingSwitchingKeys[(LogN - 1, LogN)].h, ctN[0].h, ctN[1].h))
+
+    def MergeNew(self, level, ctEvenNHalf, ctOddNHalf):
+        if ctEvenNHalf is None:
+            raise ValueError("ctEvenNHalf cannot be nil")
+        ctN = self.NewCiphertext(self._logN(ctEvenNHalf) + 1, level, ctEvenNHalf[0].batch)
+        self.Merge(level, ctEvenNHalf, ctOddNHalf, ctN)
+        return ctN
+
+    # ---- Expand (:448).  The map stays ONE batched handle: entry e <-> index e * 2^logGap.  Per level one batched Automorphism
+    # over the live entries and one he_ringpack_expand_step.  Returns ([Poly, Poly] of len(indices) entries, indices).
+    def Expand(self, level, ct, logGap: int, isNTT: bool = True):
+        logN = self._logN(ct)
+        if logN not in self.Evaluators:
+            raise ValueError(f"eval.Parameters[{logN}] is nil")
+        if self.ExtractKeys is None:
+            raise ValueError("eval.ExtractKeys is nil")
+        if logN not in self.ExtractKeys:
+            raise ValueError(f"eval.ExtractKeys[{logN}] is nil")
+        ev, gks = self.Evaluators[logN], self.ExtractKeys[logN]
+        if getattr(ev.ringQ, "conjugate_invariant", False):
+            raise ValueError("method is only supported for ring.Type = ring.Standard")
+        rQ = ev.ringQ.AtLevel(level)
+        N, gap = 1 << logN, 1 << logGap
+        NInv = pow(N, -1, self._modulus(logN, level))
+        cur = self.NewCiphertext(logN, level)
+        for a, b in zip(ct, cur):
+            if not isNTT:
+                rQ.NTT(a, b)
+                rQ.MulScalarBigint(b, NInv, b)
+            else:
+                rQ.MulScalarBigint(a, NInv, b)
+        m = 1
+        L = load()
+        for i in range(logN):
+            n = 1 << i
+            galEl = N // n + 1
+            tmp = self.NewCiphertext(logN, level, m)
+            ev.Automorphism(level, cur, galEl, gks.GetGaloisKey(galEl), tmp)
+            if n >= gap:  # (j + n / gap > 0 for every live j)
+                out = self.NewCiphertext(logN, level, 2 * m)
+                check(L.he_ringpack_expand_step(ev.ringQ.h, level, i, 0, cur[0].h, cur[1].h, tmp[0].h, tmp[1].h, out[0].h, out[1].h))
+                cur, m = out, 2 * m
+            else:         # (the lone entry 0: the sum alone, in place)
+                check(L.he_ringpack_expand_step(ev.ringQ.h, level, i, 1, cur[0].h, cur[1].h, tmp[0].h, tmp[1].h, cur[0].h, cur[1].h))
+        if not isNTT:
+            for c in cur:
+                rQ.INTT(c, c)
+        return cur, [e * gap for e in range(m)]
+
+    # ---- Pack (:573); cts: {index: [Poly, Poly]}, consumed
+    def Pack(self, level, cts: dict, inputLogGap: int, zeroGarbageSlots: bool, isNTT: bool = True):
+        if len(cts) == 0:
+            raise ValueError("len(cts) = 0")
+        cts = dict(cts)
+        keys = sorted(cts)
+        logN = self._logN(cts[keys[0]])
+        if logN not in self.Evaluators:
+            raise ValueError(f"eval.Parameters[{logN}] is nil")
+        if self.RepackKeys is None:
+            raise ValueError("eval.RepackKeys is nil")
+        if logN not in self.RepackKeys:
+            raise ValueError(f"eval.RepackKeys[{logN}] is nil")
+        ev, gks = self.Evaluators[logN], self.RepackKeys[logN]
+        if getattr(ev.ringQ, "conjugate_invariant", False):
+            raise ValueError("procedure is only supported for ring.Type = ring.Standard")
+        N = 1 << logN
+        if len(keys) > 1:
+            gap, logGap = getMinimumGap(keys)
+        else:
+            gap, logGap = N, logN
+        rQ = ev.ringQ.AtLevel(level)
+        logStart, logEnd = logN - inputLogGap, logN
+        if not zeroGarbageSlots and gap > 0:
+            logEnd -= logGap
+        if logStart >= logEnd:
+            raise ValueError("gaps between ciphertexts is smaller than inputLogGap > N")
+        NInv = pow(1 << (logEnd - logStart), -1, self._modulus(logN, level))
+        for key in keys:
+            for c in cts[key]:
+                if not isNTT:
+                    rQ.NTT(c, c)
+                rQ.MulScalarBigint(c, NInv, c)
+        L = load()
+        for i in range(logStart, logEnd):
+            t = 1 << (logN - 1 - i)
+            pairs = []
+            for jx in sorted({j & (t - 1) for j in cts if j < 2 * t}):
+                a, b = cts.get(jx), cts.get(jx + t)
+                if a is not None or b is not None:
+                    pairs.append((jx, a, b))
+            if not pairs:
+                continue
+            count = len(pairs)
+            nil = [None, None]
+            a0, a1 = _harr([(a or nil)[0] for _, a, _ in pairs]), _harr([(a or nil)[1] for _, a, _ in pairs])
+            b0, b1 = _harr([(b or nil)[0] for _, _, b in pairs]), _harr([(b or nil)[1] for _, _, b in pairs])
+            T = self.NewCiphertext(logN, level, count)
+            galEl = 2 * N - 1 if i == 0 else GaloisElement(2 * N, 1 << (i - 1))
+            check(L.he_ringpack_pack_pre(ev.ringQ.h, level, logN - 1 - i, count, a0, a1, b0, b1, T[0].h, T[1].h))
+            ev.Automorphism(level, T, galEl, gks.GetGaloisKey(galEl), T)
+            check(L.he_ringpack_pack_post(ev.ringQ.h, level, count, a0, a1, b0, b1, T[0].h, T[1].h))
+            for jx, a, b in pairs:
+                if b is not None:
+                    if a is None:
+                        cts[jx] = b
+                    del cts[jx + t]
+        out = cts[0]
+        if not isNTT:
+            for c in out:
+                rQ.INTT(c, c)
+        return out
+
+    # ---- Extract / ExtractNaive (:52-171): {index: [Poly, Poly] of degree 2^MinLogN}
+    def Extract(self, level, ct, idx):
+        return self._extract(level, ct, idx, False)
+
+    def ExtractNaive(self, level, ct, idx):
+        return self._extract(level, ct, idx, True)
+
+    def _extract(self, level, ct, idx, naive: bool):
+        logNMax, logNMin = self._logN(ct), self.MinLogN()
+        logNFactor = logNMax - logNMin
+        NFactor = 1 << logNFactor
+        keys = sorted(idx)
+        _, logGap = getMinimumGap(keys)
+        tmpCts = {0: ct}
+        for i in range(logNFactor):
+            t = 1 << i
+            logGap = max(0, logGap - 1)
+            for j in range(t):
+                if j in tmpCts:
+                    tmpCts[j], tmpCts[j + t] = self.SplitNew(level, tmpCts[j])
+        buckets = {}
+        for i in keys:
+            buckets.setdefault(i & (NFactor - 1), []).append(i // NFactor)
+        rQ = self.Evaluators[logNMin].ringQ
+        rL = rQ.AtLevel(level)
+        cts = {}
+        xinv = {}
+        for i, js in buckets.items():
+            if naive:
+                for j in js:
+                    c = self.NewCiphertext(logNMin, level)
+                    for a, b in zip(tmpCts[i], c):
+                        b.CopyLvl(level, a)
+                    for bit in range(logNMin):
+                        if (j >> bit) & 1:
+                            if bit not in xinv:
+                                xinv[bit] = Poly(rQ, level + 1, 1, zero=False)
+                                XPow2NTT(rQ, level, bit, True, xinv[bit])
+                            for p in c:
+                                rL.MulCoeffsMontgomery(p, xinv[bit], p)
+                    cts[i + j * NFactor] = c
+            else:
+                stack, indices = self.Expand(level, tmpCts[i], logGap)
+                pos = {j: e for e, j in enumerate(indices)}
+                for j in js:
+                    if j not in pos:
+                        raise ValueError(f"invalid ciphertexts map: index {j} is nil")
+                    c = self.NewCiphertext(logNMin, level)
+                    for a, b in zip(stack, c):
+                        b.CopyBatch(level, 0, a, pos[j], 1)
+                    cts[i + j * NFactor] = c
+        return cts
+
+    # ---- Repack / RepackNaive (:242-374); cts: {index: [Poly, Poly]}, consumed
+    def Repack(self, level, cts: dict):
+        return self._repack(level, cts, False)
+
+    def RepackNaive(self, level, cts: dict):
+        return self._repack(level, cts, True)
+
+    def _repack(self, level, cts: dict, naive: bool):
+        keys = sorted(cts)
+        logNMin, logNMax = self._logN(cts[keys[0]]), self.MaxLogN()
+        logNFactor = logNMax - logNMin
+        NFactor = 1 << logNFactor
+        ctsSmallN = [dict() for _ in range(NFactor)]
+        for i in keys:
+            ctsSmallN[i & (NFactor - 1)][i // NFactor] = cts[i]
+        ctsLargeN = {}
+        rQ = self.Evaluators[logNMin].ringQ
+        rL = rQ.AtLevel(level)
+        xpow = {}
+        for i in range(NFactor):
+            if naive:
+                tmpCts = ctsSmallN[i]
+                for l in range(logNMin):
+                    t = 1 << (logNMin - 1 - l)
+                    k = logNMin - 1 - l
+                    for jx in sorted({j & (t - 1) for j in tmpCts if t <= j < 2 * t}):
+                        a, b = tmpCts.get(jx), tmpCts[jx + t]
+                        if k not in xpow:
+                            xpow[k] = Poly(rQ, level + 1, 1, zero=False)
+                            XPow2NTT(rQ, level, k, False, xpow[k])
+                        for p in b:
+                            rL.MulCoeffsMontgomery(p, xpow[k], p)
+                        if a is not None:
+                            for p, r in zip(a, b):
+                                rL.Add(p, r, p)
+                        else:
+                            tmpCts[jx] = b
+                        del tmpCts[jx + t]
+                if 0 in tmpCts:
+                    ctsLargeN[i] = tmpCts[0]
+            elif len(ctsSmallN[i]) != 0:
+                ctsLargeN[i] = self.Pack(level, ctsSmallN[i], logNMin, True)
+        for i in range(logNFactor - 1, -1, -1):
+            t = 1 << i
+            for j in range(t):
+                if ctsLargeN.get(j) is not None or ctsLargeN.get(j + 1) is not None:
+                    ctsLargeN[j] = self.MergeNew(level, ctsLargeN.get(j), ctsLargeN.get(j + t))
+                    ctsLargeN.pop(j + t, None)
+        return ctsLargeN.get(0)
+
+
 class InnerSumEvaluator:
     """The inner_sum.go methods of rlwe.Evaluator, bound to an Evaluator and a Galois key set."""
 
