@@ -16,6 +16,7 @@ import pytest
 
 import lattigo_amd as la
 from oracle import oracle as O
+from tests.boundary import primes_below, worst_case_inputs as _worst_case_inputs
 from tests.gpu_common import Pair, ctx  # noqa: F401
 from tests.helpers import rng_for, uniform_poly
 
@@ -191,30 +192,6 @@ def test_byte_accounting_matches_the_survey_formulas(ctx):
 # ---------------------------------------------------------------------------------------------------------------
 # class boundaries
 # ---------------------------------------------------------------------------------------------------------------
-def primes_below(bits: int, log_nth_root: int, count: int):
-    """the `count` largest primes q < 2^bits with q = 1 mod 2^log_nth_root"""
-    out, step = [], 1 << log_nth_root
-    q = (1 << bits) - step + 1
-    while len(out) < count:
-        if O.IsPrime(q):
-            out.append(q)
-        q -= step
-    return out
-
-
-def _worst_case_inputs(rng, q, N):
-    """worst cases inside the reference's input domain: canonical words and lazy words below 2q (ring/ntt.go:164-171 takes
-    U, V in [0, 2q))"""
-    alt = np.zeros(N, dtype=np.uint64)
-    alt[::2] = q - 1
-    alt2 = np.zeros(N, dtype=np.uint64)
-    alt2[1::2] = 2 * q - 1
-    half = np.zeros(N, dtype=np.uint64)
-    half[: N // 2] = q - 1
-    return [np.full(N, q - 1, dtype=np.uint64), alt, alt2, half, np.full(N, 2 * q - 1, dtype=np.uint64),
-            rng.integers(0, q, size=N, dtype=np.uint64), rng.integers(0, 2 * q, size=N, dtype=np.uint64)]
-
-
 @pytest.mark.parametrize("logN", [15, 16, 17, 20])
 @pytest.mark.parametrize("bits", [47, 58, 61])
 def test_ntt_class_boundary_moduli(ctx, logN, bits):
@@ -264,9 +241,12 @@ def test_ntt_class_boundary_moduli(ctx, logN, bits):
 @pytest.mark.parametrize("logN,B", [(16, 2), (15, 3)])
 def test_keyswitch_class_boundary_moduli(ctx, logN, B):
     """GadgetProduct / MulRelin with Q and P made of boundary primes of every class (largest below 2^47, largest below
-    2^58, 61-bit), worst-case ciphertext words (all q-1, alternating) and worst-case key words (all q-1): every kernel of
-    the key-switch pipeline (fused basis extension incl. its float step, row NTTs of the three classes, NTT+MAC in doubles,
-    128-bit inner product, fused ModDown epilogue) runs at the edge of its exactness argument."""
+    2^58, 61-bit), worst-case ciphertext words (all q-1, alternating) and worst-case key words (all q-1): the kernels of the
+    key-switch pipeline (fused basis extension incl. its float step, row NTTs of the three classes, NTT+MAC in doubles,
+    128-bit inner product) run at the edge of their exactness arguments.  P holds a limb below 2^47, so every call here takes
+    the double-format-accumulator path: the NTT + MAC kernel writes double-format Q accumulators and P-limb items, and the
+    ModDown epilogue is the forward row kernel's.  The epilogue INSIDE the NTT + MAC kernel needs special primes of the integer
+    classes only; tests/test_gpu_mac_boundary.py runs it at these primes."""
     N = 1 << logN
     s47, s58 = primes_below(47, logN + 1, 5), primes_below(58, logN + 1, 4)
     s61 = primes_below(61, logN + 1, 2)

@@ -9,6 +9,7 @@ import pytest
 
 import lattigo_amd as la
 from oracle import oracle as O
+from tests.boundary import CANONICAL_KINDS, class_chain, word_row
 from tests.conftest import Pi60, Qi60
 from tests.gpu_common import Pair, ctx  # noqa: F401
 from tests.helpers import rng_for, uniform_poly
@@ -259,6 +260,49 @@ def test_rescale_two_pass_rings_batched_in_place(ctx, logN):
             getattr(pr.gQ.AtLevel(level), name)(pin, pin)
             assert np.array_equal(pin.get()[:, :level], want), (name, level, "in place")
             cur = np.concatenate([want, cur[:, level:]], axis=1)
+
+
+@pytest.mark.parametrize("logN,letters", [(13, "didhdId"), (16, "didhdId"), (13, "hidi")])
+def test_rescale_two_pass_rings_at_the_class_boundaries(ctx, logN, letters):
+    """The same descent of the whole chain (out of place and in place, batched, Round and Floor, plus ...Many with nb = 2 from
+    the top) on the chain [s47, s58, s47, s61, s47, s58^, s47]: the largest primes below 2^47 / 2^58 / 2^61 and the smallest
+    one above 2^58 (tests/boundary.py), ordered so that the dropped modulus takes each class and a dropped modulus
+    of the double-precision and of the Harvey class meets destinations of every class (its one correction-free prime is dropped
+    last, over a double-precision limb only: [s61, s58, s47, s58] adds that class over the other two,
+    tests/test_boundary.py).  logN = 13 is the smallest two-pass degree.  Words: the worst-case set in the NTT
+    domain (all q - 1, alternating, half, uniform), and the transforms of the coefficient-domain all-(q - 1) and alternating
+    polynomials, so that the inverse transform's OUTPUT -- what the scalar prologue and the MRed epilogue of the row kernels
+    meet -- is extreme and not only its input."""
+    qs = class_chain(logN, letters)
+    pr = Pair(ctx, logN, len(qs), qmods=qs)
+    rng = rng_for(1320 + logN)
+    B, top = 2, len(qs) - 1
+    polys = [np.stack([word_row(kind, rng, m, pr.N) for m in qs]) for kind in CANONICAL_KINDS]
+    polys += [pr.oQ.NTT(polys[0]), pr.oQ.NTT(polys[1])]
+    for c0 in range(0, len(polys), B):
+        xs = np.stack(polys[c0 : c0 + B])
+        for name in ("DivRoundByLastModulusNTT", "DivFloorByLastModulusNTT"):
+            cur = xs.copy()
+            pin = pr.up(pr.gQ, cur, batch=B)
+            many = name.replace("NTT", "ManyNTT")
+            want = np.stack([getattr(pr.oQ, many)(2, cur[b]) for b in range(B)])
+            po = la.Poly(pr.gQ, len(qs), B)
+            getattr(pr.gQ, many)(2, pin, po)
+            assert np.array_equal(po.get()[:, : top - 1], want), (many, c0)
+            for level in range(top, 0, -1):
+                sub = O.Ring(pr.N, pr.q[: level + 1])
+                want = np.stack([getattr(sub, name)(cur[b, : level + 1]) for b in range(B)])
+                po = la.Poly(pr.gQ, len(qs), B)
+                getattr(pr.gQ.AtLevel(level), name)(pin, po)
+                assert np.array_equal(po.get()[:, :level], want), (name, c0, level, "out of place")
+                getattr(pr.gQ.AtLevel(level), name)(pin, pin)
+                assert np.array_equal(pin.get()[:, :level], want), (name, c0, level, "in place")
+                cur = np.concatenate([want, cur[:, level:]], axis=1)
+                # and the extreme words themselves at this level (the descent above hands its own outputs down)
+                want = np.stack([getattr(sub, name)(xs[b, : level + 1]) for b in range(B)])
+                pfresh = pr.up(pr.gQ, xs, batch=B)
+                getattr(pr.gQ.AtLevel(level), name)(pfresh, pfresh)
+                assert np.array_equal(pfresh.get()[:, :level], want), (name, c0, level, "extreme words, in place")
 
 
 def test_automorphism(ctx):

@@ -9,6 +9,7 @@ import pytest
 import lattigo_amd as la
 from lattigo_amd import rlwe as R
 from oracle import oracle as O
+from tests.boundary import class_chain, primes_above, primes_below, word_row
 from tests.conftest import Pi60, Qi60
 from tests.gpu_common import Pair, ctx  # noqa: F401
 from tests.helpers import prod, rand_bigints, rng_for, set_coefficients_bigint, uniform_poly
@@ -877,15 +878,37 @@ def test_evaluator_moddown_matches_basis_extender(ctx, logN, batch):
         assert np.array_equal(pq.download(), want), ("in place", levelQ, levelP)
 
 
+def _split_residue_chains(logN, logq, logp):
+    """GenModuli bit sizes, or explicit boundary chains: class letters (tests/boundary.py) for the destination, and for the
+    sources class letters or "51" = [largest below 2^51, smallest above 2^51, largest 61-bit] -- the `src_split` threshold
+    with the largest residues still carried as doubles and the smallest split ones"""
+    if not isinstance(logq, str):
+        return O.GenModuli(logN + 1, logq, logp)
+    q = class_chain(logN, logq)
+    p = [primes_below(51, logN + 1, 1)[0], primes_above(51, logN + 1, 1)[0], primes_below(61, logN + 1, 1)[0]] if logp == "51" \
+        else class_chain(logN, logp)
+    return q, p
+
+
 @pytest.mark.parametrize("logN,logq,logp", [(13, [55, 45, 45, 45], [55, 55, 55]), (13, [60, 45, 40, 36], [61, 61, 61, 61]),
-                                            (12, [45, 45, 58], [61, 55])])
+                                            (12, [45, 45, 58], [61, 55]),
+                                            (12, "ddi", "hhhhhhhh"), (15, "ddi", "hhhhhhhh"), (16, "ddi", "hhhhh"), (13, "ddi", "51")])
 def test_moddown_split_residues_at_their_extremes(ctx, logN, logq, logp):
     """ModDown from special primes of 2^51 and above into double-precision limbs: the residues y_i = (x_i + P/2)(P/p_i)^-1 do
     not fit a double, the kernel splits them at 29 bits and sums the products exactly in one binade before a single reduction.
-    Drive every source's y_i through 0, 1, p_i - 1 and the values around the split point and the top of its high half, in all
-    combinations across the sources, and require ModDownQPtoQNTT's words (ring/basis_extension.go:235-256)."""
+    Drive every source's y_i through 0, 1, p_i - 1, the values around the split point, the top of its high half and the values
+    around 2^51 that its modulus allows, in combinations across the sources, and require ModDownQPtoQNTT's words
+    (ring/basis_extension.go:235-256).
+
+    Besides the GenModuli rows: destinations at the class boundaries (the two largest primes below 2^47 and the largest below
+    2^58) from the eight largest 61-bit primes (logN = 12, 15: sixteen products, where the binade argument "H stays in
+    [2^84, 2^85)" is tightest), from five of them (logN = 16), and from primes on both sides of the 2^51 split threshold
+    (logN = 13).  From four sources on the combinations outnumber the columns.  The ones where every source takes the same
+    candidate (all at their maximum, all at the top of the high half, ...) come first; then every combination of the first
+    seven candidates where those fit (four sources: 7^4 of 8192 columns); the remaining columns walk through the whole product
+    with a stride coprime to its size, so that every source takes every candidate in mixed combinations."""
     import itertools
-    q, p = O.GenModuli(logN + 1, logq, logp)
+    q, p = _split_residue_chains(logN, logq, logp)
     pr = Pair(ctx, logN, len(q), len(p), qmods=q, pmods=p)
     obe = O.BasisExtender(pr.oQ, pr.oP)
     gev = la.Evaluator(pr.gQ, pr.gP)
@@ -894,10 +917,38 @@ def test_moddown_split_residues_at_their_extremes(ctx, logN, logq, logp):
     P = prod(p)
     half = P >> 1
     xp = uniform_poly(rng, p, pr.N)  # coefficient domain
-    cands = [[0, 1, m - 1, (1 << 29) - 1, 1 << 29, m - (1 << 29), ((m >> 29) << 29) - 1] for m in p]
-    for col, ys in enumerate(itertools.islice(itertools.product(*cands), pr.N)):
+    kinds = [lambda m: 0, lambda m: 1, lambda m: m - 1, lambda m: (1 << 29) - 1, lambda m: 1 << 29, lambda m: m - (1 << 29),
+             lambda m: ((m >> 29) << 29) - 1, lambda m: (1 << 51) - 1, lambda m: 1 << 51, lambda m: (1 << 51) + 1]
+    allowed = lambda m, v: v if 0 <= v < m else None
+    # every source at the same kind of candidate (its maximum where its modulus does not allow the value) comes first
+    same = [tuple(m - 1 if allowed(m, k(m)) is None else k(m) for m in p) for k in kinds]
+    cands = [list(dict.fromkeys(v for v in (allowed(m, k(m)) for k in kinds) if v is not None)) for m in p]
+    total, rest = prod(len(c) for c in cands), pr.N - len(same)
+    if total <= rest:
+        cols = same + list(itertools.product(*cands))
+    else:
+        # more combinations than columns: all of the first seven kinds where those fit, then a walk through the whole product
+        # with a stride coprime to its size (near the golden section, so that every source, the first one too, moves through
+        # its candidates from one column to the next and the columns spread evenly over the product)
+        first = [c[:7] for c in cands]
+        cols = same + (list(itertools.product(*first)) if 7 ** len(p) <= rest else [])
+        stride = int(total * 0.6180339887) | 1
+        while np.gcd(stride, total) != 1:
+            stride += 2
+        for j in range(pr.N - len(cols)):
+            k, ys = (j * stride) % total, []
+            for c in reversed(cands):
+                k, r = divmod(k, len(c))
+                ys.append(c[r])
+            cols.append(tuple(reversed(ys)))
+        # every candidate of every source is in use, and no source sits at one value through the filler
+        assert all({ys[i] for ys in cols[-(pr.N // 2):]} == set(cands[i]) for i in range(len(p)))
+    assert len(cols) <= pr.N
+    assert tuple(m - 1 for m in p) in cols and tuple(((m >> 29) << 29) - 1 for m in p) in cols
+    Phat = [P // m for m in p]
+    for col, ys in enumerate(cols):
         for i, (m, y) in enumerate(zip(p, ys)):
-            xp[i, col] = (y * (P // m) - half) % m
+            xp[i, col] = (y * Phat[i] - half) % m
     xpn = pr.oP.NTT(xp)
     xq = uniform_poly(rng, q, pr.N)
     want = obe.ModDownQPtoQNTT(levelQ, levelP, xq, xpn)
@@ -909,6 +960,47 @@ def test_moddown_split_residues_at_their_extremes(ctx, logN, logq, logp):
     got = out.download()
     for b in range(batch):
         assert np.array_equal(got[b], want), b
+
+
+@pytest.mark.parametrize("q0", ["above", "below"])
+def test_decomposition_residues_across_the_split_threshold(ctx, q0):
+    """The mirror image in the decomposition direction: a chain whose q0 is the smallest prime above 2^51 (its digit's
+    residues are split) or the largest below it (carried as doubles), extended into the largest primes below 2^47 and into
+    the special primes by DecomposeNTT, then GadgetProductHoistedLazy on that buffer.  Inputs: all q - 1 and alternating
+    0 / q - 1 as NTT-domain words, and the transforms of the same two as coefficients (the residues entering the extension
+    themselves at q - 1).  Every limb of the decomposition that the call writes, and the accumulators, against the oracle."""
+    logN, B = 13, 4
+    q = [(primes_above if q0 == "above" else primes_below)(51, logN + 1, 1)[0]] + class_chain(logN, "ddd")
+    p = class_chain(logN, "ih")
+    assert (q[0] >> 51 == 1) == (q0 == "above") and abs(q[0] - (1 << 51)) < (1 << (logN + 8))
+    pr = Pair(ctx, logN, len(q), len(p), qmods=q, pmods=p)
+    rng = rng_for(3350 + (q0 == "above"))
+    oev, gev = O.Evaluator(pr.oQ, pr.oP), la.Evaluator(pr.gQ, pr.gP)
+    beta = 2
+    kq = np.stack([np.stack([uniform_poly(rng, q, pr.N) for _ in range(2)]) for _ in range(beta)])
+    kp = np.stack([np.stack([uniform_poly(rng, p, pr.N) for _ in range(2)]) for _ in range(beta)])
+    gkey, okey = gev.NewEvaluationKey(kq, kp), O.EvaluationKey(kq, kp)
+    for levelQ in (3, 2):  # digits (2, 2) and (2, 1)
+        Qm, levelP = q[: levelQ + 1], len(p) - 1
+        sub = O.Ring(pr.N, Qm)
+        words = [np.stack([word_row(kind, rng, m, pr.N) for m in Qm]) for kind in ("max", "alt")]
+        cx = np.stack(words + [sub.NTT(w) for w in words])
+        pcx = la.Poly(pr.gQ, levelQ + 1, B).upload(cx)
+        gdec = la.Decomposition(gev, B)
+        gev.DecomposeNTT(levelQ, levelP, levelP + 1, pcx, True, gdec)
+        qp = [(la.Poly(pr.gQ, levelQ + 1, B), la.Poly(pr.gP, levelP + 1, B)) for _ in range(2)]
+        gev.GadgetProductHoistedLazy(levelQ, gdec, gkey, qp)
+        got = [[qp[k][part].download() for part in range(2)] for k in range(2)]
+        for b in range(B):
+            dq, dp = oev.DecomposeNTT(levelQ, levelP, levelP + 1, cx[b], True)
+            for d in range(beta):
+                for l in range(levelQ + 1):
+                    assert np.array_equal(gdec.limb(b, d, False, l), dq[d, l]), (q0, levelQ, b, d, l)
+                for l in range(levelP + 1):
+                    assert np.array_equal(gdec.limb(b, d, True, l), dp[d, l]), (q0, levelQ, b, d, "P", l)
+            wQ, wP = oev.GadgetProductHoistedLazy(levelQ, dq, dp, okey)
+            for k in range(2):
+                assert np.array_equal(got[k][0][b], wQ[k]) and np.array_equal(got[k][1][b], wP[k]), (q0, levelQ, b, k)
 
 
 def test_captured_graph_replays_a_call_sequence(ctx):
