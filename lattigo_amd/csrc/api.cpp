@@ -1373,41 +1373,136 @@ LimbTab ident_tab(int n, int in0 = 0, int out0 = 0, int mod0 = 0) {
     return t;
 }
 
-int check_poly(const Poly &p, const Ring &r, int level, const char *who) {
-    if (p.ctx != r.ctx) return fail(HE_EINVAL, "%s: the polynomial belongs to another context", who);
-    if (p.N != r.N) return fail(HE_EINVAL, "%s: poly degree %d != ring degree %d", who, p.N, r.N);
+int check_level(const Ring &r, int level, const char *who) {
     if (level < 0 || level >= r.nmod()) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, r.nmod() - 1);
-    if (p.nlimbs < level + 1) return fail(HE_EINVAL, "%s: poly has %d limbs, level %d needs %d", who, p.nlimbs, level, level + 1);
     return HE_OK;
 }
 
 // Operand identity (hering.h, Conventions, "aliasing"): one operand of a call, its role and its side.  `p` may be null (an absent
-// operand).  P-side operands are the special-prime parts (limbs of ringP); everything else is Q-side.
+// operand, or one that is no polynomial).  P-side operands are the special-prime parts (limbs of ringP); everything else is Q-side.
 struct AliasOp {
     const Poly *p;
-    bool out;  // written by the call (outputs and accumulating outputs)
-    bool P;    // a P-side operand
+    bool out;    // written by the call (outputs and accumulating outputs)
+    bool P;      // a P-side operand
+    bool bcast;  // an input that may have batch 1 against the call's batch
 };
 // Checked on the host before anything is filed (also in deferred mode, so the call itself returns the rejection): two operands
 // that are the same polynomial are allowed when both are only read, or when they are an (output, input) pair listed in `allowed`
-// (indices into `ops`: the in-place forms the reference computes).  Two outputs, a Q-side and a P-side operand of which one is
-// written, and every other (output, input) pair fail with HE_EINVAL.
-int reject_aliasing(const char *who, const std::vector<AliasOp> &ops, const std::vector<std::pair<int, int>> &allowed = {}) {
-    for (size_t i = 0; i < ops.size(); i++) {
+// (indices into `ops`: the in-place forms the reference computes; all_inplace: every such pair).  Two outputs, a Q-side and a
+// P-side operand of which one is written, and every other (output, input) pair fail with HE_EINVAL.
+int reject_aliasing(const char *who, const AliasOp *ops, size_t n, const std::pair<int, int> *allowed, int n_allowed, bool all_inplace) {
+    for (size_t i = 0; i < n; i++) {
         if (!ops[i].p) continue;
-        for (size_t j = i + 1; j < ops.size(); j++) {
+        for (size_t j = i + 1; j < n; j++) {
             if (!ops[j].p || ops[i].p->d != ops[j].p->d) continue;
             const AliasOp &a = ops[i], &b = ops[j];
             if (!a.out && !b.out) continue;
             if (a.P != b.P) return fail(HE_EINVAL, "%s: operands %zu and %zu are the same polynomial on the Q and the P side", who, i, j);
             if (a.out && b.out) return fail(HE_EINVAL, "%s: outputs %zu and %zu are the same polynomial", who, i, j);
-            bool ok = false;
-            for (const auto &pr : allowed) ok = ok || (pr.first == (int)i && pr.second == (int)j) || (pr.first == (int)j && pr.second == (int)i);
+            bool ok = all_inplace;
+            for (int a = 0; a < n_allowed; a++) {
+                const auto &pr = allowed[a];
+                ok = ok || (pr.first == (int)i && pr.second == (int)j) || (pr.first == (int)j && pr.second == (int)i);
+            }
             if (!ok) return fail(HE_EINVAL, "%s: output %zu aliases input %zu (not an in-place form of this operation)", who, a.out ? i : j, a.out ? j : i);
         }
     }
     return HE_OK;
 }
+// The polynomial operands of one call, each declared ONCE, in the order the request's `run` closure sees them (v[0], v[1], ...).
+// in / out / inP / outP check the operand (owner context, degree, limbs, batch), append its view to q.ops and the polynomial to
+// q.keep, and return its index -- the name in-place forms (inplace) and identity questions (same) are put with.  A null pointer
+// (or opt() of handle 0) is an absent operand: a null view.  The first failure sticks; check() returns it, or else holds the
+// broadcast operands against the call's batch and applies the aliasing rule.  Nothing is filed before check() said HE_OK.
+struct Operands {
+    static constexpr int kCall = -1, kBroadcast = -2;  // batch rules (a value >= 0: exactly that batch)
+    CoReq &q;
+    const char *who;
+    const std::shared_ptr<Ctx> &ctx;  // the owner every operand must share
+    const int N;                      // the degree of an operand that names no other
+    int B;                            // the call's batch: given, or that of the first operand held to it
+    int rc = HE_OK;
+    bool all_inplace = false;         // every output may be every input of its side
+    bool writes = false;              // some operand is written (only then can identity matter)
+    AliasOp few[12], *ops = few;      // the operands declared so far (the lintrans terms and the pack steps spill to `many`)
+    std::vector<AliasOp> many;
+    int n = 0;
+    std::pair<int, int> allowed[4];   // the (output, input) pairs declared with inplace() (no entry point has more than two)
+    int n_allowed = 0;
+    Operands(CoReq &q, const char *who, const std::shared_ptr<Ctx> &ctx, int N, int B = kCall) : q(q), who(who), ctx(ctx), N(N), B(B) {
+        q.ops.reserve(8); q.keep.reserve(12);
+    }
+    Operands(const Operands &) = delete;  // (`ops` may point into the object)
+    Operands(CoReq &q, const char *who, const Ring &r, int B = kCall) : Operands(q, who, r.ctx, r.N, B) {}
+    Operands(CoReq &q, const char *who, const BasisExtender &be, int B = kCall) : Operands(q, who, be.ctx, be.Q->N, B) {}
+    // a handle that must name a polynomial / that may be 0 (absent)
+    std::shared_ptr<Poly> poly(he_handle h, bool optional = false) {
+        std::shared_ptr<Poly> p = (optional && !h) ? nullptr : get<Poly>(h, T_POLY);
+        if (!p && !(optional && !h) && rc == HE_OK) rc = fail(HE_EHANDLE, "%s: bad Poly handle %llu (operand %zu)", who, (unsigned long long)h, (size_t)n);
+        return p;
+    }
+    std::shared_ptr<Poly> opt(he_handle h) { return poly(h, true); }
+    int add(const std::shared_ptr<Poly> &p, bool out, bool P, int limbs, const char *name, int batch, int deg) {
+        const int i = push({p.get(), out, P, batch == kBroadcast}, p ? p->view() : View{nullptr, 0});
+        writes = writes || out;
+        if (!p || rc != HE_OK) return i;
+        q.keep.push_back(p);
+        char idx[24];
+        snprintf(idx, sizeof idx, "operand %d", i);
+        if (!name) name = idx;
+        if (deg == 0) deg = N;
+        if (batch == kCall && B == kCall) B = p->batch;
+        const int want = batch == kCall ? B : batch;
+        if (p->ctx != ctx) rc = fail(HE_EINVAL, "%s: %s belongs to another context", who, name);
+        else if (p->N != deg) rc = fail(HE_EINVAL, "%s: %s has degree %d, %d expected", who, name, p->N, deg);
+        else if (p->nlimbs < limbs) rc = fail(HE_EINVAL, "%s: %s has %d limbs, %d needed", who, name, p->nlimbs, limbs);
+        else if (want >= 0 && p->batch != want) rc = fail(HE_EINVAL, "%s: batch mismatch (%s has %d entries, %d expected)", who, name, p->batch, want);
+        return i;
+    }
+    template <class H> int in(const H &h, int limbs, const char *name = nullptr, int batch = kCall, int deg = 0) { return add(ptr(h), false, false, limbs, name, batch, deg); }
+    template <class H> int out(const H &h, int limbs, const char *name = nullptr, int batch = kCall, int deg = 0) { return add(ptr(h), true, false, limbs, name, batch, deg); }
+    template <class H> int inP(const H &h, int limbs, const char *name = nullptr, int batch = kCall) { return add(ptr(h), false, true, limbs, name, batch, 0); }
+    template <class H> int outP(const H &h, int limbs, const char *name = nullptr) { return add(ptr(h), true, true, limbs, name, kCall, 0); }
+    // an operand that is no polynomial (a hoisting buffer): its view, and what keeps it alive
+    int raw(View v, std::shared_ptr<Obj> keep) {
+        q.keep.push_back(std::move(keep));
+        return push({nullptr, false, false, false}, v);
+    }
+    // the two QP components of a lazy key switch, (c0Q, c0P, c1Q, c1P) -- indices i .. i + 3; without special primes (levelP < 0)
+    // the P handles are ignored (pass 0) and their operands absent
+    int qp(bool out, he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, int levelQ, int levelP) {
+        const int i = add(poly(c0Q), out, false, levelQ + 1, "c0Q", kCall, 0);
+        add(levelP < 0 ? nullptr : poly(c0P), out, true, levelP + 1, "c0P", kCall, 0);
+        add(poly(c1Q), out, false, levelQ + 1, "c1Q", kCall, 0);
+        add(levelP < 0 ? nullptr : poly(c1P), out, true, levelP + 1, "c1P", kCall, 0);
+        return i;
+    }
+    void inplace(int o, int i) {
+        if (n_allowed < 4) allowed[n_allowed++] = {o, i};
+        else if (rc == HE_OK) rc = fail(HE_EINVAL, "%s: internal error, too many in-place forms", who);
+    }
+    bool same(int i, int j) const { return ops[i].p && ops[j].p && ops[i].p->d == ops[j].p->d; }
+    int check() {
+        for (int i = 0; i < n && rc == HE_OK; i++) {
+            if (!ops[i].bcast || !ops[i].p) continue;
+            if (ops[i].p->batch == 1) q.ops[i].bstride = 0;  // one polynomial for every entry of the batch
+            else if (ops[i].p->batch != B) rc = fail(HE_EINVAL, "%s: batch mismatch (operand %d has %d entries, 1 or %d expected)", who, i, ops[i].p->batch, B);
+        }
+        TRY(rc);
+        return writes ? reject_aliasing(who, ops, (size_t)n, allowed, n_allowed, all_inplace) : HE_OK;
+    }
+
+private:
+    int push(const AliasOp &a, View v) {
+        if (n == 12) many.assign(few, few + 12);
+        if (n >= 12) { many.push_back(a); ops = many.data(); }
+        else few[n] = a;
+        q.ops.push_back(v);
+        return n++;
+    }
+    const std::shared_ptr<Poly> &ptr(const std::shared_ptr<Poly> &p) { return p; }
+    std::shared_ptr<Poly> ptr(he_handle h) { return poly(h); }
+};
 // Galois elements act through g mod NthRoot (2N, 4N on conjugate-invariant rings): the reduced element is what keys batches and
 // index caches, so that g and g + k NthRoot share them
 inline uint64_t reduce_gal(uint64_t gal, int logN, int type) { return gal & ((2ull << (logN + type)) - 1); }
@@ -1757,20 +1852,9 @@ int he_poly_download_limb(he_handle h, int b, int limb, uint64_t *dst) {
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     return HE_OK;
 }
-int he_poly_copy(he_handle hdst, he_handle hsrc, int level) {
-    GET(d, Poly, hdst, T_POLY);
-    GET(s, Poly, hsrc, T_POLY);
-    if (d->N != s->N || d->batch != s->batch || level < 0 || d->nlimbs < level + 1 || s->nlimbs < level + 1 || d->ctx != s->ctx)
-        return fail(HE_EINVAL, "he_poly_copy: shape or context mismatch");
-    if (d->d == s->d) return HE_OK;  // Poly.CopyLvl onto itself: nothing to copy (and no overlapping memcpy to file)
-    // (the copies of concurrent single-ciphertext callers ride in the queue like every other operation: one EW_COPY launch over an
-    // entry table; a lone copy is a device-to-device memcpy as before)
-    const std::shared_ptr<Ctx> ctx = d->ctx;
-    const int N = d->N;
-    CoReq q;
+// the request of a copy of limbs 0..level, v[0] -> v[1]: a device-to-device memcpy, or one EW_COPY launch over an entry table
+static void copy_request(CoReq &q, const std::shared_ptr<Ctx> &ctx, int level, int N) {
     q.op = CO_COPY; q.obj = ctx.get(); q.par[0] = level; q.par[1] = N;
-    q.ops = {s->view(), d->view()};
-    q.keep = {s, d};
     q.run = [ctx, level, N](const View *v, int B) -> int {
         ctx->acct(2.0 * (level + 1), 0, B, N);
         if (!v[0].tab && !v[1].tab) {
@@ -1783,6 +1867,22 @@ int he_poly_copy(he_handle hdst, he_handle hsrc, int level) {
         HIP_TRY(launch_ew(dev, ident_tab(level + 1), EW_COPY, v[0], v[0], v[1], B, nullptr, nullptr, ctx->stream));
         return HE_OK;
     };
+}
+int he_poly_copy(he_handle hdst, he_handle hsrc, int level) {
+    GET(d, Poly, hdst, T_POLY);
+    GET(s, Poly, hsrc, T_POLY);
+    if (level < 0) return fail(HE_EINVAL, "he_poly_copy: negative level");
+    const std::shared_ptr<Ctx> ctx = d->ctx;
+    const int N = d->N;
+    CoReq q;
+    Operands o(q, "he_poly_copy", ctx, N);
+    const int is = o.in(s, level + 1, "src"), id = o.out(d, level + 1, "dst");
+    o.inplace(id, is);
+    TRY(o.check());
+    if (o.same(is, id)) return HE_OK;  // Poly.CopyLvl onto itself: nothing to copy (and no overlapping memcpy to file)
+    // (the copies of concurrent single-ciphertext callers ride in the queue like every other operation: one EW_COPY launch over an
+    // entry table; a lone copy is a device-to-device memcpy as before)
+    copy_request(q, ctx, level, N);
     return co_dispatch(*ctx, d->batch, q);
 }
 int he_poly_copy_batch(he_handle hdst, int dst_b0, he_handle hsrc, int src_b0, int nb, int level) {
@@ -1799,23 +1899,11 @@ int he_poly_copy_batch(he_handle hdst, int dst_b0, he_handle hsrc, int src_b0, i
     const std::shared_ptr<Ctx> ctx = d->ctx;
     const int N = d->N;
     CoReq q;
-    q.op = CO_COPY; q.obj = ctx.get(); q.par[0] = level; q.par[1] = N;
     View vs = s->view(), vd = d->view();
     vs.p += (size_t)src_b0 * vs.bstride; vd.p += (size_t)dst_b0 * vd.bstride;
-    q.ops = {vs, vd};
+    q.ops = {vs, vd};  // (entry ranges, possibly of one handle: the overlap rule above is this call's own -- not an Operands list)
     q.keep = {s, d};
-    q.run = [ctx, level, N](const View *v, int B) -> int {
-        ctx->acct(2.0 * (level + 1), 0, B, N);
-        if (!v[0].tab && !v[1].tab) {
-            HIP_TRY(hipMemcpy2DAsync(v[1].p, v[1].bstride * 8, v[0].p, v[0].bstride * 8, (size_t)(level + 1) * N * 8, B, hipMemcpyDeviceToDevice,
-                                     ctx->stream));
-            return HE_OK;
-        }
-        RingDev dev{};
-        dev.N = N;
-        HIP_TRY(launch_ew(dev, ident_tab(level + 1), EW_COPY, v[0], v[0], v[1], B, nullptr, nullptr, ctx->stream));
-        return HE_OK;
-    };
+    copy_request(q, ctx, level, N);
     return co_dispatch(*ctx, nb, q);
 }
 int he_poly_device_buffer(he_handle h, void **ptr, size_t *bytes) {
@@ -1861,17 +1949,27 @@ static hipError_t be_ntt(const BasisExtender &be, const LimbTab &tab, View in, V
     return typed_ntt(be.qp, be.type, be.ctx->stream, tab, in, out, batch, inverse, flags);
 }
 
+// the operands of the ring's one-input operations, each computed in place by the reference: p1 -> p2 at `level`
+// (B: the call's batch; inplace: whether p1 and p2 are one polynomial)
+static int unary_operands(CoReq &q, const char *who, const std::shared_ptr<Ring> &r, int level, he_handle h1, he_handle h2, int *B,
+                          bool *inplace = nullptr) {
+    TRY(check_level(*r, level, who));
+    Operands o(q, who, *r);
+    o.in(h1, level + 1);
+    o.out(h2, level + 1);
+    o.all_inplace = true;
+    q.keep.push_back(r);
+    TRY(o.check());
+    *B = o.B;
+    if (inplace) *inplace = o.same(0, 1);
+    return HE_OK;
+}
 static int ntt_api(he_handle hring, int level, he_handle h1, he_handle h2, bool inverse, int flags, const char *who) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
-    TRY(check_poly(*p1, *r, level, who));
-    TRY(check_poly(*p2, *r, level, who));
-    if (p1->batch != p2->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
     CoReq q;
+    int B = 0;
+    TRY(unary_operands(q, who, r, level, h1, h2, &B));
     q.op = CO_NTT; q.obj = r.get(); q.par[0] = level; q.par[1] = inverse; q.par[2] = flags;
-    q.ops = {p1->view(), p2->view()};
-    q.keep = {r, p1, p2};
     q.run = [r, level, inverse, flags](const View *v, int B) -> int {
         r->ctx->acct(2.0 * (level + 1), 0, B, r->N);  // NTT / INTT: 2 L limbs
         { Valu V(r->logN); for (int i = 0; i <= level; i++) V.ntt(cls_f64(r->small, i)); V.into(*r->ctx, B); }
@@ -1879,7 +1977,7 @@ static int ntt_api(he_handle hring, int level, he_handle h1, he_handle h2, bool 
         return HE_OK;
     };
     q.tables_ok = [r](bool *ok) -> int { *ok = r->type == 0; return HE_OK; };  // (the conjugate-invariant fold takes no entry tables)
-    return co_dispatch(*r->ctx, p1->batch, q);
+    return co_dispatch(*r->ctx, B, q);
 }
 int he_ntt(he_handle r, int level, he_handle p1, he_handle p2) { return ntt_api(r, level, p1, p2, false, 0, "he_ntt"); }
 int he_ntt_lazy(he_handle r, int level, he_handle p1, he_handle p2) { return ntt_api(r, level, p1, p2, false, NTT_LAZY_OUT, "he_ntt_lazy"); }
@@ -1908,23 +2006,18 @@ int he_subring_ntt_host(he_handle hring, int limb, int backward, int lazy, const
 // ---------------------------------------------------------------------------------------
 int he_binop(he_handle hring, int level, int op, he_handle h1, he_handle h2, he_handle h3) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
-    GET(p3, Poly, h3, T_POLY);
     if (op < 0 || op >= HE_BINOP_COUNT) return fail(HE_EINVAL, "he_binop: unknown op %d", op);
-    TRY(check_poly(*p1, *r, level, "he_binop"));
-    TRY(check_poly(*p2, *r, level, "he_binop"));
-    TRY(check_poly(*p3, *r, level, "he_binop"));
-    // an input of batch 1 broadcasts over the batch of the output (one plaintext against a batch of ciphertexts)
-    if ((p1->batch != p3->batch && p1->batch != 1) || (p2->batch != p3->batch && p2->batch != 1))
-        return fail(HE_EINVAL, "he_binop: batch mismatch");
-    View v1 = p1->view(), v2 = p2->view();
-    if (p1->batch != p3->batch) v1.bstride = 0;
-    if (p2->batch != p3->batch) v2.bstride = 0;
+    TRY(check_level(*r, level, "he_binop"));
     CoReq q;
+    Operands o(q, "he_binop", *r);
+    // an input of batch 1 broadcasts over the batch of the output (one plaintext against a batch of ciphertexts)
+    o.in(h1, level + 1, nullptr, Operands::kBroadcast);
+    o.in(h2, level + 1, nullptr, Operands::kBroadcast);
+    o.out(h3, level + 1);
+    o.all_inplace = true;
+    TRY(o.check());
     q.op = CO_EW; q.obj = r.get(); q.par[0] = level; q.par[1] = op;
-    q.ops = {v1, v2, p3->view()};
-    q.keep = {r, p1, p2, p3};
+    q.keep.push_back(r);
     q.run = [r, level, op](const View *v, int B) -> int {
         // binary 3 L, ...ThenAdd / ...ThenSub 4 L; a batch-1 operand is read once for the whole batch
         const bool then = op == EW_MUL_BARRETT_THEN_ADD || op == EW_MUL_BARRETT_THEN_ADD_LAZY || (op >= EW_MUL_MONT_THEN_ADD && op <= EW_MUL_MONT_LAZY_THEN_SUB_LAZY);
@@ -1934,37 +2027,32 @@ int he_binop(he_handle hring, int level, int op, he_handle h1, he_handle h2, he_
         HIP_TRY(launch_ew(r->dev, ident_tab(level + 1), op, v[0], v[1], v[2], B, nullptr, nullptr, r->ctx->stream));
         return HE_OK;
     };
-    return co_dispatch(*r->ctx, p3->batch, q);
+    return co_dispatch(*r->ctx, o.B, q);
 }
 int he_unop(he_handle hring, int level, int op, he_handle h1, he_handle h2) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
     if (op < 0 || op >= HE_UNOP_COUNT) return fail(HE_EINVAL, "he_unop: unknown op %d", op);
-    TRY(check_poly(*p1, *r, level, "he_unop"));
-    TRY(check_poly(*p2, *r, level, "he_unop"));
-    if (p1->batch != p2->batch) return fail(HE_EINVAL, "he_unop: batch mismatch");
     CoReq q;
+    int B = 0;
+    TRY(unary_operands(q, "he_unop", r, level, h1, h2, &B));
     q.op = CO_EW; q.obj = r.get(); q.par[0] = level; q.par[1] = EW_NEG + op;
-    q.ops = {p1->view(), p2->view()};
-    q.keep = {r, p1, p2};
     q.run = [r, level, op](const View *v, int B) -> int {
         r->ctx->acct(2.0 * (level + 1), 0, B, r->N);  // unary: 2 L
         if (EW_NEG + op >= EW_MFORM && EW_NEG + op <= EW_IMFORM) { Valu V(r->logN); for (int i = 0; i <= level; i++) V.mul(cls_f64(r->small, i), 1.0); V.into(*r->ctx, B); }
         HIP_TRY(launch_ew(r->dev, ident_tab(level + 1), EW_NEG + op, v[0], v[0], v[1], B, nullptr, nullptr, r->ctx->stream));
         return HE_OK;
     };
-    return co_dispatch(*r->ctx, p2->batch, q);
+    return co_dispatch(*r->ctx, B, q);
 }
 // scalar given per limb (already what the kernel consumes)
-static int scalar_launch(const std::shared_ptr<Ring> &r, int level, int ewop, const std::shared_ptr<Poly> &p1,
-                         const std::shared_ptr<Poly> &p2, const ScalarTab &st, bool dbl = false) {
+static int scalar_launch(const std::shared_ptr<Ring> &r, int level, int ewop, he_handle h1, he_handle h2, const ScalarTab &st,
+                         const char *who, bool dbl = false) {
     CoReq q;
+    int B = 0;
+    TRY(unary_operands(q, who, r, level, h1, h2, &B));
     q.op = dbl ? CO_EW_DOUBLE : CO_EW; q.obj = r.get(); q.par[0] = level; q.par[1] = ewop; q.par[2] = 1;  // (par[2]: a scalar form)
     q.blob.assign(st.s, st.s + level + 1);
     if (dbl) q.blob.insert(q.blob.end(), st.s2, st.s2 + level + 1);
-    q.ops = {p1->view(), p2->view()};
-    q.keep = {r, p1, p2};
     q.run = [r, level, ewop, st, dbl](const View *v, int B) -> int {
         r->ctx->acct((ewop == EW_MUL_SCALAR_MONT_THEN_ADD ? 3.0 : 2.0) * (level + 1), 0, B, r->N);  // unary (3 L with the addend)
         if (ewop == EW_MUL_SCALAR_MONT || ewop == EW_MUL_SCALAR_MONT_THEN_ADD) { Valu V(r->logN); for (int i = 0; i <= level; i++) V.mul(cls_f64(r->small, i), 1.0); V.into(*r->ctx, B); }
@@ -1972,15 +2060,11 @@ static int scalar_launch(const std::shared_ptr<Ring> &r, int level, int ewop, co
         else HIP_TRY(launch_ew(r->dev, ident_tab(level + 1), ewop, v[0], v[0], v[1], B, &st, nullptr, r->ctx->stream));
         return HE_OK;
     };
-    return co_dispatch(*r->ctx, p2->batch, q);
+    return co_dispatch(*r->ctx, B, q);
 }
 int he_scalarop(he_handle hring, int level, int op, he_handle h1, uint64_t scalar, he_handle h2) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
-    TRY(check_poly(*p1, *r, level, "he_scalarop"));
-    TRY(check_poly(*p2, *r, level, "he_scalarop"));
-    if (p1->batch != p2->batch) return fail(HE_EINVAL, "he_scalarop: batch mismatch");
+    TRY(check_level(*r, level, "he_scalarop"));
     ScalarTab st{};
     int ewop;
     for (int i = 0; i <= level; i++) {
@@ -2002,43 +2086,34 @@ int he_scalarop(he_handle hring, int level, int op, he_handle h1, uint64_t scala
         case HE_MUL_SCALAR: ewop = EW_MUL_SCALAR_MONT; break;
         default: ewop = EW_MUL_SCALAR_MONT_THEN_ADD; break;
     }
-    return scalar_launch(r, level, ewop, p1, p2, st);
+    return scalar_launch(r, level, ewop, h1, h2, st, "he_scalarop");
 }
 int he_mul_rns_scalar_montgomery(he_handle hring, int level, he_handle h1, const uint64_t *scalar, he_handle h2) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
-    TRY(check_poly(*p1, *r, level, "he_mul_rns_scalar_montgomery"));
-    TRY(check_poly(*p2, *r, level, "he_mul_rns_scalar_montgomery"));
-    if (!scalar || p1->batch != p2->batch) return fail(HE_EINVAL, "he_mul_rns_scalar_montgomery: bad arguments");
+    TRY(check_level(*r, level, "he_mul_rns_scalar_montgomery"));
+    if (!scalar) return fail(HE_EINVAL, "he_mul_rns_scalar_montgomery: bad arguments");
     ScalarTab st{};
     for (int i = 0; i <= level; i++) st.s[i] = scalar[i];
-    return scalar_launch(r, level, EW_MUL_SCALAR_MONT, p1, p2, st);
+    return scalar_launch(r, level, EW_MUL_SCALAR_MONT, h1, h2, st, "he_mul_rns_scalar_montgomery");
 }
 static int bigint_api(he_handle hring, int level, he_handle h1, const uint64_t *words, int nw, he_handle h2, int kind) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
-    TRY(check_poly(*p1, *r, level, "he_*_scalar_bigint"));
-    TRY(check_poly(*p2, *r, level, "he_*_scalar_bigint"));
-    if (!words || nw <= 0 || p1->batch != p2->batch) return fail(HE_EINVAL, "he_*_scalar_bigint: bad arguments");
+    TRY(check_level(*r, level, "he_*_scalar_bigint"));
+    if (!words || nw <= 0) return fail(HE_EINVAL, "he_*_scalar_bigint: bad arguments");
     ScalarTab st{};
     for (int i = 0; i <= level; i++) {
         const ModConst &m = r->sub[i].mc;
         const uint64_t v = words_mod(words, nw, m.q);
         st.s[i] = kind >= 2 ? mform(v, m.q, m.brc0, m.brc1) : v;
     }
-    return scalar_launch(r, level, kind == 0 ? EW_ADD_SCALAR : (kind == 1 ? EW_SUB_SCALAR : (kind == 2 ? EW_MUL_SCALAR_MONT : EW_MUL_SCALAR_MONT_THEN_ADD)), p1, p2, st);
+    return scalar_launch(r, level, kind == 0 ? EW_ADD_SCALAR : (kind == 1 ? EW_SUB_SCALAR : (kind == 2 ? EW_MUL_SCALAR_MONT : EW_MUL_SCALAR_MONT_THEN_ADD)), h1, h2, st, "he_*_scalar_bigint");
 }
 int he_mul_scalar_bigint_then_add(he_handle r, int l, he_handle p1, const uint64_t *w, int n, he_handle p2) { return bigint_api(r, l, p1, w, n, p2, 3); }
 int he_double_rns_scalarop(he_handle hring, int level, int op, he_handle h1, const uint64_t *s0, const uint64_t *s1, he_handle h2) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
     const char *who = "he_double_rns_scalarop";
-    TRY(check_poly(*p1, *r, level, who));
-    TRY(check_poly(*p2, *r, level, who));
-    if (!s0 || !s1 || op < 0 || op > 3 || p1->batch != p2->batch) return fail(HE_EINVAL, "%s: bad arguments", who);
+    TRY(check_level(*r, level, who));
+    if (!s0 || !s1 || op < 0 || op > 3) return fail(HE_EINVAL, "%s: bad arguments", who);
     ScalarTab st{};
     for (int i = 0; i <= level; i++) {
         const ModConst &m = r->sub[i].mc;
@@ -2046,24 +2121,19 @@ int he_double_rns_scalarop(he_handle hring, int level, int op, he_handle h1, con
         st.s2[i] = op >= 2 ? mform(s1[i], m.q, m.brc0, m.brc1) : s1[i];
     }
     static const int ops[4] = {EW_ADD_SCALAR, EW_SUB_SCALAR, EW_MUL_SCALAR_MONT, EW_MUL_SCALAR_MONT_THEN_ADD};
-    return scalar_launch(r, level, ops[op], p1, p2, st, true);
+    return scalar_launch(r, level, ops[op], h1, h2, st, who, true);
 }
 static int shift_api(he_handle hring, int level, he_handle h1, int k, he_handle h2, bool monomial, const char *who) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
-    TRY(check_poly(*p1, *r, level, who));
-    TRY(check_poly(*p2, *r, level, who));
-    if (p1->batch != p2->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    const int N = r->N, B = p1->batch;
+    CoReq q;
+    int batch = 0;
+    bool inplace = false;
+    TRY(unary_operands(q, who, r, level, h1, h2, &batch, &inplace));
+    const int N = r->N;
     const int period = monomial ? 2 * N : N;
     int kk = k % period;
     if (kk < 0) kk += period;
-    const bool inplace = p1->d == p2->d;
-    CoReq q;
     q.op = CO_SHIFT; q.obj = r.get(); q.par[0] = level; q.par[1] = kk; q.par[2] = monomial;
-    q.ops = {p1->view(), p2->view()};
-    q.keep = {r, p1, p2};
     q.run = [r, level, kk, monomial, inplace, N](const View *v, int B) -> int {
         r->ctx->acct(2.0 * (level + 1), 0, B, N);
         View in = v[0];
@@ -2079,28 +2149,23 @@ static int shift_api(he_handle hring, int level, he_handle h1, int k, he_handle 
         else HIP_TRY(launch_shift(r->dev, tab, in, kk, v[1], B, r->ctx->stream));
         return HE_OK;
     };
-    (void)B;
-    return co_dispatch(*r->ctx, p1->batch, q);
+    return co_dispatch(*r->ctx, batch, q);
 }
 int he_shift(he_handle r, int l, he_handle p1, int k, he_handle p2) { return shift_api(r, l, p1, k, p2, false, "he_shift"); }
 int he_mult_by_monomial(he_handle r, int l, he_handle p1, int k, he_handle p2) { return shift_api(r, l, p1, k, p2, true, "he_mult_by_monomial"); }
 int he_mul_by_vector_montgomery(he_handle hring, int level, he_handle h1, he_handle hv, int then_add_lazy, he_handle h2) {
     GET(r, Ring, hring, T_RING);
-    GET(p1, Poly, h1, T_POLY);
-    GET(v, Poly, hv, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
     const char *who = "he_mul_by_vector_montgomery";
-    TRY(check_poly(*p1, *r, level, who));
-    TRY(check_poly(*p2, *r, level, who));
-    if (v->N != r->N || v->batch != 1 || p1->batch != p2->batch) return fail(HE_EINVAL, "%s: the vector is one batch-1 limb of degree N", who);
-    // p2 may be p1; p2 == vector is not in place: limb 0 of the output is the vector every other limb still reads
-    TRY(reject_aliasing(who, {{p1.get(), false, false}, {v.get(), false, false}, {p2.get(), true, false}}, {{0, 2}}));
-    View vv = v->view();
-    vv.bstride = 0;  // the same vector for every batch entry and (through the limb override) every limb
+    TRY(check_level(*r, level, who));
     CoReq q;
+    Operands o(q, who, *r);
+    o.in(hv, 1, "the vector (one batch-1 limb of degree N)", 1);
+    const int i1 = o.in(h1, level + 1), i2 = o.out(h2, level + 1);
+    o.inplace(i2, i1);  // p2 == vector is not in place: limb 0 of the output is the vector every other limb still reads
+    TRY(o.check());
+    q.ops[0].bstride = 0;  // the same vector for every batch entry and (through the limb override) every limb
     q.op = CO_EW; q.obj = r.get(); q.par[0] = level; q.par[1] = then_add_lazy ? EW_MUL_MONT_THEN_ADD_LAZY : EW_MUL_MONT; q.par[2] = 2;  // (a vector form)
-    q.ops = {vv, p1->view(), p2->view()};
-    q.keep = {r, v, p1, p2};
+    q.keep.push_back(r);
     q.run = [r, level, then_add_lazy](const View *w, int B) -> int {
         const uint8_t zeros[kMaxLimbs] = {0};
         r->ctx->acct((then_add_lazy ? 3.0 : 2.0) * (level + 1), 1.0, B, r->N);
@@ -2109,7 +2174,7 @@ int he_mul_by_vector_montgomery(he_handle hring, int level, he_handle h1, he_han
                           zeros, r->ctx->stream));
         return HE_OK;
     };
-    return co_dispatch(*r->ctx, p2->batch, q);
+    return co_dispatch(*r->ctx, o.B, q);
 }
 int he_add_scalar_bigint(he_handle r, int l, he_handle p1, const uint64_t *w, int n, he_handle p2) { return bigint_api(r, l, p1, w, n, p2, 0); }
 int he_sub_scalar_bigint(he_handle r, int l, he_handle p1, const uint64_t *w, int n, he_handle p2) { return bigint_api(r, l, p1, w, n, p2, 1); }
@@ -2224,16 +2289,16 @@ int div_by_last_modulus_coeff(Ring &r, int level, View p0, View p1, int batch, b
 // the request of one DivRound / DivFloor call (validation + launches); div_many files it, he_rescale_polys files several at once
 int div_fill(CoReq &q, const std::shared_ptr<Ring> &r, int level, int nb, he_handle h0, he_handle h1, bool round, bool ntt, const char *who,
              bool many, int *batch) {
-    GET(p0, Poly, h0, T_POLY);
-    GET(p1, Poly, h1, T_POLY);
-    TRY(check_poly(*p0, *r, level, who));
+    TRY(check_level(*r, level, who));
     if (nb < 0 || nb > level) return fail(HE_EINVAL, "%s: cannot divide %d times at level %d", who, nb, level);
-    if (p1->N != r->N || p1->nlimbs < level + 1 - nb || p0->batch != p1->batch) return fail(HE_EINVAL, "%s: output shape mismatch", who);
-    const bool same = p0->d == p1->d;
-    *batch = p0->batch;
+    Operands o(q, who, *r);
+    const int i0 = o.in(h0, level + 1), i1 = o.out(h1, level + 1 - nb);
+    o.all_inplace = true;
+    TRY(o.check());
+    const bool same = o.same(i0, i1);
+    *batch = o.B;
     q.op = CO_RESCALE; q.obj = r.get(); q.par[0] = level; q.par[1] = nb; q.par[2] = round; q.par[3] = ntt; q.par[4] = many;
-    q.ops = {p0->view(), p1->view()};
-    q.keep = {r, p0, p1};
+    q.keep.push_back(r);
     q.run = [r, level, nb, round, ntt, many, same](const View *v, int B) -> int {
         for (int i = 0; i < nb; i++) r->ctx->acct(2.0 * (level - i + 1) - 1.0, 0, B, r->N);  // rescale: (2 L - 1) per polynomial and step
         {   // NTT form, one step: INTT of the top limb, one NTT and one product per remaining limb; otherwise: [INTT] + a product per
@@ -2383,49 +2448,46 @@ int he_automorphism_index_download(he_handle h, uint64_t *dst) {
 }
 static int gather_api(he_handle hring, int level, he_handle hin, he_handle hidx, he_handle hout, bool add, const char *who) {
     GET(r, Ring, hring, T_RING);
-    GET(pin, Poly, hin, T_POLY);
-    GET(pout, Poly, hout, T_POLY);
     GET(ix, AutoIndex, hidx, T_INDEX);
-    TRY(check_poly(*pin, *r, level, who));
-    TRY(check_poly(*pout, *r, level, who));
-    if (ix->N != r->N || pin->batch != pout->batch) return fail(HE_EINVAL, "%s: shape mismatch", who);
-    if (pin->d == pout->d) return fail(HE_EINVAL, "%s: the automorphism cannot be evaluated in place", who);
+    TRY(check_level(*r, level, who));
+    if (ix->N != r->N) return fail(HE_EINVAL, "%s: shape mismatch", who);
     CoReq q;
+    Operands o(q, who, *r);
+    o.in(hin, level + 1);
+    o.out(hout, level + 1);
+    TRY(o.check());  // (never in place, ring/automorphism.go:37)
     // (the index table is identified by its Galois element, not by its handle: callers that each built their own table of the same
     // automorphism share a batch -- entry 0's table serves them all)
     // ... and by the cached table it points at: handles built on rings of another type (standard / conjugate-invariant, another
     // NthRoot) with the same N and Galois element hold a different permutation and must not share entry 0's table
     q.op = CO_GATHER; q.obj = r.get(); q.par[0] = level; q.par[1] = add; q.par[2] = (int64_t)ix->gal; q.par[3] = (int64_t)(uintptr_t)ix->d;
-    q.ops = {pin->view(), pout->view()};
-    q.keep = {r, pin, pout, ix};
+    q.keep.push_back(r); q.keep.push_back(ix);
     q.run = [r, ix, level, add](const View *v, int B) -> int {
         r->ctx->acct((add ? 3.0 : 2.0) * (level + 1), 0, B, r->N);  // automorphism: 2 L (+ L for ...ThenAddLazy)
         HIP_TRY(launch_gather(r->dev, ident_tab(level + 1), v[0], ix->d, v[1], B, add, r->ctx->stream));
         return HE_OK;
     };
-    return co_dispatch(*r->ctx, pin->batch, q);
+    return co_dispatch(*r->ctx, o.B, q);
 }
 int he_automorphism_ntt_with_index(he_handle r, int l, he_handle in, he_handle idx, he_handle out) { return gather_api(r, l, in, idx, out, false, "he_automorphism_ntt_with_index"); }
 int he_automorphism_ntt_with_index_then_add_lazy(he_handle r, int l, he_handle in, he_handle idx, he_handle out) { return gather_api(r, l, in, idx, out, true, "he_automorphism_ntt_with_index_then_add_lazy"); }
 int he_automorphism(he_handle hring, int level, he_handle hin, uint64_t gal, he_handle hout) {
     GET(r, Ring, hring, T_RING);
-    GET(pin, Poly, hin, T_POLY);
-    GET(pout, Poly, hout, T_POLY);
-    TRY(check_poly(*pin, *r, level, "he_automorphism"));
-    TRY(check_poly(*pout, *r, level, "he_automorphism"));
-    if (pin->batch != pout->batch) return fail(HE_EINVAL, "he_automorphism: batch mismatch");
-    if (pin->d == pout->d) return fail(HE_EINVAL, "he_automorphism: the automorphism cannot be evaluated in place");
-    gal = reduce_gal(gal, r->logN, r->type);
+    TRY(check_level(*r, level, "he_automorphism"));
     CoReq q;
+    Operands o(q, "he_automorphism", *r);
+    o.in(hin, level + 1);
+    o.out(hout, level + 1);
+    TRY(o.check());  // (never in place)
+    gal = reduce_gal(gal, r->logN, r->type);
     q.op = CO_AUTO_COEFF; q.obj = r.get(); q.par[0] = level; q.par[1] = (int64_t)gal;
-    q.ops = {pin->view(), pout->view()};
-    q.keep = {r, pin, pout};
+    q.keep.push_back(r);
     q.run = [r, level, gal](const View *v, int B) -> int {
         r->ctx->acct(2.0 * (level + 1), 0, B, r->N);
         HIP_TRY(launch_automorphism_coeff(r->dev, ident_tab(level + 1), v[0], gal, v[1], B, r->ctx->stream, r->type == 1));
         return HE_OK;
     };
-    return co_dispatch(*r->ctx, pin->batch, q);
+    return co_dispatch(*r->ctx, o.B, q);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2526,11 +2588,6 @@ int modup_between(BasisExtender &be, bool src_is_q, int levelS, int levelD, View
     HIP_TRY(launch_modup(be.qp, ref.on(be.pool), a, src, dst, dst, batch, be.ctx->stream));
     return HE_OK;
 }
-int check_be_poly(const Poly &p, const BasisExtender &be, int nl, const char *who) {
-    if (p.ctx != be.ctx) return fail(HE_EINVAL, "%s: the polynomial belongs to another context", who);
-    if (p.N != be.Q->N || p.nlimbs < nl) return fail(HE_EINVAL, "%s: poly shape mismatch (needs %d limbs of degree %d)", who, nl, be.Q->N);
-    return HE_OK;
-}
 // ModDownQPtoQNTT for `batch` entries (basis_extension.go:235-256); pQ/pP NTT domain in, outQ NTT out.
 // scratch: sP [batch][levelP+1][N], sQ [batch][levelQ+1][N]
 int moddown_q_ntt(BasisExtender &be, int levelQ, int levelP, View pQ, View pP, View outQ, int batch, View sP, View sQ) {
@@ -2552,60 +2609,50 @@ int moddown_q_ntt(BasisExtender &be, int levelQ, int levelP, View pQ, View pP, V
 
 int he_modup_q_to_p(he_handle hbe, int levelQ, int levelP, he_handle hq, he_handle hp) {
     GET(be, BasisExtender, hbe, T_BE);
-    GET(pq, Poly, hq, T_POLY);
-    GET(pp, Poly, hp, T_POLY);
     if (levelQ < 0 || levelQ >= be->LQ || levelP < 0 || levelP >= be->LP) return fail(HE_EINVAL, "he_modup_q_to_p: level out of range");
-    TRY(check_be_poly(*pq, *be, levelQ + 1, "he_modup_q_to_p"));
-    TRY(check_be_poly(*pp, *be, levelP + 1, "he_modup_q_to_p"));
-    if (pq->batch != pp->batch) return fail(HE_EINVAL, "he_modup_q_to_p: batch mismatch");
-    TRY(reject_aliasing("he_modup_q_to_p", {{pq.get(), false, false}, {pp.get(), true, true}}));
     CoReq q;
+    Operands o(q, "he_modup_q_to_p", *be);
+    o.in(hq, levelQ + 1);
+    o.outP(hp, levelP + 1);
+    TRY(o.check());
     q.op = CO_MODUP; q.obj = be.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = 1;
-    q.ops = {pq->view(), pp->view()};
-    q.keep = {be, pq, pp};
+    q.keep.push_back(be);
     q.run = [be, levelQ, levelP](const View *v, int B) -> int {
         be->ctx->acct(levelQ + 1 + levelP + 1, 0, B, be->Q->N);  // ModUp: L_src + L_dst
         { Valu V(be->Q->logN); std::vector<int> d; for (int j = 0; j <= levelP; j++) d.push_back(be->LQ + j); valu_modup(V, be->small, 0, levelQ + 1, d); V.into(*be->ctx, B); }
         return modup_between(*be, true, levelQ, levelP, v[0], v[1], 0, B);
     };
-    return co_dispatch(*be->ctx, pq->batch, q);
+    return co_dispatch(*be->ctx, o.B, q);
 }
 int he_modup_p_to_q(he_handle hbe, int levelP, int levelQ, he_handle hp, he_handle hq) {
     GET(be, BasisExtender, hbe, T_BE);
-    GET(pq, Poly, hq, T_POLY);
-    GET(pp, Poly, hp, T_POLY);
     if (levelQ < 0 || levelQ >= be->LQ || levelP < 0 || levelP >= be->LP) return fail(HE_EINVAL, "he_modup_p_to_q: level out of range");
-    TRY(check_be_poly(*pq, *be, levelQ + 1, "he_modup_p_to_q"));
-    TRY(check_be_poly(*pp, *be, levelP + 1, "he_modup_p_to_q"));
-    if (pq->batch != pp->batch) return fail(HE_EINVAL, "he_modup_p_to_q: batch mismatch");
-    TRY(reject_aliasing("he_modup_p_to_q", {{pp.get(), false, true}, {pq.get(), true, false}}));
     CoReq q;
+    Operands o(q, "he_modup_p_to_q", *be);
+    o.inP(hp, levelP + 1);
+    o.out(hq, levelQ + 1);
+    TRY(o.check());
     q.op = CO_MODUP; q.obj = be.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = 0;
-    q.ops = {pp->view(), pq->view()};
-    q.keep = {be, pq, pp};
+    q.keep.push_back(be);
     q.run = [be, levelQ, levelP](const View *v, int B) -> int {
         be->ctx->acct(levelQ + 1 + levelP + 1, 0, B, be->Q->N);
         { Valu V(be->Q->logN); std::vector<int> d; for (int i = 0; i <= levelQ; i++) d.push_back(i); valu_modup(V, be->small, be->LQ, levelP + 1, d); V.into(*be->ctx, B); }
         return modup_between(*be, false, levelP, levelQ, v[0], v[1], 0, B);
     };
-    return co_dispatch(*be->ctx, pq->batch, q);
+    return co_dispatch(*be->ctx, o.B, q);
 }
 static int moddown_api(he_handle hbe, int levelQ, int levelP, he_handle h1q, he_handle h1p, he_handle h2, int kind, const char *who) {
     GET(be, BasisExtender, hbe, T_BE);
-    GET(p1q, Poly, h1q, T_POLY);
-    GET(p1p, Poly, h1p, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
     if (levelQ < 0 || levelQ >= be->LQ || levelP < 0 || levelP >= be->LP) return fail(HE_EINVAL, "%s: level out of range", who);
-    TRY(check_be_poly(*p1q, *be, levelQ + 1, who));
-    TRY(check_be_poly(*p1p, *be, levelP + 1, who));
-    TRY(check_be_poly(*p2, *be, (kind == 2 ? levelP : levelQ) + 1, who));
-    if (p1q->batch != p1p->batch || p1q->batch != p2->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    // in place: p2Q == p1Q (ModDownQPtoQ[NTT]) or p2P == p1P (ModDownQPtoP), element-wise in the last launch
-    TRY(reject_aliasing(who, {{p1q.get(), false, false}, {p1p.get(), false, true}, {p2.get(), true, kind == 2}}, {{kind == 2 ? 1 : 0, 2}}));
     CoReq q;
+    Operands o(q, who, *be);
+    const int iq = o.in(h1q, levelQ + 1), ip = o.inP(h1p, levelP + 1);
+    // in place: p2Q == p1Q (ModDownQPtoQ[NTT]) or p2P == p1P (ModDownQPtoP), element-wise in the last launch
+    if (kind == 2) o.inplace(o.outP(h2, levelP + 1), ip);
+    else o.inplace(o.out(h2, levelQ + 1), iq);
+    TRY(o.check());
     q.op = CO_MODDOWN_BE; q.obj = be.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = kind;
-    q.ops = {p1q->view(), p1p->view(), p2->view()};
-    q.keep = {be, p1q, p1p, p2};
+    q.keep.push_back(be);
     q.run = [be, levelQ, levelP, kind](const View *v, int B) -> int {
         const int N = be->Q->N;
         be->ctx->acct(kind == 2 ? levelQ + 1 + 2.0 * (levelP + 1) : 2.0 * (levelQ + 1) + levelP + 1, 0, B, N);  // ModDown: 2 L + alpha
@@ -2635,7 +2682,7 @@ static int moddown_api(he_handle hbe, int levelQ, int levelP, he_handle h1q, he_
         return HE_OK;
     };
     q.tables_ok = [be](bool *ok) -> int { *ok = be->type == 0; return HE_OK; };
-    return co_dispatch(*be->ctx, p1q->batch, q);
+    return co_dispatch(*be->ctx, o.B, q);
 }
 int he_moddown_qp_to_q(he_handle be, int lq, int lp, he_handle a, he_handle b, he_handle c) { return moddown_api(be, lq, lp, a, b, c, 0, "he_moddown_qp_to_q"); }
 int he_moddown_qp_to_q_ntt(he_handle be, int lq, int lp, he_handle a, he_handle b, he_handle c) { return moddown_api(be, lq, lp, a, b, c, 1, "he_moddown_qp_to_q_ntt"); }
@@ -2872,6 +2919,8 @@ int he_evk_commit(he_handle hk) {
 namespace {
 // BaseRNSDecompositionVectorSize, core/rlwe/params.go:543-550
 int base_rns_size(int levelQ, int levelP) { return levelP == -1 ? levelQ + 1 : (levelQ + levelP + 1) / (levelP + 1); }
+// digits of a gadget product with key k at levelQ (a base-2 gadget: the bit windows of limbs 0..levelQ)
+int key_beta(const Evk &k, int levelQ) { return k.pw2 ? k.prefix[levelQ + 1] : base_rns_size(levelQ, k.nPk - 1); }
 
 // DecomposeAndSplit for one digit (ring/basis_extension.go:381-502): coefficient-domain src
 // (limbs of ringQ) -> dstQ limbs (dstQ_limb0 + j) and dstP limbs (dstP_limb0 + j).
@@ -2959,7 +3008,7 @@ int ks_inner(Evaluator &ev, int levelQ, int levelP, View dec, size_t dec_ds, con
     BasisExtender &be = *ev.be;
     const int LQ = be.LQ, N = be.Q->N;
     KsArgs a{};
-    a.beta = k.pw2 ? k.prefix[levelQ + 1] : base_rns_size(levelQ, levelP);
+    a.beta = key_beta(k, levelQ);
     if (a.beta > k.beta) return fail(HE_EINVAL, "gadget product: key has %d digits, %d needed", k.beta, a.beta);
     const uint64_t *keyp = k.d;
     if (digit_end >= 0) {  // a sub-range of the digits (he_gadget_product_hoisted_lazy_digits): shift both operands
@@ -3173,7 +3222,7 @@ struct KsScratch {  // per gadget product, for `batch` entries
 };
 size_t ks_scratch_words(const BasisExtender &be, int levelQ, int levelP, int batch, bool need_dec, const Evk *key = nullptr) {
     const size_t N = be.Q->N, B = batch;
-    const size_t beta = (key && key->pw2) ? (size_t)key->prefix[levelQ + 1] : (size_t)base_rns_size(levelQ, levelP);
+    const size_t beta = key ? (size_t)key_beta(*key, levelQ) : (size_t)base_rns_size(levelQ, levelP);
     size_t w = 0;
     if (need_dec) w += B * (levelQ + 1) * N + B * beta * (be.LQ + be.LP) * N;
     w += 2 * B * (levelP + 1) * N * 2 + 2 * B * (levelQ + 1) * N * 2;
@@ -3187,21 +3236,17 @@ int decompose_fused(Evaluator &ev, const FusedPlan &plan, int levelQ, int levelP
 }
 int he_decompose_and_split(he_handle hev, int levelQ, int levelP, int nbPi, int digit, he_handle h0, he_handle h1q, he_handle h1p) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(p0, Poly, h0, T_POLY);
-    GET(p1q, Poly, h1q, T_POLY);
-    GET(p1p, Poly, h1p, T_POLY);
     BasisExtender &be = *ev->be;
     if (levelQ < 0 || levelQ >= be.LQ || levelP < 0 || levelP >= be.LP || nbPi < 1 || digit < 0)
         return fail(HE_EINVAL, "he_decompose_and_split: bad level/digit");
-    TRY(check_be_poly(*p0, be, levelQ + 1, "he_decompose_and_split"));
-    TRY(check_be_poly(*p1q, be, levelQ + 1, "he_decompose_and_split"));
-    TRY(check_be_poly(*p1p, be, levelP + 1, "he_decompose_and_split"));
-    if (p0->batch != p1q->batch || p0->batch != p1p->batch) return fail(HE_EINVAL, "he_decompose_and_split: batch mismatch");
-    TRY(reject_aliasing("he_decompose_and_split", {{p0.get(), false, false}, {p1q.get(), true, false}, {p1p.get(), true, true}}));
     CoReq q;
+    Operands o(q, "he_decompose_and_split", be);
+    o.in(h0, levelQ + 1);
+    o.out(h1q, levelQ + 1);
+    o.outP(h1p, levelP + 1);
+    TRY(o.check());
     q.op = CO_DECOMPOSE_SPLIT; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = nbPi; q.par[3] = digit;
-    q.ops = {p0->view(), p1q->view(), p1p->view()};
-    q.keep = {ev, p0, p1q, p1p};
+    q.keep.push_back(ev);
     q.run = [ev, levelQ, levelP, nbPi, digit](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(std::min(nbPi, levelQ + 1 - digit * nbPi) + levelQ + 1 + levelP + 1, 0, B, be.Q->N);  // ModUp of one digit
@@ -3216,7 +3261,7 @@ int he_decompose_and_split(he_handle hev, int levelQ, int levelP, int nbPi, int 
         }
         return decompose_digit(*ev, levelQ, levelP, nbPi, digit, v[0], v[1], 0, v[2], 0, B);
     };
-    return co_dispatch(*be.ctx, p0->batch, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 
 int he_decomp_create(he_handle hev, int batch, he_handle *out) {
@@ -3256,20 +3301,20 @@ int he_decomp_download_limb(he_handle h, int b, int digit, int is_p, int limb, u
 
 int he_decompose_ntt(he_handle hev, int levelQ, int levelP, int nbPi, he_handle hc2, int c2_is_ntt, he_handle hdec) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(c2, Poly, hc2, T_POLY);
     GET(dec, Decomp, hdec, T_DECOMP);
     BasisExtender &be = *ev->be;
     if (dec->ev != ev) return fail(HE_EINVAL, "he_decompose_ntt: decomposition buffer belongs to another evaluator");
     if (levelQ < 0 || levelQ >= be.LQ || levelP < 0 || levelP >= be.LP) return fail(HE_EINVAL, "he_decompose_ntt: level out of range");
-    TRY(check_be_poly(*c2, be, levelQ + 1, "he_decompose_ntt"));
-    if (c2->batch != dec->batch) return fail(HE_EINVAL, "he_decompose_ntt: batch mismatch");
     if (base_rns_size(levelQ, levelP) > dec->beta_max) return fail(HE_EINVAL, "he_decompose_ntt: too many digits");
+    CoReq q;
+    Operands o(q, "he_decompose_ntt", be, dec->batch);
+    o.in(hc2, levelQ + 1);
+    o.raw(dec->view(), dec);
+    TRY(o.check());
     dec->fillQ = -1;  // not filled until every launch below has been enqueued (check_decomp refuses a partial buffer)
     const size_t dec_ds = dec->dstride();
-    CoReq q;
     q.op = CO_DECOMPOSE_NTT; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = nbPi; q.par[3] = c2_is_ntt;
-    q.ops = {c2->view(), dec->view()};
-    q.keep = {ev, c2, dec};
+    q.keep.push_back(ev);
     q.run = [ev, levelQ, levelP, nbPi, c2_is_ntt, dec_ds](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -3301,34 +3346,12 @@ int he_decompose_ntt(he_handle hev, int levelQ, int levelP, int nbPi, he_handle 
         return decompose_ntt_into(*ev, levelQ, levelP, nbPi, ntt, inv, v[1], dec_ds, B);
     };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
-    TRY(co_dispatch(*be.ctx, c2->batch, q));
+    TRY(co_dispatch(*be.ctx, o.B, q));
     dec->fillQ = levelQ; dec->fillP = levelP; dec->fill_beta = base_rns_size(levelQ, levelP);
     return HE_OK;
 }
 
 namespace {
-struct QPOut {
-    std::shared_ptr<Poly> q0, p0, q1, p1;
-    View vp0() const { return p0 ? p0->view() : View{nullptr, 0}; }
-    View vp1() const { return p1 ? p1->view() : View{nullptr, 0}; }
-    std::vector<AliasOp> outs() const { return {{q0.get(), true, false}, {p0.get(), true, true}, {q1.get(), true, false}, {p1.get(), true, true}}; }
-};
-int get_qp_out(he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, const BasisExtender &be, int levelQ, int levelP, int batch,
-               QPOut &o, const char *who) {
-    o.q0 = get<Poly>(c0Q, T_POLY); o.q1 = get<Poly>(c1Q, T_POLY);
-    if (!o.q0 || !o.q1) return fail(HE_EHANDLE, "%s: bad output poly handle", who);
-    TRY(check_be_poly(*o.q0, be, levelQ + 1, who));
-    TRY(check_be_poly(*o.q1, be, levelQ + 1, who));
-    if (o.q0->batch != batch || o.q1->batch != batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    if (levelP < 0) return HE_OK;  // no special primes: the P handles are ignored (pass 0)
-    o.p0 = get<Poly>(c0P, T_POLY); o.p1 = get<Poly>(c1P, T_POLY);
-    if (!o.p0 || !o.p1) return fail(HE_EHANDLE, "%s: bad output poly handle", who);
-    TRY(check_be_poly(*o.p0, be, levelP + 1, who));
-    TRY(check_be_poly(*o.p1, be, levelP + 1, who));
-    if (o.p0->batch != batch || o.p1->batch != batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    return HE_OK;
-}
-
 // DecomposeNTT through the fused kernels: `rows_inv` = inverse ROWS pass of the NTT-domain input.
 // Own limbs are NOT written (ks_inner reads them from the input; he_decompose_ntt copies them).
 int decompose_fused(Evaluator &ev, const FusedPlan &plan, int levelQ, int levelP, int nbPi, View rows_inv, View dec, int batch,
@@ -3435,7 +3458,7 @@ int gadget_product_lazy_core(Evaluator &ev, int levelQ, View cx, int B, const Ev
     if (acc_q_f64) *acc_q_f64 = false;
     BasisExtender &be = *ev.be;
     const int levelP = k.nPk - 1, N = be.Q->N;
-    const int beta = k.pw2 ? k.prefix[levelQ + 1] : base_rns_size(levelQ, levelP);
+    const int beta = key_beta(k, levelQ);
     const size_t wq = (size_t)B * (levelQ + 1) * N, ds = (size_t)(be.LQ + be.LP) * N, bs = (size_t)beta * ds;
     uint64_t *cxinv = be.ctx->arena_take(wq);
     uint64_t *dec = be.ctx->arena_take((size_t)B * bs);
@@ -3692,30 +3715,32 @@ int check_decomp(const Evaluator &ev, const Decomp &dec, int levelQ, int levelP,
 static int keyswitch_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok);
 static int mul_relin_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok);
 // limbs of an evaluation key's 2 beta rows at (levelQ, levelP): read once per call, shared by the batch
-static double key_limbs(const Evk &k, int levelQ) {
-    const int levelP = k.nPk - 1;
-    const int beta = k.pw2 ? k.prefix[levelQ + 1] : base_rns_size(levelQ, levelP);
-    return 2.0 * beta * (levelQ + levelP + 2);
+static double key_limbs(const Evk &k, int levelQ) { return 2.0 * key_beta(k, levelQ) * (levelQ + k.nPk + 1); }
+// What every full key switch (gadget_product_core) starts with: the bytes it moves (`limbs` polynomial limbs per entry and the
+// key), its arithmetic, and its scratch plus `extra` words of the caller's.  decompose: the operand is decomposed here (false:
+// a hoisting buffer holds its digits).
+static int keyswitch_begin(Evaluator &ev, const Evk &k, int level, double limbs, bool decompose, int B, size_t extra = 0) {
+    BasisExtender &be = *ev.be;
+    be.ctx->acct(limbs, key_limbs(k, level), B, be.Q->N);
+    { Valu V(be.Q->logN); valu_gadget_product(V, be, level, k.nPk - 1, key_beta(k, level), decompose); V.into(*be.ctx, B); }
+    return be.ctx->arena_reserve(ks_scratch_words(be, level, k.nPk - 1, B, decompose, &k) + extra);
 }
 int he_gadget_product_lazy(he_handle hev, int levelQ, he_handle hcx, he_handle hk, he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(cx, Poly, hcx, T_POLY);
     GET(k, Evk, hk, T_EVK);
     BasisExtender &be = *ev->be;
     TRY(check_key(*ev, *k, levelQ, "he_gadget_product_lazy"));
-    TRY(check_be_poly(*cx, be, levelQ + 1, "he_gadget_product_lazy"));
-    QPOut o;
-    TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, k->nPk - 1, cx->batch, o, "he_gadget_product_lazy"));
-    TRY(reject_aliasing("he_gadget_product_lazy", {{cx.get(), false, false}, {o.q0.get(), true, false}, {o.p0.get(), true, true},
-                                                   {o.q1.get(), true, false}, {o.p1.get(), true, true}}));
     CoReq q;
+    Operands o(q, "he_gadget_product_lazy", be);
+    o.in(hcx, levelQ + 1, "cx");
+    o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, k->nPk - 1);
+    TRY(o.check());
     q.op = CO_GP_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.ops = {cx->view(), o.q0->view(), o.vp0(), o.q1->view(), o.vp1()};
-    q.keep = {ev, k, cx, o.q0, o.p0, o.q1, o.p1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, levelQ](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(levelQ + 1 + 2.0 * (levelQ + k->nPk + 1), key_limbs(*k, levelQ), B, be.Q->N);  // cx in, two QP accumulators out, key
-        { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, k->nPk - 1, k->pw2 ? k->prefix[levelQ + 1] : base_rns_size(levelQ, k->nPk - 1), true, true); V.into(*be.ctx, B); }
+        { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, k->nPk - 1, key_beta(*k, levelQ), true, true); V.into(*be.ctx, B); }
         TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, k->nPk - 1, B, true, k.get())));
         return gadget_product_lazy_core(*ev, levelQ, v[0], B, *k, v[1], v[2], v[3], v[4]);
     };
@@ -3728,7 +3753,7 @@ int he_gadget_product_lazy(he_handle hev, int levelQ, he_handle hcx, he_handle h
         *ok = plan->ok;
         return HE_OK;
     };
-    return co_dispatch(*be.ctx, cx->batch, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 int he_gadget_product_hoisted_lazy(he_handle hev, int levelQ, he_handle hdec, he_handle hk, he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P) {
     GET(ev, Evaluator, hev, T_EVAL);
@@ -3738,14 +3763,14 @@ int he_gadget_product_hoisted_lazy(he_handle hev, int levelQ, he_handle hdec, he
     TRY(check_key(*ev, *k, levelQ, "he_gadget_product_hoisted_lazy"));
     if (k->pw2) return fail(HE_EINVAL, "he_gadget_product_hoisted_lazy: method is unsupported for BaseTwoDecomposition != 0");
     TRY(check_decomp(*ev, *dec, levelQ, k->nPk - 1, "he_gadget_product_hoisted_lazy"));
-    QPOut o;
-    TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, k->nPk - 1, dec->batch, o, "he_gadget_product_hoisted_lazy"));
-    TRY(reject_aliasing("he_gadget_product_hoisted_lazy", o.outs()));
-    const size_t dec_ds = dec->dstride();
     CoReq q;
+    Operands o(q, "he_gadget_product_hoisted_lazy", be, dec->batch);
+    o.raw(dec->view(), dec);
+    o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, k->nPk - 1);
+    TRY(o.check());
+    const size_t dec_ds = dec->dstride();
     q.op = CO_GP_HOISTED_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.ops = {dec->view(), o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view()};
-    q.keep = {ev, k, dec, o.q0, o.p0, o.q1, o.p1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, levelQ, dec_ds](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + k->nPk + 1), key_limbs(*k, levelQ), B, be.Q->N);  // decomposition in, accumulators out, key
@@ -3766,23 +3791,23 @@ int he_gadget_product_hoisted_lazy_digits(he_handle hev, int levelQ, he_handle h
     TRY(check_decomp(*ev, *dec, levelQ, k->nPk - 1, who));
     const int beta = base_rns_size(levelQ, k->nPk - 1);
     if (digit_begin < 0 || digit_end > beta || digit_begin > digit_end) return fail(HE_EINVAL, "%s: digits [%d,%d) outside [0,%d)", who, digit_begin, digit_end, beta);
-    QPOut o;
-    TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, k->nPk - 1, dec->batch, o, who));
-    TRY(reject_aliasing(who, o.outs()));
+    CoReq q;  // (not filed: the launches below are made at once; the request only carries the operands' views)
+    Operands o(q, who, be, dec->batch);
+    o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, k->nPk - 1);
+    TRY(o.check());
     Scope sc(be.ctx.get());
     be.ctx->acct((double)(digit_end - digit_begin) * (levelQ + k->nPk + 1) + 2.0 * (levelQ + k->nPk + 1),
                  2.0 * (digit_end - digit_begin) * (levelQ + k->nPk + 1), dec->batch, be.Q->N);
     if (digit_begin == digit_end) {  // an empty share contributes zero -- to the limbs a non-empty share writes (levels + 1), not above
         const int lv[4] = {levelQ + 1, k->nPk, levelQ + 1, k->nPk};
-        int i = 0;
-        for (Poly *pp : {o.q0.get(), o.p0.get(), o.q1.get(), o.p1.get()}) {
+        for (int i = 0; i < 4; i++) {
+            const Poly *pp = o.ops[i].p;
             HIP_TRY(hipMemset2DAsync(pp->d, (size_t)pp->nlimbs * pp->N * 8, 0, (size_t)lv[i] * pp->N * 8, pp->batch, be.ctx->stream));
-            i++;
         }
         return HE_OK;
     }
-    return ks_inner(*ev, levelQ, k->nPk - 1, dec->view(), dec->dstride(), *k, o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view(),
-                    dec->batch, nullptr, 0, 0, digit_begin, digit_end);
+    return ks_inner(*ev, levelQ, k->nPk - 1, dec->view(), dec->dstride(), *k, q.ops[0], q.ops[1], q.ops[2], q.ops[3], dec->batch, nullptr, 0, 0,
+                    digit_begin, digit_end);
 }
 int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, he_handle hout0, he_handle hout1) {
     GET(ev, Evaluator, hev, T_EVAL);
@@ -3791,19 +3816,15 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
     BasisExtender &be = *ev->be;
     if (levelQ < 0 || levelQ >= be.LQ || levelP < -1 || levelP >= be.LP) return fail(HE_EINVAL, "he_moddown: level out of range");
     if (levelP == -1) {  // ModDown without special primes, NTT -> NTT: ctQP.Value[k].Q.CopyLvl(levelQ, ct.Value[k]) (:76-81)
-        GET(q0, Poly, c0Q, T_POLY);
-        GET(q1, Poly, c1Q, T_POLY);
-        for (Poly *pp : {q0.get(), q1.get(), out0.get(), out1.get()}) {
-            TRY(check_be_poly(*pp, be, levelQ + 1, "he_moddown"));
-            if (pp->batch != out0->batch) return fail(HE_EINVAL, "he_moddown: batch mismatch");
-        }
-        // out_k may be c_kQ (the reference's ModDown runs component by component); out_k == c_{1-k}Q is not in place
-        TRY(reject_aliasing("he_moddown", {{q0.get(), false, false}, {q1.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}},
-                            {{2, 0}, {3, 1}}));
         CoReq q;
+        Operands o(q, "he_moddown", be, out0->batch);
+        const int i0 = o.in(c0Q, levelQ + 1, "c0Q"), i1 = o.in(c1Q, levelQ + 1, "c1Q");
+        // out_k may be c_kQ (the reference's ModDown runs component by component); out_k == c_{1-k}Q is not in place
+        o.inplace(o.out(out0, levelQ + 1, "out0"), i0);
+        o.inplace(o.out(out1, levelQ + 1, "out1"), i1);
+        TRY(o.check());
         q.op = CO_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = -1;
-        q.ops = {q0->view(), q1->view(), out0->view(), out1->view()};
-        q.keep = {ev, q0, q1, out0, out1};
+        q.keep.push_back(ev);
         q.run = [ev, levelQ](const View *v, int B) -> int {
             BasisExtender &be = *ev->be;
             be.ctx->acct(4.0 * (levelQ + 1), 0, B, be.Q->N);
@@ -3814,17 +3835,14 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
         };
         return co_dispatch(*be.ctx, out0->batch, q);
     }
-    QPOut o;
-    TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, levelP, out0->batch, o, "he_moddown"));
-    TRY(check_be_poly(*out0, be, levelQ + 1, "he_moddown"));
-    TRY(check_be_poly(*out1, be, levelQ + 1, "he_moddown"));
-    if (out1->batch != out0->batch) return fail(HE_EINVAL, "he_moddown: batch mismatch");
-    TRY(reject_aliasing("he_moddown", {{o.q0.get(), false, false}, {o.p0.get(), false, true}, {o.q1.get(), false, false}, {o.p1.get(), false, true},
-                                       {out0.get(), true, false}, {out1.get(), true, false}}, {{4, 0}, {5, 2}}));
     CoReq q;
+    Operands o(q, "he_moddown", be, out0->batch);
+    const int ic = o.qp(false, c0Q, c0P, c1Q, c1P, levelQ, levelP);
+    o.inplace(o.out(out0, levelQ + 1, "out0"), ic);
+    o.inplace(o.out(out1, levelQ + 1, "out1"), ic + 2);
+    TRY(o.check());
     q.op = CO_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP;
-    q.ops = {o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view(), out0->view(), out1->view()};
-    q.keep = {ev, o.q0, o.p0, o.q1, o.p1, out0, out1};
+    q.keep.push_back(ev);
     q.run = [ev, levelQ, levelP](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(2.0 * (2.0 * (levelQ + 1) + levelP + 1), 0, B, be.Q->N);  // ModDown of both components: 2 (2 L + alpha)
@@ -3837,21 +3855,17 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
 }
 int he_eval_moddown_qp_to_q_ntt(he_handle hev, int levelQ, int levelP, he_handle h1q, he_handle h1p, he_handle h2) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(p1q, Poly, h1q, T_POLY);
-    GET(p1p, Poly, h1p, T_POLY);
-    GET(p2, Poly, h2, T_POLY);
     BasisExtender &be = *ev->be;
     const char *who = "he_eval_moddown_qp_to_q_ntt";
     if (levelQ < 0 || levelQ >= be.LQ || levelP < 0 || levelP >= be.LP) return fail(HE_EINVAL, "%s: level out of range", who);
-    TRY(check_be_poly(*p1q, be, levelQ + 1, who));
-    TRY(check_be_poly(*p1p, be, levelP + 1, who));
-    TRY(check_be_poly(*p2, be, levelQ + 1, who));
-    if (p1q->batch != p1p->batch || p1q->batch != p2->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    TRY(reject_aliasing(who, {{p1q.get(), false, false}, {p1p.get(), false, true}, {p2.get(), true, false}}, {{0, 2}}));
     CoReq q;
+    Operands o(q, who, be);
+    const int iq = o.in(h1q, levelQ + 1);
+    o.inP(h1p, levelP + 1);
+    o.inplace(o.out(h2, levelQ + 1), iq);
+    TRY(o.check());
     q.op = CO_EVAL_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP;
-    q.ops = {p1q->view(), p1p->view(), p2->view()};
-    q.keep = {ev, p1q, p1p, p2};
+    q.keep.push_back(ev);
     q.run = [ev, levelQ, levelP](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -3882,64 +3896,51 @@ int he_eval_moddown_qp_to_q_ntt(he_handle hev, int levelQ, int levelP, he_handle
         return HE_OK;
     };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
-    return co_dispatch(*be.ctx, p1q->batch, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 int he_gadget_product(he_handle hev, int levelQ, he_handle hcx, he_handle hk, he_handle hout0, he_handle hout1) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(cx, Poly, hcx, T_POLY);
     GET(k, Evk, hk, T_EVK);
-    GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
     BasisExtender &be = *ev->be;
     TRY(check_key(*ev, *k, levelQ, "he_gadget_product"));
-    TRY(check_be_poly(*cx, be, levelQ + 1, "he_gadget_product"));
-    TRY(check_be_poly(*out0, be, levelQ + 1, "he_gadget_product"));
-    TRY(check_be_poly(*out1, be, levelQ + 1, "he_gadget_product"));
-    if (out0->batch != cx->batch || out1->batch != cx->batch) return fail(HE_EINVAL, "he_gadget_product: batch mismatch");
-    TRY(reject_aliasing("he_gadget_product", {{cx.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}}, {{1, 0}, {2, 0}}));
+    CoReq q;
+    Operands o(q, "he_gadget_product", be);
+    const int ix = o.in(hcx, levelQ + 1, "cx"), i0 = o.out(hout0, levelQ + 1, "out0"), i1 = o.out(hout1, levelQ + 1, "out1");
+    o.all_inplace = true;
+    TRY(o.check());
     // an output that is the key switch's NTT-domain operand: its own-digit limbs are still being read while the fused epilogue
     // writes the outputs of OTHER entries' workgroups -- such requests (their own key: the aliasing pattern) are served one by one
-    const bool alias = cx->d == out0->d || cx->d == out1->d;
-    CoReq q;
+    const bool alias = o.same(ix, i0) || o.same(ix, i1);
     q.op = CO_GADGET_PRODUCT; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.ops = {cx->view(), out0->view(), out1->view()};
-    q.keep = {ev, k, cx, out0, out1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, levelQ](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        be.ctx->acct(3.0 * (levelQ + 1), key_limbs(*k, levelQ), B, be.Q->N);  // GadgetProduct: 3 L + 2 beta (L + alpha)
-        { Valu V(be.Q->logN); valu_gadget_product(V, be, levelQ, k->nPk - 1, k->pw2 ? k->prefix[levelQ + 1] : base_rns_size(levelQ, k->nPk - 1), true); V.into(*be.ctx, B); }
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, k->nPk - 1, B, true, k.get())));
+        TRY(keyswitch_begin(*ev, *k, levelQ, 3.0 * (levelQ + 1), true, B));  // GadgetProduct: 3 L + 2 beta (L + alpha)
         return gadget_product_core(*ev, levelQ, &v[0], nullptr, *k, v[1], v[2], B);
     };
     q.tables_ok = [ev, k, levelQ, alias](bool *ok) -> int {
         *ok = false;
         return alias ? HE_OK : keyswitch_tables_ok(*ev, levelQ, *k, ok);
     };
-    return co_dispatch(*be.ctx, cx->batch, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 int he_gadget_product_hoisted(he_handle hev, int levelQ, he_handle hdec, he_handle hk, he_handle hout0, he_handle hout1) {
     GET(ev, Evaluator, hev, T_EVAL);
     GET(dec, Decomp, hdec, T_DECOMP);
     GET(k, Evk, hk, T_EVK);
-    GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
     BasisExtender &be = *ev->be;
     TRY(check_key(*ev, *k, levelQ, "he_gadget_product_hoisted"));
     if (k->pw2) return fail(HE_EINVAL, "he_gadget_product_hoisted: method is unsupported for BaseTwoDecomposition != 0");
     TRY(check_decomp(*ev, *dec, levelQ, k->nPk - 1, "he_gadget_product_hoisted"));
-    TRY(check_be_poly(*out0, be, levelQ + 1, "he_gadget_product_hoisted"));
-    TRY(check_be_poly(*out1, be, levelQ + 1, "he_gadget_product_hoisted"));
-    if (out0->batch != dec->batch || out1->batch != dec->batch) return fail(HE_EINVAL, "he_gadget_product_hoisted: batch mismatch");
-    TRY(reject_aliasing("he_gadget_product_hoisted", {{out0.get(), true, false}, {out1.get(), true, false}}));
     CoReq q;
+    Operands o(q, "he_gadget_product_hoisted", be, dec->batch);
+    o.raw(dec->view(), dec);
+    o.out(hout0, levelQ + 1, "out0");
+    o.out(hout1, levelQ + 1, "out1");
+    TRY(o.check());
     q.op = CO_GP_HOISTED; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.ops = {dec->view(), out0->view(), out1->view()};
-    q.keep = {ev, k, dec, out0, out1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, levelQ](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        be.ctx->acct(key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + 1), key_limbs(*k, levelQ), B, be.Q->N);  // hoisted: decomposition in, 2 L out, key
-        { Valu V(be.Q->logN); valu_gadget_product(V, be, levelQ, k->nPk - 1, base_rns_size(levelQ, k->nPk - 1), false); V.into(*be.ctx, B); }
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, k->nPk - 1, B, false)));
+        TRY(keyswitch_begin(*ev, *k, levelQ, key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + 1), false, B));  // hoisted: decomposition in, 2 L out, key
         return gadget_product_core(*ev, levelQ, nullptr, &v[0], *k, v[1], v[2], B);
     };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
@@ -3949,37 +3950,28 @@ int he_gadget_product_hoisted(he_handle hev, int levelQ, he_handle hdec, he_hand
 // Relinearize (core/rlwe/evaluator_evaluationkey.go:117-148)
 int he_relinearize(he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hin2, he_handle hk, he_handle hout0, he_handle hout1) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(in0, Poly, hin0, T_POLY);
-    GET(in1, Poly, hin1, T_POLY);
-    GET(in2, Poly, hin2, T_POLY);
     GET(k, Evk, hk, T_EVK);
-    GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
     BasisExtender &be = *ev->be;
     TRY(check_key(*ev, *k, level, "he_relinearize"));
-    for (Poly *p : {in0.get(), in1.get(), in2.get(), out0.get(), out1.get()}) {
-        TRY(check_be_poly(*p, be, level + 1, "he_relinearize"));
-        if (p->batch != in0->batch) return fail(HE_EINVAL, "he_relinearize: batch mismatch");
-    }
-    TRY(reject_aliasing("he_relinearize", {{in0.get(), false, false}, {in1.get(), false, false}, {in2.get(), false, false}, {out0.get(), true, false},
-                                           {out1.get(), true, false}}, {{3, 0}, {3, 1}, {3, 2}, {4, 0}, {4, 1}, {4, 2}}));
+    CoReq q;
+    Operands o(q, "he_relinearize", be);
+    const int i0 = o.in(hin0, level + 1, "in0"), i1 = o.in(hin1, level + 1, "in1"), i2 = o.in(hin2, level + 1, "in2");
+    const int o0 = o.out(hout0, level + 1, "out0"), o1 = o.out(hout1, level + 1, "out1");
+    o.all_inplace = true;
+    TRY(o.check());
+    // crossed: an output is the OTHER component's addend -- the separate launches would write it before that component reads it,
+    // so the addends are staged first
+    const bool cross = o.same(i0, o1) || o.same(i1, o0);
     // Aliasing that the batched pipeline cannot take for a whole batch: an output that is the key switch's NTT-domain operand
     // (in2) or the OTHER component's addend.  An output equal to its own component's addend -- Relinearize in place -- is read and
     // written by the same thread and batches normally.
-    const bool alias = in2->d == out0->d || in2->d == out1->d || in0->d == out1->d || in1->d == out0->d;
-    // crossed: an output is the OTHER component's addend -- the separate launches would write it before that component reads it,
-    // so the addends are staged first
-    const bool cross = in0->d == out1->d || in1->d == out0->d;
-    CoReq q;
+    const bool alias = cross || o.same(i2, o0) || o.same(i2, o1);
     q.op = CO_RELINEARIZE; q.obj = ev.get(); q.key = k.get(); q.par[0] = level;
-    q.ops = {in0->view(), in1->view(), in2->view(), out0->view(), out1->view()};
-    q.keep = {ev, k, in0, in1, in2, out0, out1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, level, cross](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
-        be.ctx->acct(5.0 * (std::min(level, k->nQk - 1) + 1), key_limbs(*k, std::min(level, k->nQk - 1)), B, be.Q->N);  // Relinearize: 3 L in, 2 L out, key
-        { Valu V(be.Q->logN); const int lv = std::min(level, k->nQk - 1); valu_gadget_product(V, be, lv, k->nPk - 1, k->pw2 ? k->prefix[lv + 1] : base_rns_size(lv, k->nPk - 1), true); V.into(*be.ctx, B); }
         const size_t wQ = (size_t)B * (level + 1) * be.Q->N;
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, k->nPk - 1, B, true, k.get()) + (cross ? 2 * wQ + 4 : 0)));
+        TRY(keyswitch_begin(*ev, *k, level, 5.0 * (level + 1), true, B, cross ? 2 * wQ + 4 : 0));  // Relinearize: 3 L in, 2 L out, key
         if (cross) {  // (served one by one: plain views)
             View a0{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N}, a1{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N};
             HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, be.ctx->stream));
@@ -3992,7 +3984,7 @@ int he_relinearize(he_handle hev, int level, he_handle hin0, he_handle hin1, he_
         *ok = false;
         return alias ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
     };
-    return co_dispatch(*be.ctx, in0->batch, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 
 // Automorphism / AutomorphismHoisted (core/rlwe/evaluator_automorphism.go:13-100), NTT domain
@@ -4024,11 +4016,9 @@ static int automorphism_core(Evaluator &ev, int level, View in0, const View *in1
                              View out1, int B) {
     BasisExtender &be = *ev.be;
     const int N = be.Q->N;
-    // Rotate: (4 L + 2 beta (L + alpha)); hoisted: the decomposition replaces the second input
-    be.ctx->acct(dec ? 3.0 * (level + 1) + key_limbs(k, level) / 2 : 4.0 * (level + 1), key_limbs(k, level), B, N);
-    { Valu V(be.Q->logN); valu_gadget_product(V, be, level, k.nPk - 1, k.pw2 ? k.prefix[level + 1] : base_rns_size(level, k.nPk - 1), !dec); V.into(*be.ctx, B); }
     const size_t wQ = (size_t)B * (level + 1) * N;
-    TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, k.nPk - 1, B, !dec, &k) + 2 * wQ + (size_t)N));
+    // Rotate: (4 L + 2 beta (L + alpha)); hoisted: the decomposition replaces the second input
+    TRY(keyswitch_begin(ev, k, level, dec ? 3.0 * (level + 1) + key_limbs(k, level) / 2 : 4.0 * (level + 1), !dec, B, 2 * wQ + (size_t)N));
     hipStream_t st = be.ctx->stream;
     // The automorphism is applied where the key switch writes its result: the fused ModDown epilogues store coefficient e at
     // index_{g^-1}[e] (NttEpilogue::scatter_ginv), so that the intermediate ciphertext and the two gather passes over it disappear.
@@ -4064,35 +4054,26 @@ static int automorphism_core(Evaluator &ev, int level, View in0, const View *in1
 static int automorphism_common(he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hdec, uint64_t gal, he_handle hk,
                                he_handle hout0, he_handle hout1, const char *who) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(in0, Poly, hin0, T_POLY);
     GET(k, Evk, hk, T_EVK);
-    GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
-    std::shared_ptr<Poly> in1;
     std::shared_ptr<Decomp> dec;
     if (hdec) { dec = get<Decomp>(hdec, T_DECOMP); if (!dec) return fail(HE_EHANDLE, "%s: bad decomposition handle", who); }
-    else { in1 = get<Poly>(hin1, T_POLY); if (!in1) return fail(HE_EHANDLE, "%s: bad poly handle", who); }
     BasisExtender &be = *ev->be;
     TRY(check_key(*ev, *k, level, who));
-    TRY(check_be_poly(*in0, be, level + 1, who));
-    TRY(check_be_poly(*out0, be, level + 1, who));
-    TRY(check_be_poly(*out1, be, level + 1, who));
-    if (in1) TRY(check_be_poly(*in1, be, level + 1, who));
-    const int B = in0->batch;
-    if (out0->batch != B || out1->batch != B || (in1 && in1->batch != B) || (dec && dec->batch != B)) return fail(HE_EINVAL, "%s: batch mismatch", who);
+    const bool hoisted = dec != nullptr;
+    CoReq q;
+    Operands o(q, who, be, hoisted ? dec->batch : Operands::kCall);
+    const int i0 = o.in(hin0, level + 1, "in0"), i1 = hoisted ? o.raw(dec->view(), dec) : o.in(hin1, level + 1, "in1");
+    const int o0 = o.out(hout0, level + 1, "out0"), o1 = o.out(hout1, level + 1, "out1");
+    o.all_inplace = true;
+    TRY(o.check());
     if (!(gal & 1)) return fail(HE_EINVAL, "%s: Galois element must be odd", who);
     if (dec && k->pw2) return fail(HE_EINVAL, "%s: method is unsupported for BaseTwoDecomposition != 0", who);
     if (dec) TRY(check_decomp(*ev, *dec, level, k->nPk - 1, who));
-    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}},
-                        {{2, 0}, {2, 1}, {3, 0}, {3, 1}}));
     gal = reduce_gal(gal, be.Q->logN, be.type);
     // (an automorphism that writes onto its own inputs takes the gather form, which reads them all first: no entry tables then)
-    const bool alias = in0->d == out0->d || in0->d == out1->d || (in1 && (in1->d == out0->d || in1->d == out1->d));
-    const bool hoisted = dec != nullptr;
-    CoReq q;
+    const bool alias = o.same(i0, o0) || o.same(i0, o1) || o.same(i1, o0) || o.same(i1, o1);
     q.op = hoisted ? CO_AUTO_HOISTED : CO_AUTOMORPHISM; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = (int64_t)gal;
-    q.ops = {in0->view(), hoisted ? dec->view() : in1->view(), out0->view(), out1->view()};
-    q.keep = {ev, k, in0, in1, dec, out0, out1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, level, gal, hoisted](const View *v, int B) -> int {
         return automorphism_core(*ev, level, v[0], hoisted ? nullptr : &v[1], hoisted ? &v[1] : nullptr, gal, *k, v[2], v[3], B);
     };
@@ -4100,7 +4081,7 @@ static int automorphism_common(he_handle hev, int level, he_handle hin0, he_hand
         *ok = false;
         return alias ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
     };
-    return co_dispatch(*be.ctx, B, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 int he_automorphism_ct(he_handle ev, int level, he_handle in0, he_handle in1, uint64_t gal, he_handle gk, he_handle out0, he_handle out1) {
     return automorphism_common(ev, level, in0, in1, 0, gal, gk, out0, out1, "he_automorphism_ct");
@@ -4114,7 +4095,6 @@ int he_automorphism_hoisted(he_handle ev, int level, he_handle in0, he_handle de
 int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_handle hdec, uint64_t gal, he_handle hk, he_handle c0Q,
                                  he_handle c0P, he_handle c1Q, he_handle c1P) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(in0, Poly, hin0, T_POLY);
     GET(dec, Decomp, hdec, T_DECOMP);
     GET(k, Evk, hk, T_EVK);
     BasisExtender &be = *ev->be;
@@ -4124,21 +4104,20 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
     if (k->pw2) return fail(HE_EINVAL, "he_automorphism_hoisted_lazy: method is unsupported for BaseTwoDecomposition != 0");
     if (!(gal & 1)) return fail(HE_EINVAL, "he_automorphism_hoisted_lazy: Galois element must be odd");
     TRY(check_decomp(*ev, *dec, levelQ, levelP, "he_automorphism_hoisted_lazy"));
-    TRY(check_be_poly(*in0, be, levelQ + 1, "he_automorphism_hoisted_lazy"));
-    if (in0->batch != B) return fail(HE_EINVAL, "he_automorphism_hoisted_lazy: batch mismatch");
-    QPOut o;
-    TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, levelP, B, o, "he_automorphism_hoisted_lazy"));
-    // a Q output may be in0 (read before it is written: the gather form below)
-    std::vector<AliasOp> ops = o.outs();
-    ops.push_back({in0.get(), false, false});
-    TRY(reject_aliasing("he_automorphism_hoisted_lazy", ops, {{0, 4}, {2, 4}}));
-    gal = reduce_gal(gal, be.Q->logN, be.type);
-    const bool alias = o.q0->d == in0->d || o.q1->d == in0->d;
-    const size_t dec_ds = dec->dstride();
     CoReq q;
+    Operands o(q, "he_automorphism_hoisted_lazy", be, B);
+    const int ii = o.in(hin0, levelQ + 1, "in0");
+    o.raw(dec->view(), dec);
+    const int ic = o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, levelP);
+    // a Q output may be in0 (read before it is written: the gather form below)
+    o.inplace(ic, ii);
+    o.inplace(ic + 2, ii);
+    TRY(o.check());
+    gal = reduce_gal(gal, be.Q->logN, be.type);
+    const bool alias = o.same(ic, ii) || o.same(ic + 2, ii);
+    const size_t dec_ds = dec->dstride();
     q.op = CO_AUTO_HOISTED_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ; q.par[1] = (int64_t)gal;
-    q.ops = {in0->view(), dec->view(), o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view()};
-    q.keep = {ev, k, in0, dec, o.q0, o.p0, o.q1, o.p1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, levelQ, levelP, gal, alias, dec_ds](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -4195,29 +4174,23 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
                            he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, int accumulate) {
     const char *who = "he_lintrans_giant_step";
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(cx, Poly, hcx, T_POLY);
     GET(k, Evk, hk, T_EVK);
-    GET(addQ, Poly, haddQ, T_POLY);
     BasisExtender &be = *ev->be;
     TRY(check_key(*ev, *k, levelQ, who));
-    TRY(check_be_poly(*cx, be, levelQ + 1, who));
-    TRY(check_be_poly(*addQ, be, levelQ + 1, who));
-    const int levelP = k->nPk - 1, B = cx->batch;
+    const int levelP = k->nPk - 1;
     if (levelP < 0) return fail(HE_EINVAL, "%s: the key has no special primes", who);
     if (!(gal & 1)) return fail(HE_EINVAL, "%s: Galois element must be odd", who);
-    GET(addP, Poly, haddP, T_POLY);
-    TRY(check_be_poly(*addP, be, levelP + 1, who));
-    if (addQ->batch != B || addP->batch != B) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    QPOut o;
-    TRY(get_qp_out(c0Q, c0P, c1Q, c1P, be, levelQ, levelP, B, o, who));
-    std::vector<AliasOp> ops = o.outs();
-    ops.insert(ops.end(), {{cx.get(), false, false}, {addQ.get(), false, false}, {addP.get(), false, true}});
-    TRY(reject_aliasing(who, ops));  // no output may alias an input or another output
-    gal = reduce_gal(gal, be.Q->logN, be.type);
     CoReq q;
+    Operands o(q, who, be);
+    o.in(hcx, levelQ + 1, "cx");
+    o.in(haddQ, levelQ + 1, "addQ");
+    o.inP(haddP, levelP + 1, "addP");
+    o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, levelP);
+    TRY(o.check());  // no output may alias an input or another output
+    const int B = o.B;
+    gal = reduce_gal(gal, be.Q->logN, be.type);
     q.op = CO_GIANT_STEP; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ; q.par[1] = (int64_t)gal; q.par[2] = accumulate ? 1 : 0;
-    q.ops = {cx->view(), addQ->view(), addP->view(), o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view()};
-    q.keep = {ev, k, cx, addQ, addP, o.q0, o.p0, o.q1, o.p1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, levelQ, levelP, gal, accumulate](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -4272,22 +4245,16 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
 // centred lifts / hoisting-buffer fill of bootstrapping.Evaluator.ModUp (see hering.h)
 int he_centered_lift(he_handle hev, int strict, he_handle hsrc, int first_q, int levelQ, he_handle hdq, int levelP, he_handle hdp) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(src, Poly, hsrc, T_POLY);
-    GET(dq, Poly, hdq, T_POLY);
     BasisExtender &be = *ev->be;
     const char *who = "he_centered_lift";
     if (first_q < 0 || levelQ >= be.LQ || first_q > levelQ + 1 || levelP >= be.LP) return fail(HE_EINVAL, "%s: level out of range", who);
-    TRY(check_be_poly(*src, be, 1, who));
-    TRY(check_be_poly(*dq, be, levelQ + 1, who));
-    if (src->batch != dq->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    std::shared_ptr<Poly> dp;
-    if (levelP >= 0) {
-        dp = get<Poly>(hdp, T_POLY);
-        if (!dp) return fail(HE_EHANDLE, "%s: bad P poly handle", who);
-        TRY(check_be_poly(*dp, be, levelP + 1, who));
-        if (dp->batch != src->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    }
-    TRY(reject_aliasing(who, {{src.get(), false, false}, {dq.get(), true, false}, {dp.get(), true, true}}, {{1, 0}}));
+    CoReq q;
+    Operands o(q, who, be);
+    const int is = o.in(hsrc, 1, "src"), iq = o.out(hdq, levelQ + 1, "dstQ");
+    const int ip = o.outP(levelP >= 0 ? o.poly(hdp) : nullptr, levelP + 1, "dstP");
+    o.inplace(iq, is);
+    TRY(o.check());
+    if (levelP < 0) q.ops[ip] = q.ops[iq];  // (no P part: the launch writes nothing through it)
     ModUpArgs a{};
     a.nsrc = 1;
     a.src_limb[0] = 0;
@@ -4297,36 +4264,33 @@ int he_centered_lift(he_handle hev, int strict, he_handle hsrc, int first_q, int
     for (int j = 0; j <= levelP; j++, n++) { a.dst_limb[n] = (uint8_t)j; a.dst_mod[n] = (uint8_t)(be.LQ + j); a.dst_view[n] = 1; }
     a.ndst = n;
     if (n > kMaxLimbs) return fail(HE_EINVAL, "%s: too many destination limbs", who);
-    CoReq q;
     q.op = CO_CENTERED_LIFT; q.obj = ev.get(); q.par[0] = strict & 3; q.par[1] = first_q; q.par[2] = levelQ; q.par[3] = levelP;
-    q.ops = {src->view(), dq->view(), dp ? dp->view() : dq->view()};
-    q.keep = {ev, src, dq, dp};
+    q.keep.push_back(ev);
     q.run = [ev, a, n, strict](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(1.0 + n, 0, B, be.Q->N);
         HIP_TRY(launch_center_copy(be.qp, a, v[0], v[1], v[2], B, be.ctx->stream, strict & 3));
         return HE_OK;
     };
-    return co_dispatch(*be.ctx, src->batch, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 int he_decomp_fill(he_handle hdec, int levelQ, int levelP, he_handle hq, he_handle hp) {
     GET(d, Decomp, hdec, T_DECOMP);
-    GET(sq, Poly, hq, T_POLY);
-    GET(sp, Poly, hp, T_POLY);
     BasisExtender &be = *d->ev->be;
     const char *who = "he_decomp_fill";
     if (levelQ < 0 || levelQ >= be.LQ || levelP < 0 || levelP >= be.LP) return fail(HE_EINVAL, "%s: level out of range", who);
-    TRY(check_be_poly(*sq, be, levelQ + 1, who));
-    TRY(check_be_poly(*sp, be, levelP + 1, who));
-    if (sq->batch != d->batch || sp->batch != d->batch) return fail(HE_EINVAL, "%s: batch mismatch", who);
+    CoReq q;
+    Operands o(q, who, be, d->batch);
+    o.in(hq, levelQ + 1, "srcQ");
+    o.inP(hp, levelP + 1, "srcP");
+    o.raw(d->view(), d);
+    TRY(o.check());
     d->fillQ = -1;  // see he_decompose_ntt
     const std::shared_ptr<Evaluator> ev = d->ev;
     const int beta_max = d->beta_max;
     const size_t dec_ds = d->dstride();
-    CoReq q;
     q.op = CO_DECOMP_FILL; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP;
-    q.ops = {sq->view(), sp->view(), d->view()};
-    q.keep = {ev, sq, sp, d};
+    q.keep.push_back(ev);
     q.run = [ev, levelQ, levelP, beta_max, dec_ds](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(levelQ + levelP + 2 + (double)beta_max * (levelQ + levelP + 2), 0, B, be.Q->N);
@@ -4352,30 +4316,16 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
     if (n < 0 || n > kMaxDiag) return fail(HE_EINVAL, "%s: n must be in [0, %d]", who, kMaxDiag);
     if (levelQ < 0 || levelQ >= be.LQ || levelP < 0 || levelP >= be.LP) return fail(HE_EINVAL, "%s: level out of range", who);
     if (n > 0 && (!ptQ || !ptP || !ct0Q || !ct0P || !ct1Q || !ct1P)) return fail(HE_EINVAL, "%s: null array", who);
-    GET(q0, Poly, o0Q, T_POLY);
-    GET(p0, Poly, o0P, T_POLY);
-    GET(q1, Poly, o1Q, T_POLY);
-    GET(p1, Poly, o1P, T_POLY);
-    const int B = q0->batch;
-    QPOut o;
-    TRY(get_qp_out(o0Q, o0P, o1Q, o1P, be, levelQ, levelP, B, o, who));
     // operands of the request: [0..3] the outputs, then per term i: 6 i + 4 + {0: ptQ, 1: c0Q, 2: c1Q, 3: ptP, 4: c0P, 5: c1P}
     // (null views for the P part of a term without one)
     CoReq q;
     q.op = CO_LINTRANS; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = n; q.par[3] = accumulate ? 1 : 0;
-    q.ops = {o.q0->view(), o.p0->view(), o.q1->view(), o.p1->view()};
-    q.keep = {ev, o.q0, o.p0, o.q1, o.p1};
+    Operands o(q, who, be);
+    o.qp(true, o0Q, o0P, o1Q, o1P, levelQ, levelP);
+    q.keep.push_back(ev);
     std::vector<const uint32_t *> idx(n, nullptr);
     std::vector<uint64_t> idx_gal(n, 0);
-    std::vector<AliasOp> aops = o.outs();  // every operand, for reject_aliasing below (kept alive by q.keep)
     for (int i = 0; i < n; i++) {
-        GET(tq, Poly, ptQ[i], T_POLY);
-        GET(c0q, Poly, ct0Q[i], T_POLY);
-        GET(c1q, Poly, ct1Q[i], T_POLY);
-        TRY(check_be_poly(*tq, be, levelQ + 1, who));
-        TRY(check_be_poly(*c0q, be, levelQ + 1, who));
-        TRY(check_be_poly(*c1q, be, levelQ + 1, who));
-        if ((tq->batch != 1 && tq->batch != B) || c0q->batch != B || c1q->batch != B) return fail(HE_EINVAL, "%s: batch mismatch (term %d)", who, i);
         if (index && index[i]) {
             GET(ixo, AutoIndex, index[i], T_INDEX);
             if (ixo->N != be.Q->N) return fail(HE_EINVAL, "%s: automorphism index of another degree", who);
@@ -4385,30 +4335,16 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
         }
         q.blob.push_back(idx_gal[i]);  // (the rotation of the term is part of the key -- by Galois element, see gather_api)
         q.blob.push_back((uint64_t)(uintptr_t)idx[i]);  // ... and by the cached table (another ring type: another permutation)
-        View vt = tq->view();
-        if (tq->batch == 1) vt.bstride = 0;  // one plaintext diagonal for the whole batch
-        q.ops.push_back(vt); q.ops.push_back(c0q->view()); q.ops.push_back(c1q->view());
-        q.keep.push_back(tq); q.keep.push_back(c0q); q.keep.push_back(c1q);
-        aops.insert(aops.end(), {{tq.get(), false, false}, {c0q.get(), false, false}, {c1q.get(), false, false}});
         if ((ct0P[i] == 0) != (ct1P[i] == 0)) return fail(HE_EINVAL, "%s: term %d has only one P part", who, i);
-        if (ct0P[i] == 0) {
-            q.ops.push_back(View{nullptr, 0}); q.ops.push_back(View{nullptr, 0}); q.ops.push_back(View{nullptr, 0});
-            continue;
-        }
-        GET(tp, Poly, ptP[i], T_POLY);
-        GET(c0p, Poly, ct0P[i], T_POLY);
-        GET(c1p, Poly, ct1P[i], T_POLY);
-        TRY(check_be_poly(*tp, be, levelP + 1, who));
-        TRY(check_be_poly(*c0p, be, levelP + 1, who));
-        TRY(check_be_poly(*c1p, be, levelP + 1, who));
-        if ((tp->batch != 1 && tp->batch != B) || c0p->batch != B || c1p->batch != B) return fail(HE_EINVAL, "%s: batch mismatch (term %d)", who, i);
-        View vp = tp->view();
-        if (tp->batch == 1) vp.bstride = 0;
-        q.ops.push_back(vp); q.ops.push_back(c0p->view()); q.ops.push_back(c1p->view());
-        q.keep.push_back(tp); q.keep.push_back(c0p); q.keep.push_back(c1p);
-        aops.insert(aops.end(), {{tp.get(), false, true}, {c0p.get(), false, true}, {c1p.get(), false, true}});
+        const bool hasP = ct0P[i] != 0;
+        o.in(ptQ[i], levelQ + 1, "ptQ", Operands::kBroadcast);  // one plaintext diagonal may serve the whole batch
+        o.in(ct0Q[i], levelQ + 1, "ct0Q");
+        o.in(ct1Q[i], levelQ + 1, "ct1Q");
+        o.inP(hasP ? o.poly(ptP[i]) : nullptr, levelP + 1, "ptP", Operands::kBroadcast);
+        o.inP(hasP ? o.poly(ct0P[i]) : nullptr, levelP + 1, "ct0P");
+        o.inP(hasP ? o.poly(ct1P[i]) : nullptr, levelP + 1, "ct1P");
     }
-    TRY(reject_aliasing(who, aops));  // the outputs alias nothing: the terms' inputs are read by every workgroup of both launches
+    TRY(o.check());  // the outputs alias nothing: the terms' inputs are read by every workgroup of both launches
     q.run = [ev, levelQ, levelP, n, accumulate, idx](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         DiagMacArgs aq{}, ap{};
@@ -4445,7 +4381,7 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
         HIP_TRY(launch_diag_mac(be.qp, ap, v[1], v[3], B, st));
         return HE_OK;
     };
-    return co_dispatch(*be.ctx, B, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 
 // CKKS mulRelin / BGV tensorStandard (schemes/ckks/evaluator.go:764-872, schemes/bgv/evaluator.go:592-685)
@@ -4468,7 +4404,7 @@ static int mul_relin_core(Evaluator &ev, int level, bool bgv, uint64_t t, Evk *k
     {
         Valu V(be.Q->logN);
         for (int i = 0; i <= level; i++) V.mul(cls_f64(be.small, i), 6.0);  // the tensor
-        if (k) valu_gadget_product(V, be, level, k->nPk - 1, k->pw2 ? k->prefix[level + 1] : base_rns_size(level, k->nPk - 1), true);
+        if (k) valu_gadget_product(V, be, level, k->nPk - 1, key_beta(*k, level), true);
         V.into(*be.ctx, B);
     }
     if (k) be.ctx->acct(6.0 * (level + 1), key_limbs(*k, std::min(level, k->nQk - 1)), B, N);  // MulRelin: 6 L + 2 beta (L + alpha)
@@ -4524,14 +4460,7 @@ static int keyswitch_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok)
 static int mul_relin_common(he_handle hev, int level, bool bgv, uint64_t t, he_handle ha0, he_handle ha1, he_handle hb0, he_handle hb1,
                             he_handle hk, he_handle hout0, he_handle hout1, he_handle hout2, const char *who) {
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(a0, Poly, ha0, T_POLY);
-    GET(a1, Poly, ha1, T_POLY);
-    GET(b0, Poly, hb0, T_POLY);
-    GET(b1, Poly, hb1, T_POLY);
-    GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
     std::shared_ptr<Evk> k;
-    std::shared_ptr<Poly> out2;
     BasisExtender &be = *ev->be;
     if (level < 0 || level >= be.LQ) return fail(HE_EINVAL, "%s: level out of range", who);
     if (hk) {
@@ -4540,33 +4469,27 @@ static int mul_relin_common(he_handle hev, int level, bool bgv, uint64_t t, he_h
         int lv = level;
         TRY(check_key(*ev, *k, lv, who));
         if (lv != level) return fail(HE_EINVAL, "%s: relinearization key level %d below ciphertext level %d", who, k->nQk - 1, level);
-    } else {
-        out2 = get<Poly>(hout2, T_POLY);
-        if (!out2) return fail(HE_EHANDLE, "%s: out2 required when no relinearization key is given", who);
     }
-    const int B = a0->batch;
-    for (Poly *p : {a0.get(), a1.get(), b0.get(), b1.get(), out0.get(), out1.get(), out2.get()}) {
-        if (!p) continue;
-        TRY(check_be_poly(*p, be, level + 1, who));
-        if (p->batch != B) return fail(HE_EINVAL, "%s: batch mismatch", who);
-    }
-    // any output may be any input (MulRelin(res, res, res)); out2 is an output only without a key
-    TRY(reject_aliasing(who, {{a0.get(), false, false}, {a1.get(), false, false}, {b0.get(), false, false}, {b1.get(), false, false},
-                              {out0.get(), true, false}, {out1.get(), true, false}, {out2.get(), true, false}},
-                        {{4, 0}, {4, 1}, {4, 2}, {4, 3}, {5, 0}, {5, 1}, {5, 2}, {5, 3}, {6, 0}, {6, 1}, {6, 2}, {6, 3}}));
-    bool alias = false;
-    for (Poly *o : {out0.get(), out1.get()})
-        for (Poly *in : {a0.get(), a1.get(), b0.get(), b1.get()}) alias = alias || o->d == in->d;
-    // (a degree-2 output that is one of the inputs: the tensor kernel reads all four inputs of a coefficient before it writes)
     CoReq q;
+    Operands o(q, who, be);
+    const int i0 = o.in(ha0, level + 1, "a0");
+    o.in(ha1, level + 1, "a1");
+    o.in(hb0, level + 1, "b0");
+    o.in(hb1, level + 1, "b1");
+    const int o0 = o.out(hout0, level + 1, "out0"), o1 = o.out(hout1, level + 1, "out1");
+    o.out(k ? nullptr : o.poly(hout2), level + 1, "out2 (required when no relinearization key is given)");  // an output only without a key
+    o.all_inplace = true;  // any output may be any input (MulRelin(res, res, res))
+    TRY(o.check());
+    bool alias = false;
+    for (int in = i0; in < i0 + 4; in++) alias = alias || o.same(o0, in) || o.same(o1, in);
+    // (a degree-2 output that is one of the inputs: the tensor kernel reads all four inputs of a coefficient before it writes)
     q.op = k ? CO_MUL_RELIN : CO_MUL; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = bgv; q.par[2] = (int64_t)(bgv ? t : 0);
-    q.ops = {a0->view(), a1->view(), b0->view(), b1->view(), out0->view(), out1->view(), out2 ? out2->view() : View{nullptr, 0}};
-    q.keep = {ev, k, a0, a1, b0, b1, out0, out1, out2};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, level, bgv, t, alias](const View *v, int B) -> int {
         return mul_relin_core(*ev, level, bgv, t, k.get(), v[0], v[1], v[2], v[3], v[4], v[5], v[6], B, alias);
     };
     if (k) q.tables_ok = [ev, k, level](bool *ok) -> int { return mul_relin_tables_ok(*ev, level, *k, ok); };
-    return co_dispatch(*be.ctx, B, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 int he_ckks_mul_relin(he_handle ev, int level, he_handle a0, he_handle a1, he_handle b0, he_handle b1, he_handle rlk, he_handle o0, he_handle o1, he_handle o2) {
     return mul_relin_common(ev, level, false, 0, a0, a1, b0, b1, rlk, o0, o1, o2, "he_ckks_mul_relin");
@@ -4580,17 +4503,14 @@ int he_bgv_mul_relin(he_handle ev, int level, uint64_t t, he_handle a0, he_handl
 // ---------------------------------------------------------------------------------------
 // kinds of CO_RING_SWITCH (par[0])
 enum { RS_FOLD_NTT = 0, RS_REPLICATE_NTT, RS_STRIDE_DOWN, RS_STRIDE_UP };
-// a pair of polynomials of one context and batch, of degrees (n, n << log_gap) in either order, n >= 16, limbs 0..level in both
+// a pair of polynomials of degrees (n, n << log_gap) in either order, n >= 16 (context, batch and limbs: the operand checks)
 static int ring_switch_shape(const Poly &a, const Poly &b, int level, int *log_gap, const char *who) {
-    if (a.ctx != b.ctx) return fail(HE_EINVAL, "%s: the polynomials belong to different contexts", who);
-    if (a.batch != b.batch) return fail(HE_EINVAL, "%s: batch mismatch (%d, %d)", who, a.batch, b.batch);
     const int lo = std::min(a.N, b.N), hi = std::max(a.N, b.N);
     if (lo < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, lo);
     int lg = 0;
     while ((lo << lg) < hi) lg++;
     if ((lo << lg) != hi) return fail(HE_EINVAL, "%s: degrees %d and %d are not a power-of-two ratio", who, lo, hi);
-    if (level < 0 || level >= kMaxLimbs || a.nlimbs < level + 1 || b.nlimbs < level + 1)
-        return fail(HE_EINVAL, "%s: level %d out of range for polynomials of %d and %d limbs", who, level, a.nlimbs, b.nlimbs);
+    if (level < 0 || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range", who, level);
     *log_gap = lg;
     return HE_OK;
 }
@@ -4623,17 +4543,19 @@ static int ring_switch_launch(Ctx &c, const Ring *large, int kind, int level, in
     return HE_OK;
 }
 // files one ring-degree map of in -> out (distinct handles of different degree) on the context's queue, served one by one
-static int ring_switch_file(const std::shared_ptr<Ring> &large, int kind, int level, int log_gap, const std::shared_ptr<Poly> &in,
-                            const std::shared_ptr<Poly> &out) {
+static int ring_switch_file(const char *who, const std::shared_ptr<Ring> &large, int kind, int level, int log_gap,
+                            const std::shared_ptr<Poly> &in, const std::shared_ptr<Poly> &out) {
     const std::shared_ptr<Ctx> ctx = in->ctx;
     const int n_small = std::min(in->N, out->N);
+    CoReq q;
+    Operands o(q, who, ctx, in->N);
+    o.in(in, level + 1, "in");
+    o.out(out, level + 1, "out", Operands::kCall, out->N);
+    TRY(o.check());
     std::vector<uint64_t> gapinv;
     if (kind == RS_FOLD_NTT) gapinv = fold_constants(large->moduli, level, log_gap);
-    CoReq q;
     q.op = CO_RING_SWITCH; q.obj = large ? (const void *)large.get() : (const void *)ctx.get();
     q.par[0] = kind; q.par[1] = level; q.par[2] = log_gap; q.par[3] = n_small;
-    q.ops = {in->view(), out->view()};
-    q.keep = {in, out};
     if (large) q.keep.push_back(large);
     q.run = [ctx, large, kind, level, log_gap, n_small, gapinv](const View *v, int B) -> int {
         return ring_switch_launch(*ctx, large.get(), kind, level, log_gap, n_small, gapinv, v, B);
@@ -4648,7 +4570,7 @@ int he_map_small_to_large_ntt(he_handle hsmall, he_handle hlarge, int level) {
     TRY(ring_switch_shape(*ps, *pl, level, &lg, "he_map_small_to_large_ntt"));
     if (ps->N > pl->N) return fail(HE_EINVAL, "he_map_small_to_large_ntt: polSmall (degree %d) is larger than polLarge (%d)", ps->N, pl->N);
     if (lg == 0) return he_poly_copy(hlarge, hsmall, level);
-    return ring_switch_file(nullptr, RS_REPLICATE_NTT, level, lg, ps, pl);
+    return ring_switch_file("he_map_small_to_large_ntt", nullptr, RS_REPLICATE_NTT, level, lg, ps, pl);
 }
 int he_switch_ring_degree_ntt(he_handle hring, int level, he_handle hin, he_handle hout) {
     GET(in, Poly, hin, T_POLY);
@@ -4664,8 +4586,8 @@ int he_switch_ring_degree_ntt(he_handle hring, int level, he_handle hin, he_hand
         if (level >= r->nmod()) return fail(HE_EINVAL, "he_switch_ring_degree_ntt: level %d out of range [0,%d]", level, r->nmod() - 1);
     }
     if (lg == 0) return he_poly_copy(hout, hin, level);
-    if (in->N > out->N) return ring_switch_file(r, RS_FOLD_NTT, level, lg, in, out);
-    return ring_switch_file(nullptr, RS_REPLICATE_NTT, level, lg, in, out);
+    if (in->N > out->N) return ring_switch_file("he_switch_ring_degree_ntt", r, RS_FOLD_NTT, level, lg, in, out);
+    return ring_switch_file("he_switch_ring_degree_ntt", nullptr, RS_REPLICATE_NTT, level, lg, in, out);
 }
 int he_switch_ring_degree(int level, he_handle hin, he_handle hout) {
     GET(in, Poly, hin, T_POLY);
@@ -4673,7 +4595,7 @@ int he_switch_ring_degree(int level, he_handle hin, he_handle hout) {
     int lg = 0;
     TRY(ring_switch_shape(*in, *out, level, &lg, "he_switch_ring_degree"));
     if (lg == 0) return he_poly_copy(hout, hin, level);
-    return ring_switch_file(nullptr, in->N > out->N ? RS_STRIDE_DOWN : RS_STRIDE_UP, level, lg, in, out);
+    return ring_switch_file("he_switch_ring_degree", nullptr, in->N > out->N ? RS_STRIDE_DOWN : RS_STRIDE_UP, level, lg, in, out);
 }
 
 // ApplyEvaluationKey (core/rlwe/evaluator_evaluationkey.go:36-106): out0 = in0 + GadgetProduct(in1)_0, out1 = GadgetProduct(in1)_1
@@ -4699,40 +4621,30 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
     // same degree: both sides are the evaluator's degree (the key switch runs at N over every operand)
     if (Nin == Nout && Nin != N) return fail(HE_EINVAL, "%s: ciphertext ring degree %d does not match evaluator params ring degree %d", who, Nin, N);
     const int form = Nin == Nout ? AEK_SAME : (Nin > Nout ? AEK_DOWN : AEK_UP);
-    const int B = in0->batch;
-    for (Poly *p : {in0.get(), in1.get(), out0.get(), out1.get()}) {
-        if (p->batch != B) return fail(HE_EINVAL, "%s: batch mismatch", who);
-        if (p->N == N) TRY(check_be_poly(*p, be, level + 1, who));
-    }
     int lg = 0;
-    if (form != AEK_SAME) {
-        TRY(ring_switch_shape(*in0, *out0, level, &lg, who));
-        TRY(ring_switch_shape(*in1, *out1, level, &lg, who));
-    }
-    // (handles of different degree never coincide; at equal degree any output may be any input, out0 != out1)
-    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {out0.get(), true, false}, {out1.get(), true, false}},
-                        {{2, 0}, {2, 1}, {3, 0}, {3, 1}}));
+    if (form != AEK_SAME) TRY(ring_switch_shape(*in0, *out0, level, &lg, who));
+    CoReq q;
+    Operands o(q, who, be);
+    const int i0 = o.in(in0, level + 1, "in0", Operands::kCall, Nin), i1 = o.in(in1, level + 1, "in1", Operands::kCall, Nin);
+    const int o0 = o.out(out0, level + 1, "out0", Operands::kCall, Nout), o1 = o.out(out1, level + 1, "out1", Operands::kCall, Nout);
+    o.all_inplace = true;  // (handles of different degree never coincide; at equal degree any output may be any input, out0 != out1)
+    TRY(o.check());
     // as in he_relinearize: an output that is the key switch's operand (in1) or the OTHER component's addend (in0 == out1) cannot be
     // batched; the crossed case stages the addend first (component 1's epilogue would overwrite it before component 0 reads it)
-    const bool alias = form == AEK_SAME && (in1->d == out0->d || in1->d == out1->d || in0->d == out1->d);
-    const bool cross = form == AEK_SAME && in0->d == out1->d;
+    const bool cross = o.same(i0, o1);
+    const bool alias = cross || o.same(i1, o0) || o.same(i1, o1);
     const int n_small = std::min(Nin, Nout);
     const std::vector<uint64_t> gapinv = form == AEK_DOWN ? fold_constants(be.Q->moduli, level, lg) : std::vector<uint64_t>();
-    CoReq q;
     q.op = CO_APPLY_EVK; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = form; q.par[2] = lg;
-    q.ops = {in0->view(), in1->view(), out0->view(), out1->view()};
-    q.keep = {ev, k, in0, in1, out0, out1};
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, level, form, lg, n_small, cross, gapinv](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
-        const int N = be.Q->N, levelP = k->nPk - 1;
-        const int beta = k->pw2 ? k->prefix[level + 1] : base_rns_size(level, levelP);
+        const int N = be.Q->N;
         const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        be.ctx->acct(4.0 * (level + 1), key_limbs(*k, level), B, N);  // the key switch: 2 L in, 2 L out, key
-        { Valu V(be.Q->logN); valu_gadget_product(V, be, level, levelP, beta, true); V.into(*be.ctx, B); }
-        const size_t ks = ks_scratch_words(be, level, levelP, B, true, k.get());
+        // the key switch: 2 L in, 2 L out, key; its scratch and the staged addend / both components at degree N
+        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, form == AEK_SAME ? (cross ? wQ + 2 : 0) : 2 * wQ + 2));
         hipStream_t st = be.ctx->stream;
         if (form == AEK_SAME) {
-            TRY(be.ctx->arena_reserve(ks + (cross ? wQ + 2 : 0)));
             if (cross) {  // (served one by one: plain views)
                 View a0{be.ctx->arena_take(wQ), sQ};
                 HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, st));
@@ -4741,7 +4653,6 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
             return gadget_product_core(*ev, level, &v[1], nullptr, *k, v[2], v[3], B, &v[0], nullptr);
         }
         // both components at degree N in scratch, [2][B] entries: the key switch's result (down) or the replicated input (up)
-        TRY(be.ctx->arena_reserve(ks + 2 * wQ + 2));
         uint64_t *t = be.ctx->arena_take(2 * wQ);
         const View t0{t, sQ}, t1{t + wQ, sQ};
         RingSwitchIO io;
@@ -4763,7 +4674,7 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
         *ok = false;
         return (form != AEK_SAME || alias) ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
     };
-    return co_dispatch(*be.ctx, B, q);
+    return co_dispatch(*be.ctx, o.B, q);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4782,14 +4693,6 @@ static int rp_entries(long entries, const char *who) {
         return fail(HE_EINVAL, "%s: %ld entries in one call, at most %d (split the batch)", who, entries, kRpMaxEntries);
     return HE_OK;
 }
-// a polynomial of `ctx`, of degree N and batch B, with limbs 0..level
-static int rp_poly(const Poly &p, const std::shared_ptr<Ctx> &ctx, int N, int B, int level, const char *who, const char *what) {
-    if (p.ctx != ctx) return fail(HE_EINVAL, "%s: %s belongs to another context", who, what);
-    if (p.N != N) return fail(HE_EINVAL, "%s: %s has degree %d, %d expected", who, what, p.N, N);
-    if (p.batch != B) return fail(HE_EINVAL, "%s: batch mismatch (%s has %d entries, %d expected)", who, what, p.batch, B);
-    if (p.nlimbs < level + 1) return fail(HE_EINVAL, "%s: %s has %d limbs, level %d needs %d", who, what, p.nlimbs, level, level + 1);
-    return HE_OK;
-}
 int he_ring_xpow2_ntt(he_handle hring, int level, int i, int div, he_handle hout) {
     static const char *who = "he_ring_xpow2_ntt";
     GET(r, Ring, hring, T_RING);
@@ -4797,13 +4700,14 @@ int he_ring_xpow2_ntt(he_handle hring, int level, int i, int div, he_handle hout
     TRY(rp_ring(*r, level, who));
     if (r->N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r->N);
     if (i < 0 || i >= r->logN) return fail(HE_EINVAL, "%s: i = %d out of range [0,%d]", who, i, r->logN - 1);
-    TRY(rp_poly(*out, r->ctx, r->N, out->batch, level, who, "out"));
     TRY(rp_entries(out->batch, who));
     const std::shared_ptr<Ctx> ctx = r->ctx;
     CoReq q;
+    Operands o(q, who, *r);
+    o.out(out, level + 1, "out");
+    TRY(o.check());
     q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_XPOW2; q.par[1] = level; q.par[2] = i; q.par[3] = div != 0;
-    q.ops = {out->view()};
-    q.keep = {r, out};
+    q.keep.push_back(r);
     q.run = [ctx, r, level, i, div](const View *v, int B) -> int {
         ctx->acct(level + 1, 0, B, r->N);
         HIP_TRY(launch_xpow2_fill(r->dev, v[0], i, div != 0, level + 1, B, ctx->stream));
@@ -4829,28 +4733,20 @@ int he_ring_split_ntt(he_handle hring, int level, he_handle hin, he_handle heven
     static const char *who = "he_ring_split_ntt";
     GET(r, Ring, hring, T_RING);
     GET(in, Poly, hin, T_POLY);
-    GET(even, Poly, heven, T_POLY);
-    std::shared_ptr<Poly> odd;
-    if (hodd) {
-        odd = get<Poly>(hodd, T_POLY);
-        if (!odd) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", who, (unsigned long long)hodd);
-    }
     TRY(rp_ring(*r, level, who));
-    if (in->N != r->N) return fail(HE_EINVAL, "%s: in has degree %d, the ring's degree %d expected", who, in->N, r->N);
     if (r->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, r->N / 2);
     const int B = in->batch;
     TRY(rp_entries(B, who));
-    TRY(rp_poly(*in, r->ctx, r->N, B, level, who, "in"));
-    TRY(rp_poly(*even, r->ctx, r->N / 2, B, level, who, "outEven"));
-    if (odd) TRY(rp_poly(*odd, r->ctx, r->N / 2, B, level, who, "outOdd"));
-    TRY(reject_aliasing(who, {{in.get(), false, false}, {even.get(), true, false}, {odd.get(), true, false}}));
-    const std::shared_ptr<Ctx> ctx = r->ctx;
-    const bool has_odd = (bool)odd;
     CoReq q;
+    Operands o(q, who, *r);
+    o.in(in, level + 1, "in");
+    o.out(heven, level + 1, "outEven", B, r->N / 2);
+    o.out(o.opt(hodd), level + 1, "outOdd", B, r->N / 2);
+    TRY(o.check());
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    const bool has_odd = hodd != 0;
     q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_SPLIT; q.par[1] = level; q.par[2] = has_odd;
-    q.ops = {in->view(), even->view(), odd ? odd->view() : View{nullptr, 0}};
-    q.keep = {r, in, even};
-    if (odd) q.keep.push_back(odd);
+    q.keep.push_back(r);
     q.run = [ctx, r, level, has_odd](const View *v, int B) -> int {
         RingPackIO io;
         io.x[0] = v[0]; io.o[0] = v[1]; io.p[0] = v[2];
@@ -4862,28 +4758,21 @@ int he_ring_split_ntt(he_handle hring, int level, he_handle hin, he_handle heven
 int he_ring_merge_ntt(he_handle hring, int level, he_handle heven, he_handle hodd, he_handle hout) {
     static const char *who = "he_ring_merge_ntt";
     GET(r, Ring, hring, T_RING);
-    GET(even, Poly, heven, T_POLY);
     GET(out, Poly, hout, T_POLY);
-    std::shared_ptr<Poly> odd;
-    if (hodd) {
-        odd = get<Poly>(hodd, T_POLY);
-        if (!odd) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", who, (unsigned long long)hodd);
-    }
     TRY(rp_ring(*r, level, who));
-    if (out->N != r->N) return fail(HE_EINVAL, "%s: out has degree %d, the ring's degree %d expected", who, out->N, r->N);
     if (r->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, r->N / 2);
     const int B = out->batch;
     TRY(rp_entries(B, who));
-    TRY(rp_poly(*out, r->ctx, r->N, B, level, who, "out"));
-    TRY(rp_poly(*even, r->ctx, r->N / 2, B, level, who, "inEven"));
-    if (odd) TRY(rp_poly(*odd, r->ctx, r->N / 2, B, level, who, "inOdd"));
-    const std::shared_ptr<Ctx> ctx = r->ctx;
-    const bool has_odd = (bool)odd;
     CoReq q;
+    Operands o(q, who, *r, B);
+    o.in(heven, level + 1, "inEven", B, r->N / 2);
+    o.in(o.opt(hodd), level + 1, "inOdd", B, r->N / 2);
+    o.out(out, level + 1, "out");
+    TRY(o.check());
+    const std::shared_ptr<Ctx> ctx = r->ctx;
+    const bool has_odd = hodd != 0;
     q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_MERGE; q.par[1] = level; q.par[2] = has_odd;
-    q.ops = {even->view(), odd ? odd->view() : View{nullptr, 0}, out->view()};
-    q.keep = {r, even, out};
-    if (odd) q.keep.push_back(odd);
+    q.keep.push_back(r);
     q.run = [ctx, r, level, has_odd](const View *v, int B) -> int {
         RingPackIO io;
         io.x[0] = v[0]; io.y[0] = v[1]; io.o[0] = v[2];
@@ -4892,64 +4781,46 @@ int he_ring_merge_ntt(he_handle hring, int level, he_handle heven, he_handle hod
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
     return co_dispatch(*ctx, B, q);
 }
-// the shared checks of he_ringpack_split / he_ringpack_merge: L = the two components at the evaluator's degree N, e / o the halves
-static int rp_ct_checks(const Evaluator &ev, const Evk &k, int &level, Poly *const L[2], Poly *const e[2], Poly *const o[2], const char *who,
-                        const char *large_name) {
+// the shared checks of he_ringpack_split / he_ringpack_merge on the evaluator, the key and the odd halves' handles; B entries per operand
+static int rp_ct_checks(const Evaluator &ev, const Evk &k, int &level, int B, he_handle ho0, he_handle ho1, const char *who) {
     const BasisExtender &be = *ev.be;
     if (be.type != 0) return fail(HE_EINVAL, "%s: method is only supported for ring.Type = ring.Standard", who);
     const int asked = level;
     TRY(check_key(ev, k, level, who));
     if (level != asked) return fail(HE_EINVAL, "%s: the key has %d Q limbs, level %d needs %d", who, k.nQk, asked, asked + 1);
     if (level >= be.LQ || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, be.LQ - 1);
-    const int N = be.Q->N, B = L[0]->batch;
     TRY(rp_entries(2L * B, who));
-    if (L[0]->N != N || L[1]->N != N) return fail(HE_EINVAL, "%s: %s ring degree does not match evaluator params ring degree %d", who, large_name, N);
-    if (N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, N / 2);
-    if ((o[0] == nullptr) != (o[1] == nullptr)) return fail(HE_EINVAL, "%s: odd0 and odd1 are both given or both 0", who);
-    for (int c = 0; c < 2; c++) {
-        TRY(rp_poly(*L[c], be.ctx, N, B, level, who, large_name));
-        TRY(check_be_poly(*L[c], be, level + 1, who));
-        TRY(rp_poly(*e[c], be.ctx, N / 2, B, level, who, "even"));
-        if (o[c]) TRY(rp_poly(*o[c], be.ctx, N / 2, B, level, who, "odd"));
-    }
+    if (be.Q->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, be.Q->N / 2);
+    if ((ho0 == 0) != (ho1 == 0)) return fail(HE_EINVAL, "%s: odd0 and odd1 are both given or both 0", who);
     return HE_OK;
 }
-#define RP_GET_OPT(var, h)                                                                                 \
-    std::shared_ptr<Poly> var;                                                                             \
-    if (h) {                                                                                               \
-        var = get<Poly>(h, T_POLY);                                                                        \
-        if (!var) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", __func__, (unsigned long long)(h));  \
-    }
 int he_ringpack_split(he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hk, he_handle he0, he_handle he1, he_handle ho0,
                       he_handle ho1) {
     static const char *who = "he_ringpack_split";
     GET(ev, Evaluator, hev, T_EVAL);
     GET(in0, Poly, hin0, T_POLY);
-    GET(in1, Poly, hin1, T_POLY);
     GET(k, Evk, hk, T_EVK);
-    GET(e0, Poly, he0, T_POLY);
-    GET(e1, Poly, he1, T_POLY);
-    RP_GET_OPT(o0, ho0);
-    RP_GET_OPT(o1, ho1);
-    Poly *const L[2] = {in0.get(), in1.get()}, *const E[2] = {e0.get(), e1.get()}, *const O[2] = {o0.get(), o1.get()};
-    TRY(rp_ct_checks(*ev, *k, level, L, E, O, who, "ctN"));
-    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {e0.get(), true, false}, {e1.get(), true, false},
-                              {o0.get(), true, false}, {o1.get(), true, false}}));
-    const bool has_odd = (bool)o0;
+    const int B = in0->batch;
+    TRY(rp_ct_checks(*ev, *k, level, B, ho0, ho1, who));
     BasisExtender &be = *ev->be;
+    const int n = be.Q->N / 2;
     CoReq q;
+    Operands o(q, who, be);
+    o.in(in0, level + 1, "ctN[0]");
+    o.in(hin1, level + 1, "ctN[1]");
+    o.out(he0, level + 1, "even0", B, n);
+    o.out(he1, level + 1, "even1", B, n);
+    o.out(o.opt(ho0), level + 1, "odd0", B, n);
+    o.out(o.opt(ho1), level + 1, "odd1", B, n);
+    TRY(o.check());
+    const bool has_odd = ho0 != 0;
     q.op = CO_RINGPACK_CT; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = 0; q.par[2] = has_odd;
-    q.ops = {in0->view(), in1->view(), e0->view(), e1->view(), o0 ? o0->view() : View{nullptr, 0}, o1 ? o1->view() : View{nullptr, 0}};
-    q.keep = {ev, k, in0, in1, e0, e1};
-    if (o0) { q.keep.push_back(o0); q.keep.push_back(o1); }
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
-        const int N = be.Q->N, levelP = k->nPk - 1;
-        const int beta = k->pw2 ? k->prefix[level + 1] : base_rns_size(level, levelP);
+        const int N = be.Q->N;
         const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        be.ctx->acct(4.0 * (level + 1), key_limbs(*k, level), B, N);  // the key switch: 2 L in, 2 L out, key
-        { Valu V(be.Q->logN); valu_gadget_product(V, be, level, levelP, beta, true); V.into(*be.ctx, B); }
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, levelP, B, true, k.get()) + 2 * wQ + 2));
+        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));  // the key switch: 2 L in, 2 L out, key
         uint64_t *t = be.ctx->arena_take(2 * wQ);
         const View t0{t, sQ}, t1{t + wQ, sQ};
         TRY(gadget_product_core(*ev, level, &v[1], nullptr, *k, t0, t1, B, &v[0], nullptr));
@@ -4959,38 +4830,35 @@ int he_ringpack_split(he_handle hev, int level, he_handle hin0, he_handle hin1, 
         return rp_split_launch(*be.ctx, *be.Q, io, has_odd, level, B, 2);
     };
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*be.ctx, in0->batch, q);
+    return co_dispatch(*be.ctx, B, q);
 }
 int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he_handle ho0, he_handle ho1, he_handle hk, he_handle hout0,
                       he_handle hout1) {
     static const char *who = "he_ringpack_merge";
     GET(ev, Evaluator, hev, T_EVAL);
-    GET(e0, Poly, he0, T_POLY);
-    GET(e1, Poly, he1, T_POLY);
-    RP_GET_OPT(o0, ho0);
-    RP_GET_OPT(o1, ho1);
     GET(k, Evk, hk, T_EVK);
     GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
-    Poly *const L[2] = {out0.get(), out1.get()}, *const E[2] = {e0.get(), e1.get()}, *const O[2] = {o0.get(), o1.get()};
-    TRY(rp_ct_checks(*ev, *k, level, L, E, O, who, "ctN"));
-    TRY(reject_aliasing(who, {{e0.get(), false, false}, {e1.get(), false, false}, {o0.get(), false, false}, {o1.get(), false, false},
-                              {out0.get(), true, false}, {out1.get(), true, false}}));
-    const bool has_odd = (bool)o0;
+    const int B = out0->batch;
+    TRY(rp_ct_checks(*ev, *k, level, B, ho0, ho1, who));
     BasisExtender &be = *ev->be;
+    const int n = be.Q->N / 2;
     CoReq q;
+    Operands o(q, who, be, B);
+    o.in(he0, level + 1, "even0", B, n);
+    o.in(he1, level + 1, "even1", B, n);
+    o.in(o.opt(ho0), level + 1, "odd0", B, n);
+    o.in(o.opt(ho1), level + 1, "odd1", B, n);
+    o.out(out0, level + 1, "ctN[0]");
+    o.out(hout1, level + 1, "ctN[1]");
+    TRY(o.check());
+    const bool has_odd = ho0 != 0;
     q.op = CO_RINGPACK_CT; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = 1; q.par[2] = has_odd;
-    q.ops = {e0->view(), e1->view(), o0 ? o0->view() : View{nullptr, 0}, o1 ? o1->view() : View{nullptr, 0}, out0->view(), out1->view()};
-    q.keep = {ev, k, e0, e1, out0, out1};
-    if (o0) { q.keep.push_back(o0); q.keep.push_back(o1); }
+    q.keep.push_back(ev); q.keep.push_back(k);
     q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
-        const int N = be.Q->N, levelP = k->nPk - 1;
-        const int beta = k->pw2 ? k->prefix[level + 1] : base_rns_size(level, levelP);
+        const int N = be.Q->N;
         const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        be.ctx->acct(4.0 * (level + 1), key_limbs(*k, level), B, N);  // the key switch: 2 L in, 2 L out, key
-        { Valu V(be.Q->logN); valu_gadget_product(V, be, level, levelP, beta, true); V.into(*be.ctx, B); }
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, levelP, B, true, k.get()) + 2 * wQ + 2));
+        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));  // the key switch: 2 L in, 2 L out, key
         uint64_t *t = be.ctx->arena_take(2 * wQ);
         const View t0{t, sQ}, t1{t + wQ, sQ};
         RingPackIO io;
@@ -5000,39 +4868,30 @@ int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he
         return gadget_product_core(*ev, level, &t1, nullptr, *k, v[4], v[5], B, &t0, nullptr);
     };
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*be.ctx, out0->batch, q);
+    return co_dispatch(*be.ctx, B, q);
 }
 int he_ringpack_expand_step(he_handle hring, int level, int k, int sum_only, he_handle hin0, he_handle hin1, he_handle htmp0, he_handle htmp1,
                             he_handle hout0, he_handle hout1) {
     static const char *who = "he_ringpack_expand_step";
     GET(r, Ring, hring, T_RING);
     GET(in0, Poly, hin0, T_POLY);
-    GET(in1, Poly, hin1, T_POLY);
-    GET(tmp0, Poly, htmp0, T_POLY);
-    GET(tmp1, Poly, htmp1, T_POLY);
-    GET(out0, Poly, hout0, T_POLY);
-    GET(out1, Poly, hout1, T_POLY);
     TRY(rp_ring(*r, level, who));
     if (r->N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r->N);
     if (k < 0 || k >= r->logN) return fail(HE_EINVAL, "%s: k = %d out of range [0,%d]", who, k, r->logN - 1);
     const int m = in0->batch;
     TRY(rp_entries(2L * m, who));
-    TRY(rp_poly(*in0, r->ctx, r->N, m, level, who, "in0"));
-    TRY(rp_poly(*in1, r->ctx, r->N, m, level, who, "in1"));
-    TRY(rp_poly(*tmp0, r->ctx, r->N, m, level, who, "tmp0"));
-    TRY(rp_poly(*tmp1, r->ctx, r->N, m, level, who, "tmp1"));
-    TRY(rp_poly(*out0, r->ctx, r->N, sum_only ? m : 2 * m, level, who, "out0"));
-    TRY(rp_poly(*out1, r->ctx, r->N, sum_only ? m : 2 * m, level, who, "out1"));
-    std::vector<std::pair<int, int>> allowed;
-    if (sum_only) allowed = {{4, 0}, {5, 1}};
-    TRY(reject_aliasing(who, {{in0.get(), false, false}, {in1.get(), false, false}, {tmp0.get(), false, false}, {tmp1.get(), false, false},
-                              {out0.get(), true, false}, {out1.get(), true, false}}, allowed));
-    const std::shared_ptr<Ctx> ctx = r->ctx;
     const bool so = sum_only != 0;
     CoReq q;
+    Operands o(q, who, *r);
+    const int i0 = o.in(in0, level + 1, "in0"), i1 = o.in(hin1, level + 1, "in1");
+    o.in(htmp0, level + 1, "tmp0");
+    o.in(htmp1, level + 1, "tmp1");
+    const int o0 = o.out(hout0, level + 1, "out0", so ? m : 2 * m), o1 = o.out(hout1, level + 1, "out1", so ? m : 2 * m);
+    if (so) { o.inplace(o0, i0); o.inplace(o1, i1); }
+    TRY(o.check());
+    const std::shared_ptr<Ctx> ctx = r->ctx;
     q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_EXPAND; q.par[1] = level; q.par[2] = k; q.par[3] = so;
-    q.ops = {in0->view(), in1->view(), tmp0->view(), tmp1->view(), out0->view(), out1->view()};
-    q.keep = {r, in0, in1, tmp0, tmp1, out0, out1};
+    q.keep.push_back(r);
     q.run = [ctx, r, level, k, so](const View *v, int B) -> int {
         RingPackIO io;
         io.zsplit = B;
@@ -5055,11 +4914,12 @@ static int rp_pack_operands(const char *who, const Ring &r, int level, int count
     if (count < 1) return fail(HE_EINVAL, "%s: count = %d, at least one pair is needed", who, count);
     TRY(rp_entries(2L * count, who));
     if (!a0 || !a1 || !b0 || !b1) return fail(HE_EINVAL, "%s: null handle array", who);
-    std::shared_ptr<Poly> t[2] = {get<Poly>(ht0, T_POLY), get<Poly>(ht1, T_POLY)};
-    if (!t[0] || !t[1]) return fail(HE_EHANDLE, "%s: bad Poly handle (t0 / t1)", who);
-    TRY(rp_poly(*t[0], r.ctx, r.N, count, level, who, "t0"));
-    TRY(rp_poly(*t[1], r.ctx, r.N, count, level, who, "t1"));
+    // No handle may occur twice among the operands, whatever the step does with each: this call's own identity rule, held with a
+    // set (a step takes thousands of pairs; the pairwise rule of reject_aliasing is for the handful of operands of other calls),
+    // so the operands are declared as read.
+    Operands o(q, who, r);
     std::unordered_set<const uint64_t *> seen;
+    auto once = [&](int i) { return !o.ops[i].p || seen.insert(o.ops[i].p->d).second; };
     kinds[0] = kinds[1] = kinds[2] = 0;
     const he_handle *hs[4] = {a0, a1, b0, b1};
     for (int z = 0; z < count; z++) {
@@ -5067,22 +4927,12 @@ static int rp_pack_operands(const char *who, const Ring &r, int level, int count
             return fail(HE_EINVAL, "%s: pair %d: the two components of a ciphertext are both given or both 0", who, z);
         if (!a0[z] && !b0[z]) return fail(HE_EINVAL, "%s: pair %d is empty", who, z);
         kinds[a0[z] && b0[z] ? 0 : (a0[z] ? 1 : 2)]++;
-        for (int s = 0; s < 4; s++) {
-            if (!hs[s][z]) { q.ops.push_back(View{nullptr, 0}); continue; }
-            std::shared_ptr<Poly> p = get<Poly>(hs[s][z], T_POLY);
-            if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle %llu (pair %d)", who, (unsigned long long)hs[s][z], z);
-            TRY(rp_poly(*p, r.ctx, r.N, 1, level, who, "a / b"));
-            if (!seen.insert(p->d).second) return fail(HE_EINVAL, "%s: a handle occurs twice among the operands (pair %d)", who, z);
-            q.ops.push_back(p->view());
-            q.keep.push_back(p);
-        }
+        for (int s = 0; s < 4; s++)
+            if (!once(o.in(o.opt(hs[s][z]), level + 1, "a / b", 1))) return fail(HE_EINVAL, "%s: a handle occurs twice among the operands (pair %d)", who, z);
     }
-    for (int c = 0; c < 2; c++) {
-        if (!seen.insert(t[c]->d).second) return fail(HE_EINVAL, "%s: a handle occurs twice among the operands (t%d)", who, c);
-        q.ops.push_back(t[c]->view());
-        q.keep.push_back(t[c]);
-    }
-    return HE_OK;
+    for (he_handle ht : {ht0, ht1})
+        if (!once(o.in(ht, level + 1, "t0 / t1", count))) return fail(HE_EINVAL, "%s: a handle occurs twice among the operands (t0 / t1)", who);
+    return o.check();
 }
 static int rp_pack_step(const char *who, he_handle hring, int level, int k, bool post, int count, const he_handle *a0, const he_handle *a1,
                         const he_handle *b0, const he_handle *b1, he_handle ht0, he_handle ht1) {
