@@ -26,6 +26,7 @@
 #include "hering.h"
 #include "hering_ringswitch.h"
 #include "hering_ringpack.h"
+#include "hering_rgsw.h"
 
 namespace hering {
 
@@ -708,6 +709,32 @@ public:
         return ctN;
     }
 };
+
+// ---- RGSW (core/rgsw; hering_rgsw.h), NTT domain -----------------------------------------------------------------------------
+namespace rgsw {
+// rgsw.Ciphertext (core/rgsw/elements.go:12): Value [2]rlwe.GadgetCiphertext, two device keys of one evaluator and one shape
+struct Ciphertext {
+    std::array<EvaluationKey, 2> Value;
+    int LevelQ() const { return Value[0].LevelQ(); }
+    int LevelP() const { return Value[0].LevelP(); }
+};
+// rgsw.Evaluator (core/rgsw/evaluator.go:14): an rlwe.Evaluator with the external product
+class Evaluator : public hering::Evaluator {
+public:
+    using hering::Evaluator::Evaluator;
+    explicit Evaluator(const hering::Evaluator &ev) : hering::Evaluator(ev) {}
+    // ExternalProduct (:39): opOut = (<op0, op1[0]>, <op0, op1[1]>) at the levels of op1; opOut may be op0
+    void ExternalProduct(const hering::Ciphertext &op0, const Ciphertext &op1, hering::Ciphertext &opOut) const {
+        check(he_rgsw_external_product(h(), op0.Value.at(0).h(), op0.Value.at(1).h(), op1.Value[0].h(), op1.Value[1].h(),
+                                       opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+    }
+    // batch entry b of op0 times key sel[b] of a resident key table (he_rgsw_keyset_create); sel[b] == -1 passes the entry through
+    void ExternalProductSelect(const hering::Ciphertext &op0, he_handle keySet, const std::vector<int32_t> &sel, hering::Ciphertext &opOut) const {
+        check(he_rgsw_external_product_select(h(), op0.Value.at(0).h(), op0.Value.at(1).h(), keySet, sel.data(), (int)sel.size(),
+                                              opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+    }
+};
+}  // namespace rgsw
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

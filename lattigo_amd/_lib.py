@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HERING_LIB: A/B-test another build
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
-         os.path.join(_INC, "hering_ringpack.h")]
+         os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -117,6 +117,9 @@ def _declare(L):
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
         "he_ringpack_pack_pre": [H, i, i, i, HP, HP, HP, HP, H, H], "he_ringpack_pack_post": [H, i, i, HP, HP, HP, HP, H, H],
+        "he_rgsw_external_product": [H, H, H, H, H, H, H], "he_rgsw_keyset_create": [H, i, HP, HP, HP], "he_rgsw_keyset_destroy": [H],
+        "he_rgsw_external_product_select": [H, H, H, H, C.POINTER(C.c_int32), i, H, H],
+        "he_rgsw_key_op": [i, H, H, H, H], "he_rgsw_key_add_plaintext_lazy": [H, H, H],
         "he_automorphism_ct": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted_lazy": [H, i, H, H, C.c_uint64, H, H, H, H, H],
@@ -190,6 +193,9 @@ _TRACE_FNS = {
     "he_ringpack_split": (58, "hihhhhhhh"), "he_ringpack_merge": (59, "hihhhhhhh"), "he_ringpack_expand_step": (60, "hiiihhhhhh"),
     "he_ringpack_pack_pre": (61, "hiiiHHHHhh"), "he_ringpack_pack_post": (62, "hiiHHHHhh"),
 }
+# the product entries of include/hering_rgsw.h, numbered on from the table above (a table of their own: the numbering of each
+# earlier header is pinned by that header's tests)
+_TRACE_FNS_RGSW = {"he_rgsw_external_product": (63, "hhhhhhh"), "he_rgsw_external_product_select": (64, "hhhhAihh")}
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments)
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
               ("he_mul_scalar_bigint", 3): (4, 0), ("he_mul_scalar_bigint_then_add", 3): (4, 0), ("he_double_rns_scalarop", 4): (1, 1),
@@ -197,6 +203,7 @@ _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigin
 _TRACE_LEN.update({("he_lintrans_mul_sum", k): (3, 0) for k in range(4, 11)})
 _TRACE_LEN.update({("he_ringpack_pack_pre", k): (3, 0) for k in range(4, 8)})
 _TRACE_LEN.update({("he_ringpack_pack_post", k): (2, 0) for k in range(3, 7)})
+_TRACE_LEN[("he_rgsw_external_product_select", 4)] = (5, 0)
 # calls a replay has no use for: they read, wait or account, and do not change what the replayed calls see
 _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start", "he_timer_stop", "he_poly_download", "he_poly_shape",
                  "he_poly_download_limb", "he_prof_begin", "he_prof_end", "he_prof_end_bytes", "he_ctx_coalescing_stats",
@@ -224,7 +231,7 @@ def trace_begin():
     import inspect  # noqa: F401
 
     def wrap(name, fn):
-        spec = _TRACE_FNS.get(name)
+        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name)
 
         def call(*a):
             rc = fn(*a)

@@ -40,6 +40,7 @@
 #include "../../include/hering_debug.h"
 #include "../../include/hering_ringswitch.h"
 #include "../../include/hering_ringpack.h"
+#include "../../include/hering_rgsw.h"
 #include "host_math.h"
 #include "kernels.h"
 
@@ -68,7 +69,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET };
 
 struct Obj {
     ObjType type;
@@ -96,7 +97,7 @@ enum CoOp {
     CO_NTT, CO_EW, CO_EW_DOUBLE, CO_SHIFT, CO_RESCALE, CO_GATHER, CO_AUTO_COEFF, CO_MODUP, CO_MODDOWN_BE,
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
-    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT
+    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -661,6 +662,8 @@ struct Evk : Obj {
                                  // each row of 4096 / 8192 coefficients permuted for that kernel (launch_key_to_f64)
     uint64_t *d = nullptr;
     Evk() : Obj(T_EVK) {}
+    // the key as a batch of 2 beta rows (digit d, component c at 2 d + c) of nQk + nPk limbs
+    View rows() const { return View{d, (size_t)(nQk + nPk) * ev->be->Q->N}; }
     ~Evk() override {
         hipSetDevice(ev->be->ctx->dev);
         hipStreamSynchronize(ev->be->ctx->stream);
@@ -3429,6 +3432,44 @@ int ks_mac_f64(Evaluator &ev, int levelQ, int levelP, const uint64_t *dec, size_
     return HE_OK;
 }
 
+// windows of source limb i of a bit-window accumulation: the key's, or one per limb (BaseTwoDecomposition == 0 in core/rgsw)
+int rgsw_nj(const Evk &k, int i) { return k.pw2 ? k.nj[i] : 1; }
+// Bit-window accumulation of one polynomial against a key: windows (INTT(cx)[i] >> j pw2) & mask of every Q limb, NTT'd into every
+// limb, multiplied into the accumulators (core/rlwe/evaluator_gadget_product.go:203-338; core/rgsw/evaluator.go:139-203 for one
+// el).  pw2 == 0 is core/rgsw's all-ones mask, one uncentred window per limb (:147-149).  reduce_wide: windows that can reach the
+// modulus they are transformed in are reduced first (core/rgsw's shapes; rlwe's base-2 keys never have them).
+int window_products_core(Evaluator &ev, int levelQ, View cx, int B, const Evk &k, bool reduce_wide, View o0Q, View o0P, View o1Q, View o1P) {
+    BasisExtender &be = *ev.be;
+    const int levelP = k.nPk - 1, N = be.Q->N;
+    int beta = 0;
+    for (int i = 0; i <= levelQ; i++) beta += rgsw_nj(k, i);
+    const size_t wq = (size_t)B * (levelQ + 1) * N, ds = (size_t)(be.LQ + be.LP) * N, bs = (size_t)beta * ds;
+    View inv{be.ctx->arena_take(wq), (size_t)(levelQ + 1) * N};
+    uint64_t *dec = be.ctx->arena_take((size_t)B * bs);
+    hipStream_t st = be.ctx->stream;
+    HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), cx, inv, B, true, NTT_REDUCE_INPUT));
+    MaskSpreadArgs m{};
+    m.mask = k.pw2 ? ((uint64_t)1 << k.pw2) - 1 : ~(uint64_t)0;
+    LimbTab t;
+    t.n = 0;
+    bool reduce = false;
+    for (int j = 0; j <= levelQ; j++) { t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)j; m.dst_limb[t.n] = (uint8_t)j; t.n++; }
+    for (int j = 0; j <= levelP; j++) { t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)(be.LQ + j); m.dst_limb[t.n] = (uint8_t)(be.LQ + j); t.n++; }
+    for (int j = 0; reduce_wide && j < t.n; j++) reduce = reduce || m.mask >= be.modulus(t.mod[j]);
+    m.ndst = t.n;
+    for (int i = 0; i <= levelQ; i++)
+        for (int j = 0; j < rgsw_nj(k, i); j++) {
+            m.blk_limb[m.nblk] = (uint8_t)i;
+            m.blk_shift[m.nblk] = (uint8_t)(j * k.pw2);  // < bits(q_i) <= 62
+            m.nblk++;
+        }
+    HIP_TRY(launch_mask_spread(be.qp, m, inv, dec, bs, ds, B, st));
+    for (int d = 0; d < beta; d++) {
+        View blk{dec + (size_t)d * ds, bs};
+        HIP_TRY(be_ntt(be, t, blk, blk, B, false, reduce ? NTT_REDUCE_INPUT : 0));
+    }
+    return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B);
+}
 // GadgetProductLazy core: cx (NTT) -> accumulators (views).  Scratch from the arena.
 // cx_canonical: cx was produced by this library and is known to be in [0, q) (skips the input reduction of the first pass)
 // acc_q_f64 (in/out): on entry, whether the caller can take the Q-limb accumulators of the moduli below 2^47 as doubles; on
@@ -3460,9 +3501,6 @@ int gadget_product_lazy_core(Evaluator &ev, int levelQ, View cx, int B, const Ev
     const int levelP = k.nPk - 1, N = be.Q->N;
     const int beta = key_beta(k, levelQ);
     const size_t wq = (size_t)B * (levelQ + 1) * N, ds = (size_t)(be.LQ + be.LP) * N, bs = (size_t)beta * ds;
-    uint64_t *cxinv = be.ctx->arena_take(wq);
-    uint64_t *dec = be.ctx->arena_take((size_t)B * bs);
-    View inv{cxinv, (size_t)(levelQ + 1) * N};
     const FusedPlan *plan = nullptr;
     if (!k.pw2) TRY(get_dec_plan(ev, levelQ, levelP, levelP + 1, &plan));
     const bool make_c2 = tin && tin->make_c2;
@@ -3485,28 +3523,11 @@ int gadget_product_lazy_core(Evaluator &ev, int levelQ, View cx, int B, const Ev
     }
     if (k.pw2) {  // base-2 gadget: bit windows of every Q-limb, NTT'd into every limb (evaluator_gadget_product.go:203-338)
         if (giant) return fail(HE_EINVAL, "gadget product: giant-step stores with a base-2 gadget");
-        hipStream_t st = be.ctx->stream;
-        HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), cx, inv, B, true, NTT_REDUCE_INPUT));
-        MaskSpreadArgs m{};
-        m.mask = ((uint64_t)1 << k.pw2) - 1;
-        LimbTab t;
-        t.n = 0;
-        for (int j = 0; j <= levelQ; j++) { t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)j; m.dst_limb[t.n] = (uint8_t)j; t.n++; }
-        for (int j = 0; j <= levelP; j++) { t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)(be.LQ + j); m.dst_limb[t.n] = (uint8_t)(be.LQ + j); t.n++; }
-        m.ndst = t.n;
-        for (int i = 0; i <= levelQ; i++)
-            for (int j = 0; j < k.nj[i]; j++) {
-                m.blk_limb[m.nblk] = (uint8_t)i;
-                m.blk_shift[m.nblk] = (uint8_t)(j * k.pw2);  // < bits(q_i) <= 62
-                m.nblk++;
-            }
-        HIP_TRY(launch_mask_spread(be.qp, m, inv, dec, bs, ds, B, st));
-        for (int d = 0; d < beta; d++) {
-            View blk{dec + (size_t)d * ds, bs};
-            HIP_TRY(be_ntt(be, t, blk, blk, B, false, 0));
-        }
-        return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B);
+        return window_products_core(ev, levelQ, cx, B, k, false, o0Q, o0P, o1Q, o1P);
     }
+    uint64_t *cxinv = be.ctx->arena_take(wq);
+    uint64_t *dec = be.ctx->arena_take((size_t)B * bs);
+    View inv{cxinv, (size_t)(levelQ + 1) * N};
     if (plan->ok) {
         if (prod_in) {
             NttProdIn pin;
@@ -4972,6 +4993,351 @@ int he_ringpack_pack_pre(he_handle ring, int level, int k, int count, const he_h
 int he_ringpack_pack_post(he_handle ring, int level, int count, const he_handle *a0, const he_handle *a1, const he_handle *b0,
                           const he_handle *b1, he_handle t0, he_handle t1) {
     return rp_pack_step("he_ringpack_pack_post", ring, level, 0, true, count, a0, a1, b0, b1, t0, t1);
+}
+
+// ---------------------------------------------------------------------------------------
+// RGSW external product (include/hering_rgsw.h; core/rgsw/evaluator.go)
+// ---------------------------------------------------------------------------------------
+namespace {
+// BlindRotationEvaluationKeySet's keys: RGSW ciphertexts of one shape, each two key handles
+struct RgswSet : Obj {
+    std::shared_ptr<Evaluator> ev;
+    std::vector<std::shared_ptr<Evk>> k0, k1;
+    size_t *d_tab = nullptr;  // [2][n] device addresses of the keys' words (rgsw0 | rgsw1): what the select form indexes
+    RgswSet() : Obj(T_RGSW_SET) {}
+    ~RgswSet() override {
+        if (!d_tab) return;
+        hipSetDevice(ev->be->ctx->dev);
+        hipStreamSynchronize(ev->be->ctx->stream);
+        hipFree(d_tab);
+    }
+};
+struct RgswShape {
+    int levelQ = 0, levelP = -1;
+    bool multiple_p = false;  // branch M (levelP >= 1): RNS digits; otherwise bit windows (pw2 == 0: one uncentred window per limb)
+    bool fused = false;       // inside the domain of launch_rgsw_fused
+};
+bool rgsw_same_shape(const Evk &a, const Evk &b) {
+    return a.nQk == b.nQk && a.nPk == b.nPk && a.pw2 == b.pw2 && a.beta == b.beta && a.nj == b.nj;
+}
+int rgsw_shape(const char *who, const Evaluator &ev, const Evk &a, const Evk &b, RgswShape *s) {
+    const BasisExtender &be = *ev.be;
+    if (a.ev.get() != &ev || b.ev.get() != &ev) return fail(HE_EINVAL, "%s: key belongs to another evaluator", who);
+    if (!rgsw_same_shape(a, b)) return fail(HE_EINVAL, "%s: the two gadget ciphertexts of an RGSW ciphertext differ in shape", who);
+    s->levelQ = a.nQk - 1; s->levelP = a.nPk - 1;
+    s->multiple_p = s->levelP >= 1;
+    if (!a.pw2 && a.nPk == 0) return fail(HE_EINVAL, "%s: BaseTwoDecomposition == 0 needs a special prime", who);
+    const int need = s->multiple_p ? base_rns_size(s->levelQ, s->levelP) : (a.pw2 ? a.prefix[s->levelQ + 1] : s->levelQ + 1);
+    if (a.beta < need) return fail(HE_EINVAL, "%s: key has %d digits, %d needed", who, a.beta, need);
+    // externalProduct32Bit (:84-128) sums plain 64-bit products key * NTTLazy(window) over both components' D windows, and
+    // NTTLazy returns words up to 6q - 2 (ring/ntt.go:133): below 2^64 the sum is the value the bit-window branch computes,
+    // at or above it the reference's output is an artefact of the wrap
+    const uint64_t q0 = be.Q->moduli[0];
+    if (s->levelQ == 0 && s->levelP == -1 && (q0 >> 29) == 0) {
+        const u128 bound = (u128)2 * (u128)a.nj[0] * (u128)(6 * q0 - 2) * (u128)(q0 - 1);
+        if ((bound >> 64) != 0)
+            return fail(HE_EINVAL, "%s: 2 D W (q - 1) >= 2^64 (D = %d windows, W = 6q - 2, q = %llu): the 32-bit branch of the reference wraps",
+                        who, a.nj[0], (unsigned long long)q0);
+    }
+    bool ok = be.type == 0 && !s->multiple_p && rgsw_fused_supported(be.Q->logN, s->levelQ + 1);
+    for (int i = 0; ok && i <= s->levelQ; i++) ok = (rgsw_nj(a, i) - 1) * a.pw2 < 64 && (a.pw2 ? a.prefix[i] : i) < 256;
+    s->fused = ok;
+    return HE_OK;
+}
+// what both routes account for: two GadgetProductLazy, the sum of their accumulators and ModDown (or the copy)
+void rgsw_account(Evaluator &ev, const Evk &k, const RgswShape &s, int B) {
+    BasisExtender &be = *ev.be;
+    const int nQ = s.levelQ + 1, nP = s.levelP + 1;
+    const int beta = s.multiple_p ? base_rns_size(s.levelQ, s.levelP) : (k.pw2 ? k.prefix[nQ] : nQ);
+    be.ctx->acct(4.0 * nQ, 2.0 * 2.0 * beta * (nQ + nP), B, be.Q->N);  // (in0, in1, out0, out1) and the rows of both keys
+    Valu V(be.Q->logN);
+    for (int c = 0; c < 2; c++) {
+        if (s.multiple_p) valu_keyswitch(V, be, s.levelQ, s.levelP, beta, true, true);
+        else {  // INTT of the component, one NTT and two products per (window, destination limb)
+            for (int i = 0; i < nQ; i++) V.ntt(cls_f64(be.small, i));
+            for (int j = 0; j < nQ + nP; j++) {
+                const int m = j < nQ ? j : be.LQ + j - nQ;
+                V.ntt(cls_f64(be.small, m), beta);
+                V.mul(cls_f64(be.small, m), 2.0 * beta);
+            }
+        }
+        if (nP > 0) valu_moddown(V, be, s.levelQ, s.levelP);
+    }
+    V.into(*be.ctx, B);
+}
+size_t rgsw_generic_words(const BasisExtender &be, const Evk &k, const RgswShape &s, int B) {
+    const size_t N = be.Q->N, nQ = s.levelQ + 1, nP = s.levelP + 1;
+    size_t beta = 0;
+    if (s.multiple_p) beta = (size_t)base_rns_size(s.levelQ, s.levelP);
+    else for (int i = 0; i <= s.levelQ; i++) beta += (size_t)rgsw_nj(k, i);
+    const size_t one = (size_t)B * nQ * N + (size_t)B * beta * (be.LQ + be.LP) * N;  // INTT(in_k) and its digits
+    return 2 * one + 2 * 2 * (size_t)B * (nQ + nP) * N + 2 * (size_t)B * (nQ + nP) * N + 256;
+}
+// the generic route: the accumulators of both components through the cores that exist, one sum, one ModDown over 2B entries
+int rgsw_generic(Evaluator &ev, const Evk &ka, const Evk &kb, const RgswShape &s, View in0, View in1, View out0, View out1, int B) {
+    BasisExtender &be = *ev.be;
+    hipStream_t st = be.ctx->stream;
+    const int levelQ = s.levelQ, levelP = s.levelP, N = be.Q->N;
+    const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N, W = sQw + sPw;
+    TRY(be.ctx->arena_reserve(rgsw_generic_words(be, ka, s, B)));
+    // acc[k]: [2 output components][B] entries of Q limbs then P limbs, so that one launch covers both rings and components
+    uint64_t *acc[2] = {be.ctx->arena_take(2 * (size_t)B * W), be.ctx->arena_take(2 * (size_t)B * W)};
+    const View none{nullptr, 0};
+    for (int k = 0; k < 2; k++) {
+        const Evk &key = k ? kb : ka;
+        const View cx = k ? in1 : in0;
+        const View o0Q{acc[k], W}, o1Q{acc[k] + (size_t)B * W, W};
+        const View o0P = levelP < 0 ? none : View{acc[k] + sQw, W}, o1P = levelP < 0 ? none : View{acc[k] + (size_t)B * W + sQw, W};
+        if (s.multiple_p) TRY(gadget_product_lazy_core(ev, levelQ, cx, B, key, o0Q, o0P, o1Q, o1P));
+        else TRY(window_products_core(ev, levelQ, cx, B, key, true, o0Q, o0P, o1Q, o1P));
+    }
+    if (levelP < 0) {  // ModDown's levelP == -1 branch is a copy: the sum goes straight to the outputs
+        const LimbTab tq = ident_tab(levelQ + 1);
+        HIP_TRY(launch_ew(be.qp, tq, EW_ADD, View{acc[0], W}, View{acc[1], W}, out0, B, nullptr, nullptr, st));
+        HIP_TRY(launch_ew(be.qp, tq, EW_ADD, View{acc[0] + (size_t)B * W, W}, View{acc[1] + (size_t)B * W, W}, out1, B, nullptr, nullptr, st));
+        return HE_OK;
+    }
+    LimbTab t;
+    t.n = 0;
+    for (int j = 0; j <= levelQ; j++, t.n++) { t.in_limb[t.n] = t.out_limb[t.n] = (uint8_t)t.n; t.mod[t.n] = (uint8_t)j; }
+    for (int j = 0; j <= levelP; j++, t.n++) { t.in_limb[t.n] = t.out_limb[t.n] = (uint8_t)t.n; t.mod[t.n] = (uint8_t)(be.LQ + j); }
+    HIP_TRY(launch_ew(be.qp, t, EW_ADD, View{acc[0], W}, View{acc[1], W}, View{acc[0], W}, 2 * B, nullptr, nullptr, st));
+    View sP{be.ctx->arena_take(2 * (size_t)B * sPw), sPw}, sQ{be.ctx->arena_take(2 * (size_t)B * sQw), sQw};
+    TRY(moddown_front(ev, levelQ, levelP, View{acc[0] + sQw, W}, sP, sQ, 2 * B, true));
+    TRY(moddown_back(ev, levelQ, levelP, sQ, View{acc[0], W}, out0, nullptr, B));
+    TRY(moddown_back(ev, levelQ, levelP, View{sQ.p + (size_t)B * sQw, sQw}, View{acc[0] + (size_t)B * W, W}, out1, nullptr, B));
+    return HE_OK;
+}
+// the fused route's arguments for keys of shape k (key0 / key1 / ktab are the caller's)
+void rgsw_fused_args(RgswFusedArgs &a, const BasisExtender &be, const Evk &k, const RgswShape &s, View in0, View in1, View out0, View out1) {
+    a.in0 = in0; a.in1 = in1; a.out0 = out0; a.out1 = out1;
+    a.nQ = s.levelQ + 1; a.nP = s.levelP + 1; a.p_mod = be.LQ;
+    a.key_limbs = k.nQk + k.nPk; a.key_p_limb = k.nQk;
+    a.pw2 = k.pw2;
+    a.mask = k.pw2 ? ((uint64_t)1 << k.pw2) - 1 : ~(uint64_t)0;
+    const uint64_t p = a.nP ? be.P->moduli[0] : 0;
+    a.p_half = a.nP ? (p - 1) / 2 : 0;
+    for (int i = 0; i < kRgswMaxQ; i++) { a.nj[i] = a.prefix[i] = 0; a.md_s[i] = a.p_mod_q[i] = 0; }
+    for (int i = 0; i < a.nQ; i++) {
+        a.nj[i] = (uint8_t)rgsw_nj(k, i);
+        a.prefix[i] = (uint8_t)(k.pw2 ? k.prefix[i] : i);
+        if (a.nP) { a.md_s[i] = be.Q->moduli[i] - be.md_ptoq[0][i]; a.p_mod_q[i] = p % be.Q->moduli[i]; }
+    }
+}
+// operands shared by the two product entries: (in0, in1, out0, out1), out_k == in_k allowed
+int rgsw_operands(Operands &o, int nQ, he_handle in0, he_handle in1, he_handle out0, he_handle out1) {
+    const int i0 = o.in(in0, nQ, "in0"), i1 = o.in(in1, nQ, "in1");
+    const int o0 = o.out(out0, nQ, "out0"), o1 = o.out(out1, nQ, "out1");
+    o.inplace(o0, i0);
+    o.inplace(o1, i1);
+    return o.check();
+}
+}  // namespace
+
+int he_rgsw_external_product(he_handle hev, he_handle in0, he_handle in1, he_handle hk0, he_handle hk1, he_handle out0, he_handle out1) {
+    static const char *who = "he_rgsw_external_product";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(k0, Evk, hk0, T_EVK);
+    GET(k1, Evk, hk1, T_EVK);
+    BasisExtender &be = *ev->be;
+    RgswShape s;
+    TRY(rgsw_shape(who, *ev, *k0, *k1, &s));
+    static const bool no_fused = env_flag("HERING_NO_RGSW_FUSED");
+    if (no_fused) s.fused = false;
+    CoReq q;
+    Operands o(q, who, be);
+    TRY(rgsw_operands(o, s.levelQ + 1, in0, in1, out0, out1));
+    q.op = CO_RGSW; q.obj = ev.get(); q.key = k0.get(); q.par[0] = (int64_t)(uintptr_t)k1.get(); q.par[1] = 0;
+    q.keep.push_back(ev); q.keep.push_back(k0); q.keep.push_back(k1);
+    q.run = [ev, k0, k1, s](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        rgsw_account(*ev, *k0, s, B);
+        if (!s.fused) {
+            // both components of the batch go in one launch, 2 B entries along the grid's z: chunks of at most 32767 entries
+            for (int b0 = 0; b0 < B; b0 += 32767) {
+                View c[4];
+                for (int i = 0; i < 4; i++) c[i] = View{v[i].p + (size_t)b0 * v[i].bstride, v[i].bstride};
+                be.ctx->arena_reset();
+                TRY(rgsw_generic(*ev, *k0, *k1, s, c[0], c[1], c[2], c[3], std::min(32767, B - b0)));
+            }
+            return HE_OK;
+        }
+        RgswFusedArgs a;
+        rgsw_fused_args(a, be, *k0, s, v[0], v[1], v[2], v[3]);
+        a.key0 = k0->d; a.key1 = k1->d;
+        HIP_TRY(launch_rgsw_fused(be.qp, a, B, be.ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (queued calls are served one by one, as other base-2 shapes)
+    return co_dispatch(*be.ctx, o.B, q);
+}
+int he_rgsw_keyset_create(he_handle hev, int n, const he_handle *rgsw0, const he_handle *rgsw1, he_handle *out) {
+    static const char *who = "he_rgsw_keyset_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    if (n < 1 || !rgsw0 || !rgsw1 || !out) return fail(HE_EINVAL, "%s: at least one RGSW ciphertext and an output are needed", who);
+    auto set = std::make_shared<RgswSet>();
+    set->ev = ev;
+    for (int i = 0; i < n; i++) {
+        std::shared_ptr<Evk> a = get<Evk>(rgsw0[i], T_EVK), b = get<Evk>(rgsw1[i], T_EVK);
+        if (!a || !b) return fail(HE_EHANDLE, "%s: bad Evk handle (key %d)", who, i);
+        RgswShape s;
+        TRY(rgsw_shape(who, *ev, *a, *b, &s));
+        if (i > 0 && !rgsw_same_shape(*a, *set->k0[0])) return fail(HE_EINVAL, "%s: key %d differs in shape from key 0", who, i);
+        set->k0.push_back(a); set->k1.push_back(b);
+    }
+    std::vector<size_t> tab(2 * (size_t)n);
+    for (int i = 0; i < n; i++) { tab[i] = (size_t)(uintptr_t)set->k0[i]->d; tab[(size_t)n + i] = (size_t)(uintptr_t)set->k1[i]->d; }
+    Scope sc(ev->be->ctx.get());
+    HIP_TRY(hipMalloc((void **)&set->d_tab, tab.size() * sizeof(size_t)));
+    HIP_TRY(hipMemcpy(set->d_tab, tab.data(), tab.size() * sizeof(size_t), hipMemcpyHostToDevice));
+    *out = reg(set);
+    return HE_OK;
+}
+int he_rgsw_keyset_destroy(he_handle h) { return unreg(h, T_RGSW_SET); }
+int he_rgsw_external_product_select(he_handle hev, he_handle in0, he_handle in1, he_handle hset, const int32_t *sel, int n_sel,
+                                    he_handle out0, he_handle out1) {
+    static const char *who = "he_rgsw_external_product_select";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(set, RgswSet, hset, T_RGSW_SET);
+    BasisExtender &be = *ev->be;
+    if (set->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key set belongs to another evaluator", who);
+    RgswShape s;
+    TRY(rgsw_shape(who, *ev, *set->k0[0], *set->k1[0], &s));
+    if (!s.fused) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_rgsw.h)", who);
+    if (!sel || n_sel < 1) return fail(HE_EINVAL, "%s: null selection", who);
+    const int n = (int)set->k0.size();
+    for (int b = 0; b < n_sel; b++)
+        if (sel[b] < -1 || sel[b] >= n) return fail(HE_EINVAL, "%s: sel[%d] = %d outside [-1, %d)", who, b, (int)sel[b], n);
+    CoReq q;
+    Operands o(q, who, be);
+    TRY(rgsw_operands(o, s.levelQ + 1, in0, in1, out0, out1));
+    if (n_sel != o.B) return fail(HE_EINVAL, "%s: n_sel = %d, the batch has %d entries", who, n_sel, o.B);
+    q.op = CO_RGSW; q.obj = ev.get(); q.key = set.get(); q.par[1] = 1;
+    for (int b = 0; b < n_sel; b++) q.blob.push_back((uint64_t)(int64_t)sel[b]);
+    q.keep.push_back(ev); q.keep.push_back(set);
+    const std::vector<int32_t> selv(sel, sel + n_sel);  // frozen here: a scalar argument of the call
+    q.run = [ev, set, s, selv](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        if ((int)selv.size() != B) return fail(HE_EINVAL, "he_rgsw_external_product_select: selection of %d for %d entries", (int)selv.size(), B);
+        // the selection, two int32 per word, into scratch from kernel arguments (no host buffer outlives the call; a captured
+        // graph holds it); the keys' addresses are resident with the set
+        int used = 0;
+        std::vector<size_t> tab(((size_t)B + 1) / 2, 0);
+        for (int b = 0; b < B; b++) {
+            tab[b / 2] |= (size_t)(uint32_t)selv[b] << (32 * (b & 1));
+            used += selv[b] >= 0;
+        }
+        if (used) rgsw_account(*ev, *set->k0[0], s, used);
+        be.ctx->acct(4.0 * (s.levelQ + 1), 0, B - used, be.Q->N);
+        TRY(be.ctx->arena_reserve(tab.size() + 2));
+        size_t *d = reinterpret_cast<size_t *>(be.ctx->arena_take(tab.size()));
+        HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), be.ctx->stream));
+        RgswFusedArgs a;
+        rgsw_fused_args(a, be, *set->k0[0], s, v[0], v[1], v[2], v[3]);
+        a.ktab = set->d_tab; a.nkeys = (int)set->k0.size();
+        a.sel = reinterpret_cast<const int32_t *>(d);
+        HIP_TRY(launch_rgsw_fused(be.qp, a, B, be.ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*be.ctx, o.B, q);
+}
+
+// ---- the element-wise helpers of core/rgsw/evaluator.go:283-356 on the words of a device-resident gadget ciphertext ----------
+namespace {
+// one element-wise launch over the Q limbs of every row and one over the P limbs (y: a polynomial of the Q / P ring shared by the
+// rows, or the rows of another key when yQ.p is null)
+int key_rows_ew(const Evk &out, int op, View x, View yQ, View yP, View ykey) {
+    BasisExtender &be = *out.ev->be;
+    const int nQ = out.nQk, nP = out.nPk, rows = 2 * out.beta;
+    hipStream_t st = be.ctx->stream;
+    const View z = out.rows();
+    if (!yQ.p) {  // key (op) key: one launch over all limbs
+        LimbTab t;
+        t.n = 0;
+        for (int j = 0; j < nQ + nP; j++, t.n++) { t.in_limb[t.n] = t.out_limb[t.n] = (uint8_t)j; t.mod[t.n] = (uint8_t)(j < nQ ? j : be.LQ + j - nQ); }
+        HIP_TRY(launch_ew(be.qp, t, op, x, ykey, z, rows, nullptr, nullptr, st));
+        return HE_OK;
+    }
+    HIP_TRY(launch_ew(be.qp, ident_tab(nQ), op, x, yQ, z, rows, nullptr, nullptr, st));
+    if (nP > 0) {
+        LimbTab t;
+        uint8_t xl[kMaxLimbs];
+        t.n = nP;
+        for (int j = 0; j < nP; j++) { t.in_limb[j] = (uint8_t)j; t.out_limb[j] = xl[j] = (uint8_t)(nQ + j); t.mod[j] = (uint8_t)(be.LQ + j); }
+        HIP_TRY(launch_ew(be.qp, t, op, x, yP, z, rows, nullptr, xl, st));
+    }
+    return HE_OK;
+}
+}  // namespace
+int he_rgsw_key_op(int op, he_handle hin, he_handle hxQ, he_handle hxP, he_handle hout) {
+    static const char *who = "he_rgsw_key_op";
+    GET(in, Evk, hin, T_EVK);
+    GET(out, Evk, hout, T_EVK);
+    if (in->ev.get() != out->ev.get() || !rgsw_same_shape(*in, *out)) return fail(HE_EINVAL, "%s: the two keys differ in evaluator or shape", who);
+    BasisExtender &be = *out->ev->be;
+    const bool mul = op == HE_RGSW_MUL_LAZY || op == HE_RGSW_MUL_THEN_ADD_LAZY;
+    if (!mul && op != HE_RGSW_ADD_LAZY && op != HE_RGSW_REDUCE) return fail(HE_EINVAL, "%s: unknown operation %d", who, op);
+    std::shared_ptr<Poly> xQ, xP;
+    if (mul) {
+        xQ = get<Poly>(hxQ, T_POLY);
+        if (out->nPk > 0) xP = get<Poly>(hxP, T_POLY);
+        if (!xQ || (out->nPk > 0 && !xP)) return fail(HE_EHANDLE, "%s: bad Poly handle for powXMinusOne", who);
+        for (const Poly *x : {xQ.get(), xP.get()}) {
+            if (!x) continue;
+            if (x->ctx != be.ctx || x->N != be.Q->N || x->batch != 1 || x->nlimbs < (x == xQ.get() ? out->nQk : out->nPk))
+                return fail(HE_EINVAL, "%s: powXMinusOne is one polynomial of the evaluator's degree with the key's limbs", who);
+        }
+    }
+    Scope sc(be.ctx.get());
+    const int rows = 2 * out->beta, limbs = out->nQk + out->nPk;
+    be.ctx->acct((op == HE_RGSW_REDUCE ? 2.0 : 3.0) * limbs, mul ? limbs : 0, rows, be.Q->N);
+    if (mul) { Valu V(be.Q->logN); for (int j = 0; j < limbs; j++) V.mul(cls_f64(be.small, j < out->nQk ? j : be.LQ + j - out->nQk), 1.0); V.into(*be.ctx, rows); }
+    const View none{nullptr, 0};
+    switch (op) {
+        case HE_RGSW_ADD_LAZY: TRY(key_rows_ew(*out, EW_ADD_LAZY, out->rows(), none, none, in->rows())); break;
+        case HE_RGSW_REDUCE: TRY(key_rows_ew(*out, EW_REDUCE, in->rows(), none, none, in->rows())); break;
+        default:
+            TRY(key_rows_ew(*out, op == HE_RGSW_MUL_LAZY ? EW_MUL_MONT_LAZY : EW_MUL_MONT_LAZY_THEN_ADD_LAZY, in->rows(),
+                            View{xQ->d, 0}, xP ? View{xP->d, 0} : none, none));
+    }
+    return evk_derive(*out);  // (he_evk_commit's launches, in stream order)
+}
+int he_rgsw_key_add_plaintext_lazy(he_handle hpt, he_handle hk0, he_handle hk1) {
+    static const char *who = "he_rgsw_key_add_plaintext_lazy";
+    GET(pt, Poly, hpt, T_POLY);
+    GET(k0, Evk, hk0, T_EVK);
+    GET(k1, Evk, hk1, T_EVK);
+    if (k0->ev.get() != k1->ev.get() || !rgsw_same_shape(*k0, *k1) || k0.get() == k1.get())
+        return fail(HE_EINVAL, "%s: the two gadget ciphertexts of an RGSW ciphertext are distinct keys of one evaluator and shape", who);
+    BasisExtender &be = *k0->ev->be;
+    const int nQ = k0->nQk, N = be.Q->N;
+    const int nP = k0->nPk > 0 ? k0->nPk : 1;  // (:290-292)
+    int maxj = 1;
+    for (int i = 0; k0->pw2 && i < nQ; i++) maxj = std::max(maxj, k0->nj[i]);
+    if (pt->ctx != be.ctx || pt->N != N || pt->nlimbs < nQ || pt->batch < maxj)
+        return fail(HE_EINVAL, "%s: the plaintext holds one polynomial of %d limbs per window (%d windows)", who, nQ, maxj);
+    const int digits = k0->pw2 ? nQ : k0->beta;
+    Scope sc(be.ctx.get());
+    hipStream_t st = be.ctx->stream;
+    const size_t rs = (size_t)(k0->nQk + k0->nPk) * N;
+    int d = 0;
+    for (int i = 0; i < digits; i++) {
+        const int start = i * nP, end = std::min((i + 1) * nP, nQ);
+        const int wj = k0->pw2 ? k0->nj[i] : 1;
+        for (int j = 0; j < wj; j++, d++) {
+            if (start >= end) continue;
+            const LimbTab t = ident_tab(end - start, start, start, start);
+            const View y{pt->d + (size_t)j * pt->nlimbs * N, 0};
+            for (int c = 0; c < 2; c++) {  // Value[0][i][j][0] and Value[1][i][j][1]
+                const View row{(c ? k1->d : k0->d) + ((size_t)d * 2 + c) * rs, 0};
+                HIP_TRY(launch_ew(be.qp, t, EW_ADD_LAZY, row, y, row, 1, nullptr, nullptr, st));
+            }
+            be.ctx->acct(6.0 * (end - start), 0, 1, N);
+        }
+    }
+    TRY(evk_derive(*k0));
+    return evk_derive(*k1);
 }
 
 // ---------------------------------------------------------------------------------------

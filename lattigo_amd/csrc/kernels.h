@@ -258,6 +258,30 @@ struct MaskSpreadArgs {
 hipError_t launch_mask_spread(const RingDev &r, const MaskSpreadArgs &a, View src, uint64_t *dec, size_t dec_bs, size_t dec_ds,
                               int batch, hipStream_t s);
 
+// ---- RGSW external product, small rings (core/rgsw/evaluator.go:130-204) -------------------------
+// The whole product of one batch entry in one workgroup (rgsw_fused_kernel): out_c = [ModDown of] sum over (component k, source
+// limb i, window j) of key_k[prefix[i] + j][c] * NTT((INTT(in_k)[i] >> j pw2) & mask), limbs 0..nQ-1, canonical.  Standard rings,
+// at most one special prime (nP; its modulus record is p_mod and its limb inside a key block key_p_limb).  out_k may be in_k.
+// ktab (select form): a device array [2][nkeys] of key base addresses (rgsw0 | rgsw1) and sel, a device array of one int32 per
+// batch entry: the entry's key, or -1 = the entry is copied.
+constexpr int kRgswMaxQ = 8;
+struct RgswFusedArgs {
+    View in0, in1, out0, out1;  // no entry tables
+    const uint64_t *key0 = nullptr, *key1 = nullptr;
+    const size_t *ktab = nullptr;
+    const int32_t *sel = nullptr;
+    int nkeys = 0;
+    int nQ = 0, nP = 0, p_mod = 0, key_limbs = 0, key_p_limb = 0;
+    int pw2 = 0;                // 0: one uncentred window per limb, mask = all ones
+    uint64_t mask = 0;
+    uint8_t nj[kRgswMaxQ], prefix[kRgswMaxQ];
+    uint64_t md_s[kRgswMaxQ];     // q_u - MForm(P^-1 mod q_u)
+    uint64_t p_mod_q[kRgswMaxQ];  // p mod q_u
+    uint64_t p_half = 0;          // (p - 1) / 2
+};
+bool rgsw_fused_supported(int logN, int nQ);  // logN 9..11 and the coefficients of 2 nQ limbs beside the exchange buffer in 64 KiB of LDS
+hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s);
+
 // ---- key-switch inner product ---------------------------------------------------------------
 // acc[k][l] = sum_d evk[d][k][l] * dec[d][l] * 2^-64 mod q_l, canonical
 // (core/rlwe/evaluator_gadget_product.go:160-200 after its final Reduce).
@@ -411,7 +435,7 @@ enum KernelId {
     K_NTT_COLS_FWD = 0, K_NTT_ROWS_FWD, K_NTT_ROWS_INV, K_NTT_COLS_INV, K_EW, K_GATHER, K_AUTO_COEFF, K_INDEX,
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
-    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_COUNT
+    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

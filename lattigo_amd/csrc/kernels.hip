@@ -73,7 +73,7 @@ const char *kernel_name(int id) {
                                          "tensor", "modmul_probe", "ci_fold", "mask_spread", "ntt_rows_fwd_f64",
                                          "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
                                          "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
-                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill"};
+                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -4355,6 +4355,242 @@ hipError_t launch_tensor(const RingDev &r, const LimbTab &tab, const uint64_t *s
     // a1, b1 -> c2 always; a0, b0 -> c0, c1 when those outputs exist
     ProfScope ps(K_TENSOR, s, (c0.p ? 7.0 : 3.0) * tab.n * batch * (double)r.N * 8.0);
     hipLaunchKernelGGL(tensor_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// RGSW external product of a small ring in ONE launch (core/rgsw/evaluator.go:130-204, the bit-window branch, which also
+// serves the 32-bit branch :84-128 wherever that one cannot wrap).  One workgroup per batch entry, sixteen coefficients per
+// thread as in ntt_rows_kernel with a single row (the same radix-16 rounds and LDS exchanges).
+//   phase 1: both components, every Q limb: INTT with N^-1, the canonical coefficients parked in LDS (`coef`, thread-private
+//            slots) -- every input word is read before any output word is written, so out_k may be in_k;
+//   phase 2: per destination limb (the special prime first): for every (component, source limb, window) mask the coefficients,
+//            transform them in the destination modulus and multiply the two key rows into two register accumulators;
+//            the P limb's accumulators are inverse-transformed and kept (ext); a Q limb ends with ModDown's last step,
+//            MRed(NTT(lift(ext)) + 2q - acc, q - P^-1), or with the plain store when there is no special prime.
+// The canonical output does not depend on the reduction schedule, so windows are reduced below the destination modulus before
+// they are transformed and the accumulators are reduced after every product.
+// ------------------------------------------------------------------------------------
+template <int LOGB>
+__device__ __forceinline__ void rgsw_ntt_fwd(uint64_t (&x)[16], uint64_t *lds, const uint64_t *__restrict__ tw, int tau,
+                                             const ModConst &mc) {
+    // x[k] = coefficient (k << (LOGB - 4)) + tau, below 4q -> lds (natural order, lds_phys) in [0, 4q)
+    constexpr int NR4 = LOGB / 4, GREM = LOGB % 4;
+    const uint64_t q = mc.q, qinv = mc.qinv, twoq = mc.q << 1;
+    uint64_t t16[15];
+    rows_tw16(t16, tw, 1, 0, 0);
+#pragma unroll 1
+    for (int rho = 0; rho < NR4; rho++) {
+        const int s0 = 4 * rho, sh = LOGB - s0 - 4;
+        if (rho > 0) rows_lds_xfer<LOGB, 4>(x, lds, tau, s0, sh, false);
+        rows_round16<false, false>(x, t16, q, twoq, qinv, mc, false);
+        if (rho + 1 < NR4) rows_tw16(t16, tw, 1, s0 + 4, tau >> (sh - 4));
+        rows_lds_xfer<LOGB, 4>(x, lds, tau, s0, sh, true);
+        rows_sync(sh);
+    }
+    if constexpr (GREM > 0) {
+        constexpr int s0 = 4 * NR4;
+        rows_lds_xfer<LOGB, GREM>(x, lds, tau, s0, 0, false);
+        rows_round<GREM, false, false>(x, tw, 1, s0, 0, tau, 0, q, twoq, qinv, mc, false);
+        rows_lds_xfer<LOGB, GREM>(x, lds, tau, s0, 0, true);
+    }
+    __syncthreads();
+}
+template <int LOGB>
+__device__ __forceinline__ void rgsw_ntt_inv(uint64_t (&x)[16], uint64_t *lds, const uint64_t *__restrict__ tw, int tau,
+                                             const ModConst &mc) {
+    // lds (natural order, words in [0, 2q), written and synchronised by the caller) -> x[k] = coefficient (k << (LOGB - 4)) + tau,
+    // canonical, N^-1 included
+    constexpr int NR4 = LOGB / 4, GREM = LOGB % 4;
+    const uint64_t q = mc.q, qinv = mc.qinv, twoq = mc.q << 1;
+    if constexpr (GREM > 0) {
+        constexpr int s0 = 4 * NR4;
+        rows_lds_xfer<LOGB, GREM>(x, lds, tau, s0, 0, false);
+        rows_round<GREM, true, false>(x, tw, 1, s0, 0, tau, 0, q, twoq, qinv, mc, false);
+        rows_lds_xfer<LOGB, GREM>(x, lds, tau, s0, 0, true);
+        rows_sync(GREM);
+    }
+    uint64_t t16[15];
+    rows_tw16(t16, tw, 1, 4 * (NR4 - 1), tau >> (LOGB - 4 * NR4));
+#pragma unroll 1
+    for (int rho = NR4 - 1; rho >= 0; rho--) {
+        const int s0 = 4 * rho, sh = LOGB - s0 - 4;
+        rows_lds_xfer<LOGB, 4>(x, lds, tau, s0, sh, false);
+        rows_round16<true, false>(x, t16, q, twoq, qinv, mc, rho == 0);
+        if (rho > 0) {
+            rows_tw16(t16, tw, 1, s0 - 4, tau >> (sh + 4));
+            rows_lds_xfer<LOGB, 4>(x, lds, tau, s0, sh, true);
+            rows_sync(sh + 4);
+        }
+    }
+}
+struct RgswKArgs {
+    RgswFusedArgs a;
+    const ModConst *mc;
+    const uint64_t *twf, *twi;
+};
+template <int LOGB>
+__global__ void __launch_bounds__((1 << LOGB) / 16) rgsw_fused_kernel(RgswKArgs K) {
+    constexpr int N = 1 << LOGB, T = N / 16;
+    __shared__ uint64_t lds[N + N / 16];
+    extern __shared__ uint64_t coef[];  // [2 nQ][16][T]: slot (s, k) of thread tau
+    const RgswFusedArgs &A = K.a;
+    const int tau = threadIdx.x, nQ = A.nQ;
+    const size_t z = blockIdx.x;
+    const uint64_t *in0 = A.in0.p + z * A.in0.bstride, *in1 = A.in1.p + z * A.in1.bstride;
+    uint64_t *out0 = A.out0.p + z * A.out0.bstride, *out1 = A.out1.p + z * A.out1.bstride;
+    const uint64_t *key0 = A.key0, *key1 = A.key1;
+    if (A.ktab) {  // select form: this entry's own key of the resident table, or none (the entry is passed through)
+        const int si = A.sel[z];
+        if (si >= 0) {
+            key0 = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)si));
+            key1 = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)A.nkeys + si));
+        } else {
+            for (int e = tau; e < nQ * N; e += T) {
+                if (out0 != in0) out0[e] = in0[e];
+                if (out1 != in1) out1[e] = in1[e];
+            }
+            return;
+        }
+    }
+    // ---- phase 1
+#pragma unroll 1
+    for (int s = 0; s < 2 * nQ; s++) {
+        const int k = s >= nQ, i = s - k * nQ;
+        const uint64_t *__restrict__ src = (k ? in1 : in0) + (size_t)i * N;
+        const ModConst mc = K.mc[i];
+        const uint64_t twoq = mc.q << 1;
+        uint64_t x[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) x[kk] = ldnt(&src[nat_e<T>(kk, tau)]);
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) x[kk] = x[kk] >= twoq ? bred_add_lazy(x[kk], mc.q, mc.brc0) : x[kk];
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = x[kk];
+        __syncthreads();
+        rgsw_ntt_inv<LOGB>(x, lds, K.twi + (size_t)i * N, tau, mc);
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) coef[(s * 16 + kk) * T + tau] = x[kk];
+    }
+    // ---- phase 2
+    uint64_t ext[2][16];
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) ext[c][kk] = 0;
+    const int nD = nQ + A.nP;
+#pragma unroll 1
+    for (int ui = 0; ui < nD; ui++) {
+        const bool isP = A.nP != 0 && ui == 0;
+        const int u = isP ? 0 : ui - A.nP;        // limb of the output / of the P accumulator
+        const int mi = isP ? A.p_mod : u;         // its modulus record
+        const int kl = isP ? A.key_p_limb : u;    // its limb inside a (digit, component) block of the key
+        const ModConst mc = K.mc[mi];
+        const uint64_t q = mc.q, qinv = mc.qinv, twoq = mc.q << 1;
+        const uint64_t *__restrict__ twf = K.twf + (size_t)mi * N;
+        const bool red = A.mask >= q;  // a window may reach the modulus it is transformed in
+        uint64_t acc[2][16];
+#pragma unroll
+        for (int c = 0; c < 2; c++)
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) acc[c][kk] = 0;
+#pragma unroll 1
+        for (int s = 0; s < 2 * nQ; s++) {
+            const int k = s >= nQ, i = s - k * nQ;
+            const uint64_t *kb = k ? key1 : key0;
+            uint64_t x[16];
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) x[kk] = coef[(s * 16 + kk) * T + tau];
+#pragma unroll 1
+            for (int j = 0; j < (int)A.nj[i]; j++) {
+                const int shift = j * A.pw2;
+                uint64_t y[16];
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    y[kk] = (x[kk] >> shift) & A.mask;
+                    if (red) y[kk] = bred_add_lazy(y[kk], q, mc.brc0);
+                }
+                __syncthreads();  // (the previous transform's words are still being read)
+                rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);
+                const size_t d = (size_t)A.prefix[i] + j;
+                const uint64_t *__restrict__ k0 = kb + ((d * 2) * A.key_limbs + kl) * N;
+                const uint64_t *__restrict__ k1 = k0 + (size_t)A.key_limbs * N;
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    const int e = nat_e<T>(kk, tau);
+                    uint64_t v = lds[lds_phys(e)];
+                    v = v >= twoq ? v - twoq : v;
+                    acc[0][kk] = cred(acc[0][kk] + mred_w32(v, k0[e], q, qinv), q);
+                    acc[1][kk] = cred(acc[1][kk] + mred_w32(v, k1[e], q, qinv), q);
+                }
+            }
+        }
+        if (isP) {  // ModDownQPtoQNTT's INTT of the P part (ring/basis_extension.go:247)
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = acc[c][kk];
+                __syncthreads();
+                rgsw_ntt_inv<LOGB>(ext[c], lds, K.twi + (size_t)mi * N, tau, mc);
+            }
+            continue;
+        }
+        if (A.nP) {
+            // ModUpPtoQ of one residue: v -> v - p where v > (p - 1) / 2 (:203-207 around ModUpExact), then NTT and
+            // MRed(ext + 2q - acc, q - P^-1) (:249-255)
+            const uint64_t pmq = A.p_mod_q[u], sdn = A.md_s[u];
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                uint64_t y[16];
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    const uint64_t v = ext[c][kk];
+                    const uint64_t r = bred_add(v, q, mc.brc0);
+                    y[kk] = v > A.p_half ? cred(r + q - pmq, q) : r;
+                }
+                __syncthreads();
+                rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    uint64_t v = lds[lds_phys(nat_e<T>(kk, tau))];
+                    v = v >= twoq ? v - twoq : v;
+                    acc[c][kk] = mred_w32(v + twoq - acc[c][kk], sdn, q, qinv);
+                }
+            }
+        }
+        uint64_t *o0 = out0 + (size_t)u * N, *o1 = out1 + (size_t)u * N;
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) {
+            const int e = nat_e<T>(kk, tau);
+            o0[e] = acc[0][kk];
+            o1[e] = acc[1][kk];
+        }
+    }
+}
+bool rgsw_fused_supported(int logN, int nQ) {
+    if (logN < 9 || logN > 11 || nQ < 1 || nQ > kRgswMaxQ) return false;
+    const size_t n = (size_t)1 << logN;
+    return (n + n / 16 + 2 * (size_t)nQ * n) * 8 <= 65536;  // the exchange buffer and the parked coefficients, in LDS
+}
+hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s) {
+    if (!rgsw_fused_supported(r.logN, a.nQ) || batch <= 0 || a.nP < 0 || a.nP > 1 || !no_tab({a.in0, a.in1, a.out0, a.out1}) ||
+        !a.in0.p || !a.in1.p || !a.out0.p || !a.out1.p || (!a.ktab && (!a.key0 || !a.key1)) || (a.ktab && (!a.sel || a.nkeys <= 0)))
+        return hipErrorInvalidValue;
+    RgswKArgs K{};
+    K.a = a; K.mc = r.mc; K.twf = r.tw_fwd; K.twi = r.tw_inv;
+    const size_t dyn = 2 * (size_t)a.nQ * r.N * 8;
+    const unsigned T = (unsigned)r.N / 16;
+    double windows = 0.0;
+    for (int i = 0; i < a.nQ; i++) windows += a.nj[i];
+    // both components in and out, and the key rows of every window (shared by the batch: counted once)
+    ProfScope ps(K_RGSW_FUSED, s, (4.0 * a.nQ * batch + (a.ktab ? 0.0 : 4.0 * windows * (a.nQ + a.nP))) * (double)r.N * 8.0);
+    switch (r.logN) {
+        case 9: hipLaunchKernelGGL(rgsw_fused_kernel<9>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        case 10: hipLaunchKernelGGL(rgsw_fused_kernel<10>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        default: hipLaunchKernelGGL(rgsw_fused_kernel<11>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+    }
     return hipGetLastError();
 }
 

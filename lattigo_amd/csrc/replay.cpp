@@ -27,6 +27,7 @@
 #include "../../include/hering_debug.h"
 #include "../../include/hering_ringswitch.h"
 #include "../../include/hering_ringpack.h"
+#include "../../include/hering_rgsw.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -37,8 +38,10 @@ enum Fn : uint64_t {
     F_DECOMPOSE_NTT, F_GP_LAZY, F_GP_HOISTED_LAZY, F_MODDOWN, F_GP, F_GP_HOISTED, F_RELIN, F_AUTO_CT, F_AUTO_HOISTED, F_AUTO_HOISTED_LAZY,
     F_CENTERED_LIFT, F_DECOMP_FILL, F_LINTRANS, F_CKKS_MUL, F_BGV_MUL, F_GIANT_STEP,
     F_MAP_SMALL_TO_LARGE, F_SWITCH_RING_NTT, F_SWITCH_RING, F_APPLY_EVK,
-    F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST, F_COUNT
+    F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST,
+    F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_COUNT
 };
+static_assert(F_COUNT <= 128, "the per-function profile has 128 slots");
 struct Arg {
     uint64_t kind = 0, val = 0;
     std::vector<uint64_t> arr;
@@ -59,7 +62,8 @@ struct Worker {
     double t0 = 0, t1 = 0;
     std::string err;
 };
-std::atomic<uint64_t> g_fn_us[64], g_fn_n[64], g_fn_max[64];  // per function: microseconds inside the calls, calls, longest call (he_debug_replay_profile)
+constexpr int kFnSlots = 128;  // >= F_COUNT
+std::atomic<uint64_t> g_fn_us[kFnSlots], g_fn_n[kFnSlots], g_fn_max[kFnSlots];  // per function: microseconds inside the calls, calls, longest call (he_debug_replay_profile)
 double mono_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::vector<std::pair<uint64_t, uint64_t>> &made) {
@@ -169,6 +173,12 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
         case F_RP_EXPAND_STEP: return he_ringpack_expand_step(H(0), (int)I(1), (int)I(2), (int)I(3), H(4), H(5), H(6), H(7), H(8), H(9));
         case F_RP_PACK_PRE: return he_ringpack_pack_pre(H(0), (int)I(1), (int)I(2), (int)I(3), HA(4), HA(5), HA(6), HA(7), H(8), H(9));
         case F_RP_PACK_POST: return he_ringpack_pack_post(H(0), (int)I(1), (int)I(2), HA(3), HA(4), HA(5), HA(6), H(7), H(8));
+        case F_RGSW_EXTPROD: return he_rgsw_external_product(H(0), H(1), H(2), H(3), H(4), H(5), H(6));
+        case F_RGSW_EXTPROD_SELECT: {  // the selection travels as 64-bit words (-1 = 2^64 - 1)
+            std::vector<int32_t> sel;
+            if (a.size() > 4 && a[4].kind == 3) for (uint64_t w : a[4].arr) sel.push_back((int32_t)(int64_t)w);
+            return he_rgsw_external_product_select(H(0), H(1), H(2), H(3), sel.empty() ? nullptr : sel.data(), (int)I(5), H(6), H(7));
+        }
         default: return HE_EINVAL;
     }
 }
@@ -217,7 +227,7 @@ void *worker(void *vp) {
 // per function number of the program encoding: [3 f + 0] microseconds spent inside its calls (all threads), [3 f + 1] calls,
 // [3 f + 2] the longest single call, since the last reset
 extern "C" int he_debug_replay_profile(uint64_t *out, int n_fn, int reset) {
-    for (int f = 0; f < n_fn && f < 64; f++) {
+    for (int f = 0; f < n_fn && f < kFnSlots; f++) {
         if (out) { out[3 * f] = g_fn_us[f].load(); out[3 * f + 1] = g_fn_n[f].load(); out[3 * f + 2] = g_fn_max[f].load(); }
         if (reset) { g_fn_us[f] = 0; g_fn_n[f] = 0; g_fn_max[f] = 0; }
     }

@@ -149,6 +149,22 @@ def gadget_ciphertext_binary_size(nj, limbsQ: int, limbsP: int, N: int, comps: i
     return 8 + 8 + sum(8 + n * per for n in nj)
 
 
+def rgsw_ciphertext_marshal(value0, value1) -> bytes:
+    """rgsw.Ciphertext.WriteTo (core/rgsw/elements.go:52-67): the two gadget ciphertexts back to back.  value_k = (kq, kp,
+    BaseTwoDecomposition, nj) as gadget_ciphertext_marshal takes them."""
+    return gadget_ciphertext_marshal(*value0) + gadget_ciphertext_marshal(*value1)
+
+
+def rgsw_ciphertext_unmarshal(buf: bytes):
+    """rgsw.Ciphertext.ReadFrom (core/rgsw/elements.go:80-95) -> two (kq, kp, BaseTwoDecomposition, nj); the buffer must hold
+    exactly the two gadget ciphertexts"""
+    r = _Reader(buf)
+    out = (_gadget_ciphertext_read(r), _gadget_ciphertext_read(r))
+    if r.off != len(buf):
+        raise ValueError("trailing bytes after the second gadget ciphertext")
+    return out
+
+
 def galois_key_marshal(galois_element: int, nth_root: int, kq, kp, base_two: int = 0, nj=None) -> bytes:
     """rlwe.GaloisKey.WriteTo (core/rlwe/keys.go:628): GaloisElement, NthRoot, then the EvaluationKey (= its
     GadgetCiphertext, keys.go:443)."""
