@@ -40,6 +40,21 @@
  * The helpers of core/rgsw/evaluator.go:283-356 (AddLazy, Reduce, MulByXPowAlphaMinusOne[ThenAdd]Lazy) run as element-wise
  * launches over the words of the keys, every (digit, component, limb) row, with the reference's lazy words; they are followed by
  * what he_evk_commit does, in stream order.  They are not queued and must not run while another thread uses the keys.
+ *
+ * Key words.  Keys as created (he_evk_create*) or committed (he_evk_commit) hold canonical words.  The lazy helpers leave words
+ * at or above q on the device, and the library keeps a bound M with every key -- its words lie below M q in every limb: 1 as
+ * created, committed or after HE_RGSW_REDUCE; out.M + in.M after HE_RGSW_ADD_LAZY; 2 after HE_RGSW_MUL_LAZY; out.M + 2 after
+ * HE_RGSW_MUL_THEN_ADD_LAZY and after he_rgsw_key_add_plaintext_lazy (polynomial words lie in [0, 2q)).  M is kept up to 2^32;
+ * a key that reaches it has no known bound and both products refuse it until it is reduced.  The two products take
+ * such keys exactly where the reference's own arithmetic is exact with them, M the larger bound of the two gadget ciphertexts
+ * (of any key of the set in the select form), on both routes and with the words of the reference:
+ *  - bit-window branch (levelP < 1): every MRed(key, y) has y = NTTLazy(window) <= 6q - 2 (ring/ntt.go:133) and needs
+ *    key y < q 2^64: served when M q < 2^64 and (M q - 1)(6q - 2) < q 2^64 for every modulus of the product (the Q limbs up to
+ *    levelQ and the special prime), i.e. about M <= 2^64 / 6q: M <= 2 for q < 2^60, M = 1 only for a 61-bit prime;
+ *  - branch M (levelP >= 1): every MRedLazy(key, y) has y < 2q: served when M q < 2^64 and (M q - 1)(2q - 1) < q 2^64;
+ *  - 32-bit branch: the plain sum must not wrap: served when 2 D W (M q - 1) < 2^64 (D, W as above).
+ * Outside these bounds the reference's words depend on how its Montgomery products leave their domain and the call is HE_EINVAL
+ * before anything is filed: HE_RGSW_REDUCE the key first.
  */
 #ifndef HERING_RGSW_H
 #define HERING_RGSW_H

@@ -661,6 +661,10 @@ struct Evk : Obj {
     double *keyd = nullptr;      // plain key words as doubles for the limbs below 2^47 (fused NTT+MAC kernel): the blocks of d,
                                  // each row of 4096 / 8192 coefficients permuted for that kernel (launch_key_to_f64)
     uint64_t *d = nullptr;
+    // the key's words lie below word_mul * q: 1 for words as created or committed (canonical), raised by the lazy helpers of
+    // hering_rgsw.h and set back by HE_RGSW_REDUCE; saturates at kWordMulCap, which stands for "no bound is known"
+    uint64_t word_mul = 1;
+    static constexpr uint64_t kWordMulCap = (uint64_t)1 << 32;
     Evk() : Obj(T_EVK) {}
     // the key as a batch of 2 beta rows (digit d, component c at 2 d + c) of nQk + nPk limbs
     View rows() const { return View{d, (size_t)(nQk + nPk) * ev->be->Q->N}; }
@@ -2916,6 +2920,7 @@ int he_evk_commit(he_handle hk) {
     Scope sc(k->ev->be->ctx.get());
     if (int rc = evk_derive(*k)) return rc;
     HIP_TRY(hipStreamSynchronize(k->ev->be->ctx->stream));
+    k->word_mul = 1;  // (an external writer supplies canonical words, as he_evk_create's caller does)
     return HE_OK;
 }
 
@@ -3460,7 +3465,7 @@ int window_products_core(Evaluator &ev, int levelQ, View cx, int B, const Evk &k
     for (int i = 0; i <= levelQ; i++)
         for (int j = 0; j < rgsw_nj(k, i); j++) {
             m.blk_limb[m.nblk] = (uint8_t)i;
-            m.blk_shift[m.nblk] = (uint8_t)(j * k.pw2);  // < bits(q_i) <= 62
+            m.blk_shift[m.nblk] = (uint8_t)(j * k.pw2);  // <= 64 (he_evk_create_base2); 64: a window of zero
             m.nblk++;
         }
     HIP_TRY(launch_mask_spread(be.qp, m, inv, dec, bs, ds, B, st));
@@ -5044,6 +5049,32 @@ int rgsw_shape(const char *who, const Evaluator &ev, const Evk &a, const Evk &b,
     s->fused = ok;
     return HE_OK;
 }
+// Key words at or above q (hering_rgsw.h, "Key words"): served where the reference's own arithmetic is exact with words below
+// M q -- every MRed / MRedLazy(key, y) has key * y < q 2^64, y an NTTLazy word (at most 6q - 2) in the bit-window branch and a
+// word below 2q in branch M; the 32-bit branch's plain sum stays below 2^64 -- and refused elsewhere.
+int rgsw_key_words(const char *who, const Evaluator &ev, const Evk &a, const Evk &b, const RgswShape &s) {
+    const uint64_t M = std::max(a.word_mul, b.word_mul);
+    if (M <= 1) return HE_OK;  // (canonical keys: rgsw_shape has checked the 32-bit branch's bound)
+    if (M >= Evk::kWordMulCap)
+        return fail(HE_EINVAL, "%s: the key went through so many lazy helpers that no bound on its words is kept (HE_RGSW_REDUCE the key first)", who);
+    const BasisExtender &be = *ev.be;
+    const uint64_t q0 = be.Q->moduli[0];
+    if (s.levelQ == 0 && s.levelP == -1 && (q0 >> 29) == 0) {
+        const u128 bound = (u128)2 * (u128)a.nj[0] * (u128)(6 * q0 - 2) * (u128)(M * q0 - 1);  // M <= 2^32, q0 < 2^29
+        if ((bound >> 64) != 0)
+            return fail(HE_EINVAL, "%s: 2 D W (M q - 1) >= 2^64 with key words below M q, M = %llu (HE_RGSW_REDUCE the key first)",
+                        who, (unsigned long long)M);
+        return HE_OK;
+    }
+    for (int j = 0; j <= s.levelQ + s.levelP + 1; j++) {
+        const uint64_t q = j <= s.levelQ ? be.Q->moduli[j] : be.P->moduli[j - s.levelQ - 1];
+        const u128 kmax = (u128)M * q, ymax = s.multiple_p ? (u128)2 * q - 1 : (u128)6 * q - 2;
+        if ((kmax >> 64) != 0 || (kmax - 1) * ymax >= ((u128)q << 64))
+            return fail(HE_EINVAL, "%s: key words below M q, M = %llu, leave the domain of the reference's Montgomery products at q = %llu "
+                        "(HE_RGSW_REDUCE the key first)", who, (unsigned long long)M, (unsigned long long)q);
+    }
+    return HE_OK;
+}
 // what both routes account for: two GadgetProductLazy, the sum of their accumulators and ModDown (or the copy)
 void rgsw_account(Evaluator &ev, const Evk &k, const RgswShape &s, int B) {
     BasisExtender &be = *ev.be;
@@ -5142,6 +5173,7 @@ int he_rgsw_external_product(he_handle hev, he_handle in0, he_handle in1, he_han
     BasisExtender &be = *ev->be;
     RgswShape s;
     TRY(rgsw_shape(who, *ev, *k0, *k1, &s));
+    TRY(rgsw_key_words(who, *ev, *k0, *k1, s));
     static const bool no_fused = env_flag("HERING_NO_RGSW_FUSED");
     if (no_fused) s.fused = false;
     CoReq q;
@@ -5204,6 +5236,7 @@ int he_rgsw_external_product_select(he_handle hev, he_handle in0, he_handle in1,
     RgswShape s;
     TRY(rgsw_shape(who, *ev, *set->k0[0], *set->k1[0], &s));
     if (!s.fused) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_rgsw.h)", who);
+    for (size_t i = 0; i < set->k0.size(); i++) TRY(rgsw_key_words(who, *ev, *set->k0[i], *set->k1[i], s));
     if (!sel || n_sel < 1) return fail(HE_EINVAL, "%s: null selection", who);
     const int n = (int)set->k0.size();
     for (int b = 0; b < n_sel; b++)
@@ -5294,6 +5327,9 @@ int he_rgsw_key_op(int op, he_handle hin, he_handle hxQ, he_handle hxP, he_handl
     be.ctx->acct((op == HE_RGSW_REDUCE ? 2.0 : 3.0) * limbs, mul ? limbs : 0, rows, be.Q->N);
     if (mul) { Valu V(be.Q->logN); for (int j = 0; j < limbs; j++) V.mul(cls_f64(be.small, j < out->nQk ? j : be.LQ + j - out->nQk), 1.0); V.into(*be.ctx, rows); }
     const View none{nullptr, 0};
+    const uint64_t add = op == HE_RGSW_ADD_LAZY ? in->word_mul : 2;  // (MRedLazy returns words below 2q)
+    const uint64_t mul_after = op == HE_RGSW_REDUCE ? 1 : std::min(Evk::kWordMulCap, (op == HE_RGSW_MUL_LAZY ? 0 : out->word_mul) + add);
+    if (op != HE_RGSW_REDUCE) out->word_mul = std::max(out->word_mul, mul_after);  // (a launch that fails may have written some rows)
     switch (op) {
         case HE_RGSW_ADD_LAZY: TRY(key_rows_ew(*out, EW_ADD_LAZY, out->rows(), none, none, in->rows())); break;
         case HE_RGSW_REDUCE: TRY(key_rows_ew(*out, EW_REDUCE, in->rows(), none, none, in->rows())); break;
@@ -5301,6 +5337,7 @@ int he_rgsw_key_op(int op, he_handle hin, he_handle hxQ, he_handle hxP, he_handl
             TRY(key_rows_ew(*out, op == HE_RGSW_MUL_LAZY ? EW_MUL_MONT_LAZY : EW_MUL_MONT_LAZY_THEN_ADD_LAZY, in->rows(),
                             View{xQ->d, 0}, xP ? View{xP->d, 0} : none, none));
     }
+    out->word_mul = mul_after;  // (Reduce lowers the bound only once its launch has been made)
     return evk_derive(*out);  // (he_evk_commit's launches, in stream order)
 }
 int he_rgsw_key_add_plaintext_lazy(he_handle hpt, he_handle hk0, he_handle hk1) {
@@ -5318,6 +5355,8 @@ int he_rgsw_key_add_plaintext_lazy(he_handle hpt, he_handle hk0, he_handle hk1) 
     if (pt->ctx != be.ctx || pt->N != N || pt->nlimbs < nQ || pt->batch < maxj)
         return fail(HE_EINVAL, "%s: the plaintext holds one polynomial of %d limbs per window (%d windows)", who, nQ, maxj);
     const int digits = k0->pw2 ? nQ : k0->beta;
+    // (polynomial words lie in [0, 2q); raised before the launches: one that fails may have written some rows)
+    for (Evk *k : {k0.get(), k1.get()}) k->word_mul = std::min(Evk::kWordMulCap, k->word_mul + 2);
     Scope sc(be.ctx.get());
     hipStream_t st = be.ctx->stream;
     const size_t rs = (size_t)(k0->nQk + k0->nPk) * N;

@@ -3951,7 +3951,9 @@ __global__ void __launch_bounds__(256) mask_spread_kernel(MaskSpreadKArgs A) {
     if (x >= A.N) return;
     const int b = blockIdx.y;
     const size_t bz = blockIdx.z;
-    const uint64_t v = (A.src[bz * A.src_bs + (size_t)A.m.blk_limb[b] * A.N + x] >> A.m.blk_shift[b]) & A.m.mask;
+    // (a key may carry a window at shift 64, he_evk_create_base2: nj pw2 <= 64 + pw2; the reference's shift gives zero there)
+    const unsigned sh = A.m.blk_shift[b];
+    const uint64_t v = sh < 64 ? (A.src[bz * A.src_bs + (size_t)A.m.blk_limb[b] * A.N + x] >> sh) & A.m.mask : 0;
     uint64_t *dst = A.dec + bz * A.dec_bs + (size_t)b * A.dec_ds + x;
     for (int l = 0; l < A.m.ndst; l++) dst[(size_t)A.m.dst_limb[l] * A.N] = v;
 }
@@ -4538,17 +4540,23 @@ __global__ void __launch_bounds__((1 << LOGB) / 16) rgsw_fused_kernel(RgswKArgs 
             continue;
         }
         if (A.nP) {
-            // ModUpPtoQ of one residue: v -> v - p where v > (p - 1) / 2 (:203-207 around ModUpExact), then NTT and
-            // MRed(ext + 2q - acc, q - P^-1) (:249-255)
+            // ModUpPtoQ of one residue as the reference computes it (:195-210 around ModUpExact, :282-308): x = v + (p - 1) / 2
+            // mod p, w = uint64(float64(x) / float64(p)), lift = x - w p - (p - 1) / 2.  w is 1 only where x rounds to p as a
+            // double -- the residues just below (p - 1) / 2 of a prime above 2^53 -- and there the reference's word is that of
+            // v - p, not of v; everywhere else this is v > (p - 1) / 2 ? v - p : v.  Then NTT and MRed(ext + 2q - acc, q - P^-1)
+            // (:249-255)
             const uint64_t pmq = A.p_mod_q[u], sdn = A.md_s[u];
+            const uint64_t p = K.mc[A.p_mod].q, hq = bred_add(A.p_half, q, mc.brc0);
+            const double pd = __ull2double_rn(p);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 uint64_t y[16];
 #pragma unroll
                 for (int kk = 0; kk < 16; kk++) {
-                    const uint64_t v = ext[c][kk];
-                    const uint64_t r = bred_add(v, q, mc.brc0);
-                    y[kk] = v > A.p_half ? cred(r + q - pmq, q) : r;
+                    const uint64_t x = cred(ext[c][kk] + A.p_half, p);
+                    const uint64_t w = (uint64_t)__ddiv_rn(__ull2double_rn(x), pd);
+                    const uint64_t r = cred(bred_add(x, q, mc.brc0) + q - hq, q);
+                    y[kk] = w ? cred(r + q - pmq, q) : r;
                 }
                 __syncthreads();
                 rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);

@@ -42,8 +42,12 @@ HE_HD uint64_t mred(uint64_t x, uint64_t y, uint64_t q, uint64_t qinv) {
     return r >= q ? r - q : r;
 }
 // The same residue by two 32-bit reduction rounds (word-serial Montgomery, "CIOS"): x*y*2^-64 mod q in [0, 2q) for
-// q < 2^61 (the largest modulus the library accepts, as the reference), x + q < 2^64 (any lazy operand of the kernels: x < 4q)
-// and y < q.  gfx950 has no 64-bit multiplier; the full-width form
+// q < 2^61 (the largest modulus the library accepts, as the reference), x < 2^62 (any lazy operand of the kernels: x < 4q) and
+// x y < q 2^64 -- any y < q, and also a y at or above q while the product stays below q 2^64 (the RGSW kernel's key words after the
+// lazy helpers, hering_rgsw.h "Key words").  Why y may be any 64-bit word: with x1 = x >> 32 < 2^30 and q1 = q >> 32 < 2^29 every
+// partial sum below fits 64 bits -- u <= x1 y0 + 2^32 < 2^63, v <= m q1 + u + 2^32 < 2^64, a <= x0 y1 + 2^32 < 2^64,
+// b <= x1 y1 + 2^33 < 2^63, the result m q1 + b + 2^32 < 2^64 -- and the result is (x y + M q) / 2^64 with M < 2^64, below
+// x y / 2^64 + q < 2q.  gfx950 has no 64-bit multiplier; the full-width form
 // above costs 11 multiplies and ~15 carry / select instructions (a 64x64->128 product, a 64-bit low product and a 64x64 high
 // product), this one 8 v_mad_u64_u32 + 2 v_mul_lo_u32 + ~6 adds: the running sum never exceeds 96 bits and every partial
 // product is a 32x32+64 multiply-add.  m = -T q^-1 mod 2^64 is the same number either way (computed word by word here), so the

@@ -140,49 +140,127 @@ def takes_32bit_branch(ringQ: O.Ring, rgsw) -> bool:
     return rgsw[0].LevelQ() == 0 and rgsw[0].LevelP() == -1 and (int(ringQ.moduli[0]) >> 29) == 0
 
 
-def wrap_bound_holds(ringQ: O.Ring, rgsw) -> bool:
-    """2 D W (q - 1) < 2^64 with W = 6q - 2 the largest word of NTTLazy (ring/ntt.go:133): the 32-bit branch's sum cannot wrap"""
+def wrap_bound_holds(ringQ: O.Ring, rgsw, key_mul: int = 1) -> bool:
+    """2 D W (M q - 1) < 2^64 with W = 6q - 2 the largest word of NTTLazy (ring/ntt.go:133) and key words below M q (M = 1:
+    canonical keys): the 32-bit branch's sum cannot wrap"""
     q = int(ringQ.moduli[0])
-    return 2 * rgsw[0].q.shape[0] * (6 * q - 2) * (q - 1) < (1 << 64)
+    return 2 * rgsw[0].q.shape[0] * (6 * q - 2) * (key_mul * q - 1) < (1 << 64)
 
 
-def external_product(oev: O.Evaluator, ct: np.ndarray, rgsw, force_bit_decomp: bool = False) -> np.ndarray:
-    """ExternalProduct (:39-82) -> [2, levelQ + 1, N]; force_bit_decomp: take :66 where :60 would choose the 32-bit branch"""
+def key_words_in_domain(ringQ: O.Ring, ringP: O.Ring | None, rgsw, key_mul: int) -> bool:
+    """Whether the reference's arithmetic is exact with key words below M q (include/hering_rgsw.h, "Key words"): every
+    product MRed / MRedLazy(key, y) has key * y < q 2^64 -- y an NTTLazy word, at most 6q - 2, in the bit-window branch and a word
+    below 2q in branch M -- and the 32-bit branch's plain sum stays below 2^64."""
+    levelQ, levelP = rgsw[0].LevelQ(), rgsw[0].LevelP()
+    if levelP < 1 and takes_32bit_branch(ringQ, rgsw):
+        return wrap_bound_holds(ringQ, rgsw, key_mul)
+    mods = [int(q) for q in ringQ.moduli[: levelQ + 1]] + ([int(p) for p in ringP.moduli[: levelP + 1]] if levelP >= 0 else [])
+    ymax = (lambda q: 2 * q - 1) if levelP >= 1 else (lambda q: 6 * q - 2)
+    return all(key_mul * q < (1 << 64) and (key_mul * q - 1) * ymax(q) < (q << 64) for q in mods)
+
+
+def external_product(oev: O.Evaluator, ct: np.ndarray, rgsw, force_bit_decomp: bool = False, with_p_coeffs: bool = False):
+    """ExternalProduct (:39-82) -> [2, levelQ + 1, N]; force_bit_decomp: take :66 where :60 would choose the 32-bit branch.
+    with_p_coeffs: -> (product, [2, levelP + 1, N]) with the coefficients of the P accumulator, the residues ModDown lifts
+    (INTT of the accumulator's P part, ring/basis_extension.go:247); levelP >= 0 only."""
     ringQ, ringP = oev.ringQ, oev.ringP
     levelQ, levelP = rgsw[0].LevelQ(), rgsw[0].LevelP()
+    assert levelP >= 0 or not with_p_coeffs
     if levelP < 1:
         if takes_32bit_branch(ringQ, rgsw) and not force_bit_decomp:
             return external_product_32bit(ringQ, ct, rgsw)
         cQ, cP = external_product_bit_decomp(ringQ, ringP, ct, rgsw)
-        if levelP == 0:
-            be = O.BasisExtender(ringQ, ringP)
-            return np.stack([be.ModDownQPtoQNTT(levelQ, levelP, cQ[c], cP[c]) for c in range(2)])
-        return cQ.copy()
-    cQ, cP = external_product_multiple_p(oev, ct, rgsw)
+        if levelP < 0:
+            return cQ.copy()
+    else:
+        cQ, cP = external_product_multiple_p(oev, ct, rgsw)
     be = O.BasisExtender(ringQ, ringP)
-    return np.stack([be.ModDownQPtoQNTT(levelQ, levelP, cQ[c], cP[c]) for c in range(2)])
+    out = np.stack([be.ModDownQPtoQNTT(levelQ, levelP, cQ[c], cP[c]) for c in range(2)])
+    if with_p_coeffs:
+        subP = _at(ringP, 0, levelP + 1)
+        return out, np.stack([subP.INTT(cP[c]) for c in range(2)])
+    return out
 
 
-def uniform_rgsw(rng, ringQ: O.Ring, ringP: O.Ring | None, pw2: int, rns_p: bool = False):
+def window_counts(moduli, pw2: int):
+    """BaseTwoDecompositionVectorSize of the reference's NewCiphertext: ceil(bits(q_i) / pw2) windows of limb i"""
+    return [(int(q).bit_length() + pw2 - 1) // pw2 for q in moduli]
+
+
+def row_words(kind_of, rng, moduli, N, D):
+    """[D, 2, limbs, N] key words: kind_of(rng, moduli, N) -> [limbs, N] is called once per (digit, component) row"""
+    return np.stack([np.stack([kind_of(rng, moduli, N) for _c in range(2)]) for _d in range(D)])
+
+
+def uniform_rgsw(rng, ringQ: O.Ring, ringP: O.Ring | None, pw2: int, rns_p: bool = False, levelQ: int | None = None, nj=None,
+                 words=None):
     """Two uniformly random gadget ciphertexts of the shape the reference's NewCiphertext gives: pw2 > 0 -- bit windows, one
-    digit per Q limb; pw2 == 0 -- RNS digits (one uncentred window per limb where there is a single special prime)."""
+    digit per Q limb; pw2 == 0 -- RNS digits (one uncentred window per limb where there is a single special prime).
+    levelQ: keys of limbs 0..levelQ of ringQ (NewCiphertext(params, levelQ, levelP, ...) below the ring's top level).
+    nj: window counts other than the reference's (a key may carry more windows than its limb has bits: the upper ones are
+    windows of zero).  words(rng, moduli, N) -> [limbs, N]: another source of key words than the uniform one."""
     N = ringQ.N
-    LQ, LP = len(ringQ.moduli), (len(ringP.moduli) if ringP is not None else 0)
+    qmods = list(ringQ.moduli) if levelQ is None else list(ringQ.moduli[: levelQ + 1])
+    LQ, LP = len(qmods), (len(ringP.moduli) if ringP is not None else 0)
     if pw2:
-        nj = [(int(q).bit_length() + pw2 - 1) // pw2 for q in ringQ.moduli]
+        nj = list(nj) if nj is not None else window_counts(qmods, pw2)
+        assert len(nj) == LQ
         D = sum(nj)
     else:
         nj = None
         D = O.BaseRNSDecompositionVectorSize(LQ - 1, LP - 1)
     out = []
+    if words is not None:
+        for _ in range(2):
+            kq = row_words(words, rng, qmods, N, D)
+            kp = row_words(words, rng, list(ringP.moduli), N, D) if LP else np.zeros((D, 2, 0, N), dtype=U64)
+            out.append(O.EvaluationKey(kq, kp, pw2=pw2, nj=nj))
+        return out
     for _ in range(2):
-        kq = np.stack([np.stack([np.stack([rng.integers(0, int(q), size=N, dtype=U64) for q in ringQ.moduli]) for _c in range(2)]) for _d in range(D)])
+        kq = np.stack([np.stack([np.stack([rng.integers(0, int(q), size=N, dtype=U64) for q in qmods]) for _c in range(2)]) for _d in range(D)])
         if LP:
             kp = np.stack([np.stack([np.stack([rng.integers(0, int(q), size=N, dtype=U64) for q in ringP.moduli]) for _c in range(2)]) for _d in range(D)])
         else:
             kp = np.zeros((D, 2, 0, N), dtype=U64)
         out.append(O.EvaluationKey(kq, kp, pw2=pw2, nj=nj))
     return out
+
+
+LIFT_TARGETS = ("(p-1)/2", "(p+1)/2", "0", "p-1")
+
+
+def lift_targets(p: int, N: int) -> np.ndarray:
+    """N residues mod p cycling through (p - 1) / 2, (p + 1) / 2, 0 and p - 1: the two sides of ModDown's centred lift
+    (v > (p - 1) / 2 ? v - p : v) and the ends of the range"""
+    p = int(p)
+    return np.array([((p - 1) // 2, (p + 1) // 2, 0, p - 1)[i % 4] for i in range(N)], dtype=U64)
+
+
+def planted_rgsw(rng, ringQ: O.Ring, ringP: O.Ring, pw2: int, component: int, levelQ: int | None = None):
+    """An RGSW pair whose product with (NTT(1), 0) has lift_targets(p, N) as the coefficients of output component `component`'s P
+    accumulator (and zero as the other's): every P row is zero except digit 0 of rgsw[0], component `component`, which holds
+    MForm(NTT_p(targets)); the Q rows are uniform.  Window 0 of limb 0 of INTT(NTT(1)) = 1 is the constant 1, whose transform is
+    all ones, so that row enters the accumulator as it stands; every other window is zero or meets a zero P row."""
+    assert ringP is not None and len(ringP.moduli) == 1
+    out = uniform_rgsw(rng, ringQ, ringP, pw2, levelQ=levelQ)
+    for k in out:
+        k.p[...] = 0
+    t = lift_targets(ringP.moduli[0], ringQ.N)[None, :]
+    out[0].p[0, component] = ringP.unop("MForm", ringP.NTT(t))
+    return [O.EvaluationKey(k.q, k.p, pw2=pw2, nj=k.nj if pw2 else None) for k in out]
+
+
+def ntt_of_one(ringQ: O.Ring, nlimbs: int) -> np.ndarray:
+    """NTT(1): the constant polynomial 1 is all ones in every limb"""
+    return np.ones((nlimbs, ringQ.N), dtype=U64)
+
+
+def all_mask_coeffs(q: int, pw2: int, N: int) -> np.ndarray:
+    """The largest coefficient below q whose windows of pw2 bits are all equal to the mask, except the top one, which is what q
+    leaves of it (t - 1 with t = q >> (nj - 1) pw2 the top window of q itself)"""
+    q = int(q)
+    s = ((q.bit_length() + pw2 - 1) // pw2 - 1) * pw2
+    return np.full(N, ((q >> s) << s) - 1, dtype=U64)
 
 
 # ---- the helpers of :283-356 on pairs of oracle keys; every function returns new keys ------------------------------------------------

@@ -60,6 +60,18 @@ def test_rescale_chains_meet_every_class_pair():
     assert seen == {(a, b) for a in range(3) for b in range(3)}
 
 
+@pytest.mark.parametrize("logN", [9, 10, 11, 12])
+def test_class_chain_builds_at_the_small_rings_of_the_rgsw_edge_tests(logN):
+    """every letter, twice over (a Q chain and a special prime of the same kind), with class_chain's own class and distance
+    assertions; the 14-bit prime 12289 is NTT-friendly up to logN 11"""
+    for letter in "dihDI":
+        q = Bd.class_chain(logN, letter * 2)
+        assert q[1:] == Bd.class_chain(logN, letter, skip={letter: 1})
+        above = letter.isupper()
+        assert all((m >= (1 << Bd._LETTERS[letter][0])) == above and m % (2 << logN) == 1 for m in q)
+    assert (12289 % (2 << logN) == 1) == (logN <= 11) and O.IsPrime(12289)
+
+
 def test_class_chain_rejects_a_prime_too_far_from_its_boundary():
     with pytest.raises(AssertionError):
         Bd.class_chain(17, "d" * 40)  # forty primes = 1 mod 2^18 below 2^47 span more than 2^27

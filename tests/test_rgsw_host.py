@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import boundary as Bd
+from tests import rgsw_edges as E
 from tests import rgsw_ref as R
 from tests.helpers import prod, rng_for, uniform_poly
 from tests.rlwe_fixtures import (SecretKey, bfv_encrypt, gen_evaluation_key, gen_evaluation_key_base2, negacyclic_mul_mod, phase,
@@ -251,6 +253,161 @@ def test_wire_is_two_gadget_ciphertexts_back_to_back(logp, pw2):
         wire.rgsw_ciphertext_unmarshal(buf + b"\0")
     with pytest.raises(ValueError):
         wire.rgsw_ciphertext_unmarshal(buf[:-8])
+
+
+# ---- the constructions of tests/test_gpu_rgsw_edges.py: each has the property it is built for --------------------------------------
+def _oracle(s):
+    N = 1 << s["logN"]
+    oQ, oP = O.Ring(N, s["q"]), (O.Ring(N, s["p"]) if s["p"] else None)
+    return N, oQ, oP, O.Evaluator(oQ, oP)
+
+
+@pytest.mark.parametrize("name", sorted(E.lift_shapes()))
+def test_planted_keys_put_the_lift_boundary_into_the_p_accumulator(name):
+    s = E.lift_shapes()[name]
+    N, oQ, oP, oev = _oracle(s)
+    p = s["p"][0]
+    if "below-q" in name:
+        assert all(p < q for q in s["q"])
+    if "between" in name:
+        assert min(s["q"]) < p < max(s["q"])
+    if "p61" in name:
+        assert p == Bd.primes_below(61, s["logN"] + 1, 1)[0]
+    ct = np.stack([R.ntt_of_one(oQ, len(s["q"])), np.zeros((len(s["q"]), N), dtype=np.uint64)])
+    for component in range(2):
+        keys = R.planted_rgsw(rng_for(7500 + component), oQ, oP, s["pw2"], component)
+        out, pc = R.external_product(oev, ct, keys, with_p_coeffs=True)
+        assert not pc[1 - component].any()
+        seen = {int(v) for v in pc[component, 0]}
+        assert seen == {(p - 1) // 2, (p + 1) // 2, 0, p - 1}, "a planted residue does not occur"
+        assert [int(v) for v in pc[component, 0, :4]] == [(p - 1) // 2, (p + 1) // 2, 0, p - 1]
+        # the lift decides the product: with the boundary moved by one ((p - 1) / 2 lifted to (p - 1) / 2 - p) words change
+        be = O.BasisExtender(oQ, oP)
+        zero = np.zeros_like(out[component])
+        shifted = pc[component].copy()
+        shifted[0, 0] = (p + 1) // 2
+        a = be.ModDownQPtoQNTT(len(s["q"]) - 1, 0, zero, oP.NTT(pc[component]))
+        b = be.ModDownQPtoQNTT(len(s["q"]) - 1, 0, zero, oP.NTT(shifted))
+        assert not np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("name", sorted(E.lift_shapes()))
+def test_reference_lift_follows_its_float_quotient(name):
+    """ModUpPtoQ of one residue (ring/basis_extension.go:195-210 around ModUpExact, :282-308): x = v + (p - 1) / 2 mod p,
+    w = uint64(float64(x) / float64(p)), lift = x - w p - (p - 1) / 2.  Below 2^53 that is v > (p - 1) / 2 ? v - p : v; for the
+    61-bit prime float64(x) rounds to float64(p) within 128 of p, so (p - 1) / 2 itself and its neighbours below it are lifted to
+    v - p: the planted residue (p - 1) / 2 tells the two apart."""
+    s = E.lift_shapes()[name]
+    N, oQ, oP, _ = _oracle(s)
+    p, half = s["p"][0], (s["p"][0] - 1) // 2
+    v = R.lift_targets(p, N)
+    v[4:12] = [(half - k) % p for k in (1, 2, 64, 127, 128, 129, 300, 1 << 20)]
+    got = O.BasisExtender(oQ, oP).ModUpPtoQ(0, len(s["q"]) - 1, v[None])
+    w = [int(float((int(x) + half) % p) / float(p)) for x in v]
+    for i, q in enumerate(s["q"]):
+        assert [int(x) for x in got[i]] == [((int(x) + half) % p - wi * p - half) % q for x, wi in zip(v, w)]
+    plain = [int(int(x) > half) for x in v]
+    if "p61" in name:
+        assert w[0] == 1 and plain[0] == 0 and w[1:4] == [0, 0, 0] and w[4:8] == [1, 1, 1, 1] and w[10:12] == [0, 0]
+    else:
+        assert not any(w)
+
+
+@pytest.mark.parametrize("pw2", [7, 13, 14])
+def test_all_mask_coefficients_have_every_window_equal_to_the_mask(pw2):
+    mask = (1 << pw2) - 1
+    for q in Bd.class_chain(9, "hiIdD") + [E.Q14]:
+        c = R.all_mask_coeffs(q, pw2, 8)
+        nj = R.window_counts([q], pw2)[0]
+        w = [int(R.mask_vec(c, j * pw2, mask)[0]) for j in range(nj)]
+        assert int(c[0]) < q and all(x == mask for x in w[:-1]) and w[-1] == (q >> ((nj - 1) * pw2)) - 1
+    mods = [E.Q14, Bd.primes_below(47, 10, 1)[0]]
+    assert [int(v) for v in E.coeffs("coeff_max", mods, 4, pw2)[:, 0]] == [m - 1 for m in mods]
+    assert not E.coeffs("coeff_zero", mods, 4, pw2).any()
+    # the cycle of ciphertext words reaches every kind in ten polynomials, lazy words up to 2q - 1 included
+    ring = O.Ring(64, O.GenModuli(LOG_NTH, [35, 20], [])[0])
+    cyc = E.CtCycle(ring, pw2, start=5)
+    polys = [cyc(rng_for(7600), ring.moduli, 64) for _ in range(10)]
+    assert max(int(x[0].max()) for x in polys) == 2 * int(ring.moduli[0]) - 1
+    want = ring.NTT(E.coeffs("coeff_mask", ring.moduli, 64, pw2))
+    assert any(np.array_equal(x, want) for x in polys) and any(not x.any() for x in polys)
+
+
+def test_digit_index_shapes():
+    sh = E.digit_index_shapes()
+    nj = {k: R.window_counts(v["q"], 1) for k, v in sh.items()}
+    assert sum(nj["beta255"]) == 255 and E.fused_by_header(9, len(sh["beta255"]["q"]), 0)
+    assert sum(nj["prefix255"][:-1]) == 255 and sum(nj["prefix256"][:-1]) >= 256   # prefix[levelQ]
+    assert all(E.fused_by_header(9, len(sh[k]["q"]), 0) for k in ("prefix255", "prefix256"))
+    for v in sh.values():
+        assert len(set(v["q"])) == len(v["q"]) and all(O.IsPrime(q) and q % 1024 == 1 for q in v["q"])
+
+
+def test_shift_and_domain_shapes_lie_where_the_header_says():
+    for s in E.shift_shapes().values():
+        last = (s["nj"][0] - 1) * s["pw2"]
+        assert last in (63, 64) and (last < 64) == (s["route"] == E.ONE) and s["nj"][0] * s["pw2"] <= 64 + s["pw2"]
+    dom = E.domain_shapes()
+    for s in dom.values():
+        assert (s["route"] == E.ONE) == E.fused_by_header(s["logN"], len(s["q"]), len(s["p"]))
+    assert [len(dom[k]["q"]) for k in ("9x7+P", "9x8+P", "10x3+P", "10x3", "10x4+P", "11x1+P", "11x2+P")] == [7, 8, 3, 3, 4, 1, 2]
+    assert dom["9x8+P"]["q"][:7] == dom["9x7+P"]["q"] and dom["10x4+P"]["q"][:3] == dom["10x3+P"]["q"]
+    for name, s in E.moduli_shapes().items():
+        assert (s["route"] == E.ONE) == (E.fused_by_header(s["logN"], len(s["q"]), len(s["p"])))
+        assert len(set(s["q"] + s["p"])) == len(s["q"] + s["p"])
+    m = E.moduli_shapes()
+    assert {Bd.modulus_class(q) for q in m["12-dihDI|i"]["q"]} == {0, 1, 2} and len(m["12-dihd|ih"]["p"]) == 2
+    big = [q for q in m["9-hiIdD+14|h-pw2-14"]["q"] + m["9-hiIdD+14|h-pw2-14"]["p"] if q <= (1 << 14) - 1]
+    assert big == [E.Q14] and E.Q14 > (1 << 13) - 1
+
+
+@pytest.mark.parametrize("name", ["9-hiIdD+14|h-pw2-16", "9-hiIdD+14|h-all-ones"])
+def test_windows_exceed_the_transform_input_bound_of_one_destination(name):
+    """the forward transform of the one-launch kernel takes words below 4q: with a 16-bit mask (and with the all-ones mask) the
+    windows of the worst-case coefficients reach 4 * 12289 and beyond, so the 14-bit destination depends on the reduction before
+    the transform; the 16-bit mask stays below every other modulus of the chain"""
+    s = E.moduli_shapes()[name]
+    mask = (1 << s["pw2"]) - 1 if s["pw2"] else (1 << 64) - 1
+    assert mask >= 4 * E.Q14
+    if s["pw2"]:
+        assert [mask >= m for m in s["q"] + s["p"]].count(True) == 1 and all(mask < m for m in s["q"] + s["p"] if m != E.Q14)
+    nj = R.window_counts(s["q"], s["pw2"]) if s["pw2"] else [1] * len(s["q"])
+    for kind in ("coeff_max", "coeff_mask"):
+        c = E.coeffs(kind, s["q"], 4, s["pw2"])
+        w = [int(R.mask_vec(c[i], j * s["pw2"], mask)[0]) for i in range(len(s["q"])) for j in range(nj[i])]
+        assert sum(x >= 4 * E.Q14 for x in w) >= 4, (kind, w)   # (several source limbs have such a window)
+        assert s["pw2"] or max(w) >> 60 == 1                     # (all-ones: a whole 61-bit coefficient)
+
+
+@pytest.mark.parametrize("pw2", range(1, 9))
+def test_wrap_bound_sides(pw2):
+    lo, hi = E.wrap_primes()
+    assert lo < hi < (1 << 29) and (1 << 28) < lo and all(O.IsPrime(q) and q % 2048 == 1 for q in (lo, hi))
+    for side, q in enumerate((lo, hi)):
+        ringQ = O.Ring(1024, [q])
+        keys = R.uniform_rgsw(rng_for(7700), ringQ, None, pw2)
+        assert R.takes_32bit_branch(ringQ, keys) and keys[0].q.shape[0] == (29 + pw2 - 1) // pw2
+        assert R.wrap_bound_holds(ringQ, keys) == (pw2 >= 4 or (pw2 == 3 and side == 0)), (q, pw2)
+
+
+def test_key_words_domain_and_lazy_keys_on_the_oracle():
+    """hering_rgsw.h, "Key words": inside the bound the reference's product with a key after AddLazy is the product with the
+    reduced key (its Montgomery products stay exact); a 61-bit modulus leaves no room for M = 2"""
+    for logq, logp, pw2 in (((35, 20), (55,), 7), ((35, 20), (55, 60), 0), ((27,), (), 7)):
+        ringQ, ringP = _rings(logq, logp)
+        oev = O.Evaluator(ringQ, ringP)
+        rng = rng_for(7800 + pw2 + len(logp))
+        a, b = R.uniform_rgsw(rng, ringQ, ringP, pw2), R.uniform_rgsw(rng, ringQ, ringP, pw2)
+        lazy = R.add_lazy_ciphertext(ringQ, ringP, a, b)
+        assert any(int(k.q[:, :, 0].max()) >= ringQ.moduli[0] for k in lazy)
+        assert R.key_words_in_domain(ringQ, ringP, lazy, 2)
+        ct = _ct(rng, ringQ)
+        assert np.array_equal(R.external_product(oev, ct, lazy), R.external_product(oev, ct, R.reduce(ringQ, ringP, lazy, lazy)))
+    ringQ, ringP = _rings((35, 20), (61,))
+    keys = R.uniform_rgsw(rng_for(7810), ringQ, ringP, 7)
+    assert R.key_words_in_domain(ringQ, ringP, keys, 1) and not R.key_words_in_domain(ringQ, ringP, keys, 2)
+    p = int(ringP.moduli[0])
+    assert (2 * p - 1) * (6 * p - 2) >= (p << 64)
 
 
 # ---- the boundary's host side --------------------------------------------------------------------------------------------
