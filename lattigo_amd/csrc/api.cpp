@@ -43,6 +43,7 @@
 #include "../../include/hering_rgsw.h"
 #include "host_math.h"
 #include "kernels.h"
+#include "ks_route.h"
 
 using namespace he;
 
@@ -2930,13 +2931,48 @@ int base_rns_size(int levelQ, int levelP) { return levelP == -1 ? levelQ + 1 : (
 // digits of a gadget product with key k at levelQ (a base-2 gadget: the bit windows of limbs 0..levelQ)
 int key_beta(const Evk &k, int levelQ) { return k.pw2 ? k.prefix[levelQ + 1] : base_rns_size(levelQ, k.nPk - 1); }
 
+// The limbs of a QP element at (levelQ, levelP) in the order every launch table lists them: Q limbs 0..levelQ, then P limbs
+// 0..levelP.  idx: the limb within its ring; mod: its row of the extender's constant tables.  cls: 0 every limb, 1 those NOT
+// of the double-precision class (class 2), 2 that class only.  Q limbs [own0, own1) -- a digit's own -- are left out.
+struct QPLimb {
+    uint8_t idx, mod;
+    bool isP;
+};
+int qp_limbs(const BasisExtender &be, int levelQ, int levelP, int cls, QPLimb *out, int own0 = 0, int own1 = 0) {
+    int n = 0;
+    for (int j = 0; j <= levelQ + levelP + 1; j++) {
+        const bool isP = j > levelQ;
+        const int idx = isP ? j - levelQ - 1 : j, mod = isP ? be.LQ + idx : idx;
+        if (!isP && j >= own0 && j < own1) continue;
+        if (cls && (be.small[mod] == 2) != (cls == 2)) continue;
+        out[n++] = QPLimb{(uint8_t)idx, (uint8_t)mod, isP};
+    }
+    return n;
+}
+// ... as the limb tables of the two key inner products (KsArgs, NttMacArgs): digit limb, key limb, output limb and view
+extern "C++" template <class A>
+void key_product_limbs(A &a, const BasisExtender &be, const Evk &k, int levelQ, int levelP, int cls) {
+    QPLimb l[kMaxLimbs];
+    a.nlimbs = qp_limbs(be, levelQ, levelP, cls, l);
+    for (int n = 0; n < a.nlimbs; n++) {
+        a.dec_limb[n] = l[n].mod; a.key_limb[n] = (uint8_t)(l[n].isP ? k.nQk + l[n].idx : l[n].idx); a.out_limb[n] = l[n].idx;
+        a.out_view[n] = l[n].isP ? 1 : 0; a.mod[n] = l[n].mod;
+    }
+}
+// g^-1 mod 2N of an odd Galois element: the index the scattering stores use (NttEpilogue::scatter_ginv, KsScatter::ginv)
+uint32_t galois_inverse(uint64_t gal, int logN) {
+    const uint64_t mask = (2ull << logN) - 1;
+    uint64_t x = gal & mask;
+    for (int i = 0; i < 6; i++) x = (x * (2 - gal * x)) & mask;  // Newton
+    return (uint32_t)x;
+}
+
 // DecomposeAndSplit for one digit (ring/basis_extension.go:381-502): coefficient-domain src
 // (limbs of ringQ) -> dstQ limbs (dstQ_limb0 + j) and dstP limbs (dstP_limb0 + j).
 // own_too: for single-limb digits the reference also rewrites the digit's own limb.
 int decompose_digit(Evaluator &ev, int levelQ, int levelP, int nbPi, int digit, View src, View dstQ, int dstQ_limb0, View dstP,
                     int dstP_limb0, int batch) {
     BasisExtender &be = *ev.be;
-    const int LQ = be.LQ;
     const int st = digit * nbPi;
     int ed = st + nbPi;
     if (ed > levelQ + 1) ed = levelQ + 1;
@@ -2945,21 +2981,15 @@ int decompose_digit(Evaluator &ev, int levelQ, int levelP, int nbPi, int digit, 
     if (levelQ > nbPi * (digit + 1) - 1) decompLvl = nbPi - 2;
     else decompLvl = (levelQ % nbPi) - 1;
     ModUpArgs a{};
-    int n = 0;
     const bool single = decompLvl < 0;
     std::vector<uint64_t> basis(be.Q->moduli.begin() + st, be.Q->moduli.begin() + ed);
-    for (int j = 0; j <= levelQ; j++) {
-        if (!single && j >= st && j < ed) continue;
-        a.dst_limb[n] = (uint8_t)(dstQ_limb0 + j); a.dst_mod[n] = (uint8_t)j; a.dst_row[n] = (uint8_t)j; a.dst_view[n] = 0;
-        a.dst_half[n] = single ? 0 : half_product_mod(basis, be.Q->moduli[j]);
-        n++;
+    QPLimb l[kMaxLimbs];
+    a.ndst = qp_limbs(be, levelQ, levelP, 0, l, single ? 0 : st, single ? 0 : ed);
+    for (int n = 0; n < a.ndst; n++) {
+        a.dst_limb[n] = (uint8_t)((l[n].isP ? dstP_limb0 : dstQ_limb0) + l[n].idx); a.dst_mod[n] = a.dst_row[n] = l[n].mod;
+        a.dst_view[n] = l[n].isP ? 1 : 0;
+        a.dst_half[n] = single ? 0 : half_product_mod(basis, be.modulus(l[n].mod));
     }
-    for (int j = 0; j <= levelP; j++) {
-        a.dst_limb[n] = (uint8_t)(dstP_limb0 + j); a.dst_mod[n] = (uint8_t)(LQ + j); a.dst_row[n] = (uint8_t)(LQ + j); a.dst_view[n] = 1;
-        a.dst_half[n] = single ? 0 : half_product_mod(basis, be.P->moduli[j]);
-        n++;
-    }
-    a.ndst = n;
     if (single) {
         a.nsrc = 1; a.src_limb[0] = (uint8_t)st; a.src_mod[0] = (uint8_t)st;
         HIP_TRY(launch_center_copy(be.qp, a, src, dstQ, dstP, batch, be.ctx->stream));
@@ -2990,16 +3020,9 @@ int decompose_ntt_into(Evaluator &ev, int levelQ, int levelP, int nbPi, View c2n
         TRY(decompose_digit(ev, levelQ, levelP, nbPi, d, c2inv, blk, 0, blk, LQ, batch));
         const int s0 = d * nbPi, e0 = std::min(s0 + nbPi, levelQ + 1);
         LimbTab t;  // NTT of every limb except the digit's own
-        t.n = 0;
-        for (int j = 0; j <= levelQ; j++) {
-            if (j >= s0 && j < e0) continue;
-            t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)j;
-            t.n++;
-        }
-        for (int j = 0; j <= levelP; j++) {
-            t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)(LQ + j);
-            t.n++;
-        }
+        QPLimb l[kMaxLimbs];
+        t.n = qp_limbs(be, levelQ, levelP, 0, l, s0, e0);
+        for (int i = 0; i < t.n; i++) t.in_limb[i] = t.out_limb[i] = t.mod[i] = l[i].mod;
         const bool red = modup_out_needs_reduce(std::vector<uint64_t>(be.Q->moduli.begin() + s0, be.Q->moduli.begin() + e0));
         HIP_TRY(be_ntt(be, t, blk, blk, batch, false, red ? NTT_REDUCE_INPUT : 0));
         // own limbs: copy of the NTT-domain input                         evaluator_gadget_product.go:498-503
@@ -3014,7 +3037,7 @@ int ks_inner(Evaluator &ev, int levelQ, int levelP, View dec, size_t dec_ds, con
              View o0P, View o1Q, View o1P, int batch, const View *own = nullptr, int own_alpha = 0, int limb_filter = 0,
              int digit_begin = 0, int digit_end = -1, const KsScatter *scatter = nullptr) {
     BasisExtender &be = *ev.be;
-    const int LQ = be.LQ, N = be.Q->N;
+    const int N = be.Q->N;
     KsArgs a{};
     a.beta = key_beta(k, levelQ);
     if (a.beta > k.beta) return fail(HE_EINVAL, "gadget product: key has %d digits, %d needed", k.beta, a.beta);
@@ -3025,17 +3048,8 @@ int ks_inner(Evaluator &ev, int levelQ, int levelP, View dec, size_t dec_ds, con
         keyp += (size_t)digit_begin * 2 * (size_t)(k.nQk + k.nPk) * N;
         a.beta = digit_end - digit_begin;
     }
-    int n = 0;
-    for (int j = 0; j <= levelQ; j++) {
-        if (limb_filter == 1 && be.small[j] == 2) continue;
-        a.dec_limb[n] = (uint8_t)j; a.key_limb[n] = (uint8_t)j; a.out_limb[n] = (uint8_t)j; a.out_view[n] = 0; a.mod[n] = (uint8_t)j; n++;
-    }
-    for (int j = 0; j <= levelP; j++) {
-        if (limb_filter == 1 && be.small[LQ + j] == 2) continue;
-        a.dec_limb[n] = (uint8_t)(LQ + j); a.key_limb[n] = (uint8_t)(k.nQk + j); a.out_limb[n] = (uint8_t)j; a.out_view[n] = 1;
-        a.mod[n] = (uint8_t)(LQ + j); n++;
-    }
-    a.nlimbs = n;
+    key_product_limbs(a, be, k, levelQ, levelP, limb_filter);
+    const int n = a.nlimbs;
     a.dec_dstride = dec_ds;
     a.key_kstride = (size_t)(k.nQk + k.nPk) * N;
     a.key_dstride = 2 * a.key_kstride;
@@ -3074,6 +3088,14 @@ void mark_fast_destinations(const BasisExtender &be, ModUpDesc &D, const std::ve
         D.dst_fast[j] = !lean ? 0 : ((p >> 58) == 0 && D.nsrc + 1 <= 15 && (colsum >> 64) == 0) ? (HE_MODUP_R60 && r60 ? 3 : 1) : 2;
     }
 }
+// the constants of one basis extension, as a fused descriptor holds them
+void desc_constants(ModUpDesc &D, const ModUpRef &ref, const ConstPool &pool, const std::vector<uint64_t> &basis) {
+    const ModUpDev c = ref.on(pool);
+    D.a = c.a; D.T = c.T; D.vt = c.vt;
+    D.Td = ref.Td_on(pool); D.vtd = ref.vtd_on(pool);
+    D.fc = ref.fc_on(pool); D.t60 = ref.t60_on(pool);
+    D.reduce_out = modup_out_needs_reduce(basis) ? 1 : 0;
+}
 int upload_plan(Evaluator &ev, const std::vector<ModUpDesc> &descs, FusedPlan &plan) {
     plan.ok = !descs.empty();
     for (const ModUpDesc &d : descs)
@@ -3103,7 +3125,7 @@ int get_dec_plan(Evaluator &ev, int levelQ, int levelP, int nbPi, const FusedPla
     auto it = ev.dec_plans.find(key);
     if (it != ev.dec_plans.end()) { *out = &it->second; return HE_OK; }
     BasisExtender &be = *ev.be;
-    const int LQ = be.LQ, width = be.LQ + be.LP, N = be.Q->N;
+    const int width = be.LQ + be.LP, N = be.Q->N;
     const int beta = base_rns_size(levelQ, levelP);
     std::vector<ModUpDesc> descs;
     bool ok = true;
@@ -3121,11 +3143,7 @@ int get_dec_plan(Evaluator &ev, int levelQ, int levelP, int nbPi, const FusedPla
             if (nbPi < 2 || nbPi - 2 >= (int)ev.dec.size() || d >= (int)ev.dec[nbPi - 2].size() ||
                 decompLvl >= (int)ev.dec[nbPi - 2][d].size()) { ok = false; break; }
             const ModUpRef &ref = ev.dec[nbPi - 2][d][decompLvl];
-            const ModUpDev c = ref.on(ev.pool);
-            D.a = c.a; D.T = c.T; D.vt = c.vt;
-            D.Td = ref.Td_on(ev.pool); D.vtd = ref.vtd_on(ev.pool);
-            D.fc = ref.fc_on(ev.pool); D.t60 = ref.t60_on(ev.pool);
-            D.reduce_out = modup_out_needs_reduce(basis) ? 1 : 0;
+            desc_constants(D, ref, ev.pool, basis);
         }
         for (int i = 0; i < D.nsrc; i++) {
             D.src_limb[i] = (uint8_t)(st + i); D.src_mod[i] = (uint8_t)(st + i);
@@ -3133,19 +3151,12 @@ int get_dec_plan(Evaluator &ev, int levelQ, int levelP, int nbPi, const FusedPla
             D.src_split[i] = (be.Q->moduli[st + i] >> 51) ? 1 : 0;
         }
         D.dst_off = (size_t)d * width * N;
-        int n = 0;
-        for (int j = 0; j <= levelQ; j++) {
-            if (j >= st && j < ed) continue;  // own limbs come from the NTT-domain input
-            D.dst_limb[n] = (uint8_t)j; D.dst_mod[n] = (uint8_t)j; D.dst_row[n] = (uint8_t)j; D.dst_view[n] = 0;
-            D.dst_half[n] = D.single ? 0 : half_product_mod(basis, be.Q->moduli[j]);
-            n++;
+        QPLimb l[kMaxLimbs];
+        D.ndst = qp_limbs(be, levelQ, levelP, 0, l, st, ed);  // own limbs come from the NTT-domain input
+        for (int n = 0; n < D.ndst; n++) {
+            D.dst_limb[n] = D.dst_mod[n] = D.dst_row[n] = l[n].mod; D.dst_view[n] = 0;
+            D.dst_half[n] = D.single ? 0 : half_product_mod(basis, be.modulus(l[n].mod));
         }
-        for (int j = 0; j <= levelP; j++) {
-            D.dst_limb[n] = (uint8_t)(LQ + j); D.dst_mod[n] = (uint8_t)(LQ + j); D.dst_row[n] = (uint8_t)(LQ + j); D.dst_view[n] = 0;
-            D.dst_half[n] = D.single ? 0 : half_product_mod(basis, be.P->moduli[j]);
-            n++;
-        }
-        D.ndst = n;
         mark_fast_destinations(be, D, basis);
         descs.push_back(D);
     }
@@ -3170,11 +3181,7 @@ int get_md_plan(Evaluator &ev, int levelQ, int levelP, const FusedPlan **out) {
     D.nsrc = levelP + 1;
     FusedPlan plan;
     if (levelP >= 0 && D.nsrc <= 8 && be.type == 0) {  // levelP = -1 (no special primes): ModDown is a copy, no plan (plan.ok stays false)
-        const ModUpDev c = be.ptoq[levelP].on(be.pool);
-        D.a = c.a; D.T = c.T; D.vt = c.vt;
-        D.Td = be.ptoq[levelP].Td_on(be.pool); D.vtd = be.ptoq[levelP].vtd_on(be.pool);
-        D.fc = be.ptoq[levelP].fc_on(be.pool); D.t60 = be.ptoq[levelP].t60_on(be.pool);
-        D.reduce_out = modup_out_needs_reduce(basis) ? 1 : 0;
+        desc_constants(D, be.ptoq[levelP], be.pool, basis);
         for (int i = 0; i <= levelP; i++) {
             D.src_limb[i] = (uint8_t)i; D.src_mod[i] = (uint8_t)(be.LQ + i);
             D.src_half[i] = half_product_mod(basis, be.P->moduli[i]);
@@ -3196,7 +3203,7 @@ int get_md_plan(Evaluator &ev, int levelQ, int levelP, const FusedPlan **out) {
 // limb_filter 1: skip the class-2 limbs (their transform is fused into launch_ntt_mac_f64)
 int dec_rows_ntt(Evaluator &ev, int levelQ, int levelP, int nbPi, View dec, int batch, int limb_filter = 0) {
     BasisExtender &be = *ev.be;
-    const int LQ = be.LQ, width = be.LQ + be.LP;
+    const int width = be.LQ + be.LP;
     const int beta = base_rns_size(levelQ, levelP);
     LimbTab t;
     t.n = 0;
@@ -3207,27 +3214,18 @@ int dec_rows_ntt(Evaluator &ev, int levelQ, int levelP, int nbPi, View dec, int 
         return HE_OK;
     };
     for (int d = 0; d < beta; d++) {
-        const int st = d * nbPi, ed = std::min(st + nbPi, levelQ + 1);
-        for (int j = 0; j <= levelQ + levelP + 1; j++) {
-            const bool isP = j > levelQ;
-            const int limb = isP ? LQ + (j - levelQ - 1) : j;
-            if (!isP && j >= st && j < ed) continue;
-            if (limb_filter == 1 && be.small[limb] == 2) continue;
-            t.in_limb[t.n] = t.out_limb[t.n] = (uint8_t)(d * width + limb);
-            t.mod[t.n] = (uint8_t)limb;
+        QPLimb l[kMaxLimbs];
+        const int n = qp_limbs(be, levelQ, levelP, limb_filter, l, d * nbPi, std::min(d * nbPi + nbPi, levelQ + 1));
+        for (int i = 0; i < n; i++) {
+            t.in_limb[t.n] = t.out_limb[t.n] = (uint8_t)(d * width + l[i].mod);
+            t.mod[t.n] = l[i].mod;
             if (++t.n == kMaxLimbs) TRY(flush());
         }
     }
     return flush();
 }
 
-struct KsScratch {  // per gadget product, for `batch` entries
-    uint64_t *cxinv;       // [batch][levelQ+1][N]
-    uint64_t *dec;         // [batch][beta][LQ+LP][N]
-    uint64_t *accP;        // [2][batch][levelP+1][N]
-    uint64_t *accQ;        // [2][batch][levelQ+1][N]
-    uint64_t *sP, *sQ;     // moddown scratch, [2*batch] entries
-};
+// scratch of a gadget product over `batch` entries: inverse transform and digits (need_dec), the accumulators, as much for ModDown
 size_t ks_scratch_words(const BasisExtender &be, int levelQ, int levelP, int batch, bool need_dec, const Evk *key = nullptr) {
     const size_t N = be.Q->N, B = batch;
     const size_t beta = key ? (size_t)key_beta(*key, levelQ) : (size_t)base_rns_size(levelQ, levelP);
@@ -3370,7 +3368,6 @@ int decompose_fused(Evaluator &ev, const FusedPlan &plan, int levelQ, int levelP
         HIP_TRY(launch_modup_fused(be.qp, g.dev, g.n, g.nsrc, g.dst_classes, rows_inv, dv, dv, batch, be.ctx->stream, f64_raw, g.total_limbs));
     return dec_rows_ntt(ev, levelQ, levelP, nbPi, dec, batch, ntt_filter);
 }
-// class-2 limbs of the gadget product: forward row NTT + key MAC in one kernel (dec holds the post-column state)
 // May the basis extension hand unreduced doubles to the double-precision row kernels (launch_modup_fused f64_raw)?
 static bool f64_raw_ok(const BasisExtender &be, int levelQ, int levelP, int nsrc) {
     uint64_t mx = 0;
@@ -3378,90 +3375,99 @@ static bool f64_raw_ok(const BasisExtender &be, int levelQ, int levelP, int nsrc
     for (int j = 0; j <= levelP; j++) if (be.small[be.LQ + j] == 2) mx = std::max(mx, be.P->moduli[j]);
     return mx != 0 && modup_f64_raw_ok(be.Q->logN, nsrc, mx);
 }
-// epi (optional): the ModDown epilogue runs in the kernel (NttMacEpilogue; sp / tsp indexed by Q LIMB here, compacted below);
-// the caller guarantees that no P limb is of the double-precision class
-int ks_mac_f64(Evaluator &ev, int levelQ, int levelP, const uint64_t *dec, size_t dec_bs, size_t dec_ds, const Evk &k, View cx,
-               int own_alpha, View o0Q, View o0P, View o1Q, View o1P, int batch, bool q_out_f64 = false, bool own_reduce = true,
-               bool dec_f64 = false, const NttMacEpilogue *epi = nullptr, const KsScatter *giant = nullptr) {
+// The digits the NTT + MAC kernel reads (raw: the double-precision limbs as unreduced doubles).  With the MAC epilogue the lazy
+// core leaves that launch pending: gadget_product_core runs it after the extension of the P part, the ModDown epilogue inside.
+struct MacDigits {
+    const uint64_t *dec = nullptr;
+    size_t bs = 0, ds = 0;
+    bool raw = false, own_reduce = true;
+};
+// the four inputs of a ciphertext product whose c0 / c1 the fused ModDown epilogue forms itself (NttEpilogue::tensor).  The
+// operand of such a key switch is the (not yet computed) degree-2 term T(a1, b1): gadget_product_lazy_core forms it -- in the
+// inverse row pass itself for the limbs of the double-precision class where the route has the prologue (NttProdIn), by
+// launch_tensor otherwise
+struct TensorIn {
+    View a0, a1, b0, b1;
+    const uint64_t *ts;  // per Q limb
+};
+// what a lazy gadget product runs on: cx (NTT domain) -> accumulators (views); scratch from the arena
+struct LazyArgs {
+    View cx;
+    int B = 0;
+    View c0Q, c0P, c1Q, c1P;          // the four accumulators (null P views: no special primes)
+    bool cx_canonical = false;        // cx was produced by this library and is known to be in [0, q) (no input reduction)
+    const TensorIn *tin = nullptr;    // with route.tensor_epilogue
+    const KsScatter *giant = nullptr; // with route.giant_fused: the accumulators leave through KsScatter's giant-step stores
+    MacDigits *pending = nullptr;     // with route.moddown == KS_MD_FUSED_MAC: the launch that is left to the caller
+};
+// class-2 limbs of the gadget product (m.cx, the accumulators, m.B, m.giant): forward row NTT + key MAC in one kernel
+// epi (optional): the ModDown epilogue runs in the kernel (NttMacEpilogue; sp / tsp indexed by Q LIMB here, compacted below)
+int ks_mac_f64(Evaluator &ev, int levelQ, const Evk &k, const KsRoute &r, const LazyArgs &m, const MacDigits &dec, const NttMacEpilogue *epi) {
     BasisExtender &be = *ev.be;
     const hipStream_t st = be.ctx->stream;
-    const int LQ = be.LQ, N = be.Q->N;
+    const int levelP = k.nPk - 1, N = be.Q->N;
     NttMacArgs a{};
     a.beta = base_rns_size(levelQ, levelP);
-    int n = 0;
-    for (int j = 0; j <= levelQ; j++) {
-        if (be.small[j] != 2) continue;
-        a.dec_limb[n] = (uint8_t)j; a.key_limb[n] = (uint8_t)j; a.out_limb[n] = (uint8_t)j; a.out_view[n] = 0; a.mod[n] = (uint8_t)j; n++;
-    }
-    for (int j = 0; j <= levelP; j++) {
-        if (be.small[LQ + j] != 2) continue;
-        a.dec_limb[n] = (uint8_t)(LQ + j); a.key_limb[n] = (uint8_t)(k.nQk + j); a.out_limb[n] = (uint8_t)j; a.out_view[n] = 1;
-        a.mod[n] = (uint8_t)(LQ + j); n++;
-    }
-    a.nlimbs = n;
-    a.dec_dstride = dec_ds;
+    key_product_limbs(a, be, k, levelQ, levelP, 2);
+    a.dec_dstride = dec.ds;
     a.key_kstride = (size_t)(k.nQk + k.nPk) * N;
     a.key_dstride = 2 * a.key_kstride;
-    a.own_alpha = own_alpha;
+    a.own_alpha = levelP + 1;
     a.own_nq = levelQ + 1;
-    a.own_reduce = own_reduce ? 1 : 0;
-    a.dec_f64 = dec_f64 ? 1 : 0;
+    a.own_reduce = dec.own_reduce ? 1 : 0;
+    a.dec_f64 = dec.raw ? 1 : 0;
     a.q_out_f64 = 0;
-    const View decv{const_cast<uint64_t *>(dec), dec_bs};
+    const View decv{const_cast<uint64_t *>(dec.dec), dec.bs};
     if (epi) {
         NttMacEpilogue e = *epi;
-        for (int i = 0; i < n; i++) {
-            if (a.out_view[i]) return fail(HE_EINVAL, "ks_mac_f64: epilogue with a double-precision P limb");
-            e.sp[i] = epi->sp[a.out_limb[i]]; e.tsp[i] = epi->tsp[a.out_limb[i]];
-        }
-        HIP_TRY(launch_ntt_mac_f64(be.qp, a, decv, cx, k.keyd, o0Q, o0P, o1Q, o1P, batch, st, &e));
+        for (int i = 0; i < a.nlimbs; i++) { e.sp[i] = epi->sp[a.out_limb[i]]; e.tsp[i] = epi->tsp[a.out_limb[i]]; }
+        HIP_TRY(launch_ntt_mac_f64(be.qp, a, decv, m.cx, k.keyd, m.c0Q, m.c0P, m.c1Q, m.c1P, m.B, st, &e));
         return HE_OK;
     }
-    if (giant && q_out_f64) return fail(HE_EINVAL, "ks_mac_f64: giant-step stores with double-format accumulators");
-    if (!q_out_f64) {
-        HIP_TRY(launch_ntt_mac_f64(be.qp, a, decv, cx, k.keyd, o0Q, o0P, o1Q, o1P, batch, st, nullptr, giant));
+    if (!r.acc_q_f64) {
+        HIP_TRY(launch_ntt_mac_f64(be.qp, a, decv, m.cx, k.keyd, m.c0Q, m.c0P, m.c1Q, m.c1P, m.B, st, nullptr, m.giant));
         return HE_OK;
     }
     // double-format Q accumulators: the Q limbs and the P limbs go to separate launches (different store code)
     NttMacArgs aq = a, ap = a;
-    aq.nlimbs = ap.nlimbs = 0;
-    for (int i = 0; i < n; i++) {
-        NttMacArgs &d = a.out_view[i] ? ap : aq;
-        const int m = d.nlimbs++;
-        d.dec_limb[m] = a.dec_limb[i]; d.key_limb[m] = a.key_limb[i]; d.out_limb[m] = a.out_limb[i];
-        d.out_view[m] = a.out_view[i]; d.mod[m] = a.mod[i];
-    }
+    key_product_limbs(aq, be, k, levelQ, -1, 2);
+    key_product_limbs(ap, be, k, -1, levelP, 2);
     aq.q_out_f64 = 1;
-    HIP_TRY(launch_ntt_mac_f64(be.qp, aq, decv, cx, k.keyd, o0Q, o0P, o1Q, o1P, batch, st));
-    HIP_TRY(launch_ntt_mac_f64(be.qp, ap, decv, cx, k.keyd, o0Q, o0P, o1Q, o1P, batch, st));
+    HIP_TRY(launch_ntt_mac_f64(be.qp, aq, decv, m.cx, k.keyd, m.c0Q, m.c0P, m.c1Q, m.c1P, m.B, st));
+    HIP_TRY(launch_ntt_mac_f64(be.qp, ap, decv, m.cx, k.keyd, m.c0Q, m.c0P, m.c1Q, m.c1P, m.B, st));
     return HE_OK;
 }
-
+// the route of one call with the two plans it was decided from (null: a base-2 gadget; no special primes)
+struct KsCall {
+    KsRoute route;
+    const FusedPlan *dec = nullptr, *md = nullptr;
+};
 // windows of source limb i of a bit-window accumulation: the key's, or one per limb (BaseTwoDecomposition == 0 in core/rgsw)
 int rgsw_nj(const Evk &k, int i) { return k.pw2 ? k.nj[i] : 1; }
 // Bit-window accumulation of one polynomial against a key: windows (INTT(cx)[i] >> j pw2) & mask of every Q limb, NTT'd into every
 // limb, multiplied into the accumulators (core/rlwe/evaluator_gadget_product.go:203-338; core/rgsw/evaluator.go:139-203 for one
 // el).  pw2 == 0 is core/rgsw's all-ones mask, one uncentred window per limb (:147-149).  reduce_wide: windows that can reach the
 // modulus they are transformed in are reduced first (core/rgsw's shapes; rlwe's base-2 keys never have them).
-int window_products_core(Evaluator &ev, int levelQ, View cx, int B, const Evk &k, bool reduce_wide, View o0Q, View o0P, View o1Q, View o1P) {
+int window_products_core(Evaluator &ev, int levelQ, const Evk &k, const LazyArgs &a, bool reduce_wide) {
     BasisExtender &be = *ev.be;
-    const int levelP = k.nPk - 1, N = be.Q->N;
+    const int levelP = k.nPk - 1, N = be.Q->N, B = a.B;
     int beta = 0;
     for (int i = 0; i <= levelQ; i++) beta += rgsw_nj(k, i);
     const size_t wq = (size_t)B * (levelQ + 1) * N, ds = (size_t)(be.LQ + be.LP) * N, bs = (size_t)beta * ds;
     View inv{be.ctx->arena_take(wq), (size_t)(levelQ + 1) * N};
     uint64_t *dec = be.ctx->arena_take((size_t)B * bs);
     hipStream_t st = be.ctx->stream;
-    HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), cx, inv, B, true, NTT_REDUCE_INPUT));
+    HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), a.cx, inv, B, true, NTT_REDUCE_INPUT));
     MaskSpreadArgs m{};
     m.mask = k.pw2 ? ((uint64_t)1 << k.pw2) - 1 : ~(uint64_t)0;
     LimbTab t;
-    t.n = 0;
+    QPLimb l[kMaxLimbs];
+    t.n = m.ndst = qp_limbs(be, levelQ, levelP, 0, l);
     bool reduce = false;
-    for (int j = 0; j <= levelQ; j++) { t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)j; m.dst_limb[t.n] = (uint8_t)j; t.n++; }
-    for (int j = 0; j <= levelP; j++) { t.in_limb[t.n] = t.out_limb[t.n] = t.mod[t.n] = (uint8_t)(be.LQ + j); m.dst_limb[t.n] = (uint8_t)(be.LQ + j); t.n++; }
-    for (int j = 0; reduce_wide && j < t.n; j++) reduce = reduce || m.mask >= be.modulus(t.mod[j]);
-    m.ndst = t.n;
+    for (int j = 0; j < t.n; j++) {
+        t.in_limb[j] = t.out_limb[j] = t.mod[j] = m.dst_limb[j] = l[j].mod;
+        reduce = reduce || (reduce_wide && m.mask >= be.modulus(l[j].mod));
+    }
     for (int i = 0; i <= levelQ; i++)
         for (int j = 0; j < rgsw_nj(k, i); j++) {
             m.blk_limb[m.nblk] = (uint8_t)i;
@@ -3473,110 +3479,91 @@ int window_products_core(Evaluator &ev, int levelQ, View cx, int B, const Evk &k
         View blk{dec + (size_t)d * ds, bs};
         HIP_TRY(be_ntt(be, t, blk, blk, B, false, reduce ? NTT_REDUCE_INPUT : 0));
     }
-    return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B);
+    return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, a.c0Q, a.c0P, a.c1Q, a.c1P, B);
 }
-// GadgetProductLazy core: cx (NTT) -> accumulators (views).  Scratch from the arena.
-// cx_canonical: cx was produced by this library and is known to be in [0, q) (skips the input reduction of the first pass)
-// acc_q_f64 (in/out): on entry, whether the caller can take the Q-limb accumulators of the moduli below 2^47 as doubles; on
-// return, whether they were written that way (only the fused NTT+MAC path does)
-// the four inputs of a ciphertext product whose c0 / c1 the fused ModDown epilogue forms itself (NttEpilogue::tensor)
-struct TensorIn {
-    View a0, a1, b0, b1;
-    const uint64_t *ts;  // per Q limb
-    // cx is the (not yet computed) degree-2 term T(a1, b1): gadget_product_lazy_core forms it -- in the inverse row pass itself for
-    // the limbs of the double-precision class where that pass has the prologue (NttProdIn), by launch_tensor otherwise
-    bool make_c2 = false;
-};
-// defer (optional, in/out): when `want` is set and the call takes the fused NTT + MAC path, the launch over the double-precision
-// limbs is NOT made: `deferred` is set and the fields describe it, so that the caller can run it after the basis extension of
-// the P part with the ModDown epilogue inside (gadget_product_core)
-struct MacDefer {
-    bool want = false, deferred = false;
-    const uint64_t *dec = nullptr;
-    size_t bs = 0, ds = 0;
-    bool raw = false, own_reduce = true;
-};
-// giant (optional; the caller checked giant_step_fusable()): the accumulators leave through KsScatter's giant-step stores
-int gadget_product_lazy_core(Evaluator &ev, int levelQ, View cx, int B, const Evk &k, View o0Q, View o0P, View o1Q, View o1P,
-                             bool cx_canonical = false, bool *acc_q_f64 = nullptr, MacDefer *defer = nullptr, const TensorIn *tin = nullptr,
-                             const KsScatter *giant = nullptr) {
-    const bool want_f64 = acc_q_f64 && *acc_q_f64;
-    if (acc_q_f64) *acc_q_f64 = false;
+// GadgetProductLazy core: the digits of a.cx as the route makes them, multiplied into the accumulators
+int gadget_product_lazy_core(Evaluator &ev, int levelQ, const Evk &k, const KsCall &c, const LazyArgs &a) {
     BasisExtender &be = *ev.be;
-    const int levelP = k.nPk - 1, N = be.Q->N;
+    const KsRoute &r = c.route;
+    const int levelP = k.nPk - 1, N = be.Q->N, B = a.B;
     const int beta = key_beta(k, levelQ);
     const size_t wq = (size_t)B * (levelQ + 1) * N, ds = (size_t)(be.LQ + be.LP) * N, bs = (size_t)beta * ds;
-    const FusedPlan *plan = nullptr;
-    if (!k.pw2) TRY(get_dec_plan(ev, levelQ, levelP, levelP + 1, &plan));
-    const bool make_c2 = tin && tin->make_c2;
-    static const bool no_prod_in = env_flag("HERING_NO_PROD_PROLOGUE");
-    const bool prod_in = make_c2 && plan && plan->ok && be.d_twdi != nullptr && ntt_prod_in_supported(be.Q->logN) && !no_prod_in;
-    if (make_c2) {
-        // cx = T(a1, b1): everywhere by the tensor kernel, or -- prod_in -- only on the integer-class limbs, the others being formed
-        // by the inverse row pass below
+    const View cx = a.cx;
+    if (a.tin) {
+        // cx = T(a1, b1): everywhere by the tensor kernel, or -- with the prologue -- only on the integer-class limbs, the others
+        // being formed by the inverse row pass below
         LimbTab tt;
-        tt.n = 0;
+        QPLimb l[kMaxLimbs];
         uint64_t tsv[kMaxLimbs];
-        for (int i = 0; i <= levelQ; i++) {
-            if (prod_in && be.small[i] == 2) continue;
-            tt.in_limb[tt.n] = tt.out_limb[tt.n] = tt.mod[tt.n] = (uint8_t)i;
-            tsv[tt.n] = tin->ts[i];
-            tt.n++;
+        tt.n = qp_limbs(be, levelQ, -1, r.prod_prologue ? 1 : 0, l);
+        for (int i = 0; i < tt.n; i++) {
+            tt.in_limb[i] = tt.out_limb[i] = tt.mod[i] = l[i].mod;
+            tsv[i] = a.tin->ts[l[i].mod];
         }
         if (tt.n > 0)
-            HIP_TRY(launch_tensor(be.qp, tt, tsv, tin->a0, tin->a1, tin->b0, tin->b1, View{nullptr, 0}, View{nullptr, 0}, cx, B, be.ctx->stream));
+            HIP_TRY(launch_tensor(be.qp, tt, tsv, a.tin->a0, a.tin->a1, a.tin->b0, a.tin->b1, View{nullptr, 0}, View{nullptr, 0}, cx, B, be.ctx->stream));
     }
-    if (k.pw2) {  // base-2 gadget: bit windows of every Q-limb, NTT'd into every limb (evaluator_gadget_product.go:203-338)
-        if (giant) return fail(HE_EINVAL, "gadget product: giant-step stores with a base-2 gadget");
-        return window_products_core(ev, levelQ, cx, B, k, false, o0Q, o0P, o1Q, o1P);
-    }
+    // base-2 gadget: bit windows of every Q-limb, NTT'd into every limb (evaluator_gadget_product.go:203-338)
+    if (r.digits == KS_DIGITS_WINDOWS) return window_products_core(ev, levelQ, k, a, false);
     uint64_t *cxinv = be.ctx->arena_take(wq);
     uint64_t *dec = be.ctx->arena_take((size_t)B * bs);
     View inv{cxinv, (size_t)(levelQ + 1) * N};
-    if (plan->ok) {
-        if (prod_in) {
-            NttProdIn pin;
-            pin.a = tin->a1; pin.b = tin->b1; pin.c = cx;
-            for (int i = 0; i <= levelQ; i++) pin.ts[i] = tin->ts[i];
-            HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), cx, inv, B, true, 0, be.ctx->stream, nullptr, &pin));
-        } else {
-            HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), cx, inv, B, true, cx_canonical ? 0 : NTT_REDUCE_INPUT, be.ctx->stream));
-        }
-        if (k.keyd) {  // limbs below 2^47: NTT + MAC fused; the rest: row NTT then ks_inner
-            // the double-precision limbs of the decomposition are read by ntt_mac_f64 only: they stay doubles in between
-            int max_nsrc = 1;
-            for (const FusedGroup &g : plan->groups) max_nsrc = std::max(max_nsrc, g.nsrc);
-            const bool raw = f64_raw_ok(be, levelQ, levelP, max_nsrc);
-            TRY(decompose_fused(ev, *plan, levelQ, levelP, levelP + 1, inv, View{dec, bs}, B, 1, raw));
-            TRY(ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B, &cx, levelP + 1, 1, 0, -1, giant));
-            if (giant) return ks_mac_f64(ev, levelQ, levelP, dec, bs, ds, k, cx, levelP + 1, o0Q, o0P, o1Q, o1P, B, false, !cx_canonical, raw, nullptr, giant);
-            if (defer && defer->want) {
-                defer->deferred = true; defer->dec = dec; defer->bs = bs; defer->ds = ds; defer->raw = raw; defer->own_reduce = !cx_canonical;
-                return HE_OK;
-            }
-            if (acc_q_f64) *acc_q_f64 = want_f64;
-            return ks_mac_f64(ev, levelQ, levelP, dec, bs, ds, k, cx, levelP + 1, o0Q, o0P, o1Q, o1P, B, want_f64, !cx_canonical, raw);
-        }
-        TRY(decompose_fused(ev, *plan, levelQ, levelP, levelP + 1, inv, View{dec, bs}, B));
-        return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B, &cx, levelP + 1, 0, 0, -1, giant);
+    if (r.digits == KS_DIGITS_UNFUSED) {
+        HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), cx, inv, B, true, NTT_REDUCE_INPUT));
+        TRY(decompose_ntt_into(ev, levelQ, levelP, levelP + 1, cx, inv, View{dec, bs}, ds, B));
+        return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, a.c0Q, a.c0P, a.c1Q, a.c1P, B);
     }
-    if (giant) return fail(HE_EINVAL, "gadget product: giant-step stores need the fused decomposition");
-    HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), cx, inv, B, true, NTT_REDUCE_INPUT));
-    TRY(decompose_ntt_into(ev, levelQ, levelP, levelP + 1, cx, inv, View{dec, bs}, ds, B));
-    return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, o0Q, o0P, o1Q, o1P, B);
+    if (r.prod_prologue) {
+        NttProdIn pin;
+        pin.a = a.tin->a1; pin.b = a.tin->b1; pin.c = cx;
+        for (int i = 0; i <= levelQ; i++) pin.ts[i] = a.tin->ts[i];
+        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), cx, inv, B, true, 0, be.ctx->stream, nullptr, &pin));
+    } else {
+        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), cx, inv, B, true, a.cx_canonical ? 0 : NTT_REDUCE_INPUT, be.ctx->stream));
+    }
+    if (!r.mac_f64) {
+        TRY(decompose_fused(ev, *c.dec, levelQ, levelP, levelP + 1, inv, View{dec, bs}, B));
+        return ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, a.c0Q, a.c0P, a.c1Q, a.c1P, B, &cx, levelP + 1, 0, 0, -1, a.giant);
+    }
+    // limbs below 2^47: NTT + MAC fused; the rest: row NTT then ks_inner.  The double-precision limbs of the decomposition are
+    // read by ntt_mac_f64 only: they stay doubles in between
+    int max_nsrc = 1;
+    for (const FusedGroup &g : c.dec->groups) max_nsrc = std::max(max_nsrc, g.nsrc);
+    const MacDigits digits{dec, bs, ds, f64_raw_ok(be, levelQ, levelP, max_nsrc), !a.cx_canonical};
+    TRY(decompose_fused(ev, *c.dec, levelQ, levelP, levelP + 1, inv, View{dec, bs}, B, 1, digits.raw));
+    TRY(ks_inner(ev, levelQ, levelP, View{dec, bs}, ds, k, a.c0Q, a.c0P, a.c1Q, a.c1P, B, &cx, levelP + 1, 1, 0, -1, a.giant));
+    if (r.moddown == KS_MD_FUSED_MAC) {
+        *a.pending = digits;
+        return HE_OK;
+    }
+    return ks_mac_f64(ev, levelQ, k, r, a, digits, nullptr);
 }
-// ModDownQPtoQNTT up to (not including) its last fused op: sQ = NTTLazy(ModUpPtoQ(INTTLazy(accP))) for nb entries
-int moddown_front(Evaluator &ev, int levelQ, int levelP, View accP, View sP, View sQ, int nb, bool canonical = false) {
+// The front of the fused ModDown for nb entries: INTT rows (P) -> [cols + ModUpPtoQ + cols] into sQ; the forward rows, with their
+// epilogue, are the caller's (raw: they take NTT_INPUT_F64, the extension's doubles stay doubles).  canonical: accP is in [0, p)
+int moddown_front_fused(Evaluator &ev, const FusedPlan &plan, int levelQ, int levelP, View accP, View sP, View sQ, int nb, bool canonical, bool *raw) {
     BasisExtender &be = *ev.be;
     hipStream_t st = be.ctx->stream;
+    HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelP + 1, 0, 0, be.LQ), accP, sP, nb, true, canonical ? 0 : NTT_REDUCE_INPUT, st));
+    const FusedGroup &g = plan.groups[0];
+    *raw = f64_raw_ok(be, levelQ, -1, g.nsrc);
+    HIP_TRY(launch_modup_fused(be.qp, g.dev, 1, g.nsrc, g.dst_classes, sP, sQ, sQ, nb, st, *raw, g.total_limbs));
+    return HE_OK;
+}
+// the epilogue of those rows over the Q limbs of `tab`: out = (x - y) * P^-1 (addends, second component, tensor terms: the callers)
+void moddown_epilogue(NttEpilogue &epi, const BasisExtender &be, int levelP, const LimbTab &tab, View y) {
+    for (int i = 0; i < tab.n; i++) epi.s[i] = be.Q->moduli[tab.mod[i]] - be.md_ptoq[levelP][tab.mod[i]];
+    epi.y = y; epi.has_w = false; epi.w = y;
+}
+// ModDownQPtoQNTT up to (not including) its last fused op: sQ = NTTLazy(ModUpPtoQ(INTTLazy(accP))) for nb entries.  No key here:
+// fused exactly when the ModDown plan exists
+int moddown_front(Evaluator &ev, int levelQ, int levelP, View accP, View sP, View sQ, int nb, bool canonical = false) {
+    BasisExtender &be = *ev.be;
     const FusedPlan *plan = nullptr;
     TRY(get_md_plan(ev, levelQ, levelP, &plan));
     if (plan->ok) {
-        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelP + 1, 0, 0, be.LQ), accP, sP, nb, true, canonical ? 0 : NTT_REDUCE_INPUT, st));
-        const FusedGroup &g = plan->groups[0];
-        const bool raw = f64_raw_ok(be, levelQ, -1, g.nsrc);
-        HIP_TRY(launch_modup_fused(be.qp, g.dev, 1, g.nsrc, g.dst_classes, sP, sQ, sQ, nb, st, raw, g.total_limbs));
-        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), sQ, sQ, nb, false, NTT_LAZY_OUT | (raw ? NTT_INPUT_F64 : 0), st));
+        bool raw = false;
+        TRY(moddown_front_fused(ev, *plan, levelQ, levelP, accP, sP, sQ, nb, canonical, &raw));
+        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), sQ, sQ, nb, false, NTT_LAZY_OUT | (raw ? NTT_INPUT_F64 : 0), be.ctx->stream));
         return HE_OK;
     }
     HIP_TRY(be_ntt(be, ident_tab(levelP + 1, 0, 0, be.LQ), accP, sP, nb, true, NTT_REDUCE_INPUT));
@@ -3595,131 +3582,128 @@ int moddown_back(Evaluator &ev, int levelQ, int levelP, View sQ, View accQ, View
     else HIP_TRY(launch_ew(be.qp, ident_tab(levelQ + 1), EW_SUB_THEN_MUL_SCALAR_MONT_2Q, sQ, accQ, out, B, &s, nullptr, be.ctx->stream));
     return HE_OK;
 }
-// Evaluator.ModDown (NTT/NTT branch) on caller-provided accumulators
-int moddown_pair(Evaluator &ev, int levelQ, int levelP, View c0Q, View c0P, View c1Q, View c1P, View out0, View out1, int B) {
+// what a full gadget product runs on: out_k = [add_k +] GadgetProduct(cx)_k
+struct GpArgs {
+    const View *cx = nullptr, *hoisted = nullptr;  // the NTT-domain operand, or a hoisting buffer with its digits
+    View out0, out1;
+    int B = 0;
+    const View *add0 = nullptr, *add1 = nullptr;
+    bool cx_canonical = false;
+    const TensorIn *tin = nullptr;  // with route.tensor_epilogue (no addends then)
+    uint32_t scatter_ginv = 0;  // with KS_AUTO_EPILOGUE_SCATTER: g^-1 mod 2N, the epilogues store through it (NttEpilogue::scatter_ginv)
+};
+// full GadgetProduct.  Both components share every launch (accumulators are laid out [2][B] so ModDown runs once over 2B entries).
+int gadget_product_core(Evaluator &ev, int levelQ, const Evk &k, const KsCall &c, const GpArgs &g) {
     BasisExtender &be = *ev.be;
-    const int N = be.Q->N;
-    const size_t wP = (size_t)B * (levelP + 1) * N, wQ = (size_t)B * (levelQ + 1) * N;
-    View sP{be.ctx->arena_take(wP), (size_t)(levelP + 1) * N};
-    View sQ{be.ctx->arena_take(wQ), (size_t)(levelQ + 1) * N};
-    TRY(moddown_front(ev, levelQ, levelP, c0P, sP, sQ, B));
-    TRY(moddown_back(ev, levelQ, levelP, sQ, c0Q, out0, nullptr, B));
-    TRY(moddown_front(ev, levelQ, levelP, c1P, sP, sQ, B));
-    TRY(moddown_back(ev, levelQ, levelP, sQ, c1Q, out1, nullptr, B));
-    return HE_OK;
-}
-// full GadgetProduct: out_k = [add_k +] GadgetProduct(cx)_k.  Both components share every launch
-// (accumulators are laid out [2][B] so ModDown runs once over 2B entries).
-// scatter_ginv (optional, in/out): on entry g^-1 mod 2N of an automorphism the caller wants applied to the outputs; where the
-// fused ModDown epilogues write the result they store it through that automorphism (NttEpilogue::scatter_ginv) and the value is
-// left as it is; a path without such an epilogue sets it to 0 and the caller applies the automorphism itself (launch_gather).
-int gadget_product_core(Evaluator &ev, int levelQ, const View *cx, const View *hoisted, const Evk &k, View out0, View out1, int B,
-                        const View *add0 = nullptr, const View *add1 = nullptr, bool cx_canonical = false,
-                        const TensorIn *tin = nullptr, uint32_t *scatter_ginv = nullptr) {
-    const uint32_t want_scatter = scatter_ginv ? *scatter_ginv : 0u;
-    if (scatter_ginv) *scatter_ginv = 0;
-    BasisExtender &be = *ev.be;
-    const int levelP = k.nPk - 1, N = be.Q->N;
+    const KsRoute &r = c.route;
+    const int levelP = k.nPk - 1, N = be.Q->N, B = g.B;
     const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
     uint64_t *aQ = be.ctx->arena_take(2 * B * sQw), *aP = be.ctx->arena_take(2 * B * sPw);
     View a0Q{aQ, sQw}, a1Q{aQ + (size_t)B * sQw, sQw}, a0P{aP, sPw}, a1P{aP + (size_t)B * sPw, sPw};
-    if (levelP < 0) {
+    hipStream_t st = be.ctx->stream;
+    if (r.moddown == KS_MD_NONE) {
         // no special primes: ModDown's levelP == -1 branch is a copy of the (canonical) Q accumulators (:76-81), followed by
         // the caller's Ring.Add where there is one
-        if (!cx) return fail(HE_EINVAL, "gadget product: a hoisted decomposition needs special primes");
-        TRY(gadget_product_lazy_core(ev, levelQ, *cx, B, k, a0Q, View{nullptr, 0}, a1Q, View{nullptr, 0}, cx_canonical, nullptr));
+        TRY(gadget_product_lazy_core(ev, levelQ, k, c, LazyArgs{*g.cx, B, a0Q, View{nullptr, 0}, a1Q, View{nullptr, 0}, g.cx_canonical}));
         const LimbTab tq = ident_tab(levelQ + 1);
-        hipStream_t st = be.ctx->stream;
-        HIP_TRY(launch_ew(be.qp, tq, add0 ? EW_ADD : EW_COPY, a0Q, add0 ? *add0 : a0Q, out0, B, nullptr, nullptr, st));
-        HIP_TRY(launch_ew(be.qp, tq, add1 ? EW_ADD : EW_COPY, a1Q, add1 ? *add1 : a1Q, out1, B, nullptr, nullptr, st));
+        HIP_TRY(launch_ew(be.qp, tq, g.add0 ? EW_ADD : EW_COPY, a0Q, g.add0 ? *g.add0 : a0Q, g.out0, B, nullptr, nullptr, st));
+        HIP_TRY(launch_ew(be.qp, tq, g.add1 ? EW_ADD : EW_COPY, a1Q, g.add1 ? *g.add1 : a1Q, g.out1, B, nullptr, nullptr, st));
         return HE_OK;
     }
-    const FusedPlan *plan = nullptr;
-    TRY(get_md_plan(ev, levelQ, levelP, &plan));
-    bool acc_f64 = plan->ok;  // the fused ModDown epilogue can read double accumulators
-    // ModDown inside the NTT + MAC kernel: possible when the P part does not depend on that kernel (no P limb of the
-    // double-precision class) -- then the P accumulators come from ks_inner alone, are extended first, and the kernel over the
-    // double-precision Q limbs forms the final outputs against its accumulators in registers (NttMacEpilogue)
-    static const bool no_mac_epi = env_flag("HERING_NO_MAC_EPILOGUE");
-    MacDefer defer;
-    if (cx && plan->ok && k.keyd && !k.pw2 && !no_mac_epi && ntt_mac_epilogue_supported(be.Q->logN)) {
-        // (the kernel writes the outputs while other workgroups still read cx -- the digits' own limbs: not when they alias)
-        defer.want = out0.p != cx->p && out1.p != cx->p;
-        for (int j = 0; j <= levelP; j++) defer.want = defer.want && be.small[be.LQ + j] != 2;
-    }
-    if (cx) TRY(gadget_product_lazy_core(ev, levelQ, *cx, B, k, a0Q, a0P, a1Q, a1P, cx_canonical, &acc_f64, &defer, tin));
-    else {
-        acc_f64 = false;
-        TRY(ks_inner(ev, levelQ, levelP, *hoisted, (size_t)(be.LQ + be.LP) * N, k, a0Q, a0P, a1Q, a1P, B));
-    }
+    const bool mac_epilogue = r.moddown == KS_MD_FUSED_MAC;
+    MacDigits pending;
+    const LazyArgs lazy{g.cx ? *g.cx : View{nullptr, 0}, B, a0Q, a0P, a1Q, a1P, g.cx_canonical, g.tin, nullptr, mac_epilogue ? &pending : nullptr};
+    if (g.cx) TRY(gadget_product_lazy_core(ev, levelQ, k, c, lazy));
+    else TRY(ks_inner(ev, levelQ, levelP, *g.hoisted, (size_t)(be.LQ + be.LP) * N, k, a0Q, a0P, a1Q, a1P, B));
     View sP{be.ctx->arena_take(2 * B * sPw), sPw}, sQ{be.ctx->arena_take(2 * B * sQw), sQw};
-    if (plan->ok) {
-        // ModDown with every pass fused: INTT rows (P, both components) -> [cols + ModUpPtoQ + cols] -> NTT rows whose
-        // epilogue applies (x - acc) * P^-1 and the caller's Add and writes the final output
-        hipStream_t st = be.ctx->stream;
-        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelP + 1, 0, 0, be.LQ), View{aP, sPw}, sP, 2 * B, true, 0, st));  // canonical accumulators
-        const FusedGroup &g = plan->groups[0];
-        const bool raw = f64_raw_ok(be, levelQ, -1, g.nsrc);  // the extension's double-precision outputs stay doubles up to the row kernel
-        HIP_TRY(launch_modup_fused(be.qp, g.dev, 1, g.nsrc, g.dst_classes, sP, sQ, sQ, 2 * B, st, raw, g.total_limbs));
-        if (defer.deferred) {
-            NttMacEpilogue me;
-            me.scatter_ginv = tin ? 0u : want_scatter;
-            if (scatter_ginv && !tin) *scatter_ginv = want_scatter;
-            me.ext = sQ; me.ext_f64 = raw;
-            me.out0 = out0; me.out1 = out1;
-            me.has_w0 = add0 != nullptr && !tin; me.has_w1 = add1 != nullptr && !tin;
-            me.w0 = add0 ? *add0 : out0; me.w1 = add1 ? *add1 : out1;
-            me.tensor = tin != nullptr;
-            if (tin) { me.ta0 = tin->a0; me.ta1 = tin->a1; me.tb0 = tin->b0; me.tb1 = tin->b1; }
-            LimbTab ti;  // the Q limbs the integer kernels own: their epilogue stays with the forward rows
-            ti.n = 0;
-            NttEpilogue epi;
-            epi.scatter_ginv = me.scatter_ginv;
-            for (int i = 0; i <= levelQ; i++) {
-                const ModConst &m = be.Q->sub[i].mc;
-                const uint64_t si = be.Q->moduli[i] - be.md_ptoq[levelP][i];
-                me.sp[i] = (double)imform(si, m.q, m.qinv);
-                me.tsp[i] = tin ? (double)imform(imform(tin->ts[i], m.q, m.qinv), m.q, m.qinv) : 0.0;
-                if (be.small[i] == 2) continue;
-                ti.in_limb[ti.n] = ti.out_limb[ti.n] = ti.mod[ti.n] = (uint8_t)i;
-                epi.s[ti.n] = si;
-                if (tin) epi.ts[ti.n] = tin->ts[i];
-                ti.n++;
-            }
-            TRY(ks_mac_f64(ev, levelQ, levelP, defer.dec, defer.bs, defer.ds, k, *cx, levelP + 1, a0Q, a0P, a1Q, a1P, B, false,
-                           defer.own_reduce, defer.raw, &me));
-            if (ti.n > 0) {
-                epi.y = a0Q; epi.has_w = add0 != nullptr; epi.w = add0 ? *add0 : a0Q;
-                epi.y_small_f64 = false;
-                epi.zsplit = B; epi.out2 = out1; epi.y2 = a1Q; epi.has_w2 = add1 != nullptr; epi.w2 = add1 ? *add1 : a1Q;
-                if (tin) {
-                    epi.tensor = true; epi.has_w = epi.has_w2 = false;
-                    epi.ta0 = tin->a0; epi.ta1 = tin->a1; epi.tb0 = tin->b0; epi.tb1 = tin->b1;
-                }
-                HIP_TRY(launch_ntt_rows(be.qp, ti, sQ, out0, 2 * B, false, 0, st, &epi));
-            }
-            return HE_OK;
-        }
-        NttEpilogue epi;
-        epi.scatter_ginv = tin ? 0u : want_scatter;
-        if (scatter_ginv && !tin) *scatter_ginv = want_scatter;
-        for (int i = 0; i <= levelQ; i++) epi.s[i] = be.Q->moduli[i] - be.md_ptoq[levelP][i];
-        epi.y = a0Q; epi.has_w = add0 != nullptr; epi.w = add0 ? *add0 : a0Q;
-        epi.y_small_f64 = acc_f64;
-        epi.zsplit = B; epi.out2 = out1; epi.y2 = a1Q; epi.has_w2 = add1 != nullptr; epi.w2 = add1 ? *add1 : a1Q;
-        if (tin) {
-            epi.tensor = true; epi.has_w = epi.has_w2 = false;
-            epi.ta0 = tin->a0; epi.ta1 = tin->a1; epi.tb0 = tin->b0; epi.tb1 = tin->b1;
-            for (int i = 0; i <= levelQ; i++) epi.ts[i] = tin->ts[i];
-        }
-        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), sQ, out0, 2 * B, false, raw ? NTT_INPUT_F64 : 0, st, &epi));
+    if (r.moddown == KS_MD_UNFUSED) {
+        TRY(moddown_front(ev, levelQ, levelP, View{aP, sPw}, sP, sQ, 2 * B, true));  // accumulators of ks_inner / ntt_mac: canonical
+        TRY(moddown_back(ev, levelQ, levelP, sQ, a0Q, g.out0, g.add0, B));
+        TRY(moddown_back(ev, levelQ, levelP, View{sQ.p + (size_t)B * sQw, sQw}, a1Q, g.out1, g.add1, B));
         return HE_OK;
     }
-    if (tin) return fail(HE_EINVAL, "gadget product: tensor-mode epilogue without a fused ModDown plan");
-    TRY(moddown_front(ev, levelQ, levelP, View{aP, sPw}, sP, sQ, 2 * B, true));  // accumulators of ks_inner / ntt_mac: canonical
-    TRY(moddown_back(ev, levelQ, levelP, sQ, a0Q, out0, add0, B));
-    TRY(moddown_back(ev, levelQ, levelP, View{sQ.p + (size_t)B * sQw, sQw}, a1Q, out1, add1, B));
+    // ModDown with every pass fused: INTT rows (P, both components) -> [cols + ModUpPtoQ + cols] -> NTT rows whose epilogue
+    // applies (x - acc) * P^-1 and the caller's Add (or the tensor terms) and writes the final output.  With the MAC epilogue
+    // those rows cover the Q limbs the integer kernels own; the NTT + MAC kernel does the same for the others.
+    bool raw = false;
+    TRY(moddown_front_fused(ev, *c.md, levelQ, levelP, View{aP, sPw}, sP, sQ, 2 * B, true, &raw));
+    LimbTab ti;
+    QPLimb l[kMaxLimbs];
+    ti.n = qp_limbs(be, levelQ, -1, mac_epilogue ? 1 : 0, l);
+    for (int i = 0; i < ti.n; i++) ti.in_limb[i] = ti.out_limb[i] = ti.mod[i] = l[i].mod;
+    NttEpilogue epi;
+    moddown_epilogue(epi, be, levelP, ti, a0Q);
+    epi.scatter_ginv = g.scatter_ginv;
+    epi.has_w = g.add0 != nullptr; epi.w = g.add0 ? *g.add0 : a0Q;
+    epi.y_small_f64 = r.acc_q_f64;
+    epi.zsplit = B; epi.out2 = g.out1; epi.y2 = a1Q; epi.has_w2 = g.add1 != nullptr; epi.w2 = g.add1 ? *g.add1 : a1Q;
+    if (g.tin) {
+        epi.tensor = true; epi.has_w = epi.has_w2 = false;
+        epi.ta0 = g.tin->a0; epi.ta1 = g.tin->a1; epi.tb0 = g.tin->b0; epi.tb1 = g.tin->b1;
+        for (int i = 0; i < ti.n; i++) epi.ts[i] = g.tin->ts[ti.mod[i]];
+    }
+    if (mac_epilogue) {
+        NttMacEpilogue me;
+        me.scatter_ginv = g.scatter_ginv;
+        me.ext = sQ; me.ext_f64 = raw;
+        me.out0 = g.out0; me.out1 = g.out1;
+        me.has_w0 = g.add0 != nullptr && !g.tin; me.has_w1 = g.add1 != nullptr && !g.tin;
+        me.w0 = g.add0 ? *g.add0 : g.out0; me.w1 = g.add1 ? *g.add1 : g.out1;
+        me.tensor = g.tin != nullptr;
+        if (g.tin) { me.ta0 = g.tin->a0; me.ta1 = g.tin->a1; me.tb0 = g.tin->b0; me.tb1 = g.tin->b1; }
+        for (int i = 0; i <= levelQ; i++) {
+            const ModConst &m = be.Q->sub[i].mc;
+            me.sp[i] = (double)imform(be.Q->moduli[i] - be.md_ptoq[levelP][i], m.q, m.qinv);
+            me.tsp[i] = g.tin ? (double)imform(imform(g.tin->ts[i], m.q, m.qinv), m.q, m.qinv) : 0.0;
+        }
+        TRY(ks_mac_f64(ev, levelQ, k, r, lazy, pending, &me));
+    }
+    if (ti.n > 0) HIP_TRY(launch_ntt_rows(be.qp, ti, sQ, g.out0, 2 * B, false, (raw && !mac_epilogue) ? NTT_INPUT_F64 : 0, st, &epi));
     return HE_OK;
+}
+// The route of one call of `form` with key k at levelQ: the facts are gathered here and nowhere else (each switch read once).
+int ks_call(Evaluator &ev, KsForm form, int levelQ, const Evk &k, KsAlias alias, KsCall *out) {
+    static const bool no_mac_epilogue = env_flag("HERING_NO_MAC_EPILOGUE");
+    static const bool no_prod_prologue = env_flag("HERING_NO_PROD_PROLOGUE");
+    static const bool no_tensor_epilogue = env_flag("HERING_NO_TENSOR_EPILOGUE");
+    static const bool no_auto_scatter = env_flag("HERING_NO_AUTO_SCATTER");
+    static const bool no_giant_fusion = env_flag("HERING_NO_GIANT_FUSION");
+    const BasisExtender &be = *ev.be;
+    const int logN = be.Q->logN;
+    KsFacts f;
+    f.form = form; f.ring_type = be.type; f.levelP = k.nPk - 1;
+    f.pw2 = k.pw2 != 0; f.keyd = k.keyd != nullptr; f.f64_tables = be.d_twdi != nullptr;
+    for (int j = 0; j < k.nPk; j++) f.p_class2 = f.p_class2 || be.small[be.LQ + j] == 2;
+    // (only the plans the form's launches and tables_ok ask about)
+    const bool lazy = form == KS_LAZY || form == KS_GIANT_STEP || form == KS_AUTOMORPHISM_HOISTED_LAZY;
+    if (k.nPk > 0 && !k.pw2 && form != KS_HOISTED && form != KS_AUTOMORPHISM_HOISTED_LAZY) TRY(get_dec_plan(ev, levelQ, k.nPk - 1, k.nPk, &out->dec));
+    if (k.nPk > 0 && !lazy) TRY(get_md_plan(ev, levelQ, k.nPk - 1, &out->md));
+    f.dec_ok = out->dec && out->dec->ok; f.md_ok = out->md && out->md->ok;
+    f.prod_in_supported = ntt_prod_in_supported(logN); f.scatter_supported = epilogue_scatter_supported(logN);
+    f.mac_epilogue_supported = ntt_mac_epilogue_supported(logN); f.mac_giant_supported = ntt_mac_giant_supported(logN);
+    f.alias = alias;
+    f.no_mac_epilogue = no_mac_epilogue; f.no_prod_prologue = no_prod_prologue; f.no_tensor_epilogue = no_tensor_epilogue;
+    f.no_auto_scatter = no_auto_scatter; f.no_giant_fusion = no_giant_fusion;
+    out->route = ks_route(f);
+    return HE_OK;
+}
+// a full key switch of `form`: its route, then its launches
+int key_switch(Evaluator &ev, KsForm form, int levelQ, const Evk &k, KsAlias alias, const GpArgs &g) {
+    KsCall c;
+    TRY(ks_call(ev, form, levelQ, k, alias, &c));
+    return gadget_product_core(ev, levelQ, k, c, g);
+}
+// What every key-switch request starts with, and its tables_ok from the route of `form` (KS_FORM_COUNT: the entry sets its own)
+void ks_request(CoReq &q, int op, std::shared_ptr<Evaluator> ev, std::shared_ptr<Evk> k, int level, KsForm form, KsAlias alias) {
+    q.op = op; q.obj = ev.get(); q.key = k.get(); q.par[0] = level;
+    q.keep.push_back(ev); q.keep.push_back(k);
+    if (!k || form == KS_FORM_COUNT) return;
+    q.tables_ok = [ev, k, form, level, alias](bool *ok) -> int {
+        KsCall c;
+        TRY(ks_call(*ev, form, level, *k, alias, &c));
+        *ok = c.route.tables_ok;
+        return HE_OK;
+    };
 }
 int check_key(const Evaluator &ev, const Evk &k, int &levelQ, const char *who) {
     if (k.ev.get() != &ev) return fail(HE_EINVAL, "%s: key belongs to another evaluator", who);
@@ -3738,8 +3722,6 @@ int check_decomp(const Evaluator &ev, const Decomp &dec, int levelQ, int levelP,
 }
 }  // namespace
 
-static int keyswitch_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok);
-static int mul_relin_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok);
 // limbs of an evaluation key's 2 beta rows at (levelQ, levelP): read once per call, shared by the batch
 static double key_limbs(const Evk &k, int levelQ) { return 2.0 * key_beta(k, levelQ) * (levelQ + k.nPk + 1); }
 // What every full key switch (gadget_product_core) starts with: the bytes it moves (`limbs` polynomial limbs per entry and the
@@ -3761,23 +3743,15 @@ int he_gadget_product_lazy(he_handle hev, int levelQ, he_handle hcx, he_handle h
     o.in(hcx, levelQ + 1, "cx");
     o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, k->nPk - 1);
     TRY(o.check());
-    q.op = CO_GP_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_GP_LAZY, ev, k, levelQ, KS_LAZY, KsAlias{});
     q.run = [ev, k, levelQ](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(levelQ + 1 + 2.0 * (levelQ + k->nPk + 1), key_limbs(*k, levelQ), B, be.Q->N);  // cx in, two QP accumulators out, key
         { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, k->nPk - 1, key_beta(*k, levelQ), true, true); V.into(*be.ctx, B); }
         TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, k->nPk - 1, B, true, k.get())));
-        return gadget_product_lazy_core(*ev, levelQ, v[0], B, *k, v[1], v[2], v[3], v[4]);
-    };
-    // entry tables: the fused decomposition (the unfused / base-2 launches write the digits through pointers of their own)
-    q.tables_ok = [ev, k, levelQ](bool *ok) -> int {
-        *ok = false;
-        if (k->pw2 || k->nPk <= 0) return HE_OK;
-        const FusedPlan *plan = nullptr;
-        TRY(get_dec_plan(*ev, levelQ, k->nPk - 1, k->nPk, &plan));
-        *ok = plan->ok;
-        return HE_OK;
+        KsCall c;
+        TRY(ks_call(*ev, KS_LAZY, levelQ, *k, KsAlias{}, &c));
+        return gadget_product_lazy_core(*ev, levelQ, *k, c, LazyArgs{v[0], B, v[1], v[2], v[3], v[4]});
     };
     return co_dispatch(*be.ctx, o.B, q);
 }
@@ -3795,8 +3769,7 @@ int he_gadget_product_hoisted_lazy(he_handle hev, int levelQ, he_handle hdec, he
     o.qp(true, c0Q, c0P, c1Q, c1P, levelQ, k->nPk - 1);
     TRY(o.check());
     const size_t dec_ds = dec->dstride();
-    q.op = CO_GP_HOISTED_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_GP_HOISTED_LAZY, ev, k, levelQ, KS_FORM_COUNT, KsAlias{});
     q.run = [ev, k, levelQ, dec_ds](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         be.ctx->acct(key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + k->nPk + 1), key_limbs(*k, levelQ), B, be.Q->N);  // decomposition in, accumulators out, key
@@ -3874,7 +3847,13 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
         be.ctx->acct(2.0 * (2.0 * (levelQ + 1) + levelP + 1), 0, B, be.Q->N);  // ModDown of both components: 2 (2 L + alpha)
         { Valu V(be.Q->logN); valu_moddown(V, be, levelQ, levelP); valu_moddown(V, be, levelQ, levelP); V.into(*be.ctx, B); }
         TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, levelP, B, false)));
-        return moddown_pair(*ev, levelQ, levelP, v[0], v[1], v[2], v[3], v[4], v[5], B);
+        const size_t sPw = (size_t)(levelP + 1) * be.Q->N, sQw = (size_t)(levelQ + 1) * be.Q->N;
+        View sP{be.ctx->arena_take(B * sPw), sPw}, sQ{be.ctx->arena_take(B * sQw), sQw};
+        for (int c = 0; c < 2; c++) {  // component by component, as the reference
+            TRY(moddown_front(*ev, levelQ, levelP, v[2 * c + 1], sP, sQ, B));
+            TRY(moddown_back(*ev, levelQ, levelP, sQ, v[2 * c], v[4 + c], nullptr, B));
+        }
+        return HE_OK;
     };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
     return co_dispatch(*be.ctx, out0->batch, q);
@@ -3909,16 +3888,13 @@ int he_eval_moddown_qp_to_q_ntt(he_handle hev, int levelQ, int levelP, he_handle
         const bool wide = (size_t)B * ((size_t)1 << rowbits) / 128 >= 256;
         if (!plan->ok || !wide) return moddown_q_ntt(be, levelQ, levelP, v[0], v[1], v[2], B, sP, sQ);
         // three launches: INTT rows (P) -> [cols + ModUpPtoQ + cols] -> NTT rows whose epilogue is the last op of the ModDown
-        hipStream_t st = be.ctx->stream;
-        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelP + 1, 0, 0, be.LQ), v[1], sP, B, true, NTT_REDUCE_INPUT, st));
-        const FusedGroup &g = plan->groups[0];
-        const bool raw = f64_raw_ok(be, levelQ, -1, g.nsrc);
-        HIP_TRY(launch_modup_fused(be.qp, g.dev, 1, g.nsrc, g.dst_classes, sP, sQ, sQ, B, st, raw, g.total_limbs));
+        bool raw = false;
+        TRY(moddown_front_fused(*ev, *plan, levelQ, levelP, v[1], sP, sQ, B, false, &raw));
+        const LimbTab tq = ident_tab(levelQ + 1);
         NttEpilogue epi;
-        for (int i = 0; i <= levelQ; i++) epi.s[i] = be.Q->moduli[i] - be.md_ptoq[levelP][i];
-        epi.y = v[0]; epi.has_w = false; epi.w = v[0];
+        moddown_epilogue(epi, be, levelP, tq, v[0]);
         epi.y_reduce = true;  // p1Q is the caller's: any 64-bit word
-        HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), sQ, v[2], B, false, raw ? NTT_INPUT_F64 : 0, st, &epi));
+        HIP_TRY(launch_ntt_rows(be.qp, tq, sQ, v[2], B, false, raw ? NTT_INPUT_F64 : 0, be.ctx->stream, &epi));
         return HE_OK;
     };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
@@ -3936,16 +3912,11 @@ int he_gadget_product(he_handle hev, int levelQ, he_handle hcx, he_handle hk, he
     TRY(o.check());
     // an output that is the key switch's NTT-domain operand: its own-digit limbs are still being read while the fused epilogue
     // writes the outputs of OTHER entries' workgroups -- such requests (their own key: the aliasing pattern) are served one by one
-    const bool alias = o.same(ix, i0) || o.same(ix, i1);
-    q.op = CO_GADGET_PRODUCT; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.keep.push_back(ev); q.keep.push_back(k);
-    q.run = [ev, k, levelQ](const View *v, int B) -> int {
+    const KsAlias alias{o.same(ix, i0) || o.same(ix, i1)};
+    ks_request(q, CO_GADGET_PRODUCT, ev, k, levelQ, KS_GADGET_PRODUCT, alias);
+    q.run = [ev, k, levelQ, alias](const View *v, int B) -> int {
         TRY(keyswitch_begin(*ev, *k, levelQ, 3.0 * (levelQ + 1), true, B));  // GadgetProduct: 3 L + 2 beta (L + alpha)
-        return gadget_product_core(*ev, levelQ, &v[0], nullptr, *k, v[1], v[2], B);
-    };
-    q.tables_ok = [ev, k, levelQ, alias](bool *ok) -> int {
-        *ok = false;
-        return alias ? HE_OK : keyswitch_tables_ok(*ev, levelQ, *k, ok);
+        return key_switch(*ev, KS_GADGET_PRODUCT, levelQ, *k, alias, GpArgs{&v[0], nullptr, v[1], v[2], B});
     };
     return co_dispatch(*be.ctx, o.B, q);
 }
@@ -3963,13 +3934,11 @@ int he_gadget_product_hoisted(he_handle hev, int levelQ, he_handle hdec, he_hand
     o.out(hout0, levelQ + 1, "out0");
     o.out(hout1, levelQ + 1, "out1");
     TRY(o.check());
-    q.op = CO_GP_HOISTED; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_GP_HOISTED, ev, k, levelQ, KS_HOISTED, KsAlias{});
     q.run = [ev, k, levelQ](const View *v, int B) -> int {
         TRY(keyswitch_begin(*ev, *k, levelQ, key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + 1), false, B));  // hoisted: decomposition in, 2 L out, key
-        return gadget_product_core(*ev, levelQ, nullptr, &v[0], *k, v[1], v[2], B);
+        return key_switch(*ev, KS_HOISTED, levelQ, *k, KsAlias{}, GpArgs{nullptr, &v[0], v[1], v[2], B});
     };
-    q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
     return co_dispatch(*be.ctx, dec->batch, q);
 }
 
@@ -3991,24 +3960,19 @@ int he_relinearize(he_handle hev, int level, he_handle hin0, he_handle hin1, he_
     // Aliasing that the batched pipeline cannot take for a whole batch: an output that is the key switch's NTT-domain operand
     // (in2) or the OTHER component's addend.  An output equal to its own component's addend -- Relinearize in place -- is read and
     // written by the same thread and batches normally.
-    const bool alias = cross || o.same(i2, o0) || o.same(i2, o1);
-    q.op = CO_RELINEARIZE; q.obj = ev.get(); q.key = k.get(); q.par[0] = level;
-    q.keep.push_back(ev); q.keep.push_back(k);
-    q.run = [ev, k, level, cross](const View *v, int B) -> int {
+    const KsAlias alias{o.same(i2, o0) || o.same(i2, o1), false, cross};
+    ks_request(q, CO_RELINEARIZE, ev, k, level, KS_GADGET_PRODUCT, alias);
+    q.run = [ev, k, level, cross, alias](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const size_t wQ = (size_t)B * (level + 1) * be.Q->N;
         TRY(keyswitch_begin(*ev, *k, level, 5.0 * (level + 1), true, B, cross ? 2 * wQ + 4 : 0));  // Relinearize: 3 L in, 2 L out, key
+        View a0 = v[0], a1 = v[1];
         if (cross) {  // (served one by one: plain views)
-            View a0{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N}, a1{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N};
+            a0 = View{be.ctx->arena_take(wQ), (size_t)(level + 1) * be.Q->N}; a1 = View{be.ctx->arena_take(wQ), a0.bstride};
             HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, be.ctx->stream));
             HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[1], v[1], a1, B, nullptr, nullptr, be.ctx->stream));
-            return gadget_product_core(*ev, level, &v[2], nullptr, *k, v[3], v[4], B, &a0, &a1);
         }
-        return gadget_product_core(*ev, level, &v[2], nullptr, *k, v[3], v[4], B, &v[0], &v[1]);
-    };
-    q.tables_ok = [ev, k, level, alias](bool *ok) -> int {
-        *ok = false;
-        return alias ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
+        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[2], nullptr, v[3], v[4], B, &a0, &a1});
     };
     return co_dispatch(*be.ctx, o.B, q);
 }
@@ -4037,44 +4001,30 @@ static int cached_auto_index(Evaluator &ev, uint64_t gal, const uint32_t **out) 
 }
 // the launches of Automorphism / AutomorphismHoisted over B entries; the caller holds the context (Scope).  in1: the NTT-domain
 // second component (null when `dec` holds its decomposition).  in0 / in1 / out0 / out1 may carry entry tables (a coalesced batch)
-// when keyswitch_tables_ok() said so.
+// when the route said so.
 static int automorphism_core(Evaluator &ev, int level, View in0, const View *in1, const View *dec, uint64_t gal, const Evk &k, View out0,
-                             View out1, int B) {
+                             View out1, int B, KsAlias alias) {
     BasisExtender &be = *ev.be;
     const int N = be.Q->N;
     const size_t wQ = (size_t)B * (level + 1) * N;
     // Rotate: (4 L + 2 beta (L + alpha)); hoisted: the decomposition replaces the second input
     TRY(keyswitch_begin(ev, k, level, dec ? 3.0 * (level + 1) + key_limbs(k, level) / 2 : 4.0 * (level + 1), !dec, B, 2 * wQ + (size_t)N));
-    hipStream_t st = be.ctx->stream;
-    // The automorphism is applied where the key switch writes its result: the fused ModDown epilogues store coefficient e at
-    // index_{g^-1}[e] (NttEpilogue::scatter_ginv), so that the intermediate ciphertext and the two gather passes over it disappear.
-    // Standard ring only (NthRoot = 2N), and not when an output is an input of its own entry (a thread would read the addend at e
-    // and overwrite another position some other thread still has to read); paths without a fused epilogue report back and get
-    // the gathers.  HERING_NO_AUTO_SCATTER=1 keeps the gathers (A/B).
-    static const bool no_scatter = env_flag("HERING_NO_AUTO_SCATTER");
-    uint32_t ginv = 0;
-    // (entry-table views: aliasing requests never reach a table batch, co_submit_keyswitch)
-    const bool alias = out0.p == in0.p || out1.p == in0.p || (in1 && (out0.p == in1->p || out1.p == in1->p));
-    const FusedPlan *mdplan = nullptr;
-    if (k.nPk > 0) TRY(get_md_plan(ev, level, k.nPk - 1, &mdplan));
-    if (!no_scatter && be.type == 0 && !alias && mdplan && mdplan->ok && epilogue_scatter_supported(be.Q->logN)) {  // (a fused ModDown plan: every path below ends in an epilogue)
-        const uint64_t mask = (2ull << be.Q->logN) - 1;
-        uint64_t x = gal & mask;
-        for (int i = 0; i < 6; i++) x = (x * (2 - gal * x)) & mask;  // Newton: g^-1 mod 2N (g odd)
-        ginv = (uint32_t)x;
+    KsCall c;
+    TRY(ks_call(ev, dec ? KS_AUTOMORPHISM_HOISTED : KS_AUTOMORPHISM, level, k, alias, &c));
+    GpArgs g{in1, dec, out0, out1, B, &in0};
+    // the automorphism is applied where the key switch writes its result ...
+    if (c.route.automorphism == KS_AUTO_EPILOGUE_SCATTER) {
+        g.scatter_ginv = galois_inverse(gal, be.Q->logN);
+        return gadget_product_core(ev, level, k, c, g);
     }
-    if (ginv) {
-        uint32_t applied = ginv;
-        TRY(gadget_product_core(ev, level, in1, dec, k, out0, out1, B, &in0, nullptr, false, nullptr, &applied));
-        if (!applied) return fail(HE_EINVAL, "automorphism: internal error, the fused ModDown plan took a path without its epilogue");
-        return HE_OK;
-    }
+    // ... or by two gather passes over the intermediate ciphertext
     View t0{be.ctx->arena_take(wQ), (size_t)(level + 1) * N}, t1{be.ctx->arena_take(wQ), (size_t)(level + 1) * N};
     const uint32_t *index = nullptr;
     TRY(cached_auto_index(ev, gal, &index));
-    TRY(gadget_product_core(ev, level, in1, dec, k, t0, t1, B, &in0, nullptr));
-    HIP_TRY(launch_gather(be.qp, ident_tab(level + 1), t0, index, out0, B, false, st));
-    HIP_TRY(launch_gather(be.qp, ident_tab(level + 1), t1, index, out1, B, false, st));
+    g.out0 = t0; g.out1 = t1;
+    TRY(gadget_product_core(ev, level, k, c, g));
+    HIP_TRY(launch_gather(be.qp, ident_tab(level + 1), t0, index, out0, B, false, be.ctx->stream));
+    HIP_TRY(launch_gather(be.qp, ident_tab(level + 1), t1, index, out1, B, false, be.ctx->stream));
     return HE_OK;
 }
 static int automorphism_common(he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hdec, uint64_t gal, he_handle hk,
@@ -4097,15 +4047,10 @@ static int automorphism_common(he_handle hev, int level, he_handle hin0, he_hand
     if (dec) TRY(check_decomp(*ev, *dec, level, k->nPk - 1, who));
     gal = reduce_gal(gal, be.Q->logN, be.type);
     // (an automorphism that writes onto its own inputs takes the gather form, which reads them all first: no entry tables then)
-    const bool alias = o.same(i0, o0) || o.same(i0, o1) || o.same(i1, o0) || o.same(i1, o1);
-    q.op = hoisted ? CO_AUTO_HOISTED : CO_AUTOMORPHISM; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = (int64_t)gal;
-    q.keep.push_back(ev); q.keep.push_back(k);
-    q.run = [ev, k, level, gal, hoisted](const View *v, int B) -> int {
-        return automorphism_core(*ev, level, v[0], hoisted ? nullptr : &v[1], hoisted ? &v[1] : nullptr, gal, *k, v[2], v[3], B);
-    };
-    q.tables_ok = [ev, k, level, alias](bool *ok) -> int {
-        *ok = false;
-        return alias ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
+    const KsAlias alias{o.same(i1, o0) || o.same(i1, o1), o.same(i0, o0), o.same(i0, o1)};
+    ks_request(q, hoisted ? CO_AUTO_HOISTED : CO_AUTOMORPHISM, ev, k, level, hoisted ? KS_AUTOMORPHISM_HOISTED : KS_AUTOMORPHISM, alias); q.par[1] = (int64_t)gal;
+    q.run = [ev, k, level, gal, hoisted, alias](const View *v, int B) -> int {
+        return automorphism_core(*ev, level, v[0], hoisted ? nullptr : &v[1], hoisted ? &v[1] : nullptr, gal, *k, v[2], v[3], B, alias);
     };
     return co_dispatch(*be.ctx, o.B, q);
 }
@@ -4140,10 +4085,9 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
     o.inplace(ic + 2, ii);
     TRY(o.check());
     gal = reduce_gal(gal, be.Q->logN, be.type);
-    const bool alias = o.same(ic, ii) || o.same(ic + 2, ii);
+    const KsAlias alias{false, o.same(ic, ii), o.same(ic + 2, ii)};
     const size_t dec_ds = dec->dstride();
-    q.op = CO_AUTO_HOISTED_LAZY; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ; q.par[1] = (int64_t)gal;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_AUTO_HOISTED_LAZY, ev, k, levelQ, KS_FORM_COUNT, KsAlias{}); q.par[1] = (int64_t)gal;
     q.run = [ev, k, levelQ, levelP, gal, alias, dec_ds](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -4158,14 +4102,12 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
         }
         // ONE launch: the key inner product adds ctIn[0] * P to component 0 at the source position and stores all four accumulators
         // through the automorphism (KsScatter) -- instead of inner product, two element-wise passes and four gathers.  Standard
-        // ring, and the outputs must not be the addend (other threads still read it); HERING_NO_AUTO_SCATTER=1: the old sequence.
-        static const bool no_scatter = env_flag("HERING_NO_AUTO_SCATTER");
-        if (!no_scatter && be.type == 0 && !alias) {
+        // ring, and the outputs must not be the addend (other threads still read it).
+        KsCall c;
+        TRY(ks_call(*ev, KS_AUTOMORPHISM_HOISTED_LAZY, levelQ, *k, alias, &c));
+        if (c.route.automorphism == KS_AUTO_KS_SCATTER) {
             KsScatter ks;
-            const uint64_t mask = (2ull << be.Q->logN) - 1;
-            uint64_t x = gal & mask;
-            for (int i = 0; i < 6; i++) x = (x * (2 - gal * x)) & mask;  // Newton: g^-1 mod 2N (g odd)
-            ks.ginv = (uint32_t)x;
+            ks.ginv = galois_inverse(gal, be.Q->logN);
             ks.add0 = v[0];
             for (int i = 0; i <= levelQ; i++) ks.add_s[i] = s.s[i];
             return ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, v[2], v[3], v[4], v[5], B, nullptr, 0, 0, 0, -1, &ks);
@@ -4215,8 +4157,7 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
     TRY(o.check());  // no output may alias an input or another output
     const int B = o.B;
     gal = reduce_gal(gal, be.Q->logN, be.type);
-    q.op = CO_GIANT_STEP; q.obj = ev.get(); q.key = k.get(); q.par[0] = levelQ; q.par[1] = (int64_t)gal; q.par[2] = accumulate ? 1 : 0;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_GIANT_STEP, ev, k, levelQ, KS_GIANT_STEP, KsAlias{}); q.par[1] = (int64_t)gal; q.par[2] = accumulate ? 1 : 0;
     q.run = [ev, k, levelQ, levelP, gal, accumulate](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -4227,24 +4168,21 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
         { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), true, true); V.into(*be.ctx, B); }
         const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
         TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, levelP, B, true, k.get()) + 2 * B * (sQw + sPw) + 64));
-        const FusedPlan *plan = nullptr;
-        if (!k->pw2) TRY(get_dec_plan(*ev, levelQ, levelP, levelP + 1, &plan));
-        static const bool no_scatter = env_flag("HERING_NO_AUTO_SCATTER") || env_flag("HERING_NO_GIANT_FUSION");
-        const bool fuse = !no_scatter && be.type == 0 && plan && plan->ok && (!k->keyd || ntt_mac_giant_supported(be.Q->logN));
-        if (fuse) {
+        KsCall c;
+        TRY(ks_call(*ev, KS_GIANT_STEP, levelQ, *k, KsAlias{}, &c));
+        if (c.route.giant_fused) {
             KsScatter ks;
-            const uint64_t mask = (2ull << be.Q->logN) - 1;
-            uint64_t x = gal & mask;
-            for (int i = 0; i < 6; i++) x = (x * (2 - gal * x)) & mask;  // Newton: g^-1 mod 2N (g odd)
-            ks.ginv = (uint32_t)x;
+            ks.ginv = galois_inverse(gal, be.Q->logN);
             ks.plain = 1; ks.add0 = v[1]; ks.add0P = v[2]; ks.accumulate = acc ? 1 : 0;
             for (int i = 0; i < kMaxLimbs; i++) ks.add_s[i] = 0;
-            return gadget_product_lazy_core(*ev, levelQ, v[0], B, *k, v[3], v[4], v[5], v[6], false, nullptr, nullptr, nullptr, &ks);
+            LazyArgs a{v[0], B, v[3], v[4], v[5], v[6]};
+            a.giant = &ks;
+            return gadget_product_lazy_core(*ev, levelQ, *k, c, a);
         }
         // the separate calls' launches
         View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw};
         View t0P{be.ctx->arena_take(B * sPw), sPw}, t1P{be.ctx->arena_take(B * sPw), sPw};
-        TRY(gadget_product_lazy_core(*ev, levelQ, v[0], B, *k, t0Q, t0P, t1Q, t1P));
+        TRY(gadget_product_lazy_core(*ev, levelQ, *k, c, LazyArgs{v[0], B, t0Q, t0P, t1Q, t1P}));
         const uint32_t *index = nullptr;
         TRY(cached_auto_index(*ev, gal, &index));
         hipStream_t st = be.ctx->stream;
@@ -4255,14 +4193,6 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
         HIP_TRY(launch_gather(be.qp, tp, t0P, index, v[4], B, acc, st));
         HIP_TRY(launch_gather(be.qp, tq, t1Q, index, v[5], B, acc, st));
         HIP_TRY(launch_gather(be.qp, tp, t1P, index, v[6], B, acc, st));
-        return HE_OK;
-    };
-    q.tables_ok = [ev, k, levelQ](bool *ok) -> int {
-        *ok = false;
-        if (k->pw2 || k->nPk <= 0) return HE_OK;
-        const FusedPlan *plan = nullptr;
-        TRY(get_dec_plan(*ev, levelQ, k->nPk - 1, k->nPk, &plan));
-        *ok = plan->ok;
         return HE_OK;
     };
     return co_dispatch(*be.ctx, B, q);
@@ -4412,9 +4342,9 @@ int he_lintrans_mul_sum(he_handle hev, int levelQ, int levelP, int n, const he_h
 
 // CKKS mulRelin / BGV tensorStandard (schemes/ckks/evaluator.go:764-872, schemes/bgv/evaluator.go:592-685)
 // The launches of one call over B entries; the caller holds the context (Scope).  `alias`: some output is an input of its own
-// entry.  The views may carry entry tables (a coalesced batch) when mul_relin_tables_ok() said so.
+// entry.  The views may carry entry tables (a coalesced batch) when the route said so.
 static int mul_relin_core(Evaluator &ev, int level, bool bgv, uint64_t t, Evk *k, View a0, View a1, View b0, View b1, View o0v, View o1v,
-                          View o2v, int B, bool alias) {
+                          View o2v, int B, KsAlias alias) {
     BasisExtender &be = *ev.be;
     std::vector<uint64_t> sc_(level + 1);
     for (int i = 0; i <= level; i++) {
@@ -4443,44 +4373,19 @@ static int mul_relin_core(Evaluator &ev, int level, bool bgv, uint64_t t, Evk *k
     }
     TRY(be.ctx->arena_reserve(ks_scratch_words(be, level, k->nPk - 1, B, true, k) + wQ));
     View c2{be.ctx->arena_take(wQ), (size_t)(level + 1) * N};
-    // With a fused ModDown the tensor kernel forms c2 only: c0 / c1 are computed from the inputs where they are added, in the
-    // ModDown epilogue (24 limbs of writes and 24 of reads fewer; the inputs' second read comes from L2).  Not when an output
-    // aliases an input: the epilogue of one component would overwrite words the other still reads.
-    static const bool no_fuse = env_flag("HERING_NO_TENSOR_EPILOGUE");
-    const FusedPlan *mdplan = nullptr;
-    const bool may_fuse = k->nPk > 0 && !alias && !no_fuse;  // a P-less (base-2) key has no ModDown to fuse into
-    if (may_fuse) TRY(get_md_plan(ev, level, k->nPk - 1, &mdplan));
-    if (may_fuse && mdplan->ok) {
-        // (c2 = T(a1, b1) is formed on the way: by the inverse row pass for the double-precision limbs, by the tensor kernel for the others)
-        TensorIn tin{a0, a1, b0, b1, sc_.data(), true};
-        return gadget_product_core(ev, level, &c2, nullptr, *k, o0v, o1v, B, nullptr, nullptr, true, &tin);
+    KsCall c;
+    TRY(ks_call(ev, KS_MUL_RELIN, level, *k, alias, &c));
+    GpArgs g{&c2, nullptr, o0v, o1v, B, nullptr, nullptr, true};  // c2 is formed here: canonical
+    // With the tensor terms in the ModDown epilogue the tensor kernel forms c2 only, and that on the way: by the inverse row pass
+    // for the double-precision limbs, by the tensor kernel for the others (24 limbs of writes and 24 of reads fewer; the inputs'
+    // second read comes from L2).
+    const TensorIn tin{a0, a1, b0, b1, sc_.data()};
+    if (c.route.tensor_epilogue) g.tin = &tin;
+    else {
+        HIP_TRY(launch_tensor(be.qp, ident_tab(level + 1), sc_.data(), a0, a1, b0, b1, o0v, o1v, c2, B, st));
+        g.add0 = &o0v; g.add1 = &o1v;
     }
-    HIP_TRY(launch_tensor(be.qp, ident_tab(level + 1), sc_.data(), a0, a1, b0, b1, o0v, o1v, c2, B, st));
-    return gadget_product_core(ev, level, &c2, nullptr, *k, o0v, o1v, B, &o0v, &o1v, true);  // c2 from the tensor kernel: canonical
-}
-// May a coalesced MulRelin address its callers' polynomials through entry tables?  Every launch that touches them must be one
-// of the table-capable ones (kernels.h, View::tab): that is the case exactly when ModDown runs through the fused plan -- then
-// the inputs are read by the tensor kernel, the product prologue and the epilogues only, and the outputs written by the epilogues.
-static int mul_relin_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok) {
-    *ok = false;
-    if (k.nPk <= 0) return HE_OK;
-    const FusedPlan *mdplan = nullptr;
-    TRY(get_md_plan(ev, level, k.nPk - 1, &mdplan));
-    *ok = mdplan->ok;
-    return HE_OK;
-}
-
-// The same question for the key switches proper (GadgetProduct, Relinearize, Automorphism): their NTT-domain operand is read by
-// the inverse row pass and as the digits' own limbs, the addends and outputs by the epilogues (Automorphism: the final gathers) --
-// provided both fused plans exist (no base-2 gadget, special primes present, standard ring).
-static int keyswitch_tables_ok(Evaluator &ev, int level, const Evk &k, bool *ok) {
-    *ok = false;
-    if (k.nPk <= 0 || k.pw2) return HE_OK;
-    const FusedPlan *dplan = nullptr, *mdplan = nullptr;
-    TRY(get_dec_plan(ev, level, k.nPk - 1, k.nPk, &dplan));
-    TRY(get_md_plan(ev, level, k.nPk - 1, &mdplan));
-    *ok = dplan->ok && mdplan->ok;
-    return HE_OK;
+    return gadget_product_core(ev, level, *k, c, g);
 }
 
 static int mul_relin_common(he_handle hev, int level, bool bgv, uint64_t t, he_handle ha0, he_handle ha1, he_handle hb0, he_handle hb1,
@@ -4506,15 +4411,13 @@ static int mul_relin_common(he_handle hev, int level, bool bgv, uint64_t t, he_h
     o.out(k ? nullptr : o.poly(hout2), level + 1, "out2 (required when no relinearization key is given)");  // an output only without a key
     o.all_inplace = true;  // any output may be any input (MulRelin(res, res, res))
     TRY(o.check());
-    bool alias = false;
-    for (int in = i0; in < i0 + 4; in++) alias = alias || o.same(o0, in) || o.same(o1, in);
+    KsAlias alias;
+    for (int in = i0; in < i0 + 4; in++) alias.out_is_addend = alias.out_is_addend || o.same(o0, in) || o.same(o1, in);
     // (a degree-2 output that is one of the inputs: the tensor kernel reads all four inputs of a coefficient before it writes)
-    q.op = k ? CO_MUL_RELIN : CO_MUL; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = bgv; q.par[2] = (int64_t)(bgv ? t : 0);
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, k ? CO_MUL_RELIN : CO_MUL, ev, k, level, KS_MUL_RELIN, alias); q.par[1] = bgv; q.par[2] = (int64_t)(bgv ? t : 0);
     q.run = [ev, k, level, bgv, t, alias](const View *v, int B) -> int {
         return mul_relin_core(*ev, level, bgv, t, k.get(), v[0], v[1], v[2], v[3], v[4], v[5], v[6], B, alias);
     };
-    if (k) q.tables_ok = [ev, k, level](bool *ok) -> int { return mul_relin_tables_ok(*ev, level, *k, ok); };
     return co_dispatch(*be.ctx, o.B, q);
 }
 int he_ckks_mul_relin(he_handle ev, int level, he_handle a0, he_handle a1, he_handle b0, he_handle b1, he_handle rlk, he_handle o0, he_handle o1, he_handle o2) {
@@ -4658,12 +4561,12 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
     // as in he_relinearize: an output that is the key switch's operand (in1) or the OTHER component's addend (in0 == out1) cannot be
     // batched; the crossed case stages the addend first (component 1's epilogue would overwrite it before component 0 reads it)
     const bool cross = o.same(i0, o1);
-    const bool alias = cross || o.same(i1, o0) || o.same(i1, o1);
+    KsAlias alias;  // (of the key switch proper: the degree-changing forms run it on scratch)
+    if (form == AEK_SAME) { alias.out_is_operand = o.same(i1, o0) || o.same(i1, o1); alias.crossed = cross; }
     const int n_small = std::min(Nin, Nout);
     const std::vector<uint64_t> gapinv = form == AEK_DOWN ? fold_constants(be.Q->moduli, level, lg) : std::vector<uint64_t>();
-    q.op = CO_APPLY_EVK; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = form; q.par[2] = lg;
-    q.keep.push_back(ev); q.keep.push_back(k);
-    q.run = [ev, k, level, form, lg, n_small, cross, gapinv](const View *v, int B) -> int {
+    ks_request(q, CO_APPLY_EVK, ev, k, level, form == AEK_SAME ? KS_GADGET_PRODUCT : KS_FORM_COUNT, alias); q.par[1] = form; q.par[2] = lg;
+    q.run = [ev, k, level, form, lg, n_small, cross, alias, gapinv](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
         const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
@@ -4671,12 +4574,12 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
         TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, form == AEK_SAME ? (cross ? wQ + 2 : 0) : 2 * wQ + 2));
         hipStream_t st = be.ctx->stream;
         if (form == AEK_SAME) {
+            View a0 = v[0];
             if (cross) {  // (served one by one: plain views)
-                View a0{be.ctx->arena_take(wQ), sQ};
+                a0 = View{be.ctx->arena_take(wQ), sQ};
                 HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, st));
-                return gadget_product_core(*ev, level, &v[1], nullptr, *k, v[2], v[3], B, &a0, nullptr);
             }
-            return gadget_product_core(*ev, level, &v[1], nullptr, *k, v[2], v[3], B, &v[0], nullptr);
+            return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, v[2], v[3], B, &a0});
         }
         // both components at degree N in scratch, [2][B] entries: the key switch's result (down) or the replicated input (up)
         uint64_t *t = be.ctx->arena_take(2 * wQ);
@@ -4684,7 +4587,7 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
         RingSwitchIO io;
         io.zsplit = B;
         if (form == AEK_DOWN) {
-            TRY(gadget_product_core(*ev, level, &v[1], nullptr, *k, t0, t1, B, &v[0], nullptr));
+            TRY(key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, t0, t1, B, &v[0]}));
             io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3];
             be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, N);
             { Valu V(be.Q->logN - lg); V.mul(false, 2.0 * (level + 1)); V.into(*be.ctx, B); }  // (integer products on every limb)
@@ -4694,12 +4597,10 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
         io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1;
         be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, N);
         HIP_TRY(launch_ring_degree_replicate_ntt(ident_tab(level + 1), io, n_small, lg, 2 * B, st));
-        return gadget_product_core(*ev, level, &t1, nullptr, *k, v[2], v[3], B, &t0, nullptr);
+        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&t1, nullptr, v[2], v[3], B, &t0});
     };
-    q.tables_ok = [ev, k, level, form, alias](bool *ok) -> int {
-        *ok = false;
-        return (form != AEK_SAME || alias) ? HE_OK : keyswitch_tables_ok(*ev, level, *k, ok);
-    };
+    // (the ring maps of the degree-changing forms take no entry tables)
+    if (form != AEK_SAME) q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
     return co_dispatch(*be.ctx, o.B, q);
 }
 
@@ -4840,8 +4741,7 @@ int he_ringpack_split(he_handle hev, int level, he_handle hin0, he_handle hin1, 
     o.out(o.opt(ho1), level + 1, "odd1", B, n);
     TRY(o.check());
     const bool has_odd = ho0 != 0;
-    q.op = CO_RINGPACK_CT; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = 0; q.par[2] = has_odd;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_RINGPACK_CT, ev, k, level, KS_FORM_COUNT, KsAlias{}); q.par[1] = 0; q.par[2] = has_odd;
     q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -4849,7 +4749,7 @@ int he_ringpack_split(he_handle hev, int level, he_handle hin0, he_handle hin1, 
         TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));  // the key switch: 2 L in, 2 L out, key
         uint64_t *t = be.ctx->arena_take(2 * wQ);
         const View t0{t, sQ}, t1{t + wQ, sQ};
-        TRY(gadget_product_core(*ev, level, &v[1], nullptr, *k, t0, t1, B, &v[0], nullptr));
+        TRY(key_switch(*ev, KS_GADGET_PRODUCT, level, *k, KsAlias{}, GpArgs{&v[1], nullptr, t0, t1, B, &v[0]}));
         RingPackIO io;
         io.zsplit = B;
         io.x[0] = t0; io.x[1] = t1; io.o[0] = v[2]; io.o[1] = v[3]; io.p[0] = v[4]; io.p[1] = v[5];
@@ -4878,8 +4778,7 @@ int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he
     o.out(hout1, level + 1, "ctN[1]");
     TRY(o.check());
     const bool has_odd = ho0 != 0;
-    q.op = CO_RINGPACK_CT; q.obj = ev.get(); q.key = k.get(); q.par[0] = level; q.par[1] = 1; q.par[2] = has_odd;
-    q.keep.push_back(ev); q.keep.push_back(k);
+    ks_request(q, CO_RINGPACK_CT, ev, k, level, KS_FORM_COUNT, KsAlias{}); q.par[1] = 1; q.par[2] = has_odd;
     q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
         const int N = be.Q->N;
@@ -4891,7 +4790,7 @@ int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he
         io.zsplit = B;
         io.x[0] = v[0]; io.x[1] = v[1]; io.y[0] = v[2]; io.y[1] = v[3]; io.o[0] = t0; io.o[1] = t1;
         TRY(rp_merge_launch(*be.ctx, *be.Q, io, has_odd, level, B, 2));
-        return gadget_product_core(*ev, level, &t1, nullptr, *k, v[4], v[5], B, &t0, nullptr);
+        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, KsAlias{}, GpArgs{&t1, nullptr, v[4], v[5], B, &t0});
     };
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
     return co_dispatch(*be.ctx, B, q);
@@ -5119,8 +5018,12 @@ int rgsw_generic(Evaluator &ev, const Evk &ka, const Evk &kb, const RgswShape &s
         const View cx = k ? in1 : in0;
         const View o0Q{acc[k], W}, o1Q{acc[k] + (size_t)B * W, W};
         const View o0P = levelP < 0 ? none : View{acc[k] + sQw, W}, o1P = levelP < 0 ? none : View{acc[k] + (size_t)B * W + sQw, W};
-        if (s.multiple_p) TRY(gadget_product_lazy_core(ev, levelQ, cx, B, key, o0Q, o0P, o1Q, o1P));
-        else TRY(window_products_core(ev, levelQ, cx, B, key, true, o0Q, o0P, o1Q, o1P));
+        const LazyArgs a{cx, B, o0Q, o0P, o1Q, o1P};
+        KsCall c;
+        if (s.multiple_p) {  // (RNS digits; a base-2 gadget takes at most one special prime, he_evk_create_base2)
+            TRY(ks_call(ev, KS_LAZY, levelQ, key, KsAlias{}, &c));
+            TRY(gadget_product_lazy_core(ev, levelQ, key, c, a));
+        } else TRY(window_products_core(ev, levelQ, key, a, true));
     }
     if (levelP < 0) {  // ModDown's levelP == -1 branch is a copy: the sum goes straight to the outputs
         const LimbTab tq = ident_tab(levelQ + 1);

@@ -22,7 +22,9 @@ TESTS = ["tests/test_gpu_headline.py::test_full_size_config3_bgv_mulrelin_logN15
          "tests/test_gpu_rlwe.py::test_lintrans_giant_step", "tests/test_gpu_circuits.py::test_lintrans",
          "tests/test_gpu_aliasing.py::test_aliasing_patterns[he_lintrans_giant_step-off]",
          "tests/test_gpu_aliasing.py::test_aliasing_patterns[he_lintrans_giant_step-queue]",
-         "tests/test_gpu_aliasing.py::test_aliasing_patterns[he_lintrans_giant_step-deferred]"]
+         "tests/test_gpu_aliasing.py::test_aliasing_patterns[he_lintrans_giant_step-deferred]",
+         # the launch census: every route's launch profile and output words as recorded under these switches
+         "tests/test_gpu_keyswitch_routes.py"]
 
 
 @pytest.mark.parametrize("pair", PAIRS, ids=["+".join(s.replace("HERING_NO_", "no_").lower() for s in p) for p in PAIRS])
