@@ -27,6 +27,7 @@
 #include "hering_ringswitch.h"
 #include "hering_ringpack.h"
 #include "hering_rgsw.h"
+#include "hering_blindrot.h"
 
 namespace hering {
 
@@ -735,6 +736,69 @@ public:
     }
 };
 }  // namespace rgsw
+
+// ---- blind rotation (core/rgsw/blindrot; hering_blindrot.h), NTT domain ---------------------------------------------------------
+// The device entries only: Evaluate's prologue (the switch to modulus 2N and the accumulators' initial values) is the caller's.
+namespace blindrot {
+// a table of RGSW ciphertexts resident on the device (BlindRotationEvaluationKeySet's blind rotation keys)
+class RGSWKeySet {
+    detail::Ref r_;
+    std::vector<rgsw::Ciphertext> keys_;
+
+public:
+    RGSWKeySet(const hering::Evaluator &ev, const std::vector<rgsw::Ciphertext> &keys) : keys_(keys) {
+        std::vector<he_handle> k0, k1;
+        for (const rgsw::Ciphertext &k : keys) { k0.push_back(k.Value[0].h()); k1.push_back(k.Value[1].h()); }
+        he_handle h = 0;
+        check(he_rgsw_keyset_create(ev.h(), (int)keys.size(), k0.data(), k1.data(), &h));
+        r_ = detail::own(h, he_rgsw_keyset_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    size_t size() const { return keys_.size(); }
+};
+// the Galois keys of a blind rotation with their Galois elements and index tables (GetEvaluationKeySet, keys.go:41)
+class GaloisKeySet {
+    detail::Ref r_;
+    std::vector<uint64_t> galEls_;
+    std::vector<EvaluationKey> keys_;
+
+public:
+    GaloisKeySet(const hering::Evaluator &ev, const std::vector<uint64_t> &galEls, const std::vector<EvaluationKey> &keys) : galEls_(galEls), keys_(keys) {
+        if (galEls.size() != keys.size()) throw std::invalid_argument("GaloisKeySet: one Galois element per key");
+        std::vector<he_handle> k;
+        for (const EvaluationKey &e : keys) k.push_back(e.h());
+        he_handle h = 0;
+        check(he_galois_keyset_create(ev.h(), (int)keys.size(), galEls.data(), k.data(), &h));
+        r_ = detail::own(h, he_galois_keyset_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    const std::vector<uint64_t> &GaloisElements() const { return galEls_; }
+};
+// MemBlindRotationEvaluationKeySet (keys.go:32)
+struct MemBlindRotationEvaluationKeySet {
+    RGSWKeySet rgsw;
+    GaloisKeySet galois;
+};
+// batch entry b of ctIn through rlwe.Evaluator.Automorphism with key sel[b] of the set; sel[b] == -1 passes the entry through
+inline void AutomorphismSelect(const hering::Evaluator &ev, const Ciphertext &ctIn, const GaloisKeySet &keys, const std::vector<int32_t> &sel,
+                               Ciphertext &opOut) {
+    check(he_automorphism_ct_select(ev.h(), ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), keys.h(), sel.data(), (int)sel.size(),
+                                    opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+}
+// blindrot.Evaluator (evaluator.go:16), BlindRotateCore only
+class Evaluator {
+    rgsw::Evaluator ev_;
+
+public:
+    explicit Evaluator(const rgsw::Evaluator &ev) : ev_(ev) {}
+    // BlindRotateCore (:135) for every batch entry of acc, in place: a holds one row of n_lwe words mod 2N per entry
+    void BlindRotateCore(const std::vector<uint64_t> &a, int n_lwe, Ciphertext &acc, const MemBlindRotationEvaluationKeySet &BRK) const {
+        if (n_lwe < 1 || a.size() % (size_t)n_lwe != 0) throw std::invalid_argument("BlindRotateCore: rows of n_lwe words");
+        check(he_blind_rotate_core(ev_.h(), a.data(), (int)(a.size() / (size_t)n_lwe), n_lwe, acc.Value.at(0).h(), acc.Value.at(1).h(),
+                                   BRK.rgsw.h(), BRK.galois.h()));
+    }
+};
+}  // namespace blindrot
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

@@ -91,6 +91,16 @@ int he_debug_replay(he_handle ctx, const uint64_t *program, size_t n_words, int 
  * microseconds inside the calls of function f summed over the threads, out[3 f + 1] = calls, out[3 f + 2] = longest call */
 int he_debug_replay_profile(uint64_t *out, int n_fn, int reset);
 
+/* The schedule he_blind_rotate_core (hering_blindrot.h) follows, computed on the host (csrc/blindrot_plan.h; no device needed).
+ * One row a[n_lwe] of words mod 2N, N = 2^logN: the operations BlindRotateCore applies to that row's accumulator, in order, as
+ * pairs ops[2 i] = kind (0: Automorphism, 1: ExternalProduct), ops[2 i + 1] = the Galois element / the index of the blind
+ * rotation key.  *n_ops receives the length of the list; at most cap pairs are written.  HE_EINVAL for a non-zero even a[i]. */
+int he_debug_blindrot_schedule(int logN, const uint64_t *a, int n_lwe, uint64_t *ops, size_t cap, size_t *n_ops);
+/* the merged rounds of a batch of rows a[batch][n_lwe]: rounds[(2 r) batch + b] = the Galois element entry b's automorphism of
+ * round r takes (0: none), rounds[(2 r + 1) batch + b] = the key of its external product (-1: none).  *n_rounds receives the
+ * number of rounds; at most cap rounds are written. */
+int he_debug_blindrot_rounds(int logN, const uint64_t *a, int batch, int n_lwe, int64_t *rounds, size_t cap, size_t *n_rounds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HERING_LIB: A/B-test another build
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
-         os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h")]
+         os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -120,6 +120,11 @@ def _declare(L):
         "he_rgsw_external_product": [H, H, H, H, H, H, H], "he_rgsw_keyset_create": [H, i, HP, HP, HP], "he_rgsw_keyset_destroy": [H],
         "he_rgsw_external_product_select": [H, H, H, H, C.POINTER(C.c_int32), i, H, H],
         "he_rgsw_key_op": [i, H, H, H, H], "he_rgsw_key_add_plaintext_lazy": [H, H, H],
+        "he_galois_keyset_create": [H, i, u64p, HP, HP], "he_galois_keyset_destroy": [H],
+        "he_automorphism_ct_select": [H, H, H, H, C.POINTER(C.c_int32), i, H, H],
+        "he_blind_rotate_core": [H, u64p, i, i, H, H, H, H],
+        "he_debug_blindrot_schedule": [i, u64p, i, u64p, sz, C.POINTER(sz)],
+        "he_debug_blindrot_rounds": [i, u64p, i, i, C.POINTER(C.c_int64), sz, C.POINTER(sz)],
         "he_automorphism_ct": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted": [H, i, H, H, C.c_uint64, H, H, H],
         "he_automorphism_hoisted_lazy": [H, i, H, H, C.c_uint64, H, H, H, H, H],
@@ -196,7 +201,10 @@ _TRACE_FNS = {
 # the product entries of include/hering_rgsw.h, numbered on from the table above (a table of their own: the numbering of each
 # earlier header is pinned by that header's tests)
 _TRACE_FNS_RGSW = {"he_rgsw_external_product": (63, "hhhhhhh"), "he_rgsw_external_product_select": (64, "hhhhAihh")}
-# length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments)
+# the entries of include/hering_blindrot.h, numbered on in a table of their own
+_TRACE_FNS_BLINDROT = {"he_automorphism_ct_select": (65, "hhhhAihh"), "he_blind_rotate_core": (66, "hAiihhhh")}
+# length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments); a
+# tuple of indices: the product of those arguments
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
               ("he_mul_scalar_bigint", 3): (4, 0), ("he_mul_scalar_bigint_then_add", 3): (4, 0), ("he_double_rns_scalarop", 4): (1, 1),
               ("he_double_rns_scalarop", 5): (1, 1), ("he_rescale_polys", 4): (3, 0), ("he_rescale_polys", 5): (3, 0)}
@@ -204,13 +212,15 @@ _TRACE_LEN.update({("he_lintrans_mul_sum", k): (3, 0) for k in range(4, 11)})
 _TRACE_LEN.update({("he_ringpack_pack_pre", k): (3, 0) for k in range(4, 8)})
 _TRACE_LEN.update({("he_ringpack_pack_post", k): (2, 0) for k in range(3, 7)})
 _TRACE_LEN[("he_rgsw_external_product_select", 4)] = (5, 0)
+_TRACE_LEN[("he_automorphism_ct_select", 4)] = (5, 0)
+_TRACE_LEN[("he_blind_rotate_core", 1)] = ((2, 3), 0)
 # calls a replay has no use for: they read, wait or account, and do not change what the replayed calls see
 _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start", "he_timer_stop", "he_poly_download", "he_poly_shape",
                  "he_poly_download_limb", "he_prof_begin", "he_prof_end", "he_prof_end_bytes", "he_ctx_coalescing_stats",
                  "he_evaluator_coalescing_stats", "he_version", "he_device_info", "he_ring_constant", "he_ring_roots", "he_decomp_download_limb",
                  # a Ring owns itself (Ring._owner), so an unreachable one is released by the cycle collector, whenever that runs:
                  # no later call of the recording can name it
-                 "he_ring_destroy"}
+                 "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds"}
 _trace = None
 
 
@@ -231,7 +241,7 @@ def trace_begin():
     import inspect  # noqa: F401
 
     def wrap(name, fn):
-        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name)
+        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name)
 
         def call(*a):
             rc = fn(*a)
@@ -254,7 +264,10 @@ def trace_begin():
                     w += [2, int(x._obj.value)]
                 else:
                     src, plus = _TRACE_LEN[(name, k)]
-                    n = int(_val(a[src])) + plus
+                    if isinstance(src, tuple):
+                        n = plus + int(_val(a[src[0]])) * int(_val(a[src[1]]))
+                    else:
+                        n = int(_val(a[src])) + plus
                     if x is None or n <= 0:
                         w += [5] if x is None else [3 if kind == "A" else 4, 0]
                     else:

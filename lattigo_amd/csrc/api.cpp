@@ -41,9 +41,11 @@
 #include "../../include/hering_ringswitch.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
+#include "../../include/hering_blindrot.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "ks_route.h"
+#include "blindrot_plan.h"
 
 using namespace he;
 
@@ -70,7 +72,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET };
 
 struct Obj {
     ObjType type;
@@ -98,7 +100,7 @@ enum CoOp {
     CO_NTT, CO_EW, CO_EW_DOUBLE, CO_SHIFT, CO_RESCALE, CO_GATHER, CO_AUTO_COEFF, CO_MODUP, CO_MODDOWN_BE,
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
-    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW
+    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -5068,6 +5070,33 @@ int rgsw_operands(Operands &o, int nQ, he_handle in0, he_handle in1, he_handle o
 }
 }  // namespace
 
+namespace {
+bool rgsw_no_fused() {
+    static const bool v = env_flag("HERING_NO_RGSW_FUSED");
+    return v;
+}
+// the launches of he_rgsw_external_product over B entries (s.fused: the one-launch kernel); the caller holds the context
+int rgsw_product_run(Evaluator &ev, const Evk &k0, const Evk &k1, const RgswShape &s, const View *v, int B) {
+    BasisExtender &be = *ev.be;
+    rgsw_account(ev, k0, s, B);
+    if (!s.fused) {
+        // both components of the batch go in one launch, 2 B entries along the grid's z: chunks of at most 32767 entries
+        for (int b0 = 0; b0 < B; b0 += 32767) {
+            View c[4];
+            for (int i = 0; i < 4; i++) c[i] = View{v[i].p + (size_t)b0 * v[i].bstride, v[i].bstride};
+            be.ctx->arena_reset();
+            TRY(rgsw_generic(ev, k0, k1, s, c[0], c[1], c[2], c[3], std::min(32767, B - b0)));
+        }
+        return HE_OK;
+    }
+    RgswFusedArgs a;
+    rgsw_fused_args(a, be, k0, s, v[0], v[1], v[2], v[3]);
+    a.key0 = k0.d; a.key1 = k1.d;
+    HIP_TRY(launch_rgsw_fused(be.qp, a, B, be.ctx->stream));
+    return HE_OK;
+}
+}  // namespace
+
 int he_rgsw_external_product(he_handle hev, he_handle in0, he_handle in1, he_handle hk0, he_handle hk1, he_handle out0, he_handle out1) {
     static const char *who = "he_rgsw_external_product";
     GET(ev, Evaluator, hev, T_EVAL);
@@ -5077,32 +5106,13 @@ int he_rgsw_external_product(he_handle hev, he_handle in0, he_handle in1, he_han
     RgswShape s;
     TRY(rgsw_shape(who, *ev, *k0, *k1, &s));
     TRY(rgsw_key_words(who, *ev, *k0, *k1, s));
-    static const bool no_fused = env_flag("HERING_NO_RGSW_FUSED");
-    if (no_fused) s.fused = false;
+    if (rgsw_no_fused()) s.fused = false;
     CoReq q;
     Operands o(q, who, be);
     TRY(rgsw_operands(o, s.levelQ + 1, in0, in1, out0, out1));
     q.op = CO_RGSW; q.obj = ev.get(); q.key = k0.get(); q.par[0] = (int64_t)(uintptr_t)k1.get(); q.par[1] = 0;
     q.keep.push_back(ev); q.keep.push_back(k0); q.keep.push_back(k1);
-    q.run = [ev, k0, k1, s](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        rgsw_account(*ev, *k0, s, B);
-        if (!s.fused) {
-            // both components of the batch go in one launch, 2 B entries along the grid's z: chunks of at most 32767 entries
-            for (int b0 = 0; b0 < B; b0 += 32767) {
-                View c[4];
-                for (int i = 0; i < 4; i++) c[i] = View{v[i].p + (size_t)b0 * v[i].bstride, v[i].bstride};
-                be.ctx->arena_reset();
-                TRY(rgsw_generic(*ev, *k0, *k1, s, c[0], c[1], c[2], c[3], std::min(32767, B - b0)));
-            }
-            return HE_OK;
-        }
-        RgswFusedArgs a;
-        rgsw_fused_args(a, be, *k0, s, v[0], v[1], v[2], v[3]);
-        a.key0 = k0->d; a.key1 = k1->d;
-        HIP_TRY(launch_rgsw_fused(be.qp, a, B, be.ctx->stream));
-        return HE_OK;
-    };
+    q.run = [ev, k0, k1, s](const View *v, int B) -> int { return rgsw_product_run(*ev, *k0, *k1, s, v, B); };
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (queued calls are served one by one, as other base-2 shapes)
     return co_dispatch(*be.ctx, o.B, q);
 }
@@ -5280,6 +5290,281 @@ int he_rgsw_key_add_plaintext_lazy(he_handle hpt, he_handle hk0, he_handle hk1) 
     }
     TRY(evk_derive(*k0));
     return evk_derive(*k1);
+}
+
+// ---------------------------------------------------------------------------------------
+// Blind rotation (include/hering_blindrot.h; core/rgsw/blindrot/evaluator.go)
+// ---------------------------------------------------------------------------------------
+namespace {
+// BlindRotationEvaluationKeySet's automorphism keys: Galois keys of one shape with their Galois elements
+struct GaloisSet : Obj {
+    std::shared_ptr<Evaluator> ev;
+    std::vector<std::shared_ptr<Evk>> keys;
+    std::vector<uint64_t> gal;
+    size_t *d_tab = nullptr;      // [2][n] device addresses: the keys' words | their index tables: what the select form indexes
+    uint32_t *d_index = nullptr;  // [n][N] AutomorphismNTTWithIndex tables
+    GaloisSet() : Obj(T_GALOIS_SET) {}
+    ~GaloisSet() override {
+        if (!d_tab && !d_index) return;
+        hipSetDevice(ev->be->ctx->dev);
+        hipStreamSynchronize(ev->be->ctx->stream);
+        if (d_tab) hipFree(d_tab);
+        if (d_index) hipFree(d_index);
+    }
+    int find(uint64_t g) const {
+        for (size_t i = 0; i < gal.size(); i++)
+            if (gal[i] == g) return (int)i;
+        return -1;
+    }
+};
+// inside the domain of launch_auto_fused (hering_blindrot.h)?
+bool auto_select_domain(const Evaluator &ev, const Evk &k) {
+    const BasisExtender &be = *ev.be;
+    bool ok = be.type == 0 && k.pw2 != 0 && k.nPk <= 1 && rgsw_fused_supported(be.Q->logN, k.nQk);
+    for (int i = 0; ok && i < k.nQk; i++) ok = (k.nj[i] - 1) * k.pw2 < 64 && k.prefix[i] < 256;
+    return ok;
+}
+struct GaloisShape : RgswShape {
+    explicit GaloisShape(const Evk &k) { levelQ = k.nQk - 1; levelP = k.nPk - 1; }
+};
+// the bytes and arithmetic of `used` automorphisms with keys of shape k and of B - used copies
+void auto_select_account(Evaluator &ev, const Evk &k, int used, int B) {
+    BasisExtender &be = *ev.be;
+    const int level = k.nQk - 1;
+    if (used) {
+        be.ctx->acct(4.0 * (level + 1) + key_limbs(k, level), 0, used, be.Q->N);  // (every entry reads its own key)
+        Valu V(be.Q->logN);
+        valu_gadget_product(V, be, level, k.nPk - 1, key_beta(k, level), true);
+        V.into(*be.ctx, used);
+    }
+    be.ctx->acct(4.0 * (level + 1), 0, B - used, be.Q->N);
+}
+// what he_blind_rotate_core decided on the host before it filed its request
+struct BlindrotPlan {
+    std::vector<std::vector<blindrot::Op>> lists;  // per entry (every Galois element has a key in the set)
+    // the batched route: [rounds][2][B] selections (automorphism | external product) and which launches have something to do
+    std::vector<int32_t> sel;
+    std::vector<uint8_t> any;  // [rounds][2]
+    size_t n_auto = 0, n_prod = 0;
+};
+int blindrot_batched(Evaluator &ev, const RgswSet &rset, const GaloisSet &gset, const RgswShape &s, const BlindrotPlan &p, View acc0,
+                     View acc1, int B) {
+    BasisExtender &be = *ev.be;
+    hipStream_t st = be.ctx->stream;
+    // the selections of every round, two int32 per word, into scratch from kernel arguments (as the select forms do)
+    std::vector<size_t> tab((p.sel.size() + 1) / 2, 0);
+    for (size_t i = 0; i < p.sel.size(); i++) tab[i / 2] |= (size_t)(uint32_t)p.sel[i] << (32 * (i & 1));
+    TRY(be.ctx->arena_reserve(tab.size() + 2));
+    size_t *d = reinterpret_cast<size_t *>(be.ctx->arena_take(tab.size()));
+    HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), st));
+    const int32_t *dsel = reinterpret_cast<const int32_t *>(d);
+    const Evk &gk = *gset.keys[0];
+    RgswFusedArgs ap, aa;
+    rgsw_fused_args(ap, be, *rset.k0[0], s, acc0, acc1, acc0, acc1);
+    ap.ktab = rset.d_tab; ap.nkeys = (int)rset.k0.size();
+    rgsw_fused_args(aa, be, gk, GaloisShape(gk), acc0, acc1, acc0, acc1);
+    aa.ktab = gset.d_tab; aa.nkeys = (int)gset.keys.size();
+    if (p.n_prod) rgsw_account(ev, *rset.k0[0], s, (int)p.n_prod);
+    auto_select_account(ev, gk, (int)p.n_auto, (int)p.n_auto);
+    const size_t rounds = p.any.size() / 2;
+    for (size_t r = 0; r < rounds; r++) {
+        if (p.any[2 * r]) {
+            aa.sel = dsel + (2 * r) * (size_t)B;
+            HIP_TRY(launch_auto_fused(be.qp, aa, B, st));
+        }
+        if (p.any[2 * r + 1]) {
+            ap.sel = dsel + (2 * r + 1) * (size_t)B;
+            HIP_TRY(launch_rgsw_fused(be.qp, ap, B, st));
+        }
+    }
+    return HE_OK;
+}
+// the reference's own order, entry by entry, through the launches of he_rgsw_external_product and he_automorphism_ct
+int blindrot_per_entry(Evaluator &ev, const RgswSet &rset, const GaloisSet &gset, RgswShape s, const BlindrotPlan &p, View acc0,
+                       View acc1, int B) {
+    BasisExtender &be = *ev.be;
+    if (rgsw_no_fused()) s.fused = false;
+    for (int b = 0; b < B; b++) {
+        const View c0{acc0.p + (size_t)b * acc0.bstride, acc0.bstride}, c1{acc1.p + (size_t)b * acc1.bstride, acc1.bstride};
+        const View v[4] = {c0, c1, c0, c1};
+        for (const blindrot::Op &op : p.lists[(size_t)b]) {
+            be.ctx->arena_reset();  // (stream order: the previous operation's scratch is free once this one's launches run)
+            if (op.kind == blindrot::OP_EXTERNAL_PRODUCT) TRY(rgsw_product_run(ev, *rset.k0[op.arg], *rset.k1[op.arg], s, v, 1));
+            else TRY(automorphism_core(ev, s.levelQ, c0, &c1, nullptr, op.arg, *gset.keys[(size_t)gset.find(op.arg)], c0, c1, 1, KsAlias{true, true, false}));
+        }
+    }
+    return HE_OK;
+}
+}  // namespace
+
+int he_galois_keyset_create(he_handle hev, int n, const uint64_t *gal_els, const he_handle *keys, he_handle *out) {
+    static const char *who = "he_galois_keyset_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    if (n < 1 || !gal_els || !keys || !out) return fail(HE_EINVAL, "%s: at least one Galois key, its element and an output are needed", who);
+    const BasisExtender &be = *ev->be;
+    auto set = std::make_shared<GaloisSet>();
+    set->ev = ev;
+    for (int i = 0; i < n; i++) {
+        std::shared_ptr<Evk> k = get<Evk>(keys[i], T_EVK);
+        if (!k) return fail(HE_EHANDLE, "%s: bad Evk handle (key %d)", who, i);
+        if (k->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key %d belongs to another evaluator", who, i);
+        if (i > 0 && !rgsw_same_shape(*k, *set->keys[0])) return fail(HE_EINVAL, "%s: key %d differs in shape from key 0", who, i);
+        if (!(gal_els[i] & 1)) return fail(HE_EINVAL, "%s: Galois element %d must be odd", who, i);
+        const uint64_t g = reduce_gal(gal_els[i], be.Q->logN, be.type);
+        if (set->find(g) >= 0) return fail(HE_EINVAL, "%s: Galois element %llu is listed twice", who, (unsigned long long)g);
+        set->keys.push_back(k); set->gal.push_back(g);
+    }
+    const size_t N = be.Q->N;
+    Scope sc(be.ctx.get());
+    HIP_TRY(hipMalloc((void **)&set->d_index, (size_t)n * N * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&set->d_tab, 2 * (size_t)n * sizeof(size_t)));
+    std::vector<size_t> tab(2 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        uint32_t *ix = set->d_index + (size_t)i * N;
+        HIP_TRY(launch_build_automorphism_index(be.Q->logN, be.Q->logN + be.type, set->gal[i], ix, be.ctx->stream));
+        tab[i] = (size_t)(uintptr_t)set->keys[i]->d; tab[(size_t)n + i] = (size_t)(uintptr_t)ix;
+    }
+    HIP_TRY(hipMemcpy(set->d_tab, tab.data(), tab.size() * sizeof(size_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(be.ctx->stream));
+    *out = reg(set);
+    return HE_OK;
+}
+int he_galois_keyset_destroy(he_handle h) { return unreg(h, T_GALOIS_SET); }
+int he_automorphism_ct_select(he_handle hev, he_handle in0, he_handle in1, he_handle hset, const int32_t *sel, int n_sel,
+                              he_handle out0, he_handle out1) {
+    static const char *who = "he_automorphism_ct_select";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(set, GaloisSet, hset, T_GALOIS_SET);
+    BasisExtender &be = *ev->be;
+    if (set->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key set belongs to another evaluator", who);
+    const Evk &k = *set->keys[0];
+    if (!auto_select_domain(*ev, k)) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_blindrot.h)", who);
+    if (k.beta < k.prefix[k.nQk]) return fail(HE_EINVAL, "%s: key has %d digits, %d needed", who, k.beta, k.prefix[k.nQk]);
+    const RgswShape s = GaloisShape(k);
+    for (size_t i = 0; i < set->keys.size(); i++) TRY(rgsw_key_words(who, *ev, *set->keys[i], *set->keys[i], s));
+    if (!sel || n_sel < 1) return fail(HE_EINVAL, "%s: null selection", who);
+    const int n = (int)set->keys.size();
+    for (int b = 0; b < n_sel; b++)
+        if (sel[b] < -1 || sel[b] >= n) return fail(HE_EINVAL, "%s: sel[%d] = %d outside [-1, %d)", who, b, (int)sel[b], n);
+    CoReq q;
+    Operands o(q, who, be);
+    TRY(rgsw_operands(o, s.levelQ + 1, in0, in1, out0, out1));
+    if (n_sel != o.B) return fail(HE_EINVAL, "%s: n_sel = %d, the batch has %d entries", who, n_sel, o.B);
+    q.op = CO_AUTO_SELECT; q.obj = ev.get(); q.key = set.get();
+    for (int b = 0; b < n_sel; b++) q.blob.push_back((uint64_t)(int64_t)sel[b]);
+    q.keep.push_back(ev); q.keep.push_back(set);
+    const std::vector<int32_t> selv(sel, sel + n_sel);  // frozen here: a scalar argument of the call
+    q.run = [ev, set, s, selv](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        if ((int)selv.size() != B) return fail(HE_EINVAL, "he_automorphism_ct_select: selection of %d for %d entries", (int)selv.size(), B);
+        int used = 0;
+        std::vector<size_t> tab(((size_t)B + 1) / 2, 0);
+        for (int b = 0; b < B; b++) {
+            tab[b / 2] |= (size_t)(uint32_t)selv[b] << (32 * (b & 1));
+            used += selv[b] >= 0;
+        }
+        auto_select_account(*ev, *set->keys[0], used, B);
+        TRY(be.ctx->arena_reserve(tab.size() + 2));
+        size_t *d = reinterpret_cast<size_t *>(be.ctx->arena_take(tab.size()));
+        HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), be.ctx->stream));
+        RgswFusedArgs a;
+        rgsw_fused_args(a, be, *set->keys[0], s, v[0], v[1], v[2], v[3]);
+        a.ktab = set->d_tab; a.nkeys = (int)set->keys.size();
+        a.sel = reinterpret_cast<const int32_t *>(d);
+        HIP_TRY(launch_auto_fused(be.qp, a, B, be.ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*be.ctx, o.B, q);
+}
+int he_blind_rotate_core(he_handle hev, const uint64_t *a, int batch, int n_lwe, he_handle acc0, he_handle acc1, he_handle hrset,
+                         he_handle hgset) {
+    static const char *who = "he_blind_rotate_core";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(rset, RgswSet, hrset, T_RGSW_SET);
+    GET(gset, GaloisSet, hgset, T_GALOIS_SET);
+    BasisExtender &be = *ev->be;
+    if (rset->ev.get() != ev.get() || gset->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key set belongs to another evaluator", who);
+    if (!a || batch < 1 || n_lwe < 1) return fail(HE_EINVAL, "%s: null or empty rows", who);
+    if ((size_t)n_lwe > rset->k0.size()) return fail(HE_EINVAL, "%s: rows of %d words, the RGSW set has %d keys", who, n_lwe, (int)rset->k0.size());
+    RgswShape s;
+    TRY(rgsw_shape(who, *ev, *rset->k0[0], *rset->k1[0], &s));
+    for (int i = 0; i < n_lwe; i++) TRY(rgsw_key_words(who, *ev, *rset->k0[i], *rset->k1[i], s));
+    const Evk &gk = *gset->keys[0];
+    if (gk.nQk - 1 != s.levelQ) return fail(HE_EINVAL, "%s: the Galois keys have level %d, the RGSW keys level %d", who, gk.nQk - 1, s.levelQ);
+    CoReq q;
+    Operands o(q, who, be);
+    o.out(acc0, s.levelQ + 1, "acc0");
+    o.out(acc1, s.levelQ + 1, "acc1");
+    TRY(o.check());
+    if (batch != o.B) return fail(HE_EINVAL, "%s: %d rows, the accumulator has %d entries", who, batch, o.B);
+    const int B = o.B, logN = be.Q->logN;
+    auto plan = std::make_shared<BlindrotPlan>();
+    plan->lists.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        if (!blindrot::blindrot_ops(logN, a + (size_t)b * n_lwe, n_lwe, &plan->lists[(size_t)b]))
+            return fail(HE_EINVAL, "%s: row %d holds a word that is even and not zero, or not below 2N: no element of Z_2N^*", who, b);
+        for (blindrot::Op &op : plan->lists[(size_t)b]) {
+            if (op.kind != blindrot::OP_AUTOMORPHISM) continue;
+            if (gset->find(op.arg) < 0) return fail(HE_EINVAL, "%s: the Galois set has no key for the element %llu", who, (unsigned long long)op.arg);
+        }
+    }
+    static const bool no_batch = env_flag("HERING_NO_BLINDROT_BATCH");
+    const bool batched = !no_batch && !rgsw_no_fused() && s.fused && auto_select_domain(*ev, gk) && gk.beta >= gk.prefix[gk.nQk];
+    if (batched) {
+        for (size_t i = 0; i < gset->keys.size(); i++) TRY(rgsw_key_words(who, *ev, *gset->keys[i], *gset->keys[i], GaloisShape(gk)));
+        const std::vector<blindrot::Round> rounds = blindrot::blindrot_merge(plan->lists);
+        plan->sel.assign(rounds.size() * 2 * (size_t)B, -1);
+        plan->any.assign(rounds.size() * 2, 0);
+        for (size_t r = 0; r < rounds.size(); r++)
+            for (int b = 0; b < B; b++) {
+                const uint64_t g = rounds[r].gal[(size_t)b];
+                const int32_t p = rounds[r].prod[(size_t)b];
+                if (g) { plan->sel[(2 * r) * (size_t)B + b] = gset->find(g); plan->any[2 * r] = 1; plan->n_auto++; }
+                if (p >= 0) { plan->sel[(2 * r + 1) * (size_t)B + b] = p; plan->any[2 * r + 1] = 1; plan->n_prod++; }
+            }
+    } else {
+        for (int i = 0; i < (int)gset->keys.size(); i++) {
+            int level = s.levelQ;
+            TRY(check_key(*ev, *gset->keys[i], level, who));
+        }
+    }
+    q.op = CO_BLINDROT; q.obj = ev.get(); q.key = rset.get(); q.par[0] = (int64_t)(uintptr_t)gset.get(); q.par[1] = n_lwe;
+    q.blob.assign(a, a + (size_t)B * n_lwe);
+    q.keep.push_back(ev); q.keep.push_back(rset); q.keep.push_back(gset);
+    q.run = [ev, rset, gset, s, plan, batched](const View *v, int B) -> int {
+        if ((int)plan->lists.size() != B) return fail(HE_EINVAL, "he_blind_rotate_core: %d rows for %d entries", (int)plan->lists.size(), B);
+        return batched ? blindrot_batched(*ev, *rset, *gset, s, *plan, v[0], v[1], B)
+                       : blindrot_per_entry(*ev, *rset, *gset, s, *plan, v[0], v[1], B);
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    return co_dispatch(*be.ctx, o.B, q);
+}
+
+// the schedule queries of include/hering_debug.h: host only
+int he_debug_blindrot_schedule(int logN, const uint64_t *a, int n_lwe, uint64_t *ops, size_t cap, size_t *n_ops) {
+    if (!a || !n_ops || n_lwe < 1 || (cap && !ops)) return fail(HE_EINVAL, "he_debug_blindrot_schedule: null argument");
+    std::vector<blindrot::Op> l;
+    if (!blindrot::blindrot_ops(logN, a, n_lwe, &l))
+        return fail(HE_EINVAL, "he_debug_blindrot_schedule: logN out of range, or the row holds a word that is even and not zero, or not below 2N");
+    for (size_t i = 0; i < l.size() && i < cap; i++) { ops[2 * i] = (uint64_t)l[i].kind; ops[2 * i + 1] = l[i].arg; }
+    *n_ops = l.size();
+    return HE_OK;
+}
+int he_debug_blindrot_rounds(int logN, const uint64_t *a, int batch, int n_lwe, int64_t *rounds, size_t cap, size_t *n_rounds) {
+    if (!a || !n_rounds || batch < 1 || n_lwe < 1 || (cap && !rounds)) return fail(HE_EINVAL, "he_debug_blindrot_rounds: null argument");
+    std::vector<std::vector<blindrot::Op>> lists((size_t)batch);
+    for (int b = 0; b < batch; b++)
+        if (!blindrot::blindrot_ops(logN, a + (size_t)b * n_lwe, n_lwe, &lists[(size_t)b]))
+            return fail(HE_EINVAL, "he_debug_blindrot_rounds: logN out of range, or row %d holds a word that is even and not zero, or not below 2N", b);
+    const std::vector<blindrot::Round> r = blindrot::blindrot_merge(lists);
+    for (size_t i = 0; i < r.size() && i < cap; i++)
+        for (int b = 0; b < batch; b++) {
+            rounds[(2 * i) * (size_t)batch + b] = (int64_t)r[i].gal[(size_t)b];
+            rounds[(2 * i + 1) * (size_t)batch + b] = (int64_t)r[i].prod[(size_t)b];
+        }
+    *n_rounds = r.size();
+    return HE_OK;
 }
 
 // ---------------------------------------------------------------------------------------

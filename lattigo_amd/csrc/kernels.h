@@ -281,6 +281,12 @@ struct RgswFusedArgs {
 };
 bool rgsw_fused_supported(int logN, int nQ);  // logN 9..11 and the coefficients of 2 nQ limbs beside the exchange buffer in 64 KiB of LDS
 hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s);
+// rlwe.Evaluator.Automorphism (core/rlwe/evaluator_automorphism.go:13-56) of one batch entry in one workgroup
+// (auto_fused_kernel), select form only: entry b takes key sel[b] of the set, or is copied (sel[b] == -1).  Same domain and
+// arguments as launch_rgsw_fused with a base-2 gadget key (pw2 != 0); key0 / key1 are not read and ktab is a device array
+// [2][nkeys]: the keys' base addresses | the addresses of their automorphism index tables (uint32 [N], out[j] = in[index[j]]).
+// out_k may be in_k.
+hipError_t launch_auto_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s);
 
 // ---- key-switch inner product ---------------------------------------------------------------
 // acc[k][l] = sum_d evk[d][k][l] * dec[d][l] * 2^-64 mod q_l, canonical
@@ -435,7 +441,7 @@ enum KernelId {
     K_NTT_COLS_FWD = 0, K_NTT_ROWS_FWD, K_NTT_ROWS_INV, K_NTT_COLS_INV, K_EW, K_GATHER, K_AUTO_COEFF, K_INDEX,
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
-    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_COUNT
+    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

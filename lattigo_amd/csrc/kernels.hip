@@ -73,7 +73,7 @@ const char *kernel_name(int id) {
                                          "tensor", "modmul_probe", "ci_fold", "mask_spread", "ntt_rows_fwd_f64",
                                          "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
                                          "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
-                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product"};
+                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -4598,6 +4598,182 @@ hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch
         case 9: hipLaunchKernelGGL(rgsw_fused_kernel<9>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
         case 10: hipLaunchKernelGGL(rgsw_fused_kernel<10>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
         default: hipLaunchKernelGGL(rgsw_fused_kernel<11>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// rlwe.Evaluator.Automorphism of a small ring in ONE launch, every batch entry with its own key of a resident set
+// (core/rlwe/evaluator_automorphism.go:13-56 over a base-2 gadget key, evaluator_gadget_product.go:203-338): the sibling of
+// rgsw_fused_kernel, with its thread layout, transforms, exchange buffer and key addressing.
+//   pass-through: sel[z] < 0 copies the entry;
+//   phase 1: in1 only, every Q limb: INTT with N^-1, the canonical coefficients parked in LDS -- all of in1 is read here;
+//   phase 2: per destination limb (the special prime first): every (source limb, window) masked, transformed and multiplied
+//            by the key's two rows; the P limb's accumulators are kept as coefficients (ext), a Q limb ends with ModDown's
+//            last step (or nothing, without a special prime);
+//   add and permute: tmp0 = acc0 + in0 with one conditional subtraction (ringQ.Add), tmp1 = acc1; both go through the exchange
+//            buffer and out[e] = tmp[index[e]] (AutomorphismNTTWithIndex): every thread stores the positions e it loaded in0
+//            at, contiguous along the wave, after the barrier that follows the buffer's fill -- so out0 may be in0.
+// ------------------------------------------------------------------------------------
+template <int LOGB>
+__global__ void __launch_bounds__((1 << LOGB) / 16) auto_fused_kernel(RgswKArgs K) {
+    constexpr int N = 1 << LOGB, T = N / 16;
+    __shared__ uint64_t lds[N + N / 16];
+    extern __shared__ uint64_t coef[];  // [nQ][16][T]: slot (i, k) of thread tau
+    const RgswFusedArgs &A = K.a;
+    const int tau = threadIdx.x, nQ = A.nQ;
+    const size_t z = blockIdx.x;
+    const uint64_t *in0 = A.in0.p + z * A.in0.bstride, *in1 = A.in1.p + z * A.in1.bstride;
+    uint64_t *out0 = A.out0.p + z * A.out0.bstride, *out1 = A.out1.p + z * A.out1.bstride;
+    const int si = A.sel[z];
+    if (si < 0) {  // (uniform over the workgroup: no barrier has been passed)
+        for (int e = tau; e < nQ * N; e += T) {
+            if (out0 != in0) out0[e] = in0[e];
+            if (out1 != in1) out1[e] = in1[e];
+        }
+        return;
+    }
+    // ktab: [2][nkeys], the keys' words | their automorphism index tables
+    const uint64_t *key = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)si));
+    const uint32_t *__restrict__ index =
+        reinterpret_cast<const uint32_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)A.nkeys + si));
+    // ---- phase 1
+#pragma unroll 1
+    for (int i = 0; i < nQ; i++) {
+        const uint64_t *__restrict__ src = in1 + (size_t)i * N;
+        const ModConst mc = K.mc[i];
+        const uint64_t twoq = mc.q << 1;
+        uint64_t x[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) x[kk] = ldnt(&src[nat_e<T>(kk, tau)]);
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) x[kk] = x[kk] >= twoq ? bred_add_lazy(x[kk], mc.q, mc.brc0) : x[kk];
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = x[kk];
+        __syncthreads();
+        rgsw_ntt_inv<LOGB>(x, lds, K.twi + (size_t)i * N, tau, mc);
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) coef[(i * 16 + kk) * T + tau] = x[kk];
+    }
+    // ---- phase 2
+    uint64_t ext[2][16];
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) ext[c][kk] = 0;
+    const int nD = nQ + A.nP;
+#pragma unroll 1
+    for (int ui = 0; ui < nD; ui++) {
+        const bool isP = A.nP != 0 && ui == 0;
+        const int u = isP ? 0 : ui - A.nP;
+        const int mi = isP ? A.p_mod : u;
+        const int kl = isP ? A.key_p_limb : u;
+        const ModConst mc = K.mc[mi];
+        const uint64_t q = mc.q, qinv = mc.qinv, twoq = mc.q << 1;
+        const uint64_t *__restrict__ twf = K.twf + (size_t)mi * N;
+        const bool red = A.mask >= q;
+        uint64_t acc[2][16];
+#pragma unroll
+        for (int c = 0; c < 2; c++)
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) acc[c][kk] = 0;
+#pragma unroll 1
+        for (int i = 0; i < nQ; i++) {
+            uint64_t x[16];
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) x[kk] = coef[(i * 16 + kk) * T + tau];
+#pragma unroll 1
+            for (int j = 0; j < (int)A.nj[i]; j++) {
+                const int shift = j * A.pw2;
+                uint64_t y[16];
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    y[kk] = (x[kk] >> shift) & A.mask;
+                    if (red) y[kk] = bred_add_lazy(y[kk], q, mc.brc0);
+                }
+                __syncthreads();  // (the previous transform's words are still being read)
+                rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);
+                const size_t d = (size_t)A.prefix[i] + j;
+                const uint64_t *__restrict__ k0 = key + ((d * 2) * A.key_limbs + kl) * N;
+                const uint64_t *__restrict__ k1 = k0 + (size_t)A.key_limbs * N;
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    const int e = nat_e<T>(kk, tau);
+                    uint64_t v = lds[lds_phys(e)];
+                    v = v >= twoq ? v - twoq : v;
+                    acc[0][kk] = cred(acc[0][kk] + mred_w32(v, k0[e], q, qinv), q);
+                    acc[1][kk] = cred(acc[1][kk] + mred_w32(v, k1[e], q, qinv), q);
+                }
+            }
+        }
+        if (isP) {
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = acc[c][kk];
+                __syncthreads();
+                rgsw_ntt_inv<LOGB>(ext[c], lds, K.twi + (size_t)mi * N, tau, mc);
+            }
+            continue;
+        }
+        if (A.nP) {  // ModDown's last step with the reference's float-quotient lift, as in rgsw_fused_kernel
+            const uint64_t pmq = A.p_mod_q[u], sdn = A.md_s[u];
+            const uint64_t p = K.mc[A.p_mod].q, hq = bred_add(A.p_half, q, mc.brc0);
+            const double pd = __ull2double_rn(p);
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                uint64_t y[16];
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    const uint64_t x = cred(ext[c][kk] + A.p_half, p);
+                    const uint64_t w = (uint64_t)__ddiv_rn(__ull2double_rn(x), pd);
+                    const uint64_t r = cred(bred_add(x, q, mc.brc0) + q - hq, q);
+                    y[kk] = w ? cred(r + q - pmq, q) : r;
+                }
+                __syncthreads();
+                rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    uint64_t v = lds[lds_phys(nat_e<T>(kk, tau))];
+                    v = v >= twoq ? v - twoq : v;
+                    acc[c][kk] = mred_w32(v + twoq - acc[c][kk], sdn, q, qinv);
+                }
+            }
+        }
+        // ---- add in0 and store both components through the automorphism
+        const uint64_t *__restrict__ a0 = in0 + (size_t)u * N;
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) acc[0][kk] = cred(acc[0][kk] + a0[nat_e<T>(kk, tau)], q);
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            uint64_t *o = (c ? out1 : out0) + (size_t)u * N;
+            __syncthreads();  // (the exchange buffer's last readers)
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = acc[c][kk];
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                const int e = nat_e<T>(kk, tau);
+                o[e] = lds[lds_phys((int)index[e])];
+            }
+        }
+    }
+}
+hipError_t launch_auto_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s) {
+    if (!rgsw_fused_supported(r.logN, a.nQ) || batch <= 0 || a.nP < 0 || a.nP > 1 || !no_tab({a.in0, a.in1, a.out0, a.out1}) ||
+        !a.in0.p || !a.in1.p || !a.out0.p || !a.out1.p || !a.ktab || !a.sel || a.nkeys <= 0 || a.pw2 <= 0)
+        return hipErrorInvalidValue;
+    RgswKArgs K{};
+    K.a = a; K.mc = r.mc; K.twf = r.tw_fwd; K.twi = r.tw_inv;
+    const size_t dyn = (size_t)a.nQ * r.N * 8;
+    const unsigned T = (unsigned)r.N / 16;
+    ProfScope ps(K_AUTO_FUSED, s, 4.0 * a.nQ * batch * (double)r.N * 8.0);  // (the keys differ by entry: not counted)
+    switch (r.logN) {
+        case 9: hipLaunchKernelGGL(auto_fused_kernel<9>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        case 10: hipLaunchKernelGGL(auto_fused_kernel<10>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        default: hipLaunchKernelGGL(auto_fused_kernel<11>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
     }
     return hipGetLastError();
 }

@@ -28,6 +28,7 @@
 #include "../../include/hering_ringswitch.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
+#include "../../include/hering_blindrot.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -39,7 +40,7 @@ enum Fn : uint64_t {
     F_CENTERED_LIFT, F_DECOMP_FILL, F_LINTRANS, F_CKKS_MUL, F_BGV_MUL, F_GIANT_STEP,
     F_MAP_SMALL_TO_LARGE, F_SWITCH_RING_NTT, F_SWITCH_RING, F_APPLY_EVK,
     F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST,
-    F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_COUNT
+    F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_AUTO_CT_SELECT, F_BLIND_ROTATE_CORE, F_COUNT
 };
 static_assert(F_COUNT <= 128, "the per-function profile has 128 slots");
 struct Arg {
@@ -179,6 +180,12 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
             if (a.size() > 4 && a[4].kind == 3) for (uint64_t w : a[4].arr) sel.push_back((int32_t)(int64_t)w);
             return he_rgsw_external_product_select(H(0), H(1), H(2), H(3), sel.empty() ? nullptr : sel.data(), (int)I(5), H(6), H(7));
         }
+        case F_AUTO_CT_SELECT: {
+            std::vector<int32_t> sel;
+            if (a.size() > 4 && a[4].kind == 3) for (uint64_t w : a[4].arr) sel.push_back((int32_t)(int64_t)w);
+            return he_automorphism_ct_select(H(0), H(1), H(2), H(3), sel.empty() ? nullptr : sel.data(), (int)I(5), H(6), H(7));
+        }
+        case F_BLIND_ROTATE_CORE: return he_blind_rotate_core(H(0), A(1), (int)I(2), (int)I(3), H(4), H(5), H(6), H(7));
         default: return HE_EINVAL;
     }
 }
