@@ -28,6 +28,7 @@
 #include "hering_ringpack.h"
 #include "hering_rgsw.h"
 #include "hering_blindrot.h"
+#include "hering_bridge.h"
 
 namespace hering {
 
@@ -303,6 +304,15 @@ public:
         check(he_automorphism_ntt_with_index(h(), level_, pIn.h(), ix, pOut.h()));
     }
     void Automorphism(const Poly &pIn, uint64_t galEl, Poly &pOut) const { check(he_automorphism(h(), level_, pIn.h(), galEl, pOut.h())); }
+    // ring/conjugate_invariant.go:7,28 (hering_bridge.h): the maps between a standard polynomial of degree 2n and the compressed
+    // conjugate-invariant one of degree n, on limbs 0..level of this ring.  The fold is the one of the index table of the Galois
+    // element NthRoot - 1 (j -> 2n - 1 - j), the only one the reference passes; this ring supplies its moduli.
+    void UnfoldConjugateInvariantToStandard(const Poly &polyConjugateInvariant, Poly &polyStandard) const {
+        check(he_unfold_conjugate_invariant_to_standard(level_, polyConjugateInvariant.h(), polyStandard.h()));
+    }
+    void FoldStandardToConjugateInvariant(const Poly &polyStandard, Poly &polyConjugateInvariant) const {
+        check(he_fold_standard_to_conjugate_invariant(h(), level_, polyStandard.h(), polyConjugateInvariant.h()));
+    }
     AutomorphismIndex AutomorphismNTTIndex(uint64_t galEl) const {  // :12
         he_handle ix = 0;
         check(he_automorphism_index_create(h(), galEl, &ix));
@@ -710,6 +720,31 @@ public:
         return ctN;
     }
 };
+
+// ---- the CKKS bridge (schemes/ckks/bridge.go; hering_bridge.h), NTT domain ---------------------------------------------------------
+namespace ckks {
+// ckks.DomainSwitcher (bridge.go:13): between standard ciphertexts of the evaluator's degree N and conjugate-invariant ones of
+// degree N/2.  Either key may be absent (a default EvaluationKey).  hering::Ciphertext carries no scale: after ComplexToReal the
+// caller doubles the scale it keeps for the ciphertext (bridge.go:93).
+class DomainSwitcher {
+    Evaluator eval_;  // (a copy shares the device evaluator)
+    EvaluationKey stdToci_, ciToStd_;
+
+public:
+    DomainSwitcher(const Evaluator &eval, const EvaluationKey &comlexToRealEvk, const EvaluationKey &realToComplexEvk)
+        : eval_(eval), stdToci_(comlexToRealEvk), ciToStd_(realToComplexEvk) {}
+    void ComplexToReal(const Ciphertext &ctIn, Ciphertext &opOut) const {  // :57-95
+        if (!stdToci_.h()) throw std::invalid_argument("cannot ComplexToReal: no realToComplexEvk provided to this DomainSwitcher");
+        const int level = ctIn.Level() < opOut.Level() ? ctIn.Level() : opOut.Level();
+        check(he_complex_to_real(eval_.h(), level, ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), stdToci_.h(), opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+    }
+    void RealToComplex(const Ciphertext &ctIn, Ciphertext &opOut) const {  // :104-144
+        if (!ciToStd_.h()) throw std::invalid_argument("cannot RealToComplex: no realToComplexEvk provided to this DomainSwitcher");
+        const int level = ctIn.Level() < opOut.Level() ? ctIn.Level() : opOut.Level();
+        check(he_real_to_complex(eval_.h(), level, ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), ciToStd_.h(), opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+    }
+};
+}  // namespace ckks
 
 // ---- RGSW (core/rgsw; hering_rgsw.h), NTT domain -----------------------------------------------------------------------------
 namespace rgsw {

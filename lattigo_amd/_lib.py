@@ -10,7 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HERING_LIB: A/B-test another build
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
-         os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h")]
+         os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
+         os.path.join(_INC, "hering_bridge.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -113,6 +114,8 @@ def _declare(L):
         "he_relinearize": [H, i, H, H, H, H, H, H],
         "he_map_small_to_large_ntt": [H, H, i], "he_switch_ring_degree_ntt": [H, i, H, H], "he_switch_ring_degree": [i, H, H],
         "he_apply_evaluation_key": [H, i, H, H, H, H, H],
+        "he_unfold_conjugate_invariant_to_standard": [i, H, H], "he_fold_standard_to_conjugate_invariant": [H, i, H, H],
+        "he_complex_to_real": [H, i, H, H, H, H, H], "he_real_to_complex": [H, i, H, H, H, H, H],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
@@ -203,6 +206,9 @@ _TRACE_FNS = {
 _TRACE_FNS_RGSW = {"he_rgsw_external_product": (63, "hhhhhhh"), "he_rgsw_external_product_select": (64, "hhhhAihh")}
 # the entries of include/hering_blindrot.h, numbered on in a table of their own
 _TRACE_FNS_BLINDROT = {"he_automorphism_ct_select": (65, "hhhhAihh"), "he_blind_rotate_core": (66, "hAiihhhh")}
+# the entries of include/hering_bridge.h, numbered on in a table of their own
+_TRACE_FNS_BRIDGE = {"he_unfold_conjugate_invariant_to_standard": (67, "ihh"), "he_fold_standard_to_conjugate_invariant": (68, "hihh"),
+                     "he_complex_to_real": (69, "hihhhhh"), "he_real_to_complex": (70, "hihhhhh")}
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments); a
 # tuple of indices: the product of those arguments
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
@@ -241,7 +247,7 @@ def trace_begin():
     import inspect  # noqa: F401
 
     def wrap(name, fn):
-        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name)
+        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name)
 
         def call(*a):
             rc = fn(*a)

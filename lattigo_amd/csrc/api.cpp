@@ -39,6 +39,7 @@
 #include "../../include/hering.h"
 #include "../../include/hering_debug.h"
 #include "../../include/hering_ringswitch.h"
+#include "../../include/hering_bridge.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -100,7 +101,8 @@ enum CoOp {
     CO_NTT, CO_EW, CO_EW_DOUBLE, CO_SHIFT, CO_RESCALE, CO_GATHER, CO_AUTO_COEFF, CO_MODUP, CO_MODDOWN_BE,
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
-    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT
+    CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT,
+    CO_CI_BRIDGE, CO_CI_BRIDGE_CT
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -4604,6 +4606,127 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
     // (the ring maps of the degree-changing forms take no entry tables)
     if (form != AEK_SAME) q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
     return co_dispatch(*be.ctx, o.B, q);
+}
+
+// ---------------------------------------------------------------------------------------
+// the CKKS DomainSwitcher (include/hering_bridge.h; schemes/ckks/bridge.go, ring/conjugate_invariant.go)
+// ---------------------------------------------------------------------------------------
+// kinds of CO_CI_BRIDGE / CO_CI_BRIDGE_CT (par[1])
+enum { BR_FOLD = 0, BR_UNFOLD };
+// one launch covers every entry of both components in its grid's z dimension
+constexpr int kBridgeMaxEntries = 65535;
+// a standard polynomial of degree 2n and a conjugate-invariant one of degree n >= 16 (context, batch and limbs: the operand checks)
+static int bridge_shape(const Poly &std_, const Poly &ci, int level, const char *who, const char *ratio_msg) {
+    if (std_.N != 2 * ci.N) return fail(HE_EINVAL, "%s: %s (%d and %d)", who, ratio_msg, std_.N, ci.N);
+    if (ci.N < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, ci.N);
+    if (level < 0 || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range", who, level);
+    if (2L * std_.batch > kBridgeMaxEntries)
+        return fail(HE_EINVAL, "%s: %ld entries in one call, at most %d (split the batch)", who, 2L * std_.batch, kBridgeMaxEntries);
+    return HE_OK;
+}
+// files one ring-level map of in -> out on the context's queue, served one by one
+static int bridge_file(const char *who, const std::shared_ptr<Ring> &moduli, int kind, int level, const std::shared_ptr<Poly> &in,
+                       const std::shared_ptr<Poly> &out) {
+    const std::shared_ptr<Ctx> ctx = in->ctx;
+    const int n = std::min(in->N, out->N);
+    CoReq q;
+    Operands o(q, who, ctx, in->N);
+    o.in(in, level + 1, kind == BR_FOLD ? "polyStandard" : "polyConjugateInvariant");
+    o.out(out, level + 1, kind == BR_FOLD ? "polyConjugateInvariant" : "polyStandard", Operands::kCall, out->N);
+    TRY(o.check());
+    q.op = CO_CI_BRIDGE; q.obj = moduli ? (const void *)moduli.get() : (const void *)ctx.get();
+    q.par[0] = level; q.par[1] = kind; q.par[2] = n;
+    if (moduli) q.keep.push_back(moduli);
+    q.run = [ctx, moduli, kind, level, n](const View *v, int B) -> int {
+        RingSwitchIO io;
+        io.in = v[0]; io.out = v[1];
+        ctx->acct(1.5 * (level + 1), 0, B, 2 * n);  // (every input word read once, every output word written once)
+        if (kind == BR_FOLD) HIP_TRY(launch_ci_bridge_fold(moduli->dev, ident_tab(level + 1), io, n, B, ctx->stream));
+        else HIP_TRY(launch_ci_bridge_unfold(ident_tab(level + 1), io, n, B, ctx->stream));
+        return HE_OK;
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (the maps take no entry tables)
+    return co_dispatch(*ctx, in->batch, q);
+}
+int he_unfold_conjugate_invariant_to_standard(int level, he_handle hci, he_handle hstd) {
+    static const char *who = "he_unfold_conjugate_invariant_to_standard";
+    GET(ci, Poly, hci, T_POLY);
+    GET(st, Poly, hstd, T_POLY);
+    TRY(bridge_shape(*st, *ci, level, who, "ring degree of polyStandard must be twice the ring degree of polyConjugateInvariant"));
+    return bridge_file(who, nullptr, BR_UNFOLD, level, ci, st);
+}
+int he_fold_standard_to_conjugate_invariant(he_handle hring, int level, he_handle hstd, he_handle hci) {
+    static const char *who = "he_fold_standard_to_conjugate_invariant";
+    GET(r, Ring, hring, T_RING);
+    GET(st, Poly, hstd, T_POLY);
+    GET(ci, Poly, hci, T_POLY);
+    TRY(bridge_shape(*st, *ci, level, who, "ring degree of polyStandard must be 2N and ring degree of polyConjugateInvariant must be N"));
+    if (r->ctx != st->ctx) return fail(HE_EINVAL, "%s: the ring belongs to another context", who);
+    if (r->N != st->N && r->N != ci->N) return fail(HE_EINVAL, "%s: ring degree %d is neither %d nor %d", who, r->N, ci->N, st->N);
+    if (level >= r->nmod()) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, r->nmod() - 1);
+    return bridge_file(who, r, BR_FOLD, level, st, ci);
+}
+// ComplexToReal (bridge.go:57-95): GadgetProduct(in1) with in0 as the ModDown epilogue's addend, into scratch at N, then the fold of
+// both components in one launch over 2B entries.  RealToComplex (bridge.go:104-144): the unfold of both components into scratch at
+// N in one launch, then the key switch of the unfolded in1 with the unfolded in0 as the addend (the reference unfolds into opOut and
+// adds there: the same words, ringQ.Add being symmetric).
+static int bridge_ct(const char *who, int kind, he_handle hev, int level, he_handle hin0, he_handle hin1, he_handle hk, he_handle hout0,
+                     he_handle hout1) {
+    const auto ev = get<Evaluator>(hev, T_EVAL);
+    const auto k = get<Evk>(hk, T_EVK);
+    const auto in0 = get<Poly>(hin0, T_POLY), in1 = get<Poly>(hin1, T_POLY), out0 = get<Poly>(hout0, T_POLY), out1 = get<Poly>(hout1, T_POLY);
+    if (!ev) return fail(HE_EHANDLE, "%s: bad Evaluator handle %llu", who, (unsigned long long)hev);
+    if (!k) return fail(HE_EHANDLE, "%s: bad Evk handle %llu", who, (unsigned long long)hk);
+    if (!in0 || !in1 || !out0 || !out1) return fail(HE_EHANDLE, "%s: bad Poly handle", who);
+    BasisExtender &be = *ev->be;
+    const char *name = kind == BR_FOLD ? "ComplexToReal" : "RealToComplex";
+    if (be.type != 0) return fail(HE_EINVAL, "%s: cannot %s: provided evaluator is not instantiated with RingType ring.Standard", who, name);
+    TRY(check_key(*ev, *k, level, who));
+    const int N = be.Q->N, Nin = in0->N, Nout = out0->N;
+    if (in1->N != Nin || out1->N != Nout) return fail(HE_EINVAL, "%s: the two components of a ciphertext differ in degree", who);
+    if (kind == BR_FOLD && Nin != 2 * Nout) return fail(HE_EINVAL, "%s: cannot ComplexToReal: ctIn ring degree must be twice opOut ring degree", who);
+    if (kind == BR_UNFOLD && 2 * Nin != Nout) return fail(HE_EINVAL, "%s: cannot RealToComplex: opOut ring degree must be twice ctIn ring degree", who);
+    if (std::max(Nin, Nout) != N)
+        return fail(HE_EINVAL, "%s: %s ring degree does not match evaluator params ring degree", who, kind == BR_FOLD ? "ctIn" : "opOut");
+    TRY(bridge_shape(kind == BR_FOLD ? *in0 : *out0, kind == BR_FOLD ? *out0 : *in0, level, who, "degrees are not N and N/2"));
+    CoReq q;
+    Operands o(q, who, be);
+    o.in(in0, level + 1, "in0", Operands::kCall, Nin); o.in(in1, level + 1, "in1", Operands::kCall, Nin);
+    o.out(out0, level + 1, "out0", Operands::kCall, Nout); o.out(out1, level + 1, "out1", Operands::kCall, Nout);
+    TRY(o.check());  // (handles of different degree never coincide: only out0 == out1 can, and is rejected)
+    const int n = N / 2;
+    KsAlias alias;  // (the key switch runs on scratch on one side: none of its outputs is its operand)
+    ks_request(q, CO_CI_BRIDGE_CT, ev, k, level, KS_FORM_COUNT, alias); q.par[1] = kind;
+    q.run = [ev, k, level, kind, n, alias](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        const int N = be.Q->N;
+        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
+        // the key switch: 2 L in, 2 L out, key; its scratch and both components at degree N
+        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));
+        hipStream_t st = be.ctx->stream;
+        uint64_t *t = be.ctx->arena_take(2 * wQ);
+        const View t0{t, sQ}, t1{t + wQ, sQ};
+        RingSwitchIO io;
+        io.zsplit = B;
+        be.ctx->acct(2.0 * 1.5 * (level + 1), 0, B, N);
+        if (kind == BR_FOLD) {
+            TRY(key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, t0, t1, B, &v[0]}));
+            io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3];
+            HIP_TRY(launch_ci_bridge_fold(be.Q->dev, ident_tab(level + 1), io, n, 2 * B, st));
+            return HE_OK;
+        }
+        io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1;
+        HIP_TRY(launch_ci_bridge_unfold(ident_tab(level + 1), io, n, 2 * B, st));
+        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&t1, nullptr, v[2], v[3], B, &t0});
+    };
+    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (the ring maps take no entry tables)
+    return co_dispatch(*be.ctx, o.B, q);
+}
+int he_complex_to_real(he_handle ev, int level, he_handle in0, he_handle in1, he_handle evk, he_handle out0, he_handle out1) {
+    return bridge_ct("he_complex_to_real", BR_FOLD, ev, level, in0, in1, evk, out0, out1);
+}
+int he_real_to_complex(he_handle ev, int level, he_handle in0, he_handle in1, he_handle evk, he_handle out0, he_handle out1) {
+    return bridge_ct("he_real_to_complex", BR_UNFOLD, ev, level, in0, in1, evk, out0, out1);
 }
 
 // ---------------------------------------------------------------------------------------

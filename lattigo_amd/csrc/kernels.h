@@ -406,6 +406,12 @@ hipError_t launch_ring_degree_fold_ntt(const RingDev &large, const LimbTab &tab,
 hipError_t launch_ring_degree_replicate_ntt(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, int batch, hipStream_t s);
 // SwitchCiphertextRingDegree: down (up = false) out[w] = in[w gap]; up out[w gap] = in[w], the other words of out untouched
 hipError_t launch_ring_degree_stride(const LimbTab &tab, RingSwitchIO io, int n_small, int log_gap, bool up, int batch, hipStream_t s);
+// The CKKS bridge (ring/conjugate_invariant.go:3-44) between a standard polynomial of N = 2n words per limb and the compressed
+// conjugate-invariant one of n (>= 16).  Fold: out[j] = CRed(in[N-1-j] + in[j], q[tab.mod[y]]) for j < n, the sum wrapping in 64
+// bits (`moduli`: any ring with those modulus records); the index table of the Galois element 2N - 1 is j -> N - 1 - j.
+hipError_t launch_ci_bridge_fold(const RingDev &moduli, const LimbTab &tab, RingSwitchIO io, int n, int batch, hipStream_t s);
+// Unfold: out[j] = out[N-1-j] = in[j] for j < n
+hipError_t launch_ci_bridge_unfold(const LimbTab &tab, RingSwitchIO io, int n, int batch, hipStream_t s);
 
 // ---- ring packing (core/rlwe/ring_packing.go) -----------------------------------------------------
 // Operands by ciphertext component: entries z < zsplit are component 0, the others component 1 (entry z - zsplit), so that both
@@ -441,7 +447,8 @@ enum KernelId {
     K_NTT_COLS_FWD = 0, K_NTT_ROWS_FWD, K_NTT_ROWS_INV, K_NTT_COLS_INV, K_EW, K_GATHER, K_AUTO_COEFF, K_INDEX,
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
-    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_COUNT
+    K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_CI_BRIDGE_FOLD,
+    K_CI_BRIDGE_UNFOLD, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -73,7 +73,8 @@ const char *kernel_name(int id) {
                                          "tensor", "modmul_probe", "ci_fold", "mask_spread", "ntt_rows_fwd_f64",
                                          "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
                                          "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
-                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select"};
+                                         "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select",
+                                         "ci_bridge_fold", "ci_bridge_unfold"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -2859,6 +2860,39 @@ __global__ void __launch_bounds__(256) ring_stride_kernel(RingSwitchArgs A) {
     if (UP) out[w << A.log_gap] = ldnt(in + w);
     else out[w] = ldnt(in + (w << A.log_gap));
 }
+// The CKKS bridge between Z[X]/(X^N+1) and the compressed Z[X+X^-1]/(X^N+1) of n = N/2 words (ring/conjugate_invariant.go:3-44).
+// The reference's fold gathers through the NTT index table of the Galois element 2N - 1, which is j -> N - 1 - j: no table here.
+// FoldStandardToConjugateInvariant: out[j] = CRed(in[N-1-j] + in[j]), j < n, the 64-bit sum wrapping as the reference's does
+// (s.Add on lazy words).  Two adjacent outputs per thread: one forward 16-byte load and the mirrored pair, swapped.
+__global__ void __launch_bounds__(256) ci_bridge_fold_kernel(RingSwitchArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.n_small) return;
+    const int y = blockIdx.y;
+    const size_t z = blockIdx.z;
+    const uint64_t q = A.mc[A.mod[y]].q;
+    const size_t N = (size_t)A.n_small * 2;
+    const uint64_t *in = rs_in(A, z) + (size_t)A.in_limb[y] * N;
+    uint64_t *out = rs_out(A, z) + (size_t)A.out_limb[y] * A.n_small + j;
+    const ulonglong2 f = ldnt2(in + j), m = ldnt2(in + (N - 2 - j));
+    ulonglong2 o;
+    o.x = cred(m.y + f.x, q);
+    o.y = cred(m.x + f.y, q);
+    *reinterpret_cast<ulonglong2 *>(out) = o;
+}
+// UnfoldConjugateInvariantToStandard: out[j] = out[N-1-j] = in[j], j < n.  Two inputs per thread, stored as the forward pair and
+// the mirrored pair, swapped.
+__global__ void __launch_bounds__(256) ci_bridge_unfold_kernel(RingSwitchArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.n_small) return;
+    const int y = blockIdx.y;
+    const size_t z = blockIdx.z;
+    const size_t N = (size_t)A.n_small * 2;
+    const uint64_t *in = rs_in(A, z) + (size_t)A.in_limb[y] * A.n_small + j;
+    uint64_t *out = rs_out(A, z) + (size_t)A.out_limb[y] * N;
+    const ulonglong2 v = ldnt2(in);
+    *reinterpret_cast<ulonglong2 *>(out + j) = v;
+    *reinterpret_cast<ulonglong2 *>(out + (N - 2 - j)) = make_ulonglong2(v.y, v.x);
+}
 static bool rs_args(RingSwitchArgs &A, const LimbTab &tab, const RingSwitchIO &io, int n_small, int log_gap, int batch) {
     if (tab.n <= 0 || tab.n > kMaxLimbs || batch <= 0 || n_small < 16 || log_gap < 1 || log_gap > kMaxLogN) return false;
     if (!no_tab({io.in, io.out, io.in2, io.out2})) return false;
@@ -2899,6 +2933,23 @@ hipError_t launch_ring_degree_stride(const LimbTab &tab, RingSwitchIO io, int n_
     ProfScope ps(K_RING_STRIDE, s, 2.0 * n_small * tab.n * batch * 8.0);
     if (up) hipLaunchKernelGGL((ring_stride_kernel<true>), grid, block, 0, s, A);
     else hipLaunchKernelGGL((ring_stride_kernel<false>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_ci_bridge_fold(const RingDev &moduli, const LimbTab &tab, RingSwitchIO io, int n, int batch, hipStream_t s) {
+    RingSwitchArgs A{};
+    if (!rs_args(A, tab, io, n, 1, batch) || (n & 1)) return hipErrorInvalidValue;
+    A.mc = moduli.mc;
+    dim3 grid((unsigned)((n / 2 + 255) / 256), tab.n, batch), block(256);
+    ProfScope ps(K_CI_BRIDGE_FOLD, s, 3.0 * n * tab.n * batch * 8.0);
+    hipLaunchKernelGGL(ci_bridge_fold_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_ci_bridge_unfold(const LimbTab &tab, RingSwitchIO io, int n, int batch, hipStream_t s) {
+    RingSwitchArgs A{};
+    if (!rs_args(A, tab, io, n, 1, batch) || (n & 1)) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((n / 2 + 255) / 256), tab.n, batch), block(256);
+    ProfScope ps(K_CI_BRIDGE_UNFOLD, s, 3.0 * n * tab.n * batch * 8.0);
+    hipLaunchKernelGGL(ci_bridge_unfold_kernel, grid, block, 0, s, A);
     return hipGetLastError();
 }
 

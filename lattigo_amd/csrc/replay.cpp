@@ -29,6 +29,7 @@
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
+#include "../../include/hering_bridge.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -40,7 +41,8 @@ enum Fn : uint64_t {
     F_CENTERED_LIFT, F_DECOMP_FILL, F_LINTRANS, F_CKKS_MUL, F_BGV_MUL, F_GIANT_STEP,
     F_MAP_SMALL_TO_LARGE, F_SWITCH_RING_NTT, F_SWITCH_RING, F_APPLY_EVK,
     F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST,
-    F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_AUTO_CT_SELECT, F_BLIND_ROTATE_CORE, F_COUNT
+    F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_AUTO_CT_SELECT, F_BLIND_ROTATE_CORE,
+    F_BRIDGE_UNFOLD, F_BRIDGE_FOLD, F_COMPLEX_TO_REAL, F_REAL_TO_COMPLEX, F_COUNT
 };
 static_assert(F_COUNT <= 128, "the per-function profile has 128 slots");
 struct Arg {
@@ -186,6 +188,10 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
             return he_automorphism_ct_select(H(0), H(1), H(2), H(3), sel.empty() ? nullptr : sel.data(), (int)I(5), H(6), H(7));
         }
         case F_BLIND_ROTATE_CORE: return he_blind_rotate_core(H(0), A(1), (int)I(2), (int)I(3), H(4), H(5), H(6), H(7));
+        case F_BRIDGE_UNFOLD: return he_unfold_conjugate_invariant_to_standard((int)I(0), H(1), H(2));
+        case F_BRIDGE_FOLD: return he_fold_standard_to_conjugate_invariant(H(0), (int)I(1), H(2), H(3));
+        case F_COMPLEX_TO_REAL: return he_complex_to_real(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6));
+        case F_REAL_TO_COMPLEX: return he_real_to_complex(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6));
         default: return HE_EINVAL;
     }
 }

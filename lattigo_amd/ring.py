@@ -165,14 +165,14 @@ class Context:
 
     def prof_end(self) -> dict:
         """{kernel name: (launches, total ms)} since prof_begin()."""
-        n = 32
+        n = 64
         counts, ms, nk = (C.c_int * n)(), (C.c_float * n)(), C.c_int()
         check(load().he_prof_end(self.h, n, counts, ms, C.byref(nk)))
         return {load().he_prof_kernel_name(i).decode(): (int(counts[i]), float(ms[i])) for i in range(nk.value) if counts[i]}
 
     def prof_end_bytes(self) -> dict:
         """{kernel name: (launches, total ms, algorithmic bytes)} since prof_begin() (hering_debug.h)."""
-        n = 32
+        n = 64
         counts, ms, by, nk = (C.c_int * n)(), (C.c_float * n)(), (C.c_double * n)(), C.c_int()
         check(load().he_prof_end_bytes(self.h, n, counts, ms, by, C.byref(nk)))
         return {load().he_prof_kernel_name(i).decode(): (int(counts[i]), float(ms[i]), float(by[i])) for i in range(nk.value) if counts[i]}
@@ -473,6 +473,18 @@ class Ring:
 
     def MulByVectorMontgomeryThenAddLazy(self, p1: Poly, vector: Poly, p2: Poly):
         check(load().he_mul_by_vector_montgomery(self.h, self.level, p1.h, vector.h, 1, p2.h))
+
+    def FoldStandardToConjugateInvariant(self, polyStandard: Poly, polyConjugateInvariant: Poly):
+        """Ring.FoldStandardToConjugateInvariant (ring/conjugate_invariant.go:28) with the index table of the Galois element
+        NthRoot - 1 of the standard ring, j -> N - 1 - j, the only one the reference passes (include/hering_bridge.h):
+        polyConjugateInvariant[j] = CRed(polyStandard[N-1-j] + polyStandard[j]) on limbs 0..level of this ring, which supplies
+        the moduli (either type, of either polynomial's degree)."""
+        check(load().he_fold_standard_to_conjugate_invariant(self.h, self.level, polyStandard.h, polyConjugateInvariant.h))
+
+    def UnfoldConjugateInvariantToStandard(self, polyConjugateInvariant: Poly, polyStandard: Poly):
+        """Ring.UnfoldConjugateInvariantToStandard (ring/conjugate_invariant.go:7): polyStandard[j] = polyStandard[N-1-j] =
+        polyConjugateInvariant[j] on limbs 0..level of this ring."""
+        check(load().he_unfold_conjugate_invariant_to_standard(self.level, polyConjugateInvariant.h, polyStandard.h))
 
     def AutomorphismNTT(self, pin: Poly, galel: int, pout: Poly):
         """Ring.AutomorphismNTT (ring/automorphism.go:38)"""
