@@ -1326,8 +1326,10 @@ static void gadget_product_single_p_lazy(const lo_evaluator *e, int levelQ, cons
         if (mask == 0) lo_decompose_and_split(e->dec, levelQ, levelP, levelP + 1, i, cxInv, c2Q, c2P);
         int nj = pw2 ? evk->nj[i] : 1;
         for (int j = 0; j < nj; j++, blk++) {
-            if (mask != 0)   /* ring.MaskVec, ring/vec_ops.go:870 */
-                for (int x = 0; x < N; x++) cw[x] = (cxInv[(size_t)i * N + x] >> (j * pw2)) & mask;
+            if (mask != 0) { /* ring.MaskVec, ring/vec_ops.go:870; Go's shift by 64 or more is zero (a key may carry such a window) */
+                const int w = j * pw2;
+                for (int x = 0; x < N; x++) cw[x] = w < 64 ? (cxInv[(size_t)i * N + x] >> w) & mask : 0;
+            }
             int first = (i == 0 && j == 0);
             for (int u = 0; u <= levelQ; u++) {
                 const lo_subring *s = e->ringQ->s[u];

@@ -231,6 +231,18 @@ def test_core_against_restatement(ctx, core512, batch):
     assert np.array_equal(c.S.down(acc), c.want[:batch])
 
 
+@pytest.mark.parametrize("n_lwe", [1, 7])
+def test_core_rows_shorter_than_the_rgsw_set(ctx, core512, n_lwe):
+    """n_lwe = 1, and n_lwe below the sixteen keys of the RGSW set: the first n_lwe words of every row and the first n_lwe keys"""
+    c = core512
+    rows = np.ascontiguousarray(c.rows[:, :n_lwe])
+    assert n_lwe < len(c.obrk) == N_LWE and rows.shape == (5, n_lwe)
+    want = np.stack([BR.blind_rotate_core(c.S.oev, rows[b], c.acc[b], c.obrk, c.ogks) for b in range(5)])
+    acc = c.S.up(c.acc)
+    c.ev.BlindRotateCore(rows, acc, c.BRK)
+    assert np.array_equal(c.S.down(acc), want)
+
+
 @pytest.mark.parametrize("switch", ["HERING_NO_BLINDROT_BATCH", "HERING_NO_RGSW_FUSED"])
 def test_core_per_entry_routes(switch):
     env = dict(os.environ)
