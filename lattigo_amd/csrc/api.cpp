@@ -766,6 +766,21 @@ struct Scope {  // per-call: select device, lock the context, reset the scratch 
     }
     ~Scope() { c->mu.unlock(); }
 };
+// host words into scratch from kernel arguments (no host buffer outlives the call; a captured graph holds them)
+template <class T>
+int scratch_words(Ctx &ctx, const std::vector<size_t> &w, T **d) {
+    TRY(ctx.arena_reserve(w.size() + 2));
+    size_t *p = reinterpret_cast<size_t *>(ctx.arena_take(w.size()));
+    *d = reinterpret_cast<T *>(p);
+    HIP_TRY(launch_tab_fill(p, w.data(), (int)w.size(), ctx.stream));
+    return HE_OK;
+}
+// a host selection of key indices on the device, two int32 per word
+int scratch_selection(Ctx &ctx, const int32_t *sel, size_t n, const int32_t **d) {
+    std::vector<size_t> tab((n + 1) / 2, 0);
+    for (size_t i = 0; i < n; i++) tab[i / 2] |= (size_t)(uint32_t)sel[i] << (32 * (i & 1));
+    return scratch_words(ctx, tab, d);
+}
 
 // ---- the context's submission queue (struct Coalescer): coalescing of concurrent single-ciphertext calls ---------------------
 constexpr size_t kTabRowsMin = 16;  // rows of the entry table reserved per batch entry (he_ctx_set_coalescing sizes it)
@@ -5003,9 +5018,8 @@ static int rp_pack_step(const char *who, he_handle hring, int level, int k, bool
         std::vector<size_t> tab(4 * (size_t)count);
         for (int z = 0; z < count; z++)
             for (int s = 0; s < 4; s++) tab[(size_t)s * count + z] = (size_t)(uintptr_t)v[4 * z + s].p;
-        TRY(ctx->arena_reserve(tab.size() + 2));
-        size_t *d = reinterpret_cast<size_t *>(ctx->arena_take(tab.size()));
-        HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), ctx->stream));
+        size_t *d = nullptr;
+        TRY(scratch_words(*ctx, tab, &d));
         ctx->acct(2.0 * (level + 1) * words, 0, 1, r->N);
         if (muls > 0) { Valu V(r->logN); V.mul(false, 2.0 * (level + 1) * muls); V.into(*ctx, 1); }
         HIP_TRY(launch_pack_step(r->dev, reinterpret_cast<const uint64_t *>(d), v[4 * count], v[4 * count + 1], k, post, count, 2.0 * words,
@@ -5028,24 +5042,46 @@ int he_ringpack_pack_post(he_handle ring, int level, int count, const he_handle 
 // RGSW external product (include/hering_rgsw.h; core/rgsw/evaluator.go)
 // ---------------------------------------------------------------------------------------
 namespace {
-// BlindRotationEvaluationKeySet's keys: RGSW ciphertexts of one shape, each two key handles
-struct RgswSet : Obj {
+// What a select form indexes: the keys of one evaluator and shape, with a resident [2][n] device table of addresses (row 0: the
+// keys' words; row 1: the set's own)
+struct KeySet : Obj {
     std::shared_ptr<Evaluator> ev;
-    std::vector<std::shared_ptr<Evk>> k0, k1;
-    size_t *d_tab = nullptr;  // [2][n] device addresses of the keys' words (rgsw0 | rgsw1): what the select form indexes
-    RgswSet() : Obj(T_RGSW_SET) {}
-    ~RgswSet() override {
-        if (!d_tab) return;
+    size_t *d_tab = nullptr;
+    using Obj::Obj;
+    int upload(const std::vector<size_t> &rows) {  // (the caller holds the context)
+        HIP_TRY(hipMalloc((void **)&d_tab, rows.size() * sizeof(size_t)));
+        HIP_TRY(hipMemcpy(d_tab, rows.data(), rows.size() * sizeof(size_t), hipMemcpyHostToDevice));
+        return HE_OK;
+    }
+    void release(void *with = nullptr) {  // the table, and what the set keeps beside it, once the stream is done with them
+        if (!d_tab && !with) return;
         hipSetDevice(ev->be->ctx->dev);
         hipStreamSynchronize(ev->be->ctx->stream);
         hipFree(d_tab);
+        hipFree(with);
     }
+};
+// BlindRotationEvaluationKeySet's keys: RGSW ciphertexts of one shape, each two key handles (table: rgsw0 | rgsw1)
+struct RgswSet : KeySet {
+    std::vector<std::shared_ptr<Evk>> k0, k1;
+    RgswSet() : KeySet(T_RGSW_SET) {}
+    ~RgswSet() override { release(); }
 };
 struct RgswShape {
     int levelQ = 0, levelP = -1;
     bool multiple_p = false;  // branch M (levelP >= 1): RNS digits; otherwise bit windows (pw2 == 0: one uncentred window per limb)
     bool fused = false;       // inside the domain of launch_rgsw_fused
+    RgswShape() = default;
+    explicit RgswShape(const Evk &k) : levelQ(k.nQk - 1), levelP(k.nPk - 1), multiple_p(levelP >= 1) {}  // the shape of a gadget key
 };
+// The window domain of the one-launch kernel: a standard ring, at most one special prime, the ring and level of
+// rgsw_fused_supported, every window inside a 64-bit word and every window offset inside a byte.  launch_rgsw_fused serves all of
+// it; launch_auto_fused its base-2 keys (pw2 != 0; hering_blindrot.h)
+bool fused_window_domain(const BasisExtender &be, const Evk &k) {
+    bool ok = be.type == 0 && k.nPk <= 1 && rgsw_fused_supported(be.Q->logN, k.nQk);
+    for (int i = 0; ok && i < k.nQk; i++) ok = (rgsw_nj(k, i) - 1) * k.pw2 < 64 && (k.pw2 ? k.prefix[i] : i) < 256;
+    return ok;
+}
 bool rgsw_same_shape(const Evk &a, const Evk &b) {
     return a.nQk == b.nQk && a.nPk == b.nPk && a.pw2 == b.pw2 && a.beta == b.beta && a.nj == b.nj;
 }
@@ -5053,8 +5089,7 @@ int rgsw_shape(const char *who, const Evaluator &ev, const Evk &a, const Evk &b,
     const BasisExtender &be = *ev.be;
     if (a.ev.get() != &ev || b.ev.get() != &ev) return fail(HE_EINVAL, "%s: key belongs to another evaluator", who);
     if (!rgsw_same_shape(a, b)) return fail(HE_EINVAL, "%s: the two gadget ciphertexts of an RGSW ciphertext differ in shape", who);
-    s->levelQ = a.nQk - 1; s->levelP = a.nPk - 1;
-    s->multiple_p = s->levelP >= 1;
+    *s = RgswShape(a);
     if (!a.pw2 && a.nPk == 0) return fail(HE_EINVAL, "%s: BaseTwoDecomposition == 0 needs a special prime", who);
     const int need = s->multiple_p ? base_rns_size(s->levelQ, s->levelP) : (a.pw2 ? a.prefix[s->levelQ + 1] : s->levelQ + 1);
     if (a.beta < need) return fail(HE_EINVAL, "%s: key has %d digits, %d needed", who, a.beta, need);
@@ -5068,9 +5103,7 @@ int rgsw_shape(const char *who, const Evaluator &ev, const Evk &a, const Evk &b,
             return fail(HE_EINVAL, "%s: 2 D W (q - 1) >= 2^64 (D = %d windows, W = 6q - 2, q = %llu): the 32-bit branch of the reference wraps",
                         who, a.nj[0], (unsigned long long)q0);
     }
-    bool ok = be.type == 0 && !s->multiple_p && rgsw_fused_supported(be.Q->logN, s->levelQ + 1);
-    for (int i = 0; ok && i <= s->levelQ; i++) ok = (rgsw_nj(a, i) - 1) * a.pw2 < 64 && (a.pw2 ? a.prefix[i] : i) < 256;
-    s->fused = ok;
+    s->fused = fused_window_domain(be, a);
     return HE_OK;
 }
 // Key words at or above q (hering_rgsw.h, "Key words"): served where the reference's own arithmetic is exact with words below
@@ -5191,6 +5224,42 @@ int rgsw_operands(Operands &o, int nQ, he_handle in0, he_handle in1, he_handle o
     o.inplace(o1, i1);
     return o.check();
 }
+// What he_rgsw_external_product_select and he_automorphism_ct_select share before their request is filed.  `shape` is the entry's
+// own check of its keys' shape, digits and one-launch domain (it fills *s); then the key words of every key (k1: the second
+// gadget ciphertext of key i, or k0 again), the selection, the operands, the request's blob and the frozen copy of the selection.
+int select_request(const char *who, const std::shared_ptr<Evaluator> &ev, const std::shared_ptr<KeySet> &set,
+                   const std::vector<std::shared_ptr<Evk>> &k0, const std::vector<std::shared_ptr<Evk>> &k1,
+                   const std::function<int(RgswShape *)> &shape, const int32_t *sel, int n_sel, he_handle in0, he_handle in1,
+                   he_handle out0, he_handle out1, RgswShape *s, CoReq &q, std::vector<int32_t> *selv) {
+    if (set->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key set belongs to another evaluator", who);
+    TRY(shape(s));
+    for (size_t i = 0; i < k0.size(); i++) TRY(rgsw_key_words(who, *ev, *k0[i], *k1[i], *s));
+    if (!sel || n_sel < 1) return fail(HE_EINVAL, "%s: null selection", who);
+    const int n = (int)k0.size();
+    for (int b = 0; b < n_sel; b++)
+        if (sel[b] < -1 || sel[b] >= n) return fail(HE_EINVAL, "%s: sel[%d] = %d outside [-1, %d)", who, b, (int)sel[b], n);
+    Operands o(q, who, *ev->be);
+    TRY(rgsw_operands(o, s->levelQ + 1, in0, in1, out0, out1));
+    if (n_sel != o.B) return fail(HE_EINVAL, "%s: n_sel = %d, the batch has %d entries", who, n_sel, o.B);
+    q.obj = ev.get(); q.key = set.get();
+    for (int b = 0; b < n_sel; b++) q.blob.push_back((uint64_t)(int64_t)sel[b]);
+    q.keep.push_back(ev); q.keep.push_back(set);
+    selv->assign(sel, sel + n_sel);  // frozen here: a scalar argument of the call
+    return HE_OK;
+}
+// ... and when it runs (`account(used)` and `launch` are the entry's own): the selection into scratch, the set's resident table
+int select_run(const char *who, const KeySet &set, const std::vector<std::shared_ptr<Evk>> &k0, const RgswShape &s, const std::vector<int32_t> &selv,
+               const View *v, int B, const std::function<void(int)> &account, decltype(launch_rgsw_fused) *launch) {
+    BasisExtender &be = *set.ev->be;
+    if ((int)selv.size() != B) return fail(HE_EINVAL, "%s: selection of %d for %d entries", who, (int)selv.size(), B);
+    account((int)std::count_if(selv.begin(), selv.end(), [](int32_t x) { return x >= 0; }));
+    RgswFusedArgs a;
+    rgsw_fused_args(a, be, *k0[0], s, v[0], v[1], v[2], v[3]);
+    a.ktab = set.d_tab; a.nkeys = (int)k0.size();
+    TRY(scratch_selection(*be.ctx, selv.data(), selv.size(), &a.sel));
+    HIP_TRY(launch(be.qp, a, B, be.ctx->stream));
+    return HE_OK;
+}
 }  // namespace
 
 namespace {
@@ -5256,8 +5325,7 @@ int he_rgsw_keyset_create(he_handle hev, int n, const he_handle *rgsw0, const he
     std::vector<size_t> tab(2 * (size_t)n);
     for (int i = 0; i < n; i++) { tab[i] = (size_t)(uintptr_t)set->k0[i]->d; tab[(size_t)n + i] = (size_t)(uintptr_t)set->k1[i]->d; }
     Scope sc(ev->be->ctx.get());
-    HIP_TRY(hipMalloc((void **)&set->d_tab, tab.size() * sizeof(size_t)));
-    HIP_TRY(hipMemcpy(set->d_tab, tab.data(), tab.size() * sizeof(size_t), hipMemcpyHostToDevice));
+    TRY(set->upload(tab));
     *out = reg(set);
     return HE_OK;
 }
@@ -5267,49 +5335,25 @@ int he_rgsw_external_product_select(he_handle hev, he_handle in0, he_handle in1,
     static const char *who = "he_rgsw_external_product_select";
     GET(ev, Evaluator, hev, T_EVAL);
     GET(set, RgswSet, hset, T_RGSW_SET);
-    BasisExtender &be = *ev->be;
-    if (set->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key set belongs to another evaluator", who);
     RgswShape s;
-    TRY(rgsw_shape(who, *ev, *set->k0[0], *set->k1[0], &s));
-    if (!s.fused) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_rgsw.h)", who);
-    for (size_t i = 0; i < set->k0.size(); i++) TRY(rgsw_key_words(who, *ev, *set->k0[i], *set->k1[i], s));
-    if (!sel || n_sel < 1) return fail(HE_EINVAL, "%s: null selection", who);
-    const int n = (int)set->k0.size();
-    for (int b = 0; b < n_sel; b++)
-        if (sel[b] < -1 || sel[b] >= n) return fail(HE_EINVAL, "%s: sel[%d] = %d outside [-1, %d)", who, b, (int)sel[b], n);
     CoReq q;
-    Operands o(q, who, be);
-    TRY(rgsw_operands(o, s.levelQ + 1, in0, in1, out0, out1));
-    if (n_sel != o.B) return fail(HE_EINVAL, "%s: n_sel = %d, the batch has %d entries", who, n_sel, o.B);
-    q.op = CO_RGSW; q.obj = ev.get(); q.key = set.get(); q.par[1] = 1;
-    for (int b = 0; b < n_sel; b++) q.blob.push_back((uint64_t)(int64_t)sel[b]);
-    q.keep.push_back(ev); q.keep.push_back(set);
-    const std::vector<int32_t> selv(sel, sel + n_sel);  // frozen here: a scalar argument of the call
-    q.run = [ev, set, s, selv](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        if ((int)selv.size() != B) return fail(HE_EINVAL, "he_rgsw_external_product_select: selection of %d for %d entries", (int)selv.size(), B);
-        // the selection, two int32 per word, into scratch from kernel arguments (no host buffer outlives the call; a captured
-        // graph holds it); the keys' addresses are resident with the set
-        int used = 0;
-        std::vector<size_t> tab(((size_t)B + 1) / 2, 0);
-        for (int b = 0; b < B; b++) {
-            tab[b / 2] |= (size_t)(uint32_t)selv[b] << (32 * (b & 1));
-            used += selv[b] >= 0;
-        }
-        if (used) rgsw_account(*ev, *set->k0[0], s, used);
-        be.ctx->acct(4.0 * (s.levelQ + 1), 0, B - used, be.Q->N);
-        TRY(be.ctx->arena_reserve(tab.size() + 2));
-        size_t *d = reinterpret_cast<size_t *>(be.ctx->arena_take(tab.size()));
-        HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), be.ctx->stream));
-        RgswFusedArgs a;
-        rgsw_fused_args(a, be, *set->k0[0], s, v[0], v[1], v[2], v[3]);
-        a.ktab = set->d_tab; a.nkeys = (int)set->k0.size();
-        a.sel = reinterpret_cast<const int32_t *>(d);
-        HIP_TRY(launch_rgsw_fused(be.qp, a, B, be.ctx->stream));
+    std::vector<int32_t> selv;
+    auto shape = [&](RgswShape *sh) -> int {
+        TRY(rgsw_shape(who, *ev, *set->k0[0], *set->k1[0], sh));
+        if (!sh->fused) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_rgsw.h)", who);
         return HE_OK;
     };
+    TRY(select_request(who, ev, set, set->k0, set->k1, shape, sel, n_sel, in0, in1, out0, out1, &s, q, &selv));
+    q.op = CO_RGSW; q.par[1] = 1;
+    q.run = [ev, set, s, selv](const View *v, int B) -> int {
+        auto account = [&](int used) {
+            if (used) rgsw_account(*ev, *set->k0[0], s, used);
+            ev->be->ctx->acct(4.0 * (s.levelQ + 1), 0, B - used, ev->be->Q->N);
+        };
+        return select_run(who, *set, set->k0, s, selv, v, B, account, launch_rgsw_fused);
+    };
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*be.ctx, o.B, q);
+    return co_dispatch(*ev->be->ctx, (int)selv.size(), q);
 }
 
 // ---- the element-wise helpers of core/rgsw/evaluator.go:283-356 on the words of a device-resident gadget ciphertext ----------
@@ -5420,35 +5464,18 @@ int he_rgsw_key_add_plaintext_lazy(he_handle hpt, he_handle hk0, he_handle hk1) 
 // ---------------------------------------------------------------------------------------
 namespace {
 // BlindRotationEvaluationKeySet's automorphism keys: Galois keys of one shape with their Galois elements
-struct GaloisSet : Obj {
-    std::shared_ptr<Evaluator> ev;
+// (table: the keys' words | their index tables)
+struct GaloisSet : KeySet {
     std::vector<std::shared_ptr<Evk>> keys;
     std::vector<uint64_t> gal;
-    size_t *d_tab = nullptr;      // [2][n] device addresses: the keys' words | their index tables: what the select form indexes
     uint32_t *d_index = nullptr;  // [n][N] AutomorphismNTTWithIndex tables
-    GaloisSet() : Obj(T_GALOIS_SET) {}
-    ~GaloisSet() override {
-        if (!d_tab && !d_index) return;
-        hipSetDevice(ev->be->ctx->dev);
-        hipStreamSynchronize(ev->be->ctx->stream);
-        if (d_tab) hipFree(d_tab);
-        if (d_index) hipFree(d_index);
-    }
+    GaloisSet() : KeySet(T_GALOIS_SET) {}
+    ~GaloisSet() override { release(d_index); }
     int find(uint64_t g) const {
         for (size_t i = 0; i < gal.size(); i++)
             if (gal[i] == g) return (int)i;
         return -1;
     }
-};
-// inside the domain of launch_auto_fused (hering_blindrot.h)?
-bool auto_select_domain(const Evaluator &ev, const Evk &k) {
-    const BasisExtender &be = *ev.be;
-    bool ok = be.type == 0 && k.pw2 != 0 && k.nPk <= 1 && rgsw_fused_supported(be.Q->logN, k.nQk);
-    for (int i = 0; ok && i < k.nQk; i++) ok = (k.nj[i] - 1) * k.pw2 < 64 && k.prefix[i] < 256;
-    return ok;
-}
-struct GaloisShape : RgswShape {
-    explicit GaloisShape(const Evk &k) { levelQ = k.nQk - 1; levelP = k.nPk - 1; }
 };
 // the bytes and arithmetic of `used` automorphisms with keys of shape k and of B - used copies
 void auto_select_account(Evaluator &ev, const Evk &k, int used, int B) {
@@ -5474,18 +5501,13 @@ int blindrot_batched(Evaluator &ev, const RgswSet &rset, const GaloisSet &gset, 
                      View acc1, int B) {
     BasisExtender &be = *ev.be;
     hipStream_t st = be.ctx->stream;
-    // the selections of every round, two int32 per word, into scratch from kernel arguments (as the select forms do)
-    std::vector<size_t> tab((p.sel.size() + 1) / 2, 0);
-    for (size_t i = 0; i < p.sel.size(); i++) tab[i / 2] |= (size_t)(uint32_t)p.sel[i] << (32 * (i & 1));
-    TRY(be.ctx->arena_reserve(tab.size() + 2));
-    size_t *d = reinterpret_cast<size_t *>(be.ctx->arena_take(tab.size()));
-    HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), st));
-    const int32_t *dsel = reinterpret_cast<const int32_t *>(d);
+    const int32_t *dsel = nullptr;  // the selections of every round (as the select forms do)
+    TRY(scratch_selection(*be.ctx, p.sel.data(), p.sel.size(), &dsel));
     const Evk &gk = *gset.keys[0];
     RgswFusedArgs ap, aa;
     rgsw_fused_args(ap, be, *rset.k0[0], s, acc0, acc1, acc0, acc1);
     ap.ktab = rset.d_tab; ap.nkeys = (int)rset.k0.size();
-    rgsw_fused_args(aa, be, gk, GaloisShape(gk), acc0, acc1, acc0, acc1);
+    rgsw_fused_args(aa, be, gk, RgswShape(gk), acc0, acc1, acc0, acc1);
     aa.ktab = gset.d_tab; aa.nkeys = (int)gset.keys.size();
     if (p.n_prod) rgsw_account(ev, *rset.k0[0], s, (int)p.n_prod);
     auto_select_account(ev, gk, (int)p.n_auto, (int)p.n_auto);
@@ -5540,14 +5562,13 @@ int he_galois_keyset_create(he_handle hev, int n, const uint64_t *gal_els, const
     const size_t N = be.Q->N;
     Scope sc(be.ctx.get());
     HIP_TRY(hipMalloc((void **)&set->d_index, (size_t)n * N * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&set->d_tab, 2 * (size_t)n * sizeof(size_t)));
     std::vector<size_t> tab(2 * (size_t)n);
     for (int i = 0; i < n; i++) {
         uint32_t *ix = set->d_index + (size_t)i * N;
         HIP_TRY(launch_build_automorphism_index(be.Q->logN, be.Q->logN + be.type, set->gal[i], ix, be.ctx->stream));
         tab[i] = (size_t)(uintptr_t)set->keys[i]->d; tab[(size_t)n + i] = (size_t)(uintptr_t)ix;
     }
-    HIP_TRY(hipMemcpy(set->d_tab, tab.data(), tab.size() * sizeof(size_t), hipMemcpyHostToDevice));
+    TRY(set->upload(tab));
     HIP_TRY(hipStreamSynchronize(be.ctx->stream));
     *out = reg(set);
     return HE_OK;
@@ -5558,47 +5579,24 @@ int he_automorphism_ct_select(he_handle hev, he_handle in0, he_handle in1, he_ha
     static const char *who = "he_automorphism_ct_select";
     GET(ev, Evaluator, hev, T_EVAL);
     GET(set, GaloisSet, hset, T_GALOIS_SET);
-    BasisExtender &be = *ev->be;
-    if (set->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: key set belongs to another evaluator", who);
-    const Evk &k = *set->keys[0];
-    if (!auto_select_domain(*ev, k)) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_blindrot.h)", who);
-    if (k.beta < k.prefix[k.nQk]) return fail(HE_EINVAL, "%s: key has %d digits, %d needed", who, k.beta, k.prefix[k.nQk]);
-    const RgswShape s = GaloisShape(k);
-    for (size_t i = 0; i < set->keys.size(); i++) TRY(rgsw_key_words(who, *ev, *set->keys[i], *set->keys[i], s));
-    if (!sel || n_sel < 1) return fail(HE_EINVAL, "%s: null selection", who);
-    const int n = (int)set->keys.size();
-    for (int b = 0; b < n_sel; b++)
-        if (sel[b] < -1 || sel[b] >= n) return fail(HE_EINVAL, "%s: sel[%d] = %d outside [-1, %d)", who, b, (int)sel[b], n);
+    RgswShape s;
     CoReq q;
-    Operands o(q, who, be);
-    TRY(rgsw_operands(o, s.levelQ + 1, in0, in1, out0, out1));
-    if (n_sel != o.B) return fail(HE_EINVAL, "%s: n_sel = %d, the batch has %d entries", who, n_sel, o.B);
-    q.op = CO_AUTO_SELECT; q.obj = ev.get(); q.key = set.get();
-    for (int b = 0; b < n_sel; b++) q.blob.push_back((uint64_t)(int64_t)sel[b]);
-    q.keep.push_back(ev); q.keep.push_back(set);
-    const std::vector<int32_t> selv(sel, sel + n_sel);  // frozen here: a scalar argument of the call
-    q.run = [ev, set, s, selv](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        if ((int)selv.size() != B) return fail(HE_EINVAL, "he_automorphism_ct_select: selection of %d for %d entries", (int)selv.size(), B);
-        int used = 0;
-        std::vector<size_t> tab(((size_t)B + 1) / 2, 0);
-        for (int b = 0; b < B; b++) {
-            tab[b / 2] |= (size_t)(uint32_t)selv[b] << (32 * (b & 1));
-            used += selv[b] >= 0;
-        }
-        auto_select_account(*ev, *set->keys[0], used, B);
-        TRY(be.ctx->arena_reserve(tab.size() + 2));
-        size_t *d = reinterpret_cast<size_t *>(be.ctx->arena_take(tab.size()));
-        HIP_TRY(launch_tab_fill(d, tab.data(), (int)tab.size(), be.ctx->stream));
-        RgswFusedArgs a;
-        rgsw_fused_args(a, be, *set->keys[0], s, v[0], v[1], v[2], v[3]);
-        a.ktab = set->d_tab; a.nkeys = (int)set->keys.size();
-        a.sel = reinterpret_cast<const int32_t *>(d);
-        HIP_TRY(launch_auto_fused(be.qp, a, B, be.ctx->stream));
+    std::vector<int32_t> selv;
+    auto shape = [&](RgswShape *sh) -> int {
+        const Evk &k = *set->keys[0];
+        if (!k.pw2 || !fused_window_domain(*ev->be, k)) return fail(HE_EINVAL, "%s: the shape is outside the domain of the one-launch kernel (hering_blindrot.h)", who);
+        if (k.beta < k.prefix[k.nQk]) return fail(HE_EINVAL, "%s: key has %d digits, %d needed", who, k.beta, k.prefix[k.nQk]);
+        *sh = RgswShape(k);
         return HE_OK;
     };
+    TRY(select_request(who, ev, set, set->keys, set->keys, shape, sel, n_sel, in0, in1, out0, out1, &s, q, &selv));
+    q.op = CO_AUTO_SELECT;
+    q.run = [ev, set, s, selv](const View *v, int B) -> int {
+        auto account = [&](int used) { auto_select_account(*ev, *set->keys[0], used, B); };
+        return select_run(who, *set, set->keys, s, selv, v, B, account, launch_auto_fused);
+    };
     q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*be.ctx, o.B, q);
+    return co_dispatch(*ev->be->ctx, (int)selv.size(), q);
 }
 int he_blind_rotate_core(he_handle hev, const uint64_t *a, int batch, int n_lwe, he_handle acc0, he_handle acc1, he_handle hrset,
                          he_handle hgset) {
@@ -5633,9 +5631,9 @@ int he_blind_rotate_core(he_handle hev, const uint64_t *a, int batch, int n_lwe,
         }
     }
     static const bool no_batch = env_flag("HERING_NO_BLINDROT_BATCH");
-    const bool batched = !no_batch && !rgsw_no_fused() && s.fused && auto_select_domain(*ev, gk) && gk.beta >= gk.prefix[gk.nQk];
+    const bool batched = !no_batch && !rgsw_no_fused() && s.fused && gk.pw2 && fused_window_domain(be, gk) && gk.beta >= gk.prefix[gk.nQk];
     if (batched) {
-        for (size_t i = 0; i < gset->keys.size(); i++) TRY(rgsw_key_words(who, *ev, *gset->keys[i], *gset->keys[i], GaloisShape(gk)));
+        for (size_t i = 0; i < gset->keys.size(); i++) TRY(rgsw_key_words(who, *ev, *gset->keys[i], *gset->keys[i], RgswShape(gk)));
         const std::vector<blindrot::Round> rounds = blindrot::blindrot_merge(plan->lists);
         plan->sel.assign(rounds.size() * 2 * (size_t)B, -1);
         plan->any.assign(rounds.size() * 2, 0);

@@ -258,8 +258,8 @@ struct MaskSpreadArgs {
 hipError_t launch_mask_spread(const RingDev &r, const MaskSpreadArgs &a, View src, uint64_t *dec, size_t dec_bs, size_t dec_ds,
                               int batch, hipStream_t s);
 
-// ---- RGSW external product, small rings (core/rgsw/evaluator.go:130-204) -------------------------
-// The whole product of one batch entry in one workgroup (rgsw_fused_kernel): out_c = [ModDown of] sum over (component k, source
+// ---- the fused gadget product of a small ring: one kernel (gadget_fused_kernel), two tails --------
+// RGSW external product (core/rgsw/evaluator.go:130-204), the whole product of one batch entry in one workgroup: out_c = [ModDown of] sum over (component k, source
 // limb i, window j) of key_k[prefix[i] + j][c] * NTT((INTT(in_k)[i] >> j pw2) & mask), limbs 0..nQ-1, canonical.  Standard rings,
 // at most one special prime (nP; its modulus record is p_mod and its limb inside a key block key_p_limb).  out_k may be in_k.
 // ktab (select form): a device array [2][nkeys] of key base addresses (rgsw0 | rgsw1) and sel, a device array of one int32 per
@@ -281,11 +281,11 @@ struct RgswFusedArgs {
 };
 bool rgsw_fused_supported(int logN, int nQ);  // logN 9..11 and the coefficients of 2 nQ limbs beside the exchange buffer in 64 KiB of LDS
 hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s);
-// rlwe.Evaluator.Automorphism (core/rlwe/evaluator_automorphism.go:13-56) of one batch entry in one workgroup
-// (auto_fused_kernel), select form only: entry b takes key sel[b] of the set, or is copied (sel[b] == -1).  Same domain and
-// arguments as launch_rgsw_fused with a base-2 gadget key (pw2 != 0); key0 / key1 are not read and ktab is a device array
-// [2][nkeys]: the keys' base addresses | the addresses of their automorphism index tables (uint32 [N], out[j] = in[index[j]]).
-// out_k may be in_k.
+// rlwe.Evaluator.Automorphism (core/rlwe/evaluator_automorphism.go:13-56) of one batch entry in one workgroup: the same kernel
+// decomposing in1 alone, with the tail out = permute(acc + (in0, 0)).  Select form only: entry b takes key sel[b] of the set, or
+// is copied (sel[b] == -1).  Same domain and arguments as launch_rgsw_fused with a base-2 gadget key (pw2 != 0); key0 / key1 are
+// not read and ktab is a device array [2][nkeys]: the keys' base addresses | the addresses of their automorphism index tables
+// (uint32 [N], out[j] = in[index[j]]).  out_k may be in_k.
 hipError_t launch_auto_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s);
 
 // ---- key-switch inner product ---------------------------------------------------------------

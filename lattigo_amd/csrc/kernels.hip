@@ -4412,15 +4412,26 @@ hipError_t launch_tensor(const RingDev &r, const LimbTab &tab, const uint64_t *s
 }
 
 // ------------------------------------------------------------------------------------
-// RGSW external product of a small ring in ONE launch (core/rgsw/evaluator.go:130-204, the bit-window branch, which also
-// serves the 32-bit branch :84-128 wherever that one cannot wrap).  One workgroup per batch entry, sixteen coefficients per
-// thread as in ntt_rows_kernel with a single row (the same radix-16 rounds and LDS exchanges).
-//   phase 1: both components, every Q limb: INTT with N^-1, the canonical coefficients parked in LDS (`coef`, thread-private
-//            slots) -- every input word is read before any output word is written, so out_k may be in_k;
+// The fused gadget product of a small ring: ONE launch, one workgroup per batch entry, sixteen coefficients per thread as in
+// ntt_rows_kernel with a single row (the same radix-16 rounds and LDS exchanges).  Two instantiations share every phase:
+//   AUTO = false: the RGSW external product (core/rgsw/evaluator.go:130-204, the bit-window branch, which also serves the
+//            32-bit branch :84-128 wherever that one cannot wrap): both components are decomposed, component k against the
+//            key block key_k (the arguments', or in the select form the entry's own words ktab[k][sel[z]]);
+//   AUTO = true: rlwe.Evaluator.Automorphism, every entry with its own key of a resident set (core/rlwe/
+//            evaluator_automorphism.go:13-56 over a base-2 gadget key, evaluator_gadget_product.go:203-338), select form
+//            only: in1 alone is decomposed, against ktab[0][sel[z]]; ktab[1][sel[z]] is that key's automorphism index table.
+//   pass-through (select form): sel[z] < 0 copies the entry (uniform over the workgroup: no barrier has been passed);
+//   phase 1: every decomposed component, every Q limb: INTT with N^-1, the canonical coefficients parked in LDS (`coef`,
+//            thread-private slots) -- every decomposed input word is read before any output word is written, so out_k may
+//            be in_k;
 //   phase 2: per destination limb (the special prime first): for every (component, source limb, window) mask the coefficients,
 //            transform them in the destination modulus and multiply the two key rows into two register accumulators;
 //            the P limb's accumulators are inverse-transformed and kept (ext); a Q limb ends with ModDown's last step,
-//            MRed(NTT(lift(ext)) + 2q - acc, q - P^-1), or with the plain store when there is no special prime.
+//            MRed(NTT(lift(ext)) + 2q - acc, q - P^-1), or with nothing when there is no special prime; then its tail:
+//   tail, AUTO = false: the plain store of both accumulators;
+//   tail, AUTO = true: tmp0 = acc0 + in0 with one conditional subtraction (ringQ.Add), tmp1 = acc1; both go through the
+//            exchange buffer and out[e] = tmp[index[e]] (AutomorphismNTTWithIndex): every thread stores the positions e it
+//            loaded in0 at, contiguous along the wave, after the barrier that follows the buffer's fill -- so out0 may be in0.
 // The canonical output does not depend on the reduction schedule, so windows are reduced below the destination modulus before
 // they are transformed and the accumulators are reduced after every product.
 // ------------------------------------------------------------------------------------
@@ -4482,34 +4493,33 @@ struct RgswKArgs {
     const ModConst *mc;
     const uint64_t *twf, *twi;
 };
-template <int LOGB>
-__global__ void __launch_bounds__((1 << LOGB) / 16) rgsw_fused_kernel(RgswKArgs K) {
-    constexpr int N = 1 << LOGB, T = N / 16;
+template <int LOGB, bool AUTO>
+__global__ void __launch_bounds__((1 << LOGB) / 16) gadget_fused_kernel(RgswKArgs K) {
+    constexpr int N = 1 << LOGB, T = N / 16, NC = AUTO ? 1 : 2;  // components that are decomposed
     __shared__ uint64_t lds[N + N / 16];
-    extern __shared__ uint64_t coef[];  // [2 nQ][16][T]: slot (s, k) of thread tau
+    extern __shared__ uint64_t coef[];  // [NC nQ][16][T]: slot (s, k) of thread tau
     const RgswFusedArgs &A = K.a;
     const int tau = threadIdx.x, nQ = A.nQ;
     const size_t z = blockIdx.x;
     const uint64_t *in0 = A.in0.p + z * A.in0.bstride, *in1 = A.in1.p + z * A.in1.bstride;
     uint64_t *out0 = A.out0.p + z * A.out0.bstride, *out1 = A.out1.p + z * A.out1.bstride;
     const uint64_t *key0 = A.key0, *key1 = A.key1;
-    if (A.ktab) {  // select form: this entry's own key of the resident table, or none (the entry is passed through)
+    if (AUTO || A.ktab) {  // select form: this entry's own words of the resident table, or none (the entry is passed through)
         const int si = A.sel[z];
-        if (si >= 0) {
-            key0 = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)si));
-            key1 = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)A.nkeys + si));
-        } else {
+        if (si < 0) {  // (uniform over the workgroup: no barrier has been passed)
             for (int e = tau; e < nQ * N; e += T) {
                 if (out0 != in0) out0[e] = in0[e];
                 if (out1 != in1) out1[e] = in1[e];
             }
             return;
         }
-    }
+        key0 = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)si));
+        key1 = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)A.nkeys + si));
+    }  // (AUTO: key0 is the key, key1 the address of its uint32 index table)
     // ---- phase 1
 #pragma unroll 1
-    for (int s = 0; s < 2 * nQ; s++) {
-        const int k = s >= nQ, i = s - k * nQ;
+    for (int s = 0; s < NC * nQ; s++) {
+        const int k = AUTO ? 1 : s >= nQ, i = AUTO ? s : s - k * nQ;
         const uint64_t *__restrict__ src = (k ? in1 : in0) + (size_t)i * N;
         const ModConst mc = K.mc[i];
         const uint64_t twoq = mc.q << 1;
@@ -4549,8 +4559,8 @@ __global__ void __launch_bounds__((1 << LOGB) / 16) rgsw_fused_kernel(RgswKArgs 
 #pragma unroll
             for (int kk = 0; kk < 16; kk++) acc[c][kk] = 0;
 #pragma unroll 1
-        for (int s = 0; s < 2 * nQ; s++) {
-            const int k = s >= nQ, i = s - k * nQ;
+        for (int s = 0; s < NC * nQ; s++) {
+            const int k = AUTO ? 0 : s >= nQ, i = s - k * nQ;
             const uint64_t *kb = k ? key1 : key0;
             uint64_t x[16];
 #pragma unroll
@@ -4619,12 +4629,32 @@ __global__ void __launch_bounds__((1 << LOGB) / 16) rgsw_fused_kernel(RgswKArgs 
                 }
             }
         }
-        uint64_t *o0 = out0 + (size_t)u * N, *o1 = out1 + (size_t)u * N;
+        if constexpr (AUTO) {  // add in0 and store both components through the automorphism (key1: the index table)
+            const uint32_t *__restrict__ index = reinterpret_cast<const uint32_t *>(key1);
+            const uint64_t *__restrict__ a0 = in0 + (size_t)u * N;
 #pragma unroll
-        for (int kk = 0; kk < 16; kk++) {
-            const int e = nat_e<T>(kk, tau);
-            o0[e] = acc[0][kk];
-            o1[e] = acc[1][kk];
+            for (int kk = 0; kk < 16; kk++) acc[0][kk] = cred(acc[0][kk] + a0[nat_e<T>(kk, tau)], q);
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                uint64_t *o = (c ? out1 : out0) + (size_t)u * N;
+                __syncthreads();  // (the exchange buffer's last readers)
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = acc[c][kk];
+                __syncthreads();
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) {
+                    const int e = nat_e<T>(kk, tau);
+                    o[e] = lds[lds_phys((int)index[e])];
+                }
+            }
+        } else {
+            uint64_t *o0 = out0 + (size_t)u * N, *o1 = out1 + (size_t)u * N;
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                const int e = nat_e<T>(kk, tau);
+                o0[e] = acc[0][kk];
+                o1[e] = acc[1][kk];
+            }
         }
     }
 }
@@ -4633,200 +4663,34 @@ bool rgsw_fused_supported(int logN, int nQ) {
     const size_t n = (size_t)1 << logN;
     return (n + n / 16 + 2 * (size_t)nQ * n) * 8 <= 65536;  // the exchange buffer and the parked coefficients, in LDS
 }
-hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s) {
+template <bool AUTO>
+static hipError_t launch_gadget_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s) {
     if (!rgsw_fused_supported(r.logN, a.nQ) || batch <= 0 || a.nP < 0 || a.nP > 1 || !no_tab({a.in0, a.in1, a.out0, a.out1}) ||
-        !a.in0.p || !a.in1.p || !a.out0.p || !a.out1.p || (!a.ktab && (!a.key0 || !a.key1)) || (a.ktab && (!a.sel || a.nkeys <= 0)))
+        !a.in0.p || !a.in1.p || !a.out0.p || !a.out1.p || (a.ktab && (!a.sel || a.nkeys <= 0)) ||
+        (AUTO ? !a.ktab || a.pw2 <= 0 : !a.ktab && (!a.key0 || !a.key1)))
         return hipErrorInvalidValue;
     RgswKArgs K{};
     K.a = a; K.mc = r.mc; K.twf = r.tw_fwd; K.twi = r.tw_inv;
-    const size_t dyn = 2 * (size_t)a.nQ * r.N * 8;
+    const size_t dyn = (AUTO ? 1 : 2) * (size_t)a.nQ * r.N * 8;
     const unsigned T = (unsigned)r.N / 16;
     double windows = 0.0;
     for (int i = 0; i < a.nQ; i++) windows += a.nj[i];
-    // both components in and out, and the key rows of every window (shared by the batch: counted once)
-    ProfScope ps(K_RGSW_FUSED, s, (4.0 * a.nQ * batch + (a.ktab ? 0.0 : 4.0 * windows * (a.nQ + a.nP))) * (double)r.N * 8.0);
+    // both components in and out, and the key rows of every window where the batch shares them (counted once); the keys of a
+    // selection differ by entry and are not counted
+    ProfScope ps(AUTO ? K_AUTO_FUSED : K_RGSW_FUSED, s,
+                 (4.0 * a.nQ * batch + (a.ktab ? 0.0 : 4.0 * windows * (a.nQ + a.nP))) * (double)r.N * 8.0);
     switch (r.logN) {
-        case 9: hipLaunchKernelGGL(rgsw_fused_kernel<9>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
-        case 10: hipLaunchKernelGGL(rgsw_fused_kernel<10>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
-        default: hipLaunchKernelGGL(rgsw_fused_kernel<11>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        case 9: hipLaunchKernelGGL((gadget_fused_kernel<9, AUTO>), dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        case 10: hipLaunchKernelGGL((gadget_fused_kernel<10, AUTO>), dim3((unsigned)batch), dim3(T), dyn, s, K); break;
+        default: hipLaunchKernelGGL((gadget_fused_kernel<11, AUTO>), dim3((unsigned)batch), dim3(T), dyn, s, K); break;
     }
     return hipGetLastError();
 }
-
-// ------------------------------------------------------------------------------------
-// rlwe.Evaluator.Automorphism of a small ring in ONE launch, every batch entry with its own key of a resident set
-// (core/rlwe/evaluator_automorphism.go:13-56 over a base-2 gadget key, evaluator_gadget_product.go:203-338): the sibling of
-// rgsw_fused_kernel, with its thread layout, transforms, exchange buffer and key addressing.
-//   pass-through: sel[z] < 0 copies the entry;
-//   phase 1: in1 only, every Q limb: INTT with N^-1, the canonical coefficients parked in LDS -- all of in1 is read here;
-//   phase 2: per destination limb (the special prime first): every (source limb, window) masked, transformed and multiplied
-//            by the key's two rows; the P limb's accumulators are kept as coefficients (ext), a Q limb ends with ModDown's
-//            last step (or nothing, without a special prime);
-//   add and permute: tmp0 = acc0 + in0 with one conditional subtraction (ringQ.Add), tmp1 = acc1; both go through the exchange
-//            buffer and out[e] = tmp[index[e]] (AutomorphismNTTWithIndex): every thread stores the positions e it loaded in0
-//            at, contiguous along the wave, after the barrier that follows the buffer's fill -- so out0 may be in0.
-// ------------------------------------------------------------------------------------
-template <int LOGB>
-__global__ void __launch_bounds__((1 << LOGB) / 16) auto_fused_kernel(RgswKArgs K) {
-    constexpr int N = 1 << LOGB, T = N / 16;
-    __shared__ uint64_t lds[N + N / 16];
-    extern __shared__ uint64_t coef[];  // [nQ][16][T]: slot (i, k) of thread tau
-    const RgswFusedArgs &A = K.a;
-    const int tau = threadIdx.x, nQ = A.nQ;
-    const size_t z = blockIdx.x;
-    const uint64_t *in0 = A.in0.p + z * A.in0.bstride, *in1 = A.in1.p + z * A.in1.bstride;
-    uint64_t *out0 = A.out0.p + z * A.out0.bstride, *out1 = A.out1.p + z * A.out1.bstride;
-    const int si = A.sel[z];
-    if (si < 0) {  // (uniform over the workgroup: no barrier has been passed)
-        for (int e = tau; e < nQ * N; e += T) {
-            if (out0 != in0) out0[e] = in0[e];
-            if (out1 != in1) out1[e] = in1[e];
-        }
-        return;
-    }
-    // ktab: [2][nkeys], the keys' words | their automorphism index tables
-    const uint64_t *key = reinterpret_cast<const uint64_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)si));
-    const uint32_t *__restrict__ index =
-        reinterpret_cast<const uint32_t *>(ldc(reinterpret_cast<const uint64_t *>(A.ktab), (size_t)A.nkeys + si));
-    // ---- phase 1
-#pragma unroll 1
-    for (int i = 0; i < nQ; i++) {
-        const uint64_t *__restrict__ src = in1 + (size_t)i * N;
-        const ModConst mc = K.mc[i];
-        const uint64_t twoq = mc.q << 1;
-        uint64_t x[16];
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) x[kk] = ldnt(&src[nat_e<T>(kk, tau)]);
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) x[kk] = x[kk] >= twoq ? bred_add_lazy(x[kk], mc.q, mc.brc0) : x[kk];
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = x[kk];
-        __syncthreads();
-        rgsw_ntt_inv<LOGB>(x, lds, K.twi + (size_t)i * N, tau, mc);
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) coef[(i * 16 + kk) * T + tau] = x[kk];
-    }
-    // ---- phase 2
-    uint64_t ext[2][16];
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) ext[c][kk] = 0;
-    const int nD = nQ + A.nP;
-#pragma unroll 1
-    for (int ui = 0; ui < nD; ui++) {
-        const bool isP = A.nP != 0 && ui == 0;
-        const int u = isP ? 0 : ui - A.nP;
-        const int mi = isP ? A.p_mod : u;
-        const int kl = isP ? A.key_p_limb : u;
-        const ModConst mc = K.mc[mi];
-        const uint64_t q = mc.q, qinv = mc.qinv, twoq = mc.q << 1;
-        const uint64_t *__restrict__ twf = K.twf + (size_t)mi * N;
-        const bool red = A.mask >= q;
-        uint64_t acc[2][16];
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) acc[c][kk] = 0;
-#pragma unroll 1
-        for (int i = 0; i < nQ; i++) {
-            uint64_t x[16];
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) x[kk] = coef[(i * 16 + kk) * T + tau];
-#pragma unroll 1
-            for (int j = 0; j < (int)A.nj[i]; j++) {
-                const int shift = j * A.pw2;
-                uint64_t y[16];
-#pragma unroll
-                for (int kk = 0; kk < 16; kk++) {
-                    y[kk] = (x[kk] >> shift) & A.mask;
-                    if (red) y[kk] = bred_add_lazy(y[kk], q, mc.brc0);
-                }
-                __syncthreads();  // (the previous transform's words are still being read)
-                rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);
-                const size_t d = (size_t)A.prefix[i] + j;
-                const uint64_t *__restrict__ k0 = key + ((d * 2) * A.key_limbs + kl) * N;
-                const uint64_t *__restrict__ k1 = k0 + (size_t)A.key_limbs * N;
-#pragma unroll
-                for (int kk = 0; kk < 16; kk++) {
-                    const int e = nat_e<T>(kk, tau);
-                    uint64_t v = lds[lds_phys(e)];
-                    v = v >= twoq ? v - twoq : v;
-                    acc[0][kk] = cred(acc[0][kk] + mred_w32(v, k0[e], q, qinv), q);
-                    acc[1][kk] = cred(acc[1][kk] + mred_w32(v, k1[e], q, qinv), q);
-                }
-            }
-        }
-        if (isP) {
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                __syncthreads();
-#pragma unroll
-                for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = acc[c][kk];
-                __syncthreads();
-                rgsw_ntt_inv<LOGB>(ext[c], lds, K.twi + (size_t)mi * N, tau, mc);
-            }
-            continue;
-        }
-        if (A.nP) {  // ModDown's last step with the reference's float-quotient lift, as in rgsw_fused_kernel
-            const uint64_t pmq = A.p_mod_q[u], sdn = A.md_s[u];
-            const uint64_t p = K.mc[A.p_mod].q, hq = bred_add(A.p_half, q, mc.brc0);
-            const double pd = __ull2double_rn(p);
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                uint64_t y[16];
-#pragma unroll
-                for (int kk = 0; kk < 16; kk++) {
-                    const uint64_t x = cred(ext[c][kk] + A.p_half, p);
-                    const uint64_t w = (uint64_t)__ddiv_rn(__ull2double_rn(x), pd);
-                    const uint64_t r = cred(bred_add(x, q, mc.brc0) + q - hq, q);
-                    y[kk] = w ? cred(r + q - pmq, q) : r;
-                }
-                __syncthreads();
-                rgsw_ntt_fwd<LOGB>(y, lds, twf, tau, mc);
-#pragma unroll
-                for (int kk = 0; kk < 16; kk++) {
-                    uint64_t v = lds[lds_phys(nat_e<T>(kk, tau))];
-                    v = v >= twoq ? v - twoq : v;
-                    acc[c][kk] = mred_w32(v + twoq - acc[c][kk], sdn, q, qinv);
-                }
-            }
-        }
-        // ---- add in0 and store both components through the automorphism
-        const uint64_t *__restrict__ a0 = in0 + (size_t)u * N;
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) acc[0][kk] = cred(acc[0][kk] + a0[nat_e<T>(kk, tau)], q);
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            uint64_t *o = (c ? out1 : out0) + (size_t)u * N;
-            __syncthreads();  // (the exchange buffer's last readers)
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) lds[lds_phys(nat_e<T>(kk, tau))] = acc[c][kk];
-            __syncthreads();
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) {
-                const int e = nat_e<T>(kk, tau);
-                o[e] = lds[lds_phys((int)index[e])];
-            }
-        }
-    }
+hipError_t launch_rgsw_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s) {
+    return launch_gadget_fused<false>(r, a, batch, s);
 }
 hipError_t launch_auto_fused(const RingDev &r, const RgswFusedArgs &a, int batch, hipStream_t s) {
-    if (!rgsw_fused_supported(r.logN, a.nQ) || batch <= 0 || a.nP < 0 || a.nP > 1 || !no_tab({a.in0, a.in1, a.out0, a.out1}) ||
-        !a.in0.p || !a.in1.p || !a.out0.p || !a.out1.p || !a.ktab || !a.sel || a.nkeys <= 0 || a.pw2 <= 0)
-        return hipErrorInvalidValue;
-    RgswKArgs K{};
-    K.a = a; K.mc = r.mc; K.twf = r.tw_fwd; K.twi = r.tw_inv;
-    const size_t dyn = (size_t)a.nQ * r.N * 8;
-    const unsigned T = (unsigned)r.N / 16;
-    ProfScope ps(K_AUTO_FUSED, s, 4.0 * a.nQ * batch * (double)r.N * 8.0);  // (the keys differ by entry: not counted)
-    switch (r.logN) {
-        case 9: hipLaunchKernelGGL(auto_fused_kernel<9>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
-        case 10: hipLaunchKernelGGL(auto_fused_kernel<10>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
-        default: hipLaunchKernelGGL(auto_fused_kernel<11>, dim3((unsigned)batch), dim3(T), dyn, s, K); break;
-    }
-    return hipGetLastError();
+    return launch_gadget_fused<true>(r, a, batch, s);
 }
 
 // ------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The shapes, keys and rows of tests/test_gpu_blindrot_edges.py (host side: no device is needed to build them, and
 tests/test_blindrot_host.py checks without one that each has the property it is built for).  The shapes are those of
-tests/rgsw_edges.py -- auto_fused_kernel is a sibling of rgsw_fused_kernel and shares its domain -- narrowed to what
+tests/rgsw_edges.py -- both are instantiations of gadget_fused_kernel and share its domain -- narrowed to what
 include/hering_blindrot.h lets he_automorphism_ct_select take; the rows are the schedule edges of he_blind_rotate_core's
 batched route.
 

@@ -1,11 +1,11 @@
 """The one-launch automorphism (he_automorphism_ct_select) and the batched blind rotation (he_blind_rotate_core) at the edges of
 their domain, words, moduli and schedules (include/hering_blindrot.h), word for word against the oracle's Automorphism and
 tests/blindrot_ref.py.  tests/test_gpu_blindrot.py holds both with uniformly random words at a few shapes; this file plants the
-values and builds the shapes and rows at which auto_fused_kernel -- a hand copy of rgsw_fused_kernel with a tail of its own -- and
-the batched route's selection table can be wrong without those tests noticing (tests/blindrot_edges.py builds them,
-tests/test_blindrot_host.py checks without a device that each has the property it is built for).  Every case that claims the
-one-launch route asserts it from the launch profile before any word is compared: one launch of "automorphism_ct_select" and
-nothing else."""
+values and builds the shapes and rows at which the automorphism's instantiation of gadget_fused_kernel -- the RGSW product's
+kernel body with one decomposed component and a tail of its own -- and the batched route's selection table can be wrong
+without those tests noticing (tests/blindrot_edges.py builds them, tests/test_blindrot_host.py checks without a device that each
+has the property it is built for).  Every case that claims the one-launch route asserts it from the launch profile before any
+word is compared: one launch of "automorphism_ct_select" and nothing else."""
 import ctypes as C
 import gc
 import itertools
