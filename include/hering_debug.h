@@ -39,6 +39,29 @@ int he_probe_modmul(he_handle ctx, int iters, double *mults_per_s);
 /* the same for the exact double-precision product the limbs below 2^47 are computed with (error-free product + rounded quotient,
  * csrc/kernels.hip modmul_f64): the second ceiling of bench.py's `roofline.valu` */
 int he_probe_modmul_f64(he_handle ctx, int iters, double *mults_per_s);
+/* The scalar arithmetic primitives of the kernels, one by one (csrc/modarith.h and csrc/kernels.hip: the very __device__ functions
+ * the production kernels call), each applied to n tuples by one launch of a probe kernel -- one tuple per thread -- with q, qinv,
+ * the Barrett constants, NInv and 1/q taken from the ring's RESIDENT constant record of `limb` (so the table builders are under
+ * test too).  a, b, c, out0, out1: host arrays of n words; b, c and out1 may be null where the op does not use them (below).
+ * Doubles travel as their bit patterns.  HE_EINVAL: unknown op, bad limb, n = 0, n > 2^20, a missing array.
+ *   a, b -> out0:        MRED_LAZY, MRED, MRED_LAZY_W32, MRED_LAZY_ASM (x, y); MRED128_LAZY (hi, lo); BRED_LAZY, BRED (x, y);
+ *                        MODMUL_F64 (a, w as doubles -> double)
+ *   a -> out0:           BRED_ADD[_LAZY], MFORM[_LAZY], IMFORM[_LAZY], HALVE (words); REDUCE_F64, CANON_F64D (double -> double);
+ *                        CANON_F64, F64_TO_U52 (double -> word); U52_TO_F64 (word -> double)
+ *   a, b, c -> out0, out1: the butterflies on (a, b) with the twiddle c (BFLY_INV_SCALED[_ASM]: c = the twiddle already
+ *                        multiplied by N^-1, NInv from the record); the _ASM forms take their product through the hand-written
+ *                        sequence of the row kernels
+ *   a, b, c -> out0:     AUTO_DEST (e, g^-1 mod 2N, logN) */
+enum he_arith_op {
+    HE_ARITH_MRED_LAZY = 0, HE_ARITH_MRED, HE_ARITH_MRED_LAZY_W32, HE_ARITH_MRED_LAZY_ASM, HE_ARITH_MRED128_LAZY,
+    HE_ARITH_BRED_ADD_LAZY, HE_ARITH_BRED_ADD, HE_ARITH_BRED_LAZY, HE_ARITH_BRED, HE_ARITH_MFORM_LAZY, HE_ARITH_MFORM,
+    HE_ARITH_IMFORM_LAZY, HE_ARITH_IMFORM, HE_ARITH_BFLY_FWD, HE_ARITH_BFLY_FWD_ASM, HE_ARITH_BFLY_FWD_NC, HE_ARITH_BFLY_FWD_NC_ASM,
+    HE_ARITH_BFLY_INV, HE_ARITH_BFLY_INV_ASM, HE_ARITH_BFLY_INV_SCALED, HE_ARITH_BFLY_INV_SCALED_ASM, HE_ARITH_MODMUL_F64,
+    HE_ARITH_REDUCE_F64, HE_ARITH_CANON_F64D, HE_ARITH_CANON_F64, HE_ARITH_U52_TO_F64, HE_ARITH_F64_TO_U52, HE_ARITH_HALVE,
+    HE_ARITH_AUTO_DEST, HE_ARITH_COUNT
+};
+int he_debug_arith(he_handle ring, int limb, int op, size_t n, const uint64_t *a, const uint64_t *b, const uint64_t *c,
+                   uint64_t *out0, uint64_t *out1);
 /* submission queue of an evaluator (he_evaluator_set_coalescing) since its creation: out[0] = single-ciphertext calls served,
  * out[1] = batched launches made for them, out[2] = largest batch, out[3] = calls that ran one by one because their pipeline
  * has launches without entry tables */

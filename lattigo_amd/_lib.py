@@ -138,6 +138,7 @@ def _declare(L):
         "he_ckks_mul_relin": [H, i, H, H, H, H, H, H, H, H],
         "he_bgv_mul_relin": [H, i, C.c_uint64, H, H, H, H, H, H, H, H],
         "he_probe_modmul": [H, i, C.POINTER(C.c_double)], "he_probe_modmul_f64": [H, i, C.POINTER(C.c_double)],
+        "he_debug_arith": [H, i, i, sz, u64p, u64p, u64p, u64p, u64p],
         "he_prof_begin": [H], "he_prof_end": [H, i, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(i)],
         "he_prof_end_bytes": [H, i, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(i)],
         "he_alg_bytes": [H, i, C.POINTER(C.c_double)], "he_alg_valu": [H, i, C.POINTER(C.c_double)],
@@ -226,7 +227,7 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  "he_evaluator_coalescing_stats", "he_version", "he_device_info", "he_ring_constant", "he_ring_roots", "he_decomp_download_limb",
                  # a Ring owns itself (Ring._owner), so an unreachable one is released by the cycle collector, whenever that runs:
                  # no later call of the recording can name it
-                 "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds"}
+                 "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds", "he_debug_arith"}
 _trace = None
 
 

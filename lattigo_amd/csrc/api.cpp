@@ -5839,6 +5839,34 @@ int he_probe_modmul_f64(he_handle hctx, int iters, double *out) {
     return HE_OK;
 }
 
+// the scalar primitives one by one (hering_debug.h): tuples up, one launch of the probe kernel, results down
+int he_debug_arith(he_handle hring, int limb, int op, size_t n, const uint64_t *a, const uint64_t *b, const uint64_t *c,
+                   uint64_t *out0, uint64_t *out1) {
+    GET(r, Ring, hring, T_RING);
+    static_assert((int)HE_ARITH_COUNT == (int)ARITH_COUNT && (int)HE_ARITH_AUTO_DEST == (int)ARITH_AUTO_DEST, "he_arith_op numbering");
+    if (op < 0 || op >= HE_ARITH_COUNT) return fail(HE_EINVAL, "he_debug_arith: unknown op %d", op);
+    if (limb < 0 || limb >= r->nmod()) return fail(HE_EINVAL, "he_debug_arith: limb %d out of range", limb);
+    if (n == 0 || n > ((size_t)1 << 20)) return fail(HE_EINVAL, "he_debug_arith: n must be in 1 .. 2^20");
+    const bool three = (op >= HE_ARITH_BFLY_FWD && op <= HE_ARITH_BFLY_INV_SCALED_ASM) || op == HE_ARITH_AUTO_DEST;
+    const bool two = three || op <= HE_ARITH_MRED128_LAZY || op == HE_ARITH_BRED_LAZY || op == HE_ARITH_BRED || op == HE_ARITH_MODMUL_F64;
+    const bool pair = three && op != HE_ARITH_AUTO_DEST;
+    if (!a || !out0 || (two && !b) || (three && !c) || (pair && !out1)) return fail(HE_EINVAL, "he_debug_arith: op %d misses an array", op);
+    Scope sc(r->ctx.get());
+    const size_t w = (n + 1) & ~(size_t)1;
+    TRY(r->ctx->arena_reserve(5 * w));
+    uint64_t *d[5];
+    for (int k = 0; k < 5; k++) d[k] = r->ctx->arena_take(n);
+    hipStream_t st = r->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(d[0], a, n * 8, hipMemcpyHostToDevice, st));
+    if (two) HIP_TRY(hipMemcpyAsync(d[1], b, n * 8, hipMemcpyHostToDevice, st));
+    if (three) HIP_TRY(hipMemcpyAsync(d[2], c, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_arith_probe(r->d_mc + limb, op, n, d[0], two ? d[1] : nullptr, three ? d[2] : nullptr, d[3], pair ? d[4] : nullptr, st));
+    HIP_TRY(hipMemcpyAsync(out0, d[3], n * 8, hipMemcpyDeviceToHost, st));
+    if (pair) HIP_TRY(hipMemcpyAsync(out1, d[4], n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HE_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // RCCL over xGMI ("RCCL only for key distribution", and the partial accumulators of a key switch split
 // over the GPUs by digit).  librccl is loaded at run time and driven directly on the context's stream: no framework in the

@@ -459,4 +459,16 @@ int prof_end(hipStream_t s, int *counts, float *total_ms, double *total_bytes = 
 hipError_t launch_modmul_probe(uint64_t *buf, size_t n, int iters, uint64_t q, uint64_t qinv, hipStream_t s);
 hipError_t launch_modmul_f64_probe(double *buf, size_t n, int iters, double q, hipStream_t s);
 
+// arithmetic probe (he_debug_arith): the scalar primitives one by one; the numbering is HE_ARITH_* of include/hering_debug.h
+enum ArithOp {
+    ARITH_MRED_LAZY = 0, ARITH_MRED, ARITH_MRED_LAZY_W32, ARITH_MRED_LAZY_ASM, ARITH_MRED128_LAZY, ARITH_BRED_ADD_LAZY,
+    ARITH_BRED_ADD, ARITH_BRED_LAZY, ARITH_BRED, ARITH_MFORM_LAZY, ARITH_MFORM, ARITH_IMFORM_LAZY, ARITH_IMFORM, ARITH_BFLY_FWD,
+    ARITH_BFLY_FWD_ASM, ARITH_BFLY_FWD_NC, ARITH_BFLY_FWD_NC_ASM, ARITH_BFLY_INV, ARITH_BFLY_INV_ASM, ARITH_BFLY_INV_SCALED,
+    ARITH_BFLY_INV_SCALED_ASM, ARITH_MODMUL_F64, ARITH_REDUCE_F64, ARITH_CANON_F64D, ARITH_CANON_F64, ARITH_U52_TO_F64,
+    ARITH_F64_TO_U52, ARITH_HALVE, ARITH_AUTO_DEST, ARITH_COUNT
+};
+// a, b, c, o0, o1: device arrays of n words (b, c, o1 may be null where the op does not use them); mc: ONE resident record
+hipError_t launch_arith_probe(const ModConst *mc, int op, size_t n, const uint64_t *a, const uint64_t *b, const uint64_t *c,
+                              uint64_t *o0, uint64_t *o1, hipStream_t s);
+
 }  // namespace he

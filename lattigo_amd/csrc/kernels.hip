@@ -169,16 +169,20 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned lin, unsigned n) {
 // Row kernels: the same product as ONE hand-written sequence of 16 instructions.  hipcc turns every form of it
 // into 21-26: the 64-bit addend of v_mad_u64_u32 must be an (even-aligned) register pair, so each "high word, zero-extended" is a
 // v_mov_b32 into a fresh pair, and a carry costs a 64-bit compare + select.  By column instead: L = x0 w0, M = x0 w1 + x1 w0,
-// H = x1 w1 are three aligned 64-bit accumulators (for q < 2^61 and x < 4q the middle column cannot overflow: x1 w0 < 2^63,
-// x0 w1 < 2^61), the two reduction rounds add m q0 / m q1 to (L, M) then (M, H), and what crosses from one accumulator to the
+// H = x1 w1 are three aligned 64-bit accumulators (the middle one cannot overflow on what the kernels pass: for q < 2^61 and
+// x < 4q, x1 w0 < 2^63 and x0 w1, m q1 < 2^61; for q < 2^58 and x < 34q -- the correction-free butterflies -- x1 w0 < 2.2 2^62 and
+// x0 w1, m q1 < 2^58; it DOES overflow for x < 63q at the largest prime below 2^58, so 34q is the bound, not a round number:
+// tests/test_arith_host.py), the two reduction rounds add m q0 / m q1 to (L, M) then (M, H), and what crosses from one accumulator to the
 // next is a 32-bit word or a carry -- v_add_co / v_addc on the HIGH or LOW half of a pair.  Halves of a pair cannot be named
 // through asm operands, so the seven scratch registers are fixed (v116..v122, declared clobbered: inside the 128-register
 // budget of the four-wave row kernels), which is why only the row kernels take this form.
 //   8 v_mad_u64_u32 + 2 v_mul_lo_u32 + 6 v_add(c)_co_u32, result (T + m q) / 2^64 in [0, 2q) as mred_lazy_w32.
 // gfx940 / gfx950: a VALU instruction that reads VCC (a carry-in) wants two wait states after the VALU instruction that wrote it
 // -- hipcc pads its own carry chains with `s_nop 1` (llvm's VALUWriteSGPRVALURead rule), and nothing pads an asm string.  The
-// sequence ran bit-exact without the pads through every suite of this round, which is no evidence for a hazard that shows on
+// sequence ran bit-exact without the pads through every whole-transform suite, which is no evidence for a hazard that shows on
 // "some waves of some launches": it carries them.  An s_nop costs the wave two issue cycles, not the SIMD.
+// On its own the sequence is held against mred_lazy_w32 bit for bit by tests/test_gpu_arith.py (he_debug_arith), on sets in which
+// each of the four carries takes both values wherever the modulus lets it.
 #define HE_VCC_PAD "s_nop 1\n\t"
 __device__ __forceinline__ uint64_t mred_lazy_col_asm(uint64_t x, uint64_t w, uint64_t q, uint64_t qinv) {
     const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32), w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32);
@@ -253,7 +257,7 @@ __device__ __forceinline__ void bfly_inv_scaled_asm(uint64_t &a, uint64_t &b, ui
                                                     uint64_t twoq, uint64_t qinv) {
     const uint64_t U = a, V = b;
     uint64_t X = U + V;
-    X = X >= twoq ? X - twoq : X;  // the sequence wants its operand below 4q (U, V in [0, 2q): U + V is)
+    X = X >= twoq ? X - twoq : X;  // (U, V in [0, 2q): U + V is below 4q, inside the sequence's domain already; this keeps X in [0, 2q))
     a = cred(mred_lazy_col_asm(X, ninv, q, qinv), q);
     b = cred(mred_lazy_col_asm(U + twoq - V, wn, q, qinv), q);
 }
@@ -678,7 +682,8 @@ __global__ void __launch_bounds__((1 << LOGB) / 16 > 0 ? (1 << LOGB) / 16 : 1, 4
 // integers in double-precision registers.  gfx950 has no 64-bit integer multiplier (a Montgomery
 // product costs ~30 VALU ops) but runs v_fma_f64 at the rate of one v_mad_u64_u32, so
 //     h = a*w; l = fma(a,w,-h)            (error-free product, a*w = h + l exactly)
-//     c = rint(h * (1/q)); r = fma(-c,q,h) + l   (integer, r == a*w mod q, |r| < 2q)
+//     c = rint(h * (1/q)); r = fma(-c,q,h) + l   (integer, r == a*w mod q for any integer |a| < 2^53 and 0 <= w < q;
+//                                                 |r| < 2q for |a| <= 36q, what the callers below pass: tests/arith_ref.py)
 // is an exact modular product in 6 ops (measured 3.0x the integer MRedLazy rate, tools/f64_modmul_probe.hip).
 // All values stay integers of magnitude < 2^53:  forward butterflies X = U + r, Y = U - r grow by < 2q per
 // stage (34q + input < 2^53 for q < 2^47); the inverse reduces X once per radix-16 round.
@@ -4758,6 +4763,71 @@ hipError_t launch_modmul_f64_probe(double *buf, size_t n, int iters, double q, h
 hipError_t launch_modmul_probe(uint64_t *buf, size_t n, int iters, uint64_t q, uint64_t qinv, hipStream_t s) {
     const size_t threads = n / 4;
     hipLaunchKernelGGL(modmul_probe_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, buf, n, iters, q, qinv);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// arithmetic probe (he_debug_arith, include/hering_debug.h; tests/test_gpu_arith.py): one tuple (a, b, c) per thread through ONE
+// scalar primitive of this file or of modarith.h -- the very __device__ functions the kernels above call, no copies -- with the
+// constants of a resident ModConst record.  Doubles travel as their bit patterns.  `op` is block-uniform.
+// ------------------------------------------------------------------------------------
+struct ArithProbeArgs {
+    const ModConst *mc;
+    const uint64_t *a, *b, *c;
+    uint64_t *o0, *o1;
+    unsigned n;
+    int op;
+};
+__device__ __forceinline__ uint64_t f64_bits(double x) { return (uint64_t)__double_as_longlong(x); }
+__device__ __forceinline__ double bits_f64(uint64_t x) { return __longlong_as_double((long long)x); }
+__global__ void __launch_bounds__(256) arith_probe_kernel(ArithProbeArgs A) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n) return;
+    const ModConst mc = *A.mc;
+    const uint64_t q = mc.q, qinv = mc.qinv, twoq = q << 1;
+    const double qd = (double)mc.q, qi = mc.rq;
+    uint64_t a = A.a[i], b = A.b ? A.b[i] : 0, r1 = 0;
+    const uint64_t c = A.c ? A.c[i] : 0;
+    switch (A.op) {
+    case ARITH_MRED_LAZY: a = mred_lazy(a, b, q, qinv); break;
+    case ARITH_MRED: a = mred(a, b, q, qinv); break;
+    case ARITH_MRED_LAZY_W32: a = bfly_mul<false>(a, b, q, qinv); break;
+    case ARITH_MRED_LAZY_ASM: a = bfly_mul<true>(a, b, q, qinv); break;
+    case ARITH_MRED128_LAZY: a = mred128_lazy(a, b, q, qinv); break;
+    case ARITH_BRED_ADD_LAZY: a = bred_add_lazy(a, q, mc.brc0); break;
+    case ARITH_BRED_ADD: a = bred_add(a, q, mc.brc0); break;
+    case ARITH_BRED_LAZY: a = bred_lazy(a, b, q, mc.brc0, mc.brc1); break;
+    case ARITH_BRED: a = bred(a, b, q, mc.brc0, mc.brc1); break;
+    case ARITH_MFORM_LAZY: a = mform_lazy(a, q, mc.brc0, mc.brc1); break;
+    case ARITH_MFORM: a = mform(a, q, mc.brc0, mc.brc1); break;
+    case ARITH_IMFORM_LAZY: a = imform_lazy(a, q, qinv); break;
+    case ARITH_IMFORM: a = imform(a, q, qinv); break;
+    case ARITH_BFLY_FWD: bfly_fwd<false>(a, b, c, q, twoq, qinv); r1 = b; break;
+    case ARITH_BFLY_FWD_ASM: bfly_fwd<true>(a, b, c, q, twoq, qinv); r1 = b; break;
+    case ARITH_BFLY_FWD_NC: bfly_fwd_nc<false>(a, b, c, q, qinv); r1 = b; break;
+    case ARITH_BFLY_FWD_NC_ASM: bfly_fwd_nc<true>(a, b, c, q, qinv); r1 = b; break;
+    case ARITH_BFLY_INV: bfly_inv(a, b, c, q, twoq, qinv); r1 = b; break;
+    case ARITH_BFLY_INV_ASM: bfly_inv_asm(a, b, c, q, twoq, qinv); r1 = b; break;
+    case ARITH_BFLY_INV_SCALED: bfly_inv_scaled(a, b, c, mc.ninv, q, twoq, qinv); r1 = b; break;
+    case ARITH_BFLY_INV_SCALED_ASM: bfly_inv_scaled_asm(a, b, c, mc.ninv, q, twoq, qinv); r1 = b; break;
+    case ARITH_MODMUL_F64: a = f64_bits(modmul_f64(bits_f64(a), bits_f64(b), qd, qi)); break;
+    case ARITH_REDUCE_F64: a = f64_bits(reduce_f64(bits_f64(a), qd, qi)); break;
+    case ARITH_CANON_F64D: a = f64_bits(canon_f64d(bits_f64(a), qd, qi)); break;
+    case ARITH_CANON_F64: a = canon_f64(bits_f64(a), qd, qi); break;
+    case ARITH_U52_TO_F64: a = f64_bits(u52_to_f64(a)); break;
+    case ARITH_F64_TO_U52: a = f64_to_u52(bits_f64(a)); break;
+    case ARITH_HALVE: a = halve(a, q); break;
+    case ARITH_AUTO_DEST: a = auto_dest((unsigned)a, (unsigned)b, (int)c); break;
+    default: a = 0; break;
+    }
+    A.o0[i] = a;
+    if (A.o1) A.o1[i] = r1;
+}
+hipError_t launch_arith_probe(const ModConst *mc, int op, size_t n, const uint64_t *a, const uint64_t *b, const uint64_t *c,
+                              uint64_t *o0, uint64_t *o1, hipStream_t s) {
+    ProfScope ps(K_PROBE, s);
+    ArithProbeArgs A{mc, a, b, c, o0, o1, (unsigned)n, op};
+    hipLaunchKernelGGL(arith_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 

@@ -42,17 +42,20 @@ HE_HD uint64_t mred(uint64_t x, uint64_t y, uint64_t q, uint64_t qinv) {
     return r >= q ? r - q : r;
 }
 // The same residue by two 32-bit reduction rounds (word-serial Montgomery, "CIOS"): x*y*2^-64 mod q in [0, 2q) for
-// q < 2^61 (the largest modulus the library accepts, as the reference), x < 2^62 (any lazy operand of the kernels: x < 4q) and
+// q < 2^61 (the largest modulus the library accepts, as the reference), x < 3 2^62 (what the kernels hand it: x < 4q < 2^63 in the
+// Harvey butterflies, x < 34q < 2.2 2^62 in the correction-free ones at q < 2^58) and
 // x y < q 2^64 -- any y < q, and also a y at or above q while the product stays below q 2^64 (the RGSW kernel's key words after the
-// lazy helpers, hering_rgsw.h "Key words").  Why y may be any 64-bit word: with x1 = x >> 32 < 2^30 and q1 = q >> 32 < 2^29 every
-// partial sum below fits 64 bits -- u <= x1 y0 + 2^32 < 2^63, v <= m q1 + u + 2^32 < 2^64, a <= x0 y1 + 2^32 < 2^64,
-// b <= x1 y1 + 2^33 < 2^63, the result m q1 + b + 2^32 < 2^64 -- and the result is (x y + M q) / 2^64 with M < 2^64, below
+// lazy helpers, hering_rgsw.h "Key words").  Why y may be any 64-bit word: with x1 = x >> 32 < 3 2^30 and q1 = q >> 32 < 2^29 every
+// partial sum below fits 64 bits -- u <= x1 y0 + 2^32 < 3 2^62 + 2^32, v <= m q1 + u + 2^32 < 2^61 + 3 2^62 + 2^33 < 2^64,
+// a <= x0 y1 + 2^32 < 2^64, b <= x1 y1 + 2^33 < 3 2^62 + 2^33, the result m q1 + b + 2^32 < 2^64 -- and the result is
+// (x y + M q) / 2^64 with M < 2^64, below
 // x y / 2^64 + q < 2q.  gfx950 has no 64-bit multiplier; the full-width form
 // above costs 11 multiplies and ~15 carry / select instructions (a 64x64->128 product, a 64-bit low product and a 64x64 high
 // product), this one 8 v_mad_u64_u32 + 2 v_mul_lo_u32 + ~6 adds: the running sum never exceeds 96 bits and every partial
 // product is a 32x32+64 multiply-add.  m = -T q^-1 mod 2^64 is the same number either way (computed word by word here), so the
 // result is the same element of [0, 2q) as mred_lazy's EXCEPT when T q^-1 = 0 mod 2^64, where the reference's formula returns
 // r + q: use it where only the residue class matters (butterflies, canonical MRed), never for an API-visible *Lazy word.
+// (tests/arith_ref.py restates the schedule and asserts these bounds; tests/test_gpu_arith.py runs it at the top of the domain.)
 HE_HD uint64_t mred_lazy_w32(uint64_t x, uint64_t y, uint64_t q, uint64_t qinv) {
     const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32), y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32);
     const uint32_t q0 = (uint32_t)q, q1 = (uint32_t)(q >> 32), nq = (uint32_t)(0 - qinv);  // -q^-1 mod 2^32
