@@ -122,6 +122,8 @@ struct CoReq {
     std::function<int(const View *v, int B)> run;
     // optional: may this shape be addressed through entry tables (false: the batch is served one by one)?
     std::function<int(bool *ok)> tables_ok;
+    // a batch of this request is served one by one: its launches take no entry tables
+    void one_by_one() { tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; }; }
     // ---- queue state
     std::chrono::steady_clock::time_point arrived;
     uint64_t caller = 0;  // the submitting thread (several requests of one call share it)
@@ -4490,26 +4492,40 @@ static int ring_switch_launch(Ctx &c, const Ring *large, int kind, int level, in
     }
     return HE_OK;
 }
-// files one ring-degree map of in -> out (distinct handles of different degree) on the context's queue, served one by one
+// A request that addresses a ring alone -- a ring-level map, a step of the ring-packing evaluator: its key (the operation, the
+// ring whose tables the launches read or, without one, the context, and par[0..] in order), its launches, and its dispatch over B
+// entries.  None of these kernels takes entry tables: a batch is served one by one.
+using RingRun = std::function<int(const View *v, int B)>;
+static int ring_dispatch(const std::shared_ptr<Ctx> &ctx, CoReq &q, int op, const std::shared_ptr<Ring> &ring,
+                         std::initializer_list<int64_t> par, int B, RingRun run) {
+    q.op = op; q.obj = ring ? (const void *)ring.get() : (const void *)ctx.get();
+    std::copy(par.begin(), par.end(), q.par);
+    if (ring) q.keep.push_back(ring);
+    q.run = std::move(run);
+    q.one_by_one();
+    return co_dispatch(*ctx, B, q);
+}
+// files one ring-level map of in -> out (distinct handles of different degree, named as the entry names them) on the context's queue
+static int ring_map_file(const char *who, int op, const std::shared_ptr<Ring> &ring, std::initializer_list<int64_t> par, int level,
+                         const std::shared_ptr<Poly> &in, const char *in_name, const std::shared_ptr<Poly> &out, const char *out_name,
+                         RingRun run) {
+    CoReq q;
+    Operands o(q, who, in->ctx, in->N);
+    o.in(in, level + 1, in_name);
+    o.out(out, level + 1, out_name, Operands::kCall, out->N);
+    TRY(o.check());
+    return ring_dispatch(in->ctx, q, op, ring, par, in->batch, std::move(run));
+}
+// one ring-degree map of in -> out
 static int ring_switch_file(const char *who, const std::shared_ptr<Ring> &large, int kind, int level, int log_gap,
                             const std::shared_ptr<Poly> &in, const std::shared_ptr<Poly> &out) {
     const std::shared_ptr<Ctx> ctx = in->ctx;
     const int n_small = std::min(in->N, out->N);
-    CoReq q;
-    Operands o(q, who, ctx, in->N);
-    o.in(in, level + 1, "in");
-    o.out(out, level + 1, "out", Operands::kCall, out->N);
-    TRY(o.check());
-    std::vector<uint64_t> gapinv;
-    if (kind == RS_FOLD_NTT) gapinv = fold_constants(large->moduli, level, log_gap);
-    q.op = CO_RING_SWITCH; q.obj = large ? (const void *)large.get() : (const void *)ctx.get();
-    q.par[0] = kind; q.par[1] = level; q.par[2] = log_gap; q.par[3] = n_small;
-    if (large) q.keep.push_back(large);
-    q.run = [ctx, large, kind, level, log_gap, n_small, gapinv](const View *v, int B) -> int {
+    const std::vector<uint64_t> gapinv = kind == RS_FOLD_NTT ? fold_constants(large->moduli, level, log_gap) : std::vector<uint64_t>();
+    RingRun run = [ctx, large, kind, level, log_gap, n_small, gapinv](const View *v, int B) -> int {
         return ring_switch_launch(*ctx, large.get(), kind, level, log_gap, n_small, gapinv, v, B);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (the maps take no entry tables)
-    return co_dispatch(*ctx, in->batch, q);
+    return ring_map_file(who, CO_RING_SWITCH, large, {kind, level, log_gap, n_small}, level, in, "in", out, "out", run);
 }
 int he_map_small_to_large_ntt(he_handle hsmall, he_handle hlarge, int level) {
     GET(ps, Poly, hsmall, T_POLY);
@@ -4544,6 +4560,34 @@ int he_switch_ring_degree(int level, he_handle hin, he_handle hout) {
     TRY(ring_switch_shape(*in, *out, level, &lg, "he_switch_ring_degree"));
     if (lg == 0) return he_poly_copy(hout, hin, level);
     return ring_switch_file("he_switch_ring_degree", nullptr, in->N > out->N ? RS_STRIDE_DOWN : RS_STRIDE_UP, level, lg, in, out);
+}
+
+// One key switch at the evaluator's degree N composed with one ring map over both components (2B entries in one launch, the
+// map's io.zsplit = B): the degree-changing forms of ApplyEvaluationKey, the DomainSwitcher, and ring packing's Split and Merge.
+// Both components at degree N are staged in scratch as [2][B] entries, t0 then t1: this reserves the key switch's scratch (2 L in,
+// 2 L out, key) plus the staged pair, and hands the pair back.
+static int ks_staged_begin(Evaluator &ev, const Evk &k, int level, int B, View *t0, View *t1) {
+    BasisExtender &be = *ev.be;
+    const size_t sQ = (size_t)(level + 1) * be.Q->N, wQ = (size_t)B * sQ;
+    TRY(keyswitch_begin(ev, k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));
+    uint64_t *t = be.ctx->arena_take(2 * wQ);
+    *t0 = View{t, sQ}; *t1 = View{t + wQ, sQ};
+    return HE_OK;
+}
+using StagedMap = std::function<int(const View &t0, const View &t1)>;  // the map's accounting and launch, from or into the staged pair
+// GadgetProduct(operand) with `addend` in the ModDown epilogue of component 0, into (t0, t1); then map(t0, t1) to the caller's outputs
+static int key_switch_then_map(Evaluator &ev, const Evk &k, int level, int B, const View &addend, const View &operand, const StagedMap &map) {
+    View t0{nullptr, 0}, t1{nullptr, 0};
+    TRY(ks_staged_begin(ev, k, level, B, &t0, &t1));
+    TRY(key_switch(ev, KS_GADGET_PRODUCT, level, k, KsAlias{}, GpArgs{&operand, nullptr, t0, t1, B, &addend}));
+    return map(t0, t1);
+}
+// map(t0, t1) from the caller's inputs; then GadgetProduct(t1) with t0 as the addend, into (out0, out1)
+static int map_then_key_switch(Evaluator &ev, const Evk &k, int level, int B, const StagedMap &map, const View &out0, const View &out1) {
+    View t0{nullptr, 0}, t1{nullptr, 0};
+    TRY(ks_staged_begin(ev, k, level, B, &t0, &t1));
+    TRY(map(t0, t1));
+    return key_switch(ev, KS_GADGET_PRODUCT, level, k, KsAlias{}, GpArgs{&t1, nullptr, out0, out1, B, &t0});
 }
 
 // ApplyEvaluationKey (core/rlwe/evaluator_evaluationkey.go:36-106): out0 = in0 + GadgetProduct(in1)_0, out1 = GadgetProduct(in1)_1
@@ -4585,41 +4629,41 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
     const int n_small = std::min(Nin, Nout);
     const std::vector<uint64_t> gapinv = form == AEK_DOWN ? fold_constants(be.Q->moduli, level, lg) : std::vector<uint64_t>();
     ks_request(q, CO_APPLY_EVK, ev, k, level, form == AEK_SAME ? KS_GADGET_PRODUCT : KS_FORM_COUNT, alias); q.par[1] = form; q.par[2] = lg;
-    q.run = [ev, k, level, form, lg, n_small, cross, alias, gapinv](const View *v, int B) -> int {
+    if (form == AEK_SAME) q.run = [ev, k, level, cross, alias](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        // the key switch: 2 L in, 2 L out, key; its scratch and the staged addend / both components at degree N
-        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, form == AEK_SAME ? (cross ? wQ + 2 : 0) : 2 * wQ + 2));
+        const size_t sQ = (size_t)(level + 1) * be.Q->N, wQ = (size_t)B * sQ;
+        // the key switch: 2 L in, 2 L out, key; its scratch and the staged addend
+        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, cross ? wQ + 2 : 0));
         hipStream_t st = be.ctx->stream;
-        if (form == AEK_SAME) {
-            View a0 = v[0];
-            if (cross) {  // (served one by one: plain views)
-                a0 = View{be.ctx->arena_take(wQ), sQ};
-                HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, st));
+        View a0 = v[0];
+        if (cross) {  // (served one by one: plain views)
+            a0 = View{be.ctx->arena_take(wQ), sQ};
+            HIP_TRY(launch_ew(be.qp, ident_tab(level + 1), EW_COPY, v[0], v[0], a0, B, nullptr, nullptr, st));
+        }
+        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, v[2], v[3], B, &a0});
+    };
+    // the degree-changing forms: the fold of the key switch's result (down) or the replication of its input (up)
+    else q.run = [ev, k, level, form, lg, n_small, gapinv](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        hipStream_t st = be.ctx->stream;
+        const bool up = form == AEK_UP;
+        auto map = [&](const View &t0, const View &t1) -> int {
+            RingSwitchIO io;
+            io.zsplit = B;
+            if (up) { io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1; }
+            else { io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3]; }
+            be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, be.Q->N);
+            if (up) HIP_TRY(launch_ring_degree_replicate_ntt(ident_tab(level + 1), io, n_small, lg, 2 * B, st));
+            else {
+                Valu V(be.Q->logN - lg); V.mul(false, 2.0 * (level + 1)); V.into(*be.ctx, B);  // (integer products on every limb)
+                HIP_TRY(launch_ring_degree_fold_ntt(be.Q->dev, ident_tab(level + 1), gapinv.data(), io, n_small, lg, 2 * B, st));
             }
-            return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, v[2], v[3], B, &a0});
-        }
-        // both components at degree N in scratch, [2][B] entries: the key switch's result (down) or the replicated input (up)
-        uint64_t *t = be.ctx->arena_take(2 * wQ);
-        const View t0{t, sQ}, t1{t + wQ, sQ};
-        RingSwitchIO io;
-        io.zsplit = B;
-        if (form == AEK_DOWN) {
-            TRY(key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, t0, t1, B, &v[0]}));
-            io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3];
-            be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, N);
-            { Valu V(be.Q->logN - lg); V.mul(false, 2.0 * (level + 1)); V.into(*be.ctx, B); }  // (integer products on every limb)
-            HIP_TRY(launch_ring_degree_fold_ntt(be.Q->dev, ident_tab(level + 1), gapinv.data(), io, n_small, lg, 2 * B, st));
             return HE_OK;
-        }
-        io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1;
-        be.ctx->acct(2.0 * (level + 1) * (1.0 + 1.0 / (1 << lg)), 0, B, N);
-        HIP_TRY(launch_ring_degree_replicate_ntt(ident_tab(level + 1), io, n_small, lg, 2 * B, st));
-        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&t1, nullptr, v[2], v[3], B, &t0});
+        };
+        return up ? map_then_key_switch(*ev, *k, level, B, map, v[2], v[3]) : key_switch_then_map(*ev, *k, level, B, v[0], v[1], map);
     };
     // (the ring maps of the degree-changing forms take no entry tables)
-    if (form != AEK_SAME) q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    if (form != AEK_SAME) q.one_by_one();
     return co_dispatch(*be.ctx, o.B, q);
 }
 
@@ -4628,31 +4672,26 @@ int he_apply_evaluation_key(he_handle hev, int level, he_handle hin0, he_handle 
 // ---------------------------------------------------------------------------------------
 // kinds of CO_CI_BRIDGE / CO_CI_BRIDGE_CT (par[1])
 enum { BR_FOLD = 0, BR_UNFOLD };
-// one launch covers every entry of both components in its grid's z dimension
-constexpr int kBridgeMaxEntries = 65535;
+// one launch covers every entry of both components in its grid's z dimension (the DomainSwitcher and ring packing alike)
+constexpr int kMaxZEntries = 65535;
+static int z_entries(long entries, const char *who) {
+    if (entries > kMaxZEntries)
+        return fail(HE_EINVAL, "%s: %ld entries in one call, at most %d (split the batch)", who, entries, kMaxZEntries);
+    return HE_OK;
+}
 // a standard polynomial of degree 2n and a conjugate-invariant one of degree n >= 16 (context, batch and limbs: the operand checks)
 static int bridge_shape(const Poly &std_, const Poly &ci, int level, const char *who, const char *ratio_msg) {
     if (std_.N != 2 * ci.N) return fail(HE_EINVAL, "%s: %s (%d and %d)", who, ratio_msg, std_.N, ci.N);
     if (ci.N < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, ci.N);
     if (level < 0 || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range", who, level);
-    if (2L * std_.batch > kBridgeMaxEntries)
-        return fail(HE_EINVAL, "%s: %ld entries in one call, at most %d (split the batch)", who, 2L * std_.batch, kBridgeMaxEntries);
-    return HE_OK;
+    return z_entries(2L * std_.batch, who);
 }
-// files one ring-level map of in -> out on the context's queue, served one by one
+// one bridge map of in -> out
 static int bridge_file(const char *who, const std::shared_ptr<Ring> &moduli, int kind, int level, const std::shared_ptr<Poly> &in,
                        const std::shared_ptr<Poly> &out) {
     const std::shared_ptr<Ctx> ctx = in->ctx;
     const int n = std::min(in->N, out->N);
-    CoReq q;
-    Operands o(q, who, ctx, in->N);
-    o.in(in, level + 1, kind == BR_FOLD ? "polyStandard" : "polyConjugateInvariant");
-    o.out(out, level + 1, kind == BR_FOLD ? "polyConjugateInvariant" : "polyStandard", Operands::kCall, out->N);
-    TRY(o.check());
-    q.op = CO_CI_BRIDGE; q.obj = moduli ? (const void *)moduli.get() : (const void *)ctx.get();
-    q.par[0] = level; q.par[1] = kind; q.par[2] = n;
-    if (moduli) q.keep.push_back(moduli);
-    q.run = [ctx, moduli, kind, level, n](const View *v, int B) -> int {
+    RingRun run = [ctx, moduli, kind, level, n](const View *v, int B) -> int {
         RingSwitchIO io;
         io.in = v[0]; io.out = v[1];
         ctx->acct(1.5 * (level + 1), 0, B, 2 * n);  // (every input word read once, every output word written once)
@@ -4660,8 +4699,9 @@ static int bridge_file(const char *who, const std::shared_ptr<Ring> &moduli, int
         else HIP_TRY(launch_ci_bridge_unfold(ident_tab(level + 1), io, n, B, ctx->stream));
         return HE_OK;
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (the maps take no entry tables)
-    return co_dispatch(*ctx, in->batch, q);
+    const char *std_name = "polyStandard", *ci_name = "polyConjugateInvariant";
+    return ring_map_file(who, CO_CI_BRIDGE, moduli, {level, kind, n}, level, in, kind == BR_FOLD ? std_name : ci_name, out,
+                         kind == BR_FOLD ? ci_name : std_name, run);
 }
 int he_unfold_conjugate_invariant_to_standard(int level, he_handle hci, he_handle hstd) {
     static const char *who = "he_unfold_conjugate_invariant_to_standard";
@@ -4710,31 +4750,25 @@ static int bridge_ct(const char *who, int kind, he_handle hev, int level, he_han
     o.out(out0, level + 1, "out0", Operands::kCall, Nout); o.out(out1, level + 1, "out1", Operands::kCall, Nout);
     TRY(o.check());  // (handles of different degree never coincide: only out0 == out1 can, and is rejected)
     const int n = N / 2;
-    KsAlias alias;  // (the key switch runs on scratch on one side: none of its outputs is its operand)
-    ks_request(q, CO_CI_BRIDGE_CT, ev, k, level, KS_FORM_COUNT, alias); q.par[1] = kind;
-    q.run = [ev, k, level, kind, n, alias](const View *v, int B) -> int {
+    // (the key switch runs on scratch on one side: none of its outputs is its operand)
+    ks_request(q, CO_CI_BRIDGE_CT, ev, k, level, KS_FORM_COUNT, KsAlias{}); q.par[1] = kind;
+    q.run = [ev, k, level, kind, n](const View *v, int B) -> int {
         BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        // the key switch: 2 L in, 2 L out, key; its scratch and both components at degree N
-        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));
         hipStream_t st = be.ctx->stream;
-        uint64_t *t = be.ctx->arena_take(2 * wQ);
-        const View t0{t, sQ}, t1{t + wQ, sQ};
-        RingSwitchIO io;
-        io.zsplit = B;
-        be.ctx->acct(2.0 * 1.5 * (level + 1), 0, B, N);
-        if (kind == BR_FOLD) {
-            TRY(key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&v[1], nullptr, t0, t1, B, &v[0]}));
-            io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3];
-            HIP_TRY(launch_ci_bridge_fold(be.Q->dev, ident_tab(level + 1), io, n, 2 * B, st));
+        const bool unfold = kind == BR_UNFOLD;
+        auto map = [&](const View &t0, const View &t1) -> int {
+            RingSwitchIO io;
+            io.zsplit = B;
+            if (unfold) { io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1; }
+            else { io.in = t0; io.in2 = t1; io.out = v[2]; io.out2 = v[3]; }
+            be.ctx->acct(2.0 * 1.5 * (level + 1), 0, B, be.Q->N);
+            if (unfold) HIP_TRY(launch_ci_bridge_unfold(ident_tab(level + 1), io, n, 2 * B, st));
+            else HIP_TRY(launch_ci_bridge_fold(be.Q->dev, ident_tab(level + 1), io, n, 2 * B, st));
             return HE_OK;
-        }
-        io.in = v[0]; io.in2 = v[1]; io.out = t0; io.out2 = t1;
-        HIP_TRY(launch_ci_bridge_unfold(ident_tab(level + 1), io, n, 2 * B, st));
-        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, alias, GpArgs{&t1, nullptr, v[2], v[3], B, &t0});
+        };
+        return unfold ? map_then_key_switch(*ev, *k, level, B, map, v[2], v[3]) : key_switch_then_map(*ev, *k, level, B, v[0], v[1], map);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (the ring maps take no entry tables)
+    q.one_by_one();  // (the ring maps take no entry tables)
     return co_dispatch(*be.ctx, o.B, q);
 }
 int he_complex_to_real(he_handle ev, int level, he_handle in0, he_handle in1, he_handle evk, he_handle out0, he_handle out1) {
@@ -4753,13 +4787,6 @@ static int rp_ring(const Ring &r, int level, const char *who) {
     if (level < 0 || level >= r.nmod() || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, r.nmod() - 1);
     return HE_OK;
 }
-// one launch covers every entry of both components in its grid's z dimension
-constexpr int kRpMaxEntries = 65535;
-static int rp_entries(long entries, const char *who) {
-    if (entries > kRpMaxEntries)
-        return fail(HE_EINVAL, "%s: %ld entries in one call, at most %d (split the batch)", who, entries, kRpMaxEntries);
-    return HE_OK;
-}
 int he_ring_xpow2_ntt(he_handle hring, int level, int i, int div, he_handle hout) {
     static const char *who = "he_ring_xpow2_ntt";
     GET(r, Ring, hring, T_RING);
@@ -4767,33 +4794,26 @@ int he_ring_xpow2_ntt(he_handle hring, int level, int i, int div, he_handle hout
     TRY(rp_ring(*r, level, who));
     if (r->N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r->N);
     if (i < 0 || i >= r->logN) return fail(HE_EINVAL, "%s: i = %d out of range [0,%d]", who, i, r->logN - 1);
-    TRY(rp_entries(out->batch, who));
+    TRY(z_entries(out->batch, who));
     const std::shared_ptr<Ctx> ctx = r->ctx;
     CoReq q;
     Operands o(q, who, *r);
     o.out(out, level + 1, "out");
     TRY(o.check());
-    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_XPOW2; q.par[1] = level; q.par[2] = i; q.par[3] = div != 0;
-    q.keep.push_back(r);
-    q.run = [ctx, r, level, i, div](const View *v, int B) -> int {
+    RingRun run = [ctx, r, level, i, div](const View *v, int B) -> int {
         ctx->acct(level + 1, 0, B, r->N);
         HIP_TRY(launch_xpow2_fill(r->dev, v[0], i, div != 0, level + 1, B, ctx->stream));
         return HE_OK;
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*ctx, out->batch, q);
+    return ring_dispatch(ctx, q, CO_RING_PACK, r, {RP_XPOW2, level, i, div != 0}, out->batch, run);
 }
-// the launch of Split's / Merge's ring map over B entries per component (ncomp components); the caller holds the context
-static int rp_split_launch(Ctx &c, const Ring &large, const RingPackIO &io, bool odd, int level, int B, int ncomp) {
+// the launch of Split's (RP_SPLIT) or Merge's (RP_MERGE) ring map over B entries per component (ncomp components); the caller
+// holds the context.  (The two launches are spelled out: a device error's message names the call that failed.)
+static int rp_halves_launch(int kind, Ctx &c, const Ring &large, const RingPackIO &io, bool odd, int level, int B, int ncomp) {
     c.acct(ncomp * (level + 1) * (odd ? 2.0 : 1.5), odd ? 0.5 * (level + 1) : 0.0, B, large.N);
     if (odd) { Valu V(large.logN - 1); V.mul(false, (double)ncomp * (level + 1)); V.into(c, B); }
-    HIP_TRY(launch_ring_split(large.dev, io, level + 1, ncomp * B, c.stream));
-    return HE_OK;
-}
-static int rp_merge_launch(Ctx &c, const Ring &large, const RingPackIO &io, bool odd, int level, int B, int ncomp) {
-    c.acct(ncomp * (level + 1) * (odd ? 2.0 : 1.5), odd ? 0.5 * (level + 1) : 0.0, B, large.N);
-    if (odd) { Valu V(large.logN - 1); V.mul(false, (double)ncomp * (level + 1)); V.into(c, B); }
-    HIP_TRY(launch_ring_merge(large.dev, io, level + 1, ncomp * B, c.stream));
+    if (kind == RP_MERGE) HIP_TRY(launch_ring_merge(large.dev, io, level + 1, ncomp * B, c.stream));
+    else HIP_TRY(launch_ring_split(large.dev, io, level + 1, ncomp * B, c.stream));
     return HE_OK;
 }
 int he_ring_split_ntt(he_handle hring, int level, he_handle hin, he_handle heven, he_handle hodd) {
@@ -4803,24 +4823,20 @@ int he_ring_split_ntt(he_handle hring, int level, he_handle hin, he_handle heven
     TRY(rp_ring(*r, level, who));
     if (r->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, r->N / 2);
     const int B = in->batch;
-    TRY(rp_entries(B, who));
+    TRY(z_entries(B, who));
     CoReq q;
     Operands o(q, who, *r);
     o.in(in, level + 1, "in");
     o.out(heven, level + 1, "outEven", B, r->N / 2);
     o.out(o.opt(hodd), level + 1, "outOdd", B, r->N / 2);
     TRY(o.check());
-    const std::shared_ptr<Ctx> ctx = r->ctx;
     const bool has_odd = hodd != 0;
-    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_SPLIT; q.par[1] = level; q.par[2] = has_odd;
-    q.keep.push_back(r);
-    q.run = [ctx, r, level, has_odd](const View *v, int B) -> int {
+    RingRun run = [r, level, has_odd](const View *v, int B) -> int {
         RingPackIO io;
         io.x[0] = v[0]; io.o[0] = v[1]; io.p[0] = v[2];
-        return rp_split_launch(*ctx, *r, io, has_odd, level, B, 1);
+        return rp_halves_launch(RP_SPLIT, *r->ctx, *r, io, has_odd, level, B, 1);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*ctx, B, q);
+    return ring_dispatch(r->ctx, q, CO_RING_PACK, r, {RP_SPLIT, level, has_odd}, B, run);
 }
 int he_ring_merge_ntt(he_handle hring, int level, he_handle heven, he_handle hodd, he_handle hout) {
     static const char *who = "he_ring_merge_ntt";
@@ -4829,24 +4845,20 @@ int he_ring_merge_ntt(he_handle hring, int level, he_handle heven, he_handle hod
     TRY(rp_ring(*r, level, who));
     if (r->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, r->N / 2);
     const int B = out->batch;
-    TRY(rp_entries(B, who));
+    TRY(z_entries(B, who));
     CoReq q;
     Operands o(q, who, *r, B);
     o.in(heven, level + 1, "inEven", B, r->N / 2);
     o.in(o.opt(hodd), level + 1, "inOdd", B, r->N / 2);
     o.out(out, level + 1, "out");
     TRY(o.check());
-    const std::shared_ptr<Ctx> ctx = r->ctx;
     const bool has_odd = hodd != 0;
-    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_MERGE; q.par[1] = level; q.par[2] = has_odd;
-    q.keep.push_back(r);
-    q.run = [ctx, r, level, has_odd](const View *v, int B) -> int {
+    RingRun run = [r, level, has_odd](const View *v, int B) -> int {
         RingPackIO io;
         io.x[0] = v[0]; io.y[0] = v[1]; io.o[0] = v[2];
-        return rp_merge_launch(*ctx, *r, io, has_odd, level, B, 1);
+        return rp_halves_launch(RP_MERGE, *r->ctx, *r, io, has_odd, level, B, 1);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*ctx, B, q);
+    return ring_dispatch(r->ctx, q, CO_RING_PACK, r, {RP_MERGE, level, has_odd}, B, run);
 }
 // the shared checks of he_ringpack_split / he_ringpack_merge on the evaluator, the key and the odd halves' handles; B entries per operand
 static int rp_ct_checks(const Evaluator &ev, const Evk &k, int &level, int B, he_handle ho0, he_handle ho1, const char *who) {
@@ -4856,7 +4868,7 @@ static int rp_ct_checks(const Evaluator &ev, const Evk &k, int &level, int B, he
     TRY(check_key(ev, k, level, who));
     if (level != asked) return fail(HE_EINVAL, "%s: the key has %d Q limbs, level %d needs %d", who, k.nQk, asked, asked + 1);
     if (level >= be.LQ || level >= kMaxLimbs) return fail(HE_EINVAL, "%s: level %d out of range [0,%d]", who, level, be.LQ - 1);
-    TRY(rp_entries(2L * B, who));
+    TRY(z_entries(2L * B, who));
     if (be.Q->N / 2 < 16) return fail(HE_EINVAL, "%s: the small degree %d is below 16", who, be.Q->N / 2);
     if ((ho0 == 0) != (ho1 == 0)) return fail(HE_EINVAL, "%s: odd0 and odd1 are both given or both 0", who);
     return HE_OK;
@@ -4883,19 +4895,15 @@ int he_ringpack_split(he_handle hev, int level, he_handle hin0, he_handle hin1, 
     const bool has_odd = ho0 != 0;
     ks_request(q, CO_RINGPACK_CT, ev, k, level, KS_FORM_COUNT, KsAlias{}); q.par[1] = 0; q.par[2] = has_odd;
     q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));  // the key switch: 2 L in, 2 L out, key
-        uint64_t *t = be.ctx->arena_take(2 * wQ);
-        const View t0{t, sQ}, t1{t + wQ, sQ};
-        TRY(key_switch(*ev, KS_GADGET_PRODUCT, level, *k, KsAlias{}, GpArgs{&v[1], nullptr, t0, t1, B, &v[0]}));
-        RingPackIO io;
-        io.zsplit = B;
-        io.x[0] = t0; io.x[1] = t1; io.o[0] = v[2]; io.o[1] = v[3]; io.p[0] = v[4]; io.p[1] = v[5];
-        return rp_split_launch(*be.ctx, *be.Q, io, has_odd, level, B, 2);
+        auto map = [&](const View &t0, const View &t1) {
+            RingPackIO io;
+            io.zsplit = B;
+            io.x[0] = t0; io.x[1] = t1; io.o[0] = v[2]; io.o[1] = v[3]; io.p[0] = v[4]; io.p[1] = v[5];
+            return rp_halves_launch(RP_SPLIT, *ev->be->ctx, *ev->be->Q, io, has_odd, level, B, 2);
+        };
+        return key_switch_then_map(*ev, *k, level, B, v[0], v[1], map);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    q.one_by_one();
     return co_dispatch(*be.ctx, B, q);
 }
 int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he_handle ho0, he_handle ho1, he_handle hk, he_handle hout0,
@@ -4920,19 +4928,15 @@ int he_ringpack_merge(he_handle hev, int level, he_handle he0, he_handle he1, he
     const bool has_odd = ho0 != 0;
     ks_request(q, CO_RINGPACK_CT, ev, k, level, KS_FORM_COUNT, KsAlias{}); q.par[1] = 1; q.par[2] = has_odd;
     q.run = [ev, k, level, has_odd](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        const size_t sQ = (size_t)(level + 1) * N, wQ = (size_t)B * sQ;
-        TRY(keyswitch_begin(*ev, *k, level, 4.0 * (level + 1), true, B, 2 * wQ + 2));  // the key switch: 2 L in, 2 L out, key
-        uint64_t *t = be.ctx->arena_take(2 * wQ);
-        const View t0{t, sQ}, t1{t + wQ, sQ};
-        RingPackIO io;
-        io.zsplit = B;
-        io.x[0] = v[0]; io.x[1] = v[1]; io.y[0] = v[2]; io.y[1] = v[3]; io.o[0] = t0; io.o[1] = t1;
-        TRY(rp_merge_launch(*be.ctx, *be.Q, io, has_odd, level, B, 2));
-        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, KsAlias{}, GpArgs{&t1, nullptr, v[4], v[5], B, &t0});
+        auto map = [&](const View &t0, const View &t1) {
+            RingPackIO io;
+            io.zsplit = B;
+            io.x[0] = v[0]; io.x[1] = v[1]; io.y[0] = v[2]; io.y[1] = v[3]; io.o[0] = t0; io.o[1] = t1;
+            return rp_halves_launch(RP_MERGE, *ev->be->ctx, *ev->be->Q, io, has_odd, level, B, 2);
+        };
+        return map_then_key_switch(*ev, *k, level, B, map, v[4], v[5]);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    q.one_by_one();
     return co_dispatch(*be.ctx, B, q);
 }
 int he_ringpack_expand_step(he_handle hring, int level, int k, int sum_only, he_handle hin0, he_handle hin1, he_handle htmp0, he_handle htmp1,
@@ -4944,7 +4948,7 @@ int he_ringpack_expand_step(he_handle hring, int level, int k, int sum_only, he_
     if (r->N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r->N);
     if (k < 0 || k >= r->logN) return fail(HE_EINVAL, "%s: k = %d out of range [0,%d]", who, k, r->logN - 1);
     const int m = in0->batch;
-    TRY(rp_entries(2L * m, who));
+    TRY(z_entries(2L * m, who));
     const bool so = sum_only != 0;
     CoReq q;
     Operands o(q, who, *r);
@@ -4955,9 +4959,7 @@ int he_ringpack_expand_step(he_handle hring, int level, int k, int sum_only, he_
     if (so) { o.inplace(o0, i0); o.inplace(o1, i1); }
     TRY(o.check());
     const std::shared_ptr<Ctx> ctx = r->ctx;
-    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = RP_EXPAND; q.par[1] = level; q.par[2] = k; q.par[3] = so;
-    q.keep.push_back(r);
-    q.run = [ctx, r, level, k, so](const View *v, int B) -> int {
+    RingRun run = [ctx, r, level, k, so](const View *v, int B) -> int {
         RingPackIO io;
         io.zsplit = B;
         io.x[0] = v[0]; io.x[1] = v[1]; io.y[0] = v[2]; io.y[1] = v[3]; io.o[0] = v[4]; io.o[1] = v[5];
@@ -4966,9 +4968,8 @@ int he_ringpack_expand_step(he_handle hring, int level, int k, int sum_only, he_
         HIP_TRY(launch_expand_step(r->dev, io, k, B, so, level + 1, 2 * B, ctx->stream));
         return HE_OK;
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
     // (the second half of out lies m entries past the first: a request is its whole batch, whatever the queue's limit)
-    return co_dispatch(*ctx, m, q);
+    return ring_dispatch(ctx, q, CO_RING_PACK, r, {RP_EXPAND, level, k, so}, m, run);
 }
 // the operands of a pack step: count pairs of single ciphertexts and T; fills the request (operands 4 z + {0, 1, 2, 3} = a0, a1, b0,
 // b1 of pair z, then t0, t1) and counts the pairs by kind
@@ -4977,7 +4978,7 @@ static int rp_pack_operands(const char *who, const Ring &r, int level, int count
     TRY(rp_ring(r, level, who));
     if (r.N < 16) return fail(HE_EINVAL, "%s: ring degree %d is below 16", who, r.N);
     if (count < 1) return fail(HE_EINVAL, "%s: count = %d, at least one pair is needed", who, count);
-    TRY(rp_entries(2L * count, who));
+    TRY(z_entries(2L * count, who));
     if (!a0 || !a1 || !b0 || !b1) return fail(HE_EINVAL, "%s: null handle array", who);
     // No handle may occur twice among the operands, whatever the step does with each: this call's own identity rule, held with a
     // set (a step takes thousands of pairs; the pairwise rule of reject_aliasing is for the handful of operands of other calls),
@@ -5011,9 +5012,7 @@ static int rp_pack_step(const char *who, he_handle hring, int level, int k, bool
     // polynomial limbs moved per component and limb: pre -- both: a, b in, a, T out; one: 1 in, T out (+ b out); post -- 2 in, 1 out
     const double words = post ? 3.0 * count : 4.0 * kinds[0] + 2.0 * kinds[1] + 3.0 * kinds[2];
     const double muls = post ? 0.0 : (double)(kinds[0] + kinds[2]);
-    q.op = CO_RING_PACK; q.obj = r.get(); q.par[0] = post ? RP_PACK_POST : RP_PACK_PRE; q.par[1] = level; q.par[2] = k; q.par[3] = count;
-    q.keep.push_back(r);
-    q.run = [ctx, r, level, k, post, count, words, muls](const View *v, int) -> int {
+    RingRun run = [ctx, r, level, k, post, count, words, muls](const View *v, int) -> int {
         // the addresses of the pairs' polynomials, rows [a0 | a1 | b0 | b1]: a device table in scratch, filled from kernel arguments
         std::vector<size_t> tab(4 * (size_t)count);
         for (int z = 0; z < count; z++)
@@ -5026,8 +5025,7 @@ static int rp_pack_step(const char *who, he_handle hring, int level, int k, bool
                                  level + 1, ctx->stream));
         return HE_OK;
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
-    return co_dispatch(*ctx, 1, q);
+    return ring_dispatch(ctx, q, CO_RING_PACK, r, {post ? RP_PACK_POST : RP_PACK_PRE, level, k, count}, 1, run);
 }
 int he_ringpack_pack_pre(he_handle ring, int level, int k, int count, const he_handle *a0, const he_handle *a1, const he_handle *b0,
                          const he_handle *b1, he_handle t0, he_handle t1) {
@@ -5305,7 +5303,7 @@ int he_rgsw_external_product(he_handle hev, he_handle in0, he_handle in1, he_han
     q.op = CO_RGSW; q.obj = ev.get(); q.key = k0.get(); q.par[0] = (int64_t)(uintptr_t)k1.get(); q.par[1] = 0;
     q.keep.push_back(ev); q.keep.push_back(k0); q.keep.push_back(k1);
     q.run = [ev, k0, k1, s](const View *v, int B) -> int { return rgsw_product_run(*ev, *k0, *k1, s, v, B); };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };  // (queued calls are served one by one, as other base-2 shapes)
+    q.one_by_one();  // (queued calls are served one by one, as other base-2 shapes)
     return co_dispatch(*be.ctx, o.B, q);
 }
 int he_rgsw_keyset_create(he_handle hev, int n, const he_handle *rgsw0, const he_handle *rgsw1, he_handle *out) {
@@ -5352,7 +5350,7 @@ int he_rgsw_external_product_select(he_handle hev, he_handle in0, he_handle in1,
         };
         return select_run(who, *set, set->k0, s, selv, v, B, account, launch_rgsw_fused);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    q.one_by_one();
     return co_dispatch(*ev->be->ctx, (int)selv.size(), q);
 }
 
@@ -5595,7 +5593,7 @@ int he_automorphism_ct_select(he_handle hev, he_handle in0, he_handle in1, he_ha
         auto account = [&](int used) { auto_select_account(*ev, *set->keys[0], used, B); };
         return select_run(who, *set, set->keys, s, selv, v, B, account, launch_auto_fused);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    q.one_by_one();
     return co_dispatch(*ev->be->ctx, (int)selv.size(), q);
 }
 int he_blind_rotate_core(he_handle hev, const uint64_t *a, int batch, int n_lwe, he_handle acc0, he_handle acc1, he_handle hrset,
@@ -5658,7 +5656,7 @@ int he_blind_rotate_core(he_handle hev, const uint64_t *a, int batch, int n_lwe,
         return batched ? blindrot_batched(*ev, *rset, *gset, s, *plan, v[0], v[1], B)
                        : blindrot_per_entry(*ev, *rset, *gset, s, *plan, v[0], v[1], B);
     };
-    q.tables_ok = [](bool *ok) -> int { *ok = false; return HE_OK; };
+    q.one_by_one();
     return co_dispatch(*be.ctx, o.B, q);
 }
 

@@ -281,6 +281,34 @@ def test_launch_profile_is_the_key_switch_plus_one_map(ctx, batch):
         assert other not in got
         assert got == prof["same"], (name, got, prof["same"])
     assert "ci_bridge_fold" not in prof["same"] and "ci_bridge_unfold" not in prof["same"]
+    # the counters: those of the same-degree key switch plus the map's 1.5 L limbs per component, and no product of its own
+    acct = {}
+    for name, call in calls.items():
+        ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)
+        _lib.check(call())
+        acct[name] = (ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True))
+    print(acct)
+    (s0, s1), sv = acct["same"]
+    for name in ("c2r", "r2c"):
+        assert acct[name] == ((s0 + want_bytes, s1 + want_bytes), sv), (name, acct[name], acct["same"])
+
+
+@pytest.mark.parametrize("batch", [1, 3])
+def test_ring_level_maps_accounting(ctx, batch):
+    """the fold and the unfold alone charge 1.5 L limbs of 2 n words per entry and no arithmetic"""
+    n, level = 64, 2
+    q = MAP_Q
+    rng = rng_for(8550 + batch)
+    gstd, gci = la.Ring(ctx, 2 * n, q), la.Ring(ctx, n, q, conjugate_invariant=True)
+    pstd, pci = la.Poly(gstd, len(q), batch).upload(_rand(rng, q, 2 * n, batch)), la.Poly(gci, len(q), batch).upload(_rand(rng, q, n, batch))
+    L = _lib.load()
+    want = float(1.5 * (level + 1) * batch * 2 * n * 8)
+    for call in (lambda: L.he_fold_standard_to_conjugate_invariant(gstd.h, level, pstd.h, pci.h),
+                 lambda: L.he_unfold_conjugate_invariant_to_standard(level, pci.h, pstd.h)):
+        ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)
+        _lib.check(call())
+        assert (ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)) == ((want, want), [0.0] * 4)
+    ctx.sync()
 
 
 # ---- the submission queue, graphs and replay -------------------------------------------------------------------------------------

@@ -320,6 +320,112 @@ def test_pack_steps(ctx, logN):
     ctx.sync()
 
 
+# ---- 4b. launch profile and accounting ---------------------------------------------------------------------------------------------
+def _counted(ctx, call):
+    """(alg_bytes, alg_valu) of one call, and nothing else"""
+    ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)
+    _lib.check(call())
+    return ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)
+
+
+def _profiled(ctx, call):
+    """{kernel: (launches, algorithmic bytes)} of one call after a warm-up (plans and the arena are built on first use)"""
+    _lib.check(call())
+    ctx.sync()
+    ctx.prof_begin()
+    _lib.check(call())
+    ctx.sync()
+    return {k: (v[0], v[2]) for k, v in ctx.prof_end_bytes().items()}
+
+
+@pytest.mark.parametrize("batch", [1, 2])
+def test_split_and_merge_are_the_key_switch_plus_one_map(ctx, batch):
+    """he_ringpack_split / he_ringpack_merge, with and without the odd halves: the launches and counters of the same-degree
+    he_apply_evaluation_key at that shape and level (measured here) plus exactly one map launch over both components.  The map
+    moves, per limb, N + n words per entry (+ n with the odd halves, and their monomial's n words once per launch); it is charged
+    1.5 L limbs of N words per component (2 L with the odd halves, and 0.5 L once per call), and one product per odd word."""
+    logN = 12
+    N, n = 1 << logN, 1 << (logN - 1)
+    q, p = _moduli(14, [50] * 6, [55] * 3)
+    rng = rng_for(8800 + batch)
+    gQ, gP, gn = la.Ring(ctx, N, q), la.Ring(ctx, N, p), la.Ring(ctx, n, q)
+    gev = la.Evaluator(gQ, gP)
+    k = _random_key(rng, q, p, N)
+    gk = gev.NewEvaluationKey(k.q, k.p)
+    nq, level = len(q), len(q) - 2
+    L = level + 1
+    big = [_up(gQ, _stack(rng, q, N, batch)) for _ in range(4)]
+    half = [_up(gn, _stack(rng, q, n, batch)) for _ in range(4)]
+    lib = _lib.load()
+    calls = {
+        "same": lambda: lib.he_apply_evaluation_key(gev.h, level, big[0].h, big[1].h, gk.h, big[2].h, big[3].h),
+        ("split", True): lambda: lib.he_ringpack_split(gev.h, level, big[0].h, big[1].h, gk.h, half[0].h, half[1].h, half[2].h, half[3].h),
+        ("split", False): lambda: lib.he_ringpack_split(gev.h, level, big[0].h, big[1].h, gk.h, half[0].h, half[1].h, 0, 0),
+        ("merge", True): lambda: lib.he_ringpack_merge(gev.h, level, half[0].h, half[1].h, half[2].h, half[3].h, gk.h, big[2].h, big[3].h),
+        ("merge", False): lambda: lib.he_ringpack_merge(gev.h, level, half[0].h, half[1].h, 0, 0, gk.h, big[2].h, big[3].h),
+    }
+    prof = {name: _profiled(ctx, call) for name, call in calls.items()}
+    acct = {name: _counted(ctx, call) for name, call in calls.items()}
+    print(prof, acct)
+    assert "ring_split" not in prof["same"] and "ring_merge" not in prof["same"]
+    (s0, s1), sv = acct["same"]
+    for name in calls:
+        if name == "same":
+            continue
+        kind, odd = name
+        kernel, other = ("ring_split", "ring_merge") if kind == "split" else ("ring_merge", "ring_split")
+        got = dict(prof[name])
+        moved = float((N + (2 if odd else 1) * n) * L * 2 * batch * 8 + (n * L * 8 if odd else 0))
+        assert got.pop(kernel) == (1, moved), (name, prof[name])
+        assert other not in got
+        assert got == prof["same"], (name, got, prof["same"])
+        per_entry, shared = 2 * L * (2.0 if odd else 1.5), (0.5 * L if odd else 0.0)
+        want = ((s0 + (per_entry + shared) * batch * N * 8, s1 + (per_entry * batch + shared) * N * 8),
+                [sv[0] + (2 * L * n * batch if odd else 0), sv[1], sv[2], sv[3]])
+        assert acct[name] == want, (name, acct[name], want)
+
+
+def test_ring_level_entries_accounting(ctx):
+    """the counters of every entry that addresses a ring alone, in closed form (limbs of N words; products)"""
+    logN, level, batch = 5, 1, 3
+    N, n, L = 1 << logN, 1 << (logN - 1), level + 1
+    q, _ = _moduli(13, [60, 45, 55])
+    rng = rng_for(8810)
+    gN, gn = la.Ring(ctx, N, q), la.Ring(ctx, n, q)
+    lib = _lib.load()
+    limbs = lambda per_entry, shared, B: (float((per_entry + shared) * B * N * 8), float((per_entry * B + shared) * N * 8))
+    muls = lambda x: [float(x), 0.0, 0.0, 0.0]
+    pN, pe, po = _up(gN, _stack(rng, q, N, batch)), _up(gn, _stack(rng, q, n, batch)), _up(gn, _stack(rng, q, n, batch))
+    # the monomial table: L limbs written
+    assert _counted(ctx, lambda: lib.he_ring_xpow2_ntt(gN.h, level, 2, 1, pN.h)) == (limbs(L, 0, batch), muls(0))
+    # Split's and Merge's maps: 1.5 L, or 2 L with the odd half, whose monomial is read once per call and costs a product per word
+    for call in (lambda odd: lib.he_ring_split_ntt(gN.h, level, pN.h, pe.h, po.h if odd else 0),
+                 lambda odd: lib.he_ring_merge_ntt(gN.h, level, pe.h, po.h if odd else 0, pN.h)):
+        assert _counted(ctx, lambda: call(True)) == (limbs(2.0 * L, 0.5 * L, batch), muls(L * n * batch))
+        assert _counted(ctx, lambda: call(False)) == (limbs(1.5 * L, 0, batch), muls(0))
+    # an Expand step over m ciphertexts: in, tmp and the sums (and the differences, a product per word) of both components
+    m = batch
+    cin, tmp = [_up(gN, _stack(rng, q, N, m)) for _ in range(2)], [_up(gN, _stack(rng, q, N, m)) for _ in range(2)]
+    out2, out1 = [la.Poly(gN, len(q), 2 * m) for _ in range(2)], [la.Poly(gN, len(q), m) for _ in range(2)]
+    step = lambda so, o: lib.he_ringpack_expand_step(gN.h, level, 1, so, cin[0].h, cin[1].h, tmp[0].h, tmp[1].h, o[0].h, o[1].h)
+    assert _counted(ctx, lambda: step(0, out2)) == (limbs(2 * L * 4, 0, m), muls(2 * L * N * m))
+    assert _counted(ctx, lambda: step(1, out1)) == (limbs(2 * L * 3, 0, m), muls(0))
+    # the Pack steps over pairs of all three kinds: before the automorphism a full pair moves 4 polynomials per component, a pair
+    # of a alone 2 and of b alone 3, with a product per word wherever b is present; after it every pair moves 3
+    pairs = _pair_list(rng, q, N)
+    count = len(pairs)
+    both, a_only, b_only = (sum(1 for a, b in pairs if (a is not None, b is not None) == kind) for kind in ((True, True), (True, False), (False, True)))
+    A = [(_up_ct(gN, a) if a is not None else None) for a, _ in pairs]
+    B = [(_up_ct(gN, b) if b is not None else None) for _, b in pairs]
+    nil = [None, None]
+    arrs = [R._harr([(x or nil)[c] for x in side]) for side in (A, B) for c in range(2)]
+    T = [la.Poly(gN, len(q), count) for _ in range(2)]
+    assert _counted(ctx, lambda: lib.he_ringpack_pack_pre(gN.h, level, 1, count, *arrs, T[0].h, T[1].h)) == \
+        (limbs(2 * L * (4 * both + 2 * a_only + 3 * b_only), 0, 1), muls(2 * L * N * (both + b_only)))
+    assert _counted(ctx, lambda: lib.he_ringpack_pack_post(gN.h, level, count, *arrs, T[0].h, T[1].h)) == (limbs(2 * L * 3 * count, 0, 1), muls(0))
+    ctx.sync()
+
+
 # ---- 5. the mirrors ------------------------------------------------------------------------------------------------------------------
 def _random_galois_keys(rng, q, p, N, galels):
     return {int(g): _random_key(rng, q, p, N) for g in galels}

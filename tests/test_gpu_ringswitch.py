@@ -229,6 +229,96 @@ def test_apply_evaluation_key_coefficient_domain(ctx, ci):
     assert all(np.array_equal(o[k].get(), want[k]) for k in range(2))
 
 
+# ---- launch profile and accounting -----------------------------------------------------------------------------------------------
+def _counted(ctx, call):
+    """(alg_bytes, alg_valu) of one call, and nothing else"""
+    ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)
+    check(call())
+    return ctx.alg_bytes(reset=True), ctx.alg_valu(reset=True)
+
+
+def _profiled(ctx, call):
+    """{kernel: (launches, algorithmic bytes)} of one call after a warm-up (plans and the arena are built on first use)"""
+    check(call())
+    ctx.sync()
+    ctx.prof_begin()
+    check(call())
+    ctx.sync()
+    return {k: (v[0], v[2]) for k, v in ctx.prof_end_bytes().items()}
+
+
+MAP_KERNELS = ("ring_degree_fold_ntt", "ring_degree_replicate_ntt", "ring_degree_stride")
+
+
+@pytest.mark.parametrize("batch", [1, 2])
+@pytest.mark.parametrize("logn", [11, 10])
+def test_degree_changing_forms_are_the_key_switch_plus_one_map(ctx, logn, batch):
+    """large -> small at gap 2 and 4 and small -> large: the launches and counters of the same-degree he_apply_evaluation_key at
+    that shape and level (measured here) plus exactly one map launch over both components -- N + n words per limb and entry, moved
+    and charged; the fold one integer product per output word on top"""
+    logN = 12
+    N, n, gap = 1 << logN, 1 << logn, 1 << (logN - logn)
+    q, p = _moduli(logN + 2, 6, 3, bits_q=50, bits_p=55)
+    rng = rng_for(7500 + 10 * logn + batch)
+    gQ, gP, gs = la.Ring(ctx, N, q), la.Ring(ctx, N, p), la.Ring(ctx, n, q)
+    gev = la.Evaluator(gQ, gP)
+    kq, kp, _ = _random_key(rng, q, p, N, len(q) - 1)
+    gk = gev.NewEvaluationKey(kq, kp)
+    nq, level = len(q), len(q) - 2
+    L = level + 1
+    big = [la.Poly(gQ, nq, batch).upload(_rand(rng, q, N, batch)) for _ in range(4)]
+    small = [la.Poly(gs, nq, batch).upload(_rand(rng, q, n, batch)) for _ in range(4)]
+    lib = _lib.load()
+    calls = {
+        "same": lambda: lib.he_apply_evaluation_key(gev.h, level, big[0].h, big[1].h, gk.h, big[2].h, big[3].h),
+        "down": lambda: lib.he_apply_evaluation_key(gev.h, level, big[0].h, big[1].h, gk.h, small[2].h, small[3].h),
+        "up": lambda: lib.he_apply_evaluation_key(gev.h, level, small[0].h, small[1].h, gk.h, big[2].h, big[3].h),
+    }
+    prof = {name: _profiled(ctx, call) for name, call in calls.items()}
+    acct = {name: _counted(ctx, call) for name, call in calls.items()}
+    print(prof, acct)
+    assert not any(k in prof["same"] for k in MAP_KERNELS)
+    map_bytes = float((N + n) * L * 2 * batch * 8)
+    for name, kernel in (("down", "ring_degree_fold_ntt"), ("up", "ring_degree_replicate_ntt")):
+        got = dict(prof[name])
+        assert got.pop(kernel) == (1, map_bytes), (name, prof[name])
+        assert not any(k in got for k in MAP_KERNELS), (name, prof[name])
+        assert got == prof["same"], (name, got, prof["same"])
+        # charged: L (1 + 1/gap) limbs per component, no shared part
+        assert 2 * L * (1 + 1 / gap) * batch * N * 8 == map_bytes
+        (b0, b1), v = acct[name]
+        (s0, s1), sv = acct["same"]
+        assert (b0, b1) == (s0 + map_bytes, s1 + map_bytes), (name, acct[name], acct["same"])
+        muls = 2 * L * n * batch if name == "down" else 0
+        assert v == [sv[0] + muls, sv[1], sv[2], sv[3]], (name, v, sv)
+
+
+@pytest.mark.parametrize("ci", [False, True])
+def test_ring_level_maps_accounting(ctx, ci):
+    """the counters of he_switch_ring_degree_ntt (both directions) and he_switch_ring_degree (both directions) in closed form:
+    L (1 + 1/gap) limbs of N words for the fold and the replication, 2 L / gap for the strides, one product per word of the fold"""
+    logN, logn, batch, level = 8, 6, 3, 1
+    N, n, gap, L = 1 << logN, 1 << logn, 1 << (logN - logn), level + 1
+    q, _ = _moduli(logN + 2, 3)
+    rng = rng_for(7600 + ci)
+    gbig, gsmall = la.Ring(ctx, N, q, conjugate_invariant=ci), la.Ring(ctx, n, q, conjugate_invariant=ci)
+    pbig = la.Poly(gbig, len(q), batch).upload(np.stack([uniform_poly(rng, q, N) for _ in range(batch)]))
+    psmall = la.Poly(gsmall, len(q), batch).upload(np.stack([uniform_poly(rng, q, n) for _ in range(batch)]))
+    obig, osmall = la.Poly(gbig, len(q), batch), la.Poly(gsmall, len(q), batch)
+    lib = _lib.load()
+    ntt_bytes = float(L * (N + n) * batch * 8)
+    assert L * (1 + 1 / gap) * batch * N * 8 == ntt_bytes
+    stride_bytes = float(2 * L * n * batch * 8)
+    zero = [0.0, 0.0, 0.0, 0.0]
+    assert _counted(ctx, lambda: lib.he_switch_ring_degree_ntt(gbig.h, level, pbig.h, osmall.h)) == \
+        ((ntt_bytes, ntt_bytes), [float(L * n * batch), 0.0, 0.0, 0.0])
+    assert _counted(ctx, lambda: lib.he_switch_ring_degree_ntt(0, level, psmall.h, obig.h)) == ((ntt_bytes, ntt_bytes), zero)
+    assert _counted(ctx, lambda: lib.he_map_small_to_large_ntt(psmall.h, obig.h, level)) == ((ntt_bytes, ntt_bytes), zero)
+    assert _counted(ctx, lambda: lib.he_switch_ring_degree(level, pbig.h, osmall.h)) == ((stride_bytes, stride_bytes), zero)
+    assert _counted(ctx, lambda: lib.he_switch_ring_degree(level, psmall.h, obig.h)) == ((stride_bytes, stride_bytes), zero)
+    ctx.sync()
+
+
 # ---- functional: real keys --------------------------------------------------------------------------------------------------------
 def _functional_setup(ctx, logN, logn, seed):
     N, n, gap = 1 << logN, 1 << logn, 1 << (logN - logn)
