@@ -29,6 +29,7 @@
 #include "hering_rgsw.h"
 #include "hering_blindrot.h"
 #include "hering_bridge.h"
+#include "hering_bfv.h"
 
 namespace hering {
 
@@ -745,6 +746,51 @@ public:
     }
 };
 }  // namespace ckks
+
+// ---- BFV (schemes/bgv/evaluator.go with ScaleInvariant = true; hering_bfv.h), NTT domain ----------------------------------------
+namespace bgv {
+// bgv.Evaluator restricted to the scale-invariant ct x ct multiplication: newEvaluatorPrecomp (:38-70) over the device evaluator of
+// the parameters, Parameters.RingQMul() and the plaintext modulus; `rlk` as the reference's evaluation key set holds it (a default
+// EvaluationKey: none).  hering::Ciphertext carries no scale: the caller records MulScaleInvariant(params, a, b, level) (:983).
+class Evaluator {
+    detail::Ref r_;
+    hering::Evaluator eval_;  // (a copy shares the device evaluator)
+    Ring ringQMul_;
+    EvaluationKey rlk_;
+    std::vector<int> levelQMul_;
+
+    void tensor(const Ciphertext &op0, const Ciphertext &op1, bool relin, Ciphertext &opOut) const {
+        if (op0.Degree() != 1 || op1.Degree() != 1)
+            throw std::invalid_argument("cannot MulScaleInvariant: input elements total degree cannot be larger than 2");  // :831
+        if (relin && !rlk_.h()) throw std::invalid_argument("cannot relinearize: no relinearization key");
+        int level = op0.Level() < op1.Level() ? op0.Level() : op1.Level();
+        if (opOut.Level() < level) level = opOut.Level();  // :810
+        check(he_bfv_mul_relin(h(), level, op0.Value[0].h(), op0.Value[1].h(), op1.Value[0].h(), op1.Value[1].h(), relin ? rlk_.h() : 0,
+                               opOut.Value.at(0).h(), opOut.Value.at(1).h(), relin ? 0 : opOut.Value.at(2).h()));
+    }
+
+public:
+    Evaluator(const hering::Evaluator &eval, const Ring &ringQMul, uint64_t t, const EvaluationKey &rlk = EvaluationKey())
+        : eval_(eval), ringQMul_(ringQMul), rlk_(rlk) {
+        he_handle h = 0;
+        check(he_bfv_evaluator_create(eval.h(), ringQMul.h(), t, &h));
+        r_ = detail::own(h, he_bfv_evaluator_destroy);
+        for (int level = 0; level <= eval.RingQ().MaxLevel(); level++) {
+            int lm = 0;
+            check(he_bfv_level_qmul(h, level, &lm));
+            levelQMul_.push_back(lm);
+        }
+    }
+    he_handle h() const { return r_->h; }
+    const std::vector<int> &LevelQMul() const { return levelQMul_; }
+    // MulScaleInvariant (:799): the degree-2 result, opOut of three components
+    void MulScaleInvariant(const Ciphertext &op0, const Ciphertext &op1, Ciphertext &opOut) const { tensor(op0, op1, false, opOut); }
+    // MulRelinScaleInvariant (:838)
+    void MulRelinScaleInvariant(const Ciphertext &op0, const Ciphertext &op1, Ciphertext &opOut) const { tensor(op0, op1, true, opOut); }
+    // quantize (:1050) as a piece: c2Q1 on Q, c2Q2 on QMul at levelQMul, NTT domain; the result replaces c2Q1 as in the reference
+    void Quantize(int level, Poly &c2Q1, const Poly &c2Q2) const { check(he_bfv_quantize(h(), level, c2Q1.h(), c2Q2.h(), c2Q1.h())); }
+};
+}  // namespace bgv
 
 // ---- RGSW (core/rgsw; hering_rgsw.h), NTT domain -----------------------------------------------------------------------------
 namespace rgsw {

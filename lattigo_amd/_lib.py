@@ -11,7 +11,7 @@ _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HER
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
-         os.path.join(_INC, "hering_bridge.h")]
+         os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -116,6 +116,8 @@ def _declare(L):
         "he_apply_evaluation_key": [H, i, H, H, H, H, H],
         "he_unfold_conjugate_invariant_to_standard": [i, H, H], "he_fold_standard_to_conjugate_invariant": [H, i, H, H],
         "he_complex_to_real": [H, i, H, H, H, H, H], "he_real_to_complex": [H, i, H, H, H, H, H],
+        "he_bfv_evaluator_create": [H, H, C.c_uint64, HP], "he_bfv_evaluator_destroy": [H], "he_bfv_level_qmul": [H, i, C.POINTER(i)],
+        "he_bfv_mul_relin": [H, i, H, H, H, H, H, H, H, H], "he_bfv_quantize": [H, i, H, H, H],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
@@ -210,6 +212,8 @@ _TRACE_FNS_BLINDROT = {"he_automorphism_ct_select": (65, "hhhhAihh"), "he_blind_
 # the entries of include/hering_bridge.h, numbered on in a table of their own
 _TRACE_FNS_BRIDGE = {"he_unfold_conjugate_invariant_to_standard": (67, "ihh"), "he_fold_standard_to_conjugate_invariant": (68, "hihh"),
                      "he_complex_to_real": (69, "hihhhhh"), "he_real_to_complex": (70, "hihhhhh")}
+# the product entries of include/hering_bfv.h, numbered on in a table of their own
+_TRACE_FNS_BFV = {"he_bfv_mul_relin": (71, "hihhhhhhhh"), "he_bfv_quantize": (72, "hihhh")}
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments); a
 # tuple of indices: the product of those arguments
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
@@ -227,7 +231,8 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  "he_evaluator_coalescing_stats", "he_version", "he_device_info", "he_ring_constant", "he_ring_roots", "he_decomp_download_limb",
                  # a Ring owns itself (Ring._owner), so an unreachable one is released by the cycle collector, whenever that runs:
                  # no later call of the recording can name it
-                 "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds", "he_debug_arith"}
+                 "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds", "he_debug_arith",
+                 "he_bfv_level_qmul"}
 _trace = None
 
 
@@ -248,7 +253,7 @@ def trace_begin():
     import inspect  # noqa: F401
 
     def wrap(name, fn):
-        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name)
+        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name) or _TRACE_FNS_BFV.get(name)
 
         def call(*a):
             rc = fn(*a)

@@ -40,6 +40,7 @@
 #include "../../include/hering_debug.h"
 #include "../../include/hering_ringswitch.h"
 #include "../../include/hering_bridge.h"
+#include "../../include/hering_bfv.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -73,7 +74,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV };
 
 struct Obj {
     ObjType type;
@@ -102,7 +103,7 @@ enum CoOp {
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
     CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT,
-    CO_CI_BRIDGE, CO_CI_BRIDGE_CT
+    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -4446,6 +4447,228 @@ int he_ckks_mul_relin(he_handle ev, int level, he_handle a0, he_handle a1, he_ha
 }
 int he_bgv_mul_relin(he_handle ev, int level, uint64_t t, he_handle a0, he_handle a1, he_handle b0, he_handle b1, he_handle rlk, he_handle o0, he_handle o1, he_handle o2) {
     return mul_relin_common(ev, level, true, t, a0, a1, b0, b1, rlk, o0, o1, o2, "he_bgv_mul_relin");
+}
+
+// ---------------------------------------------------------------------------------------
+// BFV: the scale-invariant multiplication (include/hering_bfv.h; schemes/bgv/evaluator.go:38-70, :898-1071)
+// ---------------------------------------------------------------------------------------
+// evaluatorBase (evaluator.go:31-36) beside a device evaluator: the basis extender Q <-> QMul, levelQMul and t in Montgomery form
+struct BfvEvaluator : Obj {
+    std::shared_ptr<Evaluator> ev;
+    std::shared_ptr<BasisExtender> be;  // basisExtenderQ1toQ2: Q = the evaluator's RingQ, P = ringQMul
+    uint64_t t = 0;
+    std::vector<int> level_qmul;        // by level of Q
+    std::vector<uint64_t> t_mont;       // MForm(t mod q_i): the scalar of ringQ.MulScalar (ring/operations.go:201)
+    BfvEvaluator() : Obj(T_BFV) {}
+};
+// bits of prod(m[0..n)) (big.Int.BitLen of evaluator.go:46-47)
+static std::vector<int> product_bitlens(const std::vector<uint64_t> &m) {
+    std::vector<uint64_t> w{1};
+    std::vector<int> out;
+    for (uint64_t q : m) {
+        uint64_t carry = 0;
+        for (uint64_t &x : w) {
+            const u128 p = (u128)x * q + carry;
+            x = (uint64_t)p; carry = (uint64_t)(p >> 64);
+        }
+        if (carry) w.push_back(carry);
+        out.push_back((int)(w.size() - 1) * 64 + (64 - __builtin_clzll(w.back())));
+    }
+    return out;
+}
+int he_bfv_evaluator_create(he_handle hev, he_handle hqmul, uint64_t t, he_handle *out) {
+    static const char *who = "he_bfv_evaluator_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(M, Ring, hqmul, T_RING);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    const std::shared_ptr<Ring> Q = ev->be->Q;
+    if (t == 0) return fail(HE_EINVAL, "%s: the plaintext modulus is zero", who);
+    if (M->ctx != Q->ctx) return fail(HE_EINVAL, "%s: ringQMul belongs to another context", who);
+    if (M->N != Q->N) return fail(HE_EINVAL, "%s: ringQMul has degree %d, the evaluator's ring %d", who, M->N, Q->N);
+    if (Q->type != 0 || M->type != 0)
+        return fail(HE_EINVAL, "%s: conjugate-invariant rings are not served (%s); bgv parameters are standard", who, Q->type ? "the evaluator" : "ringQMul");
+    if (Q->nmod() > 32 || M->nmod() > 32)
+        return fail(HE_EINVAL, "%s: %d moduli in Q and %d in QMul, at most 32 each (ring/basis_extension.go:285)", who, Q->nmod(), M->nmod());
+    auto b = std::make_shared<BfvEvaluator>();
+    b->ev = ev; b->t = t;
+    for (int bits : product_bitlens(Q->moduli)) b->level_qmul.push_back((bits + Q->logN + 60) / 61 - 1);  // evaluator.go:47
+    if (b->level_qmul.back() > M->nmod() - 1)
+        return fail(HE_EINVAL, "%s: ringQMul has %d moduli, levelQMul at the top level is %d", who, M->nmod(), b->level_qmul.back());
+    he_handle hbe = 0;
+    TRY(basis_extender_build(Q, M, &hbe));
+    b->be = get<BasisExtender>(hbe, T_BE);
+    reg_drop(hbe);  // owned by this object
+    for (const SubRingHost &sr : Q->sub) b->t_mont.push_back(mform(t, sr.mc.q, sr.mc.brc0, sr.mc.brc1));
+    *out = reg(b);
+    return HE_OK;
+}
+int he_bfv_evaluator_destroy(he_handle h) { return unreg(h, T_BFV); }
+int he_bfv_level_qmul(he_handle h, int level, int *lm) {
+    GET(b, BfvEvaluator, h, T_BFV);
+    if (!lm) return fail(HE_EINVAL, "he_bfv_level_qmul: null output");
+    TRY(check_level(*b->be->Q, level, "he_bfv_level_qmul"));
+    *lm = b->level_qmul[level];
+    return HE_OK;
+}
+// the middle of quantize (:1057-1067) over `nb` coefficient-domain entries: cQ (level + 1 limbs) and cM (lm + 1 limbs) -> out
+static int bfv_quantize_launch(const BfvEvaluator &b, int level, View cQ, View cM, View outQ, int nb) {
+    const BasisExtender &be = *b.be;
+    const int lm = b.level_qmul[level];
+    const std::vector<uint64_t> Qb(be.Q->moduli.begin(), be.Q->moduli.begin() + level + 1), Mb(be.P->moduli.begin(), be.P->moduli.begin() + lm + 1);
+    BfvQuantizeArgs a{};
+    a.nq = level + 1; a.nm = lm + 1; a.mod_m0 = be.LQ;
+    for (int i = 0; i <= level; i++) {
+        a.q_half_q[i] = half_product_mod(Qb, Qb[i]);
+        a.m_half_q[i] = half_product_mod(Mb, Qb[i]);
+        a.t_mont[i] = b.t_mont[i];
+    }
+    for (int j = 0; j <= lm; j++) {
+        a.q_half_m[j] = half_product_mod(Qb, Mb[j]);
+        a.m_half_m[j] = half_product_mod(Mb, Mb[j]);
+        a.div_s[j] = Mb[j] - be.md_qtop[level][j];
+    }
+    HIP_TRY(launch_bfv_quantize(be.qp, be.qtop[level].on(be.pool), be.ptoq[lm].on(be.pool), a, cQ, cM, outQ, nb, be.ctx->stream));
+    return HE_OK;
+}
+// bytes and arithmetic of the quantize of one polynomial between its transforms: 2 (L + lm) limbs, two reconstructions
+static void bfv_quantize_acct(const BfvEvaluator &b, int level, int lm, Valu &V) {
+    const BasisExtender &be = *b.be;
+    std::vector<int> dq, dm;
+    for (int i = 0; i <= level; i++) { dq.push_back(i); V.mul(false, 1.0); }
+    for (int j = 0; j <= lm; j++) { dm.push_back(be.LQ + j); V.mul(false, 1.0); }
+    valu_modup(V, be.small, 0, level + 1, dm);
+    valu_modup(V, be.small, be.LQ, lm + 1, dq);
+}
+int he_bfv_quantize(he_handle hb, int level, he_handle hcq, he_handle hcm, he_handle hout) {
+    static const char *who = "he_bfv_quantize";
+    GET(b, BfvEvaluator, hb, T_BFV);
+    BasisExtender &be = *b->be;
+    TRY(check_level(*be.Q, level, who));
+    const int lm = b->level_qmul[level];
+    CoReq q;
+    Operands o(q, who, be);
+    const int iq = o.in(hcq, level + 1, "cQ");
+    o.inP(hcm, lm + 1, "cM");
+    o.inplace(o.out(hout, level + 1, "outQ"), iq);
+    TRY(o.check());
+    if (o.B > 65535) return fail(HE_EINVAL, "%s: %d entries in one call, at most 65535 (split the batch)", who, o.B);
+    q.op = CO_BFV_QUANTIZE; q.obj = b.get(); q.par[0] = level;
+    q.keep.push_back(b);
+    q.run = [b, level, lm](const View *v, int B) -> int {
+        BasisExtender &be = *b->be;
+        const int N = be.Q->N;
+        const size_t sQ = (size_t)(level + 1) * N, sM = (size_t)(lm + 1) * N;
+        be.ctx->acct(2.0 * (level + 1) + lm + 1, 0, B, N);
+        {
+            Valu V(be.Q->logN);
+            for (int i = 0; i <= level; i++) V.ntt(cls_f64(be.small, i), 2.0);
+            for (int j = 0; j <= lm; j++) V.ntt(cls_f64(be.small, be.LQ + j));
+            bfv_quantize_acct(*b, level, lm, V);
+            V.into(*be.ctx, B);
+        }
+        TRY(be.ctx->arena_reserve(B * (sQ + sM) + 4));
+        const View tQ{be.ctx->arena_take(B * sQ), sQ}, tM{be.ctx->arena_take(B * sM), sM};
+        HIP_TRY(be_ntt(be, ident_tab(level + 1), v[0], tQ, B, true, NTT_REDUCE_INPUT));
+        HIP_TRY(be_ntt(be, ident_tab(lm + 1, 0, 0, be.LQ), v[1], tM, B, true, NTT_REDUCE_INPUT));
+        TRY(bfv_quantize_launch(*b, level, tQ, tM, tQ, B));
+        HIP_TRY(be_ntt(be, ident_tab(level + 1), tQ, v[2], B, false, NTT_REDUCE_INPUT));
+        return HE_OK;
+    };
+    q.one_by_one();  // (the quantize launch takes no entry tables)
+    return co_dispatch(*be.ctx, o.B, q);
+}
+// tensorScaleInvariant (:898-972).  Everything between the inputs and the outputs lives in scratch: the inverse transforms of the
+// nin = 4 (squaring: 2) input components [nin][B], their extension to QMul [nin][B], the products on Q and on QMul [3][B].  The
+// inputs are last read by the Q tensor, the first output word is written by the final transform (or the key switch's epilogue):
+// any output may be any input.
+int he_bfv_mul_relin(he_handle hb, int level, he_handle ha0, he_handle ha1, he_handle hb0, he_handle hb1, he_handle hk, he_handle hout0,
+                     he_handle hout1, he_handle hout2) {
+    static const char *who = "he_bfv_mul_relin";
+    GET(b, BfvEvaluator, hb, T_BFV);
+    const std::shared_ptr<Evaluator> ev = b->ev;
+    BasisExtender &be = *b->be;
+    TRY(check_level(*be.Q, level, who));
+    std::shared_ptr<Evk> k;
+    if (hk) {
+        k = get<Evk>(hk, T_EVK);
+        if (!k) return fail(HE_EHANDLE, "%s: bad relinearization key handle", who);
+        int lv = level;
+        TRY(check_key(*ev, *k, lv, who));
+        if (lv != level) return fail(HE_EINVAL, "%s: relinearization key level %d below ciphertext level %d", who, k->nQk - 1, level);
+    }
+    const bool square = ha0 == hb0 && ha1 == hb1;
+    const int lm = b->level_qmul[level];
+    CoReq q;
+    Operands o(q, who, be);
+    o.in(ha0, level + 1, "a0"); o.in(ha1, level + 1, "a1"); o.in(hb0, level + 1, "b0"); o.in(hb1, level + 1, "b1");
+    o.out(hout0, level + 1, "out0"); o.out(hout1, level + 1, "out1");
+    o.out(k ? nullptr : o.poly(hout2), level + 1, "out2 (required when no relinearization key is given)");
+    o.all_inplace = true;
+    TRY(o.check());
+    if (4L * o.B > 65535) return fail(HE_EINVAL, "%s: %d entries in one call, at most %d (split the batch)", who, o.B, 65535 / 4);
+    ks_request(q, CO_BFV_MUL, ev, k, level, KS_FORM_COUNT, KsAlias{});
+    q.obj = b.get(); q.par[1] = square;
+    q.keep.push_back(b);
+    q.run = [b, ev, k, level, lm, square](const View *v, int B) -> int {
+        BasisExtender &be = *b->be;
+        Ctx &ctx = *be.ctx;
+        const int N = be.Q->N, nin = square ? 2 : 4;
+        const size_t sQ = (size_t)(level + 1) * N, sM = (size_t)(lm + 1) * N, nB = (size_t)nin * B;
+        const LimbTab tq = ident_tab(level + 1), tm = ident_tab(lm + 1, 0, 0, be.LQ);
+        {
+            Valu V(be.Q->logN);
+            std::vector<int> dm;
+            for (int j = 0; j <= lm; j++) dm.push_back(be.LQ + j);
+            Valu I(be.Q->logN), P(be.Q->logN);  // per input component / per product
+            for (int i = 0; i <= level; i++) I.ntt(cls_f64(be.small, i));
+            valu_modup(I, be.small, 0, level + 1, dm);
+            for (int j = 0; j <= lm; j++) I.ntt(cls_f64(be.small, be.LQ + j));
+            for (int i = 0; i <= level; i++) { P.ntt(cls_f64(be.small, i), 2.0); P.mul(cls_f64(be.small, i), 2.0); }
+            for (int j = 0; j <= lm; j++) { P.ntt(cls_f64(be.small, be.LQ + j)); P.mul(cls_f64(be.small, be.LQ + j), 2.0); }
+            bfv_quantize_acct(*b, level, lm, P);
+            for (int c = 0; c < 4; c++) V.v[c] = nin * I.v[c] + 3.0 * P.v[c];
+            V.into(ctx, B);
+        }
+        const size_t extra = nB * (sQ + sM) + 3 * (size_t)B * (sQ + sM) + 3 * (size_t)B + 16;
+        if (k) TRY(keyswitch_begin(*ev, *k, level, 6.0 * (level + 1), true, B, extra));  // 4 L in, 2 L out, the key
+        else { ctx.acct(7.0 * (level + 1), 0, B, N); TRY(ctx.arena_reserve(extra)); }
+        const View inQ{ctx.arena_take(nB * sQ), sQ}, inM{ctx.arena_take(nB * sM), sM};
+        const View cQ{ctx.arena_take(3 * B * sQ), sQ}, cM{ctx.arena_take(3 * B * sM), sM};
+        auto part = [B](const View &w, int c) { return View{w.p + (size_t)c * B * w.bstride, w.bstride}; };
+        // modUpAndNTT (:991-1001): INTT of every component, ONE extension Q -> QMul and ONE lazy transform over all of them
+        for (int c = 0; c < nin; c++) HIP_TRY(be_ntt(be, tq, v[c], part(inQ, c), B, true, NTT_REDUCE_INPUT));
+        TRY(modup_between(be, true, level, lm, inQ, inM, 0, (int)nB));
+        HIP_TRY(be_ntt(be, tm, inM, inM, (int)nB, false, NTT_LAZY_OUT | NTT_REDUCE_INPUT));
+        // tensorLowDeg (:1003-1048) on Q and on QMul: MForm of the first operand, the three products; c1 is the canonical
+        // representative of the reference's lazy sum (squaring: of its doubled product), which the inverse transform reduces anyway
+        std::vector<uint64_t> r2(std::max(level, lm) + 1);
+        for (int i = 0; i <= level; i++) r2[i] = be.Q->sub[i].mc.r2;
+        HIP_TRY(launch_tensor(be.qp, tq, r2.data(), v[0], v[1], v[2], v[3], part(cQ, 0), part(cQ, 1), part(cQ, 2), B, ctx.stream));
+        for (int j = 0; j <= lm; j++) r2[j] = be.P->sub[j].mc.r2;
+        HIP_TRY(launch_tensor(be.qp, tm, r2.data(), part(inM, 0), part(inM, 1), part(inM, square ? 0 : 2), part(inM, square ? 1 : 3),
+                              part(cM, 0), part(cM, 1), part(cM, 2), B, ctx.stream));
+        // quantize (:1050-1071) of the three products at once
+        HIP_TRY(be_ntt(be, tq, cQ, cQ, 3 * B, true, NTT_REDUCE_INPUT));
+        HIP_TRY(be_ntt(be, tm, cM, cM, 3 * B, true, NTT_REDUCE_INPUT));
+        TRY(bfv_quantize_launch(*b, level, cQ, cM, cQ, 3 * B));
+        if (k) {
+            // :966-969: the key switch of c2 with c0 / c1 as the ModDown epilogue's addends (the two ringQ.Add)
+            HIP_TRY(be_ntt(be, tq, cQ, cQ, 3 * B, false, NTT_REDUCE_INPUT));
+            const View c0 = part(cQ, 0), c1 = part(cQ, 1), c2 = part(cQ, 2);
+            GpArgs g{&c2, nullptr, v[4], v[5], B, &c0, &c1, true};
+            return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, KsAlias{}, g);
+        }
+        // three outputs of the caller's: one transform whose stores go through an entry table (entry c B + e -> out_c, entry e)
+        std::vector<size_t> off(3 * (size_t)B);
+        for (int c = 0; c < 3; c++)
+            for (int e = 0; e < B; e++) off[(size_t)c * B + e] = (size_t)(v[4 + c].p - v[4].p) + (size_t)e * v[4 + c].bstride;
+        size_t *tab = reinterpret_cast<size_t *>(ctx.arena_take(off.size()));
+        HIP_TRY(launch_tab_fill(tab, off.data(), (int)off.size(), ctx.stream));
+        HIP_TRY(be_ntt(be, tq, cQ, View{v[4].p, 0, tab}, 3 * B, false, NTT_REDUCE_INPUT));
+        return HE_OK;
+    };
+    q.one_by_one();  // (scratch-to-scratch launches: no entry tables)
+    return co_dispatch(*be.ctx, o.B, q);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -389,6 +389,26 @@ bool ntt_mac_giant_supported(int logN);
 hipError_t launch_key_to_f64(const RingDev &r, const uint64_t *key, double *keyd, int nblocks, const uint8_t *limb_mod_host,
                              int nlimbs, hipStream_t s);
 
+// ---- BFV quantize (schemes/bgv/evaluator.go:1050-1071, coefficient domain) -----------------------------
+// The middle of the reference's quantize(level, levelQMul, c2Q1, c2Q2) per coefficient, with no HBM round trip between its four
+// steps: ModDownQPtoP (the extension Q -> QMul of cQ as ModUpQtoP does it, then z_j = MRed(e_j + 2 m_j - cM_j, m_j - c_j)),
+// ModUpPtoQ of z (centred by QMul / 2) and MulScalar by t.  `r`: the combined table of a basis extender Q | QMul (Q moduli first);
+// up: GenModUpConstants(Q[:nq], QMul), down: GenModUpConstants(QMul[:nm], Q), both resident.  cQ: nq limbs, cM: nm limbs,
+// canonical coefficient-domain words; out: nq limbs, canonical; out may be cQ (a thread reads all its words before it writes).
+// No entry tables.
+struct BfvQuantizeArgs {
+    int nq, nm;                  // limbs of Q (level + 1) and of QMul (levelQMul + 1), each 1..32
+    int mod_m0;                  // modulus record of QMul limb 0 in r.mc (the Q limbs are records 0..nq-1)
+    uint64_t q_half_q[32];       // (Q / 2) mod q_i: added before the first reconstruction
+    uint64_t q_half_m[32];       // (Q / 2) mod m_j: subtracted after it
+    uint64_t div_s[32];          // m_j - modDownConstantsQtoP[level][j]
+    uint64_t m_half_m[32];       // (QMul / 2) mod m_j
+    uint64_t m_half_q[32];       // (QMul / 2) mod q_i
+    uint64_t t_mont[32];         // MForm(t mod q_i)
+};
+hipError_t launch_bfv_quantize(const RingDev &r, const ModUpDev &up, const ModUpDev &down, const BfvQuantizeArgs &a, View cQ, View cM,
+                               View out, int batch, hipStream_t s);
+
 // ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
 // One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
 // ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
@@ -448,7 +468,7 @@ enum KernelId {
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
     K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_CI_BRIDGE_FOLD,
-    K_CI_BRIDGE_UNFOLD, K_COUNT
+    K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -74,7 +74,7 @@ const char *kernel_name(int id) {
                                          "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
                                          "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
                                          "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select",
-                                         "ci_bridge_fold", "ci_bridge_unfold"};
+                                         "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -3350,6 +3350,102 @@ hipError_t launch_modup(const RingDev &r, const ModUpDev &c, const ModUpArgs &a,
         case 8: hipLaunchKernelGGL((modup_kernel<8>), grid, block, 0, s, A); break;
         default: hipLaunchKernelGGL((modup_kernel<0>), grid, block, 0, s, A); break;
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// BFV quantize (schemes/bgv/evaluator.go:1050-1071 between its transforms): ModDownQPtoP, ModUpPtoQ and MulScalar of one
+// coefficient in one thread.  Both reconstructions are modup_kernel's, helper by helper (the y_i, the sequential float64 sum in
+// limb order, the 128-bit multSum with its lazy Montgomery reduction, the table word and the centring CRed); what lies between
+// them never leaves the registers.  The first extension runs destination by destination (QMul limb j): its word e_j is divided
+// (z_j), lifted into the second reconstruction's y'_j at once, and y'_j is spread over the Q limbs' 128-bit sums -- so only
+// the y_i and the CAP running sums are indexed, both by unrolled loops.  CAP: the instantiation's bound on the Q limbs.
+// ------------------------------------------------------------------------------------
+struct BfvQuantizeKArgs {
+    const uint64_t *cQ, *cM;
+    uint64_t *out;
+    size_t cQ_bs, cM_bs, out_bs;
+    const ModConst *mc;
+    const uint64_t *a1, *T1, *vt1;  // Q[:nq] -> QMul
+    const uint64_t *a2, *T2, *vt2;  // QMul[:nm] -> Q
+    int N;
+    BfvQuantizeArgs m;
+};
+template <int CAP>
+__global__ void __launch_bounds__(64) bfv_quantize_kernel(BfvQuantizeKArgs A) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= A.N) return;
+    const size_t bz = blockIdx.z;
+    const int nq = A.m.nq, nm = A.m.nm;
+    uint64_t yv[CAP];
+    u128 acc[CAP];
+    double vi = 0.0;
+    const uint64_t *srcQ = A.cQ + bz * A.cQ_bs + x;
+#pragma unroll
+    for (int i = 0; i < CAP; i++) {
+        acc[i] = 0;
+        yv[i] = 0;
+        if (i < nq) {
+            const ModConst mq = A.mc[i];
+            const uint64_t v = cred(srcQ[(size_t)i * A.N] + A.m.q_half_q[i], mq.q);
+            const uint64_t yi = mred(v, ldc(A.a1, i), mq.q, mq.qinv);
+            yv[i] = yi;
+            vi = __dadd_rn(vi, __ddiv_rn(__ull2double_rn(yi), __ull2double_rn(mq.q)));
+        }
+    }
+    const uint64_t v1 = (uint64_t)vi;
+    const uint64_t *srcM = A.cM + bz * A.cM_bs + x;
+    double vj = 0.0;
+    for (int j = 0; j < nm; j++) {
+        const ModConst mp = A.mc[A.m.mod_m0 + j];
+        const uint64_t *Tr = A.T1 + (size_t)j * nq;
+        u128 s = (u128)yv[0] * ldc(Tr, 0);
+#pragma unroll
+        for (int i = 1; i < CAP; i++)
+            if (i < nq) s += (u128)yv[i] * ldc(Tr, i);
+        const uint64_t rlo = (uint64_t)s, rhi = (uint64_t)(s >> 64);
+        uint64_t e = rhi - mulhi64(rlo * mp.qinv, mp.q) + mp.q + ldc(A.vt1, (size_t)j * (nq + 1) + v1);
+        e = cred(e + mp.q - A.m.q_half_m[j], mp.q);                               // SubScalar: ModUpQtoP done
+        const uint64_t b = srcM[(size_t)j * A.N];
+        const uint64_t z = mred(e + (mp.q << 1) - b, A.m.div_s[j], mp.q, mp.qinv);  // ModDownQPtoP: (b - e) / Q
+        const uint64_t yj = mred(cred(z + A.m.m_half_m[j], mp.q), ldc(A.a2, j), mp.q, mp.qinv);
+        vj = __dadd_rn(vj, __ddiv_rn(__ull2double_rn(yj), __ull2double_rn(mp.q)));
+#pragma unroll
+        for (int i = 0; i < CAP; i++)
+            if (i < nq) acc[i] += (u128)yj * ldc(A.T2, (size_t)i * nm + j);
+    }
+    const uint64_t v2 = (uint64_t)vj;
+    uint64_t *dst = A.out + bz * A.out_bs + x;
+#pragma unroll
+    for (int i = 0; i < CAP; i++) {
+        if (i < nq) {
+            const ModConst mq = A.mc[i];
+            const uint64_t rlo = (uint64_t)acc[i], rhi = (uint64_t)(acc[i] >> 64);
+            uint64_t w = rhi - mulhi64(rlo * mq.qinv, mq.q) + mq.q + ldc(A.vt2, (size_t)i * (nm + 1) + v2);
+            w = cred(w + mq.q - A.m.m_half_q[i], mq.q);                           // ModUpPtoQ done
+            dst[(size_t)i * A.N] = mred(w, A.m.t_mont[i], mq.q, mq.qinv);         // MulScalar
+        }
+    }
+}
+hipError_t launch_bfv_quantize(const RingDev &r, const ModUpDev &up, const ModUpDev &down, const BfvQuantizeArgs &a, View cQ, View cM,
+                               View out, int batch, hipStream_t s) {
+    if (a.nq < 1 || a.nq > 32 || a.nm < 1 || a.nm > 32 || batch <= 0 || batch > 65535 || !cQ.p || !cM.p || !out.p) return hipErrorInvalidValue;
+    if (up.nsrc != a.nq || up.ndst < a.nm || down.nsrc != a.nm || down.ndst < a.nq) return hipErrorInvalidValue;
+    if (!no_tab({cQ, cM, out})) return hipErrorInvalidValue;  // no entry tables here (View::tab)
+    BfvQuantizeKArgs A{};
+    A.cQ = cQ.p; A.cM = cM.p; A.out = out.p;
+    A.cQ_bs = cQ.bstride; A.cM_bs = cM.bstride; A.out_bs = out.bstride;
+    A.mc = r.mc; A.N = r.N; A.m = a;
+    A.a1 = up.a; A.T1 = up.T; A.vt1 = up.vt;
+    A.a2 = down.a; A.T2 = down.T; A.vt2 = down.vt;
+    dim3 grid((unsigned)((r.N + 63) / 64), 1, batch), block(64);
+    ProfScope ps(K_BFV_QUANTIZE, s, (double)(2 * a.nq + a.nm) * batch * (double)r.N * 8.0);
+    if (a.nq <= 2) hipLaunchKernelGGL((bfv_quantize_kernel<2>), grid, block, 0, s, A);
+    else if (a.nq <= 4) hipLaunchKernelGGL((bfv_quantize_kernel<4>), grid, block, 0, s, A);
+    else if (a.nq <= 8) hipLaunchKernelGGL((bfv_quantize_kernel<8>), grid, block, 0, s, A);
+    else if (a.nq <= 12) hipLaunchKernelGGL((bfv_quantize_kernel<12>), grid, block, 0, s, A);
+    else if (a.nq <= 16) hipLaunchKernelGGL((bfv_quantize_kernel<16>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((bfv_quantize_kernel<32>), grid, block, 0, s, A);
     return hipGetLastError();
 }
 

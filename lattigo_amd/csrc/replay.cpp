@@ -30,6 +30,7 @@
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
 #include "../../include/hering_bridge.h"
+#include "../../include/hering_bfv.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -42,7 +43,8 @@ enum Fn : uint64_t {
     F_MAP_SMALL_TO_LARGE, F_SWITCH_RING_NTT, F_SWITCH_RING, F_APPLY_EVK,
     F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST,
     F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_AUTO_CT_SELECT, F_BLIND_ROTATE_CORE,
-    F_BRIDGE_UNFOLD, F_BRIDGE_FOLD, F_COMPLEX_TO_REAL, F_REAL_TO_COMPLEX, F_COUNT
+    F_BRIDGE_UNFOLD, F_BRIDGE_FOLD, F_COMPLEX_TO_REAL, F_REAL_TO_COMPLEX,
+    F_BFV_MUL_RELIN, F_BFV_QUANTIZE, F_COUNT
 };
 static_assert(F_COUNT <= 128, "the per-function profile has 128 slots");
 struct Arg {
@@ -192,6 +194,8 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
         case F_BRIDGE_FOLD: return he_fold_standard_to_conjugate_invariant(H(0), (int)I(1), H(2), H(3));
         case F_COMPLEX_TO_REAL: return he_complex_to_real(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6));
         case F_REAL_TO_COMPLEX: return he_real_to_complex(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6));
+        case F_BFV_MUL_RELIN: return he_bfv_mul_relin(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6), H(7), H(8), H(9));
+        case F_BFV_QUANTIZE: return he_bfv_quantize(H(0), (int)I(1), H(2), H(3), H(4));
         default: return HE_EINVAL;
     }
 }
