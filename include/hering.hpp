@@ -17,6 +17,7 @@
 
 #include <array>
 #include <cstdint>
+#include <complex>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -30,6 +31,7 @@
 #include "hering_blindrot.h"
 #include "hering_bridge.h"
 #include "hering_bfv.h"
+#include "hering_ckks_encoder.h"
 
 namespace hering {
 
@@ -744,6 +746,75 @@ public:
         const int level = ctIn.Level() < opOut.Level() ? ctIn.Level() : opOut.Level();
         check(he_real_to_complex(eval_.h(), level, ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), ciToStd_.h(), opOut.Value.at(0).h(), opOut.Value.at(1).h()));
     }
+};
+
+// ckks.Encoder, the double-precision path (schemes/ckks/encoder.go, prec <= 53; hering_ckks_encoder.h).  A plaintext is a Poly
+// plus the fields of rlwe.MetaData the reference reads; vectors are std::vector<std::complex<double>> or std::vector<double>,
+// [batch][n] flattened (batch = the polynomial's).
+struct MetaData {
+    double Scale = 1.0;
+    int LogSlots = 0;  // LogDimensions.Cols
+    bool IsBatched = true, IsNTT = true, IsMontgomery = false;
+};
+class Encoder {
+    detail::Ref r_;
+    int info_[4] = {0, 0, 0, 0};
+    static const double *dp(const std::vector<std::complex<double>> &v) { return reinterpret_cast<const double *>(v.data()); }
+    static double *dp(std::vector<std::complex<double>> &v) { return reinterpret_cast<double *>(v.data()); }
+
+public:
+    // NewEncoder (:78): ringP for EncodeQP only; roots: empty for the built-in table, or NthRoot + 1 values
+    explicit Encoder(const Ring &ringQ, const Ring *ringP = nullptr, const std::vector<std::complex<double>> &roots = {}) {
+        if (!roots.empty() && roots.size() != (size_t)(ringQ.Type() == RingType::Standard ? 2 : 4) * ringQ.N() + 1)
+            throw std::invalid_argument("ckks::Encoder: the table of roots must hold NthRoot + 1 values");
+        he_handle h = 0;
+        check(he_ckks_encoder_create(ringQ.h(), ringP ? ringP->h() : 0, roots.empty() ? nullptr : dp(roots), &h));
+        r_ = detail::own(h, he_ckks_encoder_destroy);
+        check(he_ckks_encoder_info(h, info_));
+    }
+    he_handle h() const { return r_->h; }
+    int LogMaxSlots() const { return info_[1]; }
+    int FFTOneWorkgroupMaxLogN() const { return info_[2]; }
+    int DecodeMaxLimbs() const { return info_[3]; }
+    // GetRootsComplex128 (utils.go:53) on the host, and the table this encoder holds
+    static std::vector<std::complex<double>> RootsHost(uint64_t nthRoot) {
+        std::vector<std::complex<double>> out(nthRoot + 1);
+        check(he_ckks_roots_host(nthRoot, dp(out)));
+        return out;
+    }
+    std::vector<std::complex<double>> Roots() const {
+        std::vector<std::complex<double>> out(((size_t)1 << info_[0]) + 1);
+        check(he_ckks_encoder_roots(h(), dp(out)));
+        return out;
+    }
+    // Encoder.FFT / IFFT (:765-820), in place, values.size() = batch << logN
+    void FFT(std::vector<std::complex<double>> &values, int logN) const { check(he_ckks_fft(h(), logN, (int)(values.size() >> logN), dp(values))); }
+    void IFFT(std::vector<std::complex<double>> &values, int logN) const { check(he_ckks_ifft(h(), logN, (int)(values.size() >> logN), dp(values))); }
+    // Encoder.Encode (:156): values.size() / pt.Batch() values per entry
+    void Encode(const std::vector<std::complex<double>> &values, const MetaData &m, Poly &pt) const {
+        check(he_ckks_encode(h(), pt.Level(), m.LogSlots, m.Scale, m.IsBatched, m.IsNTT, m.IsMontgomery, dp(values), values.size() / pt.Batch(), 1,
+                             pt.Batch(), pt.h()));
+    }
+    void Encode(const std::vector<double> &values, const MetaData &m, Poly &pt) const {
+        check(he_ckks_encode(h(), pt.Level(), m.LogSlots, m.Scale, m.IsBatched, m.IsNTT, m.IsMontgomery, values.data(), values.size() / pt.Batch(), 0,
+                             pt.Batch(), pt.h()));
+    }
+    // Encoder.Embed (:208) into a ring.Poly: the batched arm of Encode; into a ringqp.Poly (:321-328): EncodeQP
+    void Embed(const std::vector<std::complex<double>> &values, MetaData m, Poly &polyOut) const {
+        m.IsBatched = true;
+        Encode(values, m, polyOut);
+    }
+    void EncodeQP(const std::vector<std::complex<double>> &values, const MetaData &m, Poly &polyQ, Poly &polyP) const {
+        check(he_ckks_encode_qp(h(), polyQ.Level(), polyP.Level(), m.LogSlots, m.Scale, m.IsNTT, m.IsMontgomery, dp(values),
+                                values.size() / polyQ.Batch(), 1, polyQ.Batch(), polyQ.h(), polyP.h()));
+    }
+    // Encoder.DecodePublic (:199): [batch][slots] complex values ([batch][N] when the plaintext is not batched)
+    std::vector<std::complex<double>> DecodePublic(const Poly &pt, const MetaData &m, double logprec) const {
+        std::vector<std::complex<double>> out((size_t)pt.Batch() * (m.IsBatched ? (size_t)1 << m.LogSlots : (size_t)pt.N()));
+        check(he_ckks_decode(h(), pt.Level(), m.LogSlots, m.Scale, m.IsBatched, m.IsNTT, logprec, pt.h(), 1, dp(out)));
+        return out;
+    }
+    std::vector<std::complex<double>> Decode(const Poly &pt, const MetaData &m) const { return DecodePublic(pt, m, 0.0); }
 };
 }  // namespace ckks
 

@@ -11,7 +11,7 @@ _SO = os.environ.get("HERING_LIB") or os.path.join(_HERE, "libhering.so")  # HER
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
-         os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h")]
+         os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -56,6 +56,7 @@ def check(rc: int):
 def _declare(L):
     i, sz = C.c_int, C.c_size_t
     HP = C.POINTER(H)
+    f64p = C.POINTER(C.c_double)
     L.he_last_error.restype = C.c_char_p
     L.he_version.restype = C.c_char_p
     L.he_prof_kernel_name.restype = C.c_char_p
@@ -118,6 +119,12 @@ def _declare(L):
         "he_complex_to_real": [H, i, H, H, H, H, H], "he_real_to_complex": [H, i, H, H, H, H, H],
         "he_bfv_evaluator_create": [H, H, C.c_uint64, HP], "he_bfv_evaluator_destroy": [H], "he_bfv_level_qmul": [H, i, C.POINTER(i)],
         "he_bfv_mul_relin": [H, i, H, H, H, H, H, H, H, H], "he_bfv_quantize": [H, i, H, H, H],
+        "he_ckks_roots_host": [C.c_uint64, f64p], "he_ckks_encoder_create": [H, H, f64p, HP], "he_ckks_encoder_destroy": [H],
+        "he_ckks_encoder_roots": [H, f64p], "he_ckks_encoder_info": [H, C.POINTER(i)],
+        "he_ckks_fft": [H, i, i, f64p], "he_ckks_ifft": [H, i, i, f64p],
+        "he_ckks_encode": [H, i, i, C.c_double, i, i, i, f64p, sz, i, i, H],
+        "he_ckks_encode_qp": [H, i, i, i, C.c_double, i, i, f64p, sz, i, i, H, H],
+        "he_ckks_decode": [H, i, i, C.c_double, i, i, C.c_double, H, i, f64p],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
@@ -232,7 +239,13 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  # a Ring owns itself (Ring._owner), so an unreachable one is released by the cycle collector, whenever that runs:
                  # no later call of the recording can name it
                  "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds", "he_debug_arith",
-                 "he_bfv_level_qmul"}
+                 "he_bfv_level_qmul",
+                 # include/hering_ckks_encoder.h: decode, the transforms and the getters read; an encode carries host data into a
+                 # polynomial, as an upload does, and is left out on purpose (it fails trace_end)
+                 "he_ckks_decode", "he_ckks_fft", "he_ckks_ifft", "he_ckks_roots_host", "he_ckks_encoder_roots", "he_ckks_encoder_info",
+                 # no replayed call can name an encoder (its entries have no numbers), and an unreachable one is released whenever the
+                 # collector runs, as a Ring is
+                 "he_ckks_encoder_destroy"}
 _trace = None
 
 

@@ -41,6 +41,7 @@
 #include "../../include/hering_ringswitch.h"
 #include "../../include/hering_bridge.h"
 #include "../../include/hering_bfv.h"
+#include "../../include/hering_ckks_encoder.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -74,7 +75,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC };
 
 struct Obj {
     ObjType type;
@@ -4669,6 +4670,280 @@ int he_bfv_mul_relin(he_handle hb, int level, he_handle ha0, he_handle ha1, he_h
     };
     q.one_by_one();  // (scratch-to-scratch launches: no entry tables)
     return co_dispatch(*be.ctx, o.B, q);
+}
+
+// ---------------------------------------------------------------------------------------
+// CKKS encoder: Encode / Decode and the special FFT (include/hering_ckks_encoder.h; schemes/ckks/encoder.go, prec <= 53)
+// ---------------------------------------------------------------------------------------
+// Encoder (encoder.go:55-72) beside its rings: the table of roots and rotGroup on the device, the Garner constants of decode.
+// The entries carry host data, so they run like he_poly_upload / he_poly_download: the calling thread's queued requests first
+// (Scope), the launches straight on the context's stream, and the call returns when they are done.
+struct CkksEncoder : Obj {
+    std::shared_ptr<Ring> Q, P;
+    int logM = 0, log_max_slots = 0;
+    std::vector<double> roots;  // host copy, (M + 1) x 2
+    double *d_roots = nullptr;
+    uint32_t *d_rot = nullptr;
+    uint64_t *d_garner = nullptr;  // g [cap][cap], then per level < cap: Q | Q >> 1 (2 cap words)
+    int dec_levels = 0;            // levels he_ckks_decode serves: min(limbs of Q, cap)
+    CkksEncoder() : Obj(T_CKKS_ENC) {}
+    ~CkksEncoder() override {
+        hipSetDevice(Q->ctx->dev);
+        hipStreamSynchronize(Q->ctx->stream);
+        if (d_roots) hipFree(d_roots);
+        if (d_rot) hipFree(d_rot);
+        if (d_garner) hipFree(d_garner);
+    }
+    CkksFftDev fft() const { return CkksFftDev{d_roots, d_rot, logM}; }
+    const uint64_t *garner() const { return d_garner; }
+    const uint64_t *qwords(int level) const { return d_garner + (size_t)kCkksDecodeMaxLimbs * kCkksDecodeMaxLimbs + (size_t)level * 2 * kCkksDecodeMaxLimbs; }
+};
+static bool all_finite(const double *v, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+int he_ckks_roots_host(uint64_t nth_root, double *out) {
+    if (!out || nth_root < 8 || nth_root > (1ull << 22) || (nth_root & (nth_root - 1)))
+        return fail(HE_EINVAL, "he_ckks_roots_host: NthRoot must be a power of two in [8, 2^22] and the output non-null");
+    ckks_roots_complex128(nth_root, out);
+    return HE_OK;
+}
+int he_ckks_encoder_create(he_handle hq, he_handle hp, const double *roots, he_handle *out) {
+    static const char *who = "he_ckks_encoder_create";
+    GET(Q, Ring, hq, T_RING);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    auto e = std::make_shared<CkksEncoder>();
+    e->Q = Q;
+    if (hp) {
+        e->P = get<Ring>(hp, T_RING);
+        if (!e->P) return fail(HE_EHANDLE, "%s: bad ringP handle", who);
+        if (e->P->ctx != Q->ctx || e->P->N != Q->N || e->P->type != Q->type)
+            return fail(HE_EINVAL, "%s: ringP must share the context, degree and type of ringQ", who);
+    }
+    e->logM = Q->logN + (Q->type ? 2 : 1);
+    e->log_max_slots = e->logM - 2;
+    const size_t M = (size_t)1 << e->logM;
+    e->roots.resize(2 * (M + 1));
+    if (roots) {
+        if (!all_finite(roots, 2 * (M + 1))) return fail(HE_EINVAL, "%s: the table of roots holds a non-finite word", who);
+        memcpy(e->roots.data(), roots, 2 * (M + 1) * sizeof(double));
+    } else {
+        ckks_roots_complex128(M, e->roots.data());
+    }
+    const std::vector<uint32_t> rot = ckks_rot_group(M);
+    e->dec_levels = std::min(Q->nmod(), kCkksDecodeMaxLimbs);
+    std::vector<uint64_t> g = build_garner_table(Q->moduli, kCkksDecodeMaxLimbs);
+    for (int l = 0; l < e->dec_levels; l++) {
+        const std::vector<uint64_t> w = product_and_half_words(Q->moduli, l + 1, kCkksDecodeMaxLimbs);
+        g.insert(g.end(), w.begin(), w.end());
+    }
+    Scope sc(Q->ctx.get());
+    HIP_TRY(hipMalloc((void **)&e->d_roots, e->roots.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(e->d_roots, e->roots.data(), e->roots.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void **)&e->d_rot, rot.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(e->d_rot, rot.data(), rot.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void **)&e->d_garner, g.size() * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(e->d_garner, g.data(), g.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    *out = reg(e);
+    return HE_OK;
+}
+int he_ckks_encoder_destroy(he_handle h) { return unreg(h, T_CKKS_ENC); }
+int he_ckks_encoder_roots(he_handle h, double *out) {
+    GET(e, CkksEncoder, h, T_CKKS_ENC);
+    if (!out) return fail(HE_EINVAL, "he_ckks_encoder_roots: null output");
+    memcpy(out, e->roots.data(), e->roots.size() * sizeof(double));
+    return HE_OK;
+}
+int he_ckks_encoder_info(he_handle h, int out[4]) {
+    GET(e, CkksEncoder, h, T_CKKS_ENC);
+    if (!out) return fail(HE_EINVAL, "he_ckks_encoder_info: null output");
+    out[0] = e->logM; out[1] = e->log_max_slots; out[2] = kCkksFftLdsLog; out[3] = kCkksDecodeMaxLimbs;
+    return HE_OK;
+}
+// two device buffers of `words` doubles each from the scratch arena (the caller holds the context)
+static int ckks_scratch(Ctx &c, size_t words, size_t extra, double **a, double **b, uint64_t **x) {
+    TRY(c.arena_reserve((b ? 2 : 1) * words + extra + 8));
+    *a = reinterpret_cast<double *>(c.arena_take(words));
+    if (b) *b = reinterpret_cast<double *>(c.arena_take(words));
+    if (x) *x = c.arena_take(extra);
+    return HE_OK;
+}
+static int ckks_fft_api(he_handle h, int logn, int batch, double *values, bool inverse, const char *who) {
+    GET(e, CkksEncoder, h, T_CKKS_ENC);
+    if (logn < 0 || logn > e->log_max_slots) return fail(HE_EINVAL, "%s: logn (%d) must be in [0, %d]", who, logn, e->log_max_slots);
+    if (!values || batch < 1 || batch > 65535) return fail(HE_EINVAL, "%s: null values or batch %d outside [1, 65535]", who, batch);
+    const size_t words = ((size_t)batch << logn) * 2;
+    if (!all_finite(values, words)) return fail(HE_EINVAL, "%s: non-finite input", who);
+    Ctx &c = *e->Q->ctx;
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+    Scope sc(&c);
+    double *a, *b;
+    TRY(ckks_scratch(c, words, 0, &a, &b, nullptr));
+    HIP_TRY(hipMemcpyAsync(a, values, words * 8, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(launch_ckks_fft(e->fft(), a, b, a, logn, batch, inverse, nullptr, c.stream));
+    HIP_TRY(hipMemcpyAsync(values, b, words * 8, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+int he_ckks_fft(he_handle enc, int logn, int batch, double *values) { return ckks_fft_api(enc, logn, batch, values, false, "he_ckks_fft"); }
+int he_ckks_ifft(he_handle enc, int logn, int batch, double *values) { return ckks_fft_api(enc, logn, batch, values, true, "he_ckks_ifft"); }
+
+// an output / input polynomial of an encoder entry: `limbs` limbs of the encoder's degree and context, `batch` entries (< 0: any)
+static int ckks_poly(const CkksEncoder &e, he_handle h, int limbs, int batch, const char *name, const char *who, std::shared_ptr<Poly> *out) {
+    auto p = get<Poly>(h, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad polynomial handle for %s", who, name);
+    if (p->ctx != e.Q->ctx) return fail(HE_EINVAL, "%s: %s belongs to another context", who, name);
+    if (p->N != e.Q->N) return fail(HE_EINVAL, "%s: %s has degree %d, %d expected", who, name, p->N, e.Q->N);
+    if (p->nlimbs < limbs) return fail(HE_EINVAL, "%s: %s has %d limbs, %d needed", who, name, p->nlimbs, limbs);
+    if (batch >= 0 && p->batch != batch) return fail(HE_EINVAL, "%s: batch mismatch (%s has %d entries, %d expected)", who, name, p->batch, batch);
+    if (p->batch > 65535) return fail(HE_EINVAL, "%s: %s has %d entries, at most 65535 per call", who, name, p->batch);
+    *out = p;
+    return HE_OK;
+}
+// Encode / Embed into outQ (and outP when level_p >= 0)
+static int ckks_encode(const char *who, he_handle h, int level_q, int level_p, int log_slots, double scale, bool batched, bool is_ntt,
+                       bool is_mont, const double *values, size_t n_values, bool cplx, int batch, he_handle hq, he_handle hp) {
+    GET(e, CkksEncoder, h, T_CKKS_ENC);
+    const Ring &Q = *e->Q;
+    TRY(check_level(Q, level_q, who));
+    if (level_p >= 0) {
+        if (!e->P) return fail(HE_EINVAL, "%s: the encoder has no ringP", who);
+        TRY(check_level(*e->P, level_p, who));
+        if (hp == hq) return fail(HE_EINVAL, "%s: outP is outQ", who);
+    }
+    if (batch < 1 || batch > 65535) return fail(HE_EINVAL, "%s: batch %d outside [1, 65535]", who, batch);
+    if (!values || n_values == 0) return fail(HE_EINVAL, "%s: no values", who);
+    const size_t N = (size_t)Q.N;
+    size_t slots = N;
+    if (batched) {
+        if (log_slots < 0 || log_slots > e->log_max_slots)  // encoder.go:221-223
+            return fail(HE_EINVAL, "cannot Embed: logSlots (%d) must be greater or equal to %d and smaller than %d", log_slots, 0, e->log_max_slots);
+        slots = (size_t)1 << log_slots;
+        if (n_values > slots)  // :238-240
+            return fail(HE_EINVAL, "cannot Embed: ensure that #values (%zu) <= slots (%zu) <= maxCols (%zu)", n_values, slots, (size_t)1 << e->log_max_slots);
+    } else {
+        if (cplx) return fail(HE_EINVAL, "cannot Encode: supported values.(type) for IsBatched=False is []float64");  // :179-181
+        if (n_values > N) return fail(HE_EINVAL, "cannot Encode: maximum number of values is %zu but len(values) is %zu", N, n_values);  // :165-167
+    }
+    if (!std::isfinite(scale)) return fail(HE_EINVAL, "%s: the scale is not finite", who);
+    if (!all_finite(values, (size_t)batch * n_values * (cplx ? 2 : 1))) return fail(HE_EINVAL, "%s: non-finite input", who);
+    std::shared_ptr<Poly> oq, op;
+    TRY(ckks_poly(*e, hq, level_q + 1, batch, "outQ", who, &oq));
+    if (level_p >= 0) TRY(ckks_poly(*e, hp, level_p + 1, batch, "outP", who, &op));
+    Ctx &c = *Q.ctx;
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+
+    // the vectors as the reference's buffer holds them before the transform: zero-padded (:309-312), the imaginary parts dropped
+    // on a conjugate-invariant ring (:242-246); not batched: N reals
+    const size_t per = batched ? 2 * slots : N, words = (size_t)batch * per;
+    // (a full vector that needs neither padding nor its imaginary parts dropped goes to the device straight from the caller's buffer)
+    const bool direct = n_values * (cplx ? 2 : 1) == per && (!batched || Q.type == 0);
+    std::vector<double> host;
+    if (!direct) {
+        host.assign(words, 0.0);
+        for (int b = 0; b < batch; b++) {
+            const double *src = values + (size_t)b * n_values * (cplx ? 2 : 1);
+            double *dst = host.data() + (size_t)b * per;
+            if (!batched) memcpy(dst, src, n_values * sizeof(double));
+            else if (cplx && Q.type == 0) memcpy(dst, src, 2 * n_values * sizeof(double));
+            else for (size_t i = 0; i < n_values; i++) dst[2 * i] = src[cplx ? 2 * i : i];
+        }
+    }
+    CkksQuantArgs qa;
+    qa.mcQ = Q.dev.mc; qa.outQ = oq->view(); qa.nQ = level_q + 1;
+    if (op) { qa.mcP = e->P->dev.mc; qa.outP = op->view(); qa.nP = level_p + 1; }
+    qa.logN = Q.logN; qa.standard = Q.type == 0; qa.scale = scale;
+    qa.log_gap = batched ? e->log_max_slots - log_slots : 0;
+
+    const bool multipass = batched && log_slots > kCkksFftLdsLog;  // (only then do the values come back from the transform)
+    Scope sc(&c);
+    double *a, *b = nullptr;
+    TRY(ckks_scratch(c, words, 0, &a, multipass ? &b : nullptr, nullptr));
+    HIP_TRY(hipMemcpyAsync(a, direct ? values : host.data(), words * 8, hipMemcpyHostToDevice, c.stream));
+    if (!batched) {
+        HIP_TRY(launch_f64_to_rns(a, 0, true, qa, batch, c.stream));
+    } else if (!multipass) {
+        HIP_TRY(launch_ckks_fft(e->fft(), a, nullptr, nullptr, log_slots, batch, true, &qa, c.stream));  // IFFT + quantiser: one launch
+    } else {
+        HIP_TRY(launch_ckks_fft(e->fft(), a, b, a, log_slots, batch, true, nullptr, c.stream));
+        HIP_TRY(launch_f64_to_rns(b, log_slots, false, qa, batch, c.stream));
+    }
+    // NTTSparseAndMontgomery (core/rlwe/utils.go:187-244): the transform of dimension n with the roots of N replicated gap times IS
+    // the transform of the polynomial in Y = X^gap the quantiser wrote; the words are reduced on the way in, and the NTT of the
+    // quirk words (q, an unreduced c) is the NTT of their residues.  MForm commutes with the transform (both outputs canonical).
+    for (int side = 0; side < (op ? 2 : 1); side++) {
+        const Ring &r = side ? *e->P : Q;
+        const Poly &p = side ? *op : *oq;
+        const int lv = side ? level_p : level_q;
+        if (is_ntt) HIP_TRY(ring_ntt(r, ident_tab(lv + 1), p.view(), p.view(), batch, false, NTT_REDUCE_INPUT));
+        if (batched && is_mont) HIP_TRY(launch_ew(r.dev, ident_tab(lv + 1), EW_MFORM, p.view(), p.view(), p.view(), batch, nullptr, nullptr, c.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+int he_ckks_encode(he_handle enc, int level, int log_slots, double scale, int is_batched, int is_ntt, int is_montgomery, const double *values,
+                   size_t n_values, int is_complex, int batch, he_handle outQ) {
+    return ckks_encode("he_ckks_encode", enc, level, -1, log_slots, scale, is_batched != 0, is_ntt != 0, is_montgomery != 0, values, n_values,
+                       is_complex != 0, batch, outQ, 0);
+}
+int he_ckks_encode_qp(he_handle enc, int level_q, int level_p, int log_slots, double scale, int is_ntt, int is_montgomery, const double *values,
+                      size_t n_values, int is_complex, int batch, he_handle outQ, he_handle outP) {
+    return ckks_encode("he_ckks_encode_qp", enc, level_q, level_p < 0 ? -1 : level_p, log_slots, scale, true, is_ntt != 0, is_montgomery != 0, values,
+                       n_values, is_complex != 0, batch, outQ, outP);
+}
+int he_ckks_decode(he_handle h, int level, int log_slots, double scale, int is_batched, int is_ntt, double logprec, he_handle hpt, int is_complex,
+                   double *values) {
+    static const char *who = "he_ckks_decode";
+    GET(e, CkksEncoder, h, T_CKKS_ENC);
+    const Ring &Q = *e->Q;
+    TRY(check_level(Q, level, who));
+    if (level + 1 > kCkksDecodeMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs, at most %d are reconstructed", who, level + 1, kCkksDecodeMaxLimbs);
+    if (is_batched && (log_slots < 0 || log_slots > e->log_max_slots))  // encoder.go:502-504
+        return fail(HE_EINVAL, "cannot Decode: ensure that %d <= logSlots (%d) <= %d", 0, log_slots, e->log_max_slots);
+    if (!values) return fail(HE_EINVAL, "%s: null output", who);
+    if (!std::isfinite(scale) || scale == 0.0 || !std::isfinite(logprec)) return fail(HE_EINVAL, "%s: the scale must be finite and non-zero, logprec finite", who);
+    std::shared_ptr<Poly> pt;
+    TRY(ckks_poly(*e, hpt, level + 1, -1, "pt", who, &pt));
+    Ctx &c = *Q.ctx;
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+    const int B = pt->batch;
+    const size_t N = (size_t)Q.N, sQ = (size_t)(level + 1) * N;
+    const size_t count = is_batched ? (size_t)1 << log_slots : N;
+    const size_t words = (size_t)B * count * 2;
+
+    CkksDecodeArgs da;
+    da.nl = level + 1; da.log_slots = is_batched ? log_slots : 0; da.log_gap = is_batched ? e->log_max_slots - log_slots : 0;
+    da.batched = is_batched != 0; da.standard = Q.type == 0; da.cplx = is_complex != 0; da.scale = scale;
+    da.g = e->garner(); da.Qw = e->qwords(level);
+
+    Scope sc(&c);
+    double *a, *b;
+    uint64_t *x = nullptr;
+    TRY(ckks_scratch(c, words, is_ntt ? (size_t)B * sQ : 0, &a, &b, &x));
+    View src = pt->view();
+    if (is_ntt) {  // :508-512
+        const View t{x, sQ};
+        HIP_TRY(ring_ntt(Q, ident_tab(level + 1), src, t, B, true, NTT_REDUCE_INPUT));
+        src = t;
+    }
+    HIP_TRY(launch_rns_to_f64(Q.dev, da, src, a, B, c.stream));
+    if (!is_batched) {  // plaintextToFloat (:488-493, :757-759)
+        HIP_TRY(hipMemcpyAsync(values, a, (size_t)B * N * (is_complex ? 2 : 1) * 8, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        return HE_OK;
+    }
+    HIP_TRY(launch_ckks_fft(e->fft(), a, b, a, log_slots, B, false, nullptr, c.stream));
+    std::vector<double> host(words);
+    HIP_TRY(hipMemcpyAsync(host.data(), b, words * 8, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (logprec != 0) {  // :536-550: math.Round is half away from zero
+        const double s = std::exp2(logprec);
+        for (size_t i = 0; i < words; i++) host[i] = std::round(host[i] * s) / s;
+    }
+    if (is_complex) memcpy(values, host.data(), words * 8);
+    else for (size_t i = 0; i < words / 2; i++) values[i] = host[2 * i];
+    return HE_OK;
 }
 
 // ---------------------------------------------------------------------------------------

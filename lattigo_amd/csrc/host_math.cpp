@@ -1,6 +1,8 @@
 // host_math.cpp -- see host_math.h.
 #include "host_math.h"
 
+#include <cmath>
+
 #include <algorithm>
 
 namespace he {
@@ -224,6 +226,62 @@ uint64_t words_mod(const uint64_t *w, int n, uint64_t q) {
     u128 rem = 0;
     for (int i = n - 1; i >= 0; i--) rem = ((rem << 64) | w[i]) % q;
     return (uint64_t)rem;
+}
+
+void ckks_roots_complex128(uint64_t M, double *out) {
+    for (uint64_t i = 0; i < 2 * (M + 1); i++) out[i] = 0.0;
+    const uint64_t quarm = M >> 2;
+    const double angle = 2 * 3.141592653589793 / (double)M;
+    auto re = [&](uint64_t i) -> double & { return out[2 * i]; };
+    auto im = [&](uint64_t i) -> double & { return out[2 * i + 1]; };
+    for (uint64_t i = 0; i < quarm; i++) re(i) = std::cos(angle * (double)i);                         // :60-62
+    for (uint64_t i = 0; i < quarm; i++) { re(quarm - i) += 0.0; im(quarm - i) += re(i); }              // :64-66
+    for (uint64_t i = 1; i < quarm + 1; i++) {                                                         // :68-72
+        re(i + quarm) = -re(quarm - i); im(i + quarm) = im(quarm - i);
+        re(i + 2 * quarm) = -re(i); im(i + 2 * quarm) = -im(i);
+        re(i + 3 * quarm) = re(quarm - i); im(i + 3 * quarm) = -im(quarm - i);
+    }
+    re(M) = re(0); im(M) = im(0);                                                                      // :74
+}
+
+std::vector<uint32_t> ckks_rot_group(uint64_t M) {
+    std::vector<uint32_t> rot(M >> 2);
+    uint64_t five = 1;
+    for (auto &r : rot) {
+        r = (uint32_t)five;
+        five = (five * 5) & (M - 1);
+    }
+    return rot;
+}
+
+std::vector<uint64_t> build_garner_table(const std::vector<uint64_t> &moduli, int cap) {
+    std::vector<uint64_t> g((size_t)cap * cap, 0);
+    const int n = (int)moduli.size() < cap ? (int)moduli.size() : cap;
+    for (int i = 0; i < n; i++) {
+        const uint64_t q = moduli[i];
+        uint64_t p = 1;
+        for (int j = 0; j < i; j++) {
+            g[(size_t)i * cap + j] = to_mont(p, q);
+            p = mulmod(p, moduli[j] % q, q);
+        }
+        g[(size_t)i * cap + i] = to_mont(invmod(p, q), q);
+    }
+    return g;
+}
+
+std::vector<uint64_t> product_and_half_words(const std::vector<uint64_t> &moduli, int n, int cap) {
+    std::vector<uint64_t> w((size_t)2 * cap, 0);
+    w[0] = 1;
+    for (int i = 0; i < n; i++) {
+        uint64_t carry = 0;
+        for (int k = 0; k < cap; k++) {
+            const u128 p = (u128)w[k] * moduli[i] + carry;
+            w[k] = (uint64_t)p;
+            carry = (uint64_t)(p >> 64);
+        }
+    }
+    for (int k = 0; k < cap; k++) w[cap + k] = (w[k] >> 1) | (k + 1 < cap ? w[k + 1] << 63 : 0);
+    return w;
 }
 
 }  // namespace he

@@ -53,4 +53,16 @@ uint64_t inv_product_mont(const std::vector<uint64_t> &S, uint64_t q);
 // multiword (little-endian) scalar mod q
 uint64_t words_mod(const uint64_t *w, int n, uint64_t q);
 
+// ---- CKKS encoder (schemes/ckks) -------------------------------------------------------------------------------------
+// GetRootsComplex128(M) (schemes/ckks/utils.go:53-77): M + 1 complex128 as (re, im) pairs.  cos(angle * float64(i)) for the first
+// quarter only (this host's libm), every other word a copy or a negation of those, written as :60-74 write them
+void ckks_roots_complex128(uint64_t M, double *out);
+// rotGroup[j] = 5^j mod M, j < M / 4 (schemes/ckks/encoder.go:83-89)
+std::vector<uint32_t> ckks_rot_group(uint64_t M);
+// Mixed-radix (Garner) constants of the first min(n, cap) moduli, [cap][cap]: g[i][j] = MForm(q_0 .. q_{j-1} mod q_i) for j < i,
+// g[i][i] = MForm((q_0 .. q_{i-1})^-1 mod q_i); they do not depend on the level
+std::vector<uint64_t> build_garner_table(const std::vector<uint64_t> &moduli, int cap);
+// prod(moduli[0..n)) little-endian in `cap` words, followed by that product >> 1 in `cap` words (n <= cap)
+std::vector<uint64_t> product_and_half_words(const std::vector<uint64_t> &moduli, int n, int cap);
+
 }  // namespace he

@@ -409,6 +409,49 @@ struct BfvQuantizeArgs {
 hipError_t launch_bfv_quantize(const RingDev &r, const ModUpDev &up, const ModUpDev &down, const BfvQuantizeArgs &a, View cQ, View cM,
                                View out, int batch, hipStream_t s);
 
+// ---- CKKS encoder (schemes/ckks/encoder.go, double-precision path; include/hering_ckks_encoder.h) -------------------------
+// The special FFT / iFFT of ckks_vector_ops.go:18-76 over n = 2^logn complex128 per batch entry, butterfly for butterfly (one IEEE
+// operation per written operation, no fused multiply-add, complex product (ac - bd, ad + bc)).  Up to 2^kCkksFftLdsLog values one
+// workgroup per entry runs every stage in LDS (two arrays of doubles: 2^13 x 16 B = 128 KiB of the 160 KiB a workgroup may
+// declare); above, one launch per outer stage over global memory and the LDS kernel on blocks of 2^kCkksFftLdsLog for the rest.
+constexpr int kCkksFftLdsLog = 13;
+constexpr int kCkksDecodeMaxLimbs = 32;  // limbs rns_to_f64_kernel reconstructs (multi-word integer in registers)
+struct CkksFftDev {
+    const double *roots;  // [M + 1][2]: GetRootsComplex128(M) (utils.go:53-77), or the caller's table
+    const uint32_t *rot;  // [M / 4]: 5^j mod M
+    int logM;             // M = NthRoot of the ring
+};
+// Where the quantiser (SingleFloat64ToFixedPointCRT, utils.go:171-234, placed as Complex128ToFixedPointCRT :130-153 places it)
+// writes: limbs 0..nQ-1 of outQ with the modulus records mcQ[0..nQ) (device), optionally limbs 0..nP-1 of outP; coefficient c of
+// [re(slots) | im(slots)] lands at position c << log_gap, every other word of the polynomial is 0.  No entry tables.
+struct CkksQuantArgs {
+    const ModConst *mcQ = nullptr, *mcP = nullptr;
+    View outQ{nullptr, 0}, outP{nullptr, 0};
+    int nQ = 0, nP = 0;
+    int logN = 0, log_gap = 0;
+    int standard = 1;  // 0: conjugate-invariant ring (imaginary parts discarded)
+    double scale = 0.0;
+};
+// in -> out ([batch][n][2] doubles, out != in).  logn > kCkksFftLdsLog: `work` is needed -- inverse: work == in, whose contents the
+// outer stages overwrite; forward: unused (the outer stages run in place on out).  quant (inverse, logn <= kCkksFftLdsLog only):
+// the values are not stored; the kernel's last step quantises them from LDS into the polynomial(s), zeros included -- ONE launch.
+hipError_t launch_ckks_fft(const CkksFftDev &t, const double *in, double *out, double *work, int logn, int batch, bool inverse,
+                           const CkksQuantArgs *quant, hipStream_t s);
+// the quantiser as a launch of its own: src = [batch][n][2] slot values (direct = false), or [batch][N] real coefficients, already
+// zero-padded (direct = true: Float64ToFixedPointCRT, utils.go:156-168)
+hipError_t launch_f64_to_rns(const double *src, int logn, bool direct, const CkksQuantArgs &q, int batch, hipStream_t s);
+// RNS -> float64 of the coefficients Decode needs (encoder.go:823-1116): batched -- slot i gets (coefficient i << log_gap,
+// coefficient N/2 + (i << log_gap)) / scale as [batch][slots][2] (conjugate-invariant: the imaginary part is -real of slot
+// slots - i, 0 for i = 0, :965-970); not batched -- every coefficient, [batch][N] reals ([N][2] with cplx).  g / Qw: device tables
+// of host_math's build_garner_table / the level's modulus (Q little-endian in kCkksDecodeMaxLimbs words, then Q >> 1).
+struct CkksDecodeArgs {
+    int nl = 0;  // limbs (level + 1), 1..kCkksDecodeMaxLimbs
+    int log_slots = 0, log_gap = 0, batched = 1, standard = 1, cplx = 1;
+    double scale = 1.0;
+    const uint64_t *g = nullptr, *Qw = nullptr;
+};
+hipError_t launch_rns_to_f64(const RingDev &r, const CkksDecodeArgs &a, View src, double *dst, int batch, hipStream_t s);
+
 // ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
 // One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
 // ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
@@ -468,7 +511,7 @@ enum KernelId {
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
     K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_CI_BRIDGE_FOLD,
-    K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_COUNT
+    K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

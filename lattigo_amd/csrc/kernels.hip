@@ -74,7 +74,8 @@ const char *kernel_name(int id) {
                                          "ntt_rows_inv_f64", "ntt_mac_f64", "diag_mac", "ring_degree_fold_ntt",
                                          "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
                                          "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select",
-                                         "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize"};
+                                         "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize", "special_fft", "ckks_fft_pass",
+                                         "special_ifft_quantize", "f64_to_rns", "rns_to_f64"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -4924,6 +4925,384 @@ hipError_t launch_arith_probe(const ModConst *mc, int op, size_t n, const uint64
     ProfScope ps(K_PROBE, s);
     ArithProbeArgs A{mc, a, b, c, o0, o1, (unsigned)n, op};
     hipLaunchKernelGGL(arith_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// CKKS encoder (schemes/ckks/encoder.go, ckks_vector_ops.go:18-76, utils.go:130-234; see kernels.h).  Every float64 operation below
+// is one IEEE round-to-nearest operation written with the __d*_rn intrinsics, so that no contraction can fuse a product into a sum
+// whatever the flags of the translation unit: the words are those of the reference's scalar code.
+// ------------------------------------------------------------------------------------
+// SingleFloat64ToFixedPointCRT (utils.go:171-234) of one value into every limb of one ring, at word offset `pos` of batch entry bz
+__device__ __forceinline__ void ckks_quant_store(double value, double scale, const ModConst *mc, int nl, uint64_t *out, size_t N, size_t pos) {
+    uint64_t *dst = out + pos;
+    const bool neg = value < 0.0;
+    // value *= scale, with the sign of scale flipped for a negative value (:189-194): a positive product
+    const double v = __dmul_rn(value, neg ? -scale : scale);
+    if (value == 0.0 || !(v >= 0.0) || !(v < __longlong_as_double(0x7ff0000000000000ll))) {
+        // zero (:173-179).  A product that is negative (a negative scale), infinite or NaN (overflow inside the transform) has no
+        // defined word in the reference (the conversion of :215 is undefined there): 0.  A product that IS zero -- scale 0, or an
+        // underflow -- takes the path below like any other value under 2^64: c = uint64(0.5) = 0, the word q for a negative value
+        for (int i = 0; i < nl; i++) dst[(size_t)i * N] = 0;
+        return;
+    }
+    if (v >= 18446744073709551616.0) {
+        // :198-210.  big.NewFloat(v) + 0.5 at 53 bits of precision rounds back to v (v >= 2^64 has an ulp of 2^12 or more), so the
+        // integer is v itself = m 2^e with m the 53-bit significand: m 2^e mod q with the Barrett / Montgomery helpers -- the
+        // remainder of e by 64 as one Montgomery product with MForm(2^s), then one MForm (a multiplication by 2^64) per 64 bits
+        const uint64_t bits = (uint64_t)__double_as_longlong(v);
+        const int e = (int)((bits >> 52) & 0x7ff) - 1075;  // >= 12
+        const uint64_t m = (bits & 0xfffffffffffffull) | (1ull << 52);
+        for (int i = 0; i < nl; i++) {
+            const ModConst k = mc[i];
+            uint64_t r = bred_add(m, k.q, k.brc0);
+            r = mred(r, mform(1ull << (e & 63), k.q, k.brc0, k.brc1), k.q, k.qinv);
+            for (int t = e >> 6; t > 0; t--) r = mform(r, k.q, k.brc0, k.brc1);
+            dst[(size_t)i * N] = neg ? k.q - r : r;  // (:206: the word q when q | v)
+        }
+        return;
+    }
+    const uint64_t c = (uint64_t)__dadd_rn(v, 0.5);  // :215 (v + 0.5 < 2^64: the ulp of v is at most 2^11 there)
+    for (int i = 0; i < nl; i++) {
+        const ModConst k = mc[i];
+        uint64_t w;
+        if (neg) w = c > k.q ? k.q - bred_add(c, k.q, k.brc0) : k.q - c;            // :217-223
+        else w = c > 0x1fffffffffffffffull ? bred_add(c, k.q, k.brc0) : c;           // :225-231 (unreduced below 2^61)
+        dst[(size_t)i * N] = w;
+    }
+}
+// Complex128ToFixedPointCRT (utils.go:130-153) at stride gap = N / (slots << standard): the word of polynomial position pos, read
+// from the slot values through `re(p)` / `im(p)` (slot p), into every limb of Q and of P; everything else 0
+struct CkksQuantK {
+    const ModConst *mcQ, *mcP;
+    uint64_t *outQ, *outP;
+    size_t outQ_bs, outP_bs;
+    int nQ, nP;         // limbs written (nP = 0: no P side)
+    int logN, log_gap;  // position of coefficient c: c << log_gap
+    int standard;       // 1: imaginary parts from coefficient `slots` on; 0 (conjugate-invariant): discarded
+    double scale;
+};
+template <class Re, class Im>
+__device__ __forceinline__ void ckks_quant_pos(const CkksQuantK &Q, size_t bz, unsigned pos, int logn, Re re, Im im) {
+    double value = 0.0;
+    if ((pos & ((1u << Q.log_gap) - 1u)) == 0) {
+        const unsigned c = pos >> Q.log_gap, p = c & ((1u << logn) - 1u);
+        value = (c >> logn) ? im(p) : re(p);
+    }
+    const size_t N = (size_t)1 << Q.logN;
+    ckks_quant_store(value, Q.scale, Q.mcQ, Q.nQ, Q.outQ + bz * Q.outQ_bs, N, pos);
+    if (Q.nP) ckks_quant_store(value, Q.scale, Q.mcP, Q.nP, Q.outP + bz * Q.outP_bs, N, pos);
+}
+
+// The special FFT / iFFT (SpecialFFTDouble / SpecialIFFTDouble, ckks_vector_ops.go:18-76) over n = 2^logn complex128 values per
+// batch entry.  A workgroup owns the 2^logb consecutive values of block blockIdx.x of entry blockIdx.y and runs the stages of
+// length up to 2^logb over them in LDS -- all of them when logb = logn; the outer stages are ckks_fft_pass_kernel's.  Real and
+// imaginary parts live in two double arrays: every LDS access is 8 bytes at a stride of one double over the butterflies of a
+// stage, and the 16-byte stores with their extra cycles never occur.  The bit reversal (over all logn bits) is the forward
+// transform's load and the inverse's store; the inverse divides by n after its last stage (:42-44), and with `quant` it then
+// quantises from LDS into every limb of the output polynomial(s), zeros included, instead of storing the values.
+struct CkksFftKArgs {
+    const double *in;  // [batch][n][2]
+    double *out;       // [batch][n][2] (not `in`: the bit reversal crosses blocks)
+    const double *roots;   // [M + 1][2]
+    const uint32_t *rot;   // [M / 4]: 5^j mod M
+    int logn, logb, logM, quant;
+    CkksQuantK q;
+};
+__device__ __forceinline__ unsigned ckks_brev(unsigned x, int bits) { return bits ? __brev(x) >> (32 - bits) : 0u; }
+template <bool INVERSE, int LOGCAP, int THREADS>
+__global__ void __launch_bounds__(THREADS) special_fft_kernel(CkksFftKArgs A) {
+    __shared__ double sre[1 << LOGCAP], sim[1 << LOGCAP];
+    const int logn = A.logn, logb = A.logb;
+    const unsigned nb = 1u << logb, base = blockIdx.x << logb;
+    const size_t bz = blockIdx.y;
+    const double *src = A.in + (bz << logn) * 2;
+    for (unsigned i = threadIdx.x; i < nb; i += THREADS) {
+        const unsigned g = INVERSE ? base + i : ckks_brev(base + i, logn);
+        sre[i] = src[2 * (size_t)g];
+        sim[i] = src[2 * (size_t)g + 1];
+    }
+    __syncthreads();
+    for (int s = 0; s < logb; s++) {
+        const int loglen = INVERSE ? logb - s : s + 1;
+        const unsigned lenh = 1u << (loglen - 1), lenq = 4u << loglen, mask = lenq - 1u;
+        const int log_gap = A.logM - 2 - loglen;
+        for (unsigned t = threadIdx.x; t < (nb >> 1); t += THREADS) {
+            const unsigned j = t & (lenh - 1u), k = ((t >> (loglen - 1)) << loglen) + j;
+            const unsigned r = A.rot[j] & mask;
+            const size_t wi = (size_t)(INVERSE ? lenq - r : r) << log_gap;
+            const double wr = A.roots[2 * wi], wim = A.roots[2 * wi + 1];
+            const double ur = sre[k], ui = sim[k], vr = sre[k + lenh], vi = sim[k + lenh];
+            if (INVERSE) {  // (u + v, (u - v) w)  (:37)
+                const double dr = __dsub_rn(ur, vr), di = __dsub_rn(ui, vi);
+                sre[k] = __dadd_rn(ur, vr);
+                sim[k] = __dadd_rn(ui, vi);
+                sre[k + lenh] = __dsub_rn(__dmul_rn(dr, wr), __dmul_rn(di, wim));
+                sim[k + lenh] = __dadd_rn(__dmul_rn(dr, wim), __dmul_rn(di, wr));
+            } else {        // v *= w; (u + v, u - v)  (:71-72)
+                const double pr = __dsub_rn(__dmul_rn(vr, wr), __dmul_rn(vi, wim));
+                const double pi = __dadd_rn(__dmul_rn(vr, wim), __dmul_rn(vi, wr));
+                sre[k] = __dadd_rn(ur, pr);
+                sim[k] = __dadd_rn(ui, pi);
+                sre[k + lenh] = __dsub_rn(ur, pr);
+                sim[k + lenh] = __dsub_rn(ui, pi);
+            }
+        }
+        __syncthreads();
+    }
+    if (INVERSE) {
+        const double nd = (double)(1u << logn);  // values[i] /= complex(float64(N), 0)  (:43): two real divisions
+        for (unsigned i = threadIdx.x; i < nb; i += THREADS) {
+            sre[i] = __ddiv_rn(sre[i], nd);
+            sim[i] = __ddiv_rn(sim[i], nd);
+        }
+        if (A.quant) {  // (one workgroup per entry: logb == logn)
+            __syncthreads();
+            const unsigned N = 1u << A.q.logN;
+            auto re = [&](unsigned p) { return sre[ckks_brev(p, logn)]; };
+            auto im = [&](unsigned p) { return A.q.standard ? sim[ckks_brev(p, logn)] : 0.0; };
+            for (unsigned pos = threadIdx.x; pos < N; pos += THREADS) ckks_quant_pos(A.q, bz, pos, logn, re, im);
+            return;
+        }
+    }
+    double *dst = A.out + (bz << logn) * 2;
+    for (unsigned i = threadIdx.x; i < nb; i += THREADS) {
+        const unsigned g = INVERSE ? ckks_brev(base + i, logn) : base + i;
+        dst[2 * (size_t)g] = sre[i];
+        dst[2 * (size_t)g + 1] = sim[i];
+    }
+}
+// one outer stage (length 2^loglen > the LDS block) of the same transform over global memory, in place: thread t of entry
+// blockIdx.y owns butterfly t -- its own pair, so the words do not depend on the blocking
+template <bool INVERSE>
+__global__ void __launch_bounds__(256) ckks_fft_pass_kernel(double *data, const double *roots, const uint32_t *rot, int logn, int loglen, int logM) {
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (1u << logn) >> 1) return;
+    double *v = data + ((size_t)blockIdx.y << logn) * 2;
+    const unsigned lenh = 1u << (loglen - 1), lenq = 4u << loglen, mask = lenq - 1u;
+    const unsigned j = t & (lenh - 1u), k = ((t >> (loglen - 1)) << loglen) + j;
+    const unsigned r = rot[j] & mask;
+    const size_t wi = (size_t)(INVERSE ? lenq - r : r) << (logM - 2 - loglen);
+    const double wr = roots[2 * wi], wim = roots[2 * wi + 1];
+    const size_t a = 2 * (size_t)k, b = 2 * (size_t)(k + lenh);
+    const double ur = v[a], ui = v[a + 1], vr = v[b], vi = v[b + 1];
+    if (INVERSE) {
+        const double dr = __dsub_rn(ur, vr), di = __dsub_rn(ui, vi);
+        v[a] = __dadd_rn(ur, vr);
+        v[a + 1] = __dadd_rn(ui, vi);
+        v[b] = __dsub_rn(__dmul_rn(dr, wr), __dmul_rn(di, wim));
+        v[b + 1] = __dadd_rn(__dmul_rn(dr, wim), __dmul_rn(di, wr));
+    } else {
+        const double pr = __dsub_rn(__dmul_rn(vr, wr), __dmul_rn(vi, wim));
+        const double pi = __dadd_rn(__dmul_rn(vr, wim), __dmul_rn(vi, wr));
+        v[a] = __dadd_rn(ur, pr);
+        v[a + 1] = __dadd_rn(ui, pi);
+        v[b] = __dsub_rn(ur, pr);
+        v[b + 1] = __dsub_rn(ui, pi);
+    }
+}
+hipError_t launch_ckks_fft(const CkksFftDev &t, const double *in, double *out, double *work, int logn, int batch, bool inverse,
+                           const CkksQuantArgs *quant, hipStream_t s) {
+    if (logn < 0 || logn > t.logM - 2 || batch <= 0 || batch > 65535 || !in || !t.roots || !t.rot) return hipErrorInvalidValue;
+    const int logb = logn < kCkksFftLdsLog ? logn : kCkksFftLdsLog;
+    if (quant && (logb != logn || !inverse)) return hipErrorInvalidValue;
+    if (!quant && (!out || out == in)) return hipErrorInvalidValue;
+    if (logb != logn && (!work || (inverse && work != in))) return hipErrorInvalidValue;
+    CkksFftKArgs A{};
+    A.in = in; A.out = out; A.roots = t.roots; A.rot = t.rot;
+    A.logn = logn; A.logb = logb; A.logM = t.logM; A.quant = quant != nullptr;
+    if (quant) {
+        const CkksQuantArgs &q = *quant;
+        if (q.nQ < 1 || q.nQ > kMaxLimbs || q.nP < 0 || q.nP > kMaxLimbs || !q.outQ.p || (q.nP && !q.outP.p) || !no_tab({q.outQ, q.outP}))
+            return hipErrorInvalidValue;
+        if (q.logN - q.log_gap != logn + q.standard) return hipErrorInvalidValue;  // the coefficients fill the polynomial exactly
+        A.q = CkksQuantK{q.mcQ, q.mcP, q.outQ.p, q.outP.p, q.outQ.bstride, q.outP.bstride, q.nQ, q.nP, q.logN, q.log_gap, q.standard, q.scale};
+    }
+    const unsigned n = 1u << logn;
+    const dim3 grid(n >> logb, batch);
+    const double bytes = 32.0 * n * batch;
+    if (inverse) {
+        // the outer stages first, in place on `in` (== work), then the LDS stages
+        for (int loglen = logn; loglen > logb; loglen--) {
+            ProfScope ps(K_CKKS_FFT_PASS, s, bytes);
+            hipLaunchKernelGGL((ckks_fft_pass_kernel<true>), dim3((n / 2 + 255) / 256, batch), dim3(256), 0, s, work, t.roots, t.rot, logn, loglen, t.logM);
+        }
+        ProfScope ps(quant ? K_CKKS_IFFT_QUANT : K_CKKS_FFT, s, bytes);
+        if (logb <= 10) hipLaunchKernelGGL((special_fft_kernel<true, 10, 256>), grid, dim3(256), 0, s, A);
+        else hipLaunchKernelGGL((special_fft_kernel<true, kCkksFftLdsLog, 1024>), grid, dim3(1024), 0, s, A);
+        return hipGetLastError();
+    }
+    {
+        ProfScope ps(K_CKKS_FFT, s, bytes);
+        if (logb <= 10) hipLaunchKernelGGL((special_fft_kernel<false, 10, 256>), grid, dim3(256), 0, s, A);
+        else hipLaunchKernelGGL((special_fft_kernel<false, kCkksFftLdsLog, 1024>), grid, dim3(1024), 0, s, A);
+    }
+    for (int loglen = logb + 1; loglen <= logn; loglen++) {
+        ProfScope ps(K_CKKS_FFT_PASS, s, bytes);
+        hipLaunchKernelGGL((ckks_fft_pass_kernel<false>), dim3((n / 2 + 255) / 256, batch), dim3(256), 0, s, out, t.roots, t.rot, logn, loglen, t.logM);
+    }
+    return hipGetLastError();
+}
+
+// the quantiser on its own: the values of a transform too large for one workgroup (src: [batch][n][2], slot order), or -- direct
+// -- the coefficient-domain Encode (Float64ToFixedPointCRT, utils.go:156-168; src: [batch][N] reals, zero-padded by the caller)
+struct F64ToRnsKArgs {
+    const double *src;
+    int logn, direct;
+    CkksQuantK q;
+};
+__global__ void __launch_bounds__(256) f64_to_rns_kernel(F64ToRnsKArgs A) {
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= (1u << A.q.logN)) return;
+    const size_t bz = blockIdx.y;
+    if (A.direct) {
+        const double value = A.src[(bz << A.q.logN) + pos];
+        const size_t N = (size_t)1 << A.q.logN;
+        ckks_quant_store(value, A.q.scale, A.q.mcQ, A.q.nQ, A.q.outQ + bz * A.q.outQ_bs, N, pos);
+        if (A.q.nP) ckks_quant_store(value, A.q.scale, A.q.mcP, A.q.nP, A.q.outP + bz * A.q.outP_bs, N, pos);
+        return;
+    }
+    const double *src = A.src + (bz << A.logn) * 2;
+    auto re = [&](unsigned p) { return src[2 * (size_t)p]; };
+    auto im = [&](unsigned p) { return A.q.standard ? src[2 * (size_t)p + 1] : 0.0; };
+    ckks_quant_pos(A.q, bz, pos, A.logn, re, im);
+}
+hipError_t launch_f64_to_rns(const double *src, int logn, bool direct, const CkksQuantArgs &q, int batch, hipStream_t s) {
+    if (!src || batch <= 0 || batch > 65535 || q.nQ < 1 || q.nQ > kMaxLimbs || q.nP < 0 || q.nP > kMaxLimbs || !q.outQ.p || (q.nP && !q.outP.p) ||
+        !no_tab({q.outQ, q.outP}))
+        return hipErrorInvalidValue;
+    if (!direct && q.logN - q.log_gap != logn + q.standard) return hipErrorInvalidValue;
+    F64ToRnsKArgs A{src, logn, direct ? 1 : 0,
+                    CkksQuantK{q.mcQ, q.mcP, q.outQ.p, q.outP.p, q.outQ.bstride, q.outP.bstride, q.nQ, q.nP, q.logN, q.log_gap, q.standard, q.scale}};
+    ProfScope ps(K_F64_TO_RNS, s, (double)(q.nQ + q.nP) * batch * (double)(1u << q.logN) * 8.0);
+    hipLaunchKernelGGL(f64_to_rns_kernel, dim3(((1u << q.logN) + 255) / 256, batch), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+// RNS -> float64 (polyToComplexCRT / polyToFloatCRT, encoder.go:924-1116, with scaleDown, scaling.go:46): per needed coefficient
+// the exact integer x mod Q from its residues -- mixed-radix (Garner) digits d_i, x = sum d_i q_0 .. q_{i-1}, by Montgomery
+// products with the table g[i][j] = MForm(q_0 .. q_{j-1} mod q_i) (j < i) and g[i][i] = MForm((q_0 .. q_{i-1})^-1 mod q_i); Horner
+// into a multi-word integer; the centring x >= Q >> 1 -> x - Q as a compare and a subtraction from Q; the round-to-nearest-even of
+// the top 53 bits with a sticky bit (big.Float.SetInt(..).Float64()); one division by the scale.  Level 0 is the same formula
+// (float64(uint64) is that rounding).  Everything is indexed by unrolled loops up to CAP limbs: registers only.
+struct RnsToF64KArgs {
+    const uint64_t *src;
+    size_t src_bs;
+    double *dst;          // batched: [batch][slots][2]; else [batch][N] ([2] when cplx)
+    const ModConst *mc;
+    const uint64_t *g;    // [kCkksDecodeMaxLimbs][kCkksDecodeMaxLimbs]
+    const uint64_t *Qw;   // [nl]: Q at this level, little-endian;  Qh = Qw + kCkksDecodeMaxLimbs: Q >> 1
+    int nl, logN, log_slots, log_gap, batched, standard, cplx;
+    double scale;
+};
+template <int CAP>
+__device__ __forceinline__ double rns_to_f64_coeff(const RnsToF64KArgs &A, const uint64_t *src) {
+    const int nl = A.nl;
+    const size_t N = (size_t)1 << A.logN;
+    uint64_t d[CAP];
+#pragma unroll
+    for (int i = 0; i < CAP; i++) {
+        d[i] = 0;
+        if (i < nl) {
+            const ModConst k = A.mc[i];
+            const uint64_t *gi = A.g + (size_t)i * kCkksDecodeMaxLimbs;
+            const uint64_t xi = bred_add(src[(size_t)i * N], k.q, k.brc0);
+            uint64_t t = 0;
+#pragma unroll
+            for (int j = 0; j < i; j++) t = cred(t + mred(d[j], ldc(gi, j), k.q, k.qinv), k.q);
+            d[i] = i == 0 ? xi : mred(cred(xi + k.q - t, k.q), ldc(gi, i), k.q, k.qinv);
+        }
+    }
+    // Horner from the top digit: X = X q_{i} + d_i
+    uint64_t X[CAP];
+#pragma unroll
+    for (int w = 0; w < CAP; w++) X[w] = 0;
+#pragma unroll
+    for (int i = CAP - 1; i >= 0; i--) {
+        if (i < nl) {
+            const uint64_t q = ldc(&A.mc[i].q, 0);
+            uint64_t carry = d[i];
+#pragma unroll
+            for (int w = 0; w < CAP - i; w++) {  // (at most nl - i words are in use)
+                const u128 p = (u128)X[w] * q + carry;
+                X[w] = (uint64_t)p;
+                carry = (uint64_t)(p >> 64);
+            }
+        }
+    }
+    // x >= Q >> 1 ?  (compare from the top word), then |x - Q| = Q - x
+    int cmp = 0;
+#pragma unroll
+    for (int w = CAP - 1; w >= 0; w--) {
+        const uint64_t h = w < nl ? ldc(A.Qw, kCkksDecodeMaxLimbs + w) : 0;
+        if (cmp == 0) cmp = X[w] > h ? 1 : (X[w] < h ? -1 : 0);
+    }
+    const bool neg = cmp >= 0;
+    if (neg) {
+        uint64_t borrow = 0;
+#pragma unroll
+        for (int w = 0; w < CAP; w++) {
+            const uint64_t qw = w < nl ? ldc(A.Qw, w) : 0;
+            const uint64_t a = qw - X[w], b = a - borrow;
+            borrow = (uint64_t)(qw < X[w]) | (uint64_t)(a < borrow);
+            X[w] = b;
+        }
+    }
+    // the two top words, the position of the top one and whether anything lies below them
+    uint64_t hi = 0, lo = 0;
+    int topw = -1;
+    bool sticky = false;
+#pragma unroll
+    for (int w = CAP - 1; w >= 0; w--) {
+        if (topw < 0) {
+            if (X[w]) { topw = w; hi = X[w]; }
+        } else if (topw == w + 1) lo = X[w];
+        else sticky |= X[w] != 0;
+    }
+    if (topw < 0) return __ddiv_rn(0.0, A.scale);
+    const int lz = __clzll((long long)hi);
+    const u128 V = (((u128)hi << 64) | lo) << lz;        // top bit at 127
+    uint64_t mant = (uint64_t)(V >> 75);                 // 53 bits
+    const bool round = (uint64_t)(V >> 74) & 1;
+    sticky |= (V & ((((u128)1) << 74) - 1)) != 0;
+    if (round && (sticky || (mant & 1))) mant++;
+    const double mag = ldexp((double)mant, 64 * (topw - 1) + 75 - lz);  // (exact: mant <= 2^53; beyond the float64 range: infinity)
+    return __ddiv_rn(neg ? -mag : mag, A.scale);
+}
+template <int CAP>
+__global__ void __launch_bounds__(64) rns_to_f64_kernel(RnsToF64KArgs A) {
+    const unsigned x = blockIdx.x * 64u + threadIdx.x;
+    const size_t bz = blockIdx.y;
+    const uint64_t *src = A.src + bz * A.src_bs;
+    if (!A.batched) {  // polyToFloatCRT: every coefficient, real
+        if (x >= (1u << A.logN)) return;
+        const double v = rns_to_f64_coeff<CAP>(A, src + x);
+        double *dst = A.dst + ((bz << A.logN) + x) * (A.cplx ? 2 : 1);
+        dst[0] = v;
+        if (A.cplx) dst[1] = 0.0;
+        return;
+    }
+    const unsigned slots = 1u << A.log_slots;
+    if (x >= slots) return;
+    double *dst = A.dst + ((bz << A.log_slots) + x) * 2;
+    dst[0] = rns_to_f64_coeff<CAP>(A, src + ((size_t)x << A.log_gap));
+    if (A.standard) dst[1] = rns_to_f64_coeff<CAP>(A, src + ((size_t)1 << (A.logN - 1)) + ((size_t)x << A.log_gap));
+    // [X]/(X^N+1) to [X+X^-1]/(X^N+1) (encoder.go:965-970): values[i] -= complex(0, real(values[slots - i])) for i >= 1 -- the real
+    // parts are never written by that loop, so the entries it reads "already updated" hold the real parts it would read before
+    else dst[1] = x == 0 ? 0.0 : __dsub_rn(0.0, rns_to_f64_coeff<CAP>(A, src + ((size_t)(slots - x) << A.log_gap)));
+}
+hipError_t launch_rns_to_f64(const RingDev &r, const CkksDecodeArgs &a, View src, double *dst, int batch, hipStream_t s) {
+    if (a.nl < 1 || a.nl > kCkksDecodeMaxLimbs || batch <= 0 || batch > 65535 || !src.p || src.tab || !dst || !a.g || !a.Qw) return hipErrorInvalidValue;
+    if (a.batched && (a.log_slots < 0 || a.log_slots + a.log_gap + a.standard != r.logN)) return hipErrorInvalidValue;
+    RnsToF64KArgs A{src.p, src.bstride, dst, r.mc, a.g, a.Qw, a.nl, r.logN, a.log_slots, a.log_gap, a.batched, a.standard, a.cplx, a.scale};
+    const unsigned count = a.batched ? 1u << a.log_slots : 1u << r.logN;
+    const dim3 grid((count + 63) / 64, batch), block(64);
+    ProfScope ps(K_RNS_TO_F64, s, (double)a.nl * batch * (double)count * 8.0);
+    if (a.nl <= 2) hipLaunchKernelGGL((rns_to_f64_kernel<2>), grid, block, 0, s, A);
+    else if (a.nl <= 4) hipLaunchKernelGGL((rns_to_f64_kernel<4>), grid, block, 0, s, A);
+    else if (a.nl <= 8) hipLaunchKernelGGL((rns_to_f64_kernel<8>), grid, block, 0, s, A);
+    else if (a.nl <= 16) hipLaunchKernelGGL((rns_to_f64_kernel<16>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((rns_to_f64_kernel<32>), grid, block, 0, s, A);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The check of go/hering/*.go that is possible without a Go toolchain: every `C.he_*(...)` call names a function
-declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h), passes as many arguments as the declaration has parameters, and -- round 4 --
+declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h), passes as many arguments as the declaration has parameters, and -- round 4 --
 every argument has the KIND the parameter wants (int / uint64_t / he_handle / he_handle* / uint64_t* / int*), judged from the
 shape of the Go expression (`C.int(..)`, `C.uint64_t(..)`, `x.h`, `&x.h`, `(*C.uint64_t)(unsafe.Pointer(..))`, identifiers whose
 declaration in the file names a Handle or a C pointer type); every `C.HE_*` constant exists in the header's enums.  Also
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_decls():
-    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h"))
+    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h"))
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls, kinds = {}, {}
     for m in re.finditer(r"\b(?:int|const char \*)\s*(he_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
@@ -121,6 +121,8 @@ BLINDROT = ["BlindRotateCore", "AutomorphismSelect"]                            
 BRIDGE = ["ComplexToReal", "RealToComplex"]                                           # schemes/ckks/bridge.go:57,104
 # bgv.Evaluator with ScaleInvariant = true (go/hering/bfv.go)
 BFV = ["MulScaleInvariant", "MulScaleInvariantNew", "MulRelinScaleInvariant", "MulRelinScaleInvariantNew"]  # schemes/bgv/evaluator.go:705-895
+# ckks.Encoder, double-precision path (go/hering/encoder.go)
+ENCODER = ["Encode", "Embed", "Decode", "DecodePublic", "FFT", "IFFT"]                # schemes/ckks/encoder.go:156-820
 SCHEMES = ["Add", "AddNew", "Sub", "SubNew", "Mul", "MulNew", "MulRelin", "MulRelinNew", "MulThenAdd", "Relinearize",
            "Rescale", "GetRLWEParameters"]                                            # schemes/schemes.go:14-28
 
@@ -185,6 +187,10 @@ def main():
     for m in BFV:
         if m not in bfv_methods:
             errors.append(f"go/hering: method {m} (bgv.Evaluator, scale-invariant) is not defined")
+    enc_methods = set(re.findall(r"func \(\w+ \*Encoder\) (\w+)\(", src))
+    for m in ENCODER:
+        if m not in enc_methods:
+            errors.append(f"go/hering: method {m} (ckks.Encoder) is not defined")
     print(f"{len(files)} Go files, {ncalls} C.he_* calls to {len(used)} of {len(decls)} declared entry points, {nchecked} of {nargs_total} "
           f"arguments kind-checked; {len(PROVIDER)} EvaluatorProvider + {len(SCHEMES)} schemes.Evaluator methods present; "
           f"rlwe.Evaluator also: {', '.join(m for m in EXTRA if m in methods)}; "
@@ -192,7 +198,8 @@ def main():
           f"rgsw.Evaluator: {', '.join(m for m in RGSW if m in rgsw_methods)}; "
           f"blindrot.Evaluator: {', '.join(m for m in BLINDROT if m in br_methods)}; "
           f"ckks.DomainSwitcher: {', '.join(m for m in BRIDGE if m in ds_methods)}; "
-          f"bgv.Evaluator (scale-invariant): {', '.join(m for m in BFV if m in bfv_methods)}"
+          f"bgv.Evaluator (scale-invariant): {', '.join(m for m in BFV if m in bfv_methods)}; "
+          f"ckks.Encoder: {', '.join(m for m in ENCODER if m in enc_methods)}"
           if not errors else "\n".join(errors))
     return 1 if errors else 0
 
