@@ -30,7 +30,10 @@ int he_map_small_to_large_ntt(he_handle polSmall, he_handle polLarge, int level)
 /* rlwe.SwitchCiphertextRingDegreeNTT on one polynomial (core/rlwe/element.go:250): the direction is set by the two degrees;
  * ringLarge (degree max(N_in, N_out)) is required for large -> small and may be 0 otherwise; equal degrees = copy.
  * Large -> small is one pass, out[j] = gap^-1 sum_{s<gap} in[j gap + s] mod q (the reference's INTT at N, stride and NTT at n,
- * word for word for inputs in [0, q)); canonical output.  Limbs 0..level. */
+ * word for word for inputs in [0, 2q): canonical words and the lazy words the reference's transforms take; four lazy words sum to
+ * at most 8q - 4 < 2^64 at q < 2^61.  Words at or above 2q are outside the domain); canonical output.  Limbs 0..level.
+ * The batch is the launch's gridDim.z, as for the other ring-level entries of hering.h: no limit is stated and none is needed
+ * (batches 65535, 65536 and 65537 are tested through the fold, the replication and both strides). */
 int he_switch_ring_degree_ntt(he_handle ringLarge, int level, he_handle in, he_handle out);
 /* rlwe.SwitchCiphertextRingDegree on one polynomial (core/rlwe/element.go:293), coefficient domain, limbs 0..level:
  * down out[w] = in[w gap]; up out[w gap] = in[w] and the other words of out are left untouched, as in the reference */

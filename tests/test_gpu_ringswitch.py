@@ -14,6 +14,7 @@ from lattigo_amd import rlwe as R
 from oracle import oracle as O
 from tests.gpu_common import ctx  # noqa: F401
 from tests.helpers import rng_for, uniform_poly
+from tests.ringmap_ref import ref_down_ntt, ref_up_ntt  # (SwitchCiphertextRingDegreeNTT and the replication, on the oracle)
 from tests.rlwe_fixtures import SecretKey, gen_evaluation_key, phase, small_to_rns
 
 pytestmark = pytest.mark.gpu
@@ -23,16 +24,6 @@ C5_LOGP = [61] * 5
 
 
 # ---- the reference's sequences of calls, on the oracle ------------------------------------------------------------------------
-def ref_down_ntt(a, q, N, gap, ci):
-    """SwitchCiphertextRingDegreeNTT, N -> N / gap, on [limbs, N] (element.go:260-279)"""
-    big, small = O.Ring(N, q[: a.shape[0]], ci), O.Ring(N // gap, q[: a.shape[0]], ci)
-    return small.NTT(big.INTT(a)[:, ::gap].copy())
-
-
-def ref_up_ntt(a, gap):
-    return np.repeat(a, gap, axis=1)
-
-
 def ref_apply(oev, oQ, level, ct, oevk, ci):
     """applyEvaluationKey at the evaluator's degree: GadgetProduct(ct[1]) -> (Add(ct[0], .[0]), .[1])"""
     gp = oev.GadgetProduct(level, ct[1][: level + 1], oevk)
