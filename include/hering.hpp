@@ -21,6 +21,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -32,6 +33,7 @@
 #include "hering_bridge.h"
 #include "hering_bfv.h"
 #include "hering_ckks_encoder.h"
+#include "hering_bgv_encoder.h"
 
 namespace hering {
 
@@ -860,6 +862,72 @@ public:
     void MulRelinScaleInvariant(const Ciphertext &op0, const Ciphertext &op1, Ciphertext &opOut) const { tensor(op0, op1, true, opOut); }
     // quantize (:1050) as a piece: c2Q1 on Q, c2Q2 on QMul at levelQMul, NTT domain; the result replaces c2Q1 as in the reference
     void Quantize(int level, Poly &c2Q1, const Poly &c2Q2) const { check(he_bfv_quantize(h(), level, c2Q1.h(), c2Q2.h(), c2Q1.h())); }
+};
+
+// bgv.Encoder (schemes/bgv/encoder.go; hering_bgv_encoder.h).  A plaintext is a Poly plus the fields of rlwe.MetaData the reference
+// reads; value vectors are std::vector<uint64_t> ([]uint64) or std::vector<int64_t> ([]int64), [batch][n] flattened (batch = the
+// polynomial's); decoded vectors are [batch][MaxSlots].
+struct MetaData {
+    uint64_t Scale = 1;
+    bool IsBatched = true, IsNTT = true, IsMontgomery = false;
+};
+class Encoder {
+    detail::Ref r_;
+    int info_[4] = {0, 0, 0, 0};
+    static const uint64_t *up(const std::vector<uint64_t> &v) { return v.data(); }
+    static const uint64_t *up(const std::vector<int64_t> &v) { return reinterpret_cast<const uint64_t *>(v.data()); }
+    static uint64_t *up(std::vector<uint64_t> &v) { return v.data(); }
+    static uint64_t *up(std::vector<int64_t> &v) { return reinterpret_cast<uint64_t *>(v.data()); }
+    template <class V> static constexpr int is_signed() { return std::is_same<typename V::value_type, int64_t>::value ? 1 : 0; }
+
+public:
+    // NewEncoder (:49): ringT = Parameters.RingT(); ringP for EncodeQP and RingT2Q into ringP only
+    Encoder(const Ring &ringQ, const Ring &ringT, const Ring *ringP = nullptr) {
+        he_handle h = 0;
+        check(he_bgv_encoder_create(ringQ.h(), ringP ? ringP->h() : 0, ringT.h(), &h));
+        r_ = detail::own(h, he_bgv_encoder_destroy);
+        check(he_bgv_encoder_info(h, info_));
+    }
+    he_handle h() const { return r_->h; }
+    int LogMaxSlots() const { return info_[0]; }
+    int MaxSlots() const { return 1 << info_[0]; }
+    int LogGap() const { return info_[1]; }
+    int RingQ2TMaxLimbs() const { return info_[2]; }
+    std::vector<uint64_t> IndexMatrix() const {  // permuteMatrix (:110)
+        std::vector<uint64_t> out((size_t)MaxSlots());
+        check(he_bgv_encoder_index(h(), out.data()));
+        return out;
+    }
+    // EncodeRingT (:203) / DecodeRingT (:341): V = std::vector<uint64_t> or std::vector<int64_t>
+    template <class V> void EncodeRingT(const V &values, uint64_t scale, Poly &pT) const {
+        check(he_bgv_encode_ring_t(h(), scale, up(values), values.size() / pT.Batch(), is_signed<V>(), pT.Batch(), pT.h()));
+    }
+    template <class V> void DecodeRingT(const Poly &pT, uint64_t scale, V &values) const {
+        values.resize((size_t)pT.Batch() * MaxSlots());
+        check(he_bgv_decode_ring_t(h(), scale, pT.h(), is_signed<V>(), up(values)));
+    }
+    // RingT2Q (:378; toP: pQ is a polynomial of ringP) / RingQ2T (:412)
+    void RingT2Q(int level, bool scaleUp, const Poly &pT, Poly &pQ, bool toP = false) const {
+        check(he_bgv_ring_t2q(h(), level, scaleUp, toP, pT.h(), pQ.h()));
+    }
+    void RingQ2T(int level, bool scaleDown, const Poly &pQ, Poly &pT) const { check(he_bgv_ring_q2t(h(), level, scaleDown, pQ.h(), pT.h())); }
+    // Encode (:143), and EmbedScale (:268) into a ring.Poly: Embed (:336) is scaleUp = false
+    template <class V> void Encode(const V &values, const MetaData &m, Poly &pt) const { EmbedScale(values, true, m, pt, m.IsBatched); }
+    template <class V> void Embed(const V &values, const MetaData &m, Poly &polyOut) const { EmbedScale(values, false, m, polyOut); }
+    template <class V> void EmbedScale(const V &values, bool scaleUp, const MetaData &m, Poly &polyOut, bool batched = true) const {
+        check(he_bgv_encode(h(), polyOut.Level(), m.Scale, batched, m.IsNTT, m.IsMontgomery, scaleUp, up(values), values.size() / polyOut.Batch(),
+                            is_signed<V>(), polyOut.Batch(), polyOut.h()));
+    }
+    // EmbedScale into a ringqp.Poly (:280-311)
+    template <class V> void EncodeQP(const V &values, bool scaleUp, const MetaData &m, Poly &polyQ, Poly &polyP) const {
+        check(he_bgv_encode_qp(h(), polyQ.Level(), polyP.Level(), m.Scale, m.IsNTT, m.IsMontgomery, scaleUp, up(values), values.size() / polyQ.Batch(),
+                               is_signed<V>(), polyQ.Batch(), polyQ.h(), polyP.h()));
+    }
+    // Decode (:470)
+    template <class V> void Decode(const Poly &pt, const MetaData &m, V &values) const {
+        values.resize((size_t)pt.Batch() * MaxSlots());
+        check(he_bgv_decode(h(), pt.Level(), m.Scale, m.IsBatched, m.IsNTT, pt.h(), is_signed<V>(), up(values)));
+    }
 };
 }  // namespace bgv
 

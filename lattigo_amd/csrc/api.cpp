@@ -21,6 +21,7 @@
 #include <memory>
 #include <tuple>
 #include <mutex>
+#include <numeric>
 #include <shared_mutex>
 #include <string>
 #include <thread>
@@ -42,6 +43,7 @@
 #include "../../include/hering_bridge.h"
 #include "../../include/hering_bfv.h"
 #include "../../include/hering_ckks_encoder.h"
+#include "../../include/hering_bgv_encoder.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -75,7 +77,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC };
 
 struct Obj {
     ObjType type;
@@ -4944,6 +4946,363 @@ int he_ckks_decode(he_handle h, int level, int log_slots, double scale, int is_b
     if (is_complex) memcpy(values, host.data(), words * 8);
     else for (size_t i = 0; i < words / 2; i++) values[i] = host[2 * i];
     return HE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// BGV / BFV encoder: Encode / Decode, EncodeRingT / DecodeRingT, RingT2Q / RingQ2T (include/hering_bgv_encoder.h;
+// schemes/bgv/encoder.go)
+// ---------------------------------------------------------------------------------------
+// Encoder (encoder.go:27-46) beside its rings.  On the device: the index matrix and its inverse, the Garner table with the words of
+// Q and Q >> 1 per level, the constants of GenModUpConstants(Q[:level + 1], {T}) per level.  On the host: what the launches take as
+// kernel arguments.  The entries run like he_poly_upload / he_poly_download: the calling thread's queued requests first (Scope),
+// the launches straight on the context's stream, and the call returns when they are done.
+struct BgvEncoder : Obj {
+    std::shared_ptr<Ring> Q, P, T;
+    int log_gap = 0;
+    uint64_t t = 0;
+    std::vector<uint64_t> perm;                // permuteMatrix(logN_T)
+    uint32_t *d_perm = nullptr;                // [N_T] perm | [N_T] its inverse
+    std::vector<uint64_t> tinvQ, tinvP;        // T^-1 mod q_i / p_j
+    std::vector<uint64_t> tmodQ;               // MForm(T mod q_i)
+    int q2t_levels = 0;                        // levels he_bgv_ring_q2t serves: min(limbs of Q, 32)
+    uint64_t *d_garner = nullptr;              // as CkksEncoder::d_garner
+    ConstPool pool;
+    std::vector<ModUpRef> up;                  // [level], level >= 1
+    std::vector<std::vector<uint64_t>> halfQ;  // [level][i]: (Q_level >> 1) mod q_i
+    std::vector<uint64_t> halfT, qmodT;        // [level]: (Q_level >> 1) mod T, Q_level mod T
+    std::vector<uint64_t> prodT;               // [i]: MForm_T(q_0 .. q_{i-1} mod T)
+    BgvEncoder() : Obj(T_BGV_ENC) {}
+    ~BgvEncoder() override {
+        hipSetDevice(Q->ctx->dev);
+        hipStreamSynchronize(Q->ctx->stream);
+        if (d_perm) hipFree(d_perm);
+        if (d_garner) hipFree(d_garner);
+        pool.release();
+    }
+    int NT() const { return T->N; }
+    const uint32_t *perm_dev() const { return d_perm; }
+    const uint32_t *inv_dev() const { return d_perm + T->N; }
+    const ModConst *mcT() const { return T->dev.mc; }
+    uint64_t mont_t(uint64_t x) const { return to_mont(x % t, t); }
+};
+// permuteMatrix (encoder.go:110-133)
+static std::vector<uint64_t> bgv_permute_matrix(int logN) {
+    const uint64_t N = 1ull << logN, mask = 2 * N - 1;
+    std::vector<uint64_t> perm(N);
+    uint64_t pow = 1;
+    for (uint64_t i = 0, j = N >> 1; i < (N >> 1); i++, j++) {
+        uint64_t x = pow >> 1, pos = 0;  // BitReverse64(pow >> 1, logN)
+        for (int b = 0; b < logN; b++, x >>= 1) pos = (pos << 1) | (x & 1);
+        perm[i] = pos;
+        perm[j] = N - pos - 1;
+        pow = (pow * 5) & mask;
+    }
+    return perm;
+}
+int he_bgv_encoder_create(he_handle hq, he_handle hp, he_handle ht, he_handle *out) {
+    static const char *who = "he_bgv_encoder_create";
+    GET(Q, Ring, hq, T_RING);
+    GET(T, Ring, ht, T_RING);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    auto e = std::make_shared<BgvEncoder>();
+    e->Q = Q; e->T = T;
+    if (hp) {
+        e->P = get<Ring>(hp, T_RING);
+        if (!e->P) return fail(HE_EHANDLE, "%s: bad ringP handle", who);
+        if (e->P->ctx != Q->ctx || e->P->N != Q->N || e->P->type != 0)
+            return fail(HE_EINVAL, "%s: ringP must share the context and degree of ringQ and be of the standard type", who);
+    }
+    if (T->ctx != Q->ctx) return fail(HE_EINVAL, "%s: ringT belongs to another context", who);
+    if (Q->type != 0 || T->type != 0) return fail(HE_EINVAL, "%s: the rings must be of the standard type", who);
+    if (T->nmod() != 1) return fail(HE_EINVAL, "%s: ringT has %d moduli, exactly one expected", who, T->nmod());
+    const uint64_t t = T->moduli[0];
+    e->t = t;
+    const int want = std::min(Q->logN, (int)__builtin_ctzll(t - 1) - 1);  // params.go:120-123
+    if (T->logN != want) return fail(HE_EINVAL, "%s: ringT has logN %d, min(logN_Q, v2(T - 1) - 1) = %d expected", who, T->logN, want);
+    for (const Ring *r : {Q.get(), e->P.get()})
+        if (r)
+            for (uint64_t q : r->moduli)
+                if (std::gcd(q, t) != 1) return fail(HE_EINVAL, "%s: the plaintext modulus %llu is not coprime to the modulus %llu", who,
+                                                     (unsigned long long)t, (unsigned long long)q);
+    e->log_gap = Q->logN - T->logN;
+    e->perm = bgv_permute_matrix(T->logN);
+    const size_t NT = (size_t)T->N;
+    std::vector<uint32_t> tab(2 * NT);
+    for (size_t i = 0; i < NT; i++) { tab[i] = (uint32_t)e->perm[i]; tab[NT + e->perm[i]] = (uint32_t)i; }
+    for (uint64_t q : Q->moduli) { e->tinvQ.push_back(invmod(t % q, q)); e->tmodQ.push_back(to_mont(t % q, q)); }
+    if (e->P) for (uint64_t p : e->P->moduli) e->tinvP.push_back(invmod(t % p, p));
+    e->q2t_levels = std::min(Q->nmod(), kBgvQ2TMaxLimbs);
+    std::vector<uint64_t> g = build_garner_table(Q->moduli, kCkksDecodeMaxLimbs);
+    e->up.resize(e->q2t_levels); e->halfQ.resize(e->q2t_levels); e->halfT.resize(e->q2t_levels); e->qmodT.resize(e->q2t_levels);
+    uint64_t prod = 1;
+    for (int l = 0; l < e->q2t_levels; l++) {
+        const std::vector<uint64_t> S(Q->moduli.begin(), Q->moduli.begin() + l + 1);
+        const std::vector<uint64_t> w = product_and_half_words(Q->moduli, l + 1, kCkksDecodeMaxLimbs);
+        g.insert(g.end(), w.begin(), w.end());
+        e->prodT.push_back(to_mont(prod, t));
+        prod = mulmod(prod, Q->moduli[l] % t, t);
+        e->qmodT[l] = prod;
+        e->halfT[l] = half_product_mod(S, t);
+        for (int i = 0; i <= l; i++) e->halfQ[l].push_back(half_product_mod(S, Q->moduli[i]));
+        if (l >= 1) e->up[l] = pool_modup(e->pool, S, {t});  // encoder.go:62
+    }
+    Scope sc(Q->ctx.get());
+    HIP_TRY(hipMalloc((void **)&e->d_perm, tab.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(e->d_perm, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void **)&e->d_garner, g.size() * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(e->d_garner, g.data(), g.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TRY(e->pool.upload());
+    *out = reg(e);
+    return HE_OK;
+}
+int he_bgv_encoder_destroy(he_handle h) { return unreg(h, T_BGV_ENC); }
+int he_bgv_encoder_info(he_handle h, int out[4]) {
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    if (!out) return fail(HE_EINVAL, "he_bgv_encoder_info: null output");
+    out[0] = e->T->logN; out[1] = e->log_gap; out[2] = kBgvQ2TMaxLimbs; out[3] = 0;
+    return HE_OK;
+}
+int he_bgv_encoder_index(he_handle h, uint64_t *out) {
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    if (!out) return fail(HE_EINVAL, "he_bgv_encoder_index: null output");
+    Scope sc(e->Q->ctx.get());
+    std::vector<uint32_t> tab(e->NT());
+    HIP_TRY(hipMemcpy(tab.data(), e->d_perm, tab.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < tab.size(); i++) out[i] = tab[i];
+    return HE_OK;
+}
+// an operand of an encoder entry: a polynomial of `ring`'s degree and the encoder's context with `limbs` limbs, `batch` entries (< 0: any)
+static int bgv_poly(const BgvEncoder &e, const Ring &ring, he_handle h, int limbs, int batch, const char *name, const char *who,
+                    std::shared_ptr<Poly> *out) {
+    auto p = get<Poly>(h, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad polynomial handle for %s", who, name);
+    if (p->ctx != e.Q->ctx) return fail(HE_EINVAL, "%s: %s belongs to another context", who, name);
+    if (p->N != ring.N) return fail(HE_EINVAL, "%s: %s has degree %d, %d expected", who, name, p->N, ring.N);
+    if (p->nlimbs < limbs) return fail(HE_EINVAL, "%s: %s has %d limbs, %d needed", who, name, p->nlimbs, limbs);
+    if (batch >= 0 && p->batch != batch) return fail(HE_EINVAL, "%s: batch mismatch (%s has %d entries, %d expected)", who, name, p->batch, batch);
+    if (p->batch > 65535) return fail(HE_EINVAL, "%s: %s has %d entries, at most 65535 per call", who, name, p->batch);
+    *out = p;
+    return HE_OK;
+}
+static int bgv_scale(const BgvEncoder &e, uint64_t scale, const char *who) {
+    if (scale < 1 || scale >= e.t) return fail(HE_EINVAL, "%s: the scale (%llu) must be in [1, T)", who, (unsigned long long)scale);
+    return HE_OK;
+}
+static int bgv_values(const BgvEncoder &e, const uint64_t *values, size_t n_values, int batch, const char *who) {
+    if (batch < 1 || batch > 65535) return fail(HE_EINVAL, "%s: batch %d outside [1, 65535]", who, batch);
+    if (!values || n_values == 0) return fail(HE_EINVAL, "%s: no values", who);
+    if (n_values > (size_t)e.NT())  // encoder.go:163-165, :216-218
+        return fail(HE_EINVAL, "%s: len(values)=%zu > slots=%d", who, n_values, e.NT());
+    return HE_OK;
+}
+static int bgv_not_capturing(Ctx &c, const char *who) {
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+    return HE_OK;
+}
+// the launches of RingT2Q into limbs 0..level of oq (and 0..level_p of op): one fan-out; scale: the MulScalar of EncodeRingT folded in (0: none)
+static int bgv_fanout(const BgvEncoder &e, View pT, uint64_t scale, bool scale_up, bool mont, const Ring *rq, const Poly *oq, int level_q,
+                      const Ring *rp, const Poly *op, int level_p, bool q_is_p, int batch) {
+    BgvFanoutArgs fa;
+    auto constant = [&](uint64_t tinv, uint64_t q) {
+        const uint64_t k = scale_up ? tinv : 1;
+        return to_mont(mont ? to_mont(k, q) : k, q);
+    };
+    fa.mcQ = rq->dev.mc; fa.outQ = oq->view(); fa.nQ = level_q + 1;
+    for (int i = 0; i <= level_q; i++) fa.cQ[i] = constant((q_is_p ? e.tinvP : e.tinvQ)[i], rq->moduli[i]);
+    if (op) {
+        fa.mcP = rp->dev.mc; fa.outP = op->view(); fa.nP = level_p + 1;
+        for (int i = 0; i <= level_p; i++) fa.cP[i] = constant(e.tinvP[i], rp->moduli[i]);
+    }
+    fa.logN = e.Q->logN; fa.log_gap = e.log_gap;
+    fa.scale_t = scale ? e.mont_t(scale) : 0;
+    HIP_TRY(launch_bgv_t_to_rns(e.mcT(), pT, fa, batch, e.Q->ctx->stream));
+    return HE_OK;
+}
+// values (host) -> dT (ring T, [batch][N_T]) on the stream: the upload and the scatter; inv: through the index matrix
+static int bgv_scatter(const BgvEncoder &e, const uint64_t *values, size_t n_values, bool is_signed, bool through_index, uint64_t *d_vals, View dT,
+                       int batch) {
+    Ctx &c = *e.Q->ctx;
+    HIP_TRY(hipMemcpyAsync(d_vals, values, (size_t)batch * n_values * 8, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(launch_bgv_slots_to_t(e.mcT(), through_index ? e.inv_dev() : nullptr, d_vals, n_values, is_signed, dT, e.T->logN, batch, c.stream));
+    return HE_OK;
+}
+int he_bgv_encode_ring_t(he_handle h, uint64_t scale, const uint64_t *values, size_t n_values, int is_signed, int batch, he_handle hpT) {
+    static const char *who = "he_bgv_encode_ring_t";
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    TRY(bgv_scale(*e, scale, who));
+    TRY(bgv_values(*e, values, n_values, batch, who));
+    std::shared_ptr<Poly> pT;
+    TRY(bgv_poly(*e, *e->T, hpT, 1, batch, "pT", who, &pT));
+    Ctx &c = *e->Q->ctx;
+    TRY(bgv_not_capturing(c, who));
+    Scope sc(&c);
+    TRY(c.arena_reserve((size_t)batch * n_values + 8));
+    uint64_t *d_vals = c.arena_take((size_t)batch * n_values);
+    TRY(bgv_scatter(*e, values, n_values, is_signed != 0, true, d_vals, pT->view(), batch));
+    HIP_TRY(ring_ntt(*e->T, ident_tab(1), pT->view(), pT->view(), batch, true, 0));  // :258
+    ScalarTab st;
+    st.s[0] = e->mont_t(scale);
+    HIP_TRY(launch_ew(e->T->dev, ident_tab(1), EW_MUL_SCALAR_MONT, pT->view(), pT->view(), pT->view(), batch, &st, nullptr, c.stream));  // :259
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+// dT (ring T, scratch, [B][N_T]) -> values (host): [the NTT and the gather through the index matrix | the plain copy], centred when signed
+static int bgv_gather(const BgvEncoder &e, View dT, bool through_index, bool is_signed, uint64_t *d_vals, uint64_t *values, int B) {
+    Ctx &c = *e.Q->ctx;
+    if (through_index) HIP_TRY(ring_ntt(*e.T, ident_tab(1), dT, dT, B, false, 0));  // :347
+    HIP_TRY(launch_bgv_t_to_slots(e.mcT(), through_index ? e.perm_dev() : nullptr, dT, is_signed, d_vals, e.T->logN, B, c.stream));
+    HIP_TRY(hipMemcpyAsync(values, d_vals, (size_t)B * e.NT() * 8, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+int he_bgv_decode_ring_t(he_handle h, uint64_t scale, he_handle hpT, int is_signed, uint64_t *values) {
+    static const char *who = "he_bgv_decode_ring_t";
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    TRY(bgv_scale(*e, scale, who));
+    if (!values) return fail(HE_EINVAL, "%s: null output", who);
+    std::shared_ptr<Poly> pT;
+    TRY(bgv_poly(*e, *e->T, hpT, 1, -1, "pT", who, &pT));
+    Ctx &c = *e->Q->ctx;
+    TRY(bgv_not_capturing(c, who));
+    const int B = pT->batch;
+    const size_t w = (size_t)B * e->NT();
+    Scope sc(&c);
+    TRY(c.arena_reserve(2 * w + 8));
+    const View dT{c.arena_take(w), (size_t)e->NT()};
+    uint64_t *d_vals = c.arena_take(w);
+    ScalarTab st;
+    st.s[0] = e->mont_t(invmod(scale, e->t));  // :346
+    HIP_TRY(launch_ew(e->T->dev, ident_tab(1), EW_MUL_SCALAR_MONT, pT->view(), pT->view(), dT, B, &st, nullptr, c.stream));
+    return bgv_gather(*e, dT, true, is_signed != 0, d_vals, values, B);
+}
+int he_bgv_ring_t2q(he_handle h, int level, int scale_up, int to_p, he_handle hpT, he_handle hout) {
+    static const char *who = "he_bgv_ring_t2q";
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    if (to_p && !e->P) return fail(HE_EINVAL, "%s: the encoder has no ringP", who);
+    const Ring &r = to_p ? *e->P : *e->Q;
+    TRY(check_level(r, level, who));
+    if (level + 1 > kMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs, at most %d per call", who, level + 1, kMaxLimbs);
+    std::shared_ptr<Poly> pT, po;
+    TRY(bgv_poly(*e, *e->T, hpT, 1, -1, "pT", who, &pT));
+    TRY(bgv_poly(*e, r, hout, level + 1, pT->batch, "pOut", who, &po));
+    Ctx &c = *e->Q->ctx;
+    TRY(bgv_not_capturing(c, who));
+    Scope sc(&c);
+    TRY(bgv_fanout(*e, pT->view(), 0, scale_up != 0, false, &r, po.get(), level, nullptr, nullptr, -1, to_p != 0, pT->batch));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+// RingQ2T of src (coefficient domain, limbs 0..level) into dT; post: MForm_T of the factor that follows (0: none)
+static int bgv_q2t(const BgvEncoder &e, int level, bool scale_down, uint64_t post, View src, View dT, int B) {
+    BgvQ2TArgs a;
+    a.nl = level + 1; a.log_gap = e.log_gap; a.post = post;
+    a.half_t = e.halfT[level]; a.q_mod_t = e.qmodT[level];
+    a.g = e.d_garner;
+    a.Qw = e.d_garner + (size_t)kCkksDecodeMaxLimbs * kCkksDecodeMaxLimbs + (size_t)level * 2 * kCkksDecodeMaxLimbs;
+    for (int i = 0; i <= level; i++) {
+        a.pre[i] = scale_down ? e.tmodQ[i] : 0;
+        a.half_q[i] = e.halfQ[level][i];
+        a.prod_t[i] = e.prodT[i];
+    }
+    for (int i = level + 1; i < kBgvQ2TMaxLimbs; i++) a.pre[i] = a.half_q[i] = a.prod_t[i] = 0;
+    const ModUpDev up = level >= 1 ? e.up[level].on(e.pool) : ModUpDev{0, 0, nullptr, nullptr, nullptr};
+    HIP_TRY(launch_bgv_rns_to_t(e.Q->dev, e.mcT(), up, a, src, dT, e.T->logN, B, e.Q->ctx->stream));
+    return HE_OK;
+}
+static int bgv_q2t_level(const BgvEncoder &e, int level, const char *who) {
+    TRY(check_level(*e.Q, level, who));
+    if (level + 1 > kBgvQ2TMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs, at most %d are reconstructed", who, level + 1, kBgvQ2TMaxLimbs);
+    return HE_OK;
+}
+int he_bgv_ring_q2t(he_handle h, int level, int scale_down, he_handle hpQ, he_handle hpT) {
+    static const char *who = "he_bgv_ring_q2t";
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    TRY(bgv_q2t_level(*e, level, who));
+    std::shared_ptr<Poly> pQ, pT;
+    TRY(bgv_poly(*e, *e->Q, hpQ, level + 1, -1, "pQ", who, &pQ));
+    TRY(bgv_poly(*e, *e->T, hpT, 1, pQ->batch, "pT", who, &pT));
+    Ctx &c = *e->Q->ctx;
+    TRY(bgv_not_capturing(c, who));
+    Scope sc(&c);
+    TRY(bgv_q2t(*e, level, scale_down != 0, 0, pQ->view(), pT->view(), pQ->batch));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+// Encode / Embed into outQ (and outP when level_p >= 0)
+static int bgv_encode(const char *who, he_handle h, int level_q, int level_p, uint64_t scale, bool batched, bool is_ntt, bool is_mont, bool scale_up,
+                      const uint64_t *values, size_t n_values, bool is_signed, int batch, he_handle hq, he_handle hp) {
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    const Ring &Q = *e->Q;
+    TRY(check_level(Q, level_q, who));
+    if (level_q + 1 > kMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs, at most %d per call", who, level_q + 1, kMaxLimbs);
+    if (level_p >= 0) {
+        if (!e->P) return fail(HE_EINVAL, "%s: the encoder has no ringP", who);
+        TRY(check_level(*e->P, level_p, who));
+        if (level_p + 1 > kMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs, at most %d per call", who, level_p + 1, kMaxLimbs);
+        if (hp == hq) return fail(HE_EINVAL, "%s: outP is outQ", who);
+    }
+    if (!batched && e->log_gap != 0)  // the reference handles only the first N_T of N words there (encoder.go:191)
+        return fail(HE_EINVAL, "%s: the coefficient encoding needs N_T = N_Q (N_T = %d, N_Q = %d)", who, e->NT(), Q.N);
+    TRY(bgv_scale(*e, scale, who));
+    TRY(bgv_values(*e, values, n_values, batch, who));
+    std::shared_ptr<Poly> oq, op;
+    TRY(bgv_poly(*e, Q, hq, level_q + 1, batch, "outQ", who, &oq));
+    if (level_p >= 0) TRY(bgv_poly(*e, *e->P, hp, level_p + 1, batch, "outP", who, &op));
+    Ctx &c = *Q.ctx;
+    TRY(bgv_not_capturing(c, who));
+    const size_t wT = (size_t)batch * e->NT(), wV = (size_t)batch * n_values;
+    Scope sc(&c);
+    TRY(c.arena_reserve(wT + wV + 8));
+    const View dT{c.arena_take(wT), (size_t)e->NT()};
+    uint64_t *d_vals = c.arena_take(wV);
+    TRY(bgv_scatter(*e, values, n_values, is_signed, batched, d_vals, dT, batch));
+    if (batched) HIP_TRY(ring_ntt(*e->T, ident_tab(1), dT, dT, batch, true, 0));  // :258
+    // :259 / :191 (MulScalar modulo T), RingT2Q and, batched, MForm (:292, :308, :325) in one launch; not batched: no MForm
+    TRY(bgv_fanout(*e, dT, scale, scale_up, batched && is_mont, &Q, oq.get(), level_q, e->P.get(), op.get(), level_p, false, batch));
+    if (is_ntt) {
+        HIP_TRY(ring_ntt(Q, ident_tab(level_q + 1), oq->view(), oq->view(), batch, false, 0));
+        if (op) HIP_TRY(ring_ntt(*e->P, ident_tab(level_p + 1), op->view(), op->view(), batch, false, 0));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+int he_bgv_encode(he_handle enc, int level, uint64_t scale, int is_batched, int is_ntt, int is_montgomery, int scale_up, const uint64_t *values,
+                  size_t n_values, int is_signed, int batch, he_handle outQ) {
+    return bgv_encode("he_bgv_encode", enc, level, -1, scale, is_batched != 0, is_ntt != 0, is_montgomery != 0, scale_up != 0, values, n_values,
+                      is_signed != 0, batch, outQ, 0);
+}
+int he_bgv_encode_qp(he_handle enc, int level_q, int level_p, uint64_t scale, int is_ntt, int is_montgomery, int scale_up, const uint64_t *values,
+                     size_t n_values, int is_signed, int batch, he_handle outQ, he_handle outP) {
+    return bgv_encode("he_bgv_encode_qp", enc, level_q, level_p < 0 ? -1 : level_p, scale, true, is_ntt != 0, is_montgomery != 0, scale_up != 0, values,
+                      n_values, is_signed != 0, batch, outQ, outP);
+}
+int he_bgv_decode(he_handle h, int level, uint64_t scale, int is_batched, int is_ntt, he_handle hpt, int is_signed, uint64_t *values) {
+    static const char *who = "he_bgv_decode";
+    GET(e, BgvEncoder, h, T_BGV_ENC);
+    const Ring &Q = *e->Q;
+    TRY(bgv_q2t_level(*e, level, who));
+    if (!is_batched && e->log_gap != 0)  // encoder.go:496-518
+        return fail(HE_EINVAL, "%s: the coefficient encoding needs N_T = N_Q (N_T = %d, N_Q = %d)", who, e->NT(), Q.N);
+    TRY(bgv_scale(*e, scale, who));
+    if (!values) return fail(HE_EINVAL, "%s: null output", who);
+    std::shared_ptr<Poly> pt;
+    TRY(bgv_poly(*e, Q, hpt, level + 1, -1, "pt", who, &pt));
+    Ctx &c = *Q.ctx;
+    TRY(bgv_not_capturing(c, who));
+    const int B = pt->batch;
+    const size_t sQ = (size_t)(level + 1) * Q.N, wT = (size_t)B * e->NT();
+    Scope sc(&c);
+    TRY(c.arena_reserve(2 * wT + (is_ntt ? (size_t)B * sQ : 0) + 8));
+    const View dT{c.arena_take(wT), (size_t)e->NT()};
+    uint64_t *d_vals = c.arena_take(wT);
+    View src = pt->view();
+    if (is_ntt) {  // :481-487
+        const View x{c.arena_take((size_t)B * sQ), sQ};
+        HIP_TRY(ring_ntt(Q, ident_tab(level + 1), src, x, B, true, NTT_REDUCE_INPUT));
+        src = x;
+    }
+    TRY(bgv_q2t(*e, level, true, e->mont_t(invmod(scale, e->t)), src, dT, B));  // RingQ2T, then the MulScalar of :346 / :496
+    return bgv_gather(*e, dT, is_batched != 0, is_signed != 0, d_vals, values, B);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -452,6 +452,52 @@ struct CkksDecodeArgs {
 };
 hipError_t launch_rns_to_f64(const RingDev &r, const CkksDecodeArgs &a, View src, double *dst, int batch, hipStream_t s);
 
+// ---- BGV / BFV encoder (schemes/bgv/encoder.go; include/hering_bgv_encoder.h) ------------------------------------------------
+// ringT is a ring of one modulus T and degree n_t = 2^logNT; mcT: its resident modulus record.  No entry tables anywhere here.
+constexpr int kBgvQ2TMaxLimbs = 32;  // the [32]uint64 of reconstructRNS (ring/basis_extension.go:550)
+// Slots -> ring T (EncodeRingT :214-255 before its transform): dst[b][j] = reduce(values[b][inv[j]]) when inv[j] < n_values, else 0,
+// for every j < n_t -- one thread per word of the polynomial, so the stores are contiguous and every word is written.  inv: the
+// inverse of the index matrix (device, uint32 [n_t]); null: the identity (the coefficient encoding).  values: device, [batch][n_values].
+// is_signed: the sign / BRedAdd sequence of :237-244 in wrapping arithmetic; a negative multiple of T gives 0.
+hipError_t launch_bgv_slots_to_t(const ModConst *mcT, const uint32_t *inv, const uint64_t *values, size_t n_values, bool is_signed, View dst,
+                                 int logNT, int batch, hipStream_t s);
+// Ring T -> slots (DecodeRingT :349-368 after its transform): values[b][i] = src[b][perm[i]] for i < n_t, centred
+// (v >= T >> 1 -> v - T) when is_signed.  perm: the index matrix (device, uint32 [n_t]); null: the identity.
+hipError_t launch_bgv_t_to_slots(const ModConst *mcT, const uint32_t *perm, View src, bool is_signed, uint64_t *values, int logNT, int batch,
+                                 hipStream_t s);
+// Ring T -> RNS fan-out (RingT2Q :378-407 with the MulScalar of EncodeRingT :259 in front and MForm behind): word c of src (read
+// once) becomes c' = MRed(c, scale_t) modulo T (scale_t = MForm_T(scale); 0: c' = c), and coefficient j << log_gap of limb i of
+// outQ (nQ limbs, records mcQ[0..nQ)) is MRed(c', cQ[i]) modulo q_i, canonical for ANY 64-bit c' -- cQ[i] = MForm(k_i) for the
+// factor k_i wanted (1, T^-1 mod q_i, times 2^64 for a Montgomery-form output).  The words between and after the strides are 0.
+// outP (nP limbs, mcP, cP): the same from the same read; nP = 0: none.
+struct BgvFanoutArgs {
+    const ModConst *mcQ = nullptr, *mcP = nullptr;
+    View outQ{nullptr, 0}, outP{nullptr, 0};
+    int nQ = 0, nP = 0;
+    int logN = 0, log_gap = 0;
+    uint64_t scale_t = 0;
+    uint64_t cQ[kMaxLimbs], cP[kMaxLimbs];
+};
+hipError_t launch_bgv_t_to_rns(const ModConst *mcT, View src, const BgvFanoutArgs &a, int batch, hipStream_t s);
+// RNS -> ring T (RingQ2T :412-467, with the MulScalar of DecodeRingT :346 / Decode :496 behind it): one thread per coefficient j of
+// ringT reads coefficient j << log_gap of the nl limbs of src (records r.mc[0..nl)) and writes dst[b][j], canonical modulo T.
+//   pre[i] != 0 (scale_down): the word is first MRed(word, pre[i]), pre[i] = MForm(T mod q_i);
+//   nl = 1: the level-0 lane (:447-465), word for word;
+//   nl > 1, log_gap = 0: CRed(x_i + half_q[i]), reconstructRNS' float sum and multSum into T with `up` (GenModUpConstants(Q[:nl],
+//   {T}) resident), minus half_t, as modup_kernel does them helper by helper; the result reduced to [0, T);
+//   nl > 1, log_gap > 0: the Garner digits of rns_to_f64_kernel (g / Qw as in CkksDecodeArgs), x = sum d_i q_0 .. q_{i-1} compared with
+//   Q >> 1; the word is sum MRed(d_i, prod_t[i]) - [x >= Q >> 1] q_mod_t modulo T, prod_t[i] = MForm_T(q_0 .. q_{i-1} mod T);
+//   post != 0: the result times post * 2^-64 modulo T (post = MForm_T(scale^-1)).
+struct BgvQ2TArgs {
+    int nl = 0, log_gap = 0;
+    uint64_t post = 0;
+    uint64_t half_t = 0, q_mod_t = 0;
+    const uint64_t *g = nullptr, *Qw = nullptr;
+    uint64_t pre[kBgvQ2TMaxLimbs], half_q[kBgvQ2TMaxLimbs], prod_t[kBgvQ2TMaxLimbs];
+};
+hipError_t launch_bgv_rns_to_t(const RingDev &r, const ModConst *mcT, const ModUpDev &up, const BgvQ2TArgs &a, View src, View dst, int logNT,
+                               int batch, hipStream_t s);
+
 // ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
 // One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
 // ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
@@ -511,7 +557,8 @@ enum KernelId {
     K_MODUP, K_CENTER, K_KS_INNER, K_TENSOR, K_PROBE, K_CI_FOLD, K_MASK_SPREAD, K_NTT_ROWS_FWD_F64, K_NTT_ROWS_INV_F64,
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
     K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_CI_BRIDGE_FOLD,
-    K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64, K_COUNT
+    K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64,
+    K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -75,7 +75,8 @@ const char *kernel_name(int id) {
                                          "ring_degree_replicate_ntt", "ring_degree_stride", "ring_split", "ring_merge",
                                          "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select",
                                          "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize", "special_fft", "ckks_fft_pass",
-                                         "special_ifft_quantize", "f64_to_rns", "rns_to_f64"};
+                                         "special_ifft_quantize", "f64_to_rns", "rns_to_f64", "bgv_slots_to_t", "bgv_t_to_slots",
+                                         "bgv_t_to_rns", "bgv_rns_to_t"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -5195,18 +5196,19 @@ struct RnsToF64KArgs {
     int nl, logN, log_slots, log_gap, batched, standard, cplx;
     double scale;
 };
+// The exact integer x mod Q of one coefficient (limb stride N words from src): its Garner digits d and its words X, both
+// little-endian in CAP registers; returns x >= Q >> 1 (compared from the top word).  pre (optional, one word per limb, kernel
+// arguments): the residue is MRed(word, pre[i]) instead of the reduced word.
 template <int CAP>
-__device__ __forceinline__ double rns_to_f64_coeff(const RnsToF64KArgs &A, const uint64_t *src) {
-    const int nl = A.nl;
-    const size_t N = (size_t)1 << A.logN;
-    uint64_t d[CAP];
+__device__ __forceinline__ bool garner_centre(const ModConst *mc, const uint64_t *g, const uint64_t *Qw, int nl, const uint64_t *src, size_t N,
+                                              const uint64_t *pre, uint64_t (&d)[CAP], uint64_t (&X)[CAP]) {
 #pragma unroll
     for (int i = 0; i < CAP; i++) {
         d[i] = 0;
         if (i < nl) {
-            const ModConst k = A.mc[i];
-            const uint64_t *gi = A.g + (size_t)i * kCkksDecodeMaxLimbs;
-            const uint64_t xi = bred_add(src[(size_t)i * N], k.q, k.brc0);
+            const ModConst k = mc[i];
+            const uint64_t *gi = g + (size_t)i * kCkksDecodeMaxLimbs;
+            const uint64_t xi = pre ? mred(src[(size_t)i * N], pre[i], k.q, k.qinv) : bred_add(src[(size_t)i * N], k.q, k.brc0);
             uint64_t t = 0;
 #pragma unroll
             for (int j = 0; j < i; j++) t = cred(t + mred(d[j], ldc(gi, j), k.q, k.qinv), k.q);
@@ -5214,13 +5216,12 @@ __device__ __forceinline__ double rns_to_f64_coeff(const RnsToF64KArgs &A, const
         }
     }
     // Horner from the top digit: X = X q_{i} + d_i
-    uint64_t X[CAP];
 #pragma unroll
     for (int w = 0; w < CAP; w++) X[w] = 0;
 #pragma unroll
     for (int i = CAP - 1; i >= 0; i--) {
         if (i < nl) {
-            const uint64_t q = ldc(&A.mc[i].q, 0);
+            const uint64_t q = ldc(&mc[i].q, 0);
             uint64_t carry = d[i];
 #pragma unroll
             for (int w = 0; w < CAP - i; w++) {  // (at most nl - i words are in use)
@@ -5230,14 +5231,20 @@ __device__ __forceinline__ double rns_to_f64_coeff(const RnsToF64KArgs &A, const
             }
         }
     }
-    // x >= Q >> 1 ?  (compare from the top word), then |x - Q| = Q - x
     int cmp = 0;
 #pragma unroll
     for (int w = CAP - 1; w >= 0; w--) {
-        const uint64_t h = w < nl ? ldc(A.Qw, kCkksDecodeMaxLimbs + w) : 0;
+        const uint64_t h = w < nl ? ldc(Qw, kCkksDecodeMaxLimbs + w) : 0;
         if (cmp == 0) cmp = X[w] > h ? 1 : (X[w] < h ? -1 : 0);
     }
-    const bool neg = cmp >= 0;
+    return cmp >= 0;
+}
+template <int CAP>
+__device__ __forceinline__ double rns_to_f64_coeff(const RnsToF64KArgs &A, const uint64_t *src) {
+    const int nl = A.nl;
+    uint64_t d[CAP], X[CAP];
+    // x >= Q >> 1 ?  then |x - Q| = Q - x
+    const bool neg = garner_centre<CAP>(A.mc, A.g, A.Qw, nl, src, (size_t)1 << A.logN, nullptr, d, X);
     if (neg) {
         uint64_t borrow = 0;
 #pragma unroll
@@ -5303,6 +5310,192 @@ hipError_t launch_rns_to_f64(const RingDev &r, const CkksDecodeArgs &a, View src
     else if (a.nl <= 8) hipLaunchKernelGGL((rns_to_f64_kernel<8>), grid, block, 0, s, A);
     else if (a.nl <= 16) hipLaunchKernelGGL((rns_to_f64_kernel<16>), grid, block, 0, s, A);
     else hipLaunchKernelGGL((rns_to_f64_kernel<32>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// BGV / BFV encoder (schemes/bgv/encoder.go; see kernels.h).  The two permutation kernels run one thread per word of their
+// contiguous side: the polynomial for the scatter (through the inverse of the index matrix, so that the zero fill of the unmapped
+// slots is the same store), the values for the gather; the bit-reversed side is a read in both and is served by L2 (a
+// polynomial of ringT is at most 512 KiB).
+// ------------------------------------------------------------------------------------
+struct BgvSlotsKArgs {
+    const ModConst *mcT;
+    const uint32_t *map;    // inverse index matrix (to ring T) / index matrix (to slots); null: identity
+    const uint64_t *values_in;
+    uint64_t *values_out;
+    uint64_t *poly;
+    size_t poly_bs, n_values;
+    int logNT, is_signed;
+};
+__global__ void __launch_bounds__(256) bgv_slots_to_t_kernel(BgvSlotsKArgs A) {
+    const unsigned j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= (1u << A.logNT)) return;
+    const size_t bz = blockIdx.y;
+    const size_t i = A.map ? A.map[j] : j;
+    uint64_t w = 0;
+    if (i < A.n_values) {
+        const uint64_t T = ldc(&A.mcT->q, 0), brc0 = ldc(&A.mcT->brc0, 0);
+        const uint64_t v = A.values_in[bz * A.n_values + i];
+        if (A.is_signed) {  // :240-243 in wrapping arithmetic: |INT64_MIN| = 2^63
+            const uint64_t sign = v >> 63, a = bred_add(sign ? 0 - v : v, T, brc0);
+            w = (sign && a) ? T - a : a;
+        } else {
+            w = bred_add(v, T, brc0);
+        }
+    }
+    A.poly[bz * A.poly_bs + j] = w;
+}
+__global__ void __launch_bounds__(256) bgv_t_to_slots_kernel(BgvSlotsKArgs A) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (1u << A.logNT)) return;
+    const size_t bz = blockIdx.y;
+    const uint64_t v = A.poly[bz * A.poly_bs + (A.map ? A.map[i] : i)];
+    const uint64_t T = ldc(&A.mcT->q, 0);
+    A.values_out[(bz << A.logNT) + i] = (A.is_signed && v >= (T >> 1)) ? v - T : v;  // :363 (v - T wraps to the int64 pattern)
+}
+hipError_t launch_bgv_slots_to_t(const ModConst *mcT, const uint32_t *inv, const uint64_t *values, size_t n_values, bool is_signed, View dst,
+                                 int logNT, int batch, hipStream_t s) {
+    if (!mcT || !values || !dst.p || dst.tab || batch <= 0 || batch > 65535 || logNT < 0 || logNT > kMaxLogN || n_values > ((size_t)1 << logNT))
+        return hipErrorInvalidValue;
+    BgvSlotsKArgs A{mcT, inv, values, nullptr, dst.p, dst.bstride, n_values, logNT, is_signed ? 1 : 0};
+    ProfScope ps(K_BGV_SLOTS_TO_T, s, ((double)n_values + (double)(1u << logNT)) * batch * 8.0);
+    hipLaunchKernelGGL(bgv_slots_to_t_kernel, dim3(((1u << logNT) + 255) / 256, batch), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_bgv_t_to_slots(const ModConst *mcT, const uint32_t *perm, View src, bool is_signed, uint64_t *values, int logNT, int batch,
+                                 hipStream_t s) {
+    if (!mcT || !values || !src.p || src.tab || batch <= 0 || batch > 65535 || logNT < 0 || logNT > kMaxLogN) return hipErrorInvalidValue;
+    BgvSlotsKArgs A{mcT, perm, nullptr, values, src.p, src.bstride, 0, logNT, is_signed ? 1 : 0};
+    ProfScope ps(K_BGV_T_TO_SLOTS, s, 2.0 * (double)(1u << logNT) * batch * 8.0);
+    hipLaunchKernelGGL(bgv_t_to_slots_kernel, dim3(((1u << logNT) + 255) / 256, batch), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+// Ring T -> RNS fan-out: one thread per coefficient position of the output; the positions off the stride store zeros, the others
+// read their word of ringT once and store one Montgomery product per limb (any 64-bit word times a constant below q: canonical).
+struct BgvFanoutKArgs {
+    const ModConst *mcT;
+    const uint64_t *src;
+    size_t src_bs;
+    const ModConst *mcQ, *mcP;
+    uint64_t *outQ, *outP;
+    size_t outQ_bs, outP_bs;
+    int nQ, nP, logN, log_gap;
+    uint64_t scale_t;
+    uint64_t cQ[kMaxLimbs], cP[kMaxLimbs];
+};
+__global__ void __launch_bounds__(256) bgv_t_to_rns_kernel(BgvFanoutKArgs A) {
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= (1u << A.logN)) return;
+    const size_t bz = blockIdx.y, N = (size_t)1 << A.logN;
+    const bool live = (pos & ((1u << A.log_gap) - 1u)) == 0;
+    uint64_t c = 0;
+    if (live) {
+        c = A.src[bz * A.src_bs + (pos >> A.log_gap)];
+        if (A.scale_t) c = mred(c, A.scale_t, ldc(&A.mcT->q, 0), ldc(&A.mcT->qinv, 0));  // MulScalar modulo T (:259)
+    }
+    uint64_t *oq = A.outQ + bz * A.outQ_bs + pos;
+    for (int i = 0; i < A.nQ; i++) oq[(size_t)i * N] = live ? mred(c, A.cQ[i], ldc(&A.mcQ[i].q, 0), ldc(&A.mcQ[i].qinv, 0)) : 0;
+    if (A.nP) {
+        uint64_t *op = A.outP + bz * A.outP_bs + pos;
+        for (int i = 0; i < A.nP; i++) op[(size_t)i * N] = live ? mred(c, A.cP[i], ldc(&A.mcP[i].q, 0), ldc(&A.mcP[i].qinv, 0)) : 0;
+    }
+}
+hipError_t launch_bgv_t_to_rns(const ModConst *mcT, View src, const BgvFanoutArgs &a, int batch, hipStream_t s) {
+    if (!mcT || !src.p || src.tab || batch <= 0 || batch > 65535 || a.nQ < 1 || a.nQ > kMaxLimbs || a.nP < 0 || a.nP > kMaxLimbs || !a.outQ.p ||
+        (a.nP && !a.outP.p) || !no_tab({a.outQ, a.outP}) || a.log_gap < 0 || a.log_gap > a.logN || a.logN > kMaxLogN)
+        return hipErrorInvalidValue;
+    BgvFanoutKArgs A{};
+    A.mcT = mcT; A.src = src.p; A.src_bs = src.bstride; A.mcQ = a.mcQ; A.mcP = a.mcP; A.outQ = a.outQ.p; A.outP = a.outP.p;
+    A.outQ_bs = a.outQ.bstride; A.outP_bs = a.outP.bstride; A.nQ = a.nQ; A.nP = a.nP; A.logN = a.logN; A.log_gap = a.log_gap; A.scale_t = a.scale_t;
+    for (int i = 0; i < a.nQ; i++) A.cQ[i] = a.cQ[i];
+    for (int i = 0; i < a.nP; i++) A.cP[i] = a.cP[i];
+    ProfScope ps(K_BGV_T_TO_RNS, s, ((double)(a.nQ + a.nP) * (double)(1u << a.logN) + (double)(1u << (a.logN - a.log_gap))) * batch * 8.0);
+    hipLaunchKernelGGL(bgv_t_to_rns_kernel, dim3(((1u << a.logN) + 255) / 256, batch), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+// RNS -> ring T: one thread per coefficient of ringT, everything between the loads and the one store in registers (CAP: the
+// instantiation's bound on the limbs; every array is indexed by unrolled loops).
+struct BgvQ2TKArgs {
+    const uint64_t *src;
+    size_t src_bs;
+    uint64_t *dst;
+    size_t dst_bs;
+    const ModConst *mc, *mcT;
+    const uint64_t *a, *T, *vt;  // GenModUpConstants(Q[:nl], {T})
+    int logN, logNT;
+    BgvQ2TArgs m;
+};
+template <int CAP>
+__global__ void __launch_bounds__(64) bgv_rns_to_t_kernel(BgvQ2TKArgs A) {
+    const unsigned j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= (1u << A.logNT)) return;
+    const size_t bz = blockIdx.y, N = (size_t)1 << A.logN;
+    const int nl = A.m.nl;
+    const ModConst mt = A.mcT[0];
+    const uint64_t *src = A.src + bz * A.src_bs + ((size_t)j << A.m.log_gap);
+    const bool scale_down = A.m.pre[0] != 0;
+    uint64_t res;
+    if (nl == 1) {  // :447-465
+        const ModConst mq = A.mc[0];
+        uint64_t v = src[0];
+        if (scale_down) v = mred(v, A.m.pre[0], mq.q, mq.qinv);
+        v = cred(v + (mq.q >> 1), mq.q);                                              // AddScalar
+        res = bred_add(v, mt.q, mt.brc0);                                             // Reduce
+        res = cred(res + mt.q - bred_add(mq.q >> 1, mt.q, mt.brc0), mt.q);            // SubScalar
+    } else if (A.m.log_gap == 0) {  // :434-436, as modup_kernel
+        uint64_t yv[CAP];
+        double vi = 0.0;
+#pragma unroll
+        for (int i = 0; i < CAP; i++) {
+            yv[i] = 0;
+            if (i < nl) {
+                const ModConst mq = A.mc[i];
+                uint64_t v = src[(size_t)i * N];
+                if (scale_down) v = mred(v, A.m.pre[i], mq.q, mq.qinv);
+                v = cred(v + A.m.half_q[i], mq.q);                                    // AddScalarBigint(Q / 2)
+                const uint64_t yi = mred(v, ldc(A.a, i), mq.q, mq.qinv);
+                yv[i] = yi;
+                vi = __dadd_rn(vi, __ddiv_rn(__ull2double_rn(yi), __ull2double_rn(mq.q)));
+            }
+        }
+        const uint64_t v = (uint64_t)vi;
+        u128 acc = (u128)yv[0] * ldc(A.T, 0);
+#pragma unroll
+        for (int i = 1; i < CAP; i++)
+            if (i < nl) acc += (u128)yv[i] * ldc(A.T, i);
+        const uint64_t rlo = (uint64_t)acc, rhi = (uint64_t)(acc >> 64);
+        res = rhi - mulhi64(rlo * mt.qinv, mt.q) + mt.q + ldc(A.vt, v);               // multSum: below 3T
+        res = bred_add(res + mt.q - A.m.half_t, mt.q, mt.brc0);                       // SubScalarBigint(Q / 2), then canonical (below 4T < 2^63)
+    } else {  // :438-440
+        uint64_t d[CAP], X[CAP];
+        const bool neg = garner_centre<CAP>(A.mc, A.m.g, A.m.Qw, nl, src, N, scale_down ? A.m.pre : nullptr, d, X);
+        res = 0;
+#pragma unroll
+        for (int i = 0; i < CAP; i++)
+            if (i < nl) res = cred(res + mred(d[i], A.m.prod_t[i], mt.q, mt.qinv), mt.q);
+        if (neg) res = cred(res + mt.q - A.m.q_mod_t, mt.q);
+    }
+    if (A.m.post) res = mred(res, A.m.post, mt.q, mt.qinv);
+    A.dst[bz * A.dst_bs + j] = res;
+}
+hipError_t launch_bgv_rns_to_t(const RingDev &r, const ModConst *mcT, const ModUpDev &up, const BgvQ2TArgs &a, View src, View dst, int logNT,
+                               int batch, hipStream_t s) {
+    if (!mcT || a.nl < 1 || a.nl > kBgvQ2TMaxLimbs || batch <= 0 || batch > 65535 || !src.p || !dst.p || !no_tab({src, dst}) || a.log_gap < 0 ||
+        logNT + a.log_gap != r.logN)
+        return hipErrorInvalidValue;
+    if (a.nl > 1 && a.log_gap == 0 && (up.nsrc != a.nl || up.ndst < 1 || !up.a || !up.T || !up.vt)) return hipErrorInvalidValue;
+    if (a.nl > 1 && a.log_gap > 0 && (!a.g || !a.Qw)) return hipErrorInvalidValue;
+    BgvQ2TKArgs A{src.p, src.bstride, dst.p, dst.bstride, r.mc, mcT, up.a, up.T, up.vt, r.logN, logNT, a};
+    const dim3 grid(((1u << logNT) + 63) / 64, batch), block(64);
+    ProfScope ps(K_BGV_RNS_TO_T, s, (double)(a.nl + 1) * batch * (double)(1u << logNT) * 8.0);
+    if (a.nl <= 2) hipLaunchKernelGGL((bgv_rns_to_t_kernel<2>), grid, block, 0, s, A);
+    else if (a.nl <= 4) hipLaunchKernelGGL((bgv_rns_to_t_kernel<4>), grid, block, 0, s, A);
+    else if (a.nl <= 8) hipLaunchKernelGGL((bgv_rns_to_t_kernel<8>), grid, block, 0, s, A);
+    else if (a.nl <= 16) hipLaunchKernelGGL((bgv_rns_to_t_kernel<16>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((bgv_rns_to_t_kernel<32>), grid, block, 0, s, A);
     return hipGetLastError();
 }
 
