@@ -17,6 +17,7 @@
 
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <complex>
 #include <memory>
 #include <stdexcept>
@@ -34,6 +35,8 @@
 #include "hering_bfv.h"
 #include "hering_ckks_encoder.h"
 #include "hering_bgv_encoder.h"
+#include "hering_sampler.h"
+#include "hering_encryptor.h"
 
 namespace hering {
 
@@ -930,6 +933,239 @@ public:
     }
 };
 }  // namespace bgv
+
+// ---- the randomness source and the ring samplers (utils/sampling, ring/sampler_*.go; hering_sampler.h) ---------------------------
+// Every sampler is an exact function of the bytes its PRNG serves: the words, the bytes consumed and the position of the source
+// afterwards are the reference's.  A Poly of B entries is B successive Reads, entry 0 first.
+namespace sampling {
+// sampling.PRNG.  PRNG(): crypto/rand's analogue, getrandom(2).  PRNG(read): any io.Reader -- read(dst, n) fills n bytes and returns
+// true (false, or an exception: a failed read, HE_EPRNG).  Position(): the bytes consumed in the reference's sense.
+class PRNG {
+    detail::Ref r_;
+    std::shared_ptr<std::function<bool(uint8_t *, size_t)>> read_;
+    static int trampoline(void *user, uint8_t *dst, size_t n) {
+        try {
+            return (*static_cast<std::function<bool(uint8_t *, size_t)> *>(user))(dst, n) ? 0 : 1;
+        } catch (...) {
+            return 2;
+        }
+    }
+
+public:
+    PRNG() {
+        he_handle h = 0;
+        check(he_prng_create_system(&h));
+        r_ = detail::own(h, he_prng_destroy);
+    }
+    explicit PRNG(std::function<bool(uint8_t *, size_t)> read) : read_(std::make_shared<std::function<bool(uint8_t *, size_t)>>(std::move(read))) {
+        he_handle h = 0;
+        check(he_prng_create_callback(&PRNG::trampoline, read_.get(), &h));
+        r_ = detail::own(h, he_prng_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    uint64_t Position() const {
+        uint64_t v[2] = {0, 0};
+        check(he_prng_position(h(), v));
+        return v[0];
+    }
+};
+}  // namespace sampling
+
+// ring.UniformSampler (ring/sampler_uniform.go); with ringP, ringqp.UniformSampler (ring/ringqp/samplers.go) on (Q, P) pairs
+class UniformSampler {
+    sampling::PRNG prng_;
+    Ring ring_;
+    std::shared_ptr<Ring> ringP_;
+
+public:
+    UniformSampler(const sampling::PRNG &prng, const Ring &baseRing) : prng_(prng), ring_(baseRing) {}
+    UniformSampler(const sampling::PRNG &prng, const Ring &ringQ, const Ring &ringP) : prng_(prng), ring_(ringQ), ringP_(std::make_shared<Ring>(ringP)) {}
+    UniformSampler AtLevel(int level) const { return UniformSampler(prng_, ring_.AtLevel(level)); }
+    UniformSampler AtLevel(int levelQ, int levelP) const {
+        if (!ringP_) throw std::invalid_argument("UniformSampler::AtLevel(levelQ, levelP): the sampler was built over one ring");
+        return UniformSampler(prng_, ring_.AtLevel(levelQ), ringP_->AtLevel(levelP));
+    }
+    void Read(Poly &pol) const { check(he_sampler_uniform_read(ring_.h(), ring_.Level(), 0, 0, prng_.h(), 0, pol.h(), 0)); }
+    void ReadAndAdd(Poly &pol) const { check(he_sampler_uniform_read(ring_.h(), ring_.Level(), 0, 0, prng_.h(), 1, pol.h(), 0)); }
+    void Read(Poly &q, Poly &p) const { check(he_sampler_uniform_read(ring_.h(), ring_.Level(), ringP_->h(), ringP_->Level(), prng_.h(), 0, q.h(), p.h())); }
+    void ReadAndAdd(Poly &q, Poly &p) const { check(he_sampler_uniform_read(ring_.h(), ring_.Level(), ringP_->h(), ringP_->Level(), prng_.h(), 1, q.h(), p.h())); }
+    Poly ReadNew(int batch = 1) const {
+        Poly pol = ring_.NewPoly(batch);
+        Read(pol);
+        return pol;
+    }
+};
+// ring.DiscreteGaussian and ring.GaussianSampler (ring/sampler_gaussian.go), the float64 branch
+struct DiscreteGaussian {
+    double Sigma = 3.2, Bound = 19.2;
+};
+class GaussianSampler {
+    sampling::PRNG prng_;
+    Ring ring_;
+    DiscreteGaussian xe_;
+    bool montgomery_;
+
+public:
+    GaussianSampler(const sampling::PRNG &prng, const Ring &baseRing, DiscreteGaussian X, bool montgomery)
+        : prng_(prng), ring_(baseRing), xe_(X), montgomery_(montgomery) {}
+    GaussianSampler AtLevel(int level) const { return GaussianSampler(prng_, ring_.AtLevel(level), xe_, montgomery_); }
+    void Read(Poly &pol) const { check(he_sampler_gaussian_read(ring_.h(), ring_.Level(), prng_.h(), xe_.Sigma, xe_.Bound, montgomery_, 0, pol.h())); }
+    void ReadAndAdd(Poly &pol) const { check(he_sampler_gaussian_read(ring_.h(), ring_.Level(), prng_.h(), xe_.Sigma, xe_.Bound, montgomery_, 1, pol.h())); }
+    Poly ReadNew(int batch = 1) const {
+        Poly pol = ring_.NewPoly(batch);
+        Read(pol);
+        return pol;
+    }
+};
+// ring.Ternary{P} and ring.TernarySampler (ring/sampler_ternary.go); the sparse form Ternary{H} is not on the device
+struct Ternary {
+    double P = 2.0 / 3.0;
+};
+class TernarySampler {
+    sampling::PRNG prng_;
+    Ring ring_;
+    Ternary xs_;
+    bool montgomery_;
+
+public:
+    TernarySampler(const sampling::PRNG &prng, const Ring &baseRing, Ternary X, bool montgomery)
+        : prng_(prng), ring_(baseRing), xs_(X), montgomery_(montgomery) {}
+    TernarySampler AtLevel(int level) const { return TernarySampler(prng_, ring_.AtLevel(level), xs_, montgomery_); }
+    void Read(Poly &pol) const { check(he_sampler_ternary_read(ring_.h(), ring_.Level(), prng_.h(), xs_.P, montgomery_, 0, pol.h())); }
+    void ReadAndAdd(Poly &pol) const { check(he_sampler_ternary_read(ring_.h(), ring_.Level(), prng_.h(), xs_.P, montgomery_, 1, pol.h())); }
+    Poly ReadNew(int batch = 1) const {
+        Poly pol = ring_.NewPoly(batch);
+        Read(pol);
+        return pol;
+    }
+};
+
+// ---- rlwe.Encryptor / rlwe.Decryptor / KeyGenerator.GenPublicKey (core/rlwe/encryptor.go, decryptor.go, keygenerator.go:80-88;
+// hering_encryptor.h).  Every call is an exact function of the bytes the encryptor's PRNG serves; for a batch the draws are made step
+// by step over the entries.  Keys carry the batch of the ciphertexts.
+namespace rlwe {
+// ringqp.Poly: a (Q, P) pair
+struct PolyQP {
+    Poly Q, P;
+};
+// rlwe.SecretKey: Value in the NTT domain and Montgomery form
+struct SecretKey {
+    PolyQP Value;
+};
+// rlwe.PublicKey: Value[0], Value[1], NTT and Montgomery
+struct PublicKey {
+    std::array<PolyQP, 2> Value;
+};
+// rlwe.MetaData restricted to what the encryptor and the decryptor read
+struct MetaData {
+    bool IsNTT = true, IsMontgomery = false;
+};
+// rlwe.Plaintext / rlwe.Ciphertext (Element[ring.Poly]): level = limbs in use - 1 (Resize changes it, not the storage)
+struct Plaintext {
+    Poly Value;
+    MetaData Meta;
+    int level = -1;
+    int Level() const { return level < 0 ? Value.Level() : level; }
+};
+struct Ciphertext {
+    std::vector<Poly> Value;
+    MetaData Meta;
+    int level = -1;
+    int Level() const { return level < 0 ? Value[0].Level() : level; }
+    int Degree() const { return (int)Value.size() - 1; }
+};
+// rlwe.Element[ringqp.Poly] of degree 1
+struct ElementQP {
+    std::array<PolyQP, 2> Value;
+    MetaData Meta{true, true};
+    int LevelQ() const { return Value[0].Q.Level(); }
+    int LevelP() const { return Value[0].P.Level(); }
+};
+
+class Encryptor {
+    detail::Ref r_;
+    Evaluator eval_;
+    sampling::PRNG prng_;
+    Ternary xs_;
+    DiscreteGaussian xe_;
+    std::vector<Poly> key_;  // what keeps the bound key alive
+    void bind(int kind, std::vector<Poly> key) {
+        he_handle k[4] = {0, 0, 0, 0};
+        for (size_t i = 0; i < key.size() && i < 4; i++) k[i] = key[i].h();
+        check(he_encryptor_set_key(r_->h, kind, k));
+        key_ = std::move(key);
+    }
+
+public:
+    // rlwe.NewEncryptor(params, nil)
+    Encryptor(const Evaluator &eval, const sampling::PRNG &prng, Ternary Xs = {}, DiscreteGaussian Xe = {}) : eval_(eval), prng_(prng), xs_(Xs), xe_(Xe) {
+        he_handle h = 0;
+        check(he_encryptor_create(eval.h(), prng.h(), Xs.P, Xe.Sigma, Xe.Bound, &h));
+        r_ = detail::own(h, he_encryptor_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    // WithKey: a shallow copy bound to the key
+    Encryptor WithKey(const SecretKey &sk) const {
+        Encryptor e(eval_, prng_, xs_, xe_);
+        e.bind(1, {sk.Value.Q, sk.Value.P});
+        return e;
+    }
+    Encryptor WithKey(const PublicKey &pk) const {
+        Encryptor e(eval_, prng_, xs_, xe_);
+        e.bind(2, {pk.Value[0].Q, pk.Value[0].P, pk.Value[1].Q, pk.Value[1].P});
+        return e;
+    }
+    void EncryptZero(Ciphertext &ct) const { check(he_encrypt_zero(h(), ct.Level(), ct.Meta.IsNTT, ct.Meta.IsMontgomery, ct.Value[0].h(), ct.Value[1].h())); }
+    void EncryptZero(ElementQP &ct) const {
+        check(he_encrypt_zero_qp(h(), ct.LevelQ(), ct.Value[0].P.h() ? ct.LevelP() : -1, ct.Meta.IsNTT, ct.Meta.IsMontgomery, ct.Value[0].Q.h(),
+                                 ct.Value[0].P.h(), ct.Value[1].Q.h(), ct.Value[1].P.h()));
+    }
+    // Encrypt (:134-152): the ciphertext takes the plaintext's metadata and level = min of the two
+    void Encrypt(const Plaintext &pt, Ciphertext &ct) const {
+        int level = 0;
+        check(he_encrypt(h(), pt.Level(), ct.Level(), pt.Meta.IsNTT, pt.Meta.IsMontgomery, pt.Value.h(), ct.Value[0].h(), ct.Value[1].h(), &level));
+        ct.Meta = pt.Meta;
+        ct.level = level;
+    }
+    void addPtToCt(int level, const Plaintext &pt, Ciphertext &ct) const {
+        check(he_add_pt_to_ct(h(), level, pt.Meta.IsNTT, ct.Meta.IsNTT, pt.Value.h(), ct.Value[0].h()));
+    }
+};
+
+class Decryptor {
+    detail::Ref r_;
+    SecretKey sk_;
+
+public:
+    // rlwe.NewDecryptor(params, sk)
+    Decryptor(const Evaluator &eval, const SecretKey &sk) : sk_(sk) {
+        he_handle h = 0;
+        check(he_decryptor_create(eval.h(), sk.Value.Q.h(), &h));
+        r_ = detail::own(h, he_decryptor_destroy);
+    }
+    // Decrypt (:51-93): pt takes the ciphertext's metadata and level = min of the two
+    void Decrypt(const Ciphertext &ct, Plaintext &pt) const {
+        std::vector<he_handle> hs;
+        for (const Poly &p : ct.Value) hs.push_back(p.h());
+        int level = 0;
+        check(he_decryptor_decrypt(r_->h, ct.Level(), pt.Level(), ct.Meta.IsNTT, ct.Degree(), hs.data(), pt.Value.h(), &level));
+        pt.Meta = ct.Meta;
+        pt.level = level;
+    }
+};
+
+// rlwe.KeyGenerator restricted to GenPublicKey (keygenerator.go:80-88)
+class KeyGenerator {
+    Encryptor enc_;
+
+public:
+    KeyGenerator(const Evaluator &eval, const sampling::PRNG &prng, Ternary Xs = {}, DiscreteGaussian Xe = {}) : enc_(eval, prng, Xs, Xe) {}
+    void GenPublicKey(const SecretKey &sk, PublicKey &pk) const {
+        ElementQP el{pk.Value, MetaData{true, true}};
+        enc_.WithKey(sk).EncryptZero(el);
+    }
+};
+}  // namespace rlwe
 
 // ---- RGSW (core/rgsw; hering_rgsw.h), NTT domain -----------------------------------------------------------------------------
 namespace rgsw {

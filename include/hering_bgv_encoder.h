@@ -6,8 +6,8 @@
  * :282-308 / reconstructRNS / multSum :550-673; ring/ring.go PolyToBigintCentered :469-509, SetCoefficientsBigint :399-413)
  * (libhering.so).
  *
- * Out of scope: bgv.Evaluator's dispatch on []uint64 operands, the linear-transformation and polynomial drivers, encryption,
- * decryption and samplers, conjugate-invariant rings (bgv.NewParameters forces the standard type).
+ * Out of scope: bgv.Evaluator's dispatch on []uint64 operands, the linear-transformation and polynomial drivers (encryption
+ * and decryption are hering_encryptor.h), conjugate-invariant rings (bgv.NewParameters forces the standard type).
  *
  * The same conventions as hering.h (which this header includes): 0 on success, <0 on error (HE_E*), he_last_error() for the
  * message; outputs come last.  Host buffers are borrowed for the duration of the call; every entry returns with its device work

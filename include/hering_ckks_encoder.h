@@ -8,7 +8,7 @@
  * (libhering.so).
  *
  * Out of scope: the big.Float / bignum.Complex paths (embedArbitrary, Special(I)FFTArbitrary, the []*big.Float and
- * []*bignum.Complex outputs), samplers, encryption and decryption.
+ * []*bignum.Complex outputs), (encryption and decryption are hering_encryptor.h).
  *
  * The same conventions as hering.h (which this header includes): 0 on success, <0 on error (HE_E*), he_last_error() for the
  * message; outputs come last.  Host buffers are borrowed for the duration of the call; every entry that moves host data returns

@@ -12,10 +12,11 @@ _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
-         os.path.join(_INC, "hering_bgv_encoder.h")]
+         os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
+PRNG_READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)  # he_prng_read_fn (include/hering_sampler.h)
 
 
 class HeringError(RuntimeError):
@@ -133,6 +134,16 @@ def _declare(L):
         "he_bgv_encode": [H, i, C.c_uint64, i, i, i, i, u64p, sz, i, i, H],
         "he_bgv_encode_qp": [H, i, i, C.c_uint64, i, i, i, u64p, sz, i, i, H, H],
         "he_bgv_decode": [H, i, C.c_uint64, i, i, H, i, u64p],
+        "he_prng_create_system": [HP], "he_prng_create_callback": [PRNG_READ_FN, C.c_void_p, HP], "he_prng_destroy": [H],
+        "he_prng_position": [H, u64p],
+        "he_sampler_uniform_read": [H, i, H, i, H, i, H, H], "he_sampler_gaussian_read": [H, i, H, C.c_double, C.c_double, i, i, H],
+        "he_sampler_ternary_read": [H, i, H, C.c_double, i, i, H],
+        "he_debug_sampler_ternary_words": [H, i, H, C.c_uint64, C.c_uint64, i, i, H],
+        "he_gaussian_tables_host": [C.POINTER(C.c_uint32)], "he_ternary_matrix_host": [C.c_double, u64p],
+        "he_encryptor_create": [H, H, C.c_double, C.c_double, C.c_double, HP], "he_encryptor_destroy": [H], "he_encryptor_set_key": [H, i, u64p],
+        "he_encrypt_zero": [H, i, i, i, H, H], "he_encrypt_zero_qp": [H, i, i, i, i, H, H, H, H], "he_add_pt_to_ct": [H, i, i, i, H, H],
+        "he_encrypt": [H, i, i, i, i, H, H, H, C.POINTER(i)], "he_decryptor_create": [H, H, HP], "he_decryptor_destroy": [H],
+        "he_decryptor_decrypt": [H, i, i, i, i, u64p, H, C.POINTER(i)],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
@@ -256,7 +267,14 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  "he_ckks_encoder_destroy",
                  # include/hering_bgv_encoder.h, the same way: the decodes and the getters read; the encodes and the two ring maps,
                  # which no replay can name, are left out on purpose (they fail trace_end)
-                 "he_bgv_decode", "he_bgv_decode_ring_t", "he_bgv_encoder_info", "he_bgv_encoder_index", "he_bgv_encoder_destroy"}
+                 "he_bgv_decode", "he_bgv_decode_ring_t", "he_bgv_encoder_info", "he_bgv_encoder_index", "he_bgv_encoder_destroy",
+                 # include/hering_sampler.h: the getters and the handles of a source, which no replayed call can name; the three
+                 # Reads carry host data into a polynomial and are left out on purpose (they fail trace_end)
+                 "he_prng_create_system", "he_prng_create_callback", "he_prng_destroy", "he_prng_position", "he_gaussian_tables_host",
+                 "he_ternary_matrix_host",
+                 # include/hering_encryptor.h: the handles, which no replayed call can name; every Encrypt / Decrypt entry is a
+                 # composition with a frame of its own and is left out on purpose (it fails trace_end)
+                 "he_encryptor_create", "he_encryptor_destroy", "he_encryptor_set_key", "he_decryptor_create", "he_decryptor_destroy"}
 _trace = None
 
 

@@ -9,7 +9,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -34,6 +36,7 @@
 #include <sched.h>
 #include <climits>
 #include <linux/futex.h>
+#include <sys/random.h>
 #include <sys/syscall.h>
 #include <unistd.h>
 
@@ -44,6 +47,8 @@
 #include "../../include/hering_bfv.h"
 #include "../../include/hering_ckks_encoder.h"
 #include "../../include/hering_bgv_encoder.h"
+#include "../../include/hering_sampler.h"
+#include "../../include/hering_encryptor.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -77,7 +82,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR };
 
 struct Obj {
     ObjType type;
@@ -5303,6 +5308,661 @@ int he_bgv_decode(he_handle h, int level, uint64_t scale, int is_batched, int is
     }
     TRY(bgv_q2t(*e, level, true, e->mont_t(invmod(scale, e->t)), src, dT, B));  // RingQ2T, then the MulScalar of :346 / :496
     return bgv_gather(*e, dT, is_batched != 0, is_signed != 0, d_vals, values, B);
+}
+
+// ---------------------------------------------------------------------------------------
+// the randomness source and the ring samplers (include/hering_sampler.h; ring/sampler_uniform.go, sampler_gaussian.go,
+// sampler_ternary.go)
+// ---------------------------------------------------------------------------------------
+// sampling.PRNG: `buf` holds the bytes fetched and not yet consumed, `pos` the bytes consumed in the reference's sense.  One call
+// at a time per handle (mu): the order of the Reads on a source is the caller's to fix, as with the reference's samplers.
+struct Prng : Obj {
+    he_prng_read_fn read = nullptr;  // null: getrandom(2)
+    void *user = nullptr;
+    std::vector<uint8_t> buf;
+    uint64_t pos = 0;
+    std::mutex mu;
+    Prng() : Obj(T_PRNG) {}
+    ~Prng() override { wipe_all(); }
+    // the whole block: erase() and resize() leave earlier copies of fetched bytes beyond size()
+    void wipe_all() {
+        const size_t n = buf.size();
+        buf.resize(buf.capacity());
+        wipe(buf.data(), buf.size());
+        buf.resize(n);
+    }
+    static void wipe(void *p, size_t n) {
+        if (n) explicit_bzero(p, n);
+    }
+    // have at least `want` bytes in buf
+    int fetch(size_t want, const char *who) {
+        const size_t have = buf.size();
+        if (want <= have) return HE_OK;
+        if (buf.capacity() < want) {  // grow by hand: the old block is wiped before it is released
+            std::vector<uint8_t> next;
+            next.reserve(want + want / 2);
+            next.assign(buf.begin(), buf.end());
+            wipe_all();
+            buf.swap(next);
+        }
+        buf.resize(want);
+        uint8_t *dst = buf.data() + have;
+        size_t n = want - have;
+        if (read) {
+            if (read(user, dst, n) != 0) {
+                buf.resize(have);
+                return fail(HE_EPRNG, "%s: the source's reader failed or ran short of %zu bytes", who, n);
+            }
+            return HE_OK;
+        }
+        while (n) {
+            const ssize_t got = getrandom(dst, std::min(n, (size_t)1 << 24), 0);
+            if (got < 0 && errno == EINTR) continue;
+            if (got <= 0) {
+                buf.resize(have);
+                return fail(HE_EPRNG, "%s: getrandom failed (%s)", who, strerror(errno));
+            }
+            dst += got;
+            n -= (size_t)got;
+        }
+        return HE_OK;
+    }
+    void consume(size_t n) {
+        const size_t old = buf.size();
+        buf.erase(buf.begin(), buf.begin() + n);  // (the tail moves down: its old copy stays in [size, old))
+        buf.resize(old);
+        wipe(buf.data() + old - n, n);
+        buf.resize(old - n);
+        pos += n;
+    }
+};
+int he_prng_create_system(he_handle *out) {
+    if (!out) return fail(HE_EINVAL, "he_prng_create_system: null output");
+    *out = reg(std::make_shared<Prng>());
+    return HE_OK;
+}
+int he_prng_create_callback(he_prng_read_fn read, void *user, he_handle *out) {
+    if (!out || !read) return fail(HE_EINVAL, "he_prng_create_callback: null %s", out ? "reader" : "output");
+    auto g = std::make_shared<Prng>();
+    g->read = read;
+    g->user = user;
+    *out = reg(g);
+    return HE_OK;
+}
+int he_prng_destroy(he_handle h) { return unreg(h, T_PRNG); }
+int he_prng_position(he_handle h, uint64_t out[2]) {
+    GET(g, Prng, h, T_PRNG);
+    if (!out) return fail(HE_EINVAL, "he_prng_position: null output");
+    std::lock_guard<std::mutex> lk(g->mu);
+    out[0] = g->pos;
+    out[1] = g->buf.size();
+    return HE_OK;
+}
+int he_gaussian_tables_host(uint32_t out[384]) {
+    if (!out) return fail(HE_EINVAL, "he_gaussian_tables_host: null output");
+    gaussian_ziggurat_tables(out);
+    return HE_OK;
+}
+static int ternary_density(double p, const char *who) {
+    if (!(p > 0.0 && p < 1.0)) return fail(HE_EINVAL, "%s: the density P = %g is not in (0, 1)", who, p);
+    return HE_OK;
+}
+int he_ternary_matrix_host(double p, uint64_t out[2]) {
+    TRY(ternary_density(p, "he_ternary_matrix_host"));
+    if (!out) return fail(HE_EINVAL, "he_ternary_matrix_host: null output");
+    ternary_matrix_words(1 - p, out[0], out[1]);
+    return HE_OK;
+}
+// an output of a sampler entry: limbs 0..level of a polynomial of `r`
+static int sampler_poly(const Ring &r, int level, he_handle h, int batch, const char *name, const char *who, std::shared_ptr<Poly> *out) {
+    TRY(check_level(r, level, who));
+    if (level + 1 > kMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs, at most %d per call", who, level + 1, kMaxLimbs);
+    auto p = get<Poly>(h, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad polynomial handle for %s", who, name);
+    if (p->ctx != r.ctx) return fail(HE_EINVAL, "%s: %s belongs to another context", who, name);
+    if (p->N != r.N) return fail(HE_EINVAL, "%s: %s has degree %d, %d expected", who, name, p->N, r.N);
+    if (p->nlimbs < level + 1) return fail(HE_EINVAL, "%s: %s has %d limbs, %d needed", who, name, p->nlimbs, level + 1);
+    if (batch >= 0 && p->batch != batch) return fail(HE_EINVAL, "%s: batch mismatch (%s has %d entries, %d expected)", who, name, p->batch, batch);
+    if (p->batch > 65535) return fail(HE_EINVAL, "%s: %s has %d entries, at most 65535 per call", who, name, p->batch);
+    *out = p;
+    return HE_OK;
+}
+// One sampler call: fetch, stage, parse, and again with twice the stream while the parse runs out of it.  `first` bytes are
+// fetched before the first attempt, and the call gives up once an attempt would need more than 64 `expected`.  parse(stream, bytes,
+// status) enqueues the launches that read the stream and write status (kernels.h); it writes only scratch or words that a later
+// attempt rewrites, so an attempt can be abandoned.  finish() enqueues what follows a parse that succeeded.  Every scratch region
+// that held stream bytes or sampled values is zeroed on the stream before the call returns.
+struct SamplerScratch {
+    size_t words = 0;           // beside the stream and the status words
+    uint64_t *p = nullptr;
+};
+static int sampler_run(const char *who, Ctx &c, Prng &g, size_t expected, size_t first, SamplerScratch &scratch,
+                       const std::function<int(const uint64_t *, size_t, uint64_t *, uint64_t *)> &parse, const std::function<int()> &finish) {
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+    std::lock_guard<std::mutex> lk(g.mu);
+    Scope sc(&c);
+    const size_t cap = expected * 64;
+    uint64_t st[4] = {0, 0, 0, 0};
+    int rc = HE_OK;
+    size_t staged = 0;
+    uint64_t *d_stream = nullptr;
+    for (size_t want = first;; want *= 2) {
+        if (want > cap) {
+            rc = fail(HE_EPRNG, "%s: the source did not let the call finish within %zu bytes (64 times the expected %zu)", who, cap, expected);
+            break;
+        }
+        if ((rc = g.fetch(want, who)) != HE_OK) break;
+        const size_t sw = (want + 7) / 8;
+        c.arena_reset();
+        if (staged) HIP_TRY(hipMemsetAsync(d_stream, 0, staged * 8, c.stream));  // (the arena may move below)
+        if ((rc = c.arena_reserve(sw + 4 + scratch.words + 8)) != HE_OK) break;
+        d_stream = c.arena_take(sw);
+        uint64_t *d_status = c.arena_take(4);
+        scratch.p = c.arena_take(scratch.words);
+        staged = sw;
+        HIP_TRY(hipMemsetAsync(d_stream + sw - 1, 0, 8, c.stream));
+        HIP_TRY(hipMemcpyAsync(d_stream, g.buf.data(), want, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(hipMemsetAsync(d_status, 0, 32, c.stream));
+        if ((rc = parse(d_stream, want, d_status, st)) != HE_OK) break;
+        if (st[0] == 0) break;
+        if (st[0] == 2) {
+            rc = fail(HE_EINVAL, "%s: a Knuth-Yao walk reached column 55 of the probability matrix (an index panic in the reference)", who);
+            break;
+        }
+    }
+    if (rc == HE_OK) rc = finish();
+    if (d_stream) {
+        (void)hipMemsetAsync(d_stream, 0, staged * 8, c.stream);
+        if (scratch.words) (void)hipMemsetAsync(scratch.p, 0, scratch.words * 8, c.stream);
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (rc != HE_OK) return rc;
+    if (st[1] > g.buf.size()) return fail(HE_EDEVICE, "%s: the parse consumed %llu bytes of %zu", who, (unsigned long long)st[1], g.buf.size());
+    g.consume((size_t)st[1]);
+    return HE_OK;
+}
+// the status words of the attempt, on the host
+static int sampler_status(Ctx &c, const uint64_t *d_status, uint64_t *st) {
+    HIP_TRY(hipMemcpyAsync(st, d_status, 32, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+int he_sampler_uniform_read(he_handle hr, int level, he_handle hrp, int levelP, he_handle hg, int add, he_handle hpol, he_handle hpolP) {
+    static const char *who = "he_sampler_uniform_read";
+    GET(r, Ring, hr, T_RING);
+    GET(g, Prng, hg, T_PRNG);
+    std::shared_ptr<Ring> rp;
+    std::shared_ptr<Poly> pol, polP;
+    TRY(sampler_poly(*r, level, hpol, -1, "pol", who, &pol));
+    if (hrp) {
+        rp = get<Ring>(hrp, T_RING);
+        if (!rp) return fail(HE_EHANDLE, "%s: bad ringP handle", who);
+        if (rp->ctx != r->ctx || rp->N != r->N) return fail(HE_EINVAL, "%s: ringP must share the context and degree of the ring", who);
+        TRY(sampler_poly(*rp, levelP, hpolP, pol->batch, "polP", who, &polP));
+        if (polP == pol) return fail(HE_EINVAL, "%s: pol and polP are one polynomial", who);
+    }
+    Ctx &c = *r->ctx;
+    const int N = r->N, B = pol->batch, nparts = rp ? 2 : 1;
+    const int nl[2] = {level + 1, rp ? levelP + 1 : 0};
+    const size_t words[2] = {(size_t)nl[0] * N, (size_t)nl[1] * N};
+    const size_t entry_bytes = 8 * ((((words[0] + 127) & ~(size_t)127)) + ((words[1] + 127) & ~(size_t)127));
+    SamplerScratch scratch;
+    if (add) scratch.words = (size_t)B * (words[0] + words[1]);  // ReadAndAdd: the draw lands here and is added when the parse is through
+    SamplerPart parts[2];
+    auto set_parts = [&]() {
+        parts[0] = SamplerPart{r->dev.mc, add ? scratch.p : pol->d, add ? words[0] : pol->view().bstride, nl[0]};
+        if (rp) parts[1] = SamplerPart{rp->dev.mc, add ? scratch.p + (size_t)B * words[0] : polP->d, add ? words[1] : polP->view().bstride, nl[1]};
+    };
+    bool direct = true;  // the one-thread-per-word launch, until a word is rejected
+    auto parse = [&](const uint64_t *d_stream, size_t bytes, uint64_t *d_status, uint64_t *st) -> int {
+        set_parts();
+        if (direct) {
+            HIP_TRY(launch_sampler_uniform(d_stream, bytes / 8, parts, nparts, N, B, false, d_status, c.stream));
+            TRY(sampler_status(c, d_status, st));
+            if (st[2] == 0) {
+                st[1] = (uint64_t)B * entry_bytes;
+                return HE_OK;
+            }
+            direct = false;
+        }
+        HIP_TRY(launch_sampler_uniform(d_stream, bytes / 8, parts, nparts, N, B, true, d_status, c.stream));
+        return sampler_status(c, d_status, st);
+    };
+    auto finish = [&]() -> int {
+        if (!add) return HE_OK;
+        const View t0{scratch.p, words[0]};
+        HIP_TRY(launch_ew(r->dev, ident_tab(nl[0]), EW_ADD, pol->view(), t0, pol->view(), B, nullptr, nullptr, c.stream));
+        if (rp) {
+            const View t1{scratch.p + (size_t)B * words[0], words[1]};
+            HIP_TRY(launch_ew(rp->dev, ident_tab(nl[1]), EW_ADD, polP->view(), t1, polP->view(), B, nullptr, nullptr, c.stream));
+        }
+        return HE_OK;
+    };
+    return sampler_run(who, c, *g, (size_t)B * entry_bytes, (size_t)B * entry_bytes, scratch, parse, finish);
+}
+// the launches after the parse of a Gaussian or ternary call: the small values into limbs 0..level of pol
+int he_sampler_gaussian_read(he_handle hr, int level, he_handle hg, double sigma, double bound, int montgomery, int add, he_handle hpol) {
+    static const char *who = "he_sampler_gaussian_read";
+    GET(r, Ring, hr, T_RING);
+    GET(g, Prng, hg, T_PRNG);
+    std::shared_ptr<Poly> pol;
+    TRY(sampler_poly(*r, level, hpol, -1, "pol", who, &pol));
+    if (!(sigma > 0.0) || sigma > 0x1p53)  // sampler_gaussian.go:100: beyond, the reference leaves float64 when the bound is large too
+        return fail(HE_EINVAL, "%s: sigma = %g is not in (0, 2^53] (the arbitrary-precision branch is not built)", who, sigma);
+    if (!(bound >= 0.0) || bound > 0x1p62) return fail(HE_EINVAL, "%s: bound = %g is not in [0, 2^62]", who, bound);
+    Ctx &c = *r->ctx;
+    const int N = r->N, B = pol->batch;
+    const size_t entry = ((size_t)N * 8 + 1023) & ~(size_t)1023, ahead = ((size_t)N * 8 + N / 2 + 2047) & ~(size_t)1023;
+    SamplerScratch scratch;
+    scratch.words = (size_t)B * N + 192;
+    auto parse = [&](const uint64_t *d_stream, size_t bytes, uint64_t *d_status, uint64_t *st) -> int {
+        static const std::array<uint32_t, 384> tab = [] { std::array<uint32_t, 384> t; gaussian_ziggurat_tables(t.data()); return t; }();
+        uint32_t *d_tab = reinterpret_cast<uint32_t *>(scratch.p + (size_t)B * N);
+        HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof tab, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(launch_sampler_gaussian(d_stream, bytes / 8, d_tab, sigma, bound, scratch.p, N, B, d_status, c.stream));
+        return sampler_status(c, d_status, st);
+    };
+    auto finish = [&]() -> int {
+        HIP_TRY(launch_sampler_expand(r->dev.mc, scratch.p, true, add != 0, montgomery != 0, nullptr, nullptr, pol->view(), N, level + 1, B, c.stream));
+        return HE_OK;
+    };
+    return sampler_run(who, c, *g, (size_t)B * entry, (size_t)B * ahead, scratch, parse, finish);
+}
+// sampleProba: the two-bit form (half) or the Knuth-Yao walk over the rows cut from x0 / x1
+static int ternary_run(const char *who, he_handle hr, int level, he_handle hg, bool half, uint64_t x0, uint64_t x1, int montgomery, int add,
+                       he_handle hpol) {
+    GET(r, Ring, hr, T_RING);
+    GET(g, Prng, hg, T_PRNG);
+    std::shared_ptr<Poly> pol;
+    TRY(sampler_poly(*r, level, hpol, -1, "pol", who, &pol));
+    Ctx &c = *r->ctx;
+    const int N = r->N, B = pol->batch;
+    uint64_t lut1[kMaxLimbs], lut2[kMaxLimbs];  // matrixValues[i][1], [2] (:82-104)
+    for (int i = 0; i <= level; i++) {
+        const uint64_t q = r->moduli[i];
+        lut1[i] = montgomery ? to_mont(1, q) : 1;
+        lut2[i] = montgomery ? to_mont(q - 1, q) : q - 1;
+    }
+    const size_t entry = half ? (size_t)N / 4 : (size_t)N;
+    SamplerScratch scratch;
+    scratch.words = (size_t)B * N;
+    auto parse = [&](const uint64_t *d_stream, size_t bytes, uint64_t *d_status, uint64_t *st) -> int {
+        HIP_TRY(launch_sampler_ternary(reinterpret_cast<const uint8_t *>(d_stream), bytes, half, x0, x1, scratch.p, N, B, d_status, c.stream));
+        if (half) {
+            st[0] = 0;
+            st[1] = (uint64_t)B * entry;
+            return HE_OK;
+        }
+        return sampler_status(c, d_status, st);
+    };
+    auto finish = [&]() -> int {
+        HIP_TRY(launch_sampler_expand(r->dev.mc, scratch.p, false, add != 0, false, lut1, lut2, pol->view(), N, level + 1, B, c.stream));
+        return HE_OK;
+    };
+    return sampler_run(who, c, *g, (size_t)B * entry, (size_t)B * entry, scratch, parse, finish);
+}
+int he_sampler_ternary_read(he_handle hr, int level, he_handle hg, double p, int montgomery, int add, he_handle hpol) {
+    static const char *who = "he_sampler_ternary_read";
+    TRY(ternary_density(p, who));
+    const double inv_density = 1 - p;  // sampler_ternary.go:34
+    uint64_t x0 = 0, x1 = 0;
+    if (inv_density != 0.5) ternary_matrix_words(inv_density, x0, x1);
+    return ternary_run(who, hr, level, hg, inv_density == 0.5, x0, x1, montgomery, add, hpol);
+}
+int he_debug_sampler_ternary_words(he_handle hr, int level, he_handle hg, uint64_t x0, uint64_t x1, int montgomery, int add, he_handle hpol) {
+    return ternary_run("he_debug_sampler_ternary_words", hr, level, hg, false, x0, x1, montgomery, add, hpol);
+}
+
+// ---------------------------------------------------------------------------------------
+// rlwe.Encryptor and rlwe.Decryptor (include/hering_encryptor.h; core/rlwe/encryptor.go, decryptor.go): compositions of the public
+// entries above, nothing fused.  Each object registers handles of its own for the evaluator, its rings and its basis extender, so
+// that the caller's may be destroyed first.
+// ---------------------------------------------------------------------------------------
+struct RlweFrame {
+    std::shared_ptr<Evaluator> ev;
+    he_handle hev = 0, hq = 0, hp = 0, hbe = 0;  // hp = 0: no special primes
+    void bind(const std::shared_ptr<Evaluator> &e) {
+        ev = e;
+        hev = reg(e);
+        hbe = reg(e->be);
+        hq = reg(e->be->Q);
+        if (!e->be->P->moduli.empty()) hp = reg(e->be->P);
+    }
+    ~RlweFrame() {
+        for (he_handle h : {hev, hq, hp, hbe})
+            if (h) reg_drop(h);
+    }
+    Ctx &ctx() const { return *ev->be->ctx; }
+    int maxP() const { return (int)ev->be->P->moduli.size() - 1; }
+    int maxQ() const { return (int)ev->be->Q->moduli.size() - 1; }
+};
+struct Encryptor : Obj, RlweFrame {
+    std::shared_ptr<Prng> prng_keep;
+    he_handle prng = 0;
+    double xs_p = 0, sigma = 0, bound = 0;
+    std::mutex mu;  // the key binding
+    int kind = 0;
+    he_handle key[4] = {0, 0, 0, 0};
+    Encryptor() : Obj(T_ENCRYPTOR) {}
+    ~Encryptor() override {
+        if (prng) reg_drop(prng);
+    }
+};
+struct Decryptor : Obj, RlweFrame {
+    he_handle sk = 0;
+    Decryptor() : Obj(T_DECRYPTOR) {}
+};
+// a temporary of a composed entry: cleared before it goes back to the pool (it held u, e or a masked plaintext)
+struct TmpPoly {
+    he_handle h = 0;
+    int alloc(he_handle ring, int limbs, int batch) { return he_poly_alloc_scratch(ring, limbs, batch, &h); }
+    ~TmpPoly() {
+        if (h) {
+            (void)he_poly_zero(h);
+            (void)he_poly_free(h);
+        }
+    }
+};
+// every output distinct from every other output and from every other operand (0: an absent operand)
+static int rlwe_distinct(const char *who, const he_handle *outs, int nouts, const he_handle *others, int nothers) {
+    auto mem = [](he_handle h) -> const void * {
+        auto p = h ? get<Poly>(h, T_POLY) : nullptr;
+        return p ? (const void *)p->d : nullptr;
+    };
+    for (int i = 0; i < nouts; i++) {
+        const void *a = mem(outs[i]);
+        if (!a) continue;
+        for (int j = i + 1; j < nouts; j++)
+            if (mem(outs[j]) == a) return fail(HE_EINVAL, "%s: outputs %d and %d are one polynomial", who, i, j);
+        for (int j = 0; j < nothers; j++)
+            if (mem(others[j]) == a) return fail(HE_EINVAL, "%s: output %d is also an input or a key polynomial (operand %d)", who, i, j);
+    }
+    return HE_OK;
+}
+static int rlwe_frame_begin(Ctx &c, const char *who) {
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+    return HE_OK;
+}
+static int rlwe_frame_end(Ctx &c) {  // the call returns with its device work finished
+    Scope sc(&c);
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+static int batch_of(he_handle h, const char *who, int *B) {
+    auto p = get<Poly>(h, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle %llu", who, (unsigned long long)h);
+    *B = p->batch;
+    return HE_OK;
+}
+
+int he_encryptor_create(he_handle hev, he_handle hprng, double xs_p, double xe_sigma, double xe_bound, he_handle *out) {
+    static const char *who = "he_encryptor_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(g, Prng, hprng, T_PRNG);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    TRY(ternary_density(xs_p, who));
+    if (!(xe_sigma > 0.0) || xe_sigma > 0x1p53 || !(xe_bound >= 0.0) || xe_bound > 0x1p62)
+        return fail(HE_EINVAL, "%s: Xe = {%g, %g}: sigma in (0, 2^53] and bound in [0, 2^62] (hering_sampler.h)", who, xe_sigma, xe_bound);
+    auto e = std::make_shared<Encryptor>();
+    e->bind(ev);
+    e->prng_keep = g;
+    e->prng = reg(g);
+    e->xs_p = xs_p;
+    e->sigma = xe_sigma;
+    e->bound = xe_bound;
+    *out = reg(e);
+    return HE_OK;
+}
+int he_encryptor_destroy(he_handle h) { return unreg(h, T_ENCRYPTOR); }
+int he_encryptor_set_key(he_handle henc, int kind, const he_handle key[4]) {
+    static const char *who = "he_encryptor_set_key";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    if (kind < 0 || kind > 2 || (kind && !key)) return fail(HE_EINVAL, "%s: kind %d (0 none, 1 sk, 2 pk)", who, kind);
+    he_handle k[4] = {0, 0, 0, 0};
+    const int n = kind == 1 ? 2 : kind == 2 ? 4 : 0;
+    for (int i = 0; i < n; i++) {
+        const bool isP = i & 1;
+        if (isP && (!e->hp || !key[i])) continue;  // (no special primes: not read; 0 otherwise: refused by the calls that read P)
+        auto p = get<Poly>(key[i], T_POLY);  // checkSk / checkPk (:466-479): the ring degree
+        if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle for key[%d]", who, i);
+        if (p->ctx.get() != &e->ctx() || p->N != e->ev->be->Q->N) return fail(HE_EINVAL, "%s: key[%d] is not a polynomial of the encryptor's rings", who, i);
+        k[i] = key[i];
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->kind = kind;
+    std::copy(k, k + 4, e->key);
+    return HE_OK;
+}
+
+// encryptZeroSkFromC1QP (:406-433); levelP = -1: the ring.Poly form
+static int encrypt_zero_sk_from_c1(Encryptor &e, const he_handle *key, int levelQ, int levelP, int is_ntt, int is_montgomery, he_handle c0Q,
+                                   he_handle c0P, he_handle c1Q, he_handle c1P) {
+    TRY(he_sampler_gaussian_read(e.hq, levelQ, e.prng, e.sigma, e.bound, 0, 0, c0Q));
+    if (levelP >= 0) TRY(he_centered_lift(e.hev, 3, c0Q, levelQ + 1, levelQ, c0Q, levelP, c0P));
+    TRY(he_ntt(e.hq, levelQ, c0Q, c0Q));
+    if (levelP >= 0) TRY(he_ntt(e.hp, levelP, c0P, c0P));
+    if (is_montgomery) {
+        TRY(he_mform(e.hq, levelQ, c0Q, c0Q));
+        if (levelP >= 0) TRY(he_mform(e.hp, levelP, c0P, c0P));
+    }
+    TRY(he_binop(e.hq, levelQ, HE_MUL_COEFFS_MONTGOMERY_THEN_SUB, c1Q, key[0], c0Q));
+    if (levelP >= 0) TRY(he_binop(e.hp, levelP, HE_MUL_COEFFS_MONTGOMERY_THEN_SUB, c1P, key[1], c0P));
+    if (!is_ntt) {
+        TRY(he_intt(e.hq, levelQ, c0Q, c0Q));
+        if (levelP >= 0) TRY(he_intt(e.hp, levelP, c0P, c0P));
+        TRY(he_intt(e.hq, levelQ, c1Q, c1Q));
+        if (levelP >= 0) TRY(he_intt(e.hp, levelP, c1P, c1P));
+    }
+    return HE_OK;
+}
+// encryptZeroSk (:347-393)
+static int encrypt_zero_sk(Encryptor &e, const he_handle *key, int levelQ, int levelP, int is_ntt, int is_montgomery, he_handle c0Q,
+                           he_handle c0P, he_handle c1Q, he_handle c1P) {
+    TRY(he_sampler_uniform_read(e.hq, levelQ, levelP >= 0 ? e.hp : 0, levelP >= 0 ? levelP : 0, e.prng, 0, c1Q, levelP >= 0 ? c1P : 0));
+    if (!is_ntt) {
+        TRY(he_ntt(e.hq, levelQ, c1Q, c1Q));
+        if (levelP >= 0) TRY(he_ntt(e.hp, levelP, c1P, c1P));
+    }
+    return encrypt_zero_sk_from_c1(e, key, levelQ, levelP, is_ntt, is_montgomery, c0Q, c0P, c1Q, c1P);
+}
+// encryptZeroPk (:204-299); qp: the Element[ringqp.Poly] form, otherwise ct{0,1}P are the temporaries of the ring.Poly form (levelP 0)
+static int encrypt_zero_pk(Encryptor &e, const he_handle *key, int levelQ, int levelP, bool qp, int is_ntt, int is_montgomery, he_handle c0Q,
+                           he_handle c0P, he_handle c1Q, he_handle c1P, int B) {
+    TmpPoly uQ, uP, t0P, t1P;
+    TRY(uQ.alloc(e.hq, levelQ + 1, B));
+    TRY(uP.alloc(e.hp, levelP + 1, B));
+    if (!qp) {
+        TRY(t0P.alloc(e.hp, levelP + 1, B));
+        TRY(t1P.alloc(e.hp, levelP + 1, B));
+        c0P = t0P.h;
+        c1P = t1P.h;
+    }
+    const he_handle ctQ[2] = {c0Q, c1Q}, ctP[2] = {c0P, c1P};
+    TRY(he_sampler_ternary_read(e.hq, levelQ, e.prng, e.xs_p, 0, 0, uQ.h));
+    TRY(he_centered_lift(e.hev, 3, uQ.h, levelQ + 1, levelQ, uQ.h, levelP, uP.h));
+    TRY(he_ntt(e.hq, levelQ, uQ.h, uQ.h));
+    TRY(he_ntt(e.hp, levelP, uP.h, uP.h));
+    for (int k = 0; k < 2; k++) {
+        TRY(he_mul_coeffs_montgomery(e.hq, levelQ, uQ.h, key[2 * k], ctQ[k]));
+        TRY(he_mul_coeffs_montgomery(e.hp, levelP, uP.h, key[2 * k + 1], ctP[k]));
+    }
+    for (int k = 0; k < 2; k++) {
+        TRY(he_intt(e.hq, levelQ, ctQ[k], ctQ[k]));
+        TRY(he_intt(e.hp, levelP, ctP[k], ctP[k]));
+    }
+    for (int k = 0; k < 2; k++) {  // e := u (the buffer)
+        TRY(he_sampler_gaussian_read(e.hq, levelQ, e.prng, e.sigma, e.bound, 0, 0, uQ.h));
+        TRY(he_centered_lift(e.hev, 3, uQ.h, levelQ + 1, levelQ, uQ.h, levelP, uP.h));
+        TRY(he_add(e.hq, levelQ, ctQ[k], uQ.h, ctQ[k]));
+        TRY(he_add(e.hp, levelP, ctP[k], uP.h, ctP[k]));
+    }
+    if (!qp)
+        for (int k = 0; k < 2; k++) TRY(he_moddown_qp_to_q(e.hbe, levelQ, levelP, ctQ[k], ctP[k], ctQ[k]));
+    if (is_ntt)
+        for (int k = 0; k < 2; k++) {
+            TRY(he_ntt(e.hq, levelQ, ctQ[k], ctQ[k]));
+            if (qp) TRY(he_ntt(e.hp, levelP, ctP[k], ctP[k]));
+        }
+    if (is_montgomery)
+        for (int k = 0; k < 2; k++) {
+            TRY(he_mform(e.hq, levelQ, ctQ[k], ctQ[k]));
+            if (qp) TRY(he_mform(e.hp, levelP, ctP[k], ctP[k]));
+        }
+    return HE_OK;
+}
+// encryptZeroPkNoP (:301-342): the metadata's IsMontgomery is not read there
+static int encrypt_zero_pk_nop(Encryptor &e, const he_handle *key, int levelQ, int is_ntt, he_handle c0, he_handle c1, int B) {
+    TmpPoly buf;
+    TRY(buf.alloc(e.hq, levelQ + 1, B));
+    const he_handle ct[2] = {c0, c1};
+    TRY(he_sampler_ternary_read(e.hq, levelQ, e.prng, e.xs_p, 0, 0, buf.h));
+    TRY(he_ntt(e.hq, levelQ, buf.h, buf.h));
+    TRY(he_mul_coeffs_montgomery(e.hq, levelQ, buf.h, key[0], c0));
+    TRY(he_mul_coeffs_montgomery(e.hq, levelQ, buf.h, key[2], c1));
+    for (int k = 0; k < 2; k++) {
+        if (is_ntt) {
+            TRY(he_sampler_gaussian_read(e.hq, levelQ, e.prng, e.sigma, e.bound, 0, 0, buf.h));
+            TRY(he_ntt(e.hq, levelQ, buf.h, buf.h));
+            TRY(he_add(e.hq, levelQ, ct[k], buf.h, ct[k]));
+        } else {
+            TRY(he_intt(e.hq, levelQ, ct[k], ct[k]));
+            TRY(he_sampler_gaussian_read(e.hq, levelQ, e.prng, e.sigma, e.bound, 0, 1, ct[k]));
+        }
+    }
+    return HE_OK;
+}
+// EncryptZero (:176-188) without the frame; qp: an Element[ringqp.Poly]
+static int encrypt_zero(Encryptor &e, const char *who, int levelQ, int levelP, bool qp, int is_ntt, int is_montgomery, he_handle c0Q, he_handle c0P,
+                        he_handle c1Q, he_handle c1P, const he_handle *extra, int nextra) {
+    int kind;
+    he_handle key[4];
+    {
+        std::lock_guard<std::mutex> lk(e.mu);
+        kind = e.kind;
+        std::copy(e.key, e.key + 4, key);
+    }
+    if (kind == 0) return fail(HE_EINVAL, "%s: the encryptor has no encryption key", who);
+    const bool needP = e.hp && (kind == 2 || (qp && levelP >= 0));  // (encryptZeroPk lifts to P for a ring.Poly element too)
+    if (needP && (!key[1] || (kind == 2 && !key[3]))) return fail(HE_EINVAL, "%s: the key was bound without its P part, which this call reads", who);
+    if (levelQ < 0 || levelQ > e.maxQ()) return fail(HE_EINVAL, "%s: level %d, the ring has levels 0..%d", who, levelQ, e.maxQ());
+    if (qp && kind == 1 && levelP == -1) qp = false;  // a ringqp.Poly without a P part (GenPublicKey without special primes): c0P, c1P are not read
+    if (qp && (!e.hp || levelP < 0 || levelP > e.maxP())) return fail(HE_EINVAL, "%s: levelP %d, ringP has levels 0..%d", who, levelP, e.maxP());
+    int B = 0;
+    TRY(batch_of(c0Q, who, &B));
+    const he_handle outs[4] = {c0Q, c1Q, qp ? c0P : 0, qp ? c1P : 0};
+    he_handle others[8] = {key[0], key[1], key[2], key[3], 0, 0, 0, 0};
+    for (int i = 0; i < nextra && i < 4; i++) others[4 + i] = extra[i];
+    TRY(rlwe_distinct(who, outs, 4, others, 8));
+    if (kind == 1) return encrypt_zero_sk(e, key, levelQ, qp ? levelP : -1, is_ntt, is_montgomery, c0Q, c0P, c1Q, c1P);
+    if (!qp && !e.hp) return encrypt_zero_pk_nop(e, key, levelQ, is_ntt, c0Q, c1Q, B);
+    return encrypt_zero_pk(e, key, levelQ, qp ? levelP : 0, qp, is_ntt, is_montgomery, c0Q, c0P, c1Q, c1P, B);
+}
+int he_encrypt_zero(he_handle henc, int level, int is_ntt, int is_montgomery, he_handle c0, he_handle c1) {
+    static const char *who = "he_encrypt_zero";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    const int rc = encrypt_zero(*e, who, level, -1, false, is_ntt, is_montgomery, c0, 0, c1, 0, nullptr, 0);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_encrypt_zero_qp(he_handle henc, int levelQ, int levelP, int is_ntt, int is_montgomery, he_handle c0Q, he_handle c0P, he_handle c1Q,
+                       he_handle c1P) {
+    static const char *who = "he_encrypt_zero_qp";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    const int rc = encrypt_zero(*e, who, levelQ, levelP, true, is_ntt, is_montgomery, c0Q, c0P, c1Q, c1P, nullptr, 0);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+// addPtToCt (:481-507) without the frame
+static int add_pt_to_ct(Encryptor &e, const char *who, int level, int pt_is_ntt, int ct_is_ntt, he_handle pt, he_handle c0) {
+    if (level < 0 || level > e.maxQ()) return fail(HE_EINVAL, "%s: level %d, the ring has levels 0..%d", who, level, e.maxQ());
+    TRY(rlwe_distinct(who, &c0, 1, &pt, 1));
+    if (!pt_is_ntt == !ct_is_ntt) return he_add(e.hq, level, c0, pt, c0);
+    int B = 0;
+    TRY(batch_of(pt, who, &B));
+    TmpPoly buf;
+    TRY(buf.alloc(e.hq, level + 1, B));
+    if (pt_is_ntt) TRY(he_ntt(e.hq, level, pt, buf.h));  // (:493, as the reference writes it)
+    else TRY(he_intt(e.hq, level, pt, buf.h));           // (:500)
+    return he_add(e.hq, level, c0, buf.h, c0);
+}
+int he_add_pt_to_ct(he_handle henc, int level, int pt_is_ntt, int ct_is_ntt, he_handle pt, he_handle c0) {
+    static const char *who = "he_add_pt_to_ct";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    const int rc = add_pt_to_ct(*e, who, level, pt_is_ntt, ct_is_ntt, pt, c0);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_encrypt(he_handle henc, int pt_level, int ct_level, int is_ntt, int is_montgomery, he_handle pt, he_handle c0, he_handle c1, int *level_out) {
+    static const char *who = "he_encrypt";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    const int level = std::min(pt_level, ct_level);  // (:141)
+    if (level_out) *level_out = level;
+    if (!get<Poly>(pt, T_POLY)) return fail(HE_EHANDLE, "%s: bad Poly handle for the plaintext", who);
+    int rc = encrypt_zero(*e, who, level, -1, false, is_ntt, is_montgomery, c0, 0, c1, 0, &pt, 1);
+    if (rc == HE_OK) rc = add_pt_to_ct(*e, who, level, is_ntt, is_ntt, pt, c0);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+
+int he_decryptor_create(he_handle hev, he_handle skQ, he_handle *out) {
+    static const char *who = "he_decryptor_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    auto p = get<Poly>(skQ, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle for skQ", who);
+    if (p->ctx != ev->be->ctx || p->N != ev->be->Q->N) return fail(HE_EINVAL, "%s: skQ is not a polynomial of the evaluator's ringQ", who);
+    auto d = std::make_shared<Decryptor>();
+    d->bind(ev);
+    d->sk = skQ;
+    *out = reg(d);
+    return HE_OK;
+}
+int he_decryptor_destroy(he_handle h) { return unreg(h, T_DECRYPTOR); }
+static int decrypt(Decryptor &d, const char *who, int level, int is_ntt, int degree, const he_handle *ct, he_handle pt) {
+    if (is_ntt) TRY(he_poly_copy(pt, ct[degree], level));  // (:61-65)
+    else TRY(he_ntt_lazy(d.hq, level, ct[degree], pt));
+    TmpPoly buf;
+    if (!is_ntt && degree > 0) {
+        int B = 0;
+        TRY(batch_of(pt, who, &B));
+        TRY(buf.alloc(d.hq, level + 1, B));
+    }
+    for (int i = degree; i > 0; i--) {  // (:67-84)
+        TRY(he_mul_coeffs_montgomery(d.hq, level, pt, d.sk, pt));
+        if (!is_ntt) {
+            TRY(he_ntt_lazy(d.hq, level, ct[i - 1], buf.h));
+            TRY(he_add(d.hq, level, pt, buf.h, pt));
+        } else {
+            TRY(he_add(d.hq, level, pt, ct[i - 1], pt));
+        }
+        if ((i & 7) == 7) TRY(he_reduce(d.hq, level, pt, pt));
+    }
+    // (:86: no Reduce when degree & 7 == 7.  For a coefficient-domain ciphertext the reference's INTT then reads the unreduced sum of
+    // NTTLazy words, up to 7q, on which its butterflies are not exact: its words there are not the decryption.  he_ntt_lazy keeps
+    // [0, 2q) and he_intt takes canonical words, so the Reduce is made in that case too and the result is the canonical decryption)
+    if ((degree & 7) != 7 || !is_ntt) TRY(he_reduce(d.hq, level, pt, pt));
+    if (!is_ntt) TRY(he_intt(d.hq, level, pt, pt));
+    return HE_OK;
+}
+int he_decryptor_decrypt(he_handle hdec, int ct_level, int pt_level, int is_ntt, int degree, const he_handle *ct, he_handle pt, int *level_out) {
+    static const char *who = "he_decryptor_decrypt";
+    GET(d, Decryptor, hdec, T_DECRYPTOR);
+    TRY(rlwe_frame_begin(d->ctx(), who));
+    if (!ct || degree < 0 || degree > 63) return fail(HE_EINVAL, "%s: degree %d is not in [0, 63]", who, degree);
+    const int level = std::min(ct_level, pt_level);  // (:53)
+    if (level < 0 || level > d->maxQ()) return fail(HE_EINVAL, "%s: level %d, the ring has levels 0..%d", who, level, d->maxQ());
+    if (level_out) *level_out = level;
+    he_handle others[65];
+    for (int i = 0; i <= degree; i++) others[i] = ct[i];
+    others[degree + 1] = d->sk;
+    TRY(rlwe_distinct(who, &pt, 1, others, degree + 2));
+    const int rc = decrypt(*d, who, level, is_ntt, degree, ct, pt);
+    const int rs = rlwe_frame_end(d->ctx());
+    return rc != HE_OK ? rc : rs;
 }
 
 // ---------------------------------------------------------------------------------------

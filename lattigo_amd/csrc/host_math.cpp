@@ -2,6 +2,7 @@
 #include "host_math.h"
 
 #include <cmath>
+#include <cstring>
 
 #include <algorithm>
 
@@ -282,6 +283,34 @@ std::vector<uint64_t> product_and_half_words(const std::vector<uint64_t> &moduli
     }
     for (int k = 0; k < cap; k++) w[cap + k] = (w[k] >> 1) | (k + 1 < cap ? w[k + 1] << 63 : 0);
     return w;
+}
+
+void gaussian_ziggurat_tables(uint32_t out[384]) {
+    const double m1 = 2147483648.0, vn = 9.91256303526217e-3;
+    double dn = 3.442619855899, tn = dn;
+    uint32_t *kn = out;
+    float wn[128], fn[128];
+    const double q = vn / std::exp(-.5 * dn * dn);
+    kn[0] = (uint32_t)((dn / q) * m1);
+    kn[1] = 0;
+    wn[0] = (float)(q / m1);
+    wn[127] = (float)(dn / m1);
+    fn[0] = 1.0f;
+    fn[127] = (float)std::exp(-.5 * dn * dn);
+    for (int i = 126; i >= 1; i--) {
+        dn = std::sqrt(-2. * std::log(vn / dn + std::exp(-.5 * dn * dn)));
+        kn[i + 1] = (uint32_t)((dn / tn) * m1);
+        tn = dn;
+        fn[i] = (float)std::exp(-.5 * dn * dn);
+        wn[i] = (float)(dn / m1);
+    }
+    memcpy(out + 128, wn, sizeof wn);
+    memcpy(out + 256, fn, sizeof fn);
+}
+
+void ternary_matrix_words(double inv_density, uint64_t &x0, uint64_t &x1) {
+    x0 = (uint64_t)(inv_density * std::exp2(56.0));
+    x1 = (uint64_t)((1 - inv_density) * std::exp2(56.0));
 }
 
 }  // namespace he

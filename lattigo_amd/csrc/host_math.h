@@ -65,4 +65,13 @@ std::vector<uint64_t> build_garner_table(const std::vector<uint64_t> &moduli, in
 // prod(moduli[0..n)) little-endian in `cap` words, followed by that product >> 1 in `cap` words (n <= cap)
 std::vector<uint64_t> product_and_half_words(const std::vector<uint64_t> &moduli, int n, int cap);
 
+// ---- ring samplers (ring/sampler_gaussian.go, ring/sampler_ternary.go) -------------------------------------------------------
+// The ziggurat tables of normFloat64 (sampler_gaussian.go:267 on) from their construction (Marsaglia and Tsang, "The Ziggurat
+// Method for Generating Random Variables", 2000: 128 strips, r = 3.442619855899, v = 9.91256303526217e-3, m1 = 2^31), doubles
+// rounded once to uint32 / float32: out[0..128) = kn, out[128..256) = the words of wn, out[256..384) = the words of fn
+void gaussian_ziggurat_tables(uint32_t out[384]);
+// computeMatrixTernary (sampler_ternary.go:106-128): x0 = uint64(p * 2^56), x1 = uint64((1 - p) * 2^56) for p = the inverse density;
+// matrixProba[r][j] = bit 55 - j of x_r, j < 55
+void ternary_matrix_words(double inv_density, uint64_t &x0, uint64_t &x1);
+
 }  // namespace he

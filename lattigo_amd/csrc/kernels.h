@@ -498,6 +498,36 @@ struct BgvQ2TArgs {
 hipError_t launch_bgv_rns_to_t(const RingDev &r, const ModConst *mcT, const ModUpDev &up, const BgvQ2TArgs &a, View src, View dst, int logNT,
                                int batch, hipStream_t s);
 
+// ---- ring samplers (ring/sampler_uniform.go, sampler_gaussian.go, sampler_ternary.go; include/hering_sampler.h) ------------------
+// The byte stream a sampler would have read from its PRNG is resident (`stream`, 8-byte aligned); a call parses it into `batch`
+// polynomials, entry 0 first, each starting where the reference's next Read starts.  status: four device words, zeroed by the caller:
+// [0] 0 done, 1 the stream ended first (nothing may be used), 2 the reference panics; [1] the bytes consumed in the reference's sense
+// (chain launches); [2] non-zero: a word was rejected in the direct uniform launch (run the chain launch, which rewrites everything).
+// UniformSampler.read (:44-99), `nparts` Reads per entry (2: the Q part and then the P part of a ringqp.Poly, ringqp/samplers.go:
+// 47-55), part k into limbs 0..nl-1 of its polynomial.  chain = false: one thread per word, valid when no word is rejected,
+// avail_words >= batch * sum roundup(nl_k N, 128); chain = true: one workgroup, any stream.
+struct SamplerPart {
+    const ModConst *mc;  // [nl]
+    uint64_t *out;
+    size_t out_bs;
+    int nl;
+};
+hipError_t launch_sampler_uniform(const uint64_t *stream, size_t avail_words, const SamplerPart *parts, int nparts, int N, int batch,
+                                  bool chain, uint64_t *status, hipStream_t s);
+// GaussianSampler.read, float64 branch (:158-174): vals[b][i] = coeffInt << 1 | sign of sample i (bound <= 2^62).  tables: device,
+// 128 words kn, 128 float32 wn, 128 float32 fn (host_math's gaussian_ziggurat_tables).  One workgroup.
+hipError_t launch_sampler_gaussian(const uint64_t *stream, size_t avail_words, const uint32_t *tables, double sigma, double bound,
+                                   uint64_t *vals, int N, int batch, uint64_t *status, hipStream_t s);
+// TernarySampler.sampleProba (:130-196): vals[b][i] = the index into matrixValues.  half: the two-bit form of P = 0.5 (one thread
+// per coefficient, avail_bytes >= batch N / 4, status not written); else the Knuth-Yao walk with the words x0 / x1 that
+// computeMatrixTernary cuts its rows from (one workgroup).
+hipError_t launch_sampler_ternary(const uint8_t *stream, size_t avail_bytes, bool half, uint64_t x0, uint64_t x1, uint64_t *vals, int N,
+                                  int batch, uint64_t *status, hipStream_t s);
+// vals into limbs 0..nl-1 of out: gaussian -- the words of :172, then CRed(a + w) with add, then MForm with mont (:177-179);
+// else lut1[j] / lut2[j] = matrixValues[j][1] / [2] (host arrays of nl words), then CRed(a + w) with add
+hipError_t launch_sampler_expand(const ModConst *mc, const uint64_t *vals, bool gaussian, bool add, bool mont, const uint64_t *lut1,
+                                 const uint64_t *lut2, View out, int N, int nl, int batch, hipStream_t s);
+
 // ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
 // One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
 // ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
@@ -558,7 +588,8 @@ enum KernelId {
     K_NTT_MAC_F64, K_DIAG_MAC, K_RING_FOLD, K_RING_REPLICATE, K_RING_STRIDE, K_RING_SPLIT, K_RING_MERGE, K_EXPAND_STEP,
     K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_CI_BRIDGE_FOLD,
     K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64,
-    K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T, K_COUNT
+    K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
+    K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -76,7 +76,8 @@ const char *kernel_name(int id) {
                                          "expand_step", "pack_pre", "pack_post", "xpow2_fill", "rgsw_external_product", "automorphism_ct_select",
                                          "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize", "special_fft", "ckks_fft_pass",
                                          "special_ifft_quantize", "f64_to_rns", "rns_to_f64", "bgv_slots_to_t", "bgv_t_to_slots",
-                                         "bgv_t_to_rns", "bgv_rns_to_t"};
+                                         "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
+                                         "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -5496,6 +5497,371 @@ hipError_t launch_bgv_rns_to_t(const RingDev &r, const ModConst *mcT, const ModU
     else if (a.nl <= 8) hipLaunchKernelGGL((bgv_rns_to_t_kernel<8>), grid, block, 0, s, A);
     else if (a.nl <= 16) hipLaunchKernelGGL((bgv_rns_to_t_kernel<16>), grid, block, 0, s, A);
     else hipLaunchKernelGGL((bgv_rns_to_t_kernel<32>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// Ring samplers (ring/sampler_uniform.go, sampler_gaussian.go, sampler_ternary.go; see kernels.h and include/hering_sampler.h).
+// A sampler is a parse of a byte stream in which the start of one draw depends on every draw before it.  The parse runs in ONE
+// workgroup per call (nothing waits on another workgroup), chunk by chunk of 256 stream positions: every lane evaluates "one draw
+// that starts at my position" (a value or a rejection, and the position after it), the positions that really are on the chain are
+// found by pointer doubling in LDS (eight rounds for 256 positions), the accepted ones are ranked by a prefix sum and the first
+// `need` of them stored.  The position the chain leaves the chunk at is carried into the next chunk, the end of one polynomial into
+// the next batch entry.  Every loop advances the stream position or ends; running out of stream is the status word 1, never a spin.
+// ------------------------------------------------------------------------------------
+constexpr unsigned kChainChunk = 256;
+// exclusive rank of `pred` among the 256 threads of the block, and the block's count; s_w: 4 words of LDS
+__device__ __forceinline__ unsigned block_rank_256(bool pred, unsigned *s_w, unsigned &total) {
+    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(pred);
+    const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_w[wv] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned base = 0;
+    total = 0;
+    for (unsigned k = 0; k < 4; k++) {
+        const unsigned c = s_w[k];
+        if (k < wv) base += c;
+        total += c;
+    }
+    __syncthreads();
+    return base + r;
+}
+struct UniformKArgs {
+    const uint64_t *stream;  // big-endian words
+    size_t avail;            // words of stream
+    SamplerPart part[2];     // the Reads of one entry, in order (the Q part, then the P part of a ringqp.Poly)
+    int nparts, N, batch;
+    uint64_t *status;
+};
+__device__ __forceinline__ uint64_t uniform_mask(uint64_t q) { return q > 1 ? ~0ull >> __clzll(q - 1) : 0; }  // SubRing.Mask (subring.go:63)
+__host__ __device__ __forceinline__ size_t read_words(int nl, int N) { return ((size_t)nl * N + 127) & ~(size_t)127; }
+// sampler_uniform.go:61-97 when no word is rejected: word i of limb j of a part is word j N + i of that part's Read, every Read a
+// whole number of 1024-byte blocks.  A rejected word sets status[2]; the caller then runs uniform_chain_kernel over the same
+// stream, which rewrites every word.
+__global__ void __launch_bounds__(256) uniform_direct_kernel(UniformKArgs A) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)A.N) return;
+    const size_t b = blockIdx.z, w0 = read_words(A.part[0].nl, A.N), w1 = A.nparts > 1 ? read_words(A.part[1].nl, A.N) : 0;
+    const int k = (int)blockIdx.y >= A.part[0].nl ? 1 : 0;
+    const size_t j = blockIdx.y - (k ? A.part[0].nl : 0);
+    const size_t p = b * (w0 + w1) + (k ? w0 : 0) + j * (size_t)A.N + i;
+    const uint64_t q = A.part[k].mc[j].q;
+    if (p >= A.avail) { A.status[2] = 1; return; }
+    const uint64_t w = __builtin_bswap64(A.stream[p]) & uniform_mask(q);
+    if (w < q) A.part[k].out[b * A.part[k].out_bs + j * (size_t)A.N + i] = w;
+    else A.status[2] = 1;
+}
+// sampler_uniform.go:44-99 for any stream: one workgroup, limb after limb, part after part and entry after entry; a Read starts on
+// a 1024-byte block and its end is rounded up to one (the unused tail of the last buffer the reference fetched).
+__global__ void __launch_bounds__(256) uniform_chain_kernel(UniformKArgs A) {
+    __shared__ unsigned s_w[4];
+    __shared__ unsigned long long s_end;
+    const unsigned tid = threadIdx.x;
+    size_t pos = 0;
+    for (int b = 0; b < A.batch; b++) {
+        for (int k = 0; k < A.nparts; k++) {
+            for (int j = 0; j < A.part[k].nl; j++) {
+                const uint64_t q = A.part[k].mc[j].q, mask = uniform_mask(q);
+                uint64_t *dst = A.part[k].out + (size_t)b * A.part[k].out_bs + (size_t)j * A.N;
+                size_t need = (size_t)A.N, done = 0;
+                while (need) {
+                    if (pos >= A.avail) {
+                        if (tid == 0) A.status[0] = 1;
+                        return;
+                    }
+                    const size_t p = pos + tid;
+                    const bool valid = p < A.avail;
+                    const uint64_t w = valid ? __builtin_bswap64(A.stream[p]) & mask : 0;
+                    const bool acc = valid && w < q;
+                    unsigned total;
+                    const unsigned rank = block_rank_256(acc, s_w, total);
+                    if (acc && rank < need) dst[done + rank] = w;
+                    if (total >= need) {
+                        if (acc && rank == need - 1) s_end = p + 1;
+                        __syncthreads();
+                        pos = s_end;
+                        need = 0;
+                    } else {
+                        done += total;
+                        need -= total;
+                        pos += kChainChunk;
+                    }
+                }
+            }
+            pos = (pos + 127) & ~(size_t)127;
+        }
+    }
+    if (tid == 0) A.status[1] = pos * 8;
+}
+
+// one draw that starts at a stream position: len positions long (>= 1); ok: it yields val; inc: the stream ended inside it; err: the
+// reference panics inside it
+struct Draw {
+    size_t len;
+    uint64_t val;
+    bool ok, inc, err;
+};
+// GaussianSampler.read, the float64 branch (sampler_gaussian.go:158-174), and normFloat64 (:192-265) as a default amd64 build
+// evaluates them: positions are little-endian 64-bit words, one IEEE operation per written one.  val = coeffInt << 1 | sign.
+struct GaussEval {
+    const uint64_t *stream;
+    size_t avail;  // words
+    const uint32_t *kn;
+    const float *wn, *fn;
+    double sigma, bound;
+    __device__ __forceinline__ static double rand_f64(uint64_t w) {  // :215-220
+        return __ddiv_rn((double)(w & 0x1fffffffffffffull), (double)0x1fffffffffffffull);
+    }
+    __device__ Draw draw(size_t p) const {
+        Draw d{1, 0, false, false, false};
+        if (p >= avail) { d.inc = true; return d; }
+        const uint32_t ju = (uint32_t)stream[p];  // :210, the low four bytes; the draw advances eight (:211)
+        const uint32_t j = ju & 0x7fffffffu, i = j & 0x7fu;
+        const uint64_t sign = ju >> 31;
+        double norm = __dmul_rn((double)j, (double)wn[i]);
+        bool accepted;
+        if (j < kn[i]) {  // :236, the strip
+            accepted = true;
+        } else if (i == 0) {  // :242-257, the tail of the base strip
+            const double inv_rn = 0x1.2972a8afc6175p-2;  // the constant 1.0 / rn, rounded once
+            size_t q = p + 1;
+            double x;
+            for (;;) {
+                if (q + 1 >= avail) { d.inc = true; return d; }
+                x = __dmul_rn(-log(rand_f64(stream[q])), inv_rn);  // log(0) = -Inf: x = +Inf, which the bound rejects below
+                const double y = -log(rand_f64(stream[q + 1]));
+                q += 2;
+                if (__dadd_rn(y, y) >= __dmul_rn(x, x)) break;
+            }
+            norm = __dadd_rn(x, 3.442619855899);
+            d.len = q - p;
+            accepted = true;
+        } else {  // :260, the wedge, in float32
+            if (p + 1 >= avail) { d.inc = true; return d; }
+            d.len = 2;
+            const float u = (float)rand_f64(stream[p + 1]);
+            const float lhs = __fadd_rn(fn[i], __fmul_rn(u, __fsub_rn(fn[i - 1], fn[i])));
+            accepted = lhs < (float)exp(__dmul_rn(__dmul_rn(-0.5, norm), norm));
+        }
+        if (accepted) {
+            const double v = __dmul_rn(norm, sigma);  // :165
+            if (v <= bound) {
+                d.ok = true;
+                d.val = ((uint64_t)__dadd_rn(v, 0.5) << 1) | sign;  // :166
+            }
+        }
+        return d;
+    }
+    __device__ __forceinline__ size_t next_entry(size_t, size_t end) const { return (end + 127) & ~(size_t)127; }
+    __device__ __forceinline__ uint64_t bytes(size_t pos) const { return pos * 8; }
+};
+// kysampling (sampler_ternary.go:266-336): positions are bits, bit i of byte k is position 8 k + i.  x0 / x1: the words
+// computeMatrixTernary (:106-128) cuts matrixProba[0] / [1] from.  val = the index into matrixValues (:189).
+struct KyEval {
+    const uint8_t *stream;
+    size_t avail;  // bits
+    uint64_t x0, x1;
+    size_t block_bytes;  // N: the buffer of one prng.Read
+    __device__ Draw draw(size_t P) const {
+        Draw r{1, 0, false, false, false};
+        int d = 0, col = 0;
+        for (size_t q = P;; q++) {
+            if (q >= avail) { r.inc = true; return r; }
+            const int bit = (stream[q >> 3] >> (q & 7)) & 1;
+            d = (d << 1) + 1 - bit;
+            if (d > 1) { d = 1 - bit; col = 0; }        // :283-285: the walk starts again at this bit
+            if (col >= 55) { r.err = true; return r; }  // matrixProba has 55 columns: an index panic in the reference
+            int coeff = -1;
+            d -= (int)((x1 >> (55 - col)) & 1);
+            if (d == -1) coeff = 1;
+            else {
+                d -= (int)((x0 >> (55 - col)) & 1);
+                if (d == -1) coeff = 0;
+            }
+            if (coeff >= 0) {
+                uint64_t sign;
+                size_t next;
+                if ((q & 7) == 7) {  // :294-307: bit 0 of the next byte; the next walk starts at its bit 1
+                    const size_t sb = (q >> 3) + 1;
+                    if (sb * 8 >= avail) { r.inc = true; return r; }
+                    sign = stream[sb] & 1;
+                    next = sb * 8 + 1;
+                } else {  // :309-313: the next bit, where the next walk starts too
+                    sign = (stream[q >> 3] >> ((q & 7) + 1)) & 1;
+                    next = q + 1;
+                }
+                const uint64_t c = (uint64_t)coeff;
+                r.ok = true;
+                r.val = (c & (sign ^ 1)) | ((sign & c) << 1);
+                r.len = next - P;
+                return r;
+            }
+            col++;
+        }
+    }
+    // the buffers fetched: one at the start and one whenever the byte pointer reaches N; after a walk the pointer is in 1..8, so the
+    // byte it stands in is that of position end - 1
+    __device__ __forceinline__ size_t next_entry(size_t start, size_t end) const {
+        const size_t sb = start >> 3, eb = (end - 1) >> 3;
+        return (sb + ((eb - sb) / block_bytes + 1) * block_bytes) * 8;
+    }
+    __device__ __forceinline__ uint64_t bytes(size_t pos) const { return pos >> 3; }
+};
+// vals[b][0..N) = the values of the first N accepted draws of entry b; status[0] = 1: the stream ended first, 2: the reference
+// panics; status[1] = the bytes consumed in the reference's sense
+template <class E>
+__global__ void __launch_bounds__(256) chain_parse_kernel(E ev, uint64_t *vals, int N, int batch, uint64_t *status) {
+    __shared__ unsigned s_w[4];
+    __shared__ unsigned short s_nx[kChainChunk];
+    __shared__ unsigned char s_on[kChainChunk];
+    __shared__ unsigned long long s_end, s_carry;
+    __shared__ unsigned s_stop;
+    const unsigned tid = threadIdx.x;
+    size_t start = 0;
+    for (int b = 0; b < batch; b++) {
+        size_t base = start, entry = 0, need = (size_t)N, done = 0, end = start;
+        while (need) {
+            if (base >= ev.avail) {
+                if (tid == 0) status[0] = 1;
+                return;
+            }
+            if (entry >= kChainChunk) {  // a draw longer than a chunk
+                base += kChainChunk;
+                entry -= kChainChunk;
+                continue;
+            }
+            const Draw d = ev.draw(base + tid);
+            const bool dead = d.inc || d.err;
+            unsigned nx = (dead || tid + d.len >= kChainChunk) ? kChainChunk : tid + (unsigned)d.len;
+            s_nx[tid] = (unsigned short)nx;
+            s_on[tid] = tid == entry;
+            if (tid == 0) s_stop = 0;
+            __syncthreads();
+            for (unsigned k = 0; k < 8; k++) {  // after round k: s_nx = the 2^(k+1)-th successor, s_on = reached in fewer steps
+                const bool on = s_on[tid] != 0;
+                nx = s_nx[tid];
+                const unsigned nn = nx < kChainChunk ? s_nx[nx] : kChainChunk;
+                __syncthreads();
+                if (on && nx < kChainChunk) s_on[nx] = 1;
+                s_nx[tid] = (unsigned short)nn;
+                __syncthreads();
+            }
+            const bool on = s_on[tid] != 0, acc = on && d.ok;
+            unsigned total;
+            const unsigned rank = block_rank_256(acc, s_w, total);
+            if (acc && rank < need) vals[(size_t)b * N + done + rank] = d.val;
+            if (acc && rank == need - 1) s_end = base + tid + d.len;
+            if (on && dead && rank < need) s_stop = d.err ? 2u : 1u;
+            if (on && !dead && tid + d.len >= kChainChunk) s_carry = tid + d.len - kChainChunk;
+            __syncthreads();
+            const unsigned stop = s_stop;
+            if (stop) {
+                if (tid == 0) status[0] = stop;
+                return;
+            }
+            if (total >= need) {
+                end = s_end;
+                need = 0;
+            } else {
+                done += total;
+                need -= total;
+                entry = s_carry;
+                base += kChainChunk;
+            }
+            __syncthreads();
+        }
+        start = ev.next_entry(start, end);
+    }
+    if (tid == 0) status[1] = ev.bytes(start);
+}
+// sampleProba at P = 0.5 (sampler_ternary.go:147-171): entry b reads N / 8 coefficient bytes, then N / 8 sign bytes
+__global__ void __launch_bounds__(256) ternary_half_kernel(const uint8_t *stream, uint64_t *vals, int N) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)N) return;
+    const size_t b = blockIdx.y;
+    const uint8_t *s = stream + b * (size_t)(N >> 2);
+    const uint64_t coeff = (s[i >> 3] >> (i & 7)) & 1, sign = (s[(N >> 3) + (i >> 3)] >> (i & 7)) & 1;
+    vals[b * (size_t)N + i] = (coeff & (sign ^ 1)) | ((sign & coeff) << 1);
+}
+struct SamplerExpandKArgs {
+    const ModConst *mc;
+    const uint64_t *vals;
+    uint64_t *out;
+    size_t out_bs;
+    int N, gaussian, add, mont;
+    uint64_t lut1[kMaxLimbs], lut2[kMaxLimbs];
+};
+// the small values into every limb: the Gaussian words of :172 (the word q_i itself for c = 0, sign = 0) or matrixValues[j][val];
+// add: CRed(a + w) (wrapping, as the reference's); Gaussian with mont: MForm of the result (:177-179: of the whole polynomial)
+__global__ void __launch_bounds__(256) sampler_expand_kernel(SamplerExpandKArgs A) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)A.N) return;
+    const size_t j = blockIdx.y, b = blockIdx.z;
+    const ModConst m = A.mc[j];
+    const uint64_t v = A.vals[b * (size_t)A.N + i];
+    uint64_t w;
+    if (A.gaussian) {
+        const uint64_t c = v >> 1, sign = v & 1;
+        w = (c * sign) | ((m.q - c) * (sign ^ 1));
+    } else {
+        w = v == 0 ? 0 : (v == 1 ? A.lut1[j] : A.lut2[j]);
+    }
+    uint64_t *o = A.out + b * A.out_bs + j * (size_t)A.N + i;
+    if (A.add) w = cred(*o + w, m.q);
+    if (A.gaussian && A.mont) w = mform(w, m.q, m.brc0, m.brc1);
+    *o = w;
+}
+
+static bool sampler_shape_ok(int N, int batch) { return N >= 8 && N <= (1 << kMaxLogN) && (N & (N - 1)) == 0 && batch > 0 && batch <= 65535; }
+hipError_t launch_sampler_uniform(const uint64_t *stream, size_t avail_words, const SamplerPart *parts, int nparts, int N, int batch,
+                                  bool chain, uint64_t *status, hipStream_t s) {
+    if (!stream || !status || !parts || nparts < 1 || nparts > 2 || !sampler_shape_ok(N, batch)) return hipErrorInvalidValue;
+    UniformKArgs A{stream, avail_words, {parts[0], nparts > 1 ? parts[1] : SamplerPart{nullptr, nullptr, 0, 0}}, nparts, N, batch, status};
+    size_t entry_words = 0;
+    int nl = 0;
+    for (int k = 0; k < nparts; k++) {
+        if (!parts[k].mc || !parts[k].out || parts[k].nl < 1 || parts[k].nl > kMaxLimbs) return hipErrorInvalidValue;
+        entry_words += read_words(parts[k].nl, N);
+        nl += parts[k].nl;
+    }
+    if (!chain && avail_words < entry_words * batch) return hipErrorInvalidValue;
+    ProfScope ps(chain ? K_SAMPLER_UNIFORM_CHAIN : K_SAMPLER_UNIFORM, s, 2.0 * nl * (double)N * batch * 8.0);
+    if (chain) hipLaunchKernelGGL(uniform_chain_kernel, dim3(1), dim3(256), 0, s, A);
+    else hipLaunchKernelGGL(uniform_direct_kernel, dim3((N + 255) / 256, nl, batch), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+hipError_t launch_sampler_gaussian(const uint64_t *stream, size_t avail_words, const uint32_t *tables, double sigma, double bound,
+                                   uint64_t *vals, int N, int batch, uint64_t *status, hipStream_t s) {
+    if (!stream || !tables || !vals || !status || !sampler_shape_ok(N, batch) || !(sigma > 0.0) || !(bound >= 0.0)) return hipErrorInvalidValue;
+    const GaussEval ev{stream, avail_words, tables, reinterpret_cast<const float *>(tables + 128), reinterpret_cast<const float *>(tables + 256),
+                       sigma, bound};
+    ProfScope ps(K_SAMPLER_GAUSSIAN, s, 2.0 * (double)N * batch * 8.0);
+    hipLaunchKernelGGL((chain_parse_kernel<GaussEval>), dim3(1), dim3(256), 0, s, ev, vals, N, batch, status);
+    return hipGetLastError();
+}
+hipError_t launch_sampler_ternary(const uint8_t *stream, size_t avail_bytes, bool half, uint64_t x0, uint64_t x1, uint64_t *vals, int N,
+                                  int batch, uint64_t *status, hipStream_t s) {
+    if (!stream || !vals || !status || !sampler_shape_ok(N, batch)) return hipErrorInvalidValue;
+    if (half) {
+        if (avail_bytes < (size_t)batch * (N >> 2)) return hipErrorInvalidValue;
+        ProfScope ps(K_SAMPLER_TERNARY_HALF, s, (double)N * batch * 8.25);
+        hipLaunchKernelGGL(ternary_half_kernel, dim3((N + 255) / 256, batch), dim3(256), 0, s, stream, vals, N);
+        return hipGetLastError();
+    }
+    const KyEval ev{stream, avail_bytes * 8, x0, x1, (size_t)N};
+    ProfScope ps(K_SAMPLER_TERNARY_KY, s, (double)N * batch * 8.25);
+    hipLaunchKernelGGL((chain_parse_kernel<KyEval>), dim3(1), dim3(256), 0, s, ev, vals, N, batch, status);
+    return hipGetLastError();
+}
+hipError_t launch_sampler_expand(const ModConst *mc, const uint64_t *vals, bool gaussian, bool add, bool mont, const uint64_t *lut1,
+                                 const uint64_t *lut2, View out, int N, int nl, int batch, hipStream_t s) {
+    if (!mc || !vals || !out.p || out.tab || !sampler_shape_ok(N, batch) || nl < 1 || nl > kMaxLimbs || (!gaussian && (!lut1 || !lut2)))
+        return hipErrorInvalidValue;
+    SamplerExpandKArgs A{mc, vals, out.p, out.bstride, N, gaussian ? 1 : 0, add ? 1 : 0, mont ? 1 : 0, {}, {}};
+    for (int j = 0; j < nl && !gaussian; j++) { A.lut1[j] = lut1[j]; A.lut2[j] = lut2[j]; }
+    ProfScope ps(K_SAMPLER_EXPAND, s, ((add ? 2.0 : 1.0) * nl + 1.0) * (double)N * batch * 8.0);
+    hipLaunchKernelGGL(sampler_expand_kernel, dim3((N + 255) / 256, nl, batch), dim3(256), 0, s, A);
     return hipGetLastError();
 }
 
