@@ -37,6 +37,7 @@
 #include "hering_bgv_encoder.h"
 #include "hering_sampler.h"
 #include "hering_encryptor.h"
+#include "hering_keygen.h"
 
 namespace hering {
 
@@ -490,6 +491,18 @@ public:
                                         const std::vector<uint64_t> &p) const {
         he_handle h = 0;
         check(he_evk_create_base2(this->h(), pw2, nj.data(), (int)nj.size(), nQk, nPk, q.data(), nPk > 0 ? p.data() : nullptr, &h));
+        EvaluationKey k;
+        k.r_ = detail::own(h, he_evk_destroy);
+        k.nQk_ = nQk;
+        k.nPk_ = nPk;
+        return k;
+    }
+    // a zeroed key of that shape, to be generated on the device (rlwe::KeyGenerator) or filled through DeviceBuffer / Commit;
+    // pw2 != 0: nj[i] bit windows of Q-limb i and beta = their sum
+    EvaluationKey NewEvaluationKeyZero(int beta, int nQk, int nPk, int pw2 = 0, const std::vector<int> &nj = {}) const {
+        he_handle h = 0;
+        if (pw2) check(he_evk_create_base2(this->h(), pw2, nj.data(), (int)nj.size(), nQk, nPk, nullptr, nullptr, &h));
+        else check(he_evk_create(this->h(), beta, nQk, nPk, nullptr, nullptr, &h));
         EvaluationKey k;
         k.r_ = detail::own(h, he_evk_destroy);
         k.nQk_ = nQk;
@@ -1017,7 +1030,7 @@ public:
         return pol;
     }
 };
-// ring.Ternary{P} and ring.TernarySampler (ring/sampler_ternary.go); the sparse form Ternary{H} is not on the device
+// ring.Ternary{P} and ring.TernarySampler (ring/sampler_ternary.go); the sparse form Ternary{H} is SparseTernarySampler below
 struct Ternary {
     double P = 2.0 / 3.0;
 };
@@ -1038,6 +1051,20 @@ public:
         Read(pol);
         return pol;
     }
+};
+
+// ring.Ternary{H} and its TernarySampler (sampleSparse, ring/sampler_ternary.go:198-263; hering_keygen.h): Read only
+class SparseTernarySampler {
+    sampling::PRNG prng_;
+    Ring ring_;
+    int hw_;
+    bool montgomery_;
+
+public:
+    SparseTernarySampler(const sampling::PRNG &prng, const Ring &baseRing, int H, bool montgomery)
+        : prng_(prng), ring_(baseRing), hw_(H), montgomery_(montgomery) {}
+    SparseTernarySampler AtLevel(int level) const { return SparseTernarySampler(prng_, ring_.AtLevel(level), hw_, montgomery_); }
+    void Read(Poly &pol) const { check(he_keygen_ternary_sparse_read(ring_.h(), ring_.Level(), prng_.h(), hw_, montgomery_, pol.h())); }
 };
 
 // ---- rlwe.Encryptor / rlwe.Decryptor / KeyGenerator.GenPublicKey (core/rlwe/encryptor.go, decryptor.go, keygenerator.go:80-88;
@@ -1154,18 +1181,154 @@ public:
     }
 };
 
-// rlwe.KeyGenerator restricted to GenPublicKey (keygenerator.go:80-88)
+// rlwe.EvaluationKeyParameters (core/rlwe/evaluationkey.go): a negative level = the parameters' default; Compressed keys are not built
+struct EvaluationKeyParameters {
+    int LevelQ = -2, LevelP = -2, BaseTwoDecomposition = 0;
+    bool Compressed = false;
+};
+// rlwe.GaloisKey
+struct GaloisKey {
+    EvaluationKey Key;
+    uint64_t GaloisElement = 0, NthRoot = 0;
+};
+// AddPolyTimesGadgetVectorToGadgetCiphertext (core/rlwe/gadgetciphertext.go:172-241): pt times the gadget vector to component u of cts[u]
+inline void AddPolyTimesGadgetVectorToGadgetCiphertext(const Poly &pt, const std::vector<EvaluationKey> &cts) {
+    if (cts.empty() || cts.size() > 2) throw std::invalid_argument("cannot AddPolyTimesGadgetVectorToGadgetCiphertext: len(cts) should be <= 2");
+    check(he_gadget_add_poly(pt.h(), cts[0].h(), cts.size() > 1 ? cts[1].h() : 0));
+}
+
+// rlwe.KeyGenerator (core/rlwe/keygenerator.go; hering_keygen.h): every call is an exact function of the bytes the generator's PRNG
+// serves -- an evaluation key row after row (the uniform c1, then the Gaussian e), Galois keys key after key
 class KeyGenerator {
     Encryptor enc_;
+    Evaluator eval_;
+    detail::Ref r_;
+    static int logq(uint64_t q) {  // LogQi (params.go:474-481): round(log2(q))
+        int b = 63 - __builtin_clzll(q);
+        const long double m = (long double)q / (long double)((uint64_t)1 << b);  // in [1, 2): rounds up from sqrt(2)
+        return m * m >= 2.0L ? b + 1 : b;
+    }
+    bool hasP() const { return eval_.RingP().MaxLevel() >= 0; }
+    uint64_t nthRoot() const { return (uint64_t)eval_.RingQ().N() * (eval_.RingQ().Type() == RingType::Standard ? 2 : 4); }
+    SecretKey newSecretKey() const { return hasP() ? SecretKey{{eval_.RingQ().NewPoly(), eval_.RingP().NewPoly()}} : SecretKey{{eval_.RingQ().NewPoly(), Poly()}}; }
 
 public:
-    KeyGenerator(const Evaluator &eval, const sampling::PRNG &prng, Ternary Xs = {}, DiscreteGaussian Xe = {}) : enc_(eval, prng, Xs, Xe) {}
+    KeyGenerator(const Evaluator &eval, const sampling::PRNG &prng, Ternary Xs = {}, DiscreteGaussian Xe = {}) : enc_(eval, prng, Xs, Xe), eval_(eval) {
+        he_handle h = 0;
+        check(he_keygen_create(eval.h(), prng.h(), Xs.P, Xe.Sigma, Xe.Bound, &h));
+        r_ = detail::own(h, he_keygen_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    // -- secret and public keys
+    void GenSecretKey(SecretKey &sk) const {
+        check(he_keygen_secret_key(h(), sk.Value.Q.Level(), sk.Value.P.h() ? sk.Value.P.Level() : -1, sk.Value.Q.h(), sk.Value.P.h()));
+    }
+    SecretKey GenSecretKeyNew() const {
+        SecretKey sk = newSecretKey();
+        GenSecretKey(sk);
+        return sk;
+    }
+    void GenSecretKeyWithHammingWeight(int hw, SecretKey &sk) const {
+        check(he_keygen_secret_key_hw(h(), hw, sk.Value.Q.Level(), sk.Value.P.h() ? sk.Value.P.Level() : -1, sk.Value.Q.h(), sk.Value.P.h()));
+    }
+    SecretKey GenSecretKeyWithHammingWeightNew(int hw) const {
+        SecretKey sk = newSecretKey();
+        GenSecretKeyWithHammingWeight(hw, sk);
+        return sk;
+    }
     void GenPublicKey(const SecretKey &sk, PublicKey &pk) const {
         ElementQP el{pk.Value, MetaData{true, true}};
         enc_.WithKey(sk).EncryptZero(el);
+        pk.Value = el.Value;
+    }
+    PublicKey GenPublicKeyNew(const SecretKey &sk) const {
+        const Ring &q = eval_.RingQ(), &p = eval_.RingP();
+        PublicKey pk{{{{q.NewPoly(), hasP() ? p.NewPoly() : Poly()}, {q.NewPoly(), hasP() ? p.NewPoly() : Poly()}}}};
+        GenPublicKey(sk, pk);
+        return pk;
+    }
+    std::pair<SecretKey, PublicKey> GenKeyPairNew() const {
+        SecretKey sk = GenSecretKeyNew();
+        PublicKey pk = GenPublicKeyNew(sk);
+        return {sk, pk};
+    }
+    // -- evaluation keys.  newEvaluationKey: a zeroed key of degree 1 at the resolved levels (ResolveEvaluationKeyParameters)
+    EvaluationKey NewEvaluationKey(const EvaluationKeyParameters &evkParams = {}) const {
+        if (evkParams.Compressed) throw std::invalid_argument("compressed evaluation keys are not on the device (hering_keygen.h)");
+        const int levelQ = evkParams.LevelQ < -1 ? eval_.RingQ().MaxLevel() : evkParams.LevelQ;
+        const int levelP = evkParams.LevelP < -1 ? (hasP() ? eval_.RingP().MaxLevel() : -1) : evkParams.LevelP;
+        const int pw2 = evkParams.BaseTwoDecomposition;
+        const int beta = levelP == -1 ? levelQ + 1 : (levelQ + levelP + 1) / (levelP + 1);  // params.go:543-550
+        if (!pw2) return eval_.NewEvaluationKeyZero(beta, levelQ + 1, levelP + 1);
+        std::vector<int> nj;  // BaseTwoDecompositionVectorSize (params.go:523-540)
+        for (int i = 0; i < beta; i++) nj.push_back(levelP > 0 ? 1 : (logq(eval_.RingQ().ModuliChain()[(size_t)i]) + pw2 - 1) / pw2);
+        int rows = 0;
+        for (int n : nj) rows += n;
+        return eval_.NewEvaluationKeyZero(rows, levelQ + 1, levelP + 1, pw2, nj);
+    }
+    // GenEvaluationKey (:261-285): the two keys may live in rings of a smaller degree and at other levels; their Q parts are read
+    void GenEvaluationKey(const SecretKey &skInput, const SecretKey &skOutput, EvaluationKey &evk) const {
+        check(he_keygen_evaluation_key_sk(h(), skInput.Value.Q.h(), skOutput.Value.Q.h(), evk.h()));
+    }
+    EvaluationKey GenEvaluationKeyNew(const SecretKey &skInput, const SecretKey &skOutput, const EvaluationKeyParameters &evkParams = {}) const {
+        EvaluationKey evk = NewEvaluationKey(evkParams);
+        GenEvaluationKey(skInput, skOutput, evk);
+        return evk;
+    }
+    // genEvaluationKey (:287-330) on operands of the key's own ring and levels: the fused entry
+    void genEvaluationKey(const Poly &skIn, const SecretKey &skOut, EvaluationKey &evk) const {
+        check(he_keygen_evaluation_key(h(), skIn.h(), skOut.Value.Q.h(), skOut.Value.P.h(), evk.h()));
+    }
+    // GenEvaluationKeysForRingSwapNew (:211-233): (stdToci, ciToStd)
+    std::pair<EvaluationKey, EvaluationKey> GenEvaluationKeysForRingSwapNew(const SecretKey &skStd, const SecretKey &skConjugateInvariant,
+                                                                            const EvaluationKeyParameters &evkParams = {}) const {
+        const int levelQ = skStd.Value.Q.Level() < skConjugateInvariant.Value.Q.Level() ? skStd.Value.Q.Level() : skConjugateInvariant.Value.Q.Level();
+        SecretKey mapped{{eval_.RingQ().AtLevel(levelQ).NewPoly(), Poly()}};
+        eval_.RingQ().AtLevel(levelQ).UnfoldConjugateInvariantToStandard(skConjugateInvariant.Value.Q, mapped.Value.Q);
+        EvaluationKey stdToci = GenEvaluationKeyNew(skStd, mapped, evkParams);
+        EvaluationKey ciToStd = GenEvaluationKeyNew(mapped, skStd, evkParams);
+        return {stdToci, ciToStd};
+    }
+    void GenRelinearizationKey(const SecretKey &sk, EvaluationKey &rlk) const {
+        check(he_keygen_relinearization_key(h(), sk.Value.Q.h(), sk.Value.P.h(), rlk.h()));
+    }
+    EvaluationKey GenRelinearizationKeyNew(const SecretKey &sk, const EvaluationKeyParameters &evkParams = {}) const {
+        EvaluationKey rlk = NewEvaluationKey(evkParams);
+        GenRelinearizationKey(sk, rlk);
+        return rlk;
+    }
+    void GenGaloisKey(uint64_t galEl, const SecretKey &sk, GaloisKey &gk) const {
+        check(he_keygen_galois_key(h(), galEl, sk.Value.Q.h(), sk.Value.P.h(), gk.Key.h()));
+        gk.GaloisElement = galEl;
+        gk.NthRoot = nthRoot();
+    }
+    GaloisKey GenGaloisKeyNew(uint64_t galEl, const SecretKey &sk, const EvaluationKeyParameters &evkParams = {}) const {
+        GaloisKey gk{NewEvaluationKey(evkParams), galEl, nthRoot()};
+        GenGaloisKey(galEl, sk, gk);
+        return gk;
+    }
+    void GenGaloisKeys(const std::vector<uint64_t> &galEls, const SecretKey &sk, std::vector<GaloisKey> &gks) const {
+        if (galEls.size() != gks.size()) throw std::invalid_argument("galEls and gks must have the same length");
+        std::vector<he_handle> hs;
+        for (GaloisKey &gk : gks) {
+            if (!gk.Key.h()) gk.Key = NewEvaluationKey();
+            hs.push_back(gk.Key.h());
+        }
+        check(he_keygen_galois_keys(h(), (int)galEls.size(), galEls.data(), sk.Value.Q.h(), sk.Value.P.h(), hs.data()));
+        for (size_t i = 0; i < gks.size(); i++) {
+            gks[i].GaloisElement = galEls[i];
+            gks[i].NthRoot = nthRoot();
+        }
+    }
+    std::vector<GaloisKey> GenGaloisKeysNew(const std::vector<uint64_t> &galEls, const SecretKey &sk, const EvaluationKeyParameters &evkParams = {}) const {
+        std::vector<GaloisKey> gks;
+        for (uint64_t g : galEls) gks.push_back(GaloisKey{NewEvaluationKey(evkParams), g, nthRoot()});
+        GenGaloisKeys(galEls, sk, gks);
+        return gks;
     }
 };
 }  // namespace rlwe
+using KeyGenerator = rlwe::KeyGenerator;
 
 // ---- RGSW (core/rgsw; hering_rgsw.h), NTT domain -----------------------------------------------------------------------------
 namespace rgsw {

@@ -2,9 +2,9 @@
  * hering_encryptor.h -- rlwe.Encryptor (core/rlwe/encryptor.go) and rlwe.Decryptor (core/rlwe/decryptor.go) on the device, over the
  * rings of an evaluator, the samplers of hering_sampler.h and a he_prng (libhering.so).
  *
- * Out of scope: the KeyGenerator beyond GenPublicKey (genEvaluationKey is a loop of EncryptZero calls plus the gadget term); the
- * degree-0 form of encryptZeroSk that sends c1 to scratch (encryptor.go:355-359); the sparse ternary distribution and whatever
- * else hering_sampler.h leaves out.
+ * Elsewhere: the KeyGenerator beyond GenPublicKey (hering_keygen.h: genEvaluationKey is a loop of EncryptZero calls plus the gadget
+ * term, with the arithmetic after the draws fused).  Out of scope: the degree-0 form of encryptZeroSk that sends c1 to scratch
+ * (encryptor.go:355-359); the sparse ternary distribution as the encryptor's own Xs and whatever else hering_sampler.h leaves out.
  *
  * The same conventions as hering.h: 0 on success, <0 on error, he_last_error() for the message; outputs come last.  Like the
  * encoders and the samplers, these entries carry host data (the bytes of the source): a call runs after the calling thread's queued

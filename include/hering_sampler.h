@@ -4,8 +4,9 @@
  * 68-265, the float64 branch) and ring.TernarySampler with a density (ring/sampler_ternary.go:130-196, kysampling :266-336,
  * computeMatrixTernary :106-128) (libhering.so).
  *
- * Out of scope: the KeyGenerator (the Encryptor and the Decryptor are hering_encryptor.h); the sparse ternary sampler (H != 0, sampleSparse :198-263, a
- * sequential shuffle used only for secret keys); the arbitrary-precision Gaussian branch (sigma > 2^53 and bound > 2^64 - 1, :100);
+ * Elsewhere: the Encryptor and the Decryptor (hering_encryptor.h); the KeyGenerator and the sparse ternary sampler (H != 0,
+ * sampleSparse :198-263, a sequential shuffle used only for secret keys: hering_keygen.h).
+ * Out of scope: the arbitrary-precision Gaussian branch (sigma > 2^53 and bound > 2^64 - 1, :100);
  * a CSPRNG on the device; a restatement of sampling.KeyedPRNG (BLAKE2Xb): a keyed source is passed in as a callback.
  *
  * The same conventions as hering.h (which this header includes): 0 on success, <0 on error (HE_E*), he_last_error() for the

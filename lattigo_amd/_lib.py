@@ -12,7 +12,8 @@ _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), os.path.join(_INC, "hering_ringswitch.h"),
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
-         os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h")]
+         os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h"),
+         os.path.join(_INC, "hering_keygen.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -144,6 +145,11 @@ def _declare(L):
         "he_encrypt_zero": [H, i, i, i, H, H], "he_encrypt_zero_qp": [H, i, i, i, i, H, H, H, H], "he_add_pt_to_ct": [H, i, i, i, H, H],
         "he_encrypt": [H, i, i, i, i, H, H, H, C.POINTER(i)], "he_decryptor_create": [H, H, HP], "he_decryptor_destroy": [H],
         "he_decryptor_decrypt": [H, i, i, i, i, u64p, H, C.POINTER(i)],
+        "he_keygen_create": [H, H, C.c_double, C.c_double, C.c_double, HP], "he_keygen_destroy": [H],
+        "he_keygen_ternary_sparse_read": [H, i, H, i, i, H], "he_keygen_secret_key": [H, i, i, H, H],
+        "he_keygen_secret_key_hw": [H, i, i, i, H, H], "he_gadget_add_poly": [H, H, H],
+        "he_keygen_evaluation_key": [H, H, H, H, H], "he_keygen_evaluation_key_sk": [H, H, H, H], "he_keygen_relinearization_key": [H, H, H, H],
+        "he_keygen_galois_key": [H, C.c_uint64, H, H, H], "he_keygen_galois_keys": [H, i, u64p, H, H, u64p],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
@@ -274,7 +280,10 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  "he_ternary_matrix_host",
                  # include/hering_encryptor.h: the handles, which no replayed call can name; every Encrypt / Decrypt entry is a
                  # composition with a frame of its own and is left out on purpose (it fails trace_end)
-                 "he_encryptor_create", "he_encryptor_destroy", "he_encryptor_set_key", "he_decryptor_create", "he_decryptor_destroy"}
+                 "he_encryptor_create", "he_encryptor_destroy", "he_encryptor_set_key", "he_decryptor_create", "he_decryptor_destroy",
+                 # include/hering_keygen.h: the handles; every generation entry carries the bytes of a source into a key and is
+                 # left out on purpose (it fails trace_end)
+                 "he_keygen_create", "he_keygen_destroy"}
 _trace = None
 
 

@@ -49,6 +49,7 @@
 #include "../../include/hering_bgv_encoder.h"
 #include "../../include/hering_sampler.h"
 #include "../../include/hering_encryptor.h"
+#include "../../include/hering_keygen.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -82,7 +83,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR, T_KEYGEN };
 
 struct Obj {
     ObjType type;
@@ -5487,6 +5488,8 @@ static int sampler_status(Ctx &c, const uint64_t *d_status, uint64_t *st) {
     HIP_TRY(hipStreamSynchronize(c.stream));
     return HE_OK;
 }
+static int uniform_read_run(const char *who, Ctx &c, Prng &g, int N, int B, int nparts, const ModConst *const mc[2], const int nl[2],
+                            uint64_t *const out[2], const size_t bs[2], bool add, const std::function<int(uint64_t *)> &sum);
 int he_sampler_uniform_read(he_handle hr, int level, he_handle hrp, int levelP, he_handle hg, int add, he_handle hpol, he_handle hpolP) {
     static const char *who = "he_sampler_uniform_read";
     GET(r, Ring, hr, T_RING);
@@ -5505,13 +5508,32 @@ int he_sampler_uniform_read(he_handle hr, int level, he_handle hrp, int levelP, 
     const int N = r->N, B = pol->batch, nparts = rp ? 2 : 1;
     const int nl[2] = {level + 1, rp ? levelP + 1 : 0};
     const size_t words[2] = {(size_t)nl[0] * N, (size_t)nl[1] * N};
+    const ModConst *const mc[2] = {r->dev.mc, rp ? rp->dev.mc : nullptr};
+    uint64_t *const out[2] = {pol->d, rp ? polP->d : nullptr};
+    const size_t bs[2] = {pol->view().bstride, rp ? polP->view().bstride : 0};
+    auto sum = [&](uint64_t *drawn) -> int {  // ReadAndAdd: the sum is a launch of its own, per part
+        const View t0{drawn, words[0]};
+        HIP_TRY(launch_ew(r->dev, ident_tab(nl[0]), EW_ADD, pol->view(), t0, pol->view(), B, nullptr, nullptr, c.stream));
+        if (rp) {
+            const View t1{drawn + (size_t)B * words[0], words[1]};
+            HIP_TRY(launch_ew(rp->dev, ident_tab(nl[1]), EW_ADD, polP->view(), t1, polP->view(), B, nullptr, nullptr, c.stream));
+        }
+        return HE_OK;
+    };
+    return uniform_read_run(who, c, *g, N, B, nparts, mc, nl, out, bs, add != 0, sum);
+}
+// The Reads of one uniform call into raw storage: part k (k < nparts) into limbs 0..nl[k]-1 of the B entries at out[k], bs[k] words
+// apart, with the modulus records mc[k].  add: the draw lands in scratch (part 0's B entries, then part 1's) and sum(scratch) adds it.
+static int uniform_read_run(const char *who, Ctx &c, Prng &g, int N, int B, int nparts, const ModConst *const mc[2], const int nl[2],
+                            uint64_t *const out[2], const size_t bs[2], bool add, const std::function<int(uint64_t *)> &sum) {
+    const size_t words[2] = {(size_t)nl[0] * N, nparts > 1 ? (size_t)nl[1] * N : 0};
     const size_t entry_bytes = 8 * ((((words[0] + 127) & ~(size_t)127)) + ((words[1] + 127) & ~(size_t)127));
     SamplerScratch scratch;
     if (add) scratch.words = (size_t)B * (words[0] + words[1]);  // ReadAndAdd: the draw lands here and is added when the parse is through
     SamplerPart parts[2];
     auto set_parts = [&]() {
-        parts[0] = SamplerPart{r->dev.mc, add ? scratch.p : pol->d, add ? words[0] : pol->view().bstride, nl[0]};
-        if (rp) parts[1] = SamplerPart{rp->dev.mc, add ? scratch.p + (size_t)B * words[0] : polP->d, add ? words[1] : polP->view().bstride, nl[1]};
+        parts[0] = SamplerPart{mc[0], add ? scratch.p : out[0], add ? words[0] : bs[0], nl[0]};
+        if (nparts > 1) parts[1] = SamplerPart{mc[1], add ? scratch.p + (size_t)B * words[0] : out[1], add ? words[1] : bs[1], nl[1]};
     };
     bool direct = true;  // the one-thread-per-word launch, until a word is rejected
     auto parse = [&](const uint64_t *d_stream, size_t bytes, uint64_t *d_status, uint64_t *st) -> int {
@@ -5528,18 +5550,12 @@ int he_sampler_uniform_read(he_handle hr, int level, he_handle hrp, int levelP, 
         HIP_TRY(launch_sampler_uniform(d_stream, bytes / 8, parts, nparts, N, B, true, d_status, c.stream));
         return sampler_status(c, d_status, st);
     };
-    auto finish = [&]() -> int {
-        if (!add) return HE_OK;
-        const View t0{scratch.p, words[0]};
-        HIP_TRY(launch_ew(r->dev, ident_tab(nl[0]), EW_ADD, pol->view(), t0, pol->view(), B, nullptr, nullptr, c.stream));
-        if (rp) {
-            const View t1{scratch.p + (size_t)B * words[0], words[1]};
-            HIP_TRY(launch_ew(rp->dev, ident_tab(nl[1]), EW_ADD, polP->view(), t1, polP->view(), B, nullptr, nullptr, c.stream));
-        }
-        return HE_OK;
-    };
-    return sampler_run(who, c, *g, (size_t)B * entry_bytes, (size_t)B * entry_bytes, scratch, parse, finish);
+    auto finish = [&]() -> int { return add ? sum(scratch.p) : HE_OK; };
+    return sampler_run(who, c, g, (size_t)B * entry_bytes, (size_t)B * entry_bytes, scratch, parse, finish);
 }
+// The parse of one Gaussian call: the small values of B entries (launch_sampler_gaussian's words) in scratch, handed to finish(vals),
+// which enqueues what becomes of them; they are zeroed before the call returns.
+static int gaussian_parse_run(const char *who, Ctx &c, Prng &g, int N, int B, double sigma, double bound, const std::function<int(const uint64_t *)> &use);
 // the launches after the parse of a Gaussian or ternary call: the small values into limbs 0..level of pol
 int he_sampler_gaussian_read(he_handle hr, int level, he_handle hg, double sigma, double bound, int montgomery, int add, he_handle hpol) {
     static const char *who = "he_sampler_gaussian_read";
@@ -5552,6 +5568,12 @@ int he_sampler_gaussian_read(he_handle hr, int level, he_handle hg, double sigma
     if (!(bound >= 0.0) || bound > 0x1p62) return fail(HE_EINVAL, "%s: bound = %g is not in [0, 2^62]", who, bound);
     Ctx &c = *r->ctx;
     const int N = r->N, B = pol->batch;
+    return gaussian_parse_run(who, c, *g, N, B, sigma, bound, [&](const uint64_t *vals) -> int {
+        HIP_TRY(launch_sampler_expand(r->dev.mc, vals, true, add != 0, montgomery != 0, nullptr, nullptr, pol->view(), N, level + 1, B, c.stream));
+        return HE_OK;
+    });
+}
+static int gaussian_parse_run(const char *who, Ctx &c, Prng &g, int N, int B, double sigma, double bound, const std::function<int(const uint64_t *)> &use) {
     const size_t entry = ((size_t)N * 8 + 1023) & ~(size_t)1023, ahead = ((size_t)N * 8 + N / 2 + 2047) & ~(size_t)1023;
     SamplerScratch scratch;
     scratch.words = (size_t)B * N + 192;
@@ -5562,11 +5584,8 @@ int he_sampler_gaussian_read(he_handle hr, int level, he_handle hg, double sigma
         HIP_TRY(launch_sampler_gaussian(d_stream, bytes / 8, d_tab, sigma, bound, scratch.p, N, B, d_status, c.stream));
         return sampler_status(c, d_status, st);
     };
-    auto finish = [&]() -> int {
-        HIP_TRY(launch_sampler_expand(r->dev.mc, scratch.p, true, add != 0, montgomery != 0, nullptr, nullptr, pol->view(), N, level + 1, B, c.stream));
-        return HE_OK;
-    };
-    return sampler_run(who, c, *g, (size_t)B * entry, (size_t)B * ahead, scratch, parse, finish);
+    auto finish = [&]() -> int { return use(scratch.p); };
+    return sampler_run(who, c, g, (size_t)B * entry, (size_t)B * ahead, scratch, parse, finish);
 }
 // sampleProba: the two-bit form (half) or the Knuth-Yao walk over the rows cut from x0 / x1
 static int ternary_run(const char *who, he_handle hr, int level, he_handle hg, bool half, uint64_t x0, uint64_t x1, int montgomery, int add,
@@ -5962,6 +5981,448 @@ int he_decryptor_decrypt(he_handle hdec, int ct_level, int pt_level, int is_ntt,
     TRY(rlwe_distinct(who, &pt, 1, others, degree + 2));
     const int rc = decrypt(*d, who, level, is_ntt, degree, ct, pt);
     const int rs = rlwe_frame_end(d->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+
+// ---------------------------------------------------------------------------------------
+// rlwe.KeyGenerator (include/hering_keygen.h; core/rlwe/keygenerator.go).  The secret keys, the relinearization key and the Galois
+// keys are compositions in front of keygen_evaluation_key, which draws row by row into the key's own storage and then finishes
+// every row at once (launch_evk_finish).
+// ---------------------------------------------------------------------------------------
+struct KeyGen : Obj, RlweFrame {
+    std::shared_ptr<Prng> prng_keep;
+    he_handle prng = 0;
+    double xs_p = 0, sigma = 0, bound = 0;
+    KeyGen() : Obj(T_KEYGEN) {}
+    ~KeyGen() override {
+        if (prng) reg_drop(prng);
+    }
+};
+int he_keygen_create(he_handle hev, he_handle hprng, double xs_p, double xe_sigma, double xe_bound, he_handle *out) {
+    static const char *who = "he_keygen_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(g, Prng, hprng, T_PRNG);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    TRY(ternary_density(xs_p, who));
+    if (!(xe_sigma > 0.0) || xe_sigma > 0x1p53 || !(xe_bound >= 0.0) || xe_bound > 0x1p62)
+        return fail(HE_EINVAL, "%s: Xe = {%g, %g}: sigma in (0, 2^53] and bound in [0, 2^62] (hering_sampler.h)", who, xe_sigma, xe_bound);
+    auto k = std::make_shared<KeyGen>();
+    k->bind(ev);
+    k->prng_keep = g;
+    k->prng = reg(g);
+    k->xs_p = xs_p;
+    k->sigma = xe_sigma;
+    k->bound = xe_bound;
+    *out = reg(k);
+    return HE_OK;
+}
+int he_keygen_destroy(he_handle h) { return unreg(h, T_KEYGEN); }
+
+// sampleSparse (ring/sampler_ternary.go:198-263).  The walk is sequential over bytes that are on the host: it is made here, into
+// the indices of matrixValues per coefficient, which one launch of the ternary expansion then writes into every limb.
+int he_keygen_ternary_sparse_read(he_handle hr, int level, he_handle hg, int hw, int montgomery, he_handle hpol) {
+    static const char *who = "he_keygen_ternary_sparse_read";
+    GET(r, Ring, hr, T_RING);
+    GET(g, Prng, hg, T_PRNG);
+    std::shared_ptr<Poly> pol;
+    TRY(sampler_poly(*r, level, hpol, 1, "pol", who, &pol));
+    if (hw <= 0) return fail(HE_EINVAL, "%s: a Hamming weight of %d", who, hw);
+    Ctx &c = *r->ctx;
+    if (c.capturing) return fail(HE_EINVAL, "%s: host transfers cannot be captured in a graph", who);
+    const int N = r->N;
+    if (hw > N) hw = N;  // :202-204
+    uint64_t lut1[kMaxLimbs], lut2[kMaxLimbs];  // matrixValues[k][1], [2] (:82-104)
+    for (int i = 0; i <= level; i++) {
+        const uint64_t q = r->moduli[i];
+        lut1[i] = montgomery ? to_mont(1, q) : 1;
+        lut2[i] = montgomery ? to_mont(q - 1, q) : q - 1;
+    }
+    std::lock_guard<std::mutex> lk(g->mu);
+    const size_t nsign = ((size_t)hw + 7) / 8, expected = nsign + 4 * (size_t)hw, cap = expected * 64;
+    std::vector<uint64_t> vals((size_t)N, 0);
+    std::vector<uint32_t> index((size_t)N);
+    for (int i = 0; i < N; i++) index[(size_t)i] = (uint32_t)i;
+    auto wipe_host = [&]() {
+        Prng::wipe(vals.data(), vals.size() * 8);
+        Prng::wipe(index.data(), index.size() * 4);
+    };
+    size_t off = nsign;  // :216-222: the sign bytes first
+    int rc = g->fetch(expected + expected / 2, who);
+    for (int i = 0; i < hw && rc == HE_OK; i++) {
+        const uint32_t left = (uint32_t)(N - i);
+        const uint32_t mask = (uint32_t)(((uint64_t)1 << (64 - __builtin_clzll((uint64_t)left))) - 1);  // :230
+        uint32_t j;
+        do {  // randInt32 (:232-236): four bytes, big-endian, masked
+            if (off + 4 > g->buf.size()) {
+                const size_t want = std::max(off + 4, g->buf.size() * 2);
+                if (want > cap) rc = fail(HE_EPRNG, "%s: the source did not let the call finish within %zu bytes (64 times the expected %zu)", who, cap, expected);
+                else rc = g->fetch(want, who);
+                if (rc != HE_OK) break;
+            }
+            const uint8_t *b = g->buf.data() + off;
+            j = (((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | (uint32_t)b[3]) & mask;
+            off += 4;
+        } while (j >= left);
+        if (rc != HE_OK) break;
+        const uint64_t coeff = (g->buf[(size_t)i >> 3] >> (i & 7)) & 1;  // :238 (0: +1, 1: -1)
+        vals[index[j]] = coeff + 1;                                        // :240-244
+        index[j] = index[left - 1];                                        // :247-248
+    }
+    if (rc != HE_OK) {
+        wipe_host();
+        return rc;
+    }
+    {
+        Scope sc(&c);
+        if ((rc = c.arena_reserve((size_t)N + 8)) != HE_OK) {
+            wipe_host();
+            return rc;
+        }
+        uint64_t *d_vals = c.arena_take((size_t)N);
+        HIP_TRY(hipMemcpyAsync(d_vals, vals.data(), (size_t)N * 8, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(launch_sampler_expand(r->dev.mc, d_vals, false, false, false, lut1, lut2, pol->view(), N, level + 1, 1, c.stream));
+        HIP_TRY(hipMemsetAsync(d_vals, 0, (size_t)N * 8, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+    }
+    wipe_host();
+    g->consume(off);
+    return HE_OK;
+}
+
+// a secret-key operand or output: a polynomial of the generator's context and degree with `limbs` limbs, batch 1
+static int keygen_poly(const KeyGen &k, const char *who, he_handle h, int limbs, const char *name, std::shared_ptr<Poly> *out) {
+    auto p = get<Poly>(h, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle for %s", who, name);
+    if (p->ctx.get() != &k.ctx() || p->N != k.ev->be->Q->N) return fail(HE_EINVAL, "%s: %s is not a polynomial of the generator's rings", who, name);
+    if (p->nlimbs < limbs) return fail(HE_EINVAL, "%s: %s has %d limbs, %d needed", who, name, p->nlimbs, limbs);
+    if (p->batch != 1) return fail(HE_EINVAL, "%s: %s has %d entries; a secret key is one polynomial", who, name, p->batch);
+    if (out) *out = p;
+    return HE_OK;
+}
+static int keygen_sk_levels(const KeyGen &k, const char *who, int levelQ, int levelP, he_handle skQ, he_handle skP) {
+    if (levelQ < 0 || levelQ > k.maxQ()) return fail(HE_EINVAL, "%s: levelQ %d, the ring has levels 0..%d", who, levelQ, k.maxQ());
+    if (levelP < -1 || levelP > k.maxP()) return fail(HE_EINVAL, "%s: levelP %d, ringP has levels -1..%d", who, levelP, k.maxP());
+    TRY(keygen_poly(k, who, skQ, levelQ + 1, "skQ", nullptr));
+    if (levelP >= 0) {
+        TRY(keygen_poly(k, who, skP, levelP + 1, "skP", nullptr));
+        TRY(rlwe_distinct(who, &skQ, 1, &skP, 1));
+    }
+    return HE_OK;
+}
+// genSecretKeyFromSampler (:64-69) after the Read
+static int keygen_sk_finish(KeyGen &k, int levelQ, int levelP, he_handle skQ, he_handle skP) {
+    if (levelP >= 0) TRY(he_centered_lift(k.hev, 3, skQ, levelQ + 1, levelQ, skQ, levelP, skP));
+    TRY(he_ntt(k.hq, levelQ, skQ, skQ));
+    if (levelP >= 0) TRY(he_ntt(k.hp, levelP, skP, skP));
+    TRY(he_mform(k.hq, levelQ, skQ, skQ));
+    if (levelP >= 0) TRY(he_mform(k.hp, levelP, skP, skP));
+    return HE_OK;
+}
+int he_keygen_secret_key(he_handle hk, int levelQ, int levelP, he_handle skQ, he_handle skP) {
+    static const char *who = "he_keygen_secret_key";
+    GET(k, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(k->ctx(), who));
+    TRY(keygen_sk_levels(*k, who, levelQ, levelP, skQ, skP));
+    int rc = he_sampler_ternary_read(k->hq, levelQ, k->prng, k->xs_p, 0, 0, skQ);  // :62
+    if (rc == HE_OK) rc = keygen_sk_finish(*k, levelQ, levelP, skQ, skP);
+    const int rs = rlwe_frame_end(k->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_keygen_secret_key_hw(he_handle hk, int hw, int levelQ, int levelP, he_handle skQ, he_handle skP) {
+    static const char *who = "he_keygen_secret_key_hw";
+    GET(k, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(k->ctx(), who));
+    if (hw <= 0) return fail(HE_EINVAL, "%s: a Hamming weight of %d", who, hw);
+    TRY(keygen_sk_levels(*k, who, levelQ, levelP, skQ, skP));
+    int rc = he_keygen_ternary_sparse_read(k->hq, levelQ, k->prng, hw, 0, skQ);  // :50, montgomery = false
+    if (rc == HE_OK) rc = keygen_sk_finish(*k, levelQ, levelP, skQ, skP);
+    const int rs = rlwe_frame_end(k->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+
+// The gadget vector of a key, row by row: G[row][index] = MForm(P 2^(j pw2) mod q_index) on the Q limbs of the row's digit
+// (gadgetciphertext.go:183-237), 0 elsewhere.  P: the product of the key's special primes (1 without).
+static std::vector<uint64_t> gadget_table(const Evk &k) {
+    const BasisExtender &be = *k.ev->be;
+    const int nQk = k.nQk, alpha = std::max(k.nPk, 1), nrns = k.pw2 ? (int)k.nj.size() : k.beta;
+    std::vector<uint64_t> G((size_t)k.beta * nQk, 0);
+    for (int i = 0; i < nrns; i++) {
+        const int nji = k.pw2 ? k.nj[(size_t)i] : 1;
+        for (int j = 0; j < nji; j++) {
+            const int row = k.pw2 ? k.prefix[(size_t)i] + j : i;
+            for (int kk = 0; kk < alpha; kk++) {
+                const int index = i * alpha + kk;
+                if (index >= nQk) break;  // (:218: #pj does not divide #qi)
+                const uint64_t q = be.Q->moduli[(size_t)index];
+                uint64_t f = 1 % q;
+                for (int t = 0; t < k.nPk; t++) f = mulmod(f, be.P->moduli[(size_t)t] % q, q);
+                for (int t = 0; t < j; t++) f = mulmod(f, ((uint64_t)1 << k.pw2) % q, q);  // (:237, once per window)
+                G[(size_t)row * nQk + index] = to_mont(f, q);
+            }
+        }
+    }
+    return G;
+}
+static int evk_shape_for_keygen(const Evk &k, const char *who, const char *name) {
+    if (!k.pw2 && k.beta != base_rns_size(k.nQk - 1, k.nPk - 1))
+        return fail(HE_EINVAL, "%s: %s has %d digits; a key at levels (%d, %d) has %d", who, name, k.beta, k.nQk - 1, k.nPk - 1, base_rns_size(k.nQk - 1, k.nPk - 1));
+    if (k.pw2 && (int)k.nj.size() != k.nQk) return fail(HE_EINVAL, "%s: %s: one RNS digit per key Q-limb is required", who, name);
+    if (k.nQk + k.nPk > kMaxLimbs) return fail(HE_EINVAL, "%s: %s has %d limbs per row, at most %d", who, name, k.nQk + k.nPk, kMaxLimbs);
+    return HE_OK;
+}
+static void evk_rows_args(const Evk &k, EvkRowsArgs &a) {
+    const BasisExtender &be = *k.ev->be;
+    a.key = k.d;
+    a.blk = (size_t)(k.nQk + k.nPk) * be.Q->N;
+    a.N = be.Q->N; a.rows = k.beta; a.nq = k.nQk; a.np = k.nPk;
+    a.mc = be.qp.mc;
+    for (int i = 0; i < k.nQk; i++) a.mod[i] = (uint8_t)i;
+    for (int i = 0; i < k.nPk; i++) a.mod[k.nQk + i] = (uint8_t)(be.LQ + i);
+}
+// the gadget table of k in scratch (the caller holds the context and has reserved beta nQk + 2 words more)
+// (G is the caller's: it outlives the copy, which the caller's drain of the stream ends)
+static int gadget_table_upload(Ctx &c, const Evk &k, std::vector<uint64_t> &G, const uint64_t **d_G) {
+    G = gadget_table(k);
+    uint64_t *p = c.arena_take(G.size());
+    HIP_TRY(hipMemcpyAsync(p, G.data(), G.size() * 8, hipMemcpyHostToDevice, c.stream));
+    *d_G = p;
+    return HE_OK;
+}
+int he_gadget_add_poly(he_handle hpt, he_handle hk0, he_handle hk1) {
+    static const char *who = "he_gadget_add_poly";
+    GET(k0, Evk, hk0, T_EVK);
+    std::shared_ptr<Evk> k1;
+    if (hk1) {
+        k1 = get<Evk>(hk1, T_EVK);
+        if (!k1) return fail(HE_EHANDLE, "%s: bad Evk handle for evk1", who);
+        if (k1 == k0) return fail(HE_EINVAL, "%s: evk0 and evk1 are one key", who);
+        if (k1->ev != k0->ev || k1->beta != k0->beta || k1->nQk != k0->nQk || k1->nPk != k0->nPk || k1->pw2 != k0->pw2 || k1->nj != k0->nj)
+            return fail(HE_EINVAL, "%s: evk0 and evk1 differ in evaluator or shape", who);
+    }
+    TRY(evk_shape_for_keygen(*k0, who, "evk0"));
+    BasisExtender &be = *k0->ev->be;
+    Ctx &c = *be.ctx;
+    auto pt = get<Poly>(hpt, T_POLY);
+    if (!pt) return fail(HE_EHANDLE, "%s: bad Poly handle for pt", who);
+    if (pt->ctx != be.ctx || pt->N != be.Q->N || pt->nlimbs < k0->nQk || pt->batch != 1)
+        return fail(HE_EINVAL, "%s: pt must be one polynomial of the key's ringQ with %d limbs", who, k0->nQk);
+    if (c.capturing) return fail(HE_EINVAL, "%s: not inside a graph capture", who);
+    Scope sc(&c);
+    TRY(c.arena_reserve((size_t)k0->beta * k0->nQk + 8));
+    EvkRowsArgs a;
+    evk_rows_args(*k0, a);
+    a.pt = pt->d;
+    std::vector<uint64_t> G;
+    TRY(gadget_table_upload(c, *k0, G, &a.G));
+    for (int u = 0; u < (k1 ? 2 : 1); u++) {  // `for u, ct := range cts` (:225): component u of key u
+        Evk &k = u ? *k1 : *k0;
+        a.key = k.d;
+        a.comp = u;
+        HIP_TRY(launch_gadget_add(a, c.stream));
+        TRY(evk_derive(k));
+    }
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+
+// genEvaluationKey (:287-330) without the frame.  skIn (nQk limbs), skOut = (skOutQ, skOutP): device words, NTT and Montgomery.
+static int keygen_evaluation_key(KeyGen &kg, const char *who, const uint64_t *skIn, const uint64_t *skOutQ, const uint64_t *skOutP, Evk &k) {
+    BasisExtender &be = *kg.ev->be;
+    Ctx &c = *be.ctx;
+    Prng &g = *kg.prng_keep;
+    const int N = be.Q->N, R = k.beta, nQk = k.nQk, nPk = k.nPk;
+    const size_t blk = (size_t)(nQk + nPk) * N;
+    // the small values of every row's Gaussian, [R][N]: outside the arena, which every draw resets
+    const size_t stage_bytes = (size_t)R * N * 8;
+    uint64_t *d_e = nullptr;
+    {
+        Scope sc(&c);
+        HIP_TRY(c.pool_take(stage_bytes, (void **)&d_e));
+    }
+    int rc = HE_OK;
+    const ModConst *const mc[2] = {be.Q->dev.mc, nPk ? be.P->dev.mc : nullptr};
+    const int nl[2] = {nQk, nPk};
+    const size_t bs[2] = {2 * blk, 2 * blk};
+    for (int r = 0; r < R && rc == HE_OK; r++) {  // one encryptZeroSk per row (:309-320): the uniform c1 (Q, then P), then the Gaussian e
+        uint64_t *c1 = k.d + ((size_t)2 * r + 1) * blk;
+        uint64_t *const out[2] = {c1, c1 + (size_t)nQk * N};
+        rc = uniform_read_run(who, c, g, N, 1, nPk ? 2 : 1, mc, nl, out, bs, false, nullptr);
+        if (rc != HE_OK) break;
+        rc = gaussian_parse_run(who, c, g, N, 1, kg.sigma, kg.bound, [&](const uint64_t *vals) -> int {
+            HIP_TRY(hipMemcpyAsync(d_e + (size_t)r * N, vals, (size_t)N * 8, hipMemcpyDeviceToDevice, c.stream));
+            return HE_OK;
+        });
+    }
+    Scope sc(&c);
+    std::vector<uint64_t> G;
+    if (rc == HE_OK) rc = [&]() -> int {
+        TRY(c.arena_reserve((size_t)R * nQk + 8));
+        const View c0{k.d, 2 * blk};
+        // encryptor.go:411-414: the Gaussian words on the Q limbs and their centred copies on the P limbs, every row at once
+        HIP_TRY(launch_sampler_expand(be.qp.mc, d_e, true, false, false, nullptr, nullptr, c0, N, nQk, R, c.stream));
+        if (nPk)
+            HIP_TRY(launch_sampler_expand(be.qp.mc + be.LQ, d_e, true, false, false, nullptr, nullptr, View{k.d + (size_t)nQk * N, 2 * blk}, N, nPk, R, c.stream));
+        LimbTab tab = ident_tab(nQk + nPk);
+        for (int i = 0; i < nPk; i++) tab.mod[nQk + i] = (uint8_t)(be.LQ + i);
+        HIP_TRY(be_ntt(be, tab, c0, c0, R, false, NTT_REDUCE_INPUT));  // :416-418
+        EvkRowsArgs a;
+        evk_rows_args(k, a);
+        a.skOutQ = skOutQ; a.skOutP = skOutP; a.pt = skIn;
+        TRY(gadget_table_upload(c, k, G, &a.G));
+        c.acct(3.0 * (nQk + nPk), 0, R, N);
+        HIP_TRY(launch_evk_finish(a, c.stream));  // :420-425 and AddPolyTimesGadgetVectorToGadgetCiphertext (:326)
+        TRY(evk_derive(k));
+        k.word_mul = 1;
+        return HE_OK;
+    }();
+    (void)hipMemsetAsync(d_e, 0, stage_bytes, c.stream);
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    c.pool_give(stage_bytes, d_e);
+    return rc;
+}
+// the key operand of a generation call: a key of the generator's evaluator with a shape genEvaluationKey serves
+static int keygen_evk(const KeyGen &kg, const char *who, he_handle h, std::shared_ptr<Evk> *out) {
+    auto k = get<Evk>(h, T_EVK);
+    if (!k) return fail(HE_EHANDLE, "%s: bad Evk handle %llu", who, (unsigned long long)h);
+    if (k->ev != kg.ev) return fail(HE_EINVAL, "%s: the key belongs to another evaluator than the generator", who);
+    TRY(evk_shape_for_keygen(*k, who, "the key"));
+    *out = k;
+    return HE_OK;
+}
+// sk = (skQ, skP) at the levels of key k
+static int keygen_sk_for(const KeyGen &kg, const char *who, const Evk &k, he_handle skQ, he_handle skP, const char *nameQ, const char *nameP,
+                         std::shared_ptr<Poly> *q, std::shared_ptr<Poly> *p) {
+    TRY(keygen_poly(kg, who, skQ, k.nQk, nameQ, q));
+    if (k.nPk) TRY(keygen_poly(kg, who, skP, k.nPk, nameP, p));
+    return HE_OK;
+}
+int he_keygen_evaluation_key(he_handle hk, he_handle skInQ, he_handle skOutQ, he_handle skOutP, he_handle hevk) {
+    static const char *who = "he_keygen_evaluation_key";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    std::shared_ptr<Evk> k;
+    TRY(keygen_evk(*kg, who, hevk, &k));
+    std::shared_ptr<Poly> in, oq, op;
+    TRY(keygen_poly(*kg, who, skInQ, k->nQk, "skInQ", &in));
+    TRY(keygen_sk_for(*kg, who, *k, skOutQ, skOutP, "skOutQ", "skOutP", &oq, &op));
+    { Scope sc(&kg->ctx()); }  // (after the calling thread's queued requests)
+    return keygen_evaluation_key(*kg, who, in->d, oq->d, op ? op->d : nullptr, *k);
+}
+// GenEvaluationKey (:261-285): the two secret keys may live in rings of a smaller degree and at other levels
+int he_keygen_evaluation_key_sk(he_handle hk, he_handle skInQ, he_handle skOutQ, he_handle hevk) {
+    static const char *who = "he_keygen_evaluation_key_sk";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    std::shared_ptr<Evk> k;
+    TRY(keygen_evk(*kg, who, hevk, &k));
+    auto in = get<Poly>(skInQ, T_POLY), out = get<Poly>(skOutQ, T_POLY);
+    if (!in || !out) return fail(HE_EHANDLE, "%s: bad Poly handle for %s", who, in ? "skOutQ" : "skInQ");
+    const int N = kg->ev->be->Q->N;
+    for (const auto &p : {in, out})
+        if (p->ctx.get() != &kg->ctx() || p->batch != 1 || p->N > N || p->N < 16 || (p->N & (p->N - 1)))
+            return fail(HE_EINVAL, "%s: a secret key is one polynomial of the generator's context, of a degree in [16, %d]", who, N);
+    const int lin = std::min(in->nlimbs, kg->maxQ() + 1) - 1, lout = std::min(out->nlimbs, kg->maxQ() + 1) - 1;
+    if (lout < k->nQk - 1) return fail(HE_EINVAL, "%s: skOutQ has %d limbs, the key's levelQ needs %d", who, out->nlimbs, k->nQk);
+    const int levelP = k->nPk - 1;
+    TmpPoly bOutQ, bOutP, bIn, b0;
+    int rc = bOutQ.alloc(kg->hq, lout + 1, 1);
+    if (rc == HE_OK) rc = bIn.alloc(kg->hq, lout + 1, 1);
+    if (rc == HE_OK) rc = b0.alloc(kg->hq, 1, 1);
+    if (rc == HE_OK && levelP >= 0) rc = bOutP.alloc(kg->hp, levelP + 1, 1);
+    if (rc == HE_OK) rc = he_map_small_to_large_ntt(skOutQ, bOutQ.h, lout);  // :271
+    if (rc == HE_OK && levelP >= 0) {  // :276-278, ExtendBasisSmallNormAndCenterNTTMontgomery (utils.go:250-284) into P
+        rc = he_intt(kg->hq, 0, bOutQ.h, b0.h);
+        if (rc == HE_OK) rc = he_imform(kg->hq, 0, b0.h, b0.h);
+        if (rc == HE_OK) rc = he_centered_lift(kg->hev, 3, b0.h, 1, 0, b0.h, levelP, bOutP.h);
+        if (rc == HE_OK) rc = he_ntt(kg->hp, levelP, bOutP.h, bOutP.h);
+        if (rc == HE_OK) rc = he_mform(kg->hp, levelP, bOutP.h, bOutP.h);
+    }
+    if (rc == HE_OK) rc = he_map_small_to_large_ntt(skInQ, bIn.h, lin);  // :281
+    if (rc == HE_OK) rc = he_intt(kg->hq, 0, bIn.h, bIn.h);              // :282: limbs 0..lout of skIn from its limb 0
+    if (rc == HE_OK) rc = he_imform(kg->hq, 0, bIn.h, bIn.h);
+    if (rc == HE_OK) rc = he_centered_lift(kg->hev, 3, bIn.h, 1, lout, bIn.h, -1, 0);
+    if (rc == HE_OK) rc = he_ntt(kg->hq, lout, bIn.h, bIn.h);
+    if (rc == HE_OK) rc = he_mform(kg->hq, lout, bIn.h, bIn.h);
+    if (rc == HE_OK) {
+        { Scope sc(&kg->ctx()); }
+        rc = keygen_evaluation_key(*kg, who, get<Poly>(bIn.h, T_POLY)->d, get<Poly>(bOutQ.h, T_POLY)->d, levelP >= 0 ? get<Poly>(bOutP.h, T_POLY)->d : nullptr, *k);  // :284
+    }
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_keygen_relinearization_key(he_handle hk, he_handle skQ, he_handle skP, he_handle hrlk) {
+    static const char *who = "he_keygen_relinearization_key";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    std::shared_ptr<Evk> k;
+    TRY(keygen_evk(*kg, who, hrlk, &k));
+    std::shared_ptr<Poly> q, p;
+    TRY(keygen_sk_for(*kg, who, *k, skQ, skP, "skQ", "skP", &q, &p));
+    TmpPoly sk2;  // (:114-118; cleared before it goes back to the pool)
+    TRY(sk2.alloc(kg->hq, k->nQk, 1));
+    int rc = he_mul_coeffs_montgomery(kg->hq, k->nQk - 1, skQ, skQ, sk2.h);
+    if (rc == HE_OK) {
+        { Scope sc(&kg->ctx()); }
+        rc = keygen_evaluation_key(*kg, who, get<Poly>(sk2.h, T_POLY)->d, q->d, p ? p->d : nullptr, *k);
+    }
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+// GenGaloisKey (:140-177) without the frame
+static int keygen_galois_key(KeyGen &kg, const char *who, uint64_t gal, he_handle skQ, he_handle skP, he_handle hgk) {
+    if (!(gal & 1)) return fail(HE_EINVAL, "%s: the Galois element %llu is even", who, (unsigned long long)gal);
+    std::shared_ptr<Evk> k;
+    TRY(keygen_evk(kg, who, hgk, &k));
+    std::shared_ptr<Poly> q, p;
+    TRY(keygen_sk_for(kg, who, *k, skQ, skP, "skQ", "skP", &q, &p));
+    const Ring &Q = *kg.ev->be->Q;
+    gal = reduce_gal(gal, Q.logN, Q.type);
+    // a conjugate-invariant ring has the automorphisms 5^k alone: for -5^k (3 modulo 4) AutomorphismNTTIndex(N, 4N, .) holds
+    // positions in [N, 2N), an index panic in the reference's AutomorphismNTTWithIndex
+    if (Q.type == 1 && (gal & 3) != 1)
+        return fail(HE_EINVAL, "%s: the Galois element %llu is not a power of 5 modulo 4N (conjugate-invariant ring)", who, (unsigned long long)gal);
+    uint64_t inv = gal;  // ModInvGaloisElement (:157): the inverse modulo NthRoot, a power of two (five Newton steps double 3 bits to 96)
+    for (int i = 0; i < 5; i++) inv *= 2 - gal * inv;
+    inv = reduce_gal(inv, Q.logN, Q.type);
+    he_handle hix = 0;
+    TRY(he_automorphism_index_create(kg.hq, inv, &hix));  // :159
+    TmpPoly oq, op;
+    int rc = oq.alloc(kg.hq, k->nQk, 1);
+    if (rc == HE_OK && k->nPk) rc = op.alloc(kg.hp, k->nPk, 1);
+    if (rc == HE_OK) rc = he_automorphism_ntt_with_index(kg.hq, k->nQk - 1, skQ, hix, oq.h);            // :167
+    if (rc == HE_OK && k->nPk) rc = he_automorphism_ntt_with_index(kg.hp, k->nPk - 1, skP, hix, op.h);  // :169-171
+    if (rc == HE_OK) {
+        { Scope sc(&kg.ctx()); }
+        rc = keygen_evaluation_key(kg, who, q->d, get<Poly>(oq.h, T_POLY)->d, k->nPk ? get<Poly>(op.h, T_POLY)->d : nullptr, *k);  // :173
+    }
+    (void)he_automorphism_index_destroy(hix);
+    return rc;
+}
+int he_keygen_galois_key(he_handle hk, uint64_t gal_el, he_handle skQ, he_handle skP, he_handle gk) {
+    static const char *who = "he_keygen_galois_key";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    const int rc = keygen_galois_key(*kg, who, gal_el, skQ, skP, gk);
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_keygen_galois_keys(he_handle hk, int n, const uint64_t *gal_els, he_handle skQ, he_handle skP, const he_handle *gks) {
+    static const char *who = "he_keygen_galois_keys";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    if (n < 0 || (n > 0 && (!gal_els || !gks))) return fail(HE_EINVAL, "%s: %d keys with a null array", who, n);
+    for (int i = 0; i < n; i++) {  // (every check before the first draw)
+        if (!(gal_els[i] & 1) || (kg->ev->be->Q->type == 1 && (gal_els[i] & 3) != 1))
+            return fail(HE_EINVAL, "%s: the Galois element %llu is even, or not a power of 5 on a conjugate-invariant ring", who, (unsigned long long)gal_els[i]);
+        std::shared_ptr<Evk> k;
+        TRY(keygen_evk(*kg, who, gks[i], &k));
+        TRY(keygen_sk_for(*kg, who, *k, skQ, skP, "skQ", "skP", nullptr, nullptr));
+        for (int j = 0; j < i; j++)
+            if (gks[j] == gks[i]) return fail(HE_EINVAL, "%s: gks[%d] and gks[%d] are one key", who, j, i);
+    }
+    int rc = HE_OK;
+    for (int i = 0; i < n && rc == HE_OK; i++) rc = keygen_galois_key(*kg, who, gal_els[i], skQ, skP, gks[i]);  // :189-195, key after key
+    const int rs = rlwe_frame_end(kg->ctx());
     return rc != HE_OK ? rc : rs;
 }
 

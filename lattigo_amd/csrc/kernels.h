@@ -528,6 +528,27 @@ hipError_t launch_sampler_ternary(const uint8_t *stream, size_t avail_bytes, boo
 hipError_t launch_sampler_expand(const ModConst *mc, const uint64_t *vals, bool gaussian, bool add, bool mont, const uint64_t *lut1,
                                  const uint64_t *lut2, View out, int N, int nl, int batch, hipStream_t s);
 
+// ---- key generation (core/rlwe/keygenerator.go:287-330, gadgetciphertext.go:172-241; include/hering_keygen.h) -----------------
+// A key as Evk::rows() views it: R rows of two components, component c of row r at key + (2 r + c) blk, each nq + np limbs of N
+// words; limb y has the modulus record mc[mod[y]].  G: a device table [R][nq] -- MForm(P 2^(j pw2) mod q_y) on the Q limbs of the
+// row's own digit and 0 elsewhere (the factor is never 0 modulo a prime q_y); null: no gadget term.  No entry tables.
+struct EvkRowsArgs {
+    uint64_t *key = nullptr;
+    size_t blk = 0;
+    int N = 0, rows = 0, nq = 0, np = 0;
+    const ModConst *mc = nullptr;
+    uint8_t mod[kMaxLimbs];
+    const uint64_t *skOutQ = nullptr, *skOutP = nullptr;  // nq / np limbs, NTT and Montgomery (launch_evk_finish)
+    const uint64_t *pt = nullptr;                         // nq limbs, NTT and Montgomery: skIn / the plaintext; null with G null
+    const uint64_t *G = nullptr;
+    int comp = 0;                                         // launch_gadget_add: the component that receives the term
+};
+// encryptZeroSkFromC1QP (encryptor.go:420-425) and the gadget term over every row, in place: component 0 holds NTT(e), canonical,
+// component 1 the uniform c1;  c0 = CRed(MForm(c0) + q - MRed(c1, skOut)) [then CRed(c0 + MRed(pt, G))].  One launch.
+hipError_t launch_evk_finish(const EvkRowsArgs &a, hipStream_t s);
+// the gadget term alone: key[r][comp] = CRed(key[r][comp] + MRed(pt, G[r][y])) on the Q limbs where G is not 0
+hipError_t launch_gadget_add(const EvkRowsArgs &a, hipStream_t s);
+
 // ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
 // One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
 // ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
@@ -589,7 +610,8 @@ enum KernelId {
     K_PACK_PRE, K_PACK_POST, K_XPOW2_FILL, K_RGSW_FUSED, K_AUTO_FUSED, K_CI_BRIDGE_FOLD,
     K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64,
     K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
-    K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND, K_COUNT
+    K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND,
+    K_EVK_FINISH, K_GADGET_ADD, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

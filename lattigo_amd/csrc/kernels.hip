@@ -77,7 +77,7 @@ const char *kernel_name(int id) {
                                          "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize", "special_fft", "ckks_fft_pass",
                                          "special_ifft_quantize", "f64_to_rns", "rns_to_f64", "bgv_slots_to_t", "bgv_t_to_slots",
                                          "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
-                                         "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand"};
+                                         "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -5862,6 +5862,56 @@ hipError_t launch_sampler_expand(const ModConst *mc, const uint64_t *vals, bool 
     for (int j = 0; j < nl && !gaussian; j++) { A.lut1[j] = lut1[j]; A.lut2[j] = lut2[j]; }
     ProfScope ps(K_SAMPLER_EXPAND, s, ((add ? 2.0 : 1.0) * nl + 1.0) * (double)N * batch * 8.0);
     hipLaunchKernelGGL(sampler_expand_kernel, dim3((N + 255) / 256, nl, batch), dim3(256), 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// key generation (include/hering_keygen.h): the arithmetic of genEvaluationKey after its draws, over every row of a key at once.
+// Memory-bound: per word two key-sized reads (c0, c1) and one write; the secret-key limbs and the factor table are re-read by
+// every row and stay in L2.  Grid (coefficient pairs, limb, row): the limb is a block coordinate, so the modulus record, the row's
+// factor and "is this limb in the row's digit" are uniform per block; 16-byte accesses throughout.
+// ------------------------------------------------------------------------------------
+template <bool FINISH>
+__global__ void __launch_bounds__(256) evk_rows_kernel(EvkRowsArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, r = blockIdx.z;
+    const bool isq = y < A.nq;
+    const uint64_t g = (A.G && isq) ? A.G[(size_t)r * A.nq + y] : 0;
+    if (!FINISH && g == 0) return;
+    const ModConst m = A.mc[A.mod[y]];
+    const uint64_t q = m.q, qinv = m.qinv;
+    const size_t off = (size_t)y * A.N + j;
+    uint64_t *c0 = A.key + ((size_t)2 * r + (FINISH ? 0 : A.comp)) * A.blk + off;
+    ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(c0);
+    if (FINISH) {
+        const ulonglong2 c1 = ldnt2(A.key + ((size_t)2 * r + 1) * A.blk + off);
+        const uint64_t *skp = isq ? A.skOutQ + off : A.skOutP + (size_t)(y - A.nq) * A.N + j;
+        const ulonglong2 sk = *reinterpret_cast<const ulonglong2 *>(skp);
+        v.x = cred(mform(v.x, q, m.brc0, m.brc1) + (q - mred(c1.x, sk.x, q, qinv)), q);
+        v.y = cred(mform(v.y, q, m.brc0, m.brc1) + (q - mred(c1.y, sk.y, q, qinv)), q);
+    }
+    if (g != 0) {
+        const ulonglong2 p = *reinterpret_cast<const ulonglong2 *>(A.pt + off);
+        v.x = cred(v.x + mred(p.x, g, q, qinv), q);
+        v.y = cred(v.y + mred(p.y, g, q, qinv), q);
+    }
+    *reinterpret_cast<ulonglong2 *>(c0) = v;
+}
+static bool evk_rows_ok(const EvkRowsArgs &a) {
+    return a.key && a.mc && a.N >= 8 && a.N <= (1 << kMaxLogN) && (a.N & (a.N - 1)) == 0 && a.rows > 0 && a.rows <= 65535 && a.nq > 0 && a.np >= 0 &&
+           a.nq + a.np <= kMaxLimbs && a.blk >= (size_t)(a.nq + a.np) * a.N && (a.G == nullptr || a.pt != nullptr);
+}
+hipError_t launch_evk_finish(const EvkRowsArgs &a, hipStream_t s) {
+    if (!evk_rows_ok(a) || !a.skOutQ || (a.np > 0 && !a.skOutP)) return hipErrorInvalidValue;
+    ProfScope ps(K_EVK_FINISH, s, 3.0 * (a.nq + a.np) * (double)a.N * a.rows * 8.0);
+    hipLaunchKernelGGL((evk_rows_kernel<true>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq + a.np, a.rows), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_gadget_add(const EvkRowsArgs &a, hipStream_t s) {
+    if (!evk_rows_ok(a) || !a.G || a.comp < 0 || a.comp > 1) return hipErrorInvalidValue;
+    ProfScope ps(K_GADGET_ADD, s, 2.0 * a.nq * (double)a.N * 8.0);  // (each Q limb belongs to the digit of one row per window)
+    hipLaunchKernelGGL((evk_rows_kernel<false>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq, a.rows), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -120,7 +120,7 @@ class GaussianSampler:
 
 
 class TernarySampler:
-    """ring.NewTernarySampler(prng, baseRing, Ternary{P: P}, montgomery).  The sparse form (Ternary{H: h}) is not on the device."""
+    """ring.NewTernarySampler(prng, baseRing, Ternary{P: P}, montgomery).  The sparse form (Ternary{H: h}) is keygen.SparseTernarySampler."""
 
     def __init__(self, prng: PRNG, baseRing: Ring, P: float, montgomery: bool, _words=None):
         """_words: (x0, x1), the matrix words of he_debug_sampler_ternary_words instead of those of P (tests)"""

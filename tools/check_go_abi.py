@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The check of go/hering/*.go that is possible without a Go toolchain: every `C.he_*(...)` call names a function
-declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h, hering_bgv_encoder.h, hering_sampler.h, hering_encryptor.h), passes as many arguments as the declaration has parameters, and -- round 4 --
+declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h, hering_bgv_encoder.h, hering_sampler.h, hering_encryptor.h, hering_keygen.h), passes as many arguments as the declaration has parameters, and -- round 4 --
 every argument has the KIND the parameter wants (int / uint64_t / he_handle / he_handle* / uint64_t* / int*), judged from the
 shape of the Go expression (`C.int(..)`, `C.uint64_t(..)`, `x.h`, `&x.h`, `(*C.uint64_t)(unsafe.Pointer(..))`, identifiers whose
 declaration in the file names a Handle or a C pointer type); every `C.HE_*` constant exists in the header's enums.  Also
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_decls():
-    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h", "hering_bgv_encoder.h", "hering_sampler.h", "hering_encryptor.h"))
+    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h", "hering_bgv_encoder.h", "hering_sampler.h", "hering_encryptor.h", "hering_keygen.h"))
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls, kinds = {}, {}
     for m in re.finditer(r"\b(?:int|const char \*)\s*(he_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
@@ -128,6 +128,9 @@ BGV_ENCODER = ["Encode", "Embed", "EmbedScale", "Decode", "EncodeRingT", "Decode
 # ring.UniformSampler / GaussianSampler / TernarySampler (go/hering/sampler.go)
 SAMPLERS = {"UniformSampler": ["Read", "ReadAndAdd", "ReadQP", "ReadAndAddQP", "AtLevel"], "GaussianSampler": ["Read", "ReadAndAdd", "AtLevel"],
             "TernarySampler": ["Read", "ReadAndAdd", "AtLevel"]}                      # ring/sampler_uniform.go, sampler_gaussian.go, sampler_ternary.go
+# rlwe.KeyGenerator (go/hering/keygen.go)
+KEYGEN = ["GenSecretKey", "GenSecretKeyWithHammingWeight", "GenPublicKey", "GenRelinearizationKey", "GenGaloisKey", "GenGaloisKeys",
+          "GenEvaluationKey", "NewEvaluationKey"]                                    # core/rlwe/keygenerator.go:37-285
 SCHEMES = ["Add", "AddNew", "Sub", "SubNew", "Mul", "MulNew", "MulRelin", "MulRelinNew", "MulThenAdd", "Relinearize",
            "Rescale", "GetRLWEParameters"]                                            # schemes/schemes.go:14-28
 
@@ -205,6 +208,10 @@ def main():
         for m in want:
             if m not in have:
                 errors.append(f"go/hering: method {m} (ring.{t}) is not defined")
+    kg_methods = set(re.findall(r"func \(\w+ \*KeyGenerator\) (\w+)\(", src))
+    for m in KEYGEN:
+        if m not in kg_methods:
+            errors.append(f"go/hering: method {m} (rlwe.KeyGenerator) is not defined")
     print(f"{len(files)} Go files, {ncalls} C.he_* calls to {len(used)} of {len(decls)} declared entry points, {nchecked} of {nargs_total} "
           f"arguments kind-checked; {len(PROVIDER)} EvaluatorProvider + {len(SCHEMES)} schemes.Evaluator methods present; "
           f"rlwe.Evaluator also: {', '.join(m for m in EXTRA if m in methods)}; "
@@ -215,7 +222,8 @@ def main():
           f"bgv.Evaluator (scale-invariant): {', '.join(m for m in BFV if m in bfv_methods)}; "
           f"ckks.Encoder: {', '.join(m for m in ENCODER if m in enc_methods)}; "
           f"bgv.Encoder: {', '.join(m for m in BGV_ENCODER if m in bgv_enc_methods)}; "
-          f"ring samplers: {', '.join(SAMPLERS)}"
+          f"ring samplers: {', '.join(SAMPLERS)}; "
+          f"rlwe.KeyGenerator: {', '.join(m for m in KEYGEN if m in kg_methods)}"
           if not errors else "\n".join(errors))
     return 1 if errors else 0
 
