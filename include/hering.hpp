@@ -38,6 +38,7 @@
 #include "hering_sampler.h"
 #include "hering_encryptor.h"
 #include "hering_keygen.h"
+#include "hering_rgsw_encryptor.h"
 
 namespace hering {
 
@@ -1354,6 +1355,39 @@ public:
                                               opOut.Value.at(0).h(), opOut.Value.at(1).h()));
     }
 };
+// rgsw.NewCiphertext (elements.go:27): a zeroed ciphertext at the levels and BaseTwoDecomposition of evkParams
+inline Ciphertext NewCiphertext(const rlwe::KeyGenerator &kgen, const rlwe::EvaluationKeyParameters &evkParams = {}) {
+    return Ciphertext{{kgen.NewEvaluationKey(evkParams), kgen.NewEvaluationKey(evkParams)}};
+}
+// rgsw.Encryptor (core/rgsw/encryptor.go; hering_rgsw_encryptor.h): an rlwe.Encryptor under a secret key whose Encrypt and
+// EncryptZero also take an rgsw.Ciphertext.  Every call is an exact function of the bytes the PRNG serves; per row (i, j) one
+// encryptZeroSk on Value[0][i][j], then one on Value[1][i][j]; in a table, ciphertext after ciphertext.
+class Encryptor {
+    rlwe::Encryptor enc_;
+
+public:
+    // rgsw.NewEncryptor(params, key): only secret-key encryption is supported
+    Encryptor(const hering::Evaluator &params, const sampling::PRNG &prng, const rlwe::SecretKey &key, DiscreteGaussian Xe = {})
+        : enc_(rlwe::Encryptor(params, prng, Ternary{}, Xe).WithKey(key)) {}
+    he_handle h() const { return enc_.h(); }
+    void EncryptZero(Ciphertext &ct) const { check(he_rgsw_encrypt_zero(h(), ct.Value[0].h(), ct.Value[1].h())); }
+    // Encrypt (:25-73): EncryptZero, then pt times the gadget vector to component 0 of Value[0] and component 1 of Value[1]
+    void Encrypt(const rlwe::Plaintext &pt, Ciphertext &ct) const {
+        check(he_rgsw_encrypt(h(), pt.Value.h(), pt.Meta.IsNTT, pt.Meta.IsMontgomery, ct.Value[0].h(), ct.Value[1].h()));
+    }
+    // operands that are no RGSW ciphertexts go to the embedded rlwe.Encryptor
+    void EncryptZero(rlwe::Ciphertext &ct) const { enc_.EncryptZero(ct); }
+    void EncryptZero(rlwe::ElementQP &ct) const { enc_.EncryptZero(ct); }
+    void Encrypt(const rlwe::Plaintext &pt, rlwe::Ciphertext &ct) const { enc_.Encrypt(pt, ct); }
+    // cts[k] = Encrypt(entry sel[k] of pts) on the one source, ciphertext 0 first; pts: batch entries, NTT and Montgomery (an empty
+    // Poly when every sel is -1); sel[k] == -1: EncryptZero
+    void EncryptTable(const Poly &pts, const std::vector<int32_t> &sel, std::vector<Ciphertext> &cts) const {
+        if (sel.size() != cts.size()) throw std::invalid_argument("EncryptTable: one selection per ciphertext");
+        std::vector<he_handle> k0, k1;
+        for (const Ciphertext &c : cts) { k0.push_back(c.Value[0].h()); k1.push_back(c.Value[1].h()); }
+        check(he_rgsw_encrypt_table(h(), pts.h(), sel.data(), (int)cts.size(), k0.data(), k1.data()));
+    }
+};
 }  // namespace rgsw
 
 // ---- blind rotation (core/rgsw/blindrot; hering_blindrot.h), NTT domain ---------------------------------------------------------
@@ -1374,6 +1408,7 @@ public:
     }
     he_handle h() const { return r_->h; }
     size_t size() const { return keys_.size(); }
+    const std::vector<rgsw::Ciphertext> &Keys() const { return keys_; }
 };
 // the Galois keys of a blind rotation with their Galois elements and index tables (GetEvaluationKeySet, keys.go:41)
 class GaloisKeySet {
@@ -1392,6 +1427,7 @@ public:
     }
     he_handle h() const { return r_->h; }
     const std::vector<uint64_t> &GaloisElements() const { return galEls_; }
+    const std::vector<EvaluationKey> &Keys() const { return keys_; }
 };
 // MemBlindRotationEvaluationKeySet (keys.go:32)
 struct MemBlindRotationEvaluationKeySet {
@@ -1403,6 +1439,36 @@ inline void AutomorphismSelect(const hering::Evaluator &ev, const Ciphertext &ct
                                Ciphertext &opOut) {
     check(he_automorphism_ct_select(ev.h(), ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), keys.h(), sel.data(), (int)sel.size(),
                                     opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+}
+// GenEvaluationKeyNew (keys.go:46-108; hering_rgsw_encryptor.h): RGSW(X^s[i]) for every coefficient of skLWE (a key of the ring
+// paramsLWE; limb 0 of its Q part is read) and the Galois keys of 5^1 .. 5^10 and 2N - 5, under skRLWE.  prng serves the RGSW
+// ciphertexts and prngKeyGen the Galois keys; given one source for both, the RGSW ciphertexts draw first.
+inline MemBlindRotationEvaluationKeySet GenEvaluationKeyNew(const rgsw::Evaluator &paramsRLWE, const rlwe::SecretKey &skRLWE, const Ring &paramsLWE,
+                                                            const rlwe::SecretKey &skLWE, const sampling::PRNG &prng, const sampling::PRNG &prngKeyGen,
+                                                            const rlwe::EvaluationKeyParameters &evkParams = {}, DiscreteGaussian Xe = {}) {
+    constexpr int windowSize = 10;  // keys.go:14
+    rgsw::Encryptor enc(paramsRLWE, prng, skRLWE, Xe);
+    rlwe::KeyGenerator kgen(paramsRLWE, prngKeyGen, Ternary{}, Xe);
+    const int n = paramsLWE.N();
+    std::vector<rgsw::Ciphertext> brk;
+    std::vector<he_handle> k0, k1, g;
+    for (int i = 0; i < n; i++) {
+        brk.push_back(rgsw::NewCiphertext(kgen, evkParams));
+        k0.push_back(brk.back().Value[0].h());
+        k1.push_back(brk.back().Value[1].h());
+    }
+    const uint64_t twoN = (uint64_t)2 * paramsRLWE.RingQ().N();
+    std::vector<uint64_t> galEls;
+    std::vector<EvaluationKey> gks;
+    uint64_t pw = 1;
+    for (int i = 0; i <= windowSize; i++) {
+        pw = pw * 5 % twoN;
+        galEls.push_back(i < windowSize ? pw : twoN - 5);
+        gks.push_back(kgen.NewEvaluationKey(evkParams));
+        g.push_back(gks.back().h());
+    }
+    check(he_blindrot_gen_evaluation_key(enc.h(), kgen.h(), paramsLWE.h(), skLWE.Value.Q.h(), n, k0.data(), k1.data(), g.data()));
+    return MemBlindRotationEvaluationKeySet{RGSWKeySet(paramsRLWE, brk), GaloisKeySet(paramsRLWE, galEls, gks)};
 }
 // blindrot.Evaluator (evaluator.go:16), BlindRotateCore only
 class Evaluator {

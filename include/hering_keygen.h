@@ -3,9 +3,9 @@
  * hering_sampler.h and a he_prng; the sparse ternary sampler (ring/sampler_ternary.go:198-263) and
  * AddPolyTimesGadgetVectorToGadgetCiphertext (core/rlwe/gadgetciphertext.go:172-241) as entries of their own (libhering.so).
  *
- * Out of scope: compressed (seeded, degree-0) evaluation keys and sampling.KeyedPRNG; rgsw.Encryptor and the blind-rotation key
- * generator (the two-key form of he_gadget_add_poly is what they need); Ternary{H} as the Encryptor's own Xs; multiparty key
- * generation.
+ * Elsewhere: rgsw.Encryptor and the blind-rotation key generator (hering_rgsw_encryptor.h: a table of RGSW ciphertexts drawn row
+ * by row, with the arithmetic after the draws and the two-key gadget term fused per chunk of ciphertexts).  Out of scope: compressed
+ * (seeded, degree-0) evaluation keys and sampling.KeyedPRNG; Ternary{H} as the Encryptor's own Xs; multiparty key generation.
  *
  * The frame of hering_encryptor.h: 0 on success, <0 on error (HE_E*), he_last_error() for the message; outputs come last.  A call
  * runs after the calling thread's queued requests, returns with its device work finished, has no replay number and is HE_EINVAL

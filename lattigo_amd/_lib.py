@@ -13,7 +13,7 @@ _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), o
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
          os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h"),
-         os.path.join(_INC, "hering_keygen.h")]
+         os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -150,6 +150,9 @@ def _declare(L):
         "he_keygen_secret_key_hw": [H, i, i, i, H, H], "he_gadget_add_poly": [H, H, H],
         "he_keygen_evaluation_key": [H, H, H, H, H], "he_keygen_evaluation_key_sk": [H, H, H, H], "he_keygen_relinearization_key": [H, H, H, H],
         "he_keygen_galois_key": [H, C.c_uint64, H, H, H], "he_keygen_galois_keys": [H, i, u64p, H, H, u64p],
+        "he_rgsw_encrypt_zero": [H, H, H], "he_rgsw_encrypt": [H, H, i, i, H, H],
+        "he_rgsw_encrypt_table": [H, H, C.POINTER(C.c_int32), i, HP, HP],
+        "he_blindrot_gen_evaluation_key": [H, H, H, H, i, HP, HP, HP],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],
@@ -283,7 +286,10 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  "he_encryptor_create", "he_encryptor_destroy", "he_encryptor_set_key", "he_decryptor_create", "he_decryptor_destroy",
                  # include/hering_keygen.h: the handles; every generation entry carries the bytes of a source into a key and is
                  # left out on purpose (it fails trace_end)
-                 "he_keygen_create", "he_keygen_destroy"}
+                 "he_keygen_create", "he_keygen_destroy",
+                 # include/hering_rgsw_encryptor.h: the entries carry the bytes of a source into keys, which no replayed call can
+                 # reproduce; the keys they wrote stay as the recorded run left them
+                 "he_rgsw_encrypt_zero", "he_rgsw_encrypt", "he_rgsw_encrypt_table", "he_blindrot_gen_evaluation_key"}
 _trace = None
 
 

@@ -104,6 +104,32 @@ class MemBlindRotationEvaluationKeySet:
         return self.galois
 
 
+def GenEvaluationKeyNew(paramsRLWE: rgsw.Evaluator, skRLWE, paramsLWE: Ring, skLWE, evkParams=None, prng=None, prngKeyGen=None,
+                        XeSigma: float | None = None, XeBound: float | None = None) -> MemBlindRotationEvaluationKeySet:
+    """keys.go:46-108 on the device (he_blindrot_gen_evaluation_key): RGSW(X^s[i]) for every coefficient of skLWE (an rlwe SecretKey
+    of the ring paramsLWE; limb 0 of its Q part is read) and the Galois keys of GaloisElements(N), under skRLWE, at the levels and
+    BaseTwoDecomposition of evkParams (keygen.EvaluationKeyParameters).  prng: the source of the RGSW ciphertexts; prngKeyGen: that
+    of the Galois keys (None: prng, the RGSW ciphertexts drawing first).  An exact function of the byte streams."""
+    from . import keygen as _kg
+    from .sampling import PRNG
+    prng = PRNG() if prng is None else prng
+    dist = (_kg.DefaultXeSigma if XeSigma is None else XeSigma, _kg.DefaultXeBound if XeBound is None else XeBound)
+    kgen = _kg.KeyGenerator(paramsRLWE, prng if prngKeyGen is None else prngKeyGen, _kg.DefaultXsP, *dist)
+    levelQ, levelP, pw2 = kgen._resolve(evkParams)
+    enc = rgsw.Encryptor(paramsRLWE, prng, skRLWE, *dist)
+    n = paramsLWE.N
+    cts = [rgsw.NewCiphertext(paramsRLWE, levelQ, levelP, pw2) for _ in range(n)]
+    galEls = GaloisElements(paramsRLWE.ringQ.N)
+    params = _kg.EvaluationKeyParameters(levelQ, levelP, pw2)
+    gks = [kgen.NewEvaluationKey(params) for _ in galEls]
+    a0 = (H * n)(*[c.Value[0].h for c in cts])
+    a1 = (H * n)(*[c.Value[1].h for c in cts])
+    ag = (H * len(gks))(*[k.h for k in gks])
+    rc = load().he_blindrot_gen_evaluation_key(enc.h, kgen.h, paramsLWE.h, skLWE.Q.h, n, a0, a1, ag)
+    (prngKeyGen if prngKeyGen is not None and prngKeyGen.error is not None else prng).check(rc)  # (the reader's exception, if it raised one)
+    return MemBlindRotationEvaluationKeySet(paramsRLWE, cts, dict(zip(galEls, gks)))
+
+
 def Schedule(logN: int, a):
     """The operations BlindRotateCore applies for the row a, in order: ("automorphism", Galois element) or
     ("external_product", key index).  Host only (he_debug_blindrot_schedule)."""

@@ -50,6 +50,7 @@
 #include "../../include/hering_sampler.h"
 #include "../../include/hering_encryptor.h"
 #include "../../include/hering_keygen.h"
+#include "../../include/hering_rgsw_encryptor.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -6423,6 +6424,319 @@ int he_keygen_galois_keys(he_handle hk, int n, const uint64_t *gal_els, he_handl
     int rc = HE_OK;
     for (int i = 0; i < n && rc == HE_OK; i++) rc = keygen_galois_key(*kg, who, gal_els[i], skQ, skP, gks[i]);  // :189-195, key after key
     const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+
+// ---------------------------------------------------------------------------------------
+// rgsw.Encryptor and blindrot.GenEvaluationKeyNew (include/hering_rgsw_encryptor.h; core/rgsw/encryptor.go, blindrot/keys.go).  A table
+// of RGSW ciphertexts draws row by row into the keys' own storage, as keygen_evaluation_key does, and finishes every row of a
+// chunk of ciphertexts at once (launch_rgsw_table_finish).
+// ---------------------------------------------------------------------------------------
+// the staging of a chunk: N words of small values and one (nQk + nPk)-limb slab entry per table row
+static constexpr size_t kRgswStageBudget = (size_t)256 << 20;
+static int rgsw_chunk_keys(int n, int R, size_t blk, int N) {
+    const int cap = 65535 / (2 * R);  // table rows are a grid coordinate and a batch (launch_rgsw_table_finish, be_ntt)
+    size_t chunk = kRgswStageBudget / ((size_t)2 * R * (blk + N) * 8);
+    const char *s = getenv("HERING_RGSW_CHUNK_KEYS");  // (set-up code: read at each call)
+    if (s && atoi(s) > 0) chunk = (size_t)atoi(s);
+    return (int)std::max<size_t>(1, std::min<size_t>({chunk, (size_t)cap, (size_t)n}));
+}
+// the operands every entry shares: the bound secret key and the 2 n keys, keys[2 k + u] = gadget ciphertext u of ciphertext k
+struct RgswOperands {
+    std::shared_ptr<Poly> skQ, skP;
+    he_handle hskQ = 0, hskP = 0;
+    std::vector<std::shared_ptr<Evk>> keys;
+};
+static int rgsw_operands(Encryptor &e, const char *who, int n, const he_handle *h0, const he_handle *h1, RgswOperands &o) {
+    if (n < 1 || !h0 || !h1) return fail(HE_EINVAL, "%s: %d ciphertexts with a null array", who, n);
+    int kind;
+    {
+        std::lock_guard<std::mutex> lk(e.mu);
+        kind = e.kind;
+        o.hskQ = e.key[0];
+        o.hskP = e.key[1];
+    }
+    if (kind != 1) return fail(HE_EINVAL, "%s: %s; only secret-key encryption is supported", who, kind ? "a public key is bound" : "the encryptor has no encryption key");
+    o.keys.resize((size_t)2 * n);
+    for (int k = 0; k < n; k++)
+        for (int u = 0; u < 2; u++) {
+            auto key = get<Evk>(u ? h1[k] : h0[k], T_EVK);
+            if (!key) return fail(HE_EHANDLE, "%s: bad Evk handle for rgsw%d[%d]", who, u, k);
+            if (key->ev != e.ev) return fail(HE_EINVAL, "%s: rgsw%d[%d] belongs to another evaluator than the encryptor", who, u, k);
+            const Evk &f = k || u ? *o.keys[0] : *key;
+            if (key->beta != f.beta || key->nQk != f.nQk || key->nPk != f.nPk || key->pw2 != f.pw2 || key->nj != f.nj)
+                return fail(HE_EINVAL, "%s: rgsw%d[%d] differs in shape from rgsw0[0]", who, u, k);
+            o.keys[(size_t)2 * k + u] = key;
+        }
+    const Evk &f = *o.keys[0];
+    TRY(evk_shape_for_keygen(f, who, "the ciphertext"));
+    if (2 * f.beta > 65535) return fail(HE_EINVAL, "%s: %d rows per gadget ciphertext", who, f.beta);
+    {
+        std::vector<const Evk *> seen;
+        for (const auto &k : o.keys) seen.push_back(k.get());
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(HE_EINVAL, "%s: two of the output keys are one key", who);
+    }
+    const int N = e.ev->be->Q->N;
+    auto sk_part = [&](he_handle h, int limbs, const char *name, std::shared_ptr<Poly> *out) -> int {
+        auto p = get<Poly>(h, T_POLY);
+        if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle for %s of the bound key", who, name);
+        if (p->ctx.get() != &e.ctx() || p->N != N || p->nlimbs < limbs || p->batch != 1)
+            return fail(HE_EINVAL, "%s: %s of the bound key must be one polynomial of the encryptor's rings with %d limbs", who, name, limbs);
+        *out = p;
+        return HE_OK;
+    };
+    TRY(sk_part(o.hskQ, f.nQk, "sk.Q", &o.skQ));
+    if (f.nPk) {
+        if (!o.hskP) return fail(HE_EINVAL, "%s: the key was bound without its P part, which this call reads", who);
+        TRY(sk_part(o.hskP, f.nPk, "sk.P", &o.skP));
+    }
+    return HE_OK;
+}
+// n successive rgsw.Encryptor.Encrypt calls without the frame.  pts: device words of the plaintexts (entry s at pts + s pt_stride,
+// nQk limbs, NTT and Montgomery; null: every sel is -1); sel: host, checked by the caller.
+static int rgsw_encrypt_table(Encryptor &e, const char *who, const RgswOperands &o, const uint64_t *pts, size_t pt_stride, const int32_t *sel, int n) {
+    BasisExtender &be = *e.ev->be;
+    Ctx &c = *be.ctx;
+    Prng &g = *e.prng_keep;
+    const Evk &f = *o.keys[0];
+    const int N = be.Q->N, R = f.beta, nQk = f.nQk, nPk = f.nPk;
+    const size_t blk = (size_t)(nQk + nPk) * N;
+    const int chunk = rgsw_chunk_keys(n, R, blk, N);
+    // the small values of every row's Gaussian, [table rows][N], and the slab that becomes NTT(e), [table rows][nQk + nPk][N]: outside
+    // the arena, which every draw resets
+    const size_t e_bytes = (size_t)chunk * 2 * R * N * 8, slab_bytes = (size_t)chunk * 2 * R * blk * 8;
+    uint64_t *d_e = nullptr, *slab = nullptr;
+    {
+        Scope sc(&c);
+        HIP_TRY(c.pool_take(e_bytes, (void **)&d_e));
+        HIP_TRY(c.pool_take(slab_bytes, (void **)&slab));
+    }
+    int rc = HE_OK;
+    const ModConst *const mc[2] = {be.Q->dev.mc, nPk ? be.P->dev.mc : nullptr};
+    const int nl[2] = {nQk, nPk};
+    const size_t bs[2] = {2 * blk, 2 * blk};
+    const std::vector<uint64_t> G = gadget_table(f);
+    std::vector<uint64_t> bases;
+    for (int kb = 0; kb < n && rc == HE_OK; kb += chunk) {
+        const int nk = std::min(chunk, n - kb), T = nk * 2 * R;
+        // encryptor.go:92-118: per ciphertext, per row (i, j), one encryptZeroSk on Value[0][i][j] and one on Value[1][i][j]
+        for (int k = 0; k < nk && rc == HE_OK; k++)
+            for (int r = 0; r < R && rc == HE_OK; r++)
+                for (int u = 0; u < 2 && rc == HE_OK; u++) {
+                    uint64_t *c1 = o.keys[(size_t)2 * (kb + k) + u]->d + ((size_t)2 * r + 1) * blk;
+                    uint64_t *const out[2] = {c1, c1 + (size_t)nQk * N};
+                    rc = uniform_read_run(who, c, g, N, 1, nPk ? 2 : 1, mc, nl, out, bs, false, nullptr);
+                    if (rc != HE_OK) break;
+                    uint64_t *dst = d_e + ((size_t)(k * 2 + u) * R + r) * N;
+                    rc = gaussian_parse_run(who, c, g, N, 1, e.sigma, e.bound, [&](const uint64_t *vals) -> int {
+                        HIP_TRY(hipMemcpyAsync(dst, vals, (size_t)N * 8, hipMemcpyDeviceToDevice, c.stream));
+                        return HE_OK;
+                    });
+                }
+        if (rc != HE_OK) break;
+        Scope sc(&c);
+        rc = [&]() -> int {
+            const size_t sel_words = ((size_t)nk + 1) / 2;
+            TRY(c.arena_reserve(G.size() + (size_t)2 * nk + sel_words + 16));
+            const View sv{slab, blk};
+            // encryptor.go:411-414 for every table row at once: the Gaussian words on the Q limbs and their centred copies on the P limbs
+            HIP_TRY(launch_sampler_expand(be.qp.mc, d_e, true, false, false, nullptr, nullptr, sv, N, nQk, T, c.stream));
+            if (nPk)
+                HIP_TRY(launch_sampler_expand(be.qp.mc + be.LQ, d_e, true, false, false, nullptr, nullptr, View{slab + (size_t)nQk * N, blk}, N, nPk, T, c.stream));
+            LimbTab tab = ident_tab(nQk + nPk);
+            for (int i = 0; i < nPk; i++) tab.mod[nQk + i] = (uint8_t)(be.LQ + i);
+            HIP_TRY(be_ntt(be, tab, sv, sv, T, false, NTT_REDUCE_INPUT));  // :416-418
+            RgswTableArgs a;
+            a.e = slab; a.blk = blk; a.N = N; a.rows = R; a.nkeys = nk; a.nq = nQk; a.np = nPk;
+            a.mc = be.qp.mc;
+            for (int i = 0; i < nQk; i++) a.mod[i] = (uint8_t)i;
+            for (int i = 0; i < nPk; i++) a.mod[nQk + i] = (uint8_t)(be.LQ + i);
+            a.skQ = o.skQ->d; a.skP = nPk ? o.skP->d : nullptr;
+            bases.resize((size_t)2 * nk);
+            for (int i = 0; i < 2 * nk; i++) bases[(size_t)i] = (uint64_t)(uintptr_t)o.keys[(size_t)2 * kb + i]->d;
+            uint64_t *d_bases = c.arena_take(bases.size());
+            HIP_TRY(hipMemcpyAsync(d_bases, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, c.stream));
+            a.keys = reinterpret_cast<uint64_t *const *>(d_bases);
+            uint64_t *d_sel = nullptr;
+            if (pts) {
+                uint64_t *d_G = c.arena_take(G.size());
+                HIP_TRY(hipMemcpyAsync(d_G, G.data(), G.size() * 8, hipMemcpyHostToDevice, c.stream));
+                d_sel = c.arena_take(sel_words);
+                HIP_TRY(hipMemcpyAsync(d_sel, sel + kb, (size_t)nk * 4, hipMemcpyHostToDevice, c.stream));
+                a.pts = pts; a.pt_stride = pt_stride; a.G = d_G; a.sel = reinterpret_cast<const int32_t *>(d_sel);
+            }
+            c.acct(3.0 * (nQk + nPk), 0, T, N);
+            HIP_TRY(launch_rgsw_table_finish(a, c.stream));  // :420-425 and AddPolyTimesGadgetVectorToGadgetCiphertext with two keys
+            if (d_sel) HIP_TRY(hipMemsetAsync(d_sel, 0, sel_words * 8, c.stream));
+            for (int i = 0; i < 2 * nk; i++) {
+                Evk &k = *o.keys[(size_t)2 * kb + i];
+                TRY(evk_derive(k));
+                k.word_mul = 1;
+            }
+            HIP_TRY(hipStreamSynchronize(c.stream));  // (bases and sel are host memory of this call)
+            return HE_OK;
+        }();
+    }
+    Scope sc(&c);
+    (void)hipMemsetAsync(d_e, 0, e_bytes, c.stream);
+    (void)hipMemsetAsync(slab, 0, slab_bytes, c.stream);
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    c.pool_give(e_bytes, d_e);
+    c.pool_give(slab_bytes, slab);
+    return rc;
+}
+// the plaintexts of a table: one polynomial of the encryptor's ringQ with at least `limbs` limbs
+static int rgsw_plaintexts(const Encryptor &e, const char *who, he_handle h, int limbs, std::shared_ptr<Poly> *out) {
+    auto p = get<Poly>(h, T_POLY);
+    if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle for the plaintext", who);
+    if (p->ctx.get() != &e.ctx() || p->N != e.ev->be->Q->N || p->nlimbs < limbs)
+        return fail(HE_EINVAL, "%s: the plaintext must be a polynomial of the encryptor's ringQ with %d limbs", who, limbs);
+    *out = p;
+    return HE_OK;
+}
+static int rgsw_check_sel(const char *who, const int32_t *sel, int n, int m) {
+    if (!sel) return fail(HE_EINVAL, "%s: null selection", who);
+    for (int k = 0; k < n; k++)
+        if (sel[k] < -1 || sel[k] >= m) return fail(HE_EINVAL, "%s: sel[%d] = %d is not in [-1, %d)", who, k, (int)sel[k], m);
+    return HE_OK;
+}
+int he_rgsw_encrypt_table(he_handle henc, he_handle hpts, const int32_t *sel, int n, const he_handle *rgsw0, const he_handle *rgsw1) {
+    static const char *who = "he_rgsw_encrypt_table";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    RgswOperands o;
+    TRY(rgsw_operands(*e, who, n, rgsw0, rgsw1, o));
+    std::shared_ptr<Poly> pts;
+    if (hpts) TRY(rgsw_plaintexts(*e, who, hpts, o.keys[0]->nQk, &pts));
+    TRY(rgsw_check_sel(who, sel, n, pts ? pts->batch : 0));
+    { Scope sc(&e->ctx()); }  // (after the calling thread's queued requests)
+    const int rc = rgsw_encrypt_table(*e, who, o, pts ? pts->d : nullptr, pts ? pts->view().bstride : 0, sel, n);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_rgsw_encrypt(he_handle henc, he_handle hpt, int pt_is_ntt, int pt_is_montgomery, he_handle rgsw0, he_handle rgsw1) {
+    static const char *who = "he_rgsw_encrypt";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    RgswOperands o;
+    TRY(rgsw_operands(*e, who, 1, &rgsw0, &rgsw1, o));
+    const int levelQ = o.keys[0]->nQk - 1;
+    std::shared_ptr<Poly> pt;
+    TmpPoly buf;  // buffQP.Q (:44)
+    if (hpt) {
+        TRY(rgsw_plaintexts(*e, who, hpt, levelQ + 1, &pt));
+        if (pt->batch != 1) return fail(HE_EINVAL, "%s: the plaintext has %d entries; one polynomial is expected", who, pt->batch);
+        if (!pt_is_ntt || !pt_is_montgomery) {  // :47-60
+            TRY(buf.alloc(e->hq, levelQ + 1, 1));
+            he_handle src = hpt;
+            if (!pt_is_ntt) {
+                TRY(he_ntt(e->hq, levelQ, src, buf.h));
+                src = buf.h;
+            }
+            if (!pt_is_montgomery) TRY(he_mform(e->hq, levelQ, src, buf.h));
+            pt = get<Poly>(buf.h, T_POLY);
+        }
+    }
+    { Scope sc(&e->ctx()); }
+    const int32_t sel = pt ? 0 : -1;
+    const int rc = rgsw_encrypt_table(*e, who, o, pt ? pt->d : nullptr, pt ? pt->view().bstride : 0, &sel, 1);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_rgsw_encrypt_zero(he_handle henc, he_handle rgsw0, he_handle rgsw1) {
+    static const char *who = "he_rgsw_encrypt_zero";
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    RgswOperands o;
+    TRY(rgsw_operands(*e, who, 1, &rgsw0, &rgsw1, o));
+    { Scope sc(&e->ctx()); }
+    const int32_t sel = -1;
+    const int rc = rgsw_encrypt_table(*e, who, o, nullptr, 0, &sel, 1);
+    const int rs = rlwe_frame_end(e->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+// blindrot.GenEvaluationKeyNew (keys.go:46-108)
+int he_blindrot_gen_evaluation_key(he_handle henc, he_handle hkgen, he_handle hringLWE, he_handle hskLWE, int n, const he_handle *rgsw0,
+                                   const he_handle *rgsw1, const he_handle *gks) {
+    static const char *who = "he_blindrot_gen_evaluation_key";
+    constexpr int kWindowSize = 10;  // keys.go:14
+    GET(e, Encryptor, henc, T_ENCRYPTOR);
+    GET(kg, KeyGen, hkgen, T_KEYGEN);
+    GET(rl, Ring, hringLWE, T_RING);
+    TRY(rlwe_frame_begin(e->ctx(), who));
+    if (kg->ev != e->ev) return fail(HE_EINVAL, "%s: the generator belongs to another evaluator than the encryptor", who);
+    const Ring &Q = *e->ev->be->Q;
+    if (Q.type != 0) return fail(HE_EINVAL, "%s: a blind rotation runs on a standard ring", who);
+    if (rl->ctx.get() != &e->ctx()) return fail(HE_EINVAL, "%s: ringLWE belongs to another context", who);
+    if (n != rl->N) return fail(HE_EINVAL, "%s: %d ciphertexts for an LWE ring of degree %d", who, n, rl->N);
+    auto skl = get<Poly>(hskLWE, T_POLY);
+    if (!skl) return fail(HE_EHANDLE, "%s: bad Poly handle for skLWE", who);
+    if (skl->ctx != rl->ctx || skl->N != rl->N || skl->batch != 1) return fail(HE_EINVAL, "%s: skLWE must be one polynomial of ringLWE", who);
+    RgswOperands o;
+    TRY(rgsw_operands(*e, who, n, rgsw0, rgsw1, o));
+    if (!gks) return fail(HE_EINVAL, "%s: null array of Galois keys", who);
+    uint64_t gal_els[kWindowSize + 1];  // :94-99
+    const uint64_t mask = (uint64_t)2 * Q.N - 1;
+    uint64_t pw = 1;
+    for (int i = 0; i < kWindowSize; i++) gal_els[i] = pw = pw * 5 & mask;
+    gal_els[kWindowSize] = (uint64_t)2 * Q.N - 5;
+    for (int i = 0; i <= kWindowSize; i++) {  // (every check before the first draw)
+        std::shared_ptr<Evk> k;
+        TRY(keygen_evk(*kg, who, gks[i], &k));
+        TRY(keygen_sk_for(*kg, who, *k, o.hskQ, o.hskP, "sk.Q", "sk.P", nullptr, nullptr));
+        for (int j = 0; j < i; j++)
+            if (gks[j] == gks[i]) return fail(HE_EINVAL, "%s: gks[%d] and gks[%d] are one key", who, j, i);
+        for (const auto &r : o.keys)
+            if (r == k) return fail(HE_EINVAL, "%s: gks[%d] is also a key of an RGSW ciphertext", who, i);
+    }
+    const int N = Q.N, LQ = (int)Q.moduli.size(), levelQ = o.keys[0]->nQk - 1;
+    std::vector<uint64_t> s((size_t)n), mono;
+    std::vector<int64_t> values;
+    std::vector<int32_t> sel((size_t)n);
+    auto wipe_host = [&]() {
+        Prng::wipe(s.data(), s.size() * 8);
+        Prng::wipe(sel.data(), sel.size() * 4);
+        if (!values.empty()) Prng::wipe(values.data(), values.size() * 8);
+        if (!mono.empty()) Prng::wipe(mono.data(), mono.size() * 8);
+    };
+    TmpPoly t, pts;  // (cleared before they go back to the pool)
+    int rc = t.alloc(hringLWE, 1, 1);
+    if (rc == HE_OK) rc = he_intt(hringLWE, 0, hskLWE, t.h);  // :52-53
+    if (rc == HE_OK) rc = he_imform(hringLWE, 0, t.h, t.h);
+    if (rc == HE_OK) rc = he_poly_download_limb(t.h, 0, 0, s.data());
+    if (rc == HE_OK) {
+        const uint64_t q0 = rl->moduli[0];
+        for (int i = 0; i < n; i++) {  // PolyToBigintCentered (:58), then the map of :66-81 in order of first appearance
+            const int64_t v = s[(size_t)i] >= (q0 >> 1) ? (int64_t)(s[(size_t)i] - q0) : (int64_t)s[(size_t)i];
+            size_t at = std::find(values.begin(), values.end(), v) - values.begin();
+            if (at == values.size()) values.push_back(v);
+            sel[(size_t)i] = (int32_t)at;
+        }
+        const size_t m = values.size();
+        mono.assign(m * (size_t)LQ * N, 0);
+        for (size_t a = 0; a < m; a++) {  // NewMonomialXi (ring/ring.go:374-396)
+            int64_t i = values[a] & (int64_t)mask;
+            if (i >= N) i -= (int64_t)2 * N;
+            for (int k = 0; k < LQ; k++) {
+                uint64_t *row = mono.data() + (a * LQ + k) * (size_t)N;
+                if (i < 0) row[N + i] = Q.moduli[(size_t)k] - 1;
+                else row[i] = 1;
+            }
+        }
+        rc = pts.alloc(e->hq, LQ, (int)m);
+        if (rc == HE_OK) rc = he_poly_upload(pts.h, mono.data(), mono.size());
+        if (rc == HE_OK) rc = he_ntt(e->hq, LQ - 1, pts.h, pts.h);       // :78, at the ring's full level
+        if (rc == HE_OK) rc = he_mform(e->hq, levelQ, pts.h, pts.h);     // encryptor.go:56, at the ciphertext's
+    }
+    if (rc == HE_OK) {
+        { Scope sc(&e->ctx()); }
+        auto p = get<Poly>(pts.h, T_POLY);
+        rc = rgsw_encrypt_table(*e, who, o, p->d, p->view().bstride, sel.data(), n);  // :83-89
+    }
+    wipe_host();
+    for (int i = 0; i <= kWindowSize && rc == HE_OK; i++) rc = keygen_galois_key(*kg, who, gal_els[i], o.hskQ, o.hskP, gks[i]);  // :101-105
+    const int rs = rlwe_frame_end(e->ctx());
     return rc != HE_OK ? rc : rs;
 }
 

@@ -549,6 +549,28 @@ hipError_t launch_evk_finish(const EvkRowsArgs &a, hipStream_t s);
 // the gadget term alone: key[r][comp] = CRed(key[r][comp] + MRed(pt, G[r][y])) on the Q limbs where G is not 0
 hipError_t launch_gadget_add(const EvkRowsArgs &a, hipStream_t s);
 
+// ---- RGSW encryption (core/rgsw/encryptor.go; include/hering_rgsw_encryptor.h) ---------------------------------------------------
+// A table of nkeys RGSW ciphertexts, each two separately allocated keys of the shape above: gadget ciphertext u of ciphertext k
+// starts at keys[2 k + u] (a device table of base addresses).  Table row t = (k 2 + u) rows + r; e holds NTT(e) of every table row,
+// canonical, [nkeys 2 rows][nq + np][N] (blk words apart); component 1 of every row holds the uniform c1 as drawn.  sel: device,
+// [nkeys], the plaintext of ciphertext k among the entries of pts (pt_stride words apart, nq limbs, NTT and Montgomery), -1: none.
+struct RgswTableArgs {
+    uint64_t *const *keys = nullptr;
+    const int32_t *sel = nullptr;
+    const uint64_t *e = nullptr;
+    size_t blk = 0;
+    int N = 0, rows = 0, nkeys = 0, nq = 0, np = 0;
+    const ModConst *mc = nullptr;
+    uint8_t mod[kMaxLimbs];
+    const uint64_t *skQ = nullptr, *skP = nullptr;  // nq / np limbs, NTT and Montgomery
+    const uint64_t *pts = nullptr;                  // null: every sel is -1
+    size_t pt_stride = 0;
+    const uint64_t *G = nullptr;                    // [rows][nq], as EvkRowsArgs::G
+};
+// per word of table row t: c0 = CRed(MForm(e) + q - MRed(c1, sk)); with sel[k] >= 0 and G[r][y] != 0 the term MRed(pts[sel[k]], G) is
+// added to c0 for u = 0 and to c1 for u = 1 (c0 from the c1 as drawn; then c1 + term is stored).  One launch; 2 nkeys rows <= 65535.
+hipError_t launch_rgsw_table_finish(const RgswTableArgs &a, hipStream_t s);
+
 // ---- ring-degree switches (core/rlwe/element.go:250-313, ring/operations.go:380) ----------------
 // One launch over `batch` entries: entries z >= zsplit read in2 and write out2 (entry z - zsplit), so that both components of a
 // ciphertext go in one launch (zsplit >= batch, or in2 / out2 null: in / out only).  n_small = the small degree (>= 16), the large
@@ -611,7 +633,7 @@ enum KernelId {
     K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64,
     K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
     K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND,
-    K_EVK_FINISH, K_GADGET_ADD, K_COUNT
+    K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -77,7 +77,8 @@ const char *kernel_name(int id) {
                                          "ci_bridge_fold", "ci_bridge_unfold", "bfv_quantize", "special_fft", "ckks_fft_pass",
                                          "special_ifft_quantize", "f64_to_rns", "rns_to_f64", "bgv_slots_to_t", "bgv_t_to_slots",
                                          "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
-                                         "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add"};
+                                         "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add",
+                                         "rgsw_table_finish"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -5912,6 +5913,56 @@ hipError_t launch_gadget_add(const EvkRowsArgs &a, hipStream_t s) {
     if (!evk_rows_ok(a) || !a.G || a.comp < 0 || a.comp > 1) return hipErrorInvalidValue;
     ProfScope ps(K_GADGET_ADD, s, 2.0 * a.nq * (double)a.N * 8.0);  // (each Q limb belongs to the digit of one row per window)
     hipLaunchKernelGGL((evk_rows_kernel<false>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq, a.rows), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// RGSW encryption (include/hering_rgsw_encryptor.h): evk_rows_kernel<true> over a table of separately allocated keys.  Grid
+// (coefficient pairs, limb, table row): the ciphertext k, the gadget ciphertext u, the row r and the limb are block coordinates, so
+// the key's base address, sel[k], the modulus record and the row's factor are uniform per block.  Per word one read of NTT(e) from
+// the staging slab and one of the key's c1, one write of c0 and, on the limbs of the row's digit of gadget ciphertext 1, one of c1.
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) rgsw_table_finish_kernel(RgswTableArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, t = blockIdx.z;
+    const int r = t % A.rows, ku = t / A.rows, u = ku & 1, k = ku >> 1;
+    const bool isq = y < A.nq;
+    const int s = A.pts ? A.sel[k] : -1;
+    const uint64_t g = (isq && s >= 0) ? A.G[(size_t)r * A.nq + y] : 0;
+    const ModConst m = A.mc[A.mod[y]];
+    const uint64_t q = m.q, qinv = m.qinv;
+    const size_t off = (size_t)y * A.N + j;
+    uint64_t *key = A.keys[ku];
+    uint64_t *c0p = key + (size_t)2 * r * A.blk + off, *c1p = c0p + A.blk;
+    ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(A.e + (size_t)t * A.blk + off);
+    ulonglong2 c1 = ldnt2(c1p);
+    const uint64_t *skp = isq ? A.skQ + off : A.skP + (size_t)(y - A.nq) * A.N + j;
+    const ulonglong2 sk = *reinterpret_cast<const ulonglong2 *>(skp);
+    v.x = cred(mform(v.x, q, m.brc0, m.brc1) + (q - mred(c1.x, sk.x, q, qinv)), q);
+    v.y = cred(mform(v.y, q, m.brc0, m.brc1) + (q - mred(c1.y, sk.y, q, qinv)), q);
+    if (g != 0) {
+        const ulonglong2 p = *reinterpret_cast<const ulonglong2 *>(A.pts + (size_t)s * A.pt_stride + off);
+        const uint64_t tx = mred(p.x, g, q, qinv), ty = mred(p.y, g, q, qinv);
+        if (u == 0) {
+            v.x = cred(v.x + tx, q);
+            v.y = cred(v.y + ty, q);
+        } else {  // (c0 above is of the c1 as drawn)
+            c1.x = cred(c1.x + tx, q);
+            c1.y = cred(c1.y + ty, q);
+            *reinterpret_cast<ulonglong2 *>(c1p) = c1;
+        }
+    }
+    *reinterpret_cast<ulonglong2 *>(c0p) = v;
+}
+hipError_t launch_rgsw_table_finish(const RgswTableArgs &a, hipStream_t s) {
+    if (!a.keys || !a.e || !a.mc || !a.skQ || (a.np > 0 && !a.skP) || a.N < 8 || a.N > (1 << kMaxLogN) || (a.N & (a.N - 1)) != 0 || a.rows <= 0 ||
+        a.nkeys <= 0 || (long)a.nkeys * 2 * a.rows > 65535 || a.nq <= 0 || a.np < 0 || a.nq + a.np > kMaxLimbs || a.blk < (size_t)(a.nq + a.np) * a.N ||
+        (a.pts && (!a.sel || !a.G || a.pt_stride < (size_t)a.nq * a.N)))
+        return hipErrorInvalidValue;
+    const int T = a.nkeys * 2 * a.rows;
+    ProfScope ps(K_RGSW_TABLE_FINISH, s, 3.0 * (a.nq + a.np) * (double)a.N * T * 8.0);
+    hipLaunchKernelGGL(rgsw_table_finish_kernel, dim3((unsigned)((a.N / 2 + 255) / 256), a.nq + a.np, T), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

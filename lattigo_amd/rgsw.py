@@ -7,6 +7,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import encryptor as _enc
 from . import rlwe, wire
 from ._lib import H, check, load
 
@@ -87,6 +88,52 @@ class Evaluator(rlwe.Evaluator):
         s = np.ascontiguousarray(sel, dtype=np.int32)
         check(load().he_rgsw_external_product_select(self.h, op0[0].h, op0[1].h, keys.h, s.ctypes.data_as(C.POINTER(C.c_int32)),
                                                      int(s.size), opOut[0].h, opOut[1].h))
+
+
+# ---- rgsw.Encryptor (core/rgsw/encryptor.go; include/hering_rgsw_encryptor.h) ---------------------------------------------------
+def NewCiphertext(evaluator: rlwe.Evaluator, levelQ: int, levelP: int, BaseTwoDecomposition: int = 0) -> Ciphertext:
+    """rgsw.NewCiphertext (elements.go:27): a zeroed ciphertext at (levelQ, levelP, BaseTwoDecomposition)"""
+    from .keygen import BaseTwoDecompositionVectorSize
+
+    def key():
+        if BaseTwoDecomposition:
+            nj = BaseTwoDecompositionVectorSize(evaluator.ringQ.moduli, levelQ, levelP, BaseTwoDecomposition)
+            return rlwe.EvaluationKey(evaluator, None, None, BaseTwoDecomposition, nj, shape=(sum(nj), levelQ + 1, levelP + 1))
+        return rlwe.EvaluationKey(evaluator, None, None, shape=(rlwe.BaseRNSDecompositionVectorSize(levelQ, levelP), levelQ + 1, levelP + 1))
+    return Ciphertext(key(), key())
+
+
+class Encryptor(_enc.Encryptor):
+    """rgsw.NewEncryptor(params, key): an rlwe.Encryptor whose Encrypt and EncryptZero also take an rgsw.Ciphertext (secret-key
+    encryption only).  Every call is an exact function of the byte stream of the PRNG; the drawing order is the reference's: per
+    row (i, j) one encryptZeroSk on Value[0][i][j], then one on Value[1][i][j]; in a table, ciphertext after ciphertext."""
+
+    def __init__(self, evaluator: rlwe.Evaluator, prng, sk=None, XeSigma: float = _enc.DefaultXeSigma, XeBound: float = _enc.DefaultXeBound):
+        super().__init__(evaluator, prng, sk, _enc.DefaultXsP, XeSigma, XeBound)
+
+    def EncryptZero(self, ct):
+        if not isinstance(ct, Ciphertext):
+            return super().EncryptZero(ct)
+        self.prng.check(load().he_rgsw_encrypt_zero(self.h, ct.Value[0].h, ct.Value[1].h))
+
+    def Encrypt(self, pt, ct):
+        """pt: an rlwe Plaintext (Value, IsNTT, IsMontgomery) or None"""
+        if not isinstance(ct, Ciphertext):
+            return super().Encrypt(pt, ct)
+        if pt is None:
+            return self.EncryptZero(ct)
+        self.prng.check(load().he_rgsw_encrypt(self.h, pt.Value.h, int(pt.IsNTT), int(pt.IsMontgomery), ct.Value[0].h, ct.Value[1].h))
+
+    def EncryptTable(self, pts, sel, cts):
+        """cts[k] = Encrypt(entry sel[k] of pts) for k = 0, 1, ... on the one source; pts: one Poly of batch m (NTT and Montgomery)
+        or None; sel[k] == -1: EncryptZero.  One finishing launch per chunk of ciphertexts."""
+        s = np.ascontiguousarray(sel, dtype=np.int32)
+        n = len(cts)
+        if s.size != n:
+            raise ValueError("sel and cts must have the same length")
+        a0 = (H * max(n, 1))(*[c.Value[0].h for c in cts])
+        a1 = (H * max(n, 1))(*[c.Value[1].h for c in cts])
+        self.prng.check(load().he_rgsw_encrypt_table(self.h, pts.h if pts is not None else 0, s.ctypes.data_as(C.POINTER(C.c_int32)), n, a0, a1))
 
 
 # ---- the element-wise helpers of core/rgsw/evaluator.go:283-356, on the device words of the keys -----------------------------
