@@ -16,6 +16,7 @@
 #define HERING_HPP
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <complex>
@@ -39,6 +40,7 @@
 #include "hering_encryptor.h"
 #include "hering_keygen.h"
 #include "hering_rgsw_encryptor.h"
+#include "hering_multiparty.h"
 
 namespace hering {
 
@@ -1220,6 +1222,7 @@ public:
         r_ = detail::own(h, he_keygen_destroy);
     }
     he_handle h() const { return r_->h; }
+    const Evaluator &GetEvaluator() const { return eval_; }
     // -- secret and public keys
     void GenSecretKey(SecretKey &sk) const {
         check(he_keygen_secret_key(h(), sk.Value.Q.Level(), sk.Value.P.h() ? sk.Value.P.Level() : -1, sk.Value.Q.h(), sk.Value.P.h()));
@@ -1330,6 +1333,226 @@ public:
 };
 }  // namespace rlwe
 using KeyGenerator = rlwe::KeyGenerator;
+
+// The threshold protocols of the reference's multiparty package (hering_multiparty.h), with the reference's method names and argument
+// order.  A protocol object is one party's view: its private samplers are its rlwe::KeyGenerator, the common reference string any
+// sampling::PRNG.  Gadget-shaped CRPs and shares live in EvaluationKey handles: a CRP in component 1, a degree-0 share in component
+// 0, a round-one share of the relinearization protocol in both.  A Go error is an exception (hering::Error, std::invalid_argument).
+namespace multiparty {
+using CRS = sampling::PRNG;
+// EvaluationKeyGenCRP / EvaluationKeyGenShare / RelinearizationKeyGenShare: Degree = the components in use, minus one
+struct GadgetShare {
+    EvaluationKey Key;
+    int Degree = 0;
+};
+using EvaluationKeyGenCRP = GadgetShare;
+using EvaluationKeyGenShare = GadgetShare;
+using RelinearizationKeyGenCRP = GadgetShare;
+using RelinearizationKeyGenShare = GadgetShare;
+struct GaloisKeyGenShare : GadgetShare {
+    uint64_t GaloisElement = 0;
+};
+using GaloisKeyGenCRP = GadgetShare;
+
+class EvaluationKeyGenProtocol {
+protected:
+    rlwe::KeyGenerator kgen_;
+
+public:
+    explicit EvaluationKeyGenProtocol(const rlwe::KeyGenerator &kgen) : kgen_(kgen) {}
+    EvaluationKeyGenShare AllocateShare(const rlwe::EvaluationKeyParameters &evkParams = {}) const { return {kgen_.NewEvaluationKey(evkParams), 0}; }
+    // sampleCRP (keygen_evk.go:64-83): i outer and j inner, one ringqp uniform ReadNew per row
+    EvaluationKeyGenCRP SampleCRP(const CRS &crs, const rlwe::EvaluationKeyParameters &evkParams = {}) const {
+        GadgetShare crp{kgen_.NewEvaluationKey(evkParams), 0};
+        check(he_mp_crp_gadget(kgen_.GetEvaluator().h(), crs.h(), crp.Key.h()));
+        return crp;
+    }
+    void GenShare(const rlwe::SecretKey &skIn, const rlwe::SecretKey &skOut, const EvaluationKeyGenCRP &crp, EvaluationKeyGenShare &shareOut) const {
+        check(he_mp_evk_gen_share(kgen_.h(), skIn.Value.Q.h(), skOut.Value.Q.h(), skOut.Value.P.h(), crp.Key.h(), shareOut.Key.h()));
+        shareOut.Degree = 0;
+    }
+    // one Add per word on components 0..Degree()
+    void AggregateShares(const GadgetShare &share1, const GadgetShare &share2, GadgetShare &share3) const {
+        check(he_mp_gadget_aggregate(share1.Key.h(), share2.Key.h(), share1.Degree, share3.Key.h()));
+        share3.Degree = share1.Degree;
+    }
+    void GenEvaluationKey(const EvaluationKeyGenShare &share, const EvaluationKeyGenCRP &crp, EvaluationKey &evk) const {
+        check(he_mp_evk_finalize(share.Key.h(), crp.Key.h(), evk.h()));
+    }
+};
+
+class GaloisKeyGenProtocol : public EvaluationKeyGenProtocol {
+public:
+    using EvaluationKeyGenProtocol::EvaluationKeyGenProtocol;
+    GaloisKeyGenShare AllocateShare(const rlwe::EvaluationKeyParameters &evkParams = {}) const {
+        GaloisKeyGenShare s;
+        s.Key = kgen_.NewEvaluationKey(evkParams);
+        return s;
+    }
+    void GenShare(const rlwe::SecretKey &sk, uint64_t galEl, const GaloisKeyGenCRP &crp, GaloisKeyGenShare &shareOut) const {
+        check(he_mp_galois_gen_share(kgen_.h(), galEl, sk.Value.Q.h(), sk.Value.P.h(), crp.Key.h(), shareOut.Key.h()));
+        shareOut.GaloisElement = galEl;  // "Important" (keygen_gal.go:60)
+        shareOut.Degree = 0;
+    }
+    void AggregateShares(const GaloisKeyGenShare &share1, const GaloisKeyGenShare &share2, GaloisKeyGenShare &share3) const {
+        if (share1.GaloisElement != share2.GaloisElement)
+            throw std::invalid_argument("cannot aggregate: GaloisKeyGenShares do not share the same GaloisElement");
+        share3.GaloisElement = share1.GaloisElement;
+        EvaluationKeyGenProtocol::AggregateShares(share1, share2, share3);
+    }
+    void GenGaloisKey(const GaloisKeyGenShare &share, const GaloisKeyGenCRP &crp, rlwe::GaloisKey &gk) const {
+        GenEvaluationKey(share, crp, gk.Key);
+        const Ring &q = kgen_.GetEvaluator().RingQ();
+        gk.GaloisElement = share.GaloisElement;
+        gk.NthRoot = (uint64_t)q.N() * (q.Type() == RingType::Standard ? 2 : 4);
+    }
+};
+
+class RelinearizationKeyGenProtocol : public EvaluationKeyGenProtocol {
+public:
+    using EvaluationKeyGenProtocol::EvaluationKeyGenProtocol;
+    struct Shares {
+        rlwe::SecretKey ephSk;
+        RelinearizationKeyGenShare r1, r2;
+    };
+    // (ephSk at the parameters' top levels, a degree-1 and a degree-0 share)
+    Shares AllocateShare(const rlwe::EvaluationKeyParameters &evkParams = {}) const {
+        const Evaluator &ev = kgen_.GetEvaluator();
+        const bool hasP = ev.RingP().MaxLevel() >= 0;
+        return {rlwe::SecretKey{{ev.RingQ().NewPoly(), hasP ? ev.RingP().NewPoly() : Poly()}}, {kgen_.NewEvaluationKey(evkParams), 1},
+                {kgen_.NewEvaluationKey(evkParams), 0}};
+    }
+    void GenShareRoundOne(const rlwe::SecretKey &sk, const RelinearizationKeyGenCRP &crp, rlwe::SecretKey &ephSkOut, RelinearizationKeyGenShare &shareOut) const {
+        check(he_mp_rkg_round_one(kgen_.h(), sk.Value.Q.h(), sk.Value.P.h(), crp.Key.h(), ephSkOut.Value.Q.h(), ephSkOut.Value.P.h(), shareOut.Key.h()));
+        shareOut.Degree = 1;
+    }
+    // words in [0, 2q), as the reference leaves them
+    void GenShareRoundTwo(const rlwe::SecretKey &ephSk, const rlwe::SecretKey &sk, const RelinearizationKeyGenShare &round1,
+                          RelinearizationKeyGenShare &shareOut) const {
+        check(he_mp_rkg_round_two(kgen_.h(), ephSk.Value.Q.h(), ephSk.Value.P.h(), sk.Value.Q.h(), sk.Value.P.h(), round1.Key.h(), shareOut.Key.h()));
+        shareOut.Degree = 0;
+    }
+    void GenRelinearizationKey(const RelinearizationKeyGenShare &round1, const RelinearizationKeyGenShare &round2, EvaluationKey &evalKeyOut) const {
+        check(he_mp_rlk_finalize(round1.Key.h(), round2.Key.h(), evalKeyOut.h()));
+    }
+};
+
+using PublicKeyGenCRP = rlwe::PolyQP;
+using PublicKeyGenShare = rlwe::PolyQP;
+class PublicKeyGenProtocol {
+    rlwe::KeyGenerator kgen_;
+    bool hasP() const { return kgen_.GetEvaluator().RingP().MaxLevel() >= 0; }
+
+public:
+    explicit PublicKeyGenProtocol(const rlwe::KeyGenerator &kgen) : kgen_(kgen) {}
+    PublicKeyGenShare AllocateShare() const {
+        const Evaluator &ev = kgen_.GetEvaluator();
+        return {ev.RingQ().NewPoly(), hasP() ? ev.RingP().NewPoly() : Poly()};
+    }
+    PublicKeyGenCRP SampleCRP(const CRS &crs) const {
+        const Evaluator &ev = kgen_.GetEvaluator();
+        PublicKeyGenCRP crp = AllocateShare();
+        if (hasP()) UniformSampler(crs, ev.RingQ(), ev.RingP()).Read(crp.Q, crp.P);
+        else UniformSampler(crs, ev.RingQ()).Read(crp.Q);
+        return crp;
+    }
+    void GenShare(const rlwe::SecretKey &sk, const PublicKeyGenCRP &crp, PublicKeyGenShare &shareOut) const {
+        check(he_mp_pk_gen_share(kgen_.h(), sk.Value.Q.h(), sk.Value.P.h(), crp.Q.h(), crp.P.h(), shareOut.Q.h(), shareOut.P.h()));
+    }
+    void AggregateShares(const PublicKeyGenShare &share1, const PublicKeyGenShare &share2, PublicKeyGenShare &shareOut) const {
+        const Evaluator &ev = kgen_.GetEvaluator();
+        ev.RingQ().Add(share1.Q, share2.Q, shareOut.Q);
+        if (hasP()) ev.RingP().Add(share1.P, share2.P, shareOut.P);
+    }
+    void GenPublicKey(const PublicKeyGenShare &roundShare, const PublicKeyGenCRP &crp, rlwe::PublicKey &pubkey) const {
+        const rlwe::PolyQP *src[2] = {&roundShare, &crp};
+        for (int k = 0; k < 2; k++) {
+            pubkey.Value[(size_t)k].Q.CopyLvl(src[k]->Q.Level(), src[k]->Q);
+            if (hasP()) pubkey.Value[(size_t)k].P.CopyLvl(src[k]->P.Level(), src[k]->P);
+        }
+    }
+};
+
+// NewKeySwitchProtocol / NewPublicKeySwitchProtocol: DiscreteGaussian{sqrt(NoiseFreshSK^2 + noise.Sigma^2), 6 sigma} (keyswitch_sk.go:49-52)
+inline DiscreteGaussian SmudgingNoise(double noiseSigma, double NoiseFreshSK) {
+    const double s = std::sqrt(NoiseFreshSK * NoiseFreshSK + noiseSigma * noiseSigma);
+    return DiscreteGaussian{s, 6 * s};
+}
+struct KeySwitchCRP {
+    Poly Value;
+};
+struct KeySwitchShare {
+    Poly Value;  // words in [0, 2q)
+    int Level() const { return Value.Level(); }
+};
+class KeySwitchProtocol {
+    rlwe::KeyGenerator kgen_;
+    DiscreteGaussian noise_;
+
+public:
+    // (kgen, noiseFlooding.Sigma, the parameters' NoiseFreshSK)
+    KeySwitchProtocol(const rlwe::KeyGenerator &kgen, double noiseSigma, double NoiseFreshSK) : kgen_(kgen), noise_(SmudgingNoise(noiseSigma, NoiseFreshSK)) {}
+    const DiscreteGaussian &Noise() const { return noise_; }
+    KeySwitchShare AllocateShare(int level) const { return {kgen_.GetEvaluator().RingQ().AtLevel(level).NewPoly()}; }
+    KeySwitchCRP SampleCRP(int level, const CRS &crs) const { return {UniformSampler(crs, kgen_.GetEvaluator().RingQ().AtLevel(level)).ReadNew()}; }
+    void GenShare(const rlwe::SecretKey &skInput, const rlwe::SecretKey &skOutput, const rlwe::Ciphertext &ct, KeySwitchShare &shareOut) const {
+        const int level = shareOut.Level() < ct.Value[1].Level() ? shareOut.Level() : ct.Value[1].Level();  // :84
+        check(he_mp_cks_gen_share(kgen_.h(), level, skInput.Value.Q.h(), skOutput.Value.Q.h(), ct.Value[1].h(), ct.Meta.IsNTT, noise_.Sigma, noise_.Bound,
+                                  shareOut.Value.h()));
+    }
+    void AggregateShares(const KeySwitchShare &share1, const KeySwitchShare &share2, KeySwitchShare &shareOut) const {
+        if (share1.Level() != share2.Level() || share1.Level() != shareOut.Level()) throw std::invalid_argument("cannot AggregateShares: shares levels do not match");
+        kgen_.GetEvaluator().RingQ().AtLevel(share1.Level()).Add(share1.Value, share2.Value, shareOut.Value);
+    }
+    void KeySwitch(const rlwe::Ciphertext &ctIn, const KeySwitchShare &combined, rlwe::Ciphertext &opOut) const {
+        const int level = ctIn.Level();
+        if (&ctIn != &opOut) {
+            opOut.Value[1].CopyLvl(level, ctIn.Value[1]);
+            opOut.Meta = ctIn.Meta;
+            opOut.level = level;
+        }
+        kgen_.GetEvaluator().RingQ().AtLevel(level).Add(ctIn.Value[0], combined.Value, opOut.Value[0]);
+    }
+};
+
+using PublicKeySwitchShare = rlwe::Ciphertext;
+class PublicKeySwitchProtocol {
+    rlwe::Encryptor enc_;
+    Evaluator eval_;
+    sampling::PRNG noisePrng_;
+    DiscreteGaussian noise_;
+
+public:
+    // (the party's encryptor with its own source, its evaluator, the source of the smudging noise, noiseFlooding.Sigma, NoiseFreshSK)
+    PublicKeySwitchProtocol(const rlwe::Encryptor &enc, const Evaluator &eval, const sampling::PRNG &noisePrng, double noiseSigma, double NoiseFreshSK)
+        : enc_(enc), eval_(eval), noisePrng_(noisePrng), noise_(SmudgingNoise(noiseSigma, NoiseFreshSK)) {}
+    PublicKeySwitchShare AllocateShare(int levelQ) const {
+        const Ring r = eval_.RingQ().AtLevel(levelQ);
+        return rlwe::Ciphertext{{r.NewPoly(), r.NewPoly()}, rlwe::MetaData{}, -1};
+    }
+    void GenShare(const rlwe::SecretKey &sk, const rlwe::PublicKey &pk, const rlwe::Ciphertext &ct, PublicKeySwitchShare &shareOut) const {
+        const int level = shareOut.Value[0].Level() < ct.Value[1].Level() ? shareOut.Value[0].Level() : ct.Value[1].Level();  // :71
+        const rlwe::Encryptor enc = enc_.WithKey(pk);
+        check(he_mp_pcks_gen_share(enc.h(), noisePrng_.h(), level, sk.Value.Q.h(), ct.Value[1].h(), ct.Meta.IsNTT, ct.Meta.IsMontgomery, noise_.Sigma,
+                                   noise_.Bound, shareOut.Value[0].h(), shareOut.Value[1].h()));
+        shareOut.Meta = ct.Meta;
+    }
+    void AggregateShares(const PublicKeySwitchShare &share1, const PublicKeySwitchShare &share2, PublicKeySwitchShare &shareOut) const {
+        if (share1.Value[0].Level() != share1.Value[1].Level()) throw std::invalid_argument("cannot AggregateShares: the two shares are at different levelQ");
+        const Ring r = eval_.RingQ().AtLevel(share1.Value[0].Level());
+        for (size_t k = 0; k < 2; k++) r.Add(share1.Value[k], share2.Value[k], shareOut.Value[k]);
+    }
+    void KeySwitch(const rlwe::Ciphertext &ctIn, const PublicKeySwitchShare &combined, rlwe::Ciphertext &opOut) const {
+        const int level = ctIn.Level();
+        if (&ctIn != &opOut) {
+            opOut.Meta = ctIn.Meta;
+            opOut.level = level;
+        }
+        eval_.RingQ().AtLevel(level).Add(ctIn.Value[0], combined.Value[0], opOut.Value[0]);
+        opOut.Value[1].CopyLvl(level, combined.Value[1]);
+    }
+};
+}  // namespace multiparty
 
 // ---- RGSW (core/rgsw; hering_rgsw.h), NTT domain -----------------------------------------------------------------------------
 namespace rgsw {

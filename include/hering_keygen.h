@@ -5,7 +5,9 @@
  *
  * Elsewhere: rgsw.Encryptor and the blind-rotation key generator (hering_rgsw_encryptor.h: a table of RGSW ciphertexts drawn row
  * by row, with the arithmetic after the draws and the two-key gadget term fused per chunk of ciphertexts).  Out of scope: compressed
- * (seeded, degree-0) evaluation keys and sampling.KeyedPRNG; Ternary{H} as the Encryptor's own Xs; multiparty key generation.
+ * (seeded, degree-0) evaluation keys and sampling.KeyedPRNG; Ternary{H} as the Encryptor's own Xs.  The threshold protocols of the
+ * multiparty package -- collective public, evaluation, Galois and relinearization keys, collective key switching -- are in
+ * hering_multiparty.h, over this generator's handle.
  *
  * The frame of hering_encryptor.h: 0 on success, <0 on error (HE_E*), he_last_error() for the message; outputs come last.  A call
  * runs after the calling thread's queued requests, returns with its device work finished, has no replay number and is HE_EINVAL

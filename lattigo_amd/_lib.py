@@ -13,7 +13,7 @@ _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), o
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
          os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h"),
-         os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h")]
+         os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h"), os.path.join(_INC, "hering_multiparty.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -153,6 +153,11 @@ def _declare(L):
         "he_rgsw_encrypt_zero": [H, H, H], "he_rgsw_encrypt": [H, H, i, i, H, H],
         "he_rgsw_encrypt_table": [H, H, C.POINTER(C.c_int32), i, HP, HP],
         "he_blindrot_gen_evaluation_key": [H, H, H, H, i, HP, HP, HP],
+        "he_mp_crp_gadget": [H, H, H], "he_mp_evk_gen_share": [H, H, H, H, H, H], "he_mp_galois_gen_share": [H, C.c_uint64, H, H, H, H],
+        "he_mp_gadget_aggregate": [H, H, i, H], "he_mp_evk_finalize": [H, H, H],
+        "he_mp_rkg_round_one": [H, H, H, H, H, H, H], "he_mp_rkg_round_two": [H, H, H, H, H, H, H], "he_mp_rlk_finalize": [H, H, H],
+        "he_mp_pk_gen_share": [H, H, H, H, H, H, H], "he_mp_cks_gen_share": [H, i, H, H, H, i, C.c_double, C.c_double, H],
+        "he_mp_pcks_gen_share": [H, H, i, H, H, i, i, C.c_double, C.c_double, H, H],
         "he_ring_xpow2_ntt": [H, i, i, i, H], "he_ring_split_ntt": [H, i, H, H, H], "he_ring_merge_ntt": [H, i, H, H, H],
         "he_ringpack_split": [H, i, H, H, H, H, H, H, H], "he_ringpack_merge": [H, i, H, H, H, H, H, H, H],
         "he_ringpack_expand_step": [H, i, i, i, H, H, H, H, H, H],

@@ -51,6 +51,7 @@
 #include "../../include/hering_encryptor.h"
 #include "../../include/hering_keygen.h"
 #include "../../include/hering_rgsw_encryptor.h"
+#include "../../include/hering_multiparty.h"
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
@@ -6142,8 +6143,9 @@ int he_keygen_secret_key_hw(he_handle hk, int hw, int levelQ, int levelP, he_han
 }
 
 // The gadget vector of a key, row by row: G[row][index] = MForm(P 2^(j pw2) mod q_index) on the Q limbs of the row's digit
-// (gadgetciphertext.go:183-237), 0 elsewhere.  P: the product of the key's special primes (1 without).
-static std::vector<uint64_t> gadget_table(const Evk &k) {
+// (gadgetciphertext.go:183-237), 0 elsewhere.  P: the product of the key's special primes (1 without).  mont = false: P 2^(j pw2) mod
+// q_index itself (round one of the relinearization protocol, include/hering_multiparty.h).
+static std::vector<uint64_t> gadget_table(const Evk &k, bool mont = true) {
     const BasisExtender &be = *k.ev->be;
     const int nQk = k.nQk, alpha = std::max(k.nPk, 1), nrns = k.pw2 ? (int)k.nj.size() : k.beta;
     std::vector<uint64_t> G((size_t)k.beta * nQk, 0);
@@ -6158,7 +6160,7 @@ static std::vector<uint64_t> gadget_table(const Evk &k) {
                 uint64_t f = 1 % q;
                 for (int t = 0; t < k.nPk; t++) f = mulmod(f, be.P->moduli[(size_t)t] % q, q);
                 for (int t = 0; t < j; t++) f = mulmod(f, ((uint64_t)1 << k.pw2) % q, q);  // (:237, once per window)
-                G[(size_t)row * nQk + index] = to_mont(f, q);
+                G[(size_t)row * nQk + index] = mont ? to_mont(f, q) : f;
             }
         }
     }
@@ -6174,6 +6176,7 @@ static int evk_shape_for_keygen(const Evk &k, const char *who, const char *name)
 static void evk_rows_args(const Evk &k, EvkRowsArgs &a) {
     const BasisExtender &be = *k.ev->be;
     a.key = k.d;
+    a.c1 = k.d;
     a.blk = (size_t)(k.nQk + k.nPk) * be.Q->N;
     a.N = be.Q->N; a.rows = k.beta; a.nq = k.nQk; a.np = k.nPk;
     a.mc = be.qp.mc;
@@ -6182,8 +6185,8 @@ static void evk_rows_args(const Evk &k, EvkRowsArgs &a) {
 }
 // the gadget table of k in scratch (the caller holds the context and has reserved beta nQk + 2 words more)
 // (G is the caller's: it outlives the copy, which the caller's drain of the stream ends)
-static int gadget_table_upload(Ctx &c, const Evk &k, std::vector<uint64_t> &G, const uint64_t **d_G) {
-    G = gadget_table(k);
+static int gadget_table_upload(Ctx &c, const Evk &k, std::vector<uint64_t> &G, const uint64_t **d_G, bool mont = true) {
+    G = gadget_table(k, mont);
     uint64_t *p = c.arena_take(G.size());
     HIP_TRY(hipMemcpyAsync(p, G.data(), G.size() * 8, hipMemcpyHostToDevice, c.stream));
     *d_G = p;
@@ -6227,7 +6230,10 @@ int he_gadget_add_poly(he_handle hpt, he_handle hk0, he_handle hk1) {
 }
 
 // genEvaluationKey (:287-330) without the frame.  skIn (nQk limbs), skOut = (skOutQ, skOutP): device words, NTT and Montgomery.
-static int keygen_evaluation_key(KeyGen &kg, const char *who, const uint64_t *skIn, const uint64_t *skOutQ, const uint64_t *skOutP, Evk &k) {
+// crp: EvaluationKeyGenProtocol.GenShare (multiparty/keygen_evk.go:86-183; include/hering_multiparty.h) instead -- no uniform draw, c1
+// is component 1 of crp (a key of k's shape, possibly k), the Gaussians are drawn j outer and i inner, and k, a share, is not committed.
+static int keygen_evaluation_key(KeyGen &kg, const char *who, const uint64_t *skIn, const uint64_t *skOutQ, const uint64_t *skOutP, Evk &k,
+                                 const Evk *crp = nullptr) {
     BasisExtender &be = *kg.ev->be;
     Ctx &c = *be.ctx;
     Prng &g = *kg.prng_keep;
@@ -6244,11 +6250,23 @@ static int keygen_evaluation_key(KeyGen &kg, const char *who, const uint64_t *sk
     const ModConst *const mc[2] = {be.Q->dev.mc, nPk ? be.P->dev.mc : nullptr};
     const int nl[2] = {nQk, nPk};
     const size_t bs[2] = {2 * blk, 2 * blk};
-    for (int r = 0; r < R && rc == HE_OK; r++) {  // one encryptZeroSk per row (:309-320): the uniform c1 (Q, then P), then the Gaussian e
-        uint64_t *c1 = k.d + ((size_t)2 * r + 1) * blk;
-        uint64_t *const out[2] = {c1, c1 + (size_t)nQk * N};
-        rc = uniform_read_run(who, c, g, N, 1, nPk ? 2 : 1, mc, nl, out, bs, false, nullptr);
-        if (rc != HE_OK) break;
+    std::vector<int> order;  // the rows in drawing order
+    if (crp && k.pw2) {      // (keygen_evk.go:134-138)
+        const int nmax = *std::max_element(k.nj.begin(), k.nj.end());
+        for (int j = 0; j < nmax; j++)
+            for (size_t i = 0; i < k.nj.size(); i++)
+                if (j < k.nj[i]) order.push_back(k.prefix[i] + j);
+    } else {
+        for (int r = 0; r < R; r++) order.push_back(r);
+    }
+    for (size_t t = 0; t < order.size() && rc == HE_OK; t++) {  // one encryptZeroSk per row (:309-320): the uniform c1 (Q, then P), then the Gaussian e
+        const int r = order[t];
+        if (!crp) {
+            uint64_t *c1 = k.d + ((size_t)2 * r + 1) * blk;
+            uint64_t *const out[2] = {c1, c1 + (size_t)nQk * N};
+            rc = uniform_read_run(who, c, g, N, 1, nPk ? 2 : 1, mc, nl, out, bs, false, nullptr);
+            if (rc != HE_OK) break;
+        }
         rc = gaussian_parse_run(who, c, g, N, 1, kg.sigma, kg.bound, [&](const uint64_t *vals) -> int {
             HIP_TRY(hipMemcpyAsync(d_e + (size_t)r * N, vals, (size_t)N * 8, hipMemcpyDeviceToDevice, c.stream));
             return HE_OK;
@@ -6269,11 +6287,14 @@ static int keygen_evaluation_key(KeyGen &kg, const char *who, const uint64_t *sk
         EvkRowsArgs a;
         evk_rows_args(k, a);
         a.skOutQ = skOutQ; a.skOutP = skOutP; a.pt = skIn;
+        if (crp) a.c1 = crp->d;
         TRY(gadget_table_upload(c, k, G, &a.G));
         c.acct(3.0 * (nQk + nPk), 0, R, N);
         HIP_TRY(launch_evk_finish(a, c.stream));  // :420-425 and AddPolyTimesGadgetVectorToGadgetCiphertext (:326)
-        TRY(evk_derive(k));
-        k.word_mul = 1;
+        if (!crp) {
+            TRY(evk_derive(k));
+            k.word_mul = 1;
+        }
         return HE_OK;
     }();
     (void)hipMemsetAsync(d_e, 0, stage_bytes, c.stream);
@@ -6369,11 +6390,20 @@ int he_keygen_relinearization_key(he_handle hk, he_handle skQ, he_handle skP, he
     const int rs = rlwe_frame_end(kg->ctx());
     return rc != HE_OK ? rc : rs;
 }
-// GenGaloisKey (:140-177) without the frame
-static int keygen_galois_key(KeyGen &kg, const char *who, uint64_t gal, he_handle skQ, he_handle skP, he_handle hgk) {
+static int evk_same_shape(const char *who, const Evk &a, const Evk &b, const char *na, const char *nb) {
+    if (a.ev != b.ev || a.beta != b.beta || a.nQk != b.nQk || a.nPk != b.nPk || a.pw2 != b.pw2 || a.nj != b.nj)
+        return fail(HE_EINVAL, "%s: %s and %s differ in evaluator or shape", who, na, nb);
+    return HE_OK;
+}
+// GenGaloisKey (:140-177) without the frame; hcrp: GaloisKeyGenProtocol.GenShare (multiparty/keygen_gal.go:48-71) into the share hgk
+static int keygen_galois_key(KeyGen &kg, const char *who, uint64_t gal, he_handle skQ, he_handle skP, he_handle hgk, he_handle hcrp = 0) {
     if (!(gal & 1)) return fail(HE_EINVAL, "%s: the Galois element %llu is even", who, (unsigned long long)gal);
-    std::shared_ptr<Evk> k;
+    std::shared_ptr<Evk> k, crp;
     TRY(keygen_evk(kg, who, hgk, &k));
+    if (hcrp) {
+        TRY(keygen_evk(kg, who, hcrp, &crp));
+        TRY(evk_same_shape(who, *crp, *k, "crp", "share"));
+    }
     std::shared_ptr<Poly> q, p;
     TRY(keygen_sk_for(kg, who, *k, skQ, skP, "skQ", "skP", &q, &p));
     const Ring &Q = *kg.ev->be->Q;
@@ -6394,7 +6424,7 @@ static int keygen_galois_key(KeyGen &kg, const char *who, uint64_t gal, he_handl
     if (rc == HE_OK && k->nPk) rc = he_automorphism_ntt_with_index(kg.hp, k->nPk - 1, skP, hix, op.h);  // :169-171
     if (rc == HE_OK) {
         { Scope sc(&kg.ctx()); }
-        rc = keygen_evaluation_key(kg, who, q->d, get<Poly>(oq.h, T_POLY)->d, k->nPk ? get<Poly>(op.h, T_POLY)->d : nullptr, *k);  // :173
+        rc = keygen_evaluation_key(kg, who, q->d, get<Poly>(oq.h, T_POLY)->d, k->nPk ? get<Poly>(op.h, T_POLY)->d : nullptr, *k, crp.get());  // :173
     }
     (void)he_automorphism_index_destroy(hix);
     return rc;
@@ -6424,6 +6454,333 @@ int he_keygen_galois_keys(he_handle hk, int n, const uint64_t *gal_els, he_handl
     int rc = HE_OK;
     for (int i = 0; i < n && rc == HE_OK; i++) rc = keygen_galois_key(*kg, who, gal_els[i], skQ, skP, gks[i]);  // :189-195, key after key
     const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+
+// ---------------------------------------------------------------------------------------
+// multiparty.EvaluationKeyGenProtocol and GaloisKeyGenProtocol (include/hering_multiparty.h; multiparty/keygen_evk.go, keygen_gal.go).
+// A share is keygen_evaluation_key with the CRP as its c1; aggregation is one launch over the key storage.
+// ---------------------------------------------------------------------------------------
+int he_mp_crp_gadget(he_handle hev, he_handle hcrs, he_handle hevk) {
+    static const char *who = "he_mp_crp_gadget";
+    GET(ev, Evaluator, hev, T_EVAL);
+    GET(g, Prng, hcrs, T_PRNG);
+    GET(k, Evk, hevk, T_EVK);
+    BasisExtender &be = *ev->be;
+    Ctx &c = *be.ctx;
+    TRY(rlwe_frame_begin(c, who));
+    if (k->ev != ev) return fail(HE_EINVAL, "%s: the key belongs to another evaluator", who);
+    TRY(evk_shape_for_keygen(*k, who, "the key"));
+    { Scope sc(&c); }  // (after the calling thread's queued requests)
+    const int N = be.Q->N, nQk = k->nQk, nPk = k->nPk;
+    const size_t blk = (size_t)(nQk + nPk) * N;
+    const ModConst *const mc[2] = {be.Q->dev.mc, nPk ? be.P->dev.mc : nullptr};
+    const int nl[2] = {nQk, nPk};
+    const size_t bs[2] = {2 * blk, 2 * blk};
+    int rc = HE_OK;
+    for (int r = 0; r < k->beta && rc == HE_OK; r++) {  // keygen_evk.go:74-80: us.ReadNew() per (i, j), i outer
+        uint64_t *c1 = k->d + ((size_t)2 * r + 1) * blk;
+        uint64_t *const out[2] = {c1, c1 + (size_t)nQk * N};
+        rc = uniform_read_run(who, c, *g, N, 1, nPk ? 2 : 1, mc, nl, out, bs, false, nullptr);
+    }
+    const int rs = rlwe_frame_end(c);
+    return rc != HE_OK ? rc : rs;
+}
+int he_mp_evk_gen_share(he_handle hk, he_handle skInQ, he_handle skOutQ, he_handle skOutP, he_handle hcrp, he_handle hshare) {
+    static const char *who = "he_mp_evk_gen_share";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    std::shared_ptr<Evk> crp, k;
+    TRY(keygen_evk(*kg, who, hcrp, &crp));
+    TRY(keygen_evk(*kg, who, hshare, &k));
+    TRY(evk_same_shape(who, *crp, *k, "crp", "share"));
+    std::shared_ptr<Poly> in, oq, op;
+    TRY(keygen_poly(*kg, who, skInQ, k->nQk, "skInQ", &in));
+    TRY(keygen_sk_for(*kg, who, *k, skOutQ, skOutP, "skOutQ", "skOutP", &oq, &op));
+    { Scope sc(&kg->ctx()); }
+    return keygen_evaluation_key(*kg, who, in->d, oq->d, op ? op->d : nullptr, *k, crp.get());
+}
+int he_mp_galois_gen_share(he_handle hk, uint64_t gal_el, he_handle skQ, he_handle skP, he_handle hcrp, he_handle hshare) {
+    static const char *who = "he_mp_galois_gen_share";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    if (!hcrp) return fail(HE_EHANDLE, "%s: bad Evk handle 0 for crp", who);
+    const int rc = keygen_galois_key(*kg, who, gal_el, skQ, skP, hshare, hcrp);
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_mp_gadget_aggregate(he_handle ha, he_handle hb, int degree, he_handle hout) {
+    static const char *who = "he_mp_gadget_aggregate";
+    GET(a, Evk, ha, T_EVK);
+    GET(b, Evk, hb, T_EVK);
+    GET(o, Evk, hout, T_EVK);
+    BasisExtender &be = *a->ev->be;
+    Ctx &c = *be.ctx;
+    TRY(rlwe_frame_begin(c, who));
+    if (degree < 0 || degree > 1) return fail(HE_EINVAL, "%s: degree %d is not 0 or 1", who, degree);
+    TRY(evk_same_shape(who, *a, *b, "a", "b"));
+    TRY(evk_same_shape(who, *a, *o, "a", "out"));
+    if (a->nQk + a->nPk > kMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs per row, at most %d", who, a->nQk + a->nPk, kMaxLimbs);
+    Scope sc(&c);
+    EvkRowsArgs ra;
+    evk_rows_args(*a, ra);
+    GadgetAggArgs g;
+    g.a = a->d; g.b = b->d; g.out = o->d;
+    g.blk = ra.blk; g.N = ra.N; g.rows = ra.rows; g.ncomp = degree + 1; g.nl = ra.nq + ra.np; g.mc = ra.mc;
+    std::memcpy(g.mod, ra.mod, sizeof g.mod);
+    // one Add: words below ma q and mb q give words below (ma + mb - 1) q
+    o->word_mul = std::min(Evk::kWordMulCap, std::max<uint64_t>(o->word_mul, a->word_mul + b->word_mul - 1));
+    HIP_TRY(launch_gadget_aggregate(g, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+int he_mp_evk_finalize(he_handle hshare, he_handle hcrp, he_handle hevk) {
+    static const char *who = "he_mp_evk_finalize";
+    GET(sh, Evk, hshare, T_EVK);
+    GET(crp, Evk, hcrp, T_EVK);
+    GET(k, Evk, hevk, T_EVK);
+    BasisExtender &be = *k->ev->be;
+    Ctx &c = *be.ctx;
+    TRY(rlwe_frame_begin(c, who));
+    TRY(evk_same_shape(who, *sh, *k, "share", "evk"));
+    TRY(evk_same_shape(who, *crp, *k, "crp", "evk"));
+    Scope sc(&c);
+    const size_t blk = (size_t)(k->nQk + k->nPk) * be.Q->N;
+    // evk.Value[i][j][0].Copy(m[i][j][0]); evk.Value[i][j][1].Copy(p[i][j]) (keygen_evk.go:233-238): the components lie 2 blk apart
+    if (sh != k) HIP_TRY(hipMemcpy2DAsync(k->d, 2 * blk * 8, sh->d, 2 * blk * 8, blk * 8, (size_t)k->beta, hipMemcpyDeviceToDevice, c.stream));
+    if (crp != k) HIP_TRY(hipMemcpy2DAsync(k->d + blk, 2 * blk * 8, crp->d + blk, 2 * blk * 8, blk * 8, (size_t)k->beta, hipMemcpyDeviceToDevice, c.stream));
+    k->word_mul = std::min(Evk::kWordMulCap, std::max(sh->word_mul, crp->word_mul));
+    TRY(evk_derive(*k));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+
+// RelinearizationKeyGenProtocol (multiparty/keygen_relin.go).  A round draws row by row into a staging buffer of small values and then
+// makes, once for the whole share: the expansion into the Q and P limbs of every row (and component), ONE transform, ONE launch of
+// the round's kernel.  round 1: crp holds the CRP, u = the ephemeral key just drawn, 2 Gaussians per row (component 0's, then
+// component 1's) in the order j outer, i inner; round 2: `in` is the aggregated round-one share, 1 Gaussian per row, i outer.
+static int rkg_round(KeyGen &kg, const char *who, int round, const Evk &in, Evk &k, const uint64_t *skQ, const uint64_t *skP, const uint64_t *uQ,
+                     const uint64_t *uP) {
+    BasisExtender &be = *kg.ev->be;
+    Ctx &c = *be.ctx;
+    Prng &g = *kg.prng_keep;
+    const int N = be.Q->N, R = k.beta, nQk = k.nQk, nPk = k.nPk, per = round == 1 ? 2 : 1;
+    const size_t blk = (size_t)(nQk + nPk) * N;
+    const size_t stage_bytes = (size_t)R * per * N * 8;  // the small values, [R][per][N]: outside the arena, which every draw resets
+    uint64_t *d_e = nullptr;
+    {
+        Scope sc(&c);
+        HIP_TRY(c.pool_take(stage_bytes, (void **)&d_e));
+    }
+    std::vector<int> order;
+    if (round == 1 && k.pw2) {  // (:133-136)
+        const int nmax = *std::max_element(k.nj.begin(), k.nj.end());
+        for (int j = 0; j < nmax; j++)
+            for (size_t i = 0; i < k.nj.size(); i++)
+                if (j < k.nj[i]) order.push_back(k.prefix[i] + j);
+    } else {
+        for (int r = 0; r < R; r++) order.push_back(r);
+    }
+    int rc = HE_OK;
+    for (size_t t = 0; t < order.size() && rc == HE_OK; t++) {
+        const int r = order[t];
+        rc = gaussian_parse_run(who, c, g, N, per, kg.sigma, kg.bound, [&](const uint64_t *vals) -> int {
+            HIP_TRY(hipMemcpyAsync(d_e + (size_t)r * per * N, vals, (size_t)per * N * 8, hipMemcpyDeviceToDevice, c.stream));
+            return HE_OK;
+        });
+    }
+    Scope sc(&c);
+    std::vector<uint64_t> G;
+    if (rc == HE_OK) rc = [&]() -> int {
+        TRY(c.arena_reserve((size_t)R * nQk + 8));
+        // component 0 of every row (round 2) or both components (round 1): entries blk (2 blk) words apart
+        const size_t bs = round == 1 ? blk : 2 * blk;
+        const int B = R * per;
+        const View v{k.d, bs};
+        HIP_TRY(launch_sampler_expand(be.qp.mc, d_e, true, false, false, nullptr, nullptr, v, N, nQk, B, c.stream));
+        if (nPk)
+            HIP_TRY(launch_sampler_expand(be.qp.mc + be.LQ, d_e, true, false, false, nullptr, nullptr, View{k.d + (size_t)nQk * N, bs}, N, nPk, B, c.stream));
+        LimbTab tab = ident_tab(nQk + nPk);
+        for (int i = 0; i < nPk; i++) tab.mod[nQk + i] = (uint8_t)(be.LQ + i);
+        HIP_TRY(be_ntt(be, tab, v, v, B, false, NTT_REDUCE_INPUT));  // ringQP.NTT (:144, :176, :226)
+        EvkRowsArgs ra;
+        evk_rows_args(k, ra);
+        RkgRowsArgs a;
+        a.share = k.d; a.in = in.d; a.blk = blk; a.N = N; a.rows = R; a.nq = nQk; a.np = nPk; a.mc = ra.mc;
+        std::memcpy(a.mod, ra.mod, sizeof a.mod);
+        a.skQ = skQ; a.skP = skP; a.uQ = uQ; a.uP = uP;
+        if (round == 1) TRY(gadget_table_upload(c, k, G, &a.G, false));
+        c.acct((round == 1 ? 5.0 : 4.0) * (nQk + nPk), 0, R, N);
+        HIP_TRY(round == 1 ? launch_rkg_round_one(a, c.stream) : launch_rkg_round_two(a, c.stream));
+        k.word_mul = round == 1 ? 1 : 2;  // (round two leaves words in [0, 2q))
+        return HE_OK;
+    }();
+    (void)hipMemsetAsync(d_e, 0, stage_bytes, c.stream);
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    c.pool_give(stage_bytes, d_e);
+    return rc;
+}
+// the operands two rounds share: the two keys of one shape and distinct, sk and the ephemeral key at the share's levels
+static int rkg_operands(KeyGen &kg, const char *who, he_handle hin, he_handle hshare, const char *nin, he_handle skQ, he_handle skP, he_handle ephQ,
+                        he_handle ephP, std::shared_ptr<Evk> *in, std::shared_ptr<Evk> *k, std::shared_ptr<Poly> pol[4]) {
+    TRY(keygen_evk(kg, who, hin, in));
+    TRY(keygen_evk(kg, who, hshare, k));
+    TRY(evk_same_shape(who, **in, **k, nin, "the share"));
+    if (*in == *k) return fail(HE_EINVAL, "%s: %s and the share are one key", who, nin);
+    TRY(keygen_sk_for(kg, who, **k, skQ, skP, "skQ", "skP", &pol[0], &pol[1]));
+    TRY(keygen_sk_for(kg, who, **k, ephQ, ephP, "ephQ", "ephP", &pol[2], &pol[3]));
+    return HE_OK;
+}
+int he_mp_rkg_round_one(he_handle hk, he_handle skQ, he_handle skP, he_handle hcrp, he_handle ephQ, he_handle ephP, he_handle hshare) {
+    static const char *who = "he_mp_rkg_round_one";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    std::shared_ptr<Evk> crp, k;
+    std::shared_ptr<Poly> pol[4];
+    TRY(rkg_operands(*kg, who, hcrp, hshare, "crp", skQ, skP, ephQ, ephP, &crp, &k, pol));
+    const he_handle outs[2] = {ephQ, k->nPk ? ephP : 0}, others[2] = {skQ, k->nPk ? skP : 0};
+    TRY(rlwe_distinct(who, outs, 2, others, 2));
+    // u (:116-121): the ternary Read at the level of the ephemeral key's own limbs (the reference's sampler stands at the parameters'
+    // top level), then the extension, NTT and MForm at the share's levels
+    const int levelU = std::min(pol[2]->nlimbs, kg->maxQ() + 1) - 1;
+    int rc = he_sampler_ternary_read(kg->hq, levelU, kg->prng, kg->xs_p, 0, 0, ephQ);
+    if (rc == HE_OK) rc = keygen_sk_finish(*kg, k->nQk - 1, k->nPk - 1, ephQ, ephP);
+    if (rc == HE_OK) {
+        { Scope sc(&kg->ctx()); }
+        rc = rkg_round(*kg, who, 1, *crp, *k, pol[0]->d, pol[1] ? pol[1]->d : nullptr, pol[2]->d, pol[3] ? pol[3]->d : nullptr);
+    }
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_mp_rkg_round_two(he_handle hk, he_handle ephQ, he_handle ephP, he_handle skQ, he_handle skP, he_handle hround1, he_handle hshare) {
+    static const char *who = "he_mp_rkg_round_two";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    std::shared_ptr<Evk> r1, k;
+    std::shared_ptr<Poly> pol[4];
+    TRY(rkg_operands(*kg, who, hround1, hshare, "round1", skQ, skP, ephQ, ephP, &r1, &k, pol));
+    if (r1->word_mul != 1) return fail(HE_EINVAL, "%s: round1 holds lazy words; an aggregated round-one share is canonical", who);
+    { Scope sc(&kg->ctx()); }
+    return rkg_round(*kg, who, 2, *r1, *k, pol[0]->d, pol[1] ? pol[1]->d : nullptr, pol[2]->d, pol[3] ? pol[3]->d : nullptr);
+}
+int he_mp_rlk_finalize(he_handle hround1, he_handle hround2, he_handle hrlk) {
+    static const char *who = "he_mp_rlk_finalize";
+    GET(r1, Evk, hround1, T_EVK);
+    GET(r2, Evk, hround2, T_EVK);
+    GET(k, Evk, hrlk, T_EVK);
+    BasisExtender &be = *k->ev->be;
+    Ctx &c = *be.ctx;
+    TRY(rlwe_frame_begin(c, who));
+    TRY(evk_same_shape(who, *r1, *k, "round1", "rlk"));
+    TRY(evk_same_shape(who, *r2, *k, "round2", "rlk"));
+    if (k->nQk + k->nPk > kMaxLimbs) return fail(HE_EINVAL, "%s: %d limbs per row, at most %d", who, k->nQk + k->nPk, kMaxLimbs);
+    Scope sc(&c);
+    EvkRowsArgs ra;
+    evk_rows_args(*k, ra);
+    GadgetAggArgs g;
+    g.a = r2->d; g.b = r1->d; g.out = k->d;
+    g.blk = ra.blk; g.N = ra.N; g.rows = ra.rows; g.ncomp = 2; g.nl = ra.nq + ra.np; g.mc = ra.mc;
+    std::memcpy(g.mod, ra.mod, sizeof g.mod);
+    HIP_TRY(launch_rlk_finalize(g, c.stream));  // the two MForms (:272-273)
+    k->word_mul = 1;
+    TRY(evk_derive(*k));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return HE_OK;
+}
+
+// PublicKeyGenProtocol.GenShare (multiparty/keygen_cpk.go:62-75) and KeySwitchProtocol.GenShare (keyswitch_sk.go:82-118): polynomial-sized,
+// compositions of the ring and sampler entries.
+int he_mp_pk_gen_share(he_handle hk, he_handle skQ, he_handle skP, he_handle crpQ, he_handle crpP, he_handle shareQ, he_handle shareP) {
+    static const char *who = "he_mp_pk_gen_share";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    const int levelQ = kg->maxQ(), levelP = kg->maxP();  // params.RingQP(): the top levels
+    const he_handle hs[6] = {skQ, crpQ, shareQ, skP, crpP, shareP};
+    const char *const names[6] = {"skQ", "crpQ", "shareQ", "skP", "crpP", "shareP"};
+    for (int i = 0; i < (levelP >= 0 ? 6 : 3); i++) TRY(keygen_poly(*kg, who, hs[i], (i < 3 ? levelQ : levelP) + 1, names[i], nullptr));
+    const he_handle outs[2] = {shareQ, levelP >= 0 ? shareP : 0}, others[4] = {skQ, crpQ, levelP >= 0 ? skP : 0, levelP >= 0 ? crpP : 0};
+    TRY(rlwe_distinct(who, outs, 2, others, 4));
+    int rc = he_sampler_gaussian_read(kg->hq, levelQ, kg->prng, kg->sigma, kg->bound, 0, 0, shareQ);  // :65
+    if (rc == HE_OK && levelP >= 0) rc = he_centered_lift(kg->hev, 3, shareQ, levelQ + 1, levelQ, shareQ, levelP, shareP);  // :67-69
+    if (rc == HE_OK) rc = he_ntt(kg->hq, levelQ, shareQ, shareQ);  // :71
+    if (rc == HE_OK && levelP >= 0) rc = he_ntt(kg->hp, levelP, shareP, shareP);
+    if (rc == HE_OK) rc = he_mform(kg->hq, levelQ, shareQ, shareQ);  // :72
+    if (rc == HE_OK && levelP >= 0) rc = he_mform(kg->hp, levelP, shareP, shareP);
+    if (rc == HE_OK) rc = he_binop(kg->hq, levelQ, HE_MUL_COEFFS_MONTGOMERY_THEN_SUB, skQ, crpQ, shareQ);  // :74
+    if (rc == HE_OK && levelP >= 0) rc = he_binop(kg->hp, levelP, HE_MUL_COEFFS_MONTGOMERY_THEN_SUB, skP, crpP, shareP);
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+int he_mp_cks_gen_share(he_handle hk, int level, he_handle skInQ, he_handle skOutQ, he_handle c1, int is_ntt, double sigma, double bound,
+                        he_handle share) {
+    static const char *who = "he_mp_cks_gen_share";
+    GET(kg, KeyGen, hk, T_KEYGEN);
+    TRY(rlwe_frame_begin(kg->ctx(), who));
+    if (level < 0 || level > kg->maxQ()) return fail(HE_EINVAL, "%s: level %d, the ring has levels 0..%d", who, level, kg->maxQ());
+    if (!(sigma > 0.0) || sigma > 0x1p53 || !(bound >= 0.0) || bound > 0x1p62)
+        return fail(HE_EINVAL, "%s: noise = {%g, %g}: sigma in (0, 2^53] and bound in [0, 2^62] (hering_sampler.h)", who, sigma, bound);
+    const he_handle ins[3] = {skInQ, skOutQ, c1};
+    const char *const names[3] = {"skInQ", "skOutQ", "c1"};
+    for (int i = 0; i < 3; i++) TRY(keygen_poly(*kg, who, ins[i], level + 1, names[i], nullptr));
+    TRY(keygen_poly(*kg, who, share, level + 1, "share", nullptr));
+    TRY(rlwe_distinct(who, &share, 1, ins, 3));
+    TmpPoly delta, buf;  // sk_in - sk_out and the Gaussian: cleared before they go back to the pool
+    TRY(delta.alloc(kg->hq, level + 1, 1));
+    TRY(buf.alloc(kg->hq, level + 1, 1));
+    int rc = he_sub(kg->hq, level, skInQ, skOutQ, delta.h);  // :92
+    if (rc == HE_OK && !is_ntt) rc = he_ntt_lazy(kg->hq, level, c1, buf.h);  // :95-97
+    if (rc == HE_OK) rc = he_mul_coeffs_montgomery_lazy(kg->hq, level, is_ntt ? c1 : buf.h, delta.h, share);  // :103
+    if (rc == HE_OK && !is_ntt) {  // :105-108
+        rc = he_intt_lazy(kg->hq, level, share, share);
+        if (rc == HE_OK) rc = he_sampler_gaussian_read(kg->hq, level, kg->prng, sigma, bound, 0, 1, share);
+    } else if (rc == HE_OK) {      // :110-114
+        rc = he_sampler_gaussian_read(kg->hq, level, kg->prng, sigma, bound, 0, 0, buf.h);
+        if (rc == HE_OK) rc = he_ntt(kg->hq, level, buf.h, buf.h);
+        if (rc == HE_OK) rc = he_add(kg->hq, level, share, buf.h, share);
+    }
+    const int rs = rlwe_frame_end(kg->ctx());
+    return rc != HE_OK ? rc : rs;
+}
+// PublicKeySwitchProtocol.GenShare (multiparty/keyswitch_pk.go:69-105): EncryptZero under the encryptor's public key, from the
+// encryptor's own source, then the c1 s term and a Gaussian from the protocol's noise source.
+int he_mp_pcks_gen_share(he_handle henc, he_handle hnoise, int level, he_handle skQ, he_handle c1, int is_ntt, int is_montgomery, double sigma,
+                         double bound, he_handle share0, he_handle share1) {
+    static const char *who = "he_mp_pcks_gen_share";
+    GET(enc, Encryptor, henc, T_ENCRYPTOR);
+    GET(g, Prng, hnoise, T_PRNG);
+    TRY(rlwe_frame_begin(enc->ctx(), who));
+    if (level < 0 || level > enc->maxQ()) return fail(HE_EINVAL, "%s: level %d, the ring has levels 0..%d", who, level, enc->maxQ());
+    if (!(sigma > 0.0) || sigma > 0x1p53 || !(bound >= 0.0) || bound > 0x1p62)
+        return fail(HE_EINVAL, "%s: noise = {%g, %g}: sigma in (0, 2^53] and bound in [0, 2^62] (hering_sampler.h)", who, sigma, bound);
+    {
+        std::lock_guard<std::mutex> lk(enc->mu);
+        if (enc->kind != 2) return fail(HE_EINVAL, "%s: the encryptor is not bound to a public key (he_encryptor_set_key, kind 2)", who);
+    }
+    const he_handle hs[4] = {skQ, c1, share0, share1};
+    const char *const names[4] = {"skQ", "c1", "share0", "share1"};
+    for (int i = 0; i < 4; i++) {  // (a share above the ciphertext's level: HE_EINVAL, where the reference encrypts at one level and adds at another)
+        auto p = get<Poly>(hs[i], T_POLY);
+        if (!p) return fail(HE_EHANDLE, "%s: bad Poly handle for %s", who, names[i]);
+        if (p->ctx.get() != &enc->ctx() || p->N != enc->ev->be->Q->N || p->batch != 1 || p->nlimbs < level + 1)
+            return fail(HE_EINVAL, "%s: %s must be one polynomial of the encryptor's ringQ with %d limbs", who, names[i], level + 1);
+    }
+    const he_handle outs[2] = {share0, share1}, ins[2] = {skQ, c1};
+    TRY(rlwe_distinct(who, outs, 2, ins, 2));
+    TmpPoly buf;  // c1 s and the noise: cleared before it goes back to the pool
+    TRY(buf.alloc(enc->hq, level + 1, 1));
+    int rc = he_encrypt_zero(henc, level, is_ntt, is_montgomery, share0, share1);  // :77-88
+    if (rc == HE_OK && is_ntt) {  // :93-97
+        rc = he_mul_coeffs_montgomery_then_add(enc->hq, level, c1, skQ, share0);
+        if (rc == HE_OK) rc = he_sampler_gaussian_read(enc->hq, level, hnoise, sigma, bound, 0, 0, buf.h);
+        if (rc == HE_OK) rc = he_ntt(enc->hq, level, buf.h, buf.h);
+    } else if (rc == HE_OK) {     // :98-103
+        rc = he_ntt_lazy(enc->hq, level, c1, buf.h);
+        if (rc == HE_OK) rc = he_mul_coeffs_montgomery_lazy(enc->hq, level, buf.h, skQ, buf.h);
+        if (rc == HE_OK) rc = he_intt(enc->hq, level, buf.h, buf.h);
+        if (rc == HE_OK) rc = he_sampler_gaussian_read(enc->hq, level, hnoise, sigma, bound, 0, 1, buf.h);
+    }
+    if (rc == HE_OK) rc = he_add(enc->hq, level, share0, buf.h, share0);
+    const int rs = rlwe_frame_end(enc->ctx());
     return rc != HE_OK ? rc : rs;
 }
 

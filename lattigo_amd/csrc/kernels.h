@@ -534,6 +534,7 @@ hipError_t launch_sampler_expand(const ModConst *mc, const uint64_t *vals, bool 
 // row's own digit and 0 elsewhere (the factor is never 0 modulo a prime q_y); null: no gadget term.  No entry tables.
 struct EvkRowsArgs {
     uint64_t *key = nullptr;
+    const uint64_t *c1 = nullptr;  // launch_evk_finish: where component 1 is read, laid out as key (key itself, or the CRP of a share)
     size_t blk = 0;
     int N = 0, rows = 0, nq = 0, np = 0;
     const ModConst *mc = nullptr;
@@ -544,10 +545,47 @@ struct EvkRowsArgs {
     int comp = 0;                                         // launch_gadget_add: the component that receives the term
 };
 // encryptZeroSkFromC1QP (encryptor.go:420-425) and the gadget term over every row, in place: component 0 holds NTT(e), canonical,
-// component 1 the uniform c1;  c0 = CRed(MForm(c0) + q - MRed(c1, skOut)) [then CRed(c0 + MRed(pt, G))].  One launch.
+// component 1 of c1 the uniform c1;  c0 = CRed(MForm(c0) + q - MRed(c1, skOut)) [then CRed(c0 + MRed(pt, G))].  One launch.
 hipError_t launch_evk_finish(const EvkRowsArgs &a, hipStream_t s);
 // the gadget term alone: key[r][comp] = CRed(key[r][comp] + MRed(pt, G[r][y])) on the Q limbs where G is not 0
 hipError_t launch_gadget_add(const EvkRowsArgs &a, hipStream_t s);
+
+// ---- multiparty shares (multiparty/keygen_evk.go:186-215, keygen_relin.go:237-254; include/hering_multiparty.h) ----------------
+// out[r][c] = CRed(a[r][c] + b[r][c]) for the components c < ncomp of every row of three keys of one shape (EvkRowsArgs's layout):
+// ring.Add's single conditional subtraction, so words in [q, 2q) of lazy shares come out as the reference's.  out may be a or b.
+struct GadgetAggArgs {
+    const uint64_t *a = nullptr, *b = nullptr;
+    uint64_t *out = nullptr;
+    size_t blk = 0;
+    int N = 0, rows = 0, ncomp = 1, nl = 0;
+    const ModConst *mc = nullptr;
+    uint8_t mod[kMaxLimbs];
+};
+hipError_t launch_gadget_aggregate(const GadgetAggArgs &a, hipStream_t s);
+// GenRelinearizationKey (keygen_relin.go:261-276): out[r][0] = MForm(a[r][0]) (the aggregated round-two share, words in [0, 2q)),
+// out[r][1] = MForm(b[r][1]) (the aggregated round-one share).  out may be a or b.  ncomp is not read.
+hipError_t launch_rlk_finalize(const GadgetAggArgs &a, hipStream_t s);
+
+// The two rounds of RelinearizationKeyGenProtocol after their draws (keygen_relin.go:133-183, :211-233), over every row at once, in
+// place on the share: grid and layout as EvkRowsArgs.  sk = (skQ, skP) and the ephemeral key u = (uQ, uP): nq / np limbs, NTT and
+// Montgomery.
+//   round one: share[r][0], share[r][1] hold NTT(e0), NTT(e1), canonical; in: the CRP a in component 1.  G: [rows][nq], P 2^(j pw2)
+//              mod q_y -- NOT in Montgomery form -- on the Q limbs of the row's own digit, 0 elsewhere, so that MRed(sk, G) is
+//              IMForm(P sk) 2^(j pw2).    share[r][0] = CRed(CRed(e0 + MRed(sk, G)) + q - MRed(u, a));  share[r][1] = CRed(e1 + MRed(sk, a))
+//   round two: share[r][0] holds NTT(e), canonical; in: the aggregated round-one share (h0, h1), canonical.  The reference's lazy word
+//              sequence:                share[r][0] = CRed(CRed(MRedLazy(h0, sk) + e) + MRed(CRed(u + q - sk), h1)), in [0, 2q)
+struct RkgRowsArgs {
+    uint64_t *share = nullptr;
+    const uint64_t *in = nullptr;
+    size_t blk = 0;
+    int N = 0, rows = 0, nq = 0, np = 0;
+    const ModConst *mc = nullptr;
+    uint8_t mod[kMaxLimbs];
+    const uint64_t *skQ = nullptr, *skP = nullptr, *uQ = nullptr, *uP = nullptr;
+    const uint64_t *G = nullptr;  // round one
+};
+hipError_t launch_rkg_round_one(const RkgRowsArgs &a, hipStream_t s);
+hipError_t launch_rkg_round_two(const RkgRowsArgs &a, hipStream_t s);
 
 // ---- RGSW encryption (core/rgsw/encryptor.go; include/hering_rgsw_encryptor.h) ---------------------------------------------------
 // A table of nkeys RGSW ciphertexts, each two separately allocated keys of the shape above: gadget ciphertext u of ciphertext k
@@ -633,7 +671,7 @@ enum KernelId {
     K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64,
     K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
     K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND,
-    K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_COUNT
+    K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_GADGET_AGGREGATE, K_RKG_ROUND_ONE, K_RKG_ROUND_TWO, K_RLK_FINALIZE, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -78,7 +78,8 @@ const char *kernel_name(int id) {
                                          "special_ifft_quantize", "f64_to_rns", "rns_to_f64", "bgv_slots_to_t", "bgv_t_to_slots",
                                          "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
                                          "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add",
-                                         "rgsw_table_finish"};
+                                         "rgsw_table_finish", "gadget_aggregate", "rkg_round_one", "rkg_round_two",
+                                         "rlk_finalize"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -5886,7 +5887,7 @@ __global__ void __launch_bounds__(256) evk_rows_kernel(EvkRowsArgs A) {
     uint64_t *c0 = A.key + ((size_t)2 * r + (FINISH ? 0 : A.comp)) * A.blk + off;
     ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(c0);
     if (FINISH) {
-        const ulonglong2 c1 = ldnt2(A.key + ((size_t)2 * r + 1) * A.blk + off);
+        const ulonglong2 c1 = ldnt2(A.c1 + ((size_t)2 * r + 1) * A.blk + off);
         const uint64_t *skp = isq ? A.skOutQ + off : A.skOutP + (size_t)(y - A.nq) * A.N + j;
         const ulonglong2 sk = *reinterpret_cast<const ulonglong2 *>(skp);
         v.x = cred(mform(v.x, q, m.brc0, m.brc1) + (q - mred(c1.x, sk.x, q, qinv)), q);
@@ -5904,7 +5905,7 @@ static bool evk_rows_ok(const EvkRowsArgs &a) {
            a.nq + a.np <= kMaxLimbs && a.blk >= (size_t)(a.nq + a.np) * a.N && (a.G == nullptr || a.pt != nullptr);
 }
 hipError_t launch_evk_finish(const EvkRowsArgs &a, hipStream_t s) {
-    if (!evk_rows_ok(a) || !a.skOutQ || (a.np > 0 && !a.skOutP)) return hipErrorInvalidValue;
+    if (!evk_rows_ok(a) || !a.c1 || !a.skOutQ || (a.np > 0 && !a.skOutP)) return hipErrorInvalidValue;
     ProfScope ps(K_EVK_FINISH, s, 3.0 * (a.nq + a.np) * (double)a.N * a.rows * 8.0);
     hipLaunchKernelGGL((evk_rows_kernel<true>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq + a.np, a.rows), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -5913,6 +5914,110 @@ hipError_t launch_gadget_add(const EvkRowsArgs &a, hipStream_t s) {
     if (!evk_rows_ok(a) || !a.G || a.comp < 0 || a.comp > 1) return hipErrorInvalidValue;
     ProfScope ps(K_GADGET_ADD, s, 2.0 * a.nq * (double)a.N * 8.0);  // (each Q limb belongs to the digit of one row per window)
     hipLaunchKernelGGL((evk_rows_kernel<false>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq, a.rows), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// multiparty shares (include/hering_multiparty.h): AggregateShares over the whole key storage.  Grid (coefficient pairs, limb,
+// row x component), as evk_rows_kernel: the modulus is uniform per block, 16-byte accesses; two reads and one write per word.
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) gadget_aggregate_kernel(GadgetAggArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, r = blockIdx.z / A.ncomp, c = blockIdx.z % A.ncomp;
+    const uint64_t q = A.mc[A.mod[y]].q;
+    const size_t off = ((size_t)2 * r + c) * A.blk + (size_t)y * A.N + j;
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(A.a + off), b = *reinterpret_cast<const ulonglong2 *>(A.b + off);
+    ulonglong2 v;
+    v.x = cred(a.x + b.x, q);
+    v.y = cred(a.y + b.y, q);
+    *reinterpret_cast<ulonglong2 *>(A.out + off) = v;
+}
+hipError_t launch_gadget_aggregate(const GadgetAggArgs &a, hipStream_t s) {
+    if (!a.a || !a.b || !a.out || !a.mc || a.N < 8 || a.N > (1 << kMaxLogN) || (a.N & (a.N - 1)) != 0 || a.rows <= 0 || a.ncomp < 1 || a.ncomp > 2 ||
+        (long)a.rows * a.ncomp > 65535 || a.nl <= 0 || a.nl > kMaxLimbs || a.blk < (size_t)a.nl * a.N)
+        return hipErrorInvalidValue;
+    ProfScope ps(K_GADGET_AGGREGATE, s, 3.0 * a.nl * (double)a.N * a.rows * a.ncomp * 8.0);
+    hipLaunchKernelGGL(gadget_aggregate_kernel, dim3((unsigned)((a.N / 2 + 255) / 256), a.nl, a.rows * a.ncomp), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+// GenRelinearizationKey: grid (coefficient pairs, limb, row x 2); component 0 from a, component 1 from b
+__global__ void __launch_bounds__(256) rlk_finalize_kernel(GadgetAggArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, r = blockIdx.z >> 1, c = blockIdx.z & 1;
+    const ModConst m = A.mc[A.mod[y]];
+    const size_t off = ((size_t)2 * r + c) * A.blk + (size_t)y * A.N + j;
+    ulonglong2 v = ldnt2((c ? A.b : A.a) + off);
+    v.x = mform(v.x, m.q, m.brc0, m.brc1);
+    v.y = mform(v.y, m.q, m.brc0, m.brc1);
+    *reinterpret_cast<ulonglong2 *>(A.out + off) = v;
+}
+hipError_t launch_rlk_finalize(const GadgetAggArgs &a, hipStream_t s) {
+    if (!a.a || !a.b || !a.out || !a.mc || a.N < 8 || a.N > (1 << kMaxLogN) || (a.N & (a.N - 1)) != 0 || a.rows <= 0 || (long)a.rows * 2 > 65535 ||
+        a.nl <= 0 || a.nl > kMaxLimbs || a.blk < (size_t)a.nl * a.N)
+        return hipErrorInvalidValue;
+    ProfScope ps(K_RLK_FINALIZE, s, 2.0 * a.nl * (double)a.N * a.rows * 2 * 8.0);
+    hipLaunchKernelGGL(rlk_finalize_kernel, dim3((unsigned)((a.N / 2 + 255) / 256), a.nl, a.rows * 2), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// RelinearizationKeyGenProtocol (include/hering_multiparty.h): the arithmetic of a round after its draws, over every row of the share
+// at once, in the grid of evk_rows_kernel -- (coefficient pairs, limb, row), the modulus record, the row's factor and "is this limb
+// in the row's digit" uniform per block, 16-byte accesses.  Memory-bound: round one reads three key-sized streams (e0, e1, the CRP)
+// and writes two; round two reads three (e, h0, h1) and writes one; the key limbs are re-read by every row and stay in L2.
+// ------------------------------------------------------------------------------------
+template <int ROUND>
+__global__ void __launch_bounds__(256) rkg_rows_kernel(RkgRowsArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int y = blockIdx.y, r = blockIdx.z;
+    const bool isq = y < A.nq;
+    const ModConst m = A.mc[A.mod[y]];
+    const uint64_t q = m.q, qinv = m.qinv;
+    const size_t off = (size_t)y * A.N + j, koff = isq ? off : (size_t)(y - A.nq) * A.N + j;
+    const ulonglong2 sk = *reinterpret_cast<const ulonglong2 *>((isq ? A.skQ : A.skP) + koff);
+    const ulonglong2 u = *reinterpret_cast<const ulonglong2 *>((isq ? A.uQ : A.uP) + koff);
+    uint64_t *c0p = A.share + (size_t)2 * r * A.blk + off;
+    ulonglong2 v0 = *reinterpret_cast<const ulonglong2 *>(c0p);
+    if (ROUND == 1) {
+        const uint64_t g = isq ? A.G[(size_t)r * A.nq + y] : 0;
+        const ulonglong2 a = ldnt2(A.in + ((size_t)2 * r + 1) * A.blk + off);
+        ulonglong2 v1 = *reinterpret_cast<const ulonglong2 *>(c0p + A.blk);
+        if (g != 0) {  // h = sk CrtBaseDecompQi + e (:147-163)
+            v0.x = cred(v0.x + mred(sk.x, g, q, qinv), q);
+            v0.y = cred(v0.y + mred(sk.y, g, q, qinv), q);
+        }
+        v0.x = cred(v0.x + (q - mred(u.x, a.x, q, qinv)), q);  // MulCoeffsMontgomeryThenSub (:166)
+        v0.y = cred(v0.y + (q - mred(u.y, a.y, q, qinv)), q);
+        v1.x = cred(v1.x + mred(sk.x, a.x, q, qinv), q);       // MulCoeffsMontgomeryThenAdd (:178)
+        v1.y = cred(v1.y + mred(sk.y, a.y, q, qinv), q);
+        *reinterpret_cast<ulonglong2 *>(c0p + A.blk) = v1;
+    } else {
+        const ulonglong2 h0 = ldnt2(A.in + (size_t)2 * r * A.blk + off), h1 = ldnt2(A.in + ((size_t)2 * r + 1) * A.blk + off);
+        const uint64_t dx = cred(u.x + q - sk.x, q), dy = cred(u.y + q - sk.y, q);  // u - s (:205)
+        v0.x = cred(mred_lazy(h0.x, sk.x, q, qinv) + v0.x, q);  // MulCoeffsMontgomeryLazy, then Add (:217, :227)
+        v0.y = cred(mred_lazy(h0.y, sk.y, q, qinv) + v0.y, q);
+        v0.x = cred(v0.x + mred(dx, h1.x, q, qinv), q);         // MulCoeffsMontgomeryThenAdd (:231)
+        v0.y = cred(v0.y + mred(dy, h1.y, q, qinv), q);
+    }
+    *reinterpret_cast<ulonglong2 *>(c0p) = v0;
+}
+static bool rkg_rows_ok(const RkgRowsArgs &a) {
+    return a.share && a.in && a.share != a.in && a.mc && a.N >= 8 && a.N <= (1 << kMaxLogN) && (a.N & (a.N - 1)) == 0 && a.rows > 0 && a.rows <= 65535 &&
+           a.nq > 0 && a.np >= 0 && a.nq + a.np <= kMaxLimbs && a.blk >= (size_t)(a.nq + a.np) * a.N && a.skQ && a.uQ && (a.np == 0 || (a.skP && a.uP));
+}
+hipError_t launch_rkg_round_one(const RkgRowsArgs &a, hipStream_t s) {
+    if (!rkg_rows_ok(a) || !a.G) return hipErrorInvalidValue;
+    ProfScope ps(K_RKG_ROUND_ONE, s, 5.0 * (a.nq + a.np) * (double)a.N * a.rows * 8.0);
+    hipLaunchKernelGGL((rkg_rows_kernel<1>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq + a.np, a.rows), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_rkg_round_two(const RkgRowsArgs &a, hipStream_t s) {
+    if (!rkg_rows_ok(a)) return hipErrorInvalidValue;
+    ProfScope ps(K_RKG_ROUND_TWO, s, 4.0 * (a.nq + a.np) * (double)a.N * a.rows * 8.0);
+    hipLaunchKernelGGL((rkg_rows_kernel<2>), dim3((unsigned)((a.N / 2 + 255) / 256), a.nq + a.np, a.rows), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
