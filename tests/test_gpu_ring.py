@@ -9,10 +9,11 @@ import pytest
 
 import lattigo_amd as la
 from oracle import oracle as O
-from tests.boundary import CANONICAL_KINDS, class_chain, word_row
+from tests.boundary import class_chain
 from tests.conftest import Pi60, Qi60
 from tests.gpu_common import Pair, ctx  # noqa: F401
 from tests.helpers import rng_for, uniform_poly
+from tests.ntt_edges import extreme_polys, rescale_descent
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "ntt_kat.json")
@@ -276,33 +277,8 @@ def test_rescale_two_pass_rings_at_the_class_boundaries(ctx, logN, letters):
     qs = class_chain(logN, letters)
     pr = Pair(ctx, logN, len(qs), qmods=qs)
     rng = rng_for(1320 + logN)
-    B, top = 2, len(qs) - 1
-    polys = [np.stack([word_row(kind, rng, m, pr.N) for m in qs]) for kind in CANONICAL_KINDS]
-    polys += [pr.oQ.NTT(polys[0]), pr.oQ.NTT(polys[1])]
-    for c0 in range(0, len(polys), B):
-        xs = np.stack(polys[c0 : c0 + B])
-        for name in ("DivRoundByLastModulusNTT", "DivFloorByLastModulusNTT"):
-            cur = xs.copy()
-            pin = pr.up(pr.gQ, cur, batch=B)
-            many = name.replace("NTT", "ManyNTT")
-            want = np.stack([getattr(pr.oQ, many)(2, cur[b]) for b in range(B)])
-            po = la.Poly(pr.gQ, len(qs), B)
-            getattr(pr.gQ, many)(2, pin, po)
-            assert np.array_equal(po.get()[:, : top - 1], want), (many, c0)
-            for level in range(top, 0, -1):
-                sub = O.Ring(pr.N, pr.q[: level + 1])
-                want = np.stack([getattr(sub, name)(cur[b, : level + 1]) for b in range(B)])
-                po = la.Poly(pr.gQ, len(qs), B)
-                getattr(pr.gQ.AtLevel(level), name)(pin, po)
-                assert np.array_equal(po.get()[:, :level], want), (name, c0, level, "out of place")
-                getattr(pr.gQ.AtLevel(level), name)(pin, pin)
-                assert np.array_equal(pin.get()[:, :level], want), (name, c0, level, "in place")
-                cur = np.concatenate([want, cur[:, level:]], axis=1)
-                # and the extreme words themselves at this level (the descent above hands its own outputs down)
-                want = np.stack([getattr(sub, name)(xs[b, : level + 1]) for b in range(B)])
-                pfresh = pr.up(pr.gQ, xs, batch=B)
-                getattr(pr.gQ.AtLevel(level), name)(pfresh, pfresh)
-                assert np.array_equal(pfresh.get()[:, :level], want), (name, c0, level, "extreme words, in place")
+    polys = extreme_polys(pr.oQ, rng, qs, pr.N)
+    rescale_descent(pr, polys, 2)  # (the descent itself: tests/ntt_edges.py, shared with the single-pass rings)
 
 
 def test_automorphism(ctx):
