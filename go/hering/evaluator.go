@@ -622,11 +622,9 @@ func (e *Evaluator) AutomorphismHoistedLazy(levelQ int, ctIn *rlwe.Ciphertext, c
 // lintrans.Evaluator.MultiplyByDiagMatrixBSGS (circuits/common/lintrans/lintrans_evaluator.go) -- GadgetProductLazy(levelQ, cx, gk, cQP);
 // ringQP.Add(cQP.Value[0], add, cQP.Value[0]); ringQP.AutomorphismNTTWithIndex[ThenAddLazy](cQP.Value[k], index, outQP[k]) -- by one
 // native call whose key inner products store through the automorphism into the outer accumulators (he_lintrans_giant_step; word for
-// word what the separate calls produce).  A maintainer who wants it patches that loop body to
-//
-//	if dev, ok := eval.EvaluatorProvider.(*hering.Evaluator); ok {
-//		err = dev.LinTransGiantStep(levelQ, tmp1QP.Q, galEl, tmp0QP, c0OutQP, c1OutQP, cnt0 != 0)
-//	} else { ... the reference's own calls ... }
+// word what the separate calls produce).  It is a piece: the whole product -- EvaluateMany with both of its forms -- is ONE native
+// call, LinTransEvaluator.EvaluateMany (lintrans.go, he_lintrans_evaluate_many), which runs nothing of the reference's loop on the
+// host and is what a caller of lintrans.Evaluator should use.
 //
 // Staleness: as AutomorphismHoistedLazy (inputs from their device twins, outputs on the device only).  out0 / out1 must alias
 // neither cx nor add nor each other (Q or P part): the call returns an error before anything runs (hering.h, Conventions).

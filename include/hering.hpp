@@ -15,6 +15,7 @@
 #ifndef HERING_HPP
 #define HERING_HPP
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -41,6 +42,7 @@
 #include "hering_keygen.h"
 #include "hering_rgsw_encryptor.h"
 #include "hering_multiparty.h"
+#include "hering_lintrans.h"
 
 namespace hering {
 
@@ -1707,6 +1709,93 @@ public:
     }
 };
 }  // namespace blindrot
+
+// ---- linear transformations (circuits/common/lintrans; hering_lintrans.h), NTT domain ----------------------------------------
+namespace lintrans {
+// BSGSIndex (lintrans.go:344): the sorted giant steps and baby steps
+inline std::pair<std::vector<int>, std::vector<int>> BSGSIndex(const std::vector<int> &nonZeroDiags, int slots, int N1) {
+    std::vector<int> r1(nonZeroDiags.size() + 1), r2(nonZeroDiags.size() + 1);
+    int n1 = 0, n2 = 0;
+    check(he_lintrans_bsgs_index(nonZeroDiags.data(), (int)nonZeroDiags.size(), slots, N1, r1.data(), &n1, r2.data(), &n2, nullptr));
+    r1.resize((size_t)n1); r2.resize((size_t)n2);
+    return {r1, r2};
+}
+// FindBestBSGSRatio (lintrans.go:321)
+inline int FindBestBSGSRatio(const std::vector<int> &nonZeroDiags, int maxN, int logMaxRatio) {
+    int N1 = 0;
+    check(he_lintrans_find_best_bsgs_ratio(nonZeroDiags.data(), (int)nonZeroDiags.size(), maxN, logMaxRatio, &N1));
+    return N1;
+}
+// GaloisElements (lintrans.go:297) on the evaluator's ring
+inline std::vector<uint64_t> GaloisElements(const hering::Evaluator &ev, const std::vector<int> &diags, int slots, int logBSGSRatio) {
+    std::vector<uint64_t> out(2 * diags.size() + 2);
+    size_t n = 0;
+    check(he_lintrans_galois_elements(ev.h(), diags.data(), (int)diags.size(), slots, logBSGSRatio, out.data(), out.size(), &n));
+    out.resize(n);
+    return out;
+}
+// LinearTransformation (lintrans.go:127) over encoded diagonals (NTT + Montgomery) the caller keeps as polynomials: diag[k] is the
+// index of (Q[k], P[k]).  The handle keeps them alive and reads their words when the transformation is evaluated.
+class LinearTransformation {
+    detail::Ref r_;
+    std::vector<Poly> q_, p_;
+
+public:
+    int LevelQ, LevelP, LogSlots, N1;
+    LinearTransformation(const hering::Evaluator &ev, int levelQ, int levelP, int logSlots, int n1, const std::vector<int> &diag,
+                         const std::vector<Poly> &Q, const std::vector<Poly> &P)
+        : q_(Q), p_(P), LevelQ(levelQ), LevelP(levelP), LogSlots(logSlots), N1(n1) {
+        if (diag.size() != Q.size() || diag.size() != P.size()) throw std::invalid_argument("LinearTransformation: one (Q, P) pair per diagonal");
+        std::vector<he_handle> hq, hp;
+        for (const Poly &x : Q) hq.push_back(x.h());
+        for (const Poly &x : P) hp.push_back(x.h());
+        he_handle h = 0;
+        check(he_lintrans_create(ev.h(), levelQ, levelP, logSlots, n1, (int)diag.size(), diag.data(), hq.data(), hp.data(), &h));
+        r_ = detail::own(h, he_lintrans_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    // giant steps per launch of the grouped kernel: 0 (the library's default), 1, 2 or 4
+    void SetGroup(int G) const { check(he_lintrans_set_group(r_->h, G)); }
+};
+// lintrans.Evaluator (lintrans_evaluator.go:12): EvaluateMany is ONE native call
+class Evaluator {
+    hering::Evaluator ev_;
+    blindrot::GaloisKeySet gks_;
+
+public:
+    Evaluator(const hering::Evaluator &ev, const blindrot::GaloisKeySet &gks) : ev_(ev), gks_(gks) {}
+    // :27: ctIn at ctLevel; opOut[k] = linearTransformations[k] x ctIn
+    void EvaluateMany(int ctLevel, const Ciphertext &ctIn, const std::vector<LinearTransformation> &linearTransformations,
+                      std::vector<Ciphertext> &opOut) const {
+        if (opOut.size() < linearTransformations.size()) throw std::invalid_argument("output *rlwe.Ciphertext slice is too small");
+        std::vector<he_handle> lts, o0, o1;
+        for (size_t k = 0; k < linearTransformations.size(); k++) {
+            lts.push_back(linearTransformations[k].h());
+            o0.push_back(opOut[k].Value.at(0).h());
+            o1.push_back(opOut[k].Value.at(1).h());
+        }
+        check(he_lintrans_evaluate_many(ev_.h(), gks_.h(), ctLevel, ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), (int)lts.size(), lts.data(),
+                                        o0.data(), o1.data()));
+    }
+    // :122
+    void Evaluate(int ctLevel, const Ciphertext &ctIn, const LinearTransformation &lt, Ciphertext &opOut) const {
+        check(he_lintrans_evaluate(ev_.h(), gks_.h(), ctLevel, ctIn.Value.at(0).h(), ctIn.Value.at(1).h(), lt.h(), opOut.Value.at(0).h(),
+                                   opOut.Value.at(1).h()));
+    }
+    // :128: each transformation on the result of the one before; opOut receives the last result (the caller rescales between two
+    // of them where the scheme wants it: pass one transformation at a time then)
+    void EvaluateSequential(int ctLevel, const Ciphertext &ctIn, const std::vector<LinearTransformation> &linearTransformations,
+                            Ciphertext &opOut) const {
+        if (linearTransformations.empty()) return;
+        Evaluate(ctLevel, ctIn, linearTransformations[0], opOut);
+        int level = std::min(ctLevel, linearTransformations[0].LevelQ);
+        for (size_t k = 1; k < linearTransformations.size(); k++) {  // in place: n_lt = 1 takes the outputs on the inputs
+            Evaluate(level, opOut, linearTransformations[k], opOut);
+            level = std::min(level, linearTransformations[k].LevelQ);
+        }
+    }
+};
+}  // namespace lintrans
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

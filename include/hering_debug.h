@@ -124,6 +124,15 @@ int he_debug_blindrot_schedule(int logN, const uint64_t *a, int n_lwe, uint64_t 
  * number of rounds; at most cap rounds are written. */
 int he_debug_blindrot_rounds(int logN, const uint64_t *a, int batch, int n_lwe, int64_t *rounds, size_t cap, size_t *n_rounds);
 
+/* The plan he_lintrans_evaluate_many (hering_lintrans.h) follows for one transformation, computed on the host
+ * (csrc/lintrans_plan.h; no device needed): n REDUCED, distinct diagonal indices over `slots`, baby-step count N1 (0: the naive
+ * form), G giant steps per launch of the grouped kernel (1 .. 4), NthRoot of the ring.  Words: n_groups, n_galois; naive form
+ * (n_groups = 0): the position of the zero diagonal or -1; per group: n_members, n_babies, the members (giant steps, ascending),
+ * the union of their baby steps (ascending), term[n_babies][n_members] = the position of diagonal j + i in diag[] or -1; then the
+ * Galois elements the call asks the key set for (BSGS: the non-zero baby steps, then the non-zero giant steps; naive: the non-zero
+ * rotations).  *n_words receives the length; at most cap words are written. */
+int he_debug_lintrans_plan(uint64_t nth_root, int slots, int N1, int G, int n, const int *diag, int64_t *out, size_t cap, size_t *n_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), o
          os.path.join(_INC, "hering_ringpack.h"), os.path.join(_INC, "hering_rgsw.h"), os.path.join(_INC, "hering_blindrot.h"),
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
          os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h"),
-         os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h"), os.path.join(_INC, "hering_multiparty.h")]
+         os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h"), os.path.join(_INC, "hering_multiparty.h"),
+         os.path.join(_INC, "hering_lintrans.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -60,6 +61,7 @@ def _declare(L):
     i, sz = C.c_int, C.c_size_t
     HP = C.POINTER(H)
     f64p = C.POINTER(C.c_double)
+    ip = C.POINTER(C.c_int)
     L.he_last_error.restype = C.c_char_p
     L.he_version.restype = C.c_char_p
     L.he_prof_kernel_name.restype = C.c_char_p
@@ -177,6 +179,11 @@ def _declare(L):
         "he_decomp_fill": [H, i, i, H, H],
         "he_lintrans_mul_sum": [H, i, i, i, HP, HP, HP, HP, HP, HP, HP, i, H, H, H, H],
         "he_lintrans_giant_step": [H, i, H, H, C.c_uint64, H, H, H, H, H, H, i],
+        "he_lintrans_bsgs_index": [ip, i, i, i, ip, ip, ip, ip, ip], "he_lintrans_find_best_bsgs_ratio": [ip, i, i, i, ip],
+        "he_lintrans_galois_elements": [H, ip, i, i, i, u64p, sz, C.POINTER(sz)],
+        "he_lintrans_create": [H, i, i, i, i, i, ip, HP, HP, HP], "he_lintrans_destroy": [H], "he_lintrans_set_group": [H, i],
+        "he_lintrans_evaluate_many": [H, H, i, H, H, i, HP, HP, HP], "he_lintrans_evaluate": [H, H, i, H, H, H, H, H],
+        "he_debug_lintrans_plan": [C.c_uint64, i, i, i, i, ip, C.POINTER(C.c_int64), sz, C.POINTER(sz)],
         "he_ckks_mul_relin": [H, i, H, H, H, H, H, H, H, H],
         "he_bgv_mul_relin": [H, i, C.c_uint64, H, H, H, H, H, H, H, H],
         "he_probe_modmul": [H, i, C.POINTER(C.c_double)], "he_probe_modmul_f64": [H, i, C.POINTER(C.c_double)],
@@ -254,6 +261,8 @@ _TRACE_FNS_BRIDGE = {"he_unfold_conjugate_invariant_to_standard": (67, "ihh"), "
                      "he_complex_to_real": (69, "hihhhhh"), "he_real_to_complex": (70, "hihhhhh")}
 # the product entries of include/hering_bfv.h, numbered on in a table of their own
 _TRACE_FNS_BFV = {"he_bfv_mul_relin": (71, "hihhhhhhhh"), "he_bfv_quantize": (72, "hihhh")}
+# the product entries of include/hering_lintrans.h, numbered on in a table of their own
+_TRACE_FNS_LINTRANS = {"he_lintrans_evaluate": (73, "hhihhhhh"), "he_lintrans_evaluate_many": (74, "hhihhiHHH")}
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments); a
 # tuple of indices: the product of those arguments
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
@@ -265,14 +274,24 @@ _TRACE_LEN.update({("he_ringpack_pack_post", k): (2, 0) for k in range(3, 7)})
 _TRACE_LEN[("he_rgsw_external_product_select", 4)] = (5, 0)
 _TRACE_LEN[("he_automorphism_ct_select", 4)] = (5, 0)
 _TRACE_LEN[("he_blind_rotate_core", 1)] = ((2, 3), 0)
+_TRACE_LEN.update({("he_lintrans_evaluate_many", k): (5, 0) for k in (6, 7, 8)})
 # calls a replay has no use for: they read, wait or account, and do not change what the replayed calls see
 _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start", "he_timer_stop", "he_poly_download", "he_poly_shape",
                  "he_poly_download_limb", "he_prof_begin", "he_prof_end", "he_prof_end_bytes", "he_ctx_coalescing_stats",
                  "he_evaluator_coalescing_stats", "he_version", "he_device_info", "he_ring_constant", "he_ring_roots", "he_decomp_download_limb",
                  # a Ring owns itself (Ring._owner), so an unreachable one is released by the cycle collector, whenever that runs:
                  # no later call of the recording can name it
-                 "he_ring_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds", "he_debug_arith",
+                 # ... and so may a Context nothing refers to any more: every object made on it holds it, so none of them is alive
+                 # either and no later call of the recording can name it (tests/test_gpu_bfv.py, test_gpu_bgv_encoder.py, test_gpu_bridge.py
+                 # and others make a second context `ctx2` in one test and drop it; a later test's recorded window then sees its release whenever
+                 # the collector gets to the rings' cycles)
+                 "he_ring_destroy", "he_ctx_destroy", "he_debug_blindrot_schedule", "he_debug_blindrot_rounds", "he_debug_arith",
                  "he_bfv_level_qmul",
+                 # include/hering_lintrans.h: the index entries run on the host; a transformation is shared by the replaying
+                 # threads like a key, so its creation fails trace_end and its release, which the collector may issue at any
+                 # time, is left out like a ring's
+                 "he_lintrans_bsgs_index", "he_lintrans_find_best_bsgs_ratio", "he_lintrans_galois_elements", "he_debug_lintrans_plan",
+                 "he_lintrans_destroy",
                  # include/hering_ckks_encoder.h: decode, the transforms and the getters read; an encode carries host data into a
                  # polynomial, as an upload does, and is left out on purpose (it fails trace_end)
                  "he_ckks_decode", "he_ckks_fft", "he_ckks_ifft", "he_ckks_roots_host", "he_ckks_encoder_roots", "he_ckks_encoder_info",
@@ -315,7 +334,7 @@ def trace_begin():
     import inspect  # noqa: F401
 
     def wrap(name, fn):
-        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name) or _TRACE_FNS_BFV.get(name)
+        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name) or _TRACE_FNS_BFV.get(name) or _TRACE_FNS_LINTRANS.get(name)
 
         def call(*a):
             rc = fn(*a)

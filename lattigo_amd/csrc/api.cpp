@@ -55,10 +55,12 @@
 #include "../../include/hering_ringpack.h"
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
+#include "../../include/hering_lintrans.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "ks_route.h"
 #include "blindrot_plan.h"
+#include "lintrans_plan.h"
 
 using namespace he;
 
@@ -85,7 +87,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR, T_KEYGEN };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR, T_KEYGEN, T_LINTRANS };
 
 struct Obj {
     ObjType type;
@@ -114,7 +116,7 @@ enum CoOp {
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
     CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT,
-    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE
+    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE, CO_LINTRANS_EVAL
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -378,6 +380,8 @@ struct Ctx : Obj {
     // reserve the total a call needs up front (growing invalidates earlier pointers)
     int arena_reserve(size_t words) {
         if (words <= arena_words) return HE_OK;
+        if (arena_frames > 0)  // (a composed call holds pointers into the arena below a step's frame: it reserved too little)
+            return fail(HE_EINVAL, "internal error: a step of a composed call needs %zu words of scratch, %zu are left", words, arena_words);
         if (capturing)
             return fail(HE_EINVAL, "graph capture: the scratch arena would have to grow (run the sequence once before capturing it)");
         HIP_TRY(hipStreamSynchronize(stream));
@@ -395,6 +399,20 @@ struct Ctx : Obj {
         arena_used += (words + 1) & ~(size_t)1;  // keep 16-byte alignment
         return p;
     }
+    // A step of a composed call (he_lintrans_evaluate_many) runs an entry point's launches, which reserve and take their scratch
+    // as if the arena were empty: while a frame is open the arena they see starts above what the composed call has taken, and a
+    // reserve that would have to grow it fails instead (arena_reserve).  Stream order makes a closed frame's scratch free for the
+    // next one.
+    int arena_frames = 0;
+    struct ArenaFrame {
+        Ctx &c;
+        const size_t mark;
+        explicit ArenaFrame(Ctx &ctx) : c(ctx), mark(ctx.arena_used) {
+            c.arena += mark; c.arena_words -= mark; c.arena_used = 0; c.arena_frames++;
+        }
+        ~ArenaFrame() { c.arena -= mark; c.arena_words += mark; c.arena_used = mark; c.arena_frames--; }
+        ArenaFrame(const ArenaFrame &) = delete;
+    };
 };
 
 // a device-resident automorphism index table (N x 4 bytes), shared by every AutoIndex handle of its (ring, Galois element)
@@ -3267,12 +3285,25 @@ size_t ks_scratch_words(const BasisExtender &be, int levelQ, int levelP, int bat
     w += 2 * B * (levelP + 1) * N * 2 + 2 * B * (levelQ + 1) * N * 2;
     return w + 64;
 }
+// The scratch each of these entries' launches reserve and take, as the entry itself and a call composed of several of them
+// (he_lintrans_evaluate_many) size it: ONE expression per step.
+size_t decompose_ntt_words(const BasisExtender &be, int levelQ, int B) { return (size_t)B * (levelQ + 1) * be.Q->N; }
+size_t auto_hoisted_lazy_words(const BasisExtender &be, int levelQ, int levelP, int B) {
+    const size_t N = be.Q->N;
+    return 3 * (size_t)B * (levelQ + 1) * N + 2 * (size_t)B * (levelP + 1) * N + N + 64;
+}
+size_t giant_step_words(const BasisExtender &be, int levelQ, int levelP, int B, const Evk *k) {
+    return ks_scratch_words(be, levelQ, levelP, B, true, k) + 2 * (size_t)B * (levelQ + levelP + 2) * be.Q->N + 64;
+}
+size_t eval_moddown_words(const BasisExtender &be, int levelQ, int levelP, int B) { return (size_t)B * (levelQ + levelP + 2) * be.Q->N; }
 }  // namespace
 
 namespace {
 int decompose_fused(Evaluator &ev, const FusedPlan &plan, int levelQ, int levelP, int nbPi, View rows_inv, View dec, int batch,
                     int ntt_filter = 0, bool f64_raw = false);
 }
+static int decompose_ntt_run(const std::shared_ptr<Evaluator> &ev, int levelQ, int levelP, int nbPi, int c2_is_ntt, size_t dec_ds,
+                             const View *v, int B);
 int he_decompose_and_split(he_handle hev, int levelQ, int levelP, int nbPi, int digit, he_handle h0, he_handle h1q, he_handle h1p) {
     GET(ev, Evaluator, hev, T_EVAL);
     BasisExtender &be = *ev->be;
@@ -3355,39 +3386,45 @@ int he_decompose_ntt(he_handle hev, int levelQ, int levelP, int nbPi, he_handle 
     q.op = CO_DECOMPOSE_NTT; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP; q.par[2] = nbPi; q.par[3] = c2_is_ntt;
     q.keep.push_back(ev);
     q.run = [ev, levelQ, levelP, nbPi, c2_is_ntt, dec_ds](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        be.ctx->acct(levelQ + 1 + (double)base_rns_size(levelQ, levelP) * (levelQ + levelP + 2), 0, B, N);  // DecomposeNTT: L in, beta (L + alpha) out
-        { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), true, false); V.into(*be.ctx, B); }
-        const size_t w = (size_t)B * (levelQ + 1) * N;
-        TRY(be.ctx->arena_reserve(w));
-        View other{be.ctx->arena_take(w), (size_t)(levelQ + 1) * N};
-        View ntt = v[0], inv = other;
-        if (c2_is_ntt) {
-            const FusedPlan *plan = nullptr;
-            TRY(get_dec_plan(*ev, levelQ, levelP, nbPi, &plan));
-            if (plan->ok) {
-                HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), v[0], other, B, true, NTT_REDUCE_INPUT, be.ctx->stream));
-                TRY(decompose_fused(*ev, *plan, levelQ, levelP, nbPi, other, v[1], B));
-                const int beta = base_rns_size(levelQ, levelP);
-                for (int d = 0; d < beta; d++) {  // own limbs: copy of the NTT-domain input (evaluator_gadget_product.go:498-503)
-                    const int s0 = d * nbPi, e0 = std::min(s0 + nbPi, levelQ + 1);
-                    View blk{v[1].p + (size_t)d * dec_ds, v[1].bstride, v[1].tab};
-                    HIP_TRY(launch_ew(be.qp, ident_tab(e0 - s0, s0, s0, s0), EW_COPY, v[0], v[0], blk, B, nullptr, nullptr, be.ctx->stream));
-                }
-                return HE_OK;
-            }
-            HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), v[0], other, B, true, NTT_REDUCE_INPUT));
-        } else {
-            HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), v[0], other, B, false, NTT_REDUCE_INPUT));
-            ntt = other; inv = v[0];
-        }
-        return decompose_ntt_into(*ev, levelQ, levelP, nbPi, ntt, inv, v[1], dec_ds, B);
+        return decompose_ntt_run(ev, levelQ, levelP, nbPi, c2_is_ntt, dec_ds, v, B);
     };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
     TRY(co_dispatch(*be.ctx, o.B, q));
     dec->fillQ = levelQ; dec->fillP = levelP; dec->fill_beta = base_rns_size(levelQ, levelP);
     return HE_OK;
+}
+// the launches of DecomposeNTT over B entries: v = (c2, the hoisting buffer [B][digits][LQ + LP][N] with digit stride dec_ds).
+// The caller holds the context (Scope).
+static int decompose_ntt_run(const std::shared_ptr<Evaluator> &ev, int levelQ, int levelP, int nbPi, int c2_is_ntt, size_t dec_ds,
+                             const View *v, int B) {
+    BasisExtender &be = *ev->be;
+    const int N = be.Q->N;
+    be.ctx->acct(levelQ + 1 + (double)base_rns_size(levelQ, levelP) * (levelQ + levelP + 2), 0, B, N);  // DecomposeNTT: L in, beta (L + alpha) out
+    { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), true, false); V.into(*be.ctx, B); }
+    const size_t w = decompose_ntt_words(be, levelQ, B);
+    TRY(be.ctx->arena_reserve(w));
+    View other{be.ctx->arena_take(w), (size_t)(levelQ + 1) * N};
+    View ntt = v[0], inv = other;
+    if (c2_is_ntt) {
+        const FusedPlan *plan = nullptr;
+        TRY(get_dec_plan(*ev, levelQ, levelP, nbPi, &plan));
+        if (plan->ok) {
+            HIP_TRY(launch_ntt_rows(be.qp, ident_tab(levelQ + 1), v[0], other, B, true, NTT_REDUCE_INPUT, be.ctx->stream));
+            TRY(decompose_fused(*ev, *plan, levelQ, levelP, nbPi, other, v[1], B));
+            const int beta = base_rns_size(levelQ, levelP);
+            for (int d = 0; d < beta; d++) {  // own limbs: copy of the NTT-domain input (evaluator_gadget_product.go:498-503)
+                const int s0 = d * nbPi, e0 = std::min(s0 + nbPi, levelQ + 1);
+                View blk{v[1].p + (size_t)d * dec_ds, v[1].bstride, v[1].tab};
+                HIP_TRY(launch_ew(be.qp, ident_tab(e0 - s0, s0, s0, s0), EW_COPY, v[0], v[0], blk, B, nullptr, nullptr, be.ctx->stream));
+            }
+            return HE_OK;
+        }
+        HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), v[0], other, B, true, NTT_REDUCE_INPUT));
+    } else {
+        HIP_TRY(be_ntt(be, ident_tab(levelQ + 1), v[0], other, B, false, NTT_REDUCE_INPUT));
+        ntt = other; inv = v[0];
+    }
+    return decompose_ntt_into(*ev, levelQ, levelP, nbPi, ntt, inv, v[1], dec_ds, B);
 }
 
 namespace {
@@ -3891,6 +3928,33 @@ int he_moddown(he_handle hev, int levelQ, int levelP, he_handle c0Q, he_handle c
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
     return co_dispatch(*be.ctx, out0->batch, q);
 }
+// the launches of ModDownQPtoQNTT over B entries: v = (p1Q, p1P, p2Q); p2Q may be p1Q.  The caller holds the context (Scope).
+static int eval_moddown_run(const std::shared_ptr<Evaluator> &ev, int levelQ, int levelP, const View *v, int B) {
+    BasisExtender &be = *ev->be;
+    const int N = be.Q->N;
+    be.ctx->acct(2.0 * (levelQ + 1) + levelP + 1, 0, B, N);  // ModDownQPtoQNTT: 2 L + alpha
+    { Valu V(be.Q->logN); valu_moddown(V, be, levelQ, levelP); V.into(*be.ctx, B); }
+    const size_t wP = (size_t)B * (levelP + 1) * N, wQ = (size_t)B * (levelQ + 1) * N;
+    TRY(be.ctx->arena_reserve(eval_moddown_words(be, levelQ, levelP, B)));
+    View sP{be.ctx->arena_take(wP), (size_t)(levelP + 1) * N};
+    View sQ{be.ctx->arena_take(wQ), (size_t)(levelQ + 1) * N};
+    const FusedPlan *plan = nullptr;
+    TRY(get_md_plan(*ev, levelQ, levelP, &plan));
+    // the fused basis extension runs one 128-thread workgroup per 1024 coefficients and batch entry over ALL destination
+    // limbs: below one workgroup per CU the six-launch path, which also spreads the limbs over the grid, has the lower latency
+    const int rowbits = ntt_row_bits(be.Q->logN);
+    const bool wide = (size_t)B * ((size_t)1 << rowbits) / 128 >= 256;
+    if (!plan->ok || !wide) return moddown_q_ntt(be, levelQ, levelP, v[0], v[1], v[2], B, sP, sQ);
+    // three launches: INTT rows (P) -> [cols + ModUpPtoQ + cols] -> NTT rows whose epilogue is the last op of the ModDown
+    bool raw = false;
+    TRY(moddown_front_fused(*ev, *plan, levelQ, levelP, v[1], sP, sQ, B, false, &raw));
+    const LimbTab tq = ident_tab(levelQ + 1);
+    NttEpilogue epi;
+    moddown_epilogue(epi, be, levelP, tq, v[0]);
+    epi.y_reduce = true;  // p1Q is the caller's: any 64-bit word
+    HIP_TRY(launch_ntt_rows(be.qp, tq, sQ, v[2], B, false, raw ? NTT_INPUT_F64 : 0, be.ctx->stream, &epi));
+    return HE_OK;
+}
 int he_eval_moddown_qp_to_q_ntt(he_handle hev, int levelQ, int levelP, he_handle h1q, he_handle h1p, he_handle h2) {
     GET(ev, Evaluator, hev, T_EVAL);
     BasisExtender &be = *ev->be;
@@ -3904,32 +3968,7 @@ int he_eval_moddown_qp_to_q_ntt(he_handle hev, int levelQ, int levelP, he_handle
     TRY(o.check());
     q.op = CO_EVAL_MODDOWN; q.obj = ev.get(); q.par[0] = levelQ; q.par[1] = levelP;
     q.keep.push_back(ev);
-    q.run = [ev, levelQ, levelP](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        be.ctx->acct(2.0 * (levelQ + 1) + levelP + 1, 0, B, N);  // ModDownQPtoQNTT: 2 L + alpha
-        { Valu V(be.Q->logN); valu_moddown(V, be, levelQ, levelP); V.into(*be.ctx, B); }
-        const size_t wP = (size_t)B * (levelP + 1) * N, wQ = (size_t)B * (levelQ + 1) * N;
-        TRY(be.ctx->arena_reserve(wP + wQ));
-        View sP{be.ctx->arena_take(wP), (size_t)(levelP + 1) * N};
-        View sQ{be.ctx->arena_take(wQ), (size_t)(levelQ + 1) * N};
-        const FusedPlan *plan = nullptr;
-        TRY(get_md_plan(*ev, levelQ, levelP, &plan));
-        // the fused basis extension runs one 128-thread workgroup per 1024 coefficients and batch entry over ALL destination
-        // limbs: below one workgroup per CU the six-launch path, which also spreads the limbs over the grid, has the lower latency
-        const int rowbits = ntt_row_bits(be.Q->logN);
-        const bool wide = (size_t)B * ((size_t)1 << rowbits) / 128 >= 256;
-        if (!plan->ok || !wide) return moddown_q_ntt(be, levelQ, levelP, v[0], v[1], v[2], B, sP, sQ);
-        // three launches: INTT rows (P) -> [cols + ModUpPtoQ + cols] -> NTT rows whose epilogue is the last op of the ModDown
-        bool raw = false;
-        TRY(moddown_front_fused(*ev, *plan, levelQ, levelP, v[1], sP, sQ, B, false, &raw));
-        const LimbTab tq = ident_tab(levelQ + 1);
-        NttEpilogue epi;
-        moddown_epilogue(epi, be, levelP, tq, v[0]);
-        epi.y_reduce = true;  // p1Q is the caller's: any 64-bit word
-        HIP_TRY(launch_ntt_rows(be.qp, tq, sQ, v[2], B, false, raw ? NTT_INPUT_F64 : 0, be.ctx->stream, &epi));
-        return HE_OK;
-    };
+    q.run = [ev, levelQ, levelP](const View *v, int B) -> int { return eval_moddown_run(ev, levelQ, levelP, v, B); };
     q.tables_ok = [ev](bool *ok) -> int { *ok = ev->be->type == 0; return HE_OK; };
     return co_dispatch(*be.ctx, o.B, q);
 }
@@ -4096,6 +4135,8 @@ int he_automorphism_hoisted(he_handle ev, int level, he_handle in0, he_handle de
 }
 
 // AutomorphismHoistedLazy (core/rlwe/evaluator_automorphism.go:104-165), NTT domain
+static int auto_hoisted_lazy_run(const std::shared_ptr<Evaluator> &ev, const std::shared_ptr<Evk> &k, int levelQ, int levelP, uint64_t gal,
+                                 KsAlias alias, size_t dec_ds, const View *v, int B);
 int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_handle hdec, uint64_t gal, he_handle hk, he_handle c0Q,
                                  he_handle c0P, he_handle c1Q, he_handle c1P) {
     GET(ev, Evaluator, hev, T_EVAL);
@@ -4122,48 +4163,54 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
     const size_t dec_ds = dec->dstride();
     ks_request(q, CO_AUTO_HOISTED_LAZY, ev, k, levelQ, KS_FORM_COUNT, KsAlias{}); q.par[1] = (int64_t)gal;
     q.run = [ev, k, levelQ, levelP, gal, alias, dec_ds](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        be.ctx->acct(levelQ + 1 + key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + levelP + 2), key_limbs(*k, levelQ), B, N);
-        { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), false, true); for (int i = 0; i <= levelQ; i++) V.mul(cls_f64(be.small, i), 1.0); V.into(*be.ctx, B); }
-        ScalarTab s{};  // ctTmp[1].Q = ctIn[0] * P   (MulScalarBigint with P = prod p_j at levelP)
-        for (int i = 0; i <= levelQ; i++) {
-            const ModConst &m = be.Q->sub[i].mc;
-            uint64_t pm = 1;
-            for (int j = 0; j <= levelP; j++) pm = mulmod(pm, be.P->moduli[j] % m.q, m.q);
-            s.s[i] = mform(pm, m.q, m.brc0, m.brc1);
-        }
-        // ONE launch: the key inner product adds ctIn[0] * P to component 0 at the source position and stores all four accumulators
-        // through the automorphism (KsScatter) -- instead of inner product, two element-wise passes and four gathers.  Standard
-        // ring, and the outputs must not be the addend (other threads still read it).
-        KsCall c;
-        TRY(ks_call(*ev, KS_AUTOMORPHISM_HOISTED_LAZY, levelQ, *k, alias, &c));
-        if (c.route.automorphism == KS_AUTO_KS_SCATTER) {
-            KsScatter ks;
-            ks.ginv = galois_inverse(gal, be.Q->logN);
-            ks.add0 = v[0];
-            for (int i = 0; i <= levelQ; i++) ks.add_s[i] = s.s[i];
-            return ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, v[2], v[3], v[4], v[5], B, nullptr, 0, 0, 0, -1, &ks);
-        }
-        const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
-        TRY(be.ctx->arena_reserve(3 * B * sQw + 2 * B * sPw + N + 64));
-        View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw}, t2Q{be.ctx->arena_take(B * sQw), sQw};
-        View t0P{be.ctx->arena_take(B * sPw), sPw}, t1P{be.ctx->arena_take(B * sPw), sPw};
-        const uint32_t *index = nullptr;
-        TRY(cached_auto_index(*ev, gal, &index));
-        hipStream_t st = be.ctx->stream;
-        TRY(ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, t0Q, t0P, t1Q, t1P, B));
-        const LimbTab tq = ident_tab(levelQ + 1), tp = ident_tab(levelP + 1, 0, 0, be.LQ);
-        // in0 is read before any output is written (c0Q or c1Q may be in0)
-        HIP_TRY(launch_ew(be.qp, tq, EW_MUL_SCALAR_MONT, v[0], v[0], t2Q, B, &s, nullptr, st));
-        HIP_TRY(launch_ew(be.qp, tq, EW_ADD, t0Q, t2Q, t0Q, B, nullptr, nullptr, st));
-        HIP_TRY(launch_gather(be.qp, tq, t1Q, index, v[4], B, false, st));
-        HIP_TRY(launch_gather(be.qp, tp, t1P, index, v[5], B, false, st));
-        HIP_TRY(launch_gather(be.qp, tq, t0Q, index, v[2], B, false, st));
-        HIP_TRY(launch_gather(be.qp, tp, t0P, index, v[3], B, false, st));
-        return HE_OK;
+        return auto_hoisted_lazy_run(ev, k, levelQ, levelP, gal, alias, dec_ds, v, B);
     };
     return co_dispatch(*be.ctx, B, q);
+}
+// the launches of AutomorphismHoistedLazy over B entries: v = (in0, the hoisting buffer, c0Q, c0P, c1Q, c1P).  The caller holds
+// the context (Scope).
+static int auto_hoisted_lazy_run(const std::shared_ptr<Evaluator> &ev, const std::shared_ptr<Evk> &k, int levelQ, int levelP, uint64_t gal,
+                                 KsAlias alias, size_t dec_ds, const View *v, int B) {
+    BasisExtender &be = *ev->be;
+    const int N = be.Q->N;
+    be.ctx->acct(levelQ + 1 + key_limbs(*k, levelQ) / 2 + 2.0 * (levelQ + levelP + 2), key_limbs(*k, levelQ), B, N);
+    { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), false, true); for (int i = 0; i <= levelQ; i++) V.mul(cls_f64(be.small, i), 1.0); V.into(*be.ctx, B); }
+    ScalarTab s{};  // ctTmp[1].Q = ctIn[0] * P   (MulScalarBigint with P = prod p_j at levelP)
+    for (int i = 0; i <= levelQ; i++) {
+        const ModConst &m = be.Q->sub[i].mc;
+        uint64_t pm = 1;
+        for (int j = 0; j <= levelP; j++) pm = mulmod(pm, be.P->moduli[j] % m.q, m.q);
+        s.s[i] = mform(pm, m.q, m.brc0, m.brc1);
+    }
+    // ONE launch: the key inner product adds ctIn[0] * P to component 0 at the source position and stores all four accumulators
+    // through the automorphism (KsScatter) -- instead of inner product, two element-wise passes and four gathers.  Standard
+    // ring, and the outputs must not be the addend (other threads still read it).
+    KsCall c;
+    TRY(ks_call(*ev, KS_AUTOMORPHISM_HOISTED_LAZY, levelQ, *k, alias, &c));
+    if (c.route.automorphism == KS_AUTO_KS_SCATTER) {
+        KsScatter ks;
+        ks.ginv = galois_inverse(gal, be.Q->logN);
+        ks.add0 = v[0];
+        for (int i = 0; i <= levelQ; i++) ks.add_s[i] = s.s[i];
+        return ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, v[2], v[3], v[4], v[5], B, nullptr, 0, 0, 0, -1, &ks);
+    }
+    const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
+    TRY(be.ctx->arena_reserve(auto_hoisted_lazy_words(be, levelQ, levelP, B)));
+    View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw}, t2Q{be.ctx->arena_take(B * sQw), sQw};
+    View t0P{be.ctx->arena_take(B * sPw), sPw}, t1P{be.ctx->arena_take(B * sPw), sPw};
+    const uint32_t *index = nullptr;
+    TRY(cached_auto_index(*ev, gal, &index));
+    hipStream_t st = be.ctx->stream;
+    TRY(ks_inner(*ev, levelQ, levelP, v[1], dec_ds, *k, t0Q, t0P, t1Q, t1P, B));
+    const LimbTab tq = ident_tab(levelQ + 1), tp = ident_tab(levelP + 1, 0, 0, be.LQ);
+    // in0 is read before any output is written (c0Q or c1Q may be in0)
+    HIP_TRY(launch_ew(be.qp, tq, EW_MUL_SCALAR_MONT, v[0], v[0], t2Q, B, &s, nullptr, st));
+    HIP_TRY(launch_ew(be.qp, tq, EW_ADD, t0Q, t2Q, t0Q, B, nullptr, nullptr, st));
+    HIP_TRY(launch_gather(be.qp, tq, t1Q, index, v[4], B, false, st));
+    HIP_TRY(launch_gather(be.qp, tp, t1P, index, v[5], B, false, st));
+    HIP_TRY(launch_gather(be.qp, tq, t0Q, index, v[2], B, false, st));
+    HIP_TRY(launch_gather(be.qp, tp, t0P, index, v[3], B, false, st));
+    return HE_OK;
 }
 
 // The giant step of MultiplyByDiagMatrixBSGS (circuits/common/lintrans/lintrans_evaluator.go:397-441) as one call:
@@ -4171,6 +4218,8 @@ int he_automorphism_hoisted_lazy(he_handle hev, int levelQ, he_handle hin0, he_h
 // (accumulate: ...ThenAddLazy).  On standard rings with the fused decomposition the key inner products store through the
 // automorphism themselves (KsScatter giant step: no intermediate ciphertext, no Add and gather passes); otherwise the same
 // launches as the separate calls.  Bit-identical to the separate calls either way.
+static int giant_step_run(const std::shared_ptr<Evaluator> &ev, const std::shared_ptr<Evk> &k, int levelQ, int levelP, uint64_t gal,
+                          int accumulate, const View *v, int B);
 int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle hk, uint64_t gal, he_handle haddQ, he_handle haddP,
                            he_handle c0Q, he_handle c0P, he_handle c1Q, he_handle c1P, int accumulate) {
     const char *who = "he_lintrans_giant_step";
@@ -4192,43 +4241,48 @@ int he_lintrans_giant_step(he_handle hev, int levelQ, he_handle hcx, he_handle h
     gal = reduce_gal(gal, be.Q->logN, be.type);
     ks_request(q, CO_GIANT_STEP, ev, k, levelQ, KS_GIANT_STEP, KsAlias{}); q.par[1] = (int64_t)gal; q.par[2] = accumulate ? 1 : 0;
     q.run = [ev, k, levelQ, levelP, gal, accumulate](const View *v, int B) -> int {
-        BasisExtender &be = *ev->be;
-        const int N = be.Q->N;
-        const bool acc = accumulate != 0;
-        // SURVEY 8(d) accounting of the calls this one stands for: GadgetProductLazy + Add on QP + two automorphisms on QP
-        be.ctx->acct(levelQ + 1 + 2.0 * (levelQ + levelP + 2) + 3.0 * (levelQ + levelP + 2) + 2.0 * (acc ? 3.0 : 2.0) * (levelQ + levelP + 2),
-                     key_limbs(*k, levelQ), B, N);
-        { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), true, true); V.into(*be.ctx, B); }
-        const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
-        TRY(be.ctx->arena_reserve(ks_scratch_words(be, levelQ, levelP, B, true, k.get()) + 2 * B * (sQw + sPw) + 64));
-        KsCall c;
-        TRY(ks_call(*ev, KS_GIANT_STEP, levelQ, *k, KsAlias{}, &c));
-        if (c.route.giant_fused) {
-            KsScatter ks;
-            ks.ginv = galois_inverse(gal, be.Q->logN);
-            ks.plain = 1; ks.add0 = v[1]; ks.add0P = v[2]; ks.accumulate = acc ? 1 : 0;
-            for (int i = 0; i < kMaxLimbs; i++) ks.add_s[i] = 0;
-            LazyArgs a{v[0], B, v[3], v[4], v[5], v[6]};
-            a.giant = &ks;
-            return gadget_product_lazy_core(*ev, levelQ, *k, c, a);
-        }
-        // the separate calls' launches
-        View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw};
-        View t0P{be.ctx->arena_take(B * sPw), sPw}, t1P{be.ctx->arena_take(B * sPw), sPw};
-        TRY(gadget_product_lazy_core(*ev, levelQ, *k, c, LazyArgs{v[0], B, t0Q, t0P, t1Q, t1P}));
-        const uint32_t *index = nullptr;
-        TRY(cached_auto_index(*ev, gal, &index));
-        hipStream_t st = be.ctx->stream;
-        const LimbTab tq = ident_tab(levelQ + 1), tp = ident_tab(levelP + 1, 0, 0, be.LQ);
-        HIP_TRY(launch_ew(be.qp, tq, EW_ADD, t0Q, v[1], t0Q, B, nullptr, nullptr, st));
-        HIP_TRY(launch_ew(be.qp, tp, EW_ADD, t0P, v[2], t0P, B, nullptr, nullptr, st));
-        HIP_TRY(launch_gather(be.qp, tq, t0Q, index, v[3], B, acc, st));
-        HIP_TRY(launch_gather(be.qp, tp, t0P, index, v[4], B, acc, st));
-        HIP_TRY(launch_gather(be.qp, tq, t1Q, index, v[5], B, acc, st));
-        HIP_TRY(launch_gather(be.qp, tp, t1P, index, v[6], B, acc, st));
-        return HE_OK;
+        return giant_step_run(ev, k, levelQ, levelP, gal, accumulate, v, B);
     };
     return co_dispatch(*be.ctx, B, q);
+}
+// the launches of the giant step over B entries: v = (cx, addQ, addP, c0Q, c0P, c1Q, c1P).  The caller holds the context (Scope).
+static int giant_step_run(const std::shared_ptr<Evaluator> &ev, const std::shared_ptr<Evk> &k, int levelQ, int levelP, uint64_t gal,
+                          int accumulate, const View *v, int B) {
+    BasisExtender &be = *ev->be;
+    const int N = be.Q->N;
+    const bool acc = accumulate != 0;
+    // SURVEY 8(d) accounting of the calls this one stands for: GadgetProductLazy + Add on QP + two automorphisms on QP
+    be.ctx->acct(levelQ + 1 + 2.0 * (levelQ + levelP + 2) + 3.0 * (levelQ + levelP + 2) + 2.0 * (acc ? 3.0 : 2.0) * (levelQ + levelP + 2),
+                 key_limbs(*k, levelQ), B, N);
+    { Valu V(be.Q->logN); valu_keyswitch(V, be, levelQ, levelP, base_rns_size(levelQ, levelP), true, true); V.into(*be.ctx, B); }
+    const size_t sQw = (size_t)(levelQ + 1) * N, sPw = (size_t)(levelP + 1) * N;
+    TRY(be.ctx->arena_reserve(giant_step_words(be, levelQ, levelP, B, k.get())));
+    KsCall c;
+    TRY(ks_call(*ev, KS_GIANT_STEP, levelQ, *k, KsAlias{}, &c));
+    if (c.route.giant_fused) {
+        KsScatter ks;
+        ks.ginv = galois_inverse(gal, be.Q->logN);
+        ks.plain = 1; ks.add0 = v[1]; ks.add0P = v[2]; ks.accumulate = acc ? 1 : 0;
+        for (int i = 0; i < kMaxLimbs; i++) ks.add_s[i] = 0;
+        LazyArgs a{v[0], B, v[3], v[4], v[5], v[6]};
+        a.giant = &ks;
+        return gadget_product_lazy_core(*ev, levelQ, *k, c, a);
+    }
+    // the separate calls' launches
+    View t0Q{be.ctx->arena_take(B * sQw), sQw}, t1Q{be.ctx->arena_take(B * sQw), sQw};
+    View t0P{be.ctx->arena_take(B * sPw), sPw}, t1P{be.ctx->arena_take(B * sPw), sPw};
+    TRY(gadget_product_lazy_core(*ev, levelQ, *k, c, LazyArgs{v[0], B, t0Q, t0P, t1Q, t1P}));
+    const uint32_t *index = nullptr;
+    TRY(cached_auto_index(*ev, gal, &index));
+    hipStream_t st = be.ctx->stream;
+    const LimbTab tq = ident_tab(levelQ + 1), tp = ident_tab(levelP + 1, 0, 0, be.LQ);
+    HIP_TRY(launch_ew(be.qp, tq, EW_ADD, t0Q, v[1], t0Q, B, nullptr, nullptr, st));
+    HIP_TRY(launch_ew(be.qp, tp, EW_ADD, t0P, v[2], t0P, B, nullptr, nullptr, st));
+    HIP_TRY(launch_gather(be.qp, tq, t0Q, index, v[3], B, acc, st));
+    HIP_TRY(launch_gather(be.qp, tp, t0P, index, v[4], B, acc, st));
+    HIP_TRY(launch_gather(be.qp, tq, t1Q, index, v[5], B, acc, st));
+    HIP_TRY(launch_gather(be.qp, tp, t1P, index, v[6], B, acc, st));
+    return HE_OK;
 }
 
 // centred lifts / hoisting-buffer fill of bootstrapping.Evaluator.ModUp (see hering.h)
@@ -8307,6 +8361,493 @@ int he_blind_rotate_core(he_handle hev, const uint64_t *a, int batch, int n_lwe,
     };
     q.one_by_one();
     return co_dispatch(*be.ctx, o.B, q);
+}
+
+// ---------------------------------------------------------------------------------------
+// lintrans.Evaluator (include/hering_lintrans.h; circuits/common/lintrans): the index on the host, the LinearTransformation
+// handle, and EvaluateMany as one request composed of the launches of he_decompose_ntt, he_automorphism_hoisted_lazy, the
+// grouped multiply-accumulate kernel, he_eval_moddown_qp_to_q_ntt and he_lintrans_giant_step
+// ---------------------------------------------------------------------------------------
+int he_lintrans_bsgs_index(const int *diag, int n, int slots, int N1, int *rotN1, int *n1, int *rotN2, int *n2, int *index) {
+    static const char *who = "he_lintrans_bsgs_index";
+    if (n < 0 || (n > 0 && !diag) || !n1 || !n2) return fail(HE_EINVAL, "%s: null argument", who);
+    if (slots < 1 || (slots & (slots - 1)) || N1 < 1 || (N1 & (N1 - 1))) return fail(HE_EINVAL, "%s: slots and N1 must be powers of two", who);
+    const lintrans::BsgsIndex ix = lintrans::bsgs_index(diag, n, slots, N1);
+    if (rotN1) std::copy(ix.rotN1.begin(), ix.rotN1.end(), rotN1);
+    if (rotN2) std::copy(ix.rotN2.begin(), ix.rotN2.end(), rotN2);
+    *n1 = (int)ix.rotN1.size(); *n2 = (int)ix.rotN2.size();
+    if (index)
+        for (int k = 0; k < n; k++) {
+            const int64_t rot = (int64_t)diag[k] & ((int64_t)slots - 1);
+            index[2 * k] = (int)(((rot / N1) * N1) & ((int64_t)slots - 1));
+            index[2 * k + 1] = (int)(rot & ((int64_t)N1 - 1));
+        }
+    return HE_OK;
+}
+int he_lintrans_find_best_bsgs_ratio(const int *diag, int n, int maxN, int logMaxRatio, int *N1) {
+    static const char *who = "he_lintrans_find_best_bsgs_ratio";
+    if (n < 0 || (n > 0 && !diag) || !N1) return fail(HE_EINVAL, "%s: null argument", who);
+    if (maxN < 1 || (maxN & (maxN - 1)) || logMaxRatio < 0 || logMaxRatio > 30) return fail(HE_EINVAL, "%s: maxN must be a power of two and logMaxRatio in [0, 30]", who);
+    *N1 = lintrans::find_best_bsgs_ratio(diag, n, maxN, logMaxRatio);
+    return HE_OK;
+}
+int he_lintrans_galois_elements(he_handle hev, const int *diag, int n, int slots, int logBSGSRatio, uint64_t *out, size_t cap, size_t *n_out) {
+    static const char *who = "he_lintrans_galois_elements";
+    GET(ev, Evaluator, hev, T_EVAL);
+    if (n < 0 || (n > 0 && !diag) || !n_out || (cap && !out)) return fail(HE_EINVAL, "%s: null argument", who);
+    if (slots < 1 || (slots & (slots - 1)) || logBSGSRatio > 30) return fail(HE_EINVAL, "%s: slots must be a power of two and logBSGSRatio at most 30", who);
+    const BasisExtender &be = *ev->be;
+    const std::vector<uint64_t> g = lintrans::galois_elements((uint64_t)2 << (be.Q->logN + be.type), diag, n, slots, logBSGSRatio);
+    for (size_t i = 0; i < g.size() && i < cap; i++) out[i] = g[i];
+    *n_out = g.size();
+    return HE_OK;
+}
+
+namespace {
+constexpr int kLintransGroups[3] = {1, 2, 4};
+constexpr int kLintransDefaultGroup = 4;  // the fastest of 1, 2, 4 at the c5 shape (NOTES.md)
+// one launch of the grouped kernel per ring part: where its rows start in the device table
+struct LinTransGroupDev {
+    size_t off = 0;
+    int n_babies = 0, members = 0, terms_q = 0, terms_p = 0, babies_p = 0;
+};
+struct LinTrans : Obj {
+    std::shared_ptr<Evaluator> ev;
+    int levelQ = 0, levelP = 0, slots = 0, N1 = 0;
+    std::atomic<int> group{0};                // he_lintrans_set_group (0: the default)
+    std::vector<int> diag;                    // reduced
+    std::vector<std::shared_ptr<Poly>> ptQ, ptP;
+    lintrans::Plan plan[3];                   // for G = 1, 2, 4
+    std::vector<LinTransGroupDev> gdev[3];
+    uint64_t *d_tab = nullptr;                // the term tables of the three plans
+    LinTrans() : Obj(T_LINTRANS) {}
+    ~LinTrans() override {
+        if (!d_tab) return;
+        hipSetDevice(ev->be->ctx->dev);
+        hipStreamSynchronize(ev->be->ctx->stream);
+        hipFree(d_tab);
+    }
+};
+int lintrans_default_group() {
+    static const int g = [] {
+        const char *s = getenv("HERING_LINTRANS_GROUP");
+        const int v = s ? atoi(s) : 0;
+        return (v == 1 || v == 2 || v == 4) ? v : kLintransDefaultGroup;
+    }();
+    return g;
+}
+inline int lintrans_group_slot(int G) { return G >= 4 ? 2 : (G >= 2 ? 1 : 0); }
+// what one transformation of a call works with, resolved before the request is filed
+struct LinTransJob {
+    std::shared_ptr<LinTrans> lt;
+    int levelQ = 0, gslot = 0;
+    std::vector<std::shared_ptr<Evk>> giant_keys;  // BSGS: per giant step in plan order (null for j = 0); naive: per rotation
+    std::vector<uint64_t> giant_gal;
+    std::vector<size_t> slot_map;                  // BSGS: the call's pre-rotation slot of each non-zero baby step (empty: identity)
+};
+struct LinTransCall {
+    std::shared_ptr<Evaluator> ev;
+    int levelQd = 0, levelP = 0;
+    std::vector<int> babies;                       // the call's non-zero baby steps, ascending: pre-rotation slot s holds babies[s]
+    std::vector<std::shared_ptr<Evk>> baby_keys;
+    std::vector<uint64_t> baby_gal;
+    std::vector<LinTransJob> jobs;
+    bool any_naive = false, any_bsgs = false;
+    int max_group = 1;
+};
+inline uint64_t lintrans_overflow_half(const std::vector<uint64_t> &moduli, int level) {
+    uint64_t mx = 0;
+    for (int i = 0; i <= level; i++) mx = std::max(mx, moduli[(size_t)i]);
+    return (uint64_t)(18446744073709551616.0 / (double)mx) >> 1;  // Qi/PiOverflowMargin(level) >> 1 (core/rlwe/params.go:554-570)
+}
+// scratch of the steps a call composes: the largest of what its entry points' launches reserve
+size_t lintrans_step_words(const BasisExtender &be, int levelQ, int levelP, int B, const Evk *k) {
+    return std::max({decompose_ntt_words(be, levelQ, B), auto_hoisted_lazy_words(be, levelQ, levelP, B),
+                     giant_step_words(be, levelQ, levelP, B, k), eval_moddown_words(be, levelQ, levelP, B)}) + 64;
+}
+int lintrans_run(const LinTransCall &c, const View *v, int B) {
+    const std::shared_ptr<Evaluator> &ev = c.ev;
+    BasisExtender &be = *ev->be;
+    Ctx &ctx = *be.ctx;
+    hipStream_t st = ctx.stream;
+    const int N = be.Q->N, levelQd = c.levelQd, levelP = c.levelP;
+    const size_t b = (size_t)B, sQ = (size_t)(levelQd + 1) * N, sP = (size_t)(levelP + 1) * N;
+    const int beta = base_rns_size(levelQd, levelP);
+    const size_t dec_ds = (size_t)(be.LQ + be.LP) * N, dec_bs = (size_t)beta * dec_ds;
+    const size_t nslots = c.babies.size();
+    size_t map_words = 0;
+    for (const LinTransJob &j : c.jobs) map_words += (j.slot_map.size() + 1) & ~(size_t)1;
+    // the work block: the group's inner sums [G][2] QP (BSGS) or the key switch's accumulators [2] QP (naive)
+    const size_t work = (size_t)std::max(c.any_bsgs ? c.max_group : 0, c.any_naive ? 1 : 0) * 2 * b * (sQ + sP);
+    const size_t persistent = b * dec_bs + 2 * b * sQ + nslots * 2 * b * (sQ + sP) + (c.any_naive ? 2 * b * sQ : 0) + 2 * b * sP + work + map_words + 64;
+    const Evk *k0 = !c.baby_keys.empty() ? c.baby_keys[0].get() : nullptr;
+    for (const LinTransJob &j : c.jobs)
+        for (const auto &k : j.giant_keys) if (!k0 && k) k0 = k.get();
+    TRY(ctx.arena_reserve(persistent + lintrans_step_words(be, levelQd, levelP, B, k0)));
+    const View decv{ctx.arena_take(b * dec_bs), dec_bs};
+    uint64_t *pct = ctx.arena_take(2 * b * sQ);
+    uint64_t *preQ = ctx.arena_take(nslots * 2 * b * sQ), *preP = ctx.arena_take(nslots * 2 * b * sP);
+    uint64_t *cp = c.any_naive ? ctx.arena_take(2 * b * sQ) : nullptr;
+    uint64_t *accP = ctx.arena_take(2 * b * sP);
+    uint64_t *workQ = ctx.arena_take(work / (sQ + sP) * sQ), *workP = ctx.arena_take(work / (sQ + sP) * sP);
+    const View c0P{accP, sP}, c1P{accP + b * sP, sP};
+    const View pct0{pct, sQ}, pct1{pct + b * sQ, sQ};
+    const LimbTab tqd = ident_tab(levelQd + 1);
+    // ONE DecomposeNTT of c1 at levelQd with levelP + 1 special primes (:52)
+    {
+        Ctx::ArenaFrame f(ctx);
+        const View vv[2] = {v[1], decv};
+        TRY(decompose_ntt_run(ev, levelQd, levelP, levelP + 1, 1, dec_ds, vv, B));
+    }
+    // P * ct (BSGS :316-317; the naive form's P * c0 :190) and the naive form's copy of the input (:175-176)
+    {
+        ScalarTab s{};
+        for (int i = 0; i <= levelQd; i++) {
+            const ModConst &m = be.Q->sub[i].mc;
+            uint64_t pm = 1;
+            for (int j = 0; j <= levelP; j++) pm = mulmod(pm, be.P->moduli[j] % m.q, m.q);
+            s.s[i] = mform(pm, m.q, m.brc0, m.brc1);
+        }
+        const double comps = c.any_bsgs ? 2.0 : 1.0;  // (the naive form multiplies c0 only)
+        ctx.acct(2.0 * comps * (levelQd + 1), 0, B, N);
+        { Valu V(be.Q->logN); for (int i = 0; i <= levelQd; i++) V.mul(cls_f64(be.small, i), comps); V.into(ctx, B); }
+        HIP_TRY(launch_ew(be.qp, tqd, EW_MUL_SCALAR_MONT, v[0], v[0], pct0, B, &s, nullptr, st));
+        if (c.any_bsgs) HIP_TRY(launch_ew(be.qp, tqd, EW_MUL_SCALAR_MONT, v[1], v[1], pct1, B, &s, nullptr, st));
+        if (cp) {
+            ctx.acct(4.0 * (levelQd + 1), 0, B, N);
+            for (int k = 0; k < 2; k++)  // (plain views: the request is served alone)
+                HIP_TRY(hipMemcpy2DAsync(cp + (size_t)k * b * sQ, sQ * 8, v[k].p, v[k].bstride * 8, sQ * 8, B, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    // the pre-rotations every BSGS transformation of the call shares (:62, :82-104): AutomorphismHoistedLazy at levelQd
+    for (size_t s = 0; s < nslots; s++) {
+        Ctx::ArenaFrame f(ctx);
+        const View vv[6] = {v[0], decv, View{preQ + s * 2 * b * sQ, sQ}, View{preP + s * 2 * b * sP, sP},
+                            View{preQ + (s * 2 + 1) * b * sQ, sQ}, View{preP + (s * 2 + 1) * b * sP, sP}};
+        TRY(auto_hoisted_lazy_run(ev, c.baby_keys[s], levelQd, levelP, c.baby_gal[s], KsAlias{}, dec_ds, vv, B));
+    }
+    for (size_t t = 0; t < c.jobs.size(); t++) {
+        const LinTransJob &job = c.jobs[t];
+        const LinTrans &lt = *job.lt;
+        const int lq = job.levelQ;
+        const View out0 = v[2 + 2 * t], out1 = v[3 + 2 * t];
+        const LimbTab tq = ident_tab(lq + 1), tp = ident_tab(levelP + 1, 0, 0, be.LQ);
+        const lintrans::Plan &plan = lt.plan[job.gslot];
+        auto moddown = [&](View q, View p) -> int {
+            Ctx::ArenaFrame f(ctx);
+            const View vv[3] = {q, p, q};
+            return eval_moddown_run(ev, lq, levelP, vv, B);
+        };
+        if (lt.N1 == 0) {
+            // MultiplyByDiagMatrix (:142-274).  The accumulators stay canonical (launch_diag_mac), so the reference's periodic
+            // Reduce calls are no-ops here.
+            const View cQ0{workQ, sQ}, cQ1{workQ + b * sQ, sQ}, cP0{workP, sP}, cP1{workP + b * sP, sP};
+            const View cp0{cp, sQ}, cp1{cp + b * sQ, sQ};
+            for (size_t r = 0; r < plan.rotations.size(); r++) {
+                const Evk &k = *job.giant_keys[r];
+                const uint32_t *index = nullptr;
+                TRY(cached_auto_index(*ev, job.giant_gal[r], &index));
+                ctx.acct(key_limbs(k, lq) / 2 + 2.0 * (lq + levelP + 2), key_limbs(k, lq), B, N);  // he_gadget_product_hoisted_lazy
+                { Valu V(be.Q->logN); valu_keyswitch(V, be, lq, levelP, base_rns_size(lq, levelP), false, true); V.into(ctx, B); }
+                TRY(ks_inner(*ev, lq, levelP, decv, dec_ds, k, cQ0, cP0, cQ1, cP1, B));
+                ctx.acct(3.0 * (lq + 1), 0, B, N);
+                HIP_TRY(launch_ew(be.qp, tq, EW_ADD, cQ0, pct0, cQ0, B, nullptr, nullptr, st));  // + P * c0 before the automorphism (:221)
+                const Poly &dq = *lt.ptQ[(size_t)plan.rotation_term[r]], &dp = *lt.ptP[(size_t)plan.rotation_term[r]];
+                DiagMacArgs aq{}, ap{};
+                aq.n = ap.n = 1; aq.nlimbs = lq + 1; ap.nlimbs = levelP + 1; aq.accumulate = ap.accumulate = r > 0 ? 1 : 0;
+                aq.mod0 = 0; ap.mod0 = be.LQ;
+                aq.pt[0] = dq.d; aq.c0[0] = cQ0.p; aq.c1[0] = cQ1.p; aq.c0_bs[0] = aq.c1_bs[0] = sQ; aq.index[0] = index;
+                ap.pt[0] = dp.d; ap.c0[0] = cP0.p; ap.c1[0] = cP1.p; ap.c0_bs[0] = ap.c1_bs[0] = sP; ap.index[0] = index;
+                ctx.acct((r > 0 ? 6.0 : 4.0) * (lq + levelP + 2), (double)(lq + levelP + 2), B, N);
+                { Valu V(be.Q->logN); for (int i = 0; i <= lq; i++) V.mul(cls_f64(be.small, i), 4.0); for (int j = 0; j <= levelP; j++) V.mul(cls_f64(be.small, be.LQ + j), 4.0); V.into(ctx, B); }
+                HIP_TRY(launch_diag_mac(be.qp, aq, out0, out1, B, st));
+                HIP_TRY(launch_diag_mac(be.qp, ap, c0P, c1P, B, st));
+            }
+            if (!plan.rotations.empty()) {
+                TRY(moddown(out0, c0P));
+                TRY(moddown(out1, c1P));
+            }
+            // the zero diagonal after the ModDown, on the Q part only (:266-272); a transformation with no other diagonal is that
+            // product alone (no rotation has written the accumulators)
+            const bool fresh = plan.rotations.empty();
+            ctx.acct((fresh ? 4.0 : 6.0) * (lq + 1), (double)(lq + 1), B, N);
+            if (plan.zero_diag >= 0) {
+                { Valu V(be.Q->logN); for (int i = 0; i <= lq; i++) V.mul(cls_f64(be.small, i), 2.0); V.into(ctx, B); }
+                const View pt{lt.ptQ[(size_t)plan.zero_diag]->d, 0};
+                const int op = fresh ? EW_MUL_MONT : EW_MUL_MONT_THEN_ADD;
+                HIP_TRY(launch_ew(be.qp, tq, op, pt, cp0, out0, B, nullptr, nullptr, st));
+                HIP_TRY(launch_ew(be.qp, tq, op, pt, cp1, out1, B, nullptr, nullptr, st));
+            } else if (fresh) {
+                HIP_TRY(launch_ew(be.qp, tq, EW_ZERO, out0, out0, out0, B, nullptr, nullptr, st));
+                HIP_TRY(launch_ew(be.qp, tq, EW_ZERO, out1, out1, out1, B, nullptr, nullptr, st));
+            }
+            continue;
+        }
+        // MultiplyByDiagMatrixBSGS (:280-469)
+        const uint64_t *slot_map = nullptr;
+        if (!job.slot_map.empty()) {
+            size_t *m = reinterpret_cast<size_t *>(ctx.arena_take(job.slot_map.size()));
+            HIP_TRY(launch_tab_fill(m, job.slot_map.data(), (int)job.slot_map.size(), st));
+            slot_map = reinterpret_cast<const uint64_t *>(m);
+        }
+        const uint64_t QiOverF = lintrans_overflow_half(be.Q->moduli, lq), PiOverF = lintrans_overflow_half(be.P->moduli, levelP);
+        uint64_t cnt0 = 0;
+        size_t giant = 0;
+        auto reduce = [&](bool onQ) -> int {
+            ctx.acct(4.0 * (onQ ? lq + 1 : levelP + 1), 0, B, N);
+            if (onQ) {
+                HIP_TRY(launch_ew(be.qp, tq, EW_REDUCE, out0, out0, out0, B, nullptr, nullptr, st));
+                HIP_TRY(launch_ew(be.qp, tq, EW_REDUCE, out1, out1, out1, B, nullptr, nullptr, st));
+            } else {
+                HIP_TRY(launch_ew(be.qp, tp, EW_REDUCE, c0P, c0P, c0P, B, nullptr, nullptr, st));
+                HIP_TRY(launch_ew(be.qp, tp, EW_REDUCE, c1P, c1P, c1P, B, nullptr, nullptr, st));
+            }
+            return HE_OK;
+        };
+        for (size_t g = 0; g < plan.groups.size(); g++) {
+            const lintrans::Group &grp = plan.groups[g];
+            const LinTransGroupDev &gd = lt.gdev[job.gslot][g];
+            // the inner sums of the group's members (:342-394), canonical: ONE launch per ring part
+            DiagMacGroupArgs a{};
+            a.tab = lt.d_tab + gd.off; a.n_babies = gd.n_babies; a.members = gd.members; a.row_words = 1 + 2 * gd.members;
+            a.slot_map = slot_map;
+            a.out_member = 2 * b; a.out_comp = b;  // (x the part's entry stride, below)
+            DiagMacGroupArgs aq = a, ap = a;
+            aq.part = 0; aq.ct = preQ; aq.ct_slot = 2 * b * sQ; aq.ct_comp = b * sQ; aq.ct_bs = sQ;
+            aq.pct = pct; aq.pct_comp = b * sQ; aq.pct_bs = sQ;
+            aq.out = workQ; aq.out_member *= sQ; aq.out_comp *= sQ; aq.out_bs = sQ; aq.nlimbs = lq + 1; aq.mod0 = 0; aq.terms = gd.terms_q;
+            ap.part = 1; ap.ct = preP; ap.ct_slot = 2 * b * sP; ap.ct_comp = b * sP; ap.ct_bs = sP;
+            ap.pct = nullptr;  // the i = 0 term is P * ct with no P part (:349-352)
+            ap.out = workP; ap.out_member *= sP; ap.out_comp *= sP; ap.out_bs = sP; ap.nlimbs = levelP + 1; ap.mod0 = be.LQ; ap.terms = gd.terms_p;
+            // giant step j = 0 comes first (the giant steps ascend) and opens the outer accumulators with a copy (:425-433): its
+            // inner sums are written where that copy would put them
+            const bool opens = cnt0 == 0 && grp.giants[0] == 0;
+            if (opens) {
+                aq.m0[0] = out0.p; aq.m0[1] = out1.p; aq.m0_bs[0] = out0.bstride; aq.m0_bs[1] = out1.bstride;
+                ap.m0[0] = c0P.p; ap.m0[1] = c1P.p; ap.m0_bs[0] = ap.m0_bs[1] = sP;
+            }
+            ctx.acct((2.0 * gd.n_babies + 2.0 * gd.members) * (lq + 1) + (2.0 * gd.babies_p + 2.0 * gd.members) * (levelP + 1),
+                     (double)gd.terms_q * (lq + 1) + (double)gd.terms_p * (levelP + 1), B, N);
+            {
+                Valu V(be.Q->logN);
+                for (int i = 0; i <= lq; i++) V.mul(cls_f64(be.small, i), 2.0 * gd.terms_q + 2.0 * gd.members);
+                for (int j = 0; j <= levelP; j++) V.mul(cls_f64(be.small, be.LQ + j), 2.0 * gd.terms_p + 2.0 * gd.members);
+                V.into(ctx, B);
+            }
+            HIP_TRY(launch_diag_mac_group(be.qp, aq, B, st));
+            HIP_TRY(launch_diag_mac_group(be.qp, ap, B, st));
+            for (int m = 0; m < gd.members; m++, giant++) {
+                const View t0Q{workQ + (size_t)(2 * m) * b * sQ, sQ}, t1Q{workQ + (size_t)(2 * m + 1) * b * sQ, sQ};
+                const View t0P{workP + (size_t)(2 * m) * b * sP, sP}, t1P{workP + (size_t)(2 * m + 1) * b * sP, sP};
+                if (grp.giants[(size_t)m] != 0) {
+                    TRY(moddown(t1Q, t1P));  // the hoisted ModDown of sum(sum(phi(d1) * plaintext)) (:397)
+                    Ctx::ArenaFrame f(ctx);
+                    const View vv[7] = {t1Q, t0Q, t0P, out0, c0P, out1, c1P};
+                    TRY(giant_step_run(ev, job.giant_keys[giant], lq, levelP, job.giant_gal[giant], cnt0 != 0, vv, B));
+                } else if (!(opens && m == 0)) {
+                    // (the giant steps ascend and are distinct: j = 0 can only be the first member of the first group)
+                    return fail(HE_EINVAL, "internal error: giant step 0 is not the first of the plan");
+                }
+                if (cnt0 % QiOverF == QiOverF - 1) TRY(reduce(true));   // :443-453
+                if (cnt0 % PiOverF == PiOverF - 1) TRY(reduce(false));
+                cnt0++;
+            }
+        }
+        if (cnt0 % QiOverF != 0) TRY(reduce(true));   // :456-464
+        if (cnt0 % PiOverF != 0) TRY(reduce(false));
+        TRY(moddown(out0, c0P));  // sum(phi(c0 * P + d0_QP)) / P
+        TRY(moddown(out1, c1P));  // sum(phi(d1_QP)) / P
+    }
+    return HE_OK;
+}
+}  // namespace
+
+int he_lintrans_create(he_handle hev, int levelQ, int levelP, int log_slots, int N1, int n, const int *diag, const he_handle *ptQ,
+                       const he_handle *ptP, he_handle *out) {
+    static const char *who = "he_lintrans_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    BasisExtender &be = *ev->be;
+    if (!out || n < 1 || !diag || !ptQ || !ptP) return fail(HE_EINVAL, "%s: at least one diagonal, its polynomials and an output are needed", who);
+    if (levelQ < 0 || levelQ >= be.LQ || levelP < 0 || levelP >= be.LP) return fail(HE_EINVAL, "%s: level out of range", who);
+    if (log_slots < 0 || log_slots > be.Q->logN) return fail(HE_EINVAL, "%s: log_slots out of range", who);
+    const int slots = 1 << log_slots;
+    if (N1 < 0 || (N1 & (N1 - 1))) return fail(HE_EINVAL, "%s: N1 must be 0 (naive) or a power of two", who);
+    auto lt = std::make_shared<LinTrans>();
+    lt->ev = ev; lt->levelQ = levelQ; lt->levelP = levelP; lt->slots = slots; lt->N1 = N1;
+    for (int k = 0; k < n; k++) {
+        int d = diag[k] & (slots - 1);
+        if (d < 0) d += slots;
+        if (std::find(lt->diag.begin(), lt->diag.end(), d) != lt->diag.end())
+            return fail(HE_EINVAL, "%s: diagonal %d (index %d) reduces to rotation %d, which is listed already", who, k, diag[k], d);
+        std::shared_ptr<Poly> q = get<Poly>(ptQ[k], T_POLY), p = get<Poly>(ptP[k], T_POLY);
+        if (!q || !p) return fail(HE_EHANDLE, "%s: bad Poly handle (diagonal %d)", who, k);
+        if (q->ctx != be.ctx || p->ctx != be.ctx || q->N != be.Q->N || p->N != be.Q->N)
+            return fail(HE_EINVAL, "%s: diagonal %d belongs to another context or degree", who, k);
+        if (q->nlimbs < levelQ + 1 || p->nlimbs < levelP + 1) return fail(HE_EINVAL, "%s: diagonal %d has too few limbs", who, k);
+        if (q->batch != 1 || p->batch != 1) return fail(HE_EINVAL, "%s: diagonal %d must be a polynomial of one entry", who, k);
+        if (q->d == p->d) return fail(HE_EINVAL, "%s: diagonal %d names one polynomial for its Q and its P part", who, k);
+        lt->diag.push_back(d); lt->ptQ.push_back(q); lt->ptP.push_back(p);
+    }
+    const uint64_t nth_root = (uint64_t)2 << (be.Q->logN + be.type);
+    std::vector<uint64_t> tab;
+    for (int s = 0; s < 3; s++) {
+        if (!lintrans::build_plan(lt->diag.data(), n, slots, N1, kLintransGroups[s], nth_root, &lt->plan[s]))
+            return fail(HE_EINVAL, "%s: no plan for these diagonals", who);
+        const lintrans::Plan &p = lt->plan[s];
+        std::vector<int> nz;  // the non-zero baby steps: pre-rotation number 1 + position
+        for (int i : p.babies) if (i != 0) nz.push_back(i);
+        for (const lintrans::Group &g : p.groups) {
+            LinTransGroupDev gd;
+            gd.off = tab.size(); gd.n_babies = (int)g.babies.size(); gd.members = (int)g.giants.size();
+            for (size_t bs = 0; bs < g.babies.size(); bs++) {
+                const int i = g.babies[bs];
+                tab.push_back(i == 0 ? 0 : (uint64_t)(1 + (std::lower_bound(nz.begin(), nz.end(), i) - nz.begin())));
+                if (i != 0) gd.babies_p++;
+                for (int m = 0; m < gd.members; m++) {
+                    const int t = g.term[bs * (size_t)gd.members + m];
+                    tab.push_back(t < 0 ? 0 : (uint64_t)(uintptr_t)lt->ptQ[(size_t)t]->d);
+                    tab.push_back(t < 0 ? 0 : (uint64_t)(uintptr_t)lt->ptP[(size_t)t]->d);
+                    if (t >= 0) { gd.terms_q++; if (i != 0) gd.terms_p++; }
+                }
+            }
+            lt->gdev[s].push_back(gd);
+        }
+    }
+    if (!tab.empty()) {
+        Scope sc(be.ctx.get());
+        HIP_TRY(hipMalloc((void **)&lt->d_tab, tab.size() * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpy(lt->d_tab, tab.data(), tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    *out = reg(lt);
+    return HE_OK;
+}
+int he_lintrans_destroy(he_handle h) { return unreg(h, T_LINTRANS); }
+int he_lintrans_set_group(he_handle h, int G) {
+    GET(lt, LinTrans, h, T_LINTRANS);
+    if (G != 0 && G != 1 && G != 2 && G != 4) return fail(HE_EINVAL, "he_lintrans_set_group: G must be 0 (the default), 1, 2 or 4");
+    lt->group.store(G);
+    return HE_OK;
+}
+
+int he_lintrans_evaluate_many(he_handle hev, he_handle hset, int ct_level, he_handle hin0, he_handle hin1, int n_lt, const he_handle *lts,
+                              const he_handle *out0, const he_handle *out1) {
+    static const char *who = "he_lintrans_evaluate_many";
+    GET(ev, Evaluator, hev, T_EVAL);
+    std::shared_ptr<GaloisSet> set;  // (0: no key set -- transformations of the zero diagonal alone need none)
+    if (hset) { set = get<GaloisSet>(hset, T_GALOIS_SET); if (!set) return fail(HE_EHANDLE, "%s: bad Galois key set handle", who); }
+    BasisExtender &be = *ev->be;
+    if (n_lt < 1 || !lts || !out0 || !out1) return fail(HE_EINVAL, "%s: at least one transformation and its outputs are needed", who);
+    if (set && set->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: the key set belongs to another evaluator", who);
+    TRY(check_level(*be.Q, ct_level, who));
+    auto call = std::make_shared<LinTransCall>();
+    call->ev = ev;
+    int maxQ = 0;
+    for (int t = 0; t < n_lt; t++) {
+        std::shared_ptr<LinTrans> lt = get<LinTrans>(lts[t], T_LINTRANS);
+        if (!lt) return fail(HE_EHANDLE, "%s: bad LinearTransformation handle (transformation %d)", who, t);
+        if (lt->ev.get() != ev.get()) return fail(HE_EINVAL, "%s: transformation %d belongs to another evaluator", who, t);
+        if (t == 0) call->levelP = lt->levelP;
+        else if (lt->levelP != call->levelP) return fail(HE_EINVAL, "%s: all linearTransformations must have the same levelP", who);
+        maxQ = std::max(maxQ, lt->levelQ);
+        LinTransJob job;
+        job.lt = lt;
+        call->jobs.push_back(std::move(job));
+    }
+    const int levelQd = call->levelQd = std::min(maxQ, ct_level), levelP = call->levelP;
+    CoReq q;
+    Operands o(q, who, be);
+    const int i0 = o.in(hin0, ct_level + 1, "in0"), i1 = o.in(hin1, ct_level + 1, "in1");
+    for (int t = 0; t < n_lt; t++) {
+        LinTransJob &job = call->jobs[(size_t)t];
+        const std::shared_ptr<Poly> p0 = o.poly(out0[t]);
+        job.levelQ = std::min({p0 ? p0->nlimbs - 1 : 0, ct_level, job.lt->levelQ});
+        const int a = o.out(p0, job.levelQ + 1, "out0"), c = o.out(out1[t], job.levelQ + 1, "out1");
+        if (n_lt == 1) { o.inplace(a, i0); o.inplace(a, i1); o.inplace(c, i0); o.inplace(c, i1); }
+    }
+    for (const LinTransJob &job : call->jobs)
+        for (size_t k = 0; k < job.lt->ptQ.size(); k++) {
+            o.in(job.lt->ptQ[k], job.lt->levelQ + 1, "diagonal (Q)", Operands::kBroadcast);
+            o.inP(job.lt->ptP[k], levelP + 1, "diagonal (P)", Operands::kBroadcast);
+        }
+    TRY(o.check());
+    const int B = o.B;
+    // the keys: every element the plans ask for, present, of the transformations' LevelP, reaching the level it is used at
+    auto key_of = [&](uint64_t gal, int level, std::shared_ptr<Evk> *k) -> int {
+        const int at = set ? set->find(reduce_gal(gal, be.Q->logN, be.type)) : -1;
+        if (at < 0) return fail(HE_EINVAL, "%s: the key set has no key for Galois element %llu", who, (unsigned long long)gal);
+        *k = set->keys[(size_t)at];
+        if ((*k)->nPk - 1 != levelP)
+            return fail(HE_EINVAL, "%s: LinearTransformation.LevelP = %d != GaloisKey[%llu].LevelP() = %d", who, levelP, (unsigned long long)gal, (*k)->nPk - 1);
+        if ((*k)->pw2) return fail(HE_EINVAL, "%s: method is unsupported for BaseTwoDecomposition != 0", who);
+        if ((*k)->nQk - 1 < level) return fail(HE_EINVAL, "%s: the key of Galois element %llu stops at level %d, %d needed", who, (unsigned long long)gal, (*k)->nQk - 1, level);
+        return HE_OK;
+    };
+    const uint64_t nth_root = (uint64_t)2 << (be.Q->logN + be.type);
+    std::set<int> babies;
+    for (const LinTransJob &job : call->jobs)
+        if (job.lt->N1 != 0) for (int i : job.lt->plan[0].babies) if (i != 0) babies.insert(i);
+    call->babies.assign(babies.begin(), babies.end());
+    for (int i : call->babies) {
+        std::shared_ptr<Evk> k;
+        const uint64_t gal = lintrans::galois_element(nth_root, i);
+        TRY(key_of(gal, levelQd, &k));
+        call->baby_keys.push_back(k); call->baby_gal.push_back(reduce_gal(gal, be.Q->logN, be.type));
+    }
+    // the scratch of the call without the group block (lintrans_run): a group may take as much again at most -- G is halved
+    // while its [G][2] QP block is larger
+    const size_t N = be.Q->N, sQP = (size_t)(levelQd + levelP + 2) * N;
+    const size_t rest = (size_t)B * ((size_t)base_rns_size(levelQd, levelP) * (be.LQ + be.LP) * N + (2 + 2 * call->babies.size()) * sQP);
+    for (LinTransJob &job : call->jobs) {
+        const LinTrans &lt = *job.lt;
+        if (lt.N1 == 0) {
+            call->any_naive = true;
+            const lintrans::Plan &p = lt.plan[0];
+            for (size_t r = 0; r < p.rotations.size(); r++) {
+                std::shared_ptr<Evk> k;
+                TRY(key_of(p.galois[r], job.levelQ, &k));
+                job.giant_keys.push_back(k); job.giant_gal.push_back(reduce_gal(p.galois[r], be.Q->logN, be.type));
+            }
+            continue;
+        }
+        call->any_bsgs = true;
+        int G = lt.group.load();
+        if (G == 0) G = lintrans_default_group();
+        while (G > 1 && (size_t)G * 2 * B * sQP > rest) G >>= 1;
+        job.gslot = lintrans_group_slot(G);
+        call->max_group = std::max(call->max_group, G);
+        for (const lintrans::Group &g : lt.plan[job.gslot].groups)
+            for (int j : g.giants) {
+                std::shared_ptr<Evk> k;
+                const uint64_t gal = j != 0 ? lintrans::galois_element(nth_root, j) : 1;
+                if (j != 0) TRY(key_of(gal, job.levelQ, &k));
+                job.giant_keys.push_back(k); job.giant_gal.push_back(reduce_gal(gal, be.Q->logN, be.type));
+            }
+        std::vector<int> nz;
+        for (int i : lt.plan[0].babies) if (i != 0) nz.push_back(i);
+        if (nz != call->babies)
+            for (int i : nz) job.slot_map.push_back((size_t)(std::lower_bound(call->babies.begin(), call->babies.end(), i) - call->babies.begin()));
+    }
+    q.op = CO_LINTRANS_EVAL; q.obj = ev.get(); q.key = set.get(); q.par[0] = ct_level; q.par[1] = n_lt;
+    for (const LinTransJob &job : call->jobs) { q.blob.push_back((uint64_t)(uintptr_t)job.lt.get()); q.blob.push_back((uint64_t)job.gslot); q.keep.push_back(job.lt); }
+    q.keep.push_back(ev);
+    if (set) q.keep.push_back(set);
+    q.run = [call](const View *v, int B) -> int { return lintrans_run(*call, v, B); };
+    q.one_by_one();  // (scratch-to-scratch launches: no entry tables)
+    return co_dispatch(*be.ctx, B, q);
+}
+int he_lintrans_evaluate(he_handle ev, he_handle set, int ct_level, he_handle in0, he_handle in1, he_handle lt, he_handle out0, he_handle out1) {
+    return he_lintrans_evaluate_many(ev, set, ct_level, in0, in1, 1, &lt, &out0, &out1);
+}
+int he_debug_lintrans_plan(uint64_t nth_root, int slots, int N1, int G, int n, const int *diag, int64_t *out, size_t cap, size_t *n_words) {
+    static const char *who = "he_debug_lintrans_plan";
+    if (!n_words || n < 0 || (n > 0 && !diag) || (cap && !out)) return fail(HE_EINVAL, "%s: null argument", who);
+    lintrans::Plan p;
+    if (!lintrans::build_plan(diag, n, slots, N1, G, nth_root, &p))
+        return fail(HE_EINVAL, "%s: slots, N1 and NthRoot must be powers of two, G in [1, %d], the diagonals reduced and distinct", who, lintrans::kMaxGroup);
+    const std::vector<int64_t> w = lintrans::plan_words(p);
+    for (size_t i = 0; i < w.size() && i < cap; i++) out[i] = w[i];
+    *n_words = w.size();
+    return HE_OK;
 }
 
 // the schedule queries of include/hering_debug.h: host only

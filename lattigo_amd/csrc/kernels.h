@@ -345,6 +345,33 @@ struct DiagMacArgs {
 };
 hipError_t launch_diag_mac(const RingDev &r, const DiagMacArgs &a, View out0, View out1, int batch, hipStream_t s);
 
+// The inner sums of a GROUP of giant steps of MultiplyByDiagMatrixBSGS in one pass over the pre-rotated ciphertexts
+// (he_lintrans_evaluate_many): per member g of the group and component k,
+//   out[g][k] = CRed(MRedLazy128(sum_i pt_{j_g + i} * ct_i[k]))      over the baby steps i of the group's union,
+// the canonical words launch_diag_mac writes for that giant step alone.  Each ct_i is loaded once per group (non-temporal) and
+// multiplied into the accumulators of every member that has diagonal j_g + i.
+// Term table (device, built once per transformation): per baby step of the group a row of `row_words` = 1 + 2 members words,
+//   row[0] = source of ct_i: 0 = the P * ct block (`pct`, the i = 0 term: skipped where pct is null, it has no P part), s > 0 =
+//            pre-rotation s - 1 of the transformation's own list, mapped through slot_map (null: identity) to a slot of `ct`;
+//   row[1 + 2 g], row[2 + 2 g] = address of the Q and of the P words of member g's diagonal (0: the member has no such term).
+// ct: [slot][2][batch] polynomials (ct_comp = words between the components, ct_slot between slots, ct_bs between entries); pct
+// and out likewise ([2][batch] and [member][2][batch]).  One launch per ring part over a grid of (N / 256, limbs, ceil(batch / BB)).
+constexpr int kDiagGroupMax = 4;
+struct DiagMacGroupArgs {
+    const uint64_t *tab;
+    int n_babies, members, row_words, part;  // part: 0 = Q words of the diagonals, 1 = P words
+    const uint64_t *slot_map;
+    const uint64_t *ct, *pct;
+    size_t ct_slot, ct_comp, ct_bs, pct_comp, pct_bs;
+    uint64_t *out;
+    size_t out_member, out_comp, out_bs;
+    uint64_t *m0[2] = {nullptr, nullptr};  // optional: member 0's two components go here instead (entry stride m0_bs[k]) -- giant
+    size_t m0_bs[2] = {0, 0};              // step j = 0 opens the outer accumulators with a copy (:425-433), which this saves
+    int nlimbs, mod0;  // limbs [0, nlimbs) of the part; mod0 = modulus record of limb 0 in the ring's table
+    double terms;      // (host, accounting) diagonals the group multiplies
+};
+hipError_t launch_diag_mac_group(const RingDev &r, const DiagMacGroupArgs &a, int batch, hipStream_t s);
+
 // Fused "forward row NTT + key multiply-accumulate" for limbs below 2^47 (double-precision path): one workgroup
 // owns (row, limb, batch entry) and loops over the beta digits; every non-own digit's row is transformed in LDS and
 // multiplied by the two key rows straight out of LDS, the own digit's row is read from the NTT-domain input, the two
@@ -671,7 +698,8 @@ enum KernelId {
     K_CI_BRIDGE_UNFOLD, K_BFV_QUANTIZE, K_CKKS_FFT, K_CKKS_FFT_PASS, K_CKKS_IFFT_QUANT, K_F64_TO_RNS, K_RNS_TO_F64,
     K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
     K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND,
-    K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_GADGET_AGGREGATE, K_RKG_ROUND_ONE, K_RKG_ROUND_TWO, K_RLK_FINALIZE, K_COUNT
+    K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_GADGET_AGGREGATE, K_RKG_ROUND_ONE, K_RKG_ROUND_TWO, K_RLK_FINALIZE,
+    K_DIAG_MAC_GROUP, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

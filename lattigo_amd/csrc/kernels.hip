@@ -79,7 +79,7 @@ const char *kernel_name(int id) {
                                          "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
                                          "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add",
                                          "rgsw_table_finish", "gadget_aggregate", "rkg_round_one", "rkg_round_two",
-                                         "rlk_finalize"};
+                                         "rlk_finalize", "diag_mac_group"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -4446,6 +4446,108 @@ hipError_t launch_diag_mac(const RingDev &r, const DiagMacArgs &a, View out0, Vi
     if (bb == 4) hipLaunchKernelGGL((diag_mac_kernel<4>), grid, block, 0, s, A);
     else if (bb == 2) hipLaunchKernelGGL((diag_mac_kernel<2>), grid, block, 0, s, A);
     else hipLaunchKernelGGL((diag_mac_kernel<1>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// the same multiply-accumulate for a group of G giant steps at once (see kernels.h): every ct_i is loaded once per group
+// ------------------------------------------------------------------------------------
+struct DiagMacGroupKArgs {
+    DiagMacGroupArgs a;
+    const ModConst *mc;
+    int N, batch;
+};
+// The 2 G BB 128-bit accumulators live in arrays whose every index is a constant after unrolling (no runtime-indexed per-thread
+// array: nothing goes to scratch).  Which members have a term at baby step i is read from the term table through the scalar
+// cache: the test is uniform over the block.
+template <int G, int BB>
+__global__ void __launch_bounds__(256) diag_mac_group_kernel(const DiagMacGroupKArgs A) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= A.N) return;
+    const int l = blockIdx.y;
+    const int b0 = blockIdx.z * BB;
+    const ModConst m = A.mc[A.a.mod0 + l];
+    const uint64_t q = m.q;
+    uint64_t hi0[G][BB], lo0[G][BB], hi1[G][BB], lo1[G][BB];
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int b = 0; b < BB; b++) { hi0[g][b] = lo0[g][b] = hi1[g][b] = lo1[g][b] = 0; }
+    const size_t lo = (size_t)l * A.N + x;
+    for (int s = 0; s < A.a.n_babies; s++) {
+        const uint64_t *row = A.a.tab + (size_t)s * A.a.row_words;
+        const uint64_t src = ldc(row, 0);
+        const uint64_t *p0;
+        size_t comp, bs;
+        if (src == 0) {
+            if (A.a.pct == nullptr) continue;  // (the i = 0 term has no P part)
+            p0 = A.a.pct + lo; comp = A.a.pct_comp; bs = A.a.pct_bs;
+        } else {
+            const size_t slot = A.a.slot_map ? (size_t)ldc(A.a.slot_map, (size_t)(src - 1)) : (size_t)(src - 1);
+            p0 = A.a.ct + slot * A.a.ct_slot + lo; comp = A.a.ct_comp; bs = A.a.ct_bs;
+        }
+        uint64_t v0[BB], v1[BB];
+#pragma unroll
+        for (int b = 0; b < BB; b++) {
+            const bool in = b0 + b < A.batch;
+            v0[b] = in ? ldnt(&p0[(size_t)(b0 + b) * bs]) : 0;
+            v1[b] = in ? ldnt(&p0[comp + (size_t)(b0 + b) * bs]) : 0;
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (g >= A.a.members) continue;
+            const uint64_t pa = ldc(row, (size_t)(1 + 2 * g + A.a.part));
+            if (pa == 0) continue;  // block-uniform: member g has no diagonal j_g + i
+            const uint64_t w = reinterpret_cast<const uint64_t *>((uintptr_t)pa)[lo];
+#pragma unroll
+            for (int b = 0; b < BB; b++) {
+                uint64_t ph, pl;
+                mul64wide(v0[b], w, ph, pl);
+                lo0[g][b] += pl; hi0[g][b] += ph + (lo0[g][b] < pl);
+                hi0[g][b] = hi0[g][b] >= q ? hi0[g][b] - q : hi0[g][b];
+                mul64wide(v1[b], w, ph, pl);
+                lo1[g][b] += pl; hi1[g][b] += ph + (lo1[g][b] < pl);
+                hi1[g][b] = hi1[g][b] >= q ? hi1[g][b] - q : hi1[g][b];
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        if (g >= A.a.members) continue;
+#pragma unroll
+        for (int b = 0; b < BB; b++) {
+            if (b0 + b < A.batch) {
+                uint64_t *o0 = A.a.out + (size_t)g * A.a.out_member + (size_t)(b0 + b) * A.a.out_bs + lo, *o1 = o0 + A.a.out_comp;
+                if (g == 0 && A.a.m0[0] != nullptr) {
+                    o0 = A.a.m0[0] + (size_t)(b0 + b) * A.a.m0_bs[0] + lo;
+                    o1 = A.a.m0[1] + (size_t)(b0 + b) * A.a.m0_bs[1] + lo;
+                }
+                *o0 = cred(mred128_lazy(hi0[g][b], lo0[g][b], q, m.qinv), q);
+                *o1 = cred(mred128_lazy(hi1[g][b], lo1[g][b], q, m.qinv), q);
+            }
+        }
+    }
+}
+// the batch entries per thread of an instantiation: the largest of 4, 2, 1 the batch fills, G = 4 at most 2 (tools/kres.py: no
+// instantiation spills or uses scratch, but the 64 accumulator words of <4, 4> make 160 VGPRs, three waves per SIMD, where
+// <4, 2> has 104 and four -- a kernel that waits on HBM wants the waves; NOTES.md has the table)
+hipError_t launch_diag_mac_group(const RingDev &r, const DiagMacGroupArgs &a, int batch, hipStream_t s) {
+    if (a.nlimbs <= 0 || batch <= 0 || a.members <= 0) return hipSuccess;
+    if (a.members > kDiagGroupMax || a.row_words != 1 + 2 * a.members || !a.tab || !a.out || (a.m0[0] != nullptr) != (a.m0[1] != nullptr)) return hipErrorInvalidValue;
+    DiagMacGroupKArgs A{};
+    A.a = a; A.mc = r.mc; A.N = r.N; A.batch = batch;
+    const int G = a.members > 2 ? 4 : a.members;
+    int bb = batch >= 4 ? 4 : (batch >= 2 ? 2 : 1);
+    if (G == 4 && bb == 4) bb = 2;
+    dim3 grid((unsigned)((r.N + 255) / 256), a.nlimbs, (batch + bb - 1) / bb), block(256);
+    // per baby step both ciphertext components per entry, per term one diagonal shared by the batch, the 2 accumulators per member out
+    const double limbs = 2.0 * a.n_babies * batch + a.terms + 2.0 * a.members * batch;
+    ProfScope ps(K_DIAG_MAC_GROUP, s, limbs * a.nlimbs * (double)r.N * 8.0);
+#define HE_DMG(GG, BBB) hipLaunchKernelGGL((diag_mac_group_kernel<GG, BBB>), grid, block, 0, s, A)
+    if (G == 1) { if (bb == 4) HE_DMG(1, 4); else if (bb == 2) HE_DMG(1, 2); else HE_DMG(1, 1); }
+    else if (G == 2) { if (bb == 4) HE_DMG(2, 4); else if (bb == 2) HE_DMG(2, 2); else HE_DMG(2, 1); }
+    else { if (bb == 2) HE_DMG(4, 2); else HE_DMG(4, 1); }
+#undef HE_DMG
     return hipGetLastError();
 }
 

@@ -31,6 +31,7 @@
 #include "../../include/hering_blindrot.h"
 #include "../../include/hering_bridge.h"
 #include "../../include/hering_bfv.h"
+#include "../../include/hering_lintrans.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -44,7 +45,8 @@ enum Fn : uint64_t {
     F_RING_XPOW2, F_RING_SPLIT, F_RING_MERGE, F_RP_SPLIT, F_RP_MERGE, F_RP_EXPAND_STEP, F_RP_PACK_PRE, F_RP_PACK_POST,
     F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_AUTO_CT_SELECT, F_BLIND_ROTATE_CORE,
     F_BRIDGE_UNFOLD, F_BRIDGE_FOLD, F_COMPLEX_TO_REAL, F_REAL_TO_COMPLEX,
-    F_BFV_MUL_RELIN, F_BFV_QUANTIZE, F_COUNT
+    F_BFV_MUL_RELIN, F_BFV_QUANTIZE,
+    F_LINTRANS_EVALUATE, F_LINTRANS_EVALUATE_MANY, F_COUNT
 };
 static_assert(F_COUNT <= 128, "the per-function profile has 128 slots");
 struct Arg {
@@ -196,6 +198,8 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
         case F_REAL_TO_COMPLEX: return he_real_to_complex(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6));
         case F_BFV_MUL_RELIN: return he_bfv_mul_relin(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6), H(7), H(8), H(9));
         case F_BFV_QUANTIZE: return he_bfv_quantize(H(0), (int)I(1), H(2), H(3), H(4));
+        case F_LINTRANS_EVALUATE: return he_lintrans_evaluate(H(0), H(1), (int)I(2), H(3), H(4), H(5), H(6), H(7));
+        case F_LINTRANS_EVALUATE_MANY: return he_lintrans_evaluate_many(H(0), H(1), (int)I(2), H(3), H(4), (int)I(5), HA(6), HA(7), HA(8));
         default: return HE_EINVAL;
     }
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The check of go/hering/*.go that is possible without a Go toolchain: every `C.he_*(...)` call names a function
-declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h, hering_bgv_encoder.h, hering_sampler.h, hering_encryptor.h, hering_keygen.h, hering_rgsw_encryptor.h, hering_multiparty.h), passes as many arguments as the declaration has parameters, and -- round 4 --
+declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h, hering_bgv_encoder.h, hering_sampler.h, hering_encryptor.h, hering_keygen.h, hering_rgsw_encryptor.h, hering_multiparty.h, hering_lintrans.h), passes as many arguments as the declaration has parameters, and -- round 4 --
 every argument has the KIND the parameter wants (int / uint64_t / he_handle / he_handle* / uint64_t* / int*), judged from the
 shape of the Go expression (`C.int(..)`, `C.uint64_t(..)`, `x.h`, `&x.h`, `(*C.uint64_t)(unsafe.Pointer(..))`, identifiers whose
 declaration in the file names a Handle or a C pointer type); every `C.HE_*` constant exists in the header's enums.  Also
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_decls():
-    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h", "hering_bgv_encoder.h", "hering_sampler.h", "hering_encryptor.h", "hering_keygen.h", "hering_rgsw_encryptor.h", "hering_multiparty.h"))
+    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h", "hering_bgv_encoder.h", "hering_sampler.h", "hering_encryptor.h", "hering_keygen.h", "hering_rgsw_encryptor.h", "hering_multiparty.h", "hering_lintrans.h"))
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls, kinds = {}, {}
     for m in re.finditer(r"\b(?:int|const char \*)\s*(he_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
@@ -131,6 +131,8 @@ SAMPLERS = {"UniformSampler": ["Read", "ReadAndAdd", "ReadQP", "ReadAndAddQP", "
 # rlwe.KeyGenerator (go/hering/keygen.go)
 KEYGEN = ["GenSecretKey", "GenSecretKeyWithHammingWeight", "GenPublicKey", "GenRelinearizationKey", "GenGaloisKey", "GenGaloisKeys",
           "GenEvaluationKey", "NewEvaluationKey"]                                    # core/rlwe/keygenerator.go:37-285
+# lintrans.Evaluator (go/hering/lintrans.go)
+LINTRANS = ["EvaluateMany", "Evaluate"]                                               # circuits/common/lintrans/lintrans_evaluator.go:27,122
 SCHEMES = ["Add", "AddNew", "Sub", "SubNew", "Mul", "MulNew", "MulRelin", "MulRelinNew", "MulThenAdd", "Relinearize",
            "Rescale", "GetRLWEParameters"]                                            # schemes/schemes.go:14-28
 
@@ -212,6 +214,10 @@ def main():
     for m in KEYGEN:
         if m not in kg_methods:
             errors.append(f"go/hering: method {m} (rlwe.KeyGenerator) is not defined")
+    lt_methods = set(re.findall(r"func \(\w+ \*LinTransEvaluator\) (\w+)\(", src))
+    for m in LINTRANS:
+        if m not in lt_methods:
+            errors.append(f"go/hering: method {m} (lintrans.Evaluator) is not defined")
     print(f"{len(files)} Go files, {ncalls} C.he_* calls to {len(used)} of {len(decls)} declared entry points, {nchecked} of {nargs_total} "
           f"arguments kind-checked; {len(PROVIDER)} EvaluatorProvider + {len(SCHEMES)} schemes.Evaluator methods present; "
           f"rlwe.Evaluator also: {', '.join(m for m in EXTRA if m in methods)}; "
@@ -223,7 +229,8 @@ def main():
           f"ckks.Encoder: {', '.join(m for m in ENCODER if m in enc_methods)}; "
           f"bgv.Encoder: {', '.join(m for m in BGV_ENCODER if m in bgv_enc_methods)}; "
           f"ring samplers: {', '.join(SAMPLERS)}; "
-          f"rlwe.KeyGenerator: {', '.join(m for m in KEYGEN if m in kg_methods)}"
+          f"rlwe.KeyGenerator: {', '.join(m for m in KEYGEN if m in kg_methods)}; "
+          f"lintrans.Evaluator: {', '.join(m for m in LINTRANS if m in lt_methods)}"
           if not errors else "\n".join(errors))
     return 1 if errors else 0
 
