@@ -43,6 +43,7 @@
 #include "hering_rgsw_encryptor.h"
 #include "hering_multiparty.h"
 #include "hering_lintrans.h"
+#include "hering_polyeval.h"
 
 namespace hering {
 
@@ -1796,6 +1797,158 @@ public:
     }
 };
 }  // namespace lintrans
+
+// ---- polynomial evaluation (circuits/common/polynomial; hering_polyeval.h), NTT domain ---------------------------------------
+namespace polyeval {
+// bignum.OptimalSplit (utils/bignum/polynomial.go:14)
+inline int OptimalSplit(int logDegree) {
+    int s = 0;
+    check(he_polyeval_optimal_split(logDegree, &s));
+    return s;
+}
+// SplitDegree (power_basis.go:31)
+inline std::pair<int, int> SplitDegree(int n) {
+    int a = 0, b = 0;
+    check(he_polyeval_split_degree(n, &a, &b));
+    return {a, b};
+}
+// ceil(log2 degree); throws the reference's error where `level` is below it (polynomial_evaluator.go:62-65)
+inline int Depth(int degree, int level) {
+    int d = 0;
+    check(he_polyeval_depth(degree, level, &d));
+    return d;
+}
+// one power a basis holds: X^n at a level, as a ciphertext of degree 1 or 2
+struct PowerInfo { int n, level, degree; };
+struct LeafInfo { int degree, level, new_degree, ct_degree; uint32_t present; };
+struct Step { int op, dst, level, degree, a, b; };
+// the library's structure of one evaluation (he_debug_polyeval_plan)
+struct Plan {
+    int log_split = 0, depth = 0, out_level = 0;
+    std::vector<LeafInfo> leaves;
+    std::vector<Step> steps;
+    Plan(int degree, int basis, bool even, bool odd, bool lazy, const std::vector<PowerInfo> &powers, bool copyInput) {
+        std::vector<int> flat;
+        for (const PowerInfo &p : powers) { flat.push_back(p.n); flat.push_back(p.level); flat.push_back(p.degree); }
+        size_t n = 0;
+        check(he_polyeval_plan(degree, basis, even, odd, lazy, copyInput, (int)powers.size(), flat.data(), nullptr, 0, &n));
+        std::vector<int64_t> w(n);
+        check(he_polyeval_plan(degree, basis, even, odd, lazy, copyInput, (int)powers.size(), flat.data(), w.data(), n, &n));
+        log_split = (int)w[0]; depth = (int)w[1]; out_level = (int)w[4];
+        size_t at = 5;
+        for (int64_t i = 0; i < w[2]; i++, at += 5) leaves.push_back({(int)w[at], (int)w[at + 1], (int)w[at + 2], (int)w[at + 3], (uint32_t)w[at + 4]});
+        for (int64_t i = 0; i < w[3]; i++, at += 6) steps.push_back({(int)w[at], (int)w[at + 1], (int)w[at + 2], (int)w[at + 3], (int)w[at + 4], (int)w[at + 5]});
+    }
+};
+// BGV planning of the scalar words (circuits/bgv/polynomial): residues mod t, centred, the op0.Scale != opOut.Scale ratio of
+// MulThenAdd (schemes/bgv/evaluator.go:1108-1140) and the constant of Add (:144-172) times T^-1 mod Q_level.  tInvModQ[l][i] =
+// (T^-1 mod q_0 ... q_l) mod q_i, which the caller computes with its big integers.
+struct BGVWords {
+    uint64_t t;
+    std::vector<uint64_t> Q;
+    static uint64_t mulmod(uint64_t a, uint64_t b, uint64_t m) { return (uint64_t)((unsigned __int128)a * b % m); }
+    static uint64_t powmod(uint64_t a, uint64_t e, uint64_t m) {
+        uint64_t r = 1 % m;
+        for (a %= m; e; e >>= 1, a = mulmod(a, a, m))
+            if (e & 1) r = mulmod(r, a, m);
+        return r;
+    }
+    // the residue of the centred representative of v mod t, modulo q
+    uint64_t centred(uint64_t v, uint64_t q) const {
+        v %= t;
+        return v > (t >> 1) ? (q - (t - v) % q) % q : v % q;
+    }
+    // MulThenAdd(X, c, out): the words of c at (X.Scale, out.Scale)
+    std::vector<uint64_t> term(int level, uint64_t c, uint64_t xScale, uint64_t outScale) const {
+        uint64_t v = c % t;
+        if (xScale != outScale) v = mulmod(v, mulmod(powmod(xScale, t - 2, t), outScale, t), t);
+        std::vector<uint64_t> w;
+        for (int i = 0; i <= level; i++) w.push_back(centred(v, Q[(size_t)i]));
+        return w;
+    }
+    // Add(out, c): the words of c at out.Scale
+    std::vector<uint64_t> constant(int level, uint64_t c, uint64_t outScale, const std::vector<uint64_t> &tInvModQ) const {
+        const uint64_t v = mulmod(c % t, outScale % t, t);
+        std::vector<uint64_t> w;
+        for (int i = 0; i <= level; i++) w.push_back(mulmod(centred(v, Q[(size_t)i]), tInvModQ[(size_t)i], Q[(size_t)i]));
+        return w;
+    }
+};
+// the caller's numbers for the Chebyshev steps of a plan, in its order (hering_polyeval.h): kind 0 = Add(x, -1), 1 / 2 = Sub with the
+// second / first operand times the integer ratio first, 3 = Sub as it is; `words` residues per entry in s0 and s1
+struct ChebyshevWords {
+    std::vector<int> kind;
+    std::vector<uint64_t> s0, s1;
+    int words = 0;
+};
+// polynomial.PowerBasis (power_basis.go:17) on the device: NewPowerBasis copies the ciphertext into X^1
+class PowerBasis {
+    detail::Ref r_;
+
+public:
+    PowerBasis(const hering::Evaluator &ev, int basis, int level, const Ciphertext &ct) {
+        he_handle h = 0;
+        check(he_polyeval_basis_create(ev.h(), basis, level, ct.Value.at(0).h(), ct.Value.at(1).h(), &h));
+        r_ = detail::own(h, he_polyeval_basis_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    // the powers the basis holds
+    std::vector<PowerInfo> Powers() const {
+        size_t n = 0;
+        check(he_polyeval_basis_powers(r_->h, nullptr, 0, &n));
+        std::vector<int> w(3 * n + 3);
+        check(he_polyeval_basis_powers(r_->h, w.data(), n, &n));
+        std::vector<PowerInfo> out;
+        for (size_t i = 0; i < n; i++) out.push_back({w[3 * i], w[3 * i + 1], w[3 * i + 2]});
+        return out;
+    }
+    // GenPower (power_basis.go:76): scheme 0 CKKS, 1 BGV with plaintext modulus t; rlk may be null where nothing is relinearized
+    void GenPower(int scheme, uint64_t t, const EvaluationKey *rlk, int n, bool lazy, const ChebyshevWords &cw = {}) const {
+        check(he_polyeval_gen_power(r_->h, scheme, t, rlk ? rlk->h() : 0, n, lazy, (int)cw.kind.size(), cw.kind.data(), cw.s0.data(), cw.s1.data(), cw.words));
+    }
+};
+// A polynomial planned for one basis, its scalar words uploaded once (he_polyeval_poly_create): s0 / s1 hold, per baby step in
+// the library's order and per coefficient k = 0 .. degree, 1 + level(X^1) residues (BGV: s1 = s0; CKKS: the planned pairs)
+class Polynomial {
+    detail::Ref r_;
+
+public:
+    Polynomial(const Ring &ring, int degree, int basis, bool even, bool odd, bool lazy, const std::vector<PowerInfo> &powers,
+               const std::vector<int> &leafDegree, const std::vector<int> &leafLevel, const std::vector<uint64_t> &s0, const std::vector<uint64_t> &s1) {
+        if (leafDegree.size() != leafLevel.size()) throw std::invalid_argument("Polynomial: one level per baby step");
+        std::vector<int> flat;
+        for (const PowerInfo &p : powers) { flat.push_back(p.n); flat.push_back(p.level); flat.push_back(p.degree); }
+        he_handle h = 0;
+        check(he_polyeval_poly_create(ring.h(), degree, basis, even, odd, lazy, (int)powers.size(), flat.data(), (int)leafDegree.size(),
+                                      leafDegree.data(), leafLevel.data(), s0.data(), s1.data(), &h));
+        r_ = detail::own(h, he_polyeval_poly_destroy);
+    }
+    he_handle h() const { return r_->h; }
+    // baby steps per launch of the leaf-group kernel: 0 (the library's default), 1, 2 or 4
+    void SetGroup(int G) const { check(he_polyeval_poly_set_group(r_->h, G)); }
+    // EvaluatePolynomialVectorFromPowerBasis (polynomial_evaluator.go:254) for the baby steps [first, first + out.size()): X[k - 1]
+    // = the power X^k (an empty ciphertext where the basis lacks it), out[g] = the result of baby step first + g
+    void EvaluatePolynomialFromPowerBasis(int first, const std::vector<Ciphertext> &X, std::vector<Ciphertext> &out) const {
+        std::vector<he_handle> x(3 * X.size() + 1, 0), o(3 * out.size() + 1, 0);
+        for (size_t k = 0; k < X.size(); k++)
+            for (size_t c = 0; c < X[k].Value.size() && c < 3; c++) x[3 * k + c] = X[k].Value[c].h();
+        for (size_t g = 0; g < out.size(); g++)
+            for (size_t c = 0; c < out[g].Value.size() && c < 3; c++) o[3 * g + c] = out[g].Value[c].h();
+        check(he_polyeval_leaves(r_->h, first, (int)out.size(), (int)X.size(), x.data(), o.data()));
+    }
+    // Evaluator.Evaluate (polynomial_evaluator.go:33) as ONE native call: ct at `level` is left untouched, opOut receives the result
+    void Evaluate(const hering::Evaluator &ev, int scheme, uint64_t t, const EvaluationKey *rlk, int level, const Ciphertext &ct,
+                  const ChebyshevWords &cw, Ciphertext &opOut) const {
+        check(he_polyeval_evaluate(ev.h(), r_->h, scheme, t, rlk ? rlk->h() : 0, level, ct.Value.at(0).h(), ct.Value.at(1).h(), (int)cw.kind.size(),
+                                   cw.kind.data(), cw.s0.data(), cw.s1.data(), cw.words, opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+    }
+    // Evaluator.EvaluateFromPowerBasis (:47) as ONE native call on the basis the polynomial was planned for
+    void EvaluateFromPowerBasis(const PowerBasis &pb, int scheme, uint64_t t, const EvaluationKey *rlk, const ChebyshevWords &cw, Ciphertext &opOut) const {
+        check(he_polyeval_evaluate_from_power_basis(pb.h(), r_->h, scheme, t, rlk ? rlk->h() : 0, (int)cw.kind.size(), cw.kind.data(), cw.s0.data(),
+                                                    cw.s1.data(), cw.words, opOut.Value.at(0).h(), opOut.Value.at(1).h()));
+    }
+};
+}  // namespace polyeval
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

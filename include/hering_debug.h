@@ -133,6 +133,18 @@ int he_debug_blindrot_rounds(int logN, const uint64_t *a, int batch, int n_lwe, 
  * rotations).  *n_words receives the length; at most cap words are written. */
 int he_debug_lintrans_plan(uint64_t nth_root, int slots, int N1, int G, int n, const int *diag, int64_t *out, size_t cap, size_t *n_words);
 
+/* The structure of a polynomial evaluation (hering_polyeval.h), computed on the host (csrc/polyeval_plan.h; no device needed),
+ * for a polynomial of `degree` in `basis` with the reference's IsEven / IsOdd / Lazy on a basis that holds the n_powers powers
+ * powers[3 i + {0, 1, 2}] = (n, level, ciphertext degree); copy_input: Evaluate (X^1 is copied first) and not
+ * EvaluateFromPowerBasis.  Words: log_split, depth, n_leaves, n_steps, the level of the result; per baby step (degree, level,
+ * the ciphertext degree it is allocated with, the ciphertext degree of its result, bit k = it has term k); per step, in the
+ * order of the reference's primitive calls, (op, destination, level and ciphertext degree of the destination afterwards, the
+ * two sources): a power is named by n >= 1 and baby step i by -1 - i; op: 0 CopyNew, 1 Relinearize, 2 Rescale, 3 MulNew,
+ * 4 MulRelinNew, 5 Add(x, x), 6 Add(x, -1), 7 Sub, 8 NewCiphertext, 9 Add(res, c_0), 10 MulThenAdd(X[a], c_a, res), 11 Mul,
+ * 12 Add.  An evaluation the reference refuses (the level below the depth, no X^1) is HE_EINVAL with its message. */
+int he_debug_polyeval_plan(int degree, int basis, int even, int odd, int lazy, int copy_input, int n_powers, const int *powers,
+                           int64_t *out, size_t cap, size_t *n_words);
+
 #ifdef __cplusplus
 }
 #endif

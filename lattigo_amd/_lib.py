@@ -14,7 +14,7 @@ _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), o
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
          os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h"),
          os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h"), os.path.join(_INC, "hering_multiparty.h"),
-         os.path.join(_INC, "hering_lintrans.h")]
+         os.path.join(_INC, "hering_lintrans.h"), os.path.join(_INC, "hering_polyeval.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -184,6 +184,18 @@ def _declare(L):
         "he_lintrans_create": [H, i, i, i, i, i, ip, HP, HP, HP], "he_lintrans_destroy": [H], "he_lintrans_set_group": [H, i],
         "he_lintrans_evaluate_many": [H, H, i, H, H, i, HP, HP, HP], "he_lintrans_evaluate": [H, H, i, H, H, H, H, H],
         "he_debug_lintrans_plan": [C.c_uint64, i, i, i, i, ip, C.POINTER(C.c_int64), sz, C.POINTER(sz)],
+        "he_polyeval_optimal_split": [i, ip], "he_polyeval_split_degree": [i, ip, ip], "he_polyeval_depth": [i, i, ip],
+        "he_polyeval_check_leaves": [i, i, i, i, i, i, ip, i, ip, ip],
+        "he_polyeval_poly_create": [H, i, i, i, i, i, i, ip, i, ip, ip, u64p, u64p, HP], "he_polyeval_poly_destroy": [H],
+        "he_polyeval_poly_set_group": [H, i], "he_polyeval_leaves": [H, i, i, i, HP, HP],
+        "he_debug_polyeval_plan": [i, i, i, i, i, i, i, ip, C.POINTER(C.c_int64), sz, C.POINTER(sz)],
+        "he_polyeval_plan": [i, i, i, i, i, i, i, ip, C.POINTER(C.c_int64), sz, C.POINTER(sz)],
+        "he_polyeval_gen_power_plan": [i, i, i, i, ip, C.POINTER(C.c_int64), sz, C.POINTER(sz)],
+        "he_polyeval_basis_create": [H, i, i, H, H, HP], "he_polyeval_basis_destroy": [H],
+        "he_polyeval_basis_powers": [H, ip, sz, C.POINTER(sz)], "he_polyeval_basis_power": [H, i, HP],
+        "he_polyeval_gen_power": [H, i, C.c_uint64, H, i, i, i, ip, u64p, u64p, i],
+        "he_polyeval_evaluate_from_power_basis": [H, H, i, C.c_uint64, H, i, ip, u64p, u64p, i, H, H],
+        "he_polyeval_evaluate": [H, H, i, C.c_uint64, H, i, H, H, i, ip, u64p, u64p, i, H, H],
         "he_ckks_mul_relin": [H, i, H, H, H, H, H, H, H, H],
         "he_bgv_mul_relin": [H, i, C.c_uint64, H, H, H, H, H, H, H, H],
         "he_probe_modmul": [H, i, C.POINTER(C.c_double)], "he_probe_modmul_f64": [H, i, C.POINTER(C.c_double)],
@@ -292,6 +304,12 @@ _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start
                  # time, is left out like a ring's
                  "he_lintrans_bsgs_index", "he_lintrans_find_best_bsgs_ratio", "he_lintrans_galois_elements", "he_debug_lintrans_plan",
                  "he_lintrans_destroy",
+                 # include/hering_polyeval.h, the same way: the integer logic runs on the host; a Polynomial carries the caller's
+                 # scalar words into a table, as an upload does (its creation fails trace_end), and is released like a ring;
+                 # he_polyeval_leaves has no replay number: a recording that holds it fails trace_end
+                 "he_polyeval_optimal_split", "he_polyeval_split_degree", "he_polyeval_depth", "he_polyeval_check_leaves", "he_debug_polyeval_plan",
+                 "he_polyeval_poly_set_group", "he_polyeval_poly_destroy", "he_polyeval_plan", "he_polyeval_gen_power_plan", "he_polyeval_basis_powers",
+                 "he_polyeval_basis_power", "he_polyeval_basis_destroy",
                  # include/hering_ckks_encoder.h: decode, the transforms and the getters read; an encode carries host data into a
                  # polynomial, as an upload does, and is left out on purpose (it fails trace_end)
                  "he_ckks_decode", "he_ckks_fft", "he_ckks_ifft", "he_ckks_roots_host", "he_ckks_encoder_roots", "he_ckks_encoder_info",

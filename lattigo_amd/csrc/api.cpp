@@ -56,11 +56,13 @@
 #include "../../include/hering_rgsw.h"
 #include "../../include/hering_blindrot.h"
 #include "../../include/hering_lintrans.h"
+#include "../../include/hering_polyeval.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "ks_route.h"
 #include "blindrot_plan.h"
 #include "lintrans_plan.h"
+#include "polyeval_plan.h"
 
 using namespace he;
 
@@ -87,7 +89,7 @@ int fail(int code, const char *fmt, ...) {
         if (_r != HE_OK) return _r; \
     } while (0)
 
-enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR, T_KEYGEN, T_LINTRANS };
+enum ObjType { T_CTX = 1, T_RING, T_POLY, T_INDEX, T_BE, T_EVAL, T_EVK, T_DECOMP, T_GRAPH, T_COMM, T_RGSW_SET, T_GALOIS_SET, T_BFV, T_CKKS_ENC, T_BGV_ENC, T_PRNG, T_ENCRYPTOR, T_DECRYPTOR, T_KEYGEN, T_LINTRANS, T_POLYEVAL, T_POLYBASIS };
 
 struct Obj {
     ObjType type;
@@ -116,7 +118,7 @@ enum CoOp {
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
     CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT,
-    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE, CO_LINTRANS_EVAL
+    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE, CO_LINTRANS_EVAL, CO_POLY_LEAVES
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -8845,6 +8847,631 @@ int he_debug_lintrans_plan(uint64_t nth_root, int slots, int N1, int G, int n, c
     if (!lintrans::build_plan(diag, n, slots, N1, G, nth_root, &p))
         return fail(HE_EINVAL, "%s: slots, N1 and NthRoot must be powers of two, G in [1, %d], the diagonals reduced and distinct", who, lintrans::kMaxGroup);
     const std::vector<int64_t> w = lintrans::plan_words(p);
+    for (size_t i = 0; i < w.size() && i < cap; i++) out[i] = w[i];
+    *n_words = w.size();
+    return HE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// polynomial.Evaluator (include/hering_polyeval.h; circuits/common/polynomial): the integer logic on the host
+// (csrc/polyeval_plan.h), the Polynomial handle with the caller's scalar words, and the baby steps through the leaf-group kernel
+// ---------------------------------------------------------------------------------------
+int he_polyeval_optimal_split(int log_degree, int *log_split) {
+    if (!log_split || log_degree < 1 || log_degree > 30) return fail(HE_EINVAL, "he_polyeval_optimal_split: log_degree must be in [1, 30]");
+    *log_split = polyeval::optimal_split(log_degree);
+    return HE_OK;
+}
+int he_polyeval_split_degree(int n, int *a, int *b) {
+    if (!a || !b) return fail(HE_EINVAL, "he_polyeval_split_degree: null output");
+    if (n <= 0) return fail(HE_EINVAL, "invalid n: n=%d should be greater than zero", n);
+    polyeval::split_degree(n, a, b);
+    return HE_OK;
+}
+int he_polyeval_depth(int degree, int level, int *depth) {
+    if (degree < 1) return fail(HE_EINVAL, "he_polyeval_depth: the polynomial must have degree >= 1");
+    const int d = polyeval::depth_of(degree);
+    if (depth) *depth = d;
+    if (level < d) return fail(HE_EINVAL, "%d levels < %d log(d) -> cannot evaluate poly", level, d);
+    return HE_OK;
+}
+
+namespace {
+constexpr int kPolyevalDefaultGroup = 4;
+struct PolyevalPoly : Obj {
+    std::shared_ptr<Ring> ring;
+    polyeval::Plan plan;
+    int L = 0;                     // limb stride of the scalar table: 1 + the level of X^1
+    bool even = false, odd = false;
+    std::map<int, polyeval::Power> planned_for;  // the basis the polynomial was planned for
+    std::vector<uint32_t> off;     // per leaf: where its scalars start in the table
+    std::atomic<int> group{0};     // he_polyeval_poly_set_group (0: the default)
+    uint64_t *d_tab = nullptr;
+    PolyevalPoly() : Obj(T_POLYEVAL) {}
+    ~PolyevalPoly() override {
+        if (!d_tab) return;
+        hipSetDevice(ring->ctx->dev);
+        hipStreamSynchronize(ring->ctx->stream);
+        hipFree(d_tab);
+    }
+};
+int polyeval_default_group() {
+    static const int g = [] {
+        const char *s = getenv("HERING_POLYEVAL_GROUP");
+        const int v = s ? atoi(s) : 0;
+        return (v == 1 || v == 2 || v == 4) ? v : kPolyevalDefaultGroup;
+    }();
+    return g;
+}
+int polyeval_present(const char *who, int n_powers, const int *powers, std::map<int, polyeval::Power> *out) {
+    if (n_powers < 1 || !powers) return fail(HE_EINVAL, "%s: the powers the basis holds are needed (X^1 at least)", who);
+    for (int i = 0; i < n_powers; i++) {
+        const int n = powers[3 * i], level = powers[3 * i + 1], deg = powers[3 * i + 2];
+        if (n < 1 || level < 0 || deg < 1 || deg > 2) return fail(HE_EINVAL, "%s: power %d: n >= 1, level >= 0 and degree 1 or 2 expected", who, i);
+        if (!out->emplace(n, polyeval::Power{level, deg}).second) return fail(HE_EINVAL, "%s: X^{%d} is listed twice", who, n);
+    }
+    if (!out->count(1)) return fail(HE_EINVAL, "%s: cannot EvaluateFromPowerBasis: X^{1} is nil", who);
+    return HE_OK;
+}
+// the caller's baby steps against the library's decomposition
+int polyeval_check_leaves(const char *who, const polyeval::Plan &plan, int n_leaves, const int *leaf_degree, const int *leaf_level) {
+    if (!plan.error.empty()) return fail(HE_EINVAL, "%s", plan.error.c_str());
+    if (!leaf_degree || !leaf_level) return fail(HE_EINVAL, "%s: null argument", who);
+    if (n_leaves != (int)plan.leaves.size()) return fail(HE_EINVAL, "%s: %d baby steps given, the decomposition has %d", who, n_leaves, (int)plan.leaves.size());
+    for (int i = 0; i < n_leaves; i++) {
+        const polyeval::Leaf &f = plan.leaves[(size_t)i];
+        if (leaf_degree[i] != f.degree) return fail(HE_EINVAL, "%s: baby step %d has degree %d, the decomposition says %d", who, i, leaf_degree[i], f.degree);
+        if (leaf_level[i] != f.level) return fail(HE_EINVAL, "%s: baby step %d is at level %d, the decomposition says %d", who, i, leaf_level[i], f.level);
+    }
+    return HE_OK;
+}
+}  // namespace
+
+int he_polyeval_check_leaves(int degree, int basis, int even, int odd, int lazy, int n_powers, const int *powers, int n_leaves,
+                             const int *leaf_degree, const int *leaf_level) {
+    static const char *who = "he_polyeval_check_leaves";
+    std::map<int, polyeval::Power> present;
+    TRY(polyeval_present(who, n_powers, powers, &present));
+    return polyeval_check_leaves(who, polyeval::build_plan(degree, basis, even != 0, odd != 0, lazy != 0, present, false), n_leaves, leaf_degree, leaf_level);
+}
+int he_polyeval_poly_create(he_handle hring, int degree, int basis, int even, int odd, int lazy, int n_powers, const int *powers,
+                            int n_leaves, const int *leaf_degree, const int *leaf_level, const uint64_t *s0, const uint64_t *s1,
+                            he_handle *out) {
+    static const char *who = "he_polyeval_poly_create";
+    GET(r, Ring, hring, T_RING);
+    if (!out || !leaf_degree || !leaf_level || !s0 || !s1) return fail(HE_EINVAL, "%s: null argument", who);
+    std::map<int, polyeval::Power> present;
+    TRY(polyeval_present(who, n_powers, powers, &present));
+    if (present[1].level >= r->nmod()) return fail(HE_EINVAL, "%s: X^1 at level %d on a ring of %d moduli", who, present[1].level, r->nmod());
+    auto p = std::make_shared<PolyevalPoly>();
+    p->ring = r; p->even = even != 0; p->odd = odd != 0; p->planned_for = present;
+    p->plan = polyeval::build_plan(degree, basis, even != 0, odd != 0, lazy != 0, present, false);
+    const std::vector<polyeval::Leaf> &leaves = p->plan.leaves;
+    TRY(polyeval_check_leaves(who, p->plan, n_leaves, leaf_degree, leaf_level));
+    const int L = p->L = present[1].level + 1;
+    std::vector<uint64_t> tab;
+    size_t at = 0;  // scalars consumed from s0 / s1
+    for (int i = 0; i < n_leaves; i++) {
+        const polyeval::Leaf &f = leaves[(size_t)i];
+        if (f.level < 0 || f.level >= L) return fail(HE_EINVAL, "%s: baby step %d at level %d, outside [0, %d]", who, i, f.level, L - 1);
+        if (f.degree > kPolyLeafMaxTerms) return fail(HE_EINVAL, "%s: baby step %d has %d terms, at most %d are admitted", who, i, f.degree, kPolyLeafMaxTerms);
+        p->off.push_back((uint32_t)tab.size());
+        for (int k = 0; k <= f.degree; k++, at++) {
+            const bool has = (f.present >> k) & 1u;
+            for (int h = 0; h < 2; h++) {
+                const uint64_t *s = (h ? s1 : s0) + at * (size_t)L;
+                for (int l = 0; l < L; l++) {
+                    uint64_t w = 0;
+                    if (has && l <= f.level) {
+                        const ModConst &m = r->sub[(size_t)l].mc;
+                        if (s[l] >= m.q) return fail(HE_EINVAL, "%s: baby step %d, term %d: the word of limb %d is not below the modulus", who, i, k, l);
+                        w = k == 0 ? s[l] : mform(s[l], m.q, m.brc0, m.brc1);
+                    }
+                    tab.push_back(w);
+                }
+            }
+        }
+    }
+    if (tab.size() >= ((size_t)1 << 32)) return fail(HE_EINVAL, "%s: the scalar table is too large", who);
+    if (!tab.empty()) {
+        Scope sc(r->ctx.get());
+        HIP_TRY(hipMalloc((void **)&p->d_tab, tab.size() * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    *out = reg(p);
+    return HE_OK;
+}
+int he_polyeval_poly_destroy(he_handle h) { return unreg(h, T_POLYEVAL); }
+int he_polyeval_poly_set_group(he_handle h, int G) {
+    GET(p, PolyevalPoly, h, T_POLYEVAL);
+    if (G != 0 && G != 1 && G != 2 && G != 4) return fail(HE_EINVAL, "he_polyeval_poly_set_group: G must be 0 (the default), 1, 2 or 4");
+    p->group.store(G);
+    return HE_OK;
+}
+
+int he_polyeval_leaves(he_handle hpoly, int first, int count, int n_powers, const he_handle *x, const he_handle *out) {
+    static const char *who = "he_polyeval_leaves";
+    GET(p, PolyevalPoly, hpoly, T_POLYEVAL);
+    Ring &r = *p->ring;
+    const std::vector<polyeval::Leaf> &leaves = p->plan.leaves;
+    if (first < 0 || count < 1 || first + count > (int)leaves.size()) return fail(HE_EINVAL, "%s: baby steps [%d, %d) of %d", who, first, first + count, (int)leaves.size());
+    if (n_powers < 0 || n_powers > kPolyLeafMaxTerms || (n_powers > 0 && !x) || !out) return fail(HE_EINVAL, "%s: at most %d powers, and the outputs, are needed", who, kPolyLeafMaxTerms);
+    // the degree of each power given: its components must be 0 .. degree without a gap
+    std::vector<int> xdeg((size_t)n_powers, -1);
+    for (int k = 0; k < n_powers; k++) {
+        for (int c = 0; c < 3; c++)
+            if (x[3 * k + c]) {
+                if (xdeg[(size_t)k] != c - 1) return fail(HE_EINVAL, "%s: X^{%d} has component %d without component %d", who, k + 1, c, c - 1);
+                xdeg[(size_t)k] = c;
+            }
+        if (xdeg[(size_t)k] == 0) return fail(HE_EINVAL, "%s: X^{%d} is a plaintext: a ciphertext of degree 1 or 2 is expected", who, k + 1);
+        const auto planned = p->plan.powers.find(k + 1);
+        if (xdeg[(size_t)k] > 0 && planned != p->plan.powers.end() && planned->second.degree != xdeg[(size_t)k])
+            return fail(HE_EINVAL, "%s: X^{%d} has degree %d, the polynomial was planned for degree %d", who, k + 1, xdeg[(size_t)k], planned->second.degree);
+    }
+    // What the reference's sequence leaves (MulThenAdd resizes its accumulator to the degree of each operand in turn,
+    // schemes/ckks/evaluator.go:936 and schemes/bgv/evaluator.go:1118): the result has the degree of the LAST power used (the
+    // lowest), and component c of power k survives only if every lower power used has that component too.  The leaves of one
+    // polynomial use the powers its parity keeps, from the lowest up: which components of X^k survive is the same for all.
+    std::vector<int> keepc((size_t)n_powers, -1);
+    int need = 0, low = 2, lowest = 0;
+    for (int g = 0; g < count; g++) need = std::max(need, leaves[(size_t)(first + g)].degree);
+    for (int k = 1; k <= need; k++) {
+        if (!polyeval::wanted(k, p->even, p->odd)) continue;
+        if (k > n_powers || xdeg[(size_t)k - 1] < 0) return fail(HE_EINVAL, "%s: the baby steps need X^{%d}, which is not given", who, k);
+        if (!lowest) lowest = k;
+        low = std::min(low, xdeg[(size_t)k - 1]);
+        keepc[(size_t)k - 1] = low;
+    }
+    std::vector<int> ctdeg((size_t)count);
+    for (int g = 0; g < count; g++) {
+        const polyeval::Leaf &f = leaves[(size_t)(first + g)];
+        ctdeg[(size_t)g] = (f.present >> 1) ? xdeg[(size_t)lowest - 1] : f.ct_degree;
+    }
+    CoReq q;
+    Operands o(q, who, r.ctx, r.N);
+    // operands: [3 g + c] the outputs, then [3 count + 3 (k - 1) + c] the powers
+    for (int g = 0; g < count; g++) {
+        const polyeval::Leaf &f = leaves[(size_t)(first + g)];
+        for (int c = 0; c < 3; c++) {
+            const he_handle h = out[3 * g + c];
+            if ((h != 0) != (c <= ctdeg[(size_t)g]))
+                return fail(HE_EINVAL, "%s: the result of baby step %d has degree %d: component %d is %s", who, first + g, ctdeg[(size_t)g], c, h ? "not part of it" : "missing");
+            o.out(o.opt(h), f.level + 1, "out");
+        }
+    }
+    std::vector<int> xlevel((size_t)n_powers, -1);
+    for (int g = 0; g < count; g++) {
+        const polyeval::Leaf &f = leaves[(size_t)(first + g)];
+        for (int k = 1; k <= f.degree && k <= n_powers; k++)
+            if ((f.present >> k) & 1u) xlevel[(size_t)k - 1] = std::max(xlevel[(size_t)k - 1], f.level);
+    }
+    for (int k = 0; k < n_powers; k++)
+        for (int c = 0; c < 3; c++) o.in(o.opt(x[3 * k + c]), xlevel[(size_t)k] + 1, "a power");
+    TRY(o.check());
+    const int B = o.B;
+    int G = p->group.load();
+    if (G == 0) G = polyeval_default_group();
+    q.op = CO_POLY_LEAVES; q.obj = p.get(); q.par[0] = first; q.par[1] = count; q.par[2] = n_powers; q.par[3] = G;
+    for (int k = 0; k < n_powers; k++) q.blob.push_back((uint64_t)(xdeg[(size_t)k] + 1));
+    q.keep.push_back(p);
+    q.run = [p, first, count, G, keepc](const View *v, int B) -> int {
+        Ring &r = *p->ring;
+        const std::vector<polyeval::Leaf> &leaves = p->plan.leaves;
+        for (int g0 = 0; g0 < count; g0 += G) {
+            PolyLeafGroupArgs a{};
+            a.tab = p->d_tab; a.L = p->L; a.members = std::min(G, count - g0); a.ncomp = 2;
+            int top = -1;
+            for (int k = 0; k < kPolyLeafMaxTerms; k++) a.xlevel[k] = -1;
+            // a power takes part as far as the members of THIS group use it
+            for (int m = 0; m < a.members; m++) {
+                const polyeval::Leaf &f = leaves[(size_t)(first + g0 + m)];
+                a.off[m] = p->off[(size_t)(first + g0 + m)]; a.present[m] = f.present; a.level[m] = f.level;
+                top = std::max(top, f.level);
+                for (int c = 0; c < 3; c++) {
+                    const View &ov = v[3 * (g0 + m) + c];
+                    a.out[m][c] = ov.p; a.out_bs[m][c] = ov.bstride;
+                    if (ov.p && c == 2) a.ncomp = 3;
+                }
+                for (int k = 1; k <= f.degree; k++)
+                    if ((f.present >> k) & 1u) { a.n_powers = std::max(a.n_powers, k); a.xlevel[k - 1] = std::max(a.xlevel[k - 1], f.level); }
+            }
+            for (int k = 1; k <= a.n_powers; k++)
+                for (int c = 0; c < 3; c++) {
+                    const View &xv = v[3 * count + 3 * (k - 1) + c];
+                    a.x[k - 1][c] = c <= keepc[(size_t)k - 1] ? xv.p : nullptr; a.x_bs[k - 1][c] = xv.bstride;
+                }
+            a.nlimbs = top + 1;
+            double limbs = 0.0;
+            for (int l = 0; l <= top; l++) {
+                for (int k = 0; k < a.n_powers; k++) if (l <= a.xlevel[k]) for (int c = 0; c < 3; c++) limbs += a.x[k][c] ? 1.0 : 0.0;
+                for (int m = 0; m < a.members; m++) if (l <= a.level[m]) for (int c = 0; c < 3; c++) limbs += a.out[m][c] ? 1.0 : 0.0;
+            }
+            r.ctx->acct(limbs, 0, B, r.N);
+            HIP_TRY(launch_poly_leaf_group(r.dev, a, B, r.ctx->stream));
+        }
+        return HE_OK;
+    };
+    q.one_by_one();  // (the kernel takes no entry tables)
+    return co_dispatch(*r.ctx, B, q);
+}
+// ---- PowerBasis and the whole evaluation: the library's plan run step by step, every step but the baby steps one of the operator
+// entries of hering.h (each files its own request, in this thread's order, and records under a capture), the baby steps ONE
+// he_polyeval_leaves call.  Everything that can be refused is refused before the first step is filed.
+namespace {
+struct PolyevalCt {
+    std::vector<he_handle> v;  // degree + 1 polynomials, owned
+    int level = 0;
+};
+struct PolyevalBasis : Obj {
+    std::shared_ptr<Evaluator> ev;
+    he_handle ev_h = 0, ring_h = 0;  // handles of its own on the evaluator and on its ring Q
+    int basis = 0, batch = 1;
+    std::mutex mu;
+    std::map<int, PolyevalCt> X;
+    PolyevalBasis() : Obj(T_POLYBASIS) {}
+    ~PolyevalBasis() override {
+        for (auto &kv : X) for (he_handle h : kv.second.v) he_poly_free(h);
+        if (ev_h) unreg(ev_h, T_EVAL);
+        if (ring_h) unreg(ring_h, T_RING);
+    }
+    std::map<int, polyeval::Power> held() const {
+        std::map<int, polyeval::Power> m;
+        for (const auto &kv : X) m[kv.first] = polyeval::Power{kv.second.level, (int)kv.second.v.size() - 1};
+        return m;
+    }
+};
+struct PolyevalAux {  // the caller's numbers for the Chebyshev steps, in the plan's order
+    int n = 0;
+    const int *kind = nullptr;  // 0: Add(x, -1); 1 / 2: Sub with the second / the first operand times the ratio first; 3: Sub as it is
+    const uint64_t *s0 = nullptr, *s1 = nullptr;
+    int L = 0;  // words per scalar
+};
+void polyeval_free(std::vector<he_handle> &v) {
+    for (he_handle h : v) he_poly_free(h);
+    v.clear();
+}
+int polyeval_alloc(PolyevalBasis &pb, int level, int n, std::vector<he_handle> *out) {
+    for (int i = 0; i < n; i++) {
+        he_handle h = 0;
+        TRY(he_poly_alloc_scratch(pb.ring_h, level + 1, pb.batch, &h));
+        out->push_back(h);
+    }
+    return HE_OK;
+}
+// what can be refused, before anything is filed
+int polyeval_precheck(const char *who, PolyevalBasis &pb, const polyeval::Plan &plan, size_t first, bool bgv, he_handle rlk, const PolyevalAux &aux) {
+    if (!plan.error.empty()) return fail(HE_EINVAL, "%s", plan.error.c_str());
+    int n_aux = 0;
+    const int top = pb.ev->be->Q->nmod() - 1;
+    for (size_t i = first; i < plan.steps.size(); i++) {
+        const polyeval::Step &s = plan.steps[i];
+        if (s.level < 0 || s.level > top) return fail(HE_EINVAL, "%s: a step at level %d on a ring of %d moduli", who, s.level, top + 1);
+        if ((s.op == polyeval::kRelinearize || s.op == polyeval::kMulRelinNew) && !rlk)
+            return fail(HE_EINVAL, "%s: cannot relinearize: RelinearizationKey is nil", who);
+        if (s.op == polyeval::kMul && s.degree == 1 && bgv) return fail(HE_EINVAL, "%s: cannot tensor: operands must be of degree 1", who);
+        if (s.op == polyeval::kAddMinusOne || s.op == polyeval::kSub) {
+            if (n_aux < aux.n) {
+                const int k = aux.kind[n_aux];
+                if ((s.op == polyeval::kAddMinusOne) != (k == 0) || k < 0 || k > 3)
+                    return fail(HE_EINVAL, "%s: Chebyshev step %d of the plan is %s, the caller's kind is %d", who, n_aux, s.op == polyeval::kSub ? "a Sub" : "Add(x, -1)", k);
+                if (k != 3 && (!aux.s0 || !aux.s1 || aux.L < s.level + 1)) return fail(HE_EINVAL, "%s: the words of Chebyshev step %d are missing", who, n_aux);
+            }
+            n_aux++;
+        }
+    }
+    if (n_aux != aux.n) return fail(HE_EINVAL, "%s: the plan has %d Chebyshev constants and subtractions, the caller planned %d", who, n_aux, aux.n);
+    if (rlk && !get<Evk>(rlk, T_EVK)) return fail(HE_EHANDLE, "%s: bad relinearization key handle", who);
+    return HE_OK;
+}
+// steps [first, end) of the plan on the basis; poly_h: the planned polynomial (0: power steps only); out: the result's two outputs
+int polyeval_exec(PolyevalBasis &pb, const polyeval::Plan &plan, size_t first, bool bgv, uint64_t t, he_handle rlk, const PolyevalAux &aux,
+                  he_handle poly_h, const std::shared_ptr<PolyevalPoly> &poly, he_handle out0, he_handle out1) {
+    std::map<int, PolyevalCt> leaves;
+    int at_aux = 0;
+    struct Cleanup {
+        std::map<int, PolyevalCt> &l;
+        ~Cleanup() { for (auto &kv : l) polyeval_free(kv.second.v); }
+    } cleanup{leaves};
+    auto ct = [&](int name) -> PolyevalCt & { return name > 0 ? pb.X[name] : leaves[name]; };
+    auto tensor = [&](int level, const PolyevalCt &a, const PolyevalCt &b, bool relin, std::vector<he_handle> &o) -> int {
+        if (a.v.size() != 2 || b.v.size() != 2) return fail(HE_EINVAL, "he_polyeval: cannot tensor: operands must be of degree 1");
+        return bgv ? he_bgv_mul_relin(pb.ev_h, level, t, a.v[0], a.v[1], b.v[0], b.v[1], relin ? rlk : 0, o[0], o[1], relin ? 0 : o[2])
+                   : he_ckks_mul_relin(pb.ev_h, level, a.v[0], a.v[1], b.v[0], b.v[1], relin ? rlk : 0, o[0], o[1], relin ? 0 : o[2]);
+    };
+    for (size_t i = first; i < plan.steps.size(); i++) {
+        const polyeval::Step &s = plan.steps[i];
+        const int lvl = s.level;
+        switch (s.op) {
+            case polyeval::kCopyNew: break;
+            case polyeval::kNewCiphertext: {
+                if (!leaves.empty()) break;
+                const int n = (int)plan.leaves.size();
+                int topdeg = 0;
+                std::vector<he_handle> os((size_t)3 * n, 0);
+                for (int g = 0; g < n; g++) {
+                    const polyeval::Leaf &f = plan.leaves[(size_t)g];
+                    PolyevalCt &c = leaves[-1 - g];
+                    c.level = f.level;
+                    TRY(polyeval_alloc(pb, f.level, f.ct_degree + 1, &c.v));
+                    for (size_t k = 0; k < c.v.size(); k++) os[(size_t)3 * g + k] = c.v[k];
+                    topdeg = std::max(topdeg, f.degree);
+                }
+                std::vector<he_handle> xs((size_t)3 * topdeg + 1, 0);
+                for (int k = 1; k <= topdeg; k++) {
+                    const auto it = pb.X.find(k);
+                    if (it == pb.X.end()) continue;
+                    for (size_t c = 0; c < it->second.v.size() && c < 3; c++) xs[(size_t)3 * (k - 1) + c] = it->second.v[c];
+                }
+                TRY(he_polyeval_leaves(poly_h, 0, n, topdeg, xs.data(), os.data()));
+                break;
+            }
+            case polyeval::kAddConst: case polyeval::kMulThenAdd: break;
+            case polyeval::kMulNew: case polyeval::kMulRelinNew: {
+                const bool relin = s.op == polyeval::kMulRelinNew;
+                std::vector<he_handle> o;
+                TRY(polyeval_alloc(pb, lvl, relin ? 2 : 3, &o));
+                const int rc = tensor(lvl, pb.X[s.a], pb.X[s.b], relin, o);
+                if (rc != HE_OK) { polyeval_free(o); return rc; }
+                PolyevalCt &x = pb.X[s.dst];
+                x.v = o; x.level = lvl;
+                break;
+            }
+            case polyeval::kRelinearize: {
+                PolyevalCt &x = ct(s.dst);
+                std::vector<he_handle> o;
+                TRY(polyeval_alloc(pb, lvl, 2, &o));
+                const int rc = x.v.size() == 3 ? he_relinearize(pb.ev_h, lvl, x.v[0], x.v[1], x.v[2], rlk, o[0], o[1]) : fail(HE_EINVAL, "he_polyeval: Relinearize of a ciphertext that is not of degree 2");
+                if (rc != HE_OK) { polyeval_free(o); return rc; }
+                polyeval_free(x.v);
+                x.v = o; x.level = lvl;
+                break;
+            }
+            case polyeval::kRescale: {
+                PolyevalCt &x = ct(s.dst);
+                const bool last = i + 1 == plan.steps.size() && out0 != 0;
+                for (size_t c = 0; c < x.v.size(); c++) {
+                    const he_handle dst = last ? (c == 0 ? out0 : out1) : x.v[c];
+                    TRY(bgv ? he_div_round_by_last_modulus_ntt(pb.ring_h, lvl + 1, x.v[c], dst) : he_div_round_by_last_modulus_many_ntt(pb.ring_h, lvl + 1, 1, x.v[c], dst));
+                }
+                x.level = lvl;
+                break;
+            }
+            case polyeval::kAddSelf: {
+                PolyevalCt &x = ct(s.dst);
+                for (he_handle h : x.v) TRY(he_add(pb.ring_h, lvl, h, h, h));
+                x.level = lvl;
+                break;
+            }
+            case polyeval::kAddMinusOne: {
+                PolyevalCt &x = ct(s.dst);
+                const size_t o = (size_t)at_aux++ * aux.L;
+                TRY(he_double_rns_scalarop(pb.ring_h, lvl, 0, x.v[0], aux.s0 + o, aux.s1 + o, x.v[0]));
+                x.level = lvl;
+                break;
+            }
+            case polyeval::kSub: case polyeval::kAdd: {
+                PolyevalCt &x = ct(s.dst);
+                const PolyevalCt &y = ct(s.a);
+                std::vector<he_handle> yv = y.v, scaled;
+                if (s.op == polyeval::kSub) {
+                    const int k = aux.kind[at_aux];
+                    const size_t o = (size_t)at_aux++ * aux.L;
+                    if (k == 1) {  // evaluateInPlace: the operand of the smaller scale times the integer ratio, into a new ciphertext
+                        TRY(polyeval_alloc(pb, lvl, (int)y.v.size(), &scaled));
+                        for (size_t c = 0; c < y.v.size(); c++) {
+                            const int rc = he_double_rns_scalarop(pb.ring_h, lvl, 2, y.v[c], aux.s0 + o, aux.s1 + o, scaled[c]);
+                            if (rc != HE_OK) { polyeval_free(scaled); return rc; }
+                        }
+                        yv = scaled;
+                    } else if (k == 2) {
+                        for (he_handle h : x.v) TRY(he_double_rns_scalarop(pb.ring_h, lvl, 2, h, aux.s0 + o, aux.s1 + o, h));
+                    }
+                }
+                int rc = HE_OK;
+                const size_t lo = std::min(x.v.size(), yv.size());
+                for (size_t c = 0; c < lo && rc == HE_OK; c++)
+                    rc = s.op == polyeval::kSub ? he_sub(pb.ring_h, lvl, x.v[c], yv[c], x.v[c]) : he_add(pb.ring_h, lvl, x.v[c], yv[c], x.v[c]);
+                for (size_t c = lo; c < yv.size() && rc == HE_OK; c++) {  // the wider operand's further components: copied, negated for Sub
+                    std::vector<he_handle> o;
+                    rc = polyeval_alloc(pb, lvl, 1, &o);
+                    if (rc == HE_OK) rc = s.op == polyeval::kSub ? he_neg(pb.ring_h, lvl, yv[c], o[0]) : he_poly_copy(o[0], yv[c], lvl);
+                    if (rc == HE_OK) x.v.push_back(o[0]); else polyeval_free(o);
+                }
+                polyeval_free(scaled);
+                TRY(rc);
+                x.level = lvl;
+                break;
+            }
+            case polyeval::kMul: {
+                PolyevalCt &x = ct(s.dst);
+                const PolyevalCt &y = pb.X[s.a];
+                std::vector<he_handle> o;
+                int rc;
+                if (x.v.size() == 1) {  // a baby step of degree 0: plaintext x ciphertext (schemes/ckks/evaluator.go:842-870)
+                    std::vector<he_handle> m;
+                    TRY(polyeval_alloc(pb, lvl, 1, &m));
+                    rc = polyeval_alloc(pb, lvl, (int)y.v.size(), &o);
+                    if (rc == HE_OK) rc = he_mform(pb.ring_h, lvl, x.v[0], m[0]);
+                    for (size_t c = 0; c < y.v.size() && rc == HE_OK; c++) rc = he_mul_coeffs_montgomery(pb.ring_h, lvl, m[0], y.v[c], o[c]);
+                    polyeval_free(m);
+                } else {
+                    rc = polyeval_alloc(pb, lvl, 3, &o);
+                    if (rc == HE_OK) rc = tensor(lvl, x, y, false, o);
+                }
+                if (rc != HE_OK) { polyeval_free(o); return rc; }
+                polyeval_free(x.v);
+                x.v = o; x.level = lvl;
+                break;
+            }
+            default: return fail(HE_EINVAL, "he_polyeval: unknown step %d", s.op);
+        }
+    }
+    (void)poly;
+    return HE_OK;
+}
+int polyeval_aux(const char *who, int n_aux, const int *kind, const uint64_t *s0, const uint64_t *s1, int L, PolyevalAux *a) {
+    if (n_aux < 0 || (n_aux > 0 && !kind)) return fail(HE_EINVAL, "%s: the kinds of the Chebyshev steps are missing", who);
+    a->n = n_aux; a->kind = kind; a->s0 = s0; a->s1 = s1; a->L = L;
+    return HE_OK;
+}
+}  // namespace
+
+int he_polyeval_basis_create(he_handle hev, int basis, int level, he_handle in0, he_handle in1, he_handle *out) {
+    static const char *who = "he_polyeval_basis_create";
+    GET(ev, Evaluator, hev, T_EVAL);
+    if (!out) return fail(HE_EINVAL, "%s: null output", who);
+    if (basis != polyeval::kMonomial && basis != polyeval::kChebyshev) return fail(HE_EINVAL, "%s: unknown basis %d", who, basis);
+    TRY(check_level(*ev->be->Q, level, who));
+    std::shared_ptr<Poly> a = get<Poly>(in0, T_POLY), b = get<Poly>(in1, T_POLY);
+    if (!a || !b) return fail(HE_EHANDLE, "%s: bad Poly handle", who);
+    if (a->ctx != ev->be->ctx || b->ctx != ev->be->ctx || a->N != ev->be->Q->N || b->N != a->N) return fail(HE_EINVAL, "%s: the ciphertext belongs to another context or degree", who);
+    if (a->nlimbs < level + 1 || b->nlimbs < level + 1 || a->batch != b->batch) return fail(HE_EINVAL, "%s: the ciphertext has too few limbs for level %d, or two batches", who, level);
+    auto pb = std::make_shared<PolyevalBasis>();
+    pb->ev = ev; pb->basis = basis; pb->batch = a->batch;
+    pb->ev_h = reg(ev); pb->ring_h = reg(ev->be->Q);
+    PolyevalCt x;
+    x.level = level;
+    TRY(polyeval_alloc(*pb, level, 2, &x.v));
+    pb->X[1] = x;  // (owned from here on: a failure below releases it with the basis)
+    TRY(he_poly_copy(x.v[0], in0, level));
+    TRY(he_poly_copy(x.v[1], in1, level));
+    *out = reg(pb);
+    return HE_OK;
+}
+int he_polyeval_basis_destroy(he_handle h) { return unreg(h, T_POLYBASIS); }
+int he_polyeval_basis_powers(he_handle h, int *powers, size_t cap, size_t *n) {
+    GET(pb, PolyevalBasis, h, T_POLYBASIS);
+    if (!n || (cap && !powers)) return fail(HE_EINVAL, "he_polyeval_basis_powers: null argument");
+    std::lock_guard<std::mutex> lk(pb->mu);
+    size_t i = 0;
+    for (const auto &kv : pb->X) {
+        if (i < cap) { powers[3 * i] = kv.first; powers[3 * i + 1] = kv.second.level; powers[3 * i + 2] = (int)kv.second.v.size() - 1; }
+        i++;
+    }
+    *n = i;
+    return HE_OK;
+}
+int he_polyeval_basis_power(he_handle h, int n, he_handle *comps) {
+    GET(pb, PolyevalBasis, h, T_POLYBASIS);
+    if (!comps) return fail(HE_EINVAL, "he_polyeval_basis_power: null output");
+    std::lock_guard<std::mutex> lk(pb->mu);
+    const auto it = pb->X.find(n);
+    if (it == pb->X.end()) return fail(HE_EINVAL, "he_polyeval_basis_power: the basis holds no X^{%d}", n);
+    for (size_t c = 0; c < 3; c++) comps[c] = c < it->second.v.size() ? it->second.v[c] : 0;
+    return HE_OK;
+}
+int he_polyeval_gen_power(he_handle h, int scheme, uint64_t t, he_handle rlk, int n, int lazy, int n_aux, const int *aux_kind, const uint64_t *aux_s0,
+                          const uint64_t *aux_s1, int aux_words) {
+    static const char *who = "he_polyeval_gen_power";
+    GET(pb, PolyevalBasis, h, T_POLYBASIS);
+    if (n < 1) return fail(HE_EINVAL, "invalid n: n=%d should be greater than zero", n);
+    if (scheme != 0 && scheme != 1) return fail(HE_EINVAL, "%s: scheme must be 0 (CKKS) or 1 (BGV)", who);
+    std::lock_guard<std::mutex> lk(pb->mu);
+    polyeval::Plan plan;
+    plan.powers = pb->held();
+    polyeval::gen_power(plan, pb->basis, n, lazy != 0);
+    for (const polyeval::Step &s : plan.steps)
+        if (s.level < 0) return fail(HE_EINVAL, "%s: X^{%d} would sink below level 0", who, n);
+    PolyevalAux aux;
+    TRY(polyeval_aux(who, n_aux, aux_kind, aux_s0, aux_s1, aux_words, &aux));
+    TRY(polyeval_precheck(who, *pb, plan, 0, scheme == 1, rlk, aux));
+    return polyeval_exec(*pb, plan, 0, scheme == 1, t, rlk, aux, 0, nullptr, 0, 0);
+}
+int he_polyeval_evaluate_from_power_basis(he_handle h, he_handle hpoly, int scheme, uint64_t t, he_handle rlk, int n_aux, const int *aux_kind,
+                                          const uint64_t *aux_s0, const uint64_t *aux_s1, int aux_words, he_handle out0, he_handle out1) {
+    static const char *who = "he_polyeval_evaluate_from_power_basis";
+    GET(pb, PolyevalBasis, h, T_POLYBASIS);
+    GET(p, PolyevalPoly, hpoly, T_POLYEVAL);
+    if (scheme != 0 && scheme != 1) return fail(HE_EINVAL, "%s: scheme must be 0 (CKKS) or 1 (BGV)", who);
+    if (p->ring.get() != pb->ev->be->Q.get()) return fail(HE_EINVAL, "%s: the polynomial was planned on another ring", who);
+    std::lock_guard<std::mutex> lk(pb->mu);
+    // the basis must be the one the polynomial was planned for: the same powers at the same levels and degrees
+    const std::map<int, polyeval::Power> held = pb->held();
+    if (held.size() != p->planned_for.size()) return fail(HE_EINVAL, "%s: the basis holds %zu powers, the polynomial was planned for %zu", who, held.size(), p->planned_for.size());
+    for (const auto &kv : held) {
+        const auto it = p->planned_for.find(kv.first);
+        if (it == p->planned_for.end() || it->second.level != kv.second.level || it->second.degree != kv.second.degree)
+            return fail(HE_EINVAL, "%s: X^{%d} of the basis (level %d, degree %d) is not what the polynomial was planned for", who, kv.first, kv.second.level, kv.second.degree);
+    }
+    const polyeval::Plan &plan = p->plan;
+    PolyevalAux aux;
+    TRY(polyeval_aux(who, n_aux, aux_kind, aux_s0, aux_s1, aux_words, &aux));
+    TRY(polyeval_precheck(who, *pb, plan, 0, scheme == 1, rlk, aux));
+    // the outputs: two polynomials of the result's level that are neither each other nor anything the evaluation reads
+    std::shared_ptr<Poly> o0 = get<Poly>(out0, T_POLY), o1 = get<Poly>(out1, T_POLY);
+    if (!o0 || !o1) return fail(HE_EHANDLE, "%s: bad output handle", who);
+    if (plan.out_level < 0) return fail(HE_EINVAL, "%s: the result would sink below level 0", who);
+    for (const std::shared_ptr<Poly> &o : {o0, o1}) {
+        if (o->ctx != pb->ev->be->ctx || o->N != pb->ev->be->Q->N) return fail(HE_EINVAL, "%s: an output belongs to another context or degree", who);
+        if (o->nlimbs < plan.out_level + 1) return fail(HE_EINVAL, "%s: an output has %d limbs, %d needed", who, o->nlimbs, plan.out_level + 1);
+        if (o->batch != pb->batch) return fail(HE_EINVAL, "%s: batch mismatch (an output has %d entries, %d expected)", who, o->batch, pb->batch);
+    }
+    if (o0->d == o1->d) return fail(HE_EINVAL, "%s: the two outputs are the same polynomial", who);
+    for (const auto &kv : pb->X)
+        for (he_handle xh : kv.second.v) {
+            const std::shared_ptr<Poly> x = get<Poly>(xh, T_POLY);
+            if (x && (x->d == o0->d || x->d == o1->d)) return fail(HE_EINVAL, "%s: an output is a component of X^{%d}", who, kv.first);
+        }
+    return polyeval_exec(*pb, plan, 0, scheme == 1, t, rlk, aux, hpoly, p, out0, out1);
+}
+int he_polyeval_evaluate(he_handle hev, he_handle hpoly, int scheme, uint64_t t, he_handle rlk, int level, he_handle in0, he_handle in1, int n_aux,
+                         const int *aux_kind, const uint64_t *aux_s0, const uint64_t *aux_s1, int aux_words, he_handle out0, he_handle out1) {
+    static const char *who = "he_polyeval_evaluate";
+    GET(p, PolyevalPoly, hpoly, T_POLYEVAL);
+    // Evaluate (polynomial_evaluator.go:62-65): the depth check, then the input's copy -- an output may therefore not be the input
+    const int depth = p->plan.depth;
+    if (level < depth) return fail(HE_EINVAL, "%d levels < %d log(d) -> cannot evaluate poly", level, depth);
+    std::shared_ptr<Poly> a = get<Poly>(in0, T_POLY), b = get<Poly>(in1, T_POLY), o0 = get<Poly>(out0, T_POLY), o1 = get<Poly>(out1, T_POLY);
+    if (!a || !b || !o0 || !o1) return fail(HE_EHANDLE, "%s: bad Poly handle", who);
+    if (o0->d == a->d || o0->d == b->d || o1->d == a->d || o1->d == b->d) return fail(HE_EINVAL, "%s: an output is a component of the input", who);
+    if (o0->d == o1->d) return fail(HE_EINVAL, "%s: the two outputs are the same polynomial", who);
+    if (o0->nlimbs < p->plan.out_level + 1 || o1->nlimbs < p->plan.out_level + 1) return fail(HE_EINVAL, "%s: an output has too few limbs, %d needed", who, p->plan.out_level + 1);
+    if (p->planned_for.size() != 1 || p->planned_for.begin()->second.level != level || p->planned_for.begin()->second.degree != 1)
+        return fail(HE_EINVAL, "%s: the polynomial was not planned for a fresh basis at level %d", who, level);
+    {   // the refusals of the evaluation itself, before the input is copied
+        GET(ev, Evaluator, hev, T_EVAL);
+        PolyevalBasis probe;
+        probe.ev = ev;
+        PolyevalAux aux;
+        TRY(polyeval_aux(who, n_aux, aux_kind, aux_s0, aux_s1, aux_words, &aux));
+        TRY(polyeval_precheck(who, probe, p->plan, 0, scheme == 1, rlk, aux));
+        if (a->batch != o0->batch || a->batch != o1->batch) return fail(HE_EINVAL, "%s: batch mismatch between the input and the outputs", who);
+    }
+    he_handle hb = 0;
+    TRY(he_polyeval_basis_create(hev, polyeval::kMonomial, level, in0, in1, &hb));  // (the plan is the polynomial's: the basis kind is not consulted)
+    const int rc = he_polyeval_evaluate_from_power_basis(hb, hpoly, scheme, t, rlk, n_aux, aux_kind, aux_s0, aux_s1, aux_words, out0, out1);
+    const std::string msg = g_err;
+    he_polyeval_basis_destroy(hb);
+    if (rc != HE_OK) g_err = msg;
+    return rc;
+}
+int he_polyeval_gen_power_plan(int basis, int n, int lazy, int n_powers, const int *powers, int64_t *out, size_t cap, size_t *n_words) {
+    static const char *who = "he_polyeval_gen_power_plan";
+    if (!n_words || (cap && !out)) return fail(HE_EINVAL, "%s: null argument", who);
+    if (n < 1) return fail(HE_EINVAL, "invalid n: n=%d should be greater than zero", n);
+    if (basis != polyeval::kMonomial && basis != polyeval::kChebyshev) return fail(HE_EINVAL, "%s: unknown basis %d", who, basis);
+    polyeval::Plan plan;
+    TRY(polyeval_present(who, n_powers, powers, &plan.powers));
+    polyeval::gen_power(plan, basis, n, lazy != 0);
+    size_t i = 0;
+    for (const polyeval::Step &s : plan.steps)
+        for (int x : {s.op, s.dst, s.level, s.degree, s.a, s.b}) { if (i < cap) out[i] = x; i++; }
+    *n_words = i;
+    return HE_OK;
+}
+int he_polyeval_plan(int degree, int basis, int even, int odd, int lazy, int copy_input, int n_powers, const int *powers, int64_t *out, size_t cap,
+                     size_t *n_words) {
+    return he_debug_polyeval_plan(degree, basis, even, odd, lazy, copy_input, n_powers, powers, out, cap, n_words);
+}
+int he_debug_polyeval_plan(int degree, int basis, int even, int odd, int lazy, int copy_input, int n_powers, const int *powers, int64_t *out,
+                           size_t cap, size_t *n_words) {
+    static const char *who = "he_debug_polyeval_plan";
+    if (!n_words || (cap && !out)) return fail(HE_EINVAL, "%s: null argument", who);
+    std::map<int, polyeval::Power> present;
+    TRY(polyeval_present(who, n_powers, powers, &present));
+    const polyeval::Plan p = polyeval::build_plan(degree, basis, even != 0, odd != 0, lazy != 0, present, copy_input != 0);
+    if (!p.error.empty()) return fail(HE_EINVAL, "%s", p.error.c_str());
+    const std::vector<int64_t> w = polyeval::plan_words(p);
     for (size_t i = 0; i < w.size() && i < cap; i++) out[i] = w[i];
     *n_words = w.size();
     return HE_OK;

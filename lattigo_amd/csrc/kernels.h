@@ -372,6 +372,34 @@ struct DiagMacGroupArgs {
 };
 hipError_t launch_diag_mac_group(const RingDev &r, const DiagMacGroupArgs &a, int batch, hipStream_t s);
 
+// The baby steps ("leaves") of a polynomial evaluation, a GROUP of them in one pass over the power basis
+// (circuits/common/polynomial/polynomial_evaluator.go:254-359, mapping == nil: Add(res, c_0), then MulThenAdd(X[k], c_k, res) for
+// k = deg ... 1): per member g of the group, ciphertext component c and limb l <= level[g],
+//   out[g][c] = CRed(c_{g,0} [c == 0] + CRed(MRedLazy128(sum_k MForm(c_{g,k}) * X_k[c]))),
+// the canonical words the reference's sequence leaves (every step of it ends fully reduced): exact 128-bit accumulation, the
+// high word reduced after every term as in the diag kernels, so the sum is exact for any term count with moduli below 2^62.
+// A scalar is a pair of residues per limb, the first for coefficients [0, N/2) and the second for [N/2, N) (what
+// he_double_rns_scalarop takes; BGV passes the same residue twice).  Each X_k word is loaded once per group (non-temporal).
+// Scalar table (device, built once per polynomial): member g's words start at tab + off[g]; scalar k of it is
+//   [2 k + h][limb] with stride L words, h = the half; k = 0 is the constant as a plain residue, k >= 1 in Montgomery form.
+// present[g]: bit k = member g has term k (bit 0: the constant).  xlevel[k - 1]: the highest limb at which some member reads X_k
+// (the caller has checked that X_k has it).  A null x[k - 1][c] / out[g][c]: the power / the member has no such component.
+constexpr int kPolyLeafMaxTerms = 31;  // non-constant terms of one leaf the kernel admits: 2^logSplit - 1 with logSplit <= 5
+constexpr int kPolyLeafGroupMax = 4;
+struct PolyLeafGroupArgs {
+    const uint64_t *tab;
+    int L, n_powers, members, ncomp;  // ncomp: 2, or 3 when some power is of degree 2 (lazy)
+    uint32_t off[kPolyLeafGroupMax], present[kPolyLeafGroupMax];
+    int level[kPolyLeafGroupMax];
+    int xlevel[kPolyLeafMaxTerms];
+    const uint64_t *x[kPolyLeafMaxTerms][3];
+    size_t x_bs[kPolyLeafMaxTerms][3];
+    uint64_t *out[kPolyLeafGroupMax][3];
+    size_t out_bs[kPolyLeafGroupMax][3];
+    int nlimbs;  // 1 + the highest level of the group
+};
+hipError_t launch_poly_leaf_group(const RingDev &r, const PolyLeafGroupArgs &a, int batch, hipStream_t s);
+
 // Fused "forward row NTT + key multiply-accumulate" for limbs below 2^47 (double-precision path): one workgroup
 // owns (row, limb, batch entry) and loops over the beta digits; every non-own digit's row is transformed in LDS and
 // multiplied by the two key rows straight out of LDS, the own digit's row is read from the NTT-domain input, the two
@@ -699,7 +727,7 @@ enum KernelId {
     K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
     K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND,
     K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_GADGET_AGGREGATE, K_RKG_ROUND_ONE, K_RKG_ROUND_TWO, K_RLK_FINALIZE,
-    K_DIAG_MAC_GROUP, K_COUNT
+    K_DIAG_MAC_GROUP, K_POLY_LEAF_GROUP, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -79,7 +79,7 @@ const char *kernel_name(int id) {
                                          "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
                                          "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add",
                                          "rgsw_table_finish", "gadget_aggregate", "rkg_round_one", "rkg_round_two",
-                                         "rlk_finalize", "diag_mac_group"};
+                                         "rlk_finalize", "diag_mac_group", "poly_leaf_group"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -4548,6 +4548,119 @@ hipError_t launch_diag_mac_group(const RingDev &r, const DiagMacGroupArgs &a, in
     else if (G == 2) { if (bb == 4) HE_DMG(2, 4); else if (bb == 2) HE_DMG(2, 2); else HE_DMG(2, 1); }
     else { if (bb == 2) HE_DMG(4, 2); else HE_DMG(4, 1); }
 #undef HE_DMG
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// the leaves of a polynomial evaluation, a group of G per pass over the power basis (see kernels.h)
+// ------------------------------------------------------------------------------------
+struct PolyLeafGroupKArgs {
+    PolyLeafGroupArgs a;
+    const ModConst *mc;
+    int N, batch;
+};
+// As in diag_mac_group_kernel every accumulator index is a constant after unrolling (nothing goes to scratch), and which members
+// have term k, which take part in this limb and which components a power has are uniform over the block.  The two residues of a
+// scalar come through the scalar cache; the half a coefficient belongs to selects between them per thread (a ring of 16
+// coefficients has both halves inside one wave).
+template <int G, int C, int BB>
+__global__ void __launch_bounds__(256) poly_leaf_group_kernel(const PolyLeafGroupKArgs A) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= A.N) return;
+    const int l = blockIdx.y;
+    const int b0 = blockIdx.z * BB;
+    const ModConst m = A.mc[l];
+    const uint64_t q = m.q;
+    const bool upper = x >= (A.N >> 1);
+    uint64_t hi[G][C][BB], lo[G][C][BB];
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int c = 0; c < C; c++)
+#pragma unroll
+            for (int b = 0; b < BB; b++) hi[g][c][b] = lo[g][c][b] = 0;
+    const size_t pos = (size_t)l * A.N + x;
+    for (int k = 1; k <= A.a.n_powers; k++) {
+        if (l > A.a.xlevel[k - 1]) continue;  // no member reads X_k at this limb
+        uint64_t v[C][BB];
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const uint64_t *p = A.a.x[k - 1][c];
+            const size_t bs = A.a.x_bs[k - 1][c];
+#pragma unroll
+            for (int b = 0; b < BB; b++) v[c][b] = (p != nullptr && b0 + b < A.batch) ? ldnt(&p[(size_t)(b0 + b) * bs + pos]) : 0;
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (g >= A.a.members || l > A.a.level[g] || !((A.a.present[g] >> k) & 1u)) continue;
+            const size_t so = (size_t)A.a.off[g] + (size_t)(2 * k) * A.a.L + l;
+            const uint64_t s0 = ldc(A.a.tab, so), s1 = ldc(A.a.tab, so + A.a.L);
+            const uint64_t w = upper ? s1 : s0;
+#pragma unroll
+            for (int c = 0; c < C; c++)
+#pragma unroll
+                for (int b = 0; b < BB; b++) {
+                    uint64_t ph, pl;
+                    mul64wide(v[c][b], w, ph, pl);
+                    lo[g][c][b] += pl; hi[g][c][b] += ph + (lo[g][c][b] < pl);
+                    hi[g][c][b] = hi[g][c][b] >= q ? hi[g][c][b] - q : hi[g][c][b];
+                }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        if (g >= A.a.members || l > A.a.level[g]) continue;
+        uint64_t cst = 0;
+        if (A.a.present[g] & 1u) {
+            const size_t so = (size_t)A.a.off[g] + l;
+            const uint64_t s0 = ldc(A.a.tab, so), s1 = ldc(A.a.tab, so + A.a.L);
+            cst = upper ? s1 : s0;
+        }
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            uint64_t *o = A.a.out[g][c];
+            if (o == nullptr) continue;
+#pragma unroll
+            for (int b = 0; b < BB; b++) {
+                if (b0 + b < A.batch) {
+                    uint64_t r = cred(mred128_lazy(hi[g][c][b], lo[g][c][b], q, m.qinv), q);
+                    if (c == 0) r = cred(r + cst, q);
+                    o[(size_t)(b0 + b) * A.a.out_bs[g][c] + pos] = r;
+                }
+            }
+        }
+    }
+}
+// batch entries per thread: the largest of 4, 2, 1 the batch fills; an instantiation with more than 24 accumulators takes half
+// (tools/kres.py: none spills or uses scratch)
+hipError_t launch_poly_leaf_group(const RingDev &r, const PolyLeafGroupArgs &a, int batch, hipStream_t s) {
+    if (a.nlimbs <= 0 || batch <= 0 || a.members <= 0) return hipSuccess;
+    if (a.members > kPolyLeafGroupMax || a.n_powers < 0 || a.n_powers > kPolyLeafMaxTerms || (a.ncomp != 2 && a.ncomp != 3) || !a.tab || a.L < a.nlimbs)
+        return hipErrorInvalidValue;
+    PolyLeafGroupKArgs A{};
+    A.a = a; A.mc = r.mc; A.N = r.N; A.batch = batch;
+    const int G = a.members > 2 ? 4 : a.members;
+    int bb = batch >= 4 ? 4 : (batch >= 2 ? 2 : 1);
+    while (G * a.ncomp * bb > 24 && bb > 1) bb >>= 1;
+    dim3 grid((unsigned)((r.N + 255) / 256), a.nlimbs, (batch + bb - 1) / bb), block(256);
+    // per limb: every component of every power some member reads there, once per entry; every component of every member out
+    double limbs = 0.0;
+    for (int l = 0; l < a.nlimbs; l++) {
+        for (int k = 0; k < a.n_powers; k++)
+            if (l <= a.xlevel[k]) for (int c = 0; c < a.ncomp; c++) limbs += a.x[k][c] ? batch : 0;
+        for (int g = 0; g < a.members; g++)
+            if (l <= a.level[g]) for (int c = 0; c < a.ncomp; c++) limbs += a.out[g][c] ? batch : 0;
+    }
+    ProfScope ps(K_POLY_LEAF_GROUP, s, limbs * (double)r.N * 8.0);
+#define HE_PLG(GG, CC, BBB) hipLaunchKernelGGL((poly_leaf_group_kernel<GG, CC, BBB>), grid, block, 0, s, A)
+#define HE_PLG_B(GG, CC) do { if (bb == 4) HE_PLG(GG, CC, 4); else if (bb == 2) HE_PLG(GG, CC, 2); else HE_PLG(GG, CC, 1); } while (0)
+    if (a.ncomp == 2) {
+        if (G == 1) HE_PLG_B(1, 2); else if (G == 2) HE_PLG_B(2, 2); else { if (bb == 2) HE_PLG(4, 2, 2); else HE_PLG(4, 2, 1); }
+    } else {
+        if (G == 1) HE_PLG_B(1, 3); else if (G == 2) HE_PLG_B(2, 3); else { if (bb == 2) HE_PLG(4, 3, 2); else HE_PLG(4, 3, 1); }
+    }
+#undef HE_PLG_B
+#undef HE_PLG
     return hipGetLastError();
 }
 
