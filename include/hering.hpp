@@ -44,6 +44,7 @@
 #include "hering_multiparty.h"
 #include "hering_lintrans.h"
 #include "hering_polyeval.h"
+#include "hering_ckks_evaluator.h"
 
 namespace hering {
 
@@ -1949,6 +1950,56 @@ public:
     }
 };
 }  // namespace polyeval
+
+// ---- ckks.Evaluator (schemes/ckks/evaluator.go; hering_ckks_evaluator.h), NTT domain -------------------------------------------
+// The linear forms over a whole ciphertext and MulRelinThenAdd, one launch each.  The caller plans levels, scales and the residues
+// of scalars, ratios and scale-ups (as lattigo_amd.ckks.Evaluator does); every word list holds one residue per limb 0 .. level.
+namespace ckks {
+class Evaluator {
+    Ring ringQ_;
+    const hering::Evaluator *ev_;
+
+    static std::vector<he_handle> handles(const std::vector<Poly> &v) {
+        std::vector<he_handle> h;
+        for (const Poly &p : v) h.push_back(p.h());
+        return h;
+    }
+    static const uint64_t *words(const std::vector<uint64_t> *w) { return w ? w->data() : nullptr; }
+
+public:
+    // ringQ: Parameters.RingQ(); ev: the rlwe evaluator of the parameters (MulRelinThenAdd only; may be null otherwise)
+    Evaluator(const Ring &ringQ, const hering::Evaluator *ev = nullptr) : ringQ_(ringQ), ev_(ev) {}
+    // evaluateInPlace (:221-408) with Ring.Add / Ring.Sub; scaled = 1 / 2: op0 / op1 is first multiplied by the integer `ratio`
+    void AddSub(int level, bool sub, const Ciphertext &op0, const Ciphertext &op1, int scaled, const std::vector<uint64_t> *ratio,
+                Ciphertext &opOut) const {
+        const auto a = handles(op0.Value), b = handles(op1.Value), o = handles(opOut.Value);
+        check(he_ckks_add(ringQ_.h(), level, sub ? 1 : 0, (int)a.size(), a.data(), (int)b.size(), b.data(), scaled, words(ratio), (int)o.size(),
+                          o.data()));
+    }
+    // evaluateWithScalar (:410-424): op = HE_CKKS_SCALAR_*; (s0, s1): the scalar on the two halves of a limb; pre: the scale-up of
+    // opOut before MUL_THEN_ADD (:959-964)
+    void Scalar(int level, int op, const Ciphertext &op0, const std::vector<uint64_t> &s0, const std::vector<uint64_t> &s1,
+                const std::vector<uint64_t> *pre, Ciphertext &opOut) const {
+        const auto a = handles(op0.Value), o = handles(opOut.Value);
+        if (a.size() != o.size()) throw std::invalid_argument("ckks::Evaluator::Scalar: op0 and opOut differ in degree");
+        check(he_ckks_scalar(ringQ_.h(), level, op, (int)a.size(), a.data(), s0.data(), s1.data(), words(pre), o.data()));
+    }
+    // the plaintext branches of mulRelin (:842-869) and mulRelinThenAdd (:1158-1170)
+    void MulPlaintext(int level, const Ciphertext &ct, const Poly &pt, bool thenAdd, const std::vector<uint64_t> *pre, Ciphertext &opOut) const {
+        const auto a = handles(ct.Value), o = handles(opOut.Value);
+        if (a.size() != o.size()) throw std::invalid_argument("ckks::Evaluator::MulPlaintext: ct and opOut differ in degree");
+        check(he_ckks_mul_pt(ringQ_.h(), level, (int)a.size(), a.data(), pt.h(), thenAdd ? 1 : 0, words(pre), o.data()));
+    }
+    // the ciphertext x ciphertext branch of mulRelinThenAdd (:1104-1155); rlk null: MulThenAdd onto three components
+    void MulRelinThenAdd(int level, const Ciphertext &op0, const Ciphertext &op1, const EvaluationKey *rlk, const std::vector<uint64_t> *pre,
+                         Ciphertext &opOut) const {
+        if (!ev_) throw std::invalid_argument("ckks::Evaluator::MulRelinThenAdd: no rlwe evaluator");
+        check(he_ckks_mul_relin_then_add(ev_->h(), level, op0.Value.at(0).h(), op0.Value.at(1).h(), op1.Value.at(0).h(), op1.Value.at(1).h(),
+                                         rlk ? rlk->h() : 0, words(pre), opOut.Value.at(0).h(), opOut.Value.at(1).h(),
+                                         rlk ? 0 : opOut.Value.at(2).h()));
+    }
+};
+}  // namespace ckks
 
 // One process per GPU: the RCCL communicator of a context, driven by the library on the context's stream (key replication over xGMI;
 // the all-reduce of a key switch split by digit).  Rank 0 draws the id and hands it to the others over any control plane.

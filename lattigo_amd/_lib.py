@@ -14,7 +14,8 @@ _HDRS = [os.path.join(_INC, "hering.h"), os.path.join(_INC, "hering_debug.h"), o
          os.path.join(_INC, "hering_bridge.h"), os.path.join(_INC, "hering_bfv.h"), os.path.join(_INC, "hering_ckks_encoder.h"),
          os.path.join(_INC, "hering_bgv_encoder.h"), os.path.join(_INC, "hering_sampler.h"), os.path.join(_INC, "hering_encryptor.h"),
          os.path.join(_INC, "hering_keygen.h"), os.path.join(_INC, "hering_rgsw_encryptor.h"), os.path.join(_INC, "hering_multiparty.h"),
-         os.path.join(_INC, "hering_lintrans.h"), os.path.join(_INC, "hering_polyeval.h")]
+         os.path.join(_INC, "hering_lintrans.h"), os.path.join(_INC, "hering_polyeval.h"),
+         os.path.join(_INC, "hering_ckks_evaluator.h")]
 
 H = C.c_uint64
 u64p = C.POINTER(C.c_uint64)
@@ -197,6 +198,8 @@ def _declare(L):
         "he_polyeval_evaluate_from_power_basis": [H, H, i, C.c_uint64, H, i, ip, u64p, u64p, i, H, H],
         "he_polyeval_evaluate": [H, H, i, C.c_uint64, H, i, H, H, i, ip, u64p, u64p, i, H, H],
         "he_ckks_mul_relin": [H, i, H, H, H, H, H, H, H, H],
+        "he_ckks_add": [H, i, i, i, HP, i, HP, i, u64p, i, HP], "he_ckks_scalar": [H, i, i, i, HP, u64p, u64p, u64p, HP],
+        "he_ckks_mul_pt": [H, i, i, HP, H, i, u64p, HP], "he_ckks_mul_relin_then_add": [H, i, H, H, H, H, H, u64p, H, H, H],
         "he_bgv_mul_relin": [H, i, C.c_uint64, H, H, H, H, H, H, H, H],
         "he_probe_modmul": [H, i, C.POINTER(C.c_double)], "he_probe_modmul_f64": [H, i, C.POINTER(C.c_double)],
         "he_debug_arith": [H, i, i, sz, u64p, u64p, u64p, u64p, u64p],
@@ -275,6 +278,9 @@ _TRACE_FNS_BRIDGE = {"he_unfold_conjugate_invariant_to_standard": (67, "ihh"), "
 _TRACE_FNS_BFV = {"he_bfv_mul_relin": (71, "hihhhhhhhh"), "he_bfv_quantize": (72, "hihhh")}
 # the product entries of include/hering_lintrans.h, numbered on in a table of their own
 _TRACE_FNS_LINTRANS = {"he_lintrans_evaluate": (73, "hhihhhhh"), "he_lintrans_evaluate_many": (74, "hhihhiHHH")}
+# the entries of include/hering_ckks_evaluator.h, numbered on in a table of their own
+_TRACE_FNS_CKKS_EVALUATOR = {"he_ckks_add": (75, "hiiiHiHiAiH"), "he_ckks_scalar": (76, "hiiiHAAAH"), "he_ckks_mul_pt": (77, "hiiHhiAH"),
+                             "he_ckks_mul_relin_then_add": (78, "hihhhhhAhhh")}
 # length of the arrays of a call: (function, argument index) -> index of the argument holding it (+1 for "level" arguments); a
 # tuple of indices: the product of those arguments
 _TRACE_LEN = {("he_mul_rns_scalar_montgomery", 3): (1, 1), ("he_add_scalar_bigint", 3): (4, 0), ("he_sub_scalar_bigint", 3): (4, 0),
@@ -287,6 +293,10 @@ _TRACE_LEN[("he_rgsw_external_product_select", 4)] = (5, 0)
 _TRACE_LEN[("he_automorphism_ct_select", 4)] = (5, 0)
 _TRACE_LEN[("he_blind_rotate_core", 1)] = ((2, 3), 0)
 _TRACE_LEN.update({("he_lintrans_evaluate_many", k): (5, 0) for k in (6, 7, 8)})
+_TRACE_LEN.update({("he_ckks_add", 4): (3, 0), ("he_ckks_add", 6): (5, 0), ("he_ckks_add", 8): (1, 1), ("he_ckks_add", 10): (9, 0)})
+_TRACE_LEN.update({("he_ckks_scalar", 4): (3, 0), ("he_ckks_scalar", 8): (3, 0)})
+_TRACE_LEN.update({("he_ckks_scalar", k): (1, 1) for k in (5, 6, 7)})
+_TRACE_LEN.update({("he_ckks_mul_pt", 3): (2, 0), ("he_ckks_mul_pt", 7): (2, 0), ("he_ckks_mul_pt", 6): (1, 1), ("he_ckks_mul_relin_then_add", 7): (1, 1)})
 # calls a replay has no use for: they read, wait or account, and do not change what the replayed calls see
 _TRACE_IGNORE = {"he_ctx_sync", "he_last_error", "he_alg_bytes", "he_timer_start", "he_timer_stop", "he_poly_download", "he_poly_shape",
                  "he_poly_download_limb", "he_prof_begin", "he_prof_end", "he_prof_end_bytes", "he_ctx_coalescing_stats",
@@ -352,7 +362,7 @@ def trace_begin():
     import inspect  # noqa: F401
 
     def wrap(name, fn):
-        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name) or _TRACE_FNS_BFV.get(name) or _TRACE_FNS_LINTRANS.get(name)
+        spec = _TRACE_FNS.get(name) or _TRACE_FNS_RGSW.get(name) or _TRACE_FNS_BLINDROT.get(name) or _TRACE_FNS_BRIDGE.get(name) or _TRACE_FNS_BFV.get(name) or _TRACE_FNS_LINTRANS.get(name) or _TRACE_FNS_CKKS_EVALUATOR.get(name)
 
         def call(*a):
             rc = fn(*a)

@@ -57,6 +57,7 @@
 #include "../../include/hering_blindrot.h"
 #include "../../include/hering_lintrans.h"
 #include "../../include/hering_polyeval.h"
+#include "../../include/hering_ckks_evaluator.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "ks_route.h"
@@ -118,7 +119,7 @@ enum CoOp {
     CO_DECOMPOSE_SPLIT, CO_DECOMPOSE_NTT, CO_GP_LAZY, CO_GP_HOISTED_LAZY, CO_GP_HOISTED, CO_MODDOWN, CO_EVAL_MODDOWN,
     CO_AUTO_HOISTED, CO_AUTO_HOISTED_LAZY, CO_CENTERED_LIFT, CO_DECOMP_FILL, CO_LINTRANS, CO_MUL, CO_COPY, CO_ZERO, CO_GIANT_STEP,
     CO_RING_SWITCH, CO_APPLY_EVK, CO_RING_PACK, CO_RINGPACK_CT, CO_RGSW, CO_AUTO_SELECT, CO_BLINDROT,
-    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE, CO_LINTRANS_EVAL, CO_POLY_LEAVES
+    CO_CI_BRIDGE, CO_CI_BRIDGE_CT, CO_BFV_MUL, CO_BFV_QUANTIZE, CO_LINTRANS_EVAL, CO_POLY_LEAVES, CO_CT_LIN, CO_TENSOR_ADD
 };
 // kinds of CO_RING_PACK (par[0]): the entries of include/hering_ringpack.h that address a ring
 enum { RP_XPOW2 = 0, RP_SPLIT, RP_MERGE, RP_EXPAND, RP_PACK_PRE, RP_PACK_POST };
@@ -4514,6 +4515,188 @@ int he_ckks_mul_relin(he_handle ev, int level, he_handle a0, he_handle a1, he_ha
 }
 int he_bgv_mul_relin(he_handle ev, int level, uint64_t t, he_handle a0, he_handle a1, he_handle b0, he_handle b1, he_handle rlk, he_handle o0, he_handle o1, he_handle o2) {
     return mul_relin_common(ev, level, true, t, a0, a1, b0, b1, rlk, o0, o1, o2, "he_bgv_mul_relin");
+}
+
+// ---------------------------------------------------------------------------------------
+// ckks.Evaluator (include/hering_ckks_evaluator.h; schemes/ckks/evaluator.go): the linear forms over a whole ciphertext and
+// MulRelinThenAdd, one queued request and one launch of ct_lin_kernel / tensor_add_kernel each
+// ---------------------------------------------------------------------------------------
+// the residues of an integer on the limbs 0 .. level, each below its modulus: as they are, or in Montgomery form
+static int ckks_words(const Ring &r, int level, const uint64_t *w, bool mont, uint64_t *out, const char *who, const char *name) {
+    for (int i = 0; i <= level; i++) {
+        const ModConst &m = r.sub[i].mc;
+        if (w[i] >= m.q) return fail(HE_EINVAL, "%s: %s[%d] is not below its modulus", who, name, i);
+        out[i] = mont ? mform(w[i], m.q, m.brc0, m.brc1) : w[i];
+    }
+    return HE_OK;
+}
+static int ckks_list(const char *who, const char *name, int n, const he_handle *h) {
+    if (n < 1 || n > 3 || !h) return fail(HE_EINVAL, "%s: %s must hold 1 to 3 components", who, name);
+    return HE_OK;
+}
+// files the request of one ct_lin_kernel launch: the operands were declared x (n_x of them), y (a.ny), z (n_x or a.nz) in this
+// order; a.nx / a.nz may be smaller than the declared lists (the scalar Add / Sub in place moves no other component)
+static int ct_lin_file(const std::shared_ptr<Ring> &r, int level, CoReq &q, const CtLinArgs &a, int n_x, int n_z, int B) {
+    q.op = CO_CT_LIN; q.obj = r.get(); q.par[0] = level; q.par[1] = a.form; q.par[2] = a.scaled;
+    q.par[3] = a.nx | (a.ny << 4) | (a.nz << 8); q.par[4] = n_x | (n_z << 4);
+    q.blob.assign(a.r, a.r + level + 1);
+    q.blob.insert(q.blob.end(), a.s, a.s + level + 1);
+    q.blob.insert(q.blob.end(), a.s2, a.s2 + level + 1);
+    q.keep.push_back(r);
+    q.run = [r, level, a, n_x](const View *v, int B) -> int {
+        CtLinArgs k = a;
+        double shared = 0.0;  // a batch-1 operand is read once for the whole batch
+        for (int i = 0; i < k.nx; i++) k.x[i] = v[i];
+        for (int i = 0; i < k.ny; i++) { k.y[i] = v[n_x + i]; shared += (double)(k.y[i].bstride == 0 && !k.y[i].tab && B > 1); }
+        for (int i = 0; i < k.nz; i++) k.z[i] = v[n_x + a.ny + i];
+        r->ctx->acct((ct_lin_passes(k) - shared) * (level + 1), shared * (level + 1), B, r->N);
+        const bool acc = k.form == CT_SCALAR_MUL_ADD || k.form == CT_PT_MUL_ADD;
+        double muls = 0.0;  // modular products per coefficient of a limb
+        if (k.form == CT_ADD || k.form == CT_SUB) muls = k.scaled == 1 ? k.nx : (k.scaled == 2 ? k.ny : 0);
+        else if (k.form != CT_SCALAR_ADD && k.form != CT_SCALAR_SUB)
+            muls = k.nx + ((k.form == CT_PT_MUL || k.form == CT_PT_MUL_ADD) ? 1 : 0) + (acc && k.scaled ? k.nz : 0);
+        if (muls > 0) { Valu V(r->logN); for (int i = 0; i <= level; i++) V.mul(cls_f64(r->small, i), muls); V.into(*r->ctx, B); }
+        HIP_TRY(launch_ct_lin(r->dev, k, B, r->ctx->stream));
+        return HE_OK;
+    };
+    return co_dispatch(*r->ctx, B, q);
+}
+int he_ckks_add(he_handle hring, int level, int sub, int n0, const he_handle *op0, int n1, const he_handle *op1, int scaled,
+                const uint64_t *ratio, int n_out, const he_handle *out) {
+    GET(r, Ring, hring, T_RING);
+    const char *who = "he_ckks_add";
+    TRY(check_level(*r, level, who));
+    TRY(ckks_list(who, "op0", n0, op0));
+    TRY(ckks_list(who, "op1", n1, op1));
+    TRY(ckks_list(who, "out", n_out, out));
+    if (n_out != std::max(n0, n1)) return fail(HE_EINVAL, "%s: out has %d components, max(%d, %d) expected", who, n_out, n0, n1);
+    if ((sub != 0 && sub != 1) || scaled < 0 || scaled > 2 || (scaled && !ratio)) return fail(HE_EINVAL, "%s: bad arguments", who);
+    if (r->N < 4) return fail(HE_EINVAL, "%s: ring degree %d, at least 4 needed", who, r->N);
+    CtLinArgs a{};
+    a.form = sub ? CT_SUB : CT_ADD; a.scaled = scaled; a.nx = n0; a.ny = n1; a.nz = n_out; a.nlimbs = level + 1;
+    if (scaled) TRY(ckks_words(*r, level, ratio, true, a.r, who, "ratio"));
+    CoReq q;
+    Operands o(q, who, *r);
+    for (int i = 0; i < n0; i++) o.in(op0[i], level + 1, "op0");
+    for (int i = 0; i < n1; i++) o.in(op1[i], level + 1, "op1", Operands::kBroadcast);
+    for (int i = 0; i < n_out; i++) o.out(out[i], level + 1, "out");
+    o.all_inplace = true;  // any output may be any input: a thread reads every input word of its coefficients before it writes
+    TRY(o.check());
+    return ct_lin_file(r, level, q, a, n0, n_out, o.B);
+}
+int he_ckks_scalar(he_handle hring, int level, int op, int n, const he_handle *op0, const uint64_t *s0, const uint64_t *s1,
+                   const uint64_t *pre, const he_handle *out) {
+    GET(r, Ring, hring, T_RING);
+    const char *who = "he_ckks_scalar";
+    TRY(check_level(*r, level, who));
+    TRY(ckks_list(who, "op0", n, op0));
+    TRY(ckks_list(who, "out", n, out));
+    if (op < HE_CKKS_SCALAR_ADD || op > HE_CKKS_SCALAR_MUL_THEN_ADD || !s0 || !s1) return fail(HE_EINVAL, "%s: bad arguments", who);
+    if (pre && op != HE_CKKS_SCALAR_MUL_THEN_ADD) return fail(HE_EINVAL, "%s: pre is taken by HE_CKKS_SCALAR_MUL_THEN_ADD only", who);
+    if (r->N < 4) return fail(HE_EINVAL, "%s: ring degree %d, at least 4 needed", who, r->N);
+    static const int forms[4] = {CT_SCALAR_ADD, CT_SCALAR_SUB, CT_SCALAR_MUL, CT_SCALAR_MUL_ADD};
+    CtLinArgs a{};
+    a.form = forms[op]; a.scaled = pre ? 1 : 0; a.nx = a.nz = n; a.ny = 0; a.nlimbs = level + 1;
+    const bool mont = op >= HE_CKKS_SCALAR_MUL;  // MulDoubleRNSScalar takes MForm of the scalars (ring/operations.go:249-268)
+    TRY(ckks_words(*r, level, s0, mont, a.s, who, "s0"));
+    TRY(ckks_words(*r, level, s1, mont, a.s2, who, "s1"));
+    if (pre) TRY(ckks_words(*r, level, pre, true, a.r, who, "pre"));
+    CoReq q;
+    Operands o(q, who, *r);
+    for (int i = 0; i < n; i++) o.in(op0[i], level + 1, "op0");
+    for (int i = 0; i < n; i++) o.out(out[i], level + 1, "out");
+    o.all_inplace = true;
+    TRY(o.check());
+    if (op <= HE_CKKS_SCALAR_SUB) {  // in place (:82-86): the components past the first stay where they are
+        bool same = true;
+        for (int i = 1; i < n; i++) same = same && o.same(i, n + i);
+        if (same) a.nx = a.nz = 1;
+    }
+    return ct_lin_file(r, level, q, a, n, n, o.B);
+}
+int he_ckks_mul_pt(he_handle hring, int level, int n, const he_handle *ct, he_handle pt, int then_add, const uint64_t *pre,
+                   const he_handle *out) {
+    GET(r, Ring, hring, T_RING);
+    const char *who = "he_ckks_mul_pt";
+    TRY(check_level(*r, level, who));
+    TRY(ckks_list(who, "ct", n, ct));
+    TRY(ckks_list(who, "out", n, out));
+    if (then_add != 0 && then_add != 1) return fail(HE_EINVAL, "%s: bad arguments", who);
+    if (pre && !then_add) return fail(HE_EINVAL, "%s: pre is taken with then_add only", who);
+    if (r->N < 4) return fail(HE_EINVAL, "%s: ring degree %d, at least 4 needed", who, r->N);
+    CtLinArgs a{};
+    a.form = then_add ? CT_PT_MUL_ADD : CT_PT_MUL; a.scaled = pre ? 1 : 0; a.nx = a.nz = n; a.ny = 1; a.nlimbs = level + 1;
+    if (pre) TRY(ckks_words(*r, level, pre, true, a.r, who, "pre"));
+    CoReq q;
+    Operands o(q, who, *r);
+    for (int i = 0; i < n; i++) o.in(ct[i], level + 1, "ct");
+    o.in(pt, level + 1, "pt", Operands::kBroadcast);
+    for (int i = 0; i < n; i++) o.out(out[i], level + 1, "out");
+    o.all_inplace = true;
+    TRY(o.check());
+    return ct_lin_file(r, level, q, a, n, n, o.B);
+}
+int he_ckks_mul_relin_then_add(he_handle hev, int level, he_handle ha0, he_handle ha1, he_handle hb0, he_handle hb1, he_handle hk,
+                               const uint64_t *pre, he_handle hout0, he_handle hout1, he_handle hout2) {
+    GET(ev, Evaluator, hev, T_EVAL);
+    const char *who = "he_ckks_mul_relin_then_add";
+    std::shared_ptr<Evk> k;
+    BasisExtender &be = *ev->be;
+    if (level < 0 || level >= be.LQ) return fail(HE_EINVAL, "%s: level out of range", who);
+    if (be.Q->N < 4) return fail(HE_EINVAL, "%s: ring degree %d, at least 4 needed", who, be.Q->N);
+    if (hk) {
+        k = get<Evk>(hk, T_EVK);
+        if (!k) return fail(HE_EHANDLE, "%s: bad relinearization key handle", who);
+        int lv = level;
+        TRY(check_key(*ev, *k, lv, who));
+        if (lv != level) return fail(HE_EINVAL, "%s: relinearization key level %d below ciphertext level %d", who, k->nQk - 1, level);
+        if (hout2) return fail(HE_EINVAL, "%s: out2 must be 0 when a relinearization key is given", who);
+    }
+    TensorAddArgs t{};
+    t.nlimbs = level + 1; t.has_r = pre ? 1 : 0;
+    if (pre) TRY(ckks_words(*be.Q, level, pre, true, t.r, who, "pre"));
+    CoReq q;
+    Operands o(q, who, be);
+    o.in(ha0, level + 1, "a0");
+    o.in(ha1, level + 1, "a1");
+    o.in(hb0, level + 1, "b0");
+    o.in(hb1, level + 1, "b1");
+    o.out(hout0, level + 1, "out0");
+    o.out(hout1, level + 1, "out1");
+    o.out(k ? nullptr : o.poly(hout2), level + 1, "out2 (required when no relinearization key is given)");
+    TRY(o.check());  // (no in-place form: an output that is an input is the reference's error, evaluator.go:918, :1064)
+    if (!k && !q.ops[6].p) return fail(HE_EINVAL, "%s: out2 is required when no relinearization key is given", who);
+    ks_request(q, CO_TENSOR_ADD, ev, k, level, KS_GADGET_PRODUCT, KsAlias{});
+    q.par[1] = t.has_r;
+    q.blob.assign(t.r, t.r + level + 1);
+    q.run = [ev, k, level, t](const View *v, int B) -> int {
+        BasisExtender &be = *ev->be;
+        const int N = be.Q->N;
+        TensorAddArgs a = t;
+        a.a0 = v[0]; a.a1 = v[1]; a.b0 = v[2]; a.b1 = v[3]; a.acc0 = a.c0 = v[4]; a.acc1 = a.c1 = v[5];
+        {
+            Valu V(be.Q->logN);
+            for (int i = 0; i <= level; i++) V.mul(cls_f64(be.small, i), 6.0 + (a.has_r ? (k ? 2.0 : 3.0) : 0.0));
+            V.into(*be.ctx, B);
+        }
+        be.ctx->acct((k ? 9.0 : 10.0) * (level + 1), 0, B, N);  // four inputs, the accumulators in, three outputs
+        if (!k) {
+            a.acc2 = a.c2 = v[6];
+            HIP_TRY(launch_tensor_add(be.qp, a, B, be.ctx->stream));
+            return HE_OK;
+        }
+        // with a key: c2 to scratch, then the gadget product with the accumulated (c0, c1) as the ModDown epilogue's addends --
+        // he_relinearize in place on (out0, out1)
+        const size_t wQ = (size_t)B * (level + 1) * N;
+        TRY(keyswitch_begin(*ev, *k, level, 5.0 * (level + 1), true, B, wQ + 4));
+        View c2{be.ctx->arena_take(wQ), (size_t)(level + 1) * N};
+        a.acc2 = View{nullptr, 0}; a.c2 = c2;
+        HIP_TRY(launch_tensor_add(be.qp, a, B, be.ctx->stream));
+        GpArgs g{&c2, nullptr, v[4], v[5], B, &v[4], &v[5]};
+        g.cx_canonical = true;  // c2 is formed here
+        return key_switch(*ev, KS_GADGET_PRODUCT, level, *k, KsAlias{}, g);
+    };
+    return co_dispatch(*be.ctx, o.B, q);
 }
 
 // ---------------------------------------------------------------------------------------

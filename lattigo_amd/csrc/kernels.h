@@ -717,6 +717,43 @@ hipError_t launch_pack_step(const RingDev &r, const uint64_t *tab, View t0, View
 hipError_t launch_tensor(const RingDev &r, const LimbTab &tab, const uint64_t *scalar, View a0, View a1, View b0, View b1,
                          View c0, View c1, View c2, int batch, hipStream_t s);
 
+// ---- the CKKS evaluator's linear forms over a whole ciphertext (include/hering_ckks_evaluator.h) ----------------------------
+// ONE launch for all components: a thread owns its pair of adjacent coefficients of EVERY component of the operation, reads every
+// input word of them and only then writes, so any output may be any input (crossed components included) and an operand shared
+// by the components -- the plaintext and its Montgomery form, the Montgomery form of a scalar -- is loaded or formed once.
+// Limbs 0 .. nlimbs - 1 of every operand, identity limb map; every view may carry an entry table.  N >= 4: a pair never straddles
+// N/2.  Forms (schemes/ckks/evaluator.go), with [r] = MRed(., r[limb]) where `scaled` says so, i over the components:
+//   CT_ADD / CT_SUB (evaluateInPlace :221-408; scaled 1: x is multiplied first, 2: y): z_i = CRed([r] x_i +- [r] y_i) for
+//     i < min(nx, ny); beyond it z_i = [r] x_i, or [r] y_i / q - [r] y_i (Ring.Neg's word, :153-156) when they come from y
+//   CT_SCALAR_ADD / CT_SCALAR_SUB (:80-86, :171-177): z_0 = CRed(x_0 +- s), z_i = x_i for 0 < i < nx (nx = 1: no copies)
+//   CT_SCALAR_MUL (:629-666): z_i = MRed(x_i, s)
+//   CT_SCALAR_MUL_ADD (:928-975; scaled 1: the accumulator is multiplied first, :959-964): z_i = CRed([r] z_i + MRed(x_i, s))
+//   CT_PT_MUL (:842-869): m = MRed(y_0, 2^128 mod q) once, z_i = MRed(x_i, m)
+//   CT_PT_MUL_ADD (:1158-1170; scaled 1: :1087-1096): z_i = CRed([r] z_i + MRed(x_i, m))
+// s: s[limb] for the coefficients [0, N/2), s2[limb] for [N/2, N); r, s, s2 of the multiplying forms are in Montgomery form.
+enum CtLinForm { CT_ADD = 0, CT_SUB, CT_SCALAR_ADD, CT_SCALAR_SUB, CT_SCALAR_MUL, CT_SCALAR_MUL_ADD, CT_PT_MUL, CT_PT_MUL_ADD, CT_FORM_COUNT };
+struct CtLinArgs {
+    int form, scaled;
+    int nx, ny, nz;      // components of x, of y (CT_PT_*: 1, the plaintext; the scalar forms: 0) and of z
+    View x[3], y[3], z[3];
+    int nlimbs;
+    uint64_t r[kMaxLimbs], s[kMaxLimbs], s2[kMaxLimbs];
+};
+hipError_t launch_ct_lin(const RingDev &r, const CtLinArgs &a, int batch, hipStream_t s);
+double ct_lin_passes(const CtLinArgs &a);  // limb-polynomials one launch reads and writes, per limb and batch entry
+
+// The ciphertext product accumulated onto a ciphertext (mulRelinThenAdd, schemes/ckks/evaluator.go:1104-1155), one launch:
+//   c0 = CRed([r] acc0 + T(a0, b0)), c1 = CRed([r] acc1 + CRed(T(a0, b1) + T(a1, b0))), T(x, y) = MRed(MRed(x, 2^128 mod q), y),
+//   c2 = T(a1, b1) when acc2 is absent (the relinearizing form: c2 goes to scratch), else CRed([r] acc2 + T(a1, b1)).
+// has_r: the accumulators are first multiplied by the integer whose Montgomery residues are r[limb] (:1087-1096).  c_i may be
+// acc_i (that is the entry's only form); every view may carry an entry table.
+struct TensorAddArgs {
+    View a0, a1, b0, b1, acc0, acc1, acc2, c0, c1, c2;
+    int nlimbs, has_r;
+    uint64_t r[kMaxLimbs];
+};
+hipError_t launch_tensor_add(const RingDev &r, const TensorAddArgs &a, int batch, hipStream_t s);
+
 // ---- per-kernel HIP-event profiling (diagnostics: bench.py's roofline leg) --------------------
 enum KernelId {
     K_NTT_COLS_FWD = 0, K_NTT_ROWS_FWD, K_NTT_ROWS_INV, K_NTT_COLS_INV, K_EW, K_GATHER, K_AUTO_COEFF, K_INDEX,
@@ -727,7 +764,7 @@ enum KernelId {
     K_BGV_SLOTS_TO_T, K_BGV_T_TO_SLOTS, K_BGV_T_TO_RNS, K_BGV_RNS_TO_T,
     K_SAMPLER_UNIFORM, K_SAMPLER_UNIFORM_CHAIN, K_SAMPLER_GAUSSIAN, K_SAMPLER_TERNARY_KY, K_SAMPLER_TERNARY_HALF, K_SAMPLER_EXPAND,
     K_EVK_FINISH, K_GADGET_ADD, K_RGSW_TABLE_FINISH, K_GADGET_AGGREGATE, K_RKG_ROUND_ONE, K_RKG_ROUND_TWO, K_RLK_FINALIZE,
-    K_DIAG_MAC_GROUP, K_POLY_LEAF_GROUP, K_COUNT
+    K_DIAG_MAC_GROUP, K_POLY_LEAF_GROUP, K_CT_LIN, K_TENSOR_ADD, K_COUNT
 };
 const char *kernel_name(int id);
 void prof_begin(hipStream_t s);                                // start recording the launches enqueued on stream s

@@ -79,7 +79,7 @@ const char *kernel_name(int id) {
                                          "bgv_t_to_rns", "bgv_rns_to_t", "sampler_uniform", "sampler_uniform_chain", "sampler_gaussian",
                                          "sampler_ternary_ky", "sampler_ternary_half", "sampler_expand", "evk_finish", "gadget_add",
                                          "rgsw_table_finish", "gadget_aggregate", "rkg_round_one", "rkg_round_two",
-                                         "rlk_finalize", "diag_mac_group", "poly_leaf_group"};
+                                         "rlk_finalize", "diag_mac_group", "poly_leaf_group", "ct_lin", "tensor_add"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 bool prof_active(hipStream_t s) {
@@ -4729,6 +4729,189 @@ hipError_t launch_tensor(const RingDev &r, const LimbTab &tab, const uint64_t *s
     // a1, b1 -> c2 always; a0, b0 -> c0, c1 when those outputs exist
     ProfScope ps(K_TENSOR, s, (c0.p ? 7.0 : 3.0) * tab.n * batch * (double)r.N * 8.0);
     hipLaunchKernelGGL(tensor_kernel, grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// the CKKS evaluator's linear forms over every component of a ciphertext, and the ciphertext product accumulated onto a
+// ciphertext: one launch each (see kernels.h).  Two adjacent coefficients per thread, as in ew_kernel and tensor_kernel.
+// ------------------------------------------------------------------------------------
+struct CtLinKArgs {
+    const uint64_t *x[3], *y[3];
+    uint64_t *z[3];
+    size_t x_bs[3], y_bs[3], z_bs[3];
+    const size_t *x_tab[3], *y_tab[3], *z_tab[3];  // entry tables (View::tab)
+    const ModConst *mc;
+    int N, nx, ny, nz;
+    uint64_t r[kMaxLimbs], s[kMaxLimbs], s2[kMaxLimbs];
+};
+// FORM and SC are compile-time: a thread branches only on the component counts, which are uniform over the launch.  Every load
+// of a coefficient pair precedes every store of it (the outputs may be the inputs in any arrangement).
+template <int FORM, int SC>
+__global__ void __launch_bounds__(256) ct_lin_kernel(const CtLinKArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int l = blockIdx.y;
+    const ModConst m = A.mc[l];
+    const uint64_t q = m.q, qinv = m.qinv;
+    const size_t bz = blockIdx.z, pos = (size_t)l * A.N + j;
+    constexpr bool kAddSub = FORM == CT_ADD || FORM == CT_SUB;
+    constexpr bool kAcc = FORM == CT_SCALAR_MUL_ADD || FORM == CT_PT_MUL_ADD;
+    constexpr bool kPt = FORM == CT_PT_MUL || FORM == CT_PT_MUL_ADD;
+    ulonglong2 xv[3], yv[3], zv[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        xv[i] = yv[i] = zv[i] = make_ulonglong2(0, 0);
+        if (i < A.nx) xv[i] = ldnt2(A.x[i] + voff(A.x_tab[i], A.x_bs[i], bz) + pos);
+        if constexpr (kAddSub) { if (i < A.ny) yv[i] = ldnt2(A.y[i] + voff(A.y_tab[i], A.y_bs[i], bz) + pos); }
+        if constexpr (kAcc) { if (i < A.nz) zv[i] = ldnt2(A.z[i] + voff(A.z_tab[i], A.z_bs[i], bz) + pos); }
+    }
+    if constexpr (kPt) yv[0] = ldnt2(A.y[0] + voff(A.y_tab[0], A.y_bs[0], bz) + pos);
+    const uint64_t r = A.r[l];
+    uint64_t w0 = (j >= (A.N >> 1)) ? A.s2[l] : A.s[l], w1 = w0;  // the multiplier of either coefficient
+    if constexpr (kPt) { w0 = mred(yv[0].x, m.r2, q, qinv); w1 = mred(yv[0].y, m.r2, q, qinv); }  // MForm(pt), once for all components
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        if (i >= A.nz) break;
+        ulonglong2 a = xv[i], b = yv[i], o;
+        if constexpr (kAddSub) {
+            if (SC == 1 && i < A.nx) { a.x = mred(a.x, r, q, qinv); a.y = mred(a.y, r, q, qinv); }
+            if (SC == 2 && i < A.ny) { b.x = mred(b.x, r, q, qinv); b.y = mred(b.y, r, q, qinv); }
+            if (i < A.nx && i < A.ny) {
+                o.x = FORM == CT_SUB ? cred(a.x + q - b.x, q) : cred(a.x + b.x, q);
+                o.y = FORM == CT_SUB ? cred(a.y + q - b.y, q) : cred(a.y + b.y, q);
+            } else if (i < A.nx) {
+                o = a;
+            } else {  // the tail of y: a copy, or Ring.Neg's word q - y (q for a zero)
+                o.x = FORM == CT_SUB ? q - b.x : b.x;
+                o.y = FORM == CT_SUB ? q - b.y : b.y;
+            }
+        } else if constexpr (FORM == CT_SCALAR_ADD || FORM == CT_SCALAR_SUB) {
+            o = a;
+            if (i == 0) {
+                o.x = FORM == CT_SCALAR_SUB ? cred(a.x + q - w0, q) : cred(a.x + w0, q);
+                o.y = FORM == CT_SCALAR_SUB ? cred(a.y + q - w1, q) : cred(a.y + w1, q);
+            }
+        } else {
+            o.x = mred(a.x, w0, q, qinv);
+            o.y = mred(a.y, w1, q, qinv);
+            if constexpr (kAcc) {
+                ulonglong2 c = zv[i];
+                if constexpr (SC == 1) { c.x = mred(c.x, r, q, qinv); c.y = mred(c.y, r, q, qinv); }
+                o.x = cred(c.x + o.x, q);
+                o.y = cred(c.y + o.y, q);
+            }
+        }
+        *reinterpret_cast<ulonglong2 *>(A.z[i] + voff(A.z_tab[i], A.z_bs[i], bz) + pos) = o;
+    }
+}
+double ct_lin_passes(const CtLinArgs &a) {
+    const bool acc = a.form == CT_SCALAR_MUL_ADD || a.form == CT_PT_MUL_ADD;
+    return (double)a.nx + a.ny + a.nz + (acc ? a.nz : 0);
+}
+hipError_t launch_ct_lin(const RingDev &r, const CtLinArgs &a, int batch, hipStream_t s) {
+    if (a.nlimbs <= 0 || batch <= 0) return hipSuccess;
+    const bool addsub = a.form == CT_ADD || a.form == CT_SUB, acc = a.form == CT_SCALAR_MUL_ADD || a.form == CT_PT_MUL_ADD;
+    const bool pt = a.form == CT_PT_MUL || a.form == CT_PT_MUL_ADD;
+    if (r.N < 4 || a.nlimbs > kMaxLimbs || a.form < 0 || a.form >= CT_FORM_COUNT || a.nx < 1 || a.nx > 3 || a.nz < 1 || a.nz > 3 ||
+        (!addsub && a.ny != (pt ? 1 : 0)) || (addsub && (a.ny < 1 || a.ny > 3 || a.nz != (a.nx > a.ny ? a.nx : a.ny))) ||
+        (!addsub && a.nz != a.nx) || a.scaled < 0 || a.scaled > (addsub ? 2 : (acc ? 1 : 0)))
+        return hipErrorInvalidValue;
+    CtLinKArgs A{};
+    A.mc = r.mc; A.N = r.N; A.nx = a.nx; A.ny = a.ny; A.nz = a.nz;
+    for (int i = 0; i < 3; i++) {
+        if (i < a.nx) { if (!a.x[i].p) return hipErrorInvalidValue; A.x[i] = a.x[i].p; A.x_bs[i] = a.x[i].bstride; A.x_tab[i] = a.x[i].tab; }
+        if (i < a.ny) { if (!a.y[i].p) return hipErrorInvalidValue; A.y[i] = a.y[i].p; A.y_bs[i] = a.y[i].bstride; A.y_tab[i] = a.y[i].tab; }
+        if (i < a.nz) { if (!a.z[i].p) return hipErrorInvalidValue; A.z[i] = a.z[i].p; A.z_bs[i] = a.z[i].bstride; A.z_tab[i] = a.z[i].tab; }
+    }
+    for (int i = 0; i < a.nlimbs; i++) { A.r[i] = a.r[i]; A.s[i] = a.s[i]; A.s2[i] = a.s2[i]; }
+    dim3 grid((unsigned)((r.N / 2 + 255) / 256), a.nlimbs, batch), block(256);
+    ProfScope ps(K_CT_LIN, s, ct_lin_passes(a) * a.nlimbs * batch * (double)r.N * 8.0);
+#define HE_CTL(F, S) hipLaunchKernelGGL((ct_lin_kernel<F, S>), grid, block, 0, s, A)
+    switch (a.form) {
+        case CT_ADD: if (a.scaled == 0) HE_CTL(CT_ADD, 0); else if (a.scaled == 1) HE_CTL(CT_ADD, 1); else HE_CTL(CT_ADD, 2); break;
+        case CT_SUB: if (a.scaled == 0) HE_CTL(CT_SUB, 0); else if (a.scaled == 1) HE_CTL(CT_SUB, 1); else HE_CTL(CT_SUB, 2); break;
+        case CT_SCALAR_ADD: HE_CTL(CT_SCALAR_ADD, 0); break;
+        case CT_SCALAR_SUB: HE_CTL(CT_SCALAR_SUB, 0); break;
+        case CT_SCALAR_MUL: HE_CTL(CT_SCALAR_MUL, 0); break;
+        case CT_SCALAR_MUL_ADD: if (a.scaled) HE_CTL(CT_SCALAR_MUL_ADD, 1); else HE_CTL(CT_SCALAR_MUL_ADD, 0); break;
+        case CT_PT_MUL: HE_CTL(CT_PT_MUL, 0); break;
+        default: if (a.scaled) HE_CTL(CT_PT_MUL_ADD, 1); else HE_CTL(CT_PT_MUL_ADD, 0); break;
+    }
+#undef HE_CTL
+    return hipGetLastError();
+}
+
+struct TensorAddKArgs {
+    const uint64_t *a0, *a1, *b0, *b1, *acc0, *acc1, *acc2;
+    uint64_t *c0, *c1, *c2;
+    size_t a0_bs, a1_bs, b0_bs, b1_bs, acc0_bs, acc1_bs, acc2_bs, c0_bs, c1_bs, c2_bs;
+    const size_t *a0_tab, *a1_tab, *b0_tab, *b1_tab, *acc0_tab, *acc1_tab, *acc2_tab, *c0_tab, *c1_tab, *c2_tab;  // entry tables (View::tab)
+    const ModConst *mc;
+    int N;
+    uint64_t r[kMaxLimbs];
+};
+template <bool PRE, bool ACC2>
+__global__ void __launch_bounds__(256) tensor_add_kernel(const TensorAddKArgs A) {
+    const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (j >= A.N) return;
+    const int l = blockIdx.y;
+    const ModConst m = A.mc[l];
+    const uint64_t q = m.q, qinv = m.qinv, r = A.r[l];
+    const size_t bz = blockIdx.z, pos = (size_t)l * A.N + j;
+    const ulonglong2 a0 = ldnt2(A.a0 + voff(A.a0_tab, A.a0_bs, bz) + pos), a1 = ldnt2(A.a1 + voff(A.a1_tab, A.a1_bs, bz) + pos);
+    const ulonglong2 b0 = ldnt2(A.b0 + voff(A.b0_tab, A.b0_bs, bz) + pos), b1 = ldnt2(A.b1 + voff(A.b1_tab, A.b1_bs, bz) + pos);
+    ulonglong2 e0 = ldnt2(A.acc0 + voff(A.acc0_tab, A.acc0_bs, bz) + pos), e1 = ldnt2(A.acc1 + voff(A.acc1_tab, A.acc1_bs, bz) + pos);
+    ulonglong2 e2 = make_ulonglong2(0, 0);
+    if constexpr (ACC2) e2 = ldnt2(A.acc2 + voff(A.acc2_tab, A.acc2_bs, bz) + pos);
+    if constexpr (PRE) {
+        e0.x = mred(e0.x, r, q, qinv); e0.y = mred(e0.y, r, q, qinv);
+        e1.x = mred(e1.x, r, q, qinv); e1.y = mred(e1.y, r, q, qinv);
+        if constexpr (ACC2) { e2.x = mred(e2.x, r, q, qinv); e2.y = mred(e2.y, r, q, qinv); }
+    }
+    ulonglong2 c0, c1, c2;
+    {
+        const uint64_t t0 = mred(a0.x, m.r2, q, qinv), t1 = mred(a1.x, m.r2, q, qinv);
+        c0.x = cred(e0.x + mred(t0, b0.x, q, qinv), q);
+        c1.x = cred(e1.x + cred(mred(t0, b1.x, q, qinv) + mred(t1, b0.x, q, qinv), q), q);
+        c2.x = mred(t1, b1.x, q, qinv);
+    }
+    {
+        const uint64_t t0 = mred(a0.y, m.r2, q, qinv), t1 = mred(a1.y, m.r2, q, qinv);
+        c0.y = cred(e0.y + mred(t0, b0.y, q, qinv), q);
+        c1.y = cred(e1.y + cred(mred(t0, b1.y, q, qinv) + mred(t1, b0.y, q, qinv), q), q);
+        c2.y = mred(t1, b1.y, q, qinv);
+    }
+    if constexpr (ACC2) { c2.x = cred(e2.x + c2.x, q); c2.y = cred(e2.y + c2.y, q); }
+    *reinterpret_cast<ulonglong2 *>(A.c0 + voff(A.c0_tab, A.c0_bs, bz) + pos) = c0;
+    *reinterpret_cast<ulonglong2 *>(A.c1 + voff(A.c1_tab, A.c1_bs, bz) + pos) = c1;
+    *reinterpret_cast<ulonglong2 *>(A.c2 + voff(A.c2_tab, A.c2_bs, bz) + pos) = c2;
+}
+hipError_t launch_tensor_add(const RingDev &r, const TensorAddArgs &a, int batch, hipStream_t s) {
+    if (a.nlimbs <= 0 || batch <= 0) return hipSuccess;
+    if (r.N < 4 || a.nlimbs > kMaxLimbs || !a.a0.p || !a.a1.p || !a.b0.p || !a.b1.p || !a.acc0.p || !a.acc1.p || !a.c0.p || !a.c1.p || !a.c2.p)
+        return hipErrorInvalidValue;
+    TensorAddKArgs A{};
+    A.a0 = a.a0.p; A.a1 = a.a1.p; A.b0 = a.b0.p; A.b1 = a.b1.p; A.acc0 = a.acc0.p; A.acc1 = a.acc1.p; A.acc2 = a.acc2.p;
+    A.c0 = a.c0.p; A.c1 = a.c1.p; A.c2 = a.c2.p;
+    A.a0_bs = a.a0.bstride; A.a1_bs = a.a1.bstride; A.b0_bs = a.b0.bstride; A.b1_bs = a.b1.bstride;
+    A.acc0_bs = a.acc0.bstride; A.acc1_bs = a.acc1.bstride; A.acc2_bs = a.acc2.bstride;
+    A.c0_bs = a.c0.bstride; A.c1_bs = a.c1.bstride; A.c2_bs = a.c2.bstride;
+    A.a0_tab = a.a0.tab; A.a1_tab = a.a1.tab; A.b0_tab = a.b0.tab; A.b1_tab = a.b1.tab;
+    A.acc0_tab = a.acc0.tab; A.acc1_tab = a.acc1.tab; A.acc2_tab = a.acc2.tab;
+    A.c0_tab = a.c0.tab; A.c1_tab = a.c1.tab; A.c2_tab = a.c2.tab;
+    A.mc = r.mc; A.N = r.N;
+    for (int i = 0; i < a.nlimbs; i++) A.r[i] = a.has_r ? a.r[i] : 0;
+    dim3 grid((unsigned)((r.N / 2 + 255) / 256), a.nlimbs, batch), block(256);
+    // four inputs, the accumulators in, three outputs
+    ProfScope ps(K_TENSOR_ADD, s, (a.acc2.p ? 10.0 : 9.0) * a.nlimbs * batch * (double)r.N * 8.0);
+    if (a.acc2.p) {
+        if (a.has_r) hipLaunchKernelGGL((tensor_add_kernel<true, true>), grid, block, 0, s, A);
+        else hipLaunchKernelGGL((tensor_add_kernel<false, true>), grid, block, 0, s, A);
+    } else {
+        if (a.has_r) hipLaunchKernelGGL((tensor_add_kernel<true, false>), grid, block, 0, s, A);
+        else hipLaunchKernelGGL((tensor_add_kernel<false, false>), grid, block, 0, s, A);
+    }
     return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@
 #include "../../include/hering_bridge.h"
 #include "../../include/hering_bfv.h"
 #include "../../include/hering_lintrans.h"
+#include "../../include/hering_ckks_evaluator.h"
 
 namespace {
 enum Fn : uint64_t {
@@ -46,7 +47,8 @@ enum Fn : uint64_t {
     F_RGSW_EXTPROD, F_RGSW_EXTPROD_SELECT, F_AUTO_CT_SELECT, F_BLIND_ROTATE_CORE,
     F_BRIDGE_UNFOLD, F_BRIDGE_FOLD, F_COMPLEX_TO_REAL, F_REAL_TO_COMPLEX,
     F_BFV_MUL_RELIN, F_BFV_QUANTIZE,
-    F_LINTRANS_EVALUATE, F_LINTRANS_EVALUATE_MANY, F_COUNT
+    F_LINTRANS_EVALUATE, F_LINTRANS_EVALUATE_MANY,
+    F_CKKS_ADD, F_CKKS_SCALAR, F_CKKS_MUL_PT, F_CKKS_MUL_RELIN_THEN_ADD, F_COUNT
 };
 static_assert(F_COUNT <= 128, "the per-function profile has 128 slots");
 struct Arg {
@@ -200,6 +202,10 @@ int run_call(const Call &c, std::unordered_map<uint64_t, uint64_t> &map, std::ve
         case F_BFV_QUANTIZE: return he_bfv_quantize(H(0), (int)I(1), H(2), H(3), H(4));
         case F_LINTRANS_EVALUATE: return he_lintrans_evaluate(H(0), H(1), (int)I(2), H(3), H(4), H(5), H(6), H(7));
         case F_LINTRANS_EVALUATE_MANY: return he_lintrans_evaluate_many(H(0), H(1), (int)I(2), H(3), H(4), (int)I(5), HA(6), HA(7), HA(8));
+        case F_CKKS_ADD: return he_ckks_add(H(0), (int)I(1), (int)I(2), (int)I(3), HA(4), (int)I(5), HA(6), (int)I(7), A(8), (int)I(9), HA(10));
+        case F_CKKS_SCALAR: return he_ckks_scalar(H(0), (int)I(1), (int)I(2), (int)I(3), HA(4), A(5), A(6), A(7), HA(8));
+        case F_CKKS_MUL_PT: return he_ckks_mul_pt(H(0), (int)I(1), (int)I(2), HA(3), H(4), (int)I(5), A(6), HA(7));
+        case F_CKKS_MUL_RELIN_THEN_ADD: return he_ckks_mul_relin_then_add(H(0), (int)I(1), H(2), H(3), H(4), H(5), H(6), A(7), H(8), H(9), H(10));
         default: return HE_EINVAL;
     }
 }

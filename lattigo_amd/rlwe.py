@@ -892,3 +892,131 @@ def ConcurrentCalls(op: str, callers, level: int, iters: int, t: int = 0, sync_e
 def ConcurrentMulRelin(callers, level: int, iters: int, t: int = 0, sync_each: bool = False) -> float:
     """ConcurrentCalls for BGVMulRelin (t != 0) / CKKSMulRelin"""
     return ConcurrentCalls("bgv_mulrelin" if t != 0 else "ckks_mulrelin", callers, level, iters, t, sync_each)
+
+
+# ----------------------------------------------------------------------------------------------------
+# rlwe.Scale, rlwe.MetaData, rlwe.Ciphertext and rlwe.Plaintext (core/rlwe/scale.go, metadata.go, ciphertext.go, plaintext.go): what
+# ckks.Evaluator (lattigo_amd.ckks) keeps beside the device polynomials of an element.
+# ----------------------------------------------------------------------------------------------------
+ScalePrecision = 128  # core/rlwe/scale.go:17
+
+
+class Scale:
+    """rlwe.Scale: a big.Float of 128 bits.  Mul / Div round the exact result to 128 bits, nearest even; Int truncates; Float64
+    rounds to nearest even.  The value is held as the exact rational of that float (Value)."""
+
+    __slots__ = ("Value",)
+
+    def __init__(self, s=1):
+        from fractions import Fraction
+        from .polyeval import _round_bits
+        v = s.Value if isinstance(s, Scale) else Fraction(s)  # an int or a float64 is taken exactly, then rounded (NewScale, scale.go:29-56)
+        if v < 0:
+            raise ValueError("a scale cannot be negative")
+        self.Value = _round_bits(v, ScalePrecision)
+
+    def Mul(self, s1) -> "Scale":
+        return Scale(self.Value * Scale(s1).Value)
+
+    def Div(self, s1) -> "Scale":
+        return Scale(self.Value / Scale(s1).Value)
+
+    def Cmp(self, s1) -> int:
+        o = Scale(s1).Value
+        return (self.Value > o) - (self.Value < o)
+
+    def Equal(self, s1) -> bool:
+        return self.Cmp(s1) == 0
+
+    def Max(self, s1) -> "Scale":
+        return Scale(self) if self.Cmp(s1) >= 0 else Scale(s1)
+
+    def Min(self, s1) -> "Scale":
+        return Scale(self) if self.Cmp(s1) <= 0 else Scale(s1)
+
+    def Int(self) -> int:
+        return self.Value.numerator // self.Value.denominator
+
+    BigInt = Int
+
+    def Uint64(self) -> int:
+        return min(self.Int(), 0xFFFFFFFFFFFFFFFF)  # big.Float.Uint64 saturates
+
+    def Float64(self) -> float:
+        return self.Value.numerator / self.Value.denominator  # int / int is correctly rounded, ties to even
+
+    def __repr__(self):
+        return f"Scale({self.Float64()!r})"
+
+
+def NewScale(s) -> Scale:
+    return Scale(s)
+
+
+class MetaData:
+    """rlwe.MetaData (metadata.go): PlaintextMetaData (Scale, LogDimensions, IsBatched) and CiphertextMetaData (IsNTT, IsMontgomery)"""
+
+    __slots__ = ("Scale", "IsNTT", "IsMontgomery", "IsBatched", "LogDimensions")
+
+    def __init__(self, Scale_=1, IsNTT=True, IsMontgomery=False, IsBatched=True, LogDimensions=(0, 0)):
+        self.Scale, self.IsNTT, self.IsMontgomery, self.IsBatched = Scale(Scale_), IsNTT, IsMontgomery, IsBatched
+        self.LogDimensions = tuple(LogDimensions)  # (Rows, Cols)
+
+    def copy(self) -> "MetaData":
+        return MetaData(self.Scale, self.IsNTT, self.IsMontgomery, self.IsBatched, self.LogDimensions)
+
+
+class Element:
+    """rlwe.Element[ring.Poly] over device polynomials: Value[i] is a Poly of `batch` entries; the level of the element is kept
+    beside them (a Poly keeps its allocated height: Resize to a lower level drops no memory, as the reference's Resize keeps the
+    backing arrays)."""
+
+    def __init__(self, ringQ: Ring, degree: int, level: int, batch: int = 1, Value=None, MetaData_: MetaData | None = None):
+        self.ringQ, self.batch, self.level = ringQ, batch, level
+        self.Value = list(Value) if Value is not None else [Poly(ringQ, level + 1, batch) for _ in range(degree + 1)]
+        self.MetaData = MetaData_ if MetaData_ is not None else MetaData()
+
+    Scale = property(lambda self: self.MetaData.Scale, lambda self, s: setattr(self.MetaData, "Scale", Scale(s)))
+    IsNTT = property(lambda self: self.MetaData.IsNTT, lambda self, v: setattr(self.MetaData, "IsNTT", v))
+    IsBatched = property(lambda self: self.MetaData.IsBatched, lambda self, v: setattr(self.MetaData, "IsBatched", v))
+    LogDimensions = property(lambda self: self.MetaData.LogDimensions, lambda self, v: setattr(self.MetaData, "LogDimensions", tuple(v)))
+
+    def El(self):
+        return self
+
+    def Degree(self) -> int:
+        return len(self.Value) - 1
+
+    def Level(self) -> int:
+        return self.level
+
+    def Resize(self, degree: int, level: int):
+        """Element.Resize (element.go:147-176): components are dropped or added (zero), the level is lowered or raised (a raised
+        level needs the height: a component that is too short is replaced by a zero-extended copy)"""
+        self.Value = self.Value[: degree + 1]
+        for i, p in enumerate(self.Value):
+            if p.n_limbs < level + 1:
+                q = Poly(self.ringQ, level + 1, self.batch)
+                q.CopyLvl(p.n_limbs - 1, p)
+                self.Value[i] = q
+        while len(self.Value) < degree + 1:
+            self.Value.append(Poly(self.ringQ, level + 1, self.batch))
+        self.level = level
+
+    def CopyNew(self):
+        out = object.__new__(type(self))
+        Element.__init__(out, self.ringQ, self.Degree(), self.level, self.batch, MetaData_=self.MetaData.copy())
+        for a, b in zip(out.Value, self.Value):
+            a.CopyLvl(self.level, b)
+        return out
+
+
+class Ciphertext(Element):
+    """rlwe.Ciphertext"""
+
+
+class Plaintext(Element):
+    """rlwe.Plaintext: an element of degree 0"""
+
+    def __init__(self, ringQ: Ring, level: int, batch: int = 1, Value=None, MetaData_: MetaData | None = None):
+        super().__init__(ringQ, 0, level, batch, Value=Value, MetaData_=MetaData_)

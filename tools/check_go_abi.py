@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The check of go/hering/*.go that is possible without a Go toolchain: every `C.he_*(...)` call names a function
-declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h, hering_bgv_encoder.h, hering_sampler.h, hering_encryptor.h, hering_keygen.h, hering_rgsw_encryptor.h, hering_multiparty.h, hering_lintrans.h, hering_polyeval.h), passes as many arguments as the declaration has parameters, and -- round 4 --
+declared in include/hering.h (or hering_debug.h, hering_ringswitch.h, hering_ringpack.h, hering_rgsw.h, hering_blindrot.h, hering_bridge.h, hering_bfv.h, hering_ckks_encoder.h, hering_bgv_encoder.h, hering_sampler.h, hering_encryptor.h, hering_keygen.h, hering_rgsw_encryptor.h, hering_multiparty.h, hering_lintrans.h, hering_polyeval.h, hering_ckks_evaluator.h), passes as many arguments as the declaration has parameters, and -- round 4 --
 every argument has the KIND the parameter wants (int / uint64_t / he_handle / he_handle* / uint64_t* / int*), judged from the
 shape of the Go expression (`C.int(..)`, `C.uint64_t(..)`, `x.h`, `&x.h`, `(*C.uint64_t)(unsafe.Pointer(..))`, identifiers whose
 declaration in the file names a Handle or a C pointer type); every `C.HE_*` constant exists in the header's enums.  Also
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_decls():
-    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h", "hering_bgv_encoder.h", "hering_sampler.h", "hering_encryptor.h", "hering_keygen.h", "hering_rgsw_encryptor.h", "hering_multiparty.h", "hering_lintrans.h", "hering_polyeval.h"))
+    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("hering.h", "hering_debug.h", "hering_ringswitch.h", "hering_ringpack.h", "hering_rgsw.h", "hering_blindrot.h", "hering_bridge.h", "hering_bfv.h", "hering_ckks_encoder.h", "hering_bgv_encoder.h", "hering_sampler.h", "hering_encryptor.h", "hering_keygen.h", "hering_rgsw_encryptor.h", "hering_multiparty.h", "hering_lintrans.h", "hering_polyeval.h", "hering_ckks_evaluator.h"))
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls, kinds = {}, {}
     for m in re.finditer(r"\b(?:int|const char \*)\s*(he_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
